@@ -16,7 +16,15 @@ PARAM GROUP PER TENSOR (470 groups).  Metric (BASELINE.json): clips/sec over the
 B * world / step time, B = 32 clips of 3x32x128x128 per GPU, fp32.  Nothing is skipped inside the
 timed region.
 
-Legs (all in the one JSON line):
+A plain run sets up, settles the launch plans, warms up, times --steps steps and prints the JSON line
+(`value`, `ms_per_step`, the in-step `roofline` / `roofline_hbm` read from those steps).  Everything below
+that takes runs or checks of its own -- the other legs, the isolated micro-runs, `cpu_baseline`, `self_check`,
+at world > 1 the cross-rank check, the instrumented collectives and the host floor -- runs only with --full.
+--dump-outputs DIR writes what the last timed step computed (logits, targets, loss, top-1/5, the queues and a
+fixed sample of the model state after the step) as DIR/<name>.npy, so two builds can be compared output for
+output on identical inputs.
+
+Legs (all in the one JSON line; with --full):
   value                    the drop-in: `torch.optim.Adam` resolved to the single-launch subclass by the
                            model.pretrain shim, loss + accuracy through coclr_amd.loss (device scalars)
   value_unmodified_caller  what main_nce.py gets WITHOUT editing a line of it: the shim's Adam (the script
@@ -71,6 +79,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=32, help="clips per GPU")
     ap.add_argument("--moco-k", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the comparison legs, isolated micro-runs, CPU baseline and self-checks (off: "
+                         "only what `value` / `ms_per_step` need)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--net", default="s3d")
     ap.add_argument("--model", default="infonce", choices=["infonce", "coclr"])
     ap.add_argument("--seq-len", type=int, default=32)
@@ -365,6 +378,50 @@ def cpu_baseline_all_cores(args, ncpu, fastest, budget_s=75.0):
                       % (ncpu, why, fastest["cores"], fastest["value"])}
 
 
+DUMP_ARRAY_BYTES = 8 << 20          # per array; at most 11 arrays (CoCLR), whose large ones stay well under 64 MB
+
+
+def last_step_outputs(acc, model):
+    """What the last step handed its caller (logits, targets, loss, top-1/5) and what it left in the model: the
+    queue buffers and `model_state_sample`, the floating-point state (parameters, BatchNorm statistics) in
+    state-dict order, flattened.  Device tensors, detached; dump_outputs() copies them out."""
+    out = {"logits": acc["logits"], "target": acc["target"], "loss": acc["loss"].detach()}
+    for k in ("top1", "top5"):
+        if k in acc:
+            out[k] = acc[k]
+    sd = model.state_dict()
+    rest = []
+    for k, v in sd.items():
+        if k.startswith("queue"):
+            out[k] = v.detach().clone()
+        elif v.is_floating_point():
+            rest.append(v.detach().reshape(-1))
+    out["model_state_sample"] = torch.cat(rest)
+    return out
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 (float64 for integer and boolean data: exact).  An
+    array larger than DUMP_ARRAY_BYTES is replaced by a fixed, seeded sample of its flattened values (the same
+    indices on every run with the same arguments).  Returns {name: shape written}."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    shapes, total = {}, 0
+    for name, t in arrays.items():
+        t = t.detach()
+        dtype = np.float32 if t.is_floating_point() else np.float64
+        cap = DUMP_ARRAY_BYTES // np.dtype(dtype).itemsize
+        if t.numel() > cap:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.cpu().numpy().astype(dtype)
+        np.save(os.path.join(directory, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+        total += a.nbytes
+    assert total <= 64 << 20, "dumped %d bytes" % total
+    return shapes
+
+
 def csrc_sha16():
     """Hash of the kernel sources of THIS build: counter files under profiles/ carry the hash of the build they
     were collected on (tools/traffic_json.py, tools/pmc_step_table.py) and are refused for any other."""
@@ -469,6 +526,9 @@ def main():
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline(args)), flush=True)
         return
+    if not args.full:
+        # a plain run: only what the headline figure needs
+        args.no_cpu_baseline = args.no_extra_legs = args.no_self_check = True
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # a bare `python bench.py --gpus N`: start the N ranks ourselves, one per GPU, through the same launcher
@@ -663,6 +723,7 @@ def measure(args, world):
                 acc["top1"], acc["top5"] = L.calc_topk_accuracy(out, tgt, (1, 5))
             else:
                 loss = nn.functional.cross_entropy(out, tgt)
+            acc["target"] = tgt
         else:
             out, mask = net(blocks[0], blocks[1], vsrc[:blocks[0].shape[0]])
             if native:
@@ -670,7 +731,9 @@ def measure(args, world):
                 acc["top1"], acc["top5"] = L.calc_mask_accuracy(out, mask, (1, 5))
             else:
                 loss = (- torch.log((torch.softmax(out, dim=1) * mask).sum(1))).mean()
+            acc["target"] = mask
         acc["logits"] = out.detach()
+        acc["loss"] = loss
         cur.zero_grad(set_to_none=True)
         loss.backward()
         cur.step()
@@ -727,7 +790,7 @@ def measure(args, world):
         for i in range(npre):
             step(i)
         torch.cuda.synchronize()
-    if world > 1:
+    if world > 1 and args.full:
         check = cross_rank_check(model, acc["logits"], device, world)
         if not check["replicas_identical"] or not check["logits_finite_on_every_rank"]:
             print("bench: cross-rank check FAILED: %s" % json.dumps(check), file=sys.stderr, flush=True)
@@ -743,7 +806,8 @@ def measure(args, world):
         # three steps until joins are deferred again, whatever --warmup says
         for i in range(3 if not dry else 1):
             step(i)
-    if world > 1:
+    instrumented = {}
+    if world > 1 and args.full:
         dog.at("instrumented steps (collectives serialised and timed one by one)")
         _par.TIMINGS = []
         ninst = 2
@@ -762,17 +826,20 @@ def measure(args, world):
         shuffle_ms = sum(a[1] / ninst for name, a in agg.items()
                          if "_shuffle" in name or "all_to_all" in name or "parked" in name
                          or ("all_gather_into_tensor" in name and a[2] > (1 << 20)))
+        instrumented = {
+            "shuffle_exchange_ms_per_step_serialised": round(shuffle_ms, 3), "cross_rank": check, "collectives": coll,
+            "collectives_ms_per_step_serialised": round(sum(a[1] for a in agg.values()) / ninst, 3),
+            "collectives_note": "each call bracketed by device synchronisations in two extra, untimed steps: its cost "
+                                "if nothing overlapped it, INCLUDING the wait for the slowest rank to arrive; the "
+                                "timed steps run them asynchronously"}
+    if world > 1:
         multi = {"rccl_ranks": world if not (dry or args.one_gpu_rehearsal) else 0,
                  "backend": dist.get_backend(),
                  "rung": rung, "rung_name": bench_multi.RUNG_NAMES[rung],
                  "rung_what": bench_multi.RUNG_WHAT[rung], "switches": switches.describe(),
                  "shuffle_mode": _impl._SHUFFLE_MODE, "shuffle_selection": dict(_impl._SHUFFLE_INFO),
-                 "shuffle_exchange_ms_per_step_serialised": round(shuffle_ms, 3),
-                 "split_stages": True, "cross_rank": check, "collectives": coll,
-                 "collectives_ms_per_step_serialised": round(sum(a[1] for a in agg.values()) / ninst, 3),
-                 "collectives_note": "each call bracketed by device synchronisations in two extra, untimed "
-                                     "steps: its cost if nothing overlapped it, INCLUDING the wait for the "
-                                     "slowest rank to arrive; the timed steps run them asynchronously"}
+                 "split_stages": True}
+        multi.update(instrumented)
     def settle(native=True, limit=12):
         """Untimed steps until the launch plans of the structure in force have been recorded (engine.PLAN: four
         interpreted passes after the last signature change, then the recording pass) -- whatever --warmup says,
@@ -809,6 +876,10 @@ def measure(args, world):
     timer.enable(False)
     deferred_per_step = (engine.DEFERRED[0] - deferred0) / max(1, args.steps)
     assert dry or live["opt"]._plan is not None, "the single-launch Adam did not run"
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before any further leg changes the model: what the last timed step left behind
+        dumped = dump_outputs(args.dump_outputs, last_step_outputs(acc, model))
     # a number measured on a broken kernel is worse than no number
     if not (final_loss == final_loss and abs(final_loss) < 1e6):
         raise SystemExit("bench: the loss after the timed steps is %r -- refusing to report a throughput"
@@ -1031,7 +1102,7 @@ def measure(args, world):
                                    "fwd + loss + top-1/5 + bwd + Adam(lr 1e-3, wd 1e-5) over %d "
                                    "single-tensor param groups (main_nce.py:190-200); caller: "
                                    "import-swapped loss + accuracy (INTEGRATION.md section 3), the literally "
-                                   "unmodified caller is value_unmodified_caller"
+                                   "unmodified caller is value_unmodified_caller (--full)"
                                    % (args.net, args.model, K, args.seq_len, args.img_dim, B, world,
                                       len(groups)),
                        "global_batch": B * world, "parallelism": "dp%d" % world,
@@ -1063,6 +1134,8 @@ def measure(args, world):
             "deferred_joins_per_step": round(deferred_per_step, 2),
             "self_check": self_check,
         }
+        if dumped is not None:
+            rec["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if self_check is not None and not self_check["passed"]:
             rec["self_check_failed"] = True
         if check is not None and not (check["replicas_identical"] and check["logits_finite_on_every_rank"]):
@@ -1087,7 +1160,7 @@ def measure(args, world):
                 rec["cpu_baseline_all_cores"] = cpu_baseline_all_cores(args, ncpu, rec["cpu_baseline"])
 
     # ---- N > 1: host floor of the per-stage structure; optional -- a hang here must not cost the record --
-    if world > 1 and args.model == "infonce" and B >= 16 and K % (4 * world) == 0:
+    if world > 1 and args.full and args.model == "infonce" and B >= 16 and K % (4 * world) == 0:
         dog.complete_record, dog.record_complete = rec, True
         dog.at("host floor (4 clips per GPU) -- optional leg", optional=True)
         if bench_multi.FLOOR_HANG:

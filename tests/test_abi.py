@@ -34,24 +34,26 @@ def test_library_exports_every_declared_symbol():
     assert lib.coclr_abi_version() == _lib.ABI_VERSION
 
 
-def test_header_is_plain_c():
+def test_header_is_plain_c(tmp_path):
     """The boundary is a C ABI: the header must compile as C (no torch / C++ types)."""
     src = "#include \"%s\"\nint main(void){coclr_conv_desc d; d.N=1; return (int)sizeof(d)*0;}\n" % HEADER
-    path = "/tmp/coclr_hdr_check.c"
+    path = str(tmp_path / "coclr_hdr_check.c")
     open(path, "w").write(src)
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-c", path, "-o", "/tmp/coclr_hdr_check.o"])
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-c", path, "-o",
+                           str(tmp_path / "coclr_hdr_check.o")])
 
 
-def test_struct_layouts_match_header():
+def test_struct_layouts_match_header(tmp_path):
     """ctypes mirrors vs the C compiler's own layout of the header structs."""
     src = ("#include <stdio.h>\n#include <stddef.h>\n#include \"%s\"\n"
            "int main(void){printf(\"%%zu %%zu %%zu %%zu %%zu %%zu\\n\", sizeof(coclr_conv_desc),"
            "offsetof(coclr_conv_desc, x_nstride), offsetof(coclr_conv_desc, ys_t),"
            "offsetof(coclr_conv_desc, Nx), sizeof(coclr_pool_desc),"
            "offsetof(coclr_pool_desc, x_nstride)); return 0;}\n" % HEADER)
-    open("/tmp/coclr_layout.c", "w").write(src)
-    subprocess.check_call(["gcc", "-std=c99", "/tmp/coclr_layout.c", "-o", "/tmp/coclr_layout"])
-    want = [int(v) for v in subprocess.check_output(["/tmp/coclr_layout"]).split()]
+    src_path, exe = str(tmp_path / "coclr_layout.c"), str(tmp_path / "coclr_layout")
+    open(src_path, "w").write(src)
+    subprocess.check_call(["gcc", "-std=c99", src_path, "-o", exe])
+    want = [int(v) for v in subprocess.check_output([exe]).split()]
     got = [C.sizeof(_lib.ConvDesc), _lib.ConvDesc.x_nstride.offset, _lib.ConvDesc.ys_t.offset,
            _lib.ConvDesc.Nx.offset, C.sizeof(_lib.PoolDesc), _lib.PoolDesc.x_nstride.offset]
     assert got == want, (got, want)

@@ -47,7 +47,7 @@ def test_bench_n2_rehearsal_on_one_gpu(case):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(root, "tests", "bench_rehearse_gpu.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--batch", "8", "--moco-k", "2048"] + extra_args
+           "--batch", "8", "--moco-k", "2048", "--full"] + extra_args
     env = dict(os.environ, COCLR_QUIET="1", **env_extra)
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-4000:]

@@ -113,7 +113,8 @@ def _ddp_worker(rank, world, name, port, q):
     try:
         os.environ["MASTER_ADDR"] = "127.0.0.1"
         os.environ["MASTER_PORT"] = str(port)
-        torch.set_num_threads(max(1, (os.cpu_count() or 2) // world))
+        # the process's thread budget (OMP_NUM_THREADS where set), not the machine's core count
+        torch.set_num_threads(max(1, torch.get_num_threads() // world))
         dist.init_process_group("gloo", rank=rank, world_size=world)
 
         class MP:   # minimal monkeypatch stand-in inside the spawned process
@@ -572,11 +573,12 @@ def test_queues_travel_with_the_first_broadcast_only():
         assert msg == "ok", "rank %d: %s" % (rank, msg)
 
 
-def _bench_dry_run(world, port, extra_env=None, extra_args=(), bare=False):
+def _bench_dry_run(world, port, extra_env=None, extra_args=(), bare=False, full=True):
     """bench.py exactly as the driver launches it (torch.distributed.run, one process per rank) on the host
     with the ATen double; returns (the ONE JSON line rank 0 printed, stderr).
     bare: no launcher -- a plain `python <script> --gpus N`, which has to start the N ranks itself
-    (bench.self_launch)."""
+    (bench.self_launch).
+    full: with --full (the self-checks, the comparison legs, the instrumented collectives)."""
     import json
     import subprocess
     import sys
@@ -585,7 +587,7 @@ def _bench_dry_run(world, port, extra_env=None, extra_args=(), bare=False):
                                 "--master-addr", "127.0.0.1", "--master-port", str(port)]
     cmd = [sys.executable] + launcher + [
         os.path.join(root, "tests", "bench_dryrun.py"), "--gpus", str(world), "--steps", "2",
-        "--warmup", "1"] + list(extra_args)
+        "--warmup", "1"] + (["--full"] if full else []) + list(extra_args)
     env = dict(os.environ, OMP_NUM_THREADS="1", COCLR_QUIET="1", **(extra_env or {}))
     if bare:
         for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
@@ -656,6 +658,39 @@ def test_bench_launch_contract_dry_run(world):
         assert mg["rung"] == 0 and len(sc["trials"]) == 1
         hung = rec["optional_leg_hung"]
         assert "host floor" in hung["phase"] and "host_floor_ms_per_step" not in mg
+
+
+@pytest.mark.parametrize("model", ["infonce", "coclr"])
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path, model):
+    """Without --full the run times its steps and nothing else: no self-check, no comparison legs, no CPU
+    baseline, no isolated micro-runs.  --dump-outputs writes what the last timed step computed, float32 / float64,
+    and two runs with the same arguments write the same arrays (identical inputs)."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        rec, _ = _bench_dry_run(1, 29781 + 2 * i + (model == "coclr"), None,
+                                ("--model", model, "--dump-outputs", str(d)), full=False)
+        assert rec["n_gpus"] == 1 and rec["steps"] == 2 and rec["warmup"] == 1 and rec["value"] > 0
+        assert abs(rec["value"] - 2 * 2 / (rec["ms_per_step"] * 2e-3)) <= 0.02 * rec["value"]
+        assert rec["self_check"] is None and rec["roofline_nce"] is None and rec["host_floor_ms_per_step"] is None
+        for leg in ("value_unmodified_caller", "value_split_stages", "value_caller_optimizer", "value_k16384",
+                    "cpu_baseline", "cpu_baseline_all_cores", "multi_gpu"):
+            assert leg not in rec, leg
+        files = sorted(os.listdir(d))
+        assert sorted(rec["dump_outputs"]["arrays"]) == sorted(f[:-4] for f in files)
+        want = {"logits", "target", "loss", "queue", "queue_ptr", "model_state_sample", "top1", "top5"}
+        if model == "coclr":
+            want |= {"queue_second", "queue_label", "queue_vname"}
+        assert want <= set(rec["dump_outputs"]["arrays"]), rec["dump_outputs"]
+        arrays = {f: np.load(str(d / f)) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["logits.npy"].shape[0] == 2 and np.isfinite(arrays["logits.npy"]).all()
+        assert abs(float(arrays["loss.npy"]) - rec["config"]["final_loss"]) < 1e-3
+        dumps.append(arrays)
+    for f, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][f]), f
 
 
 def test_bench_dry_run_coclr_self_check():

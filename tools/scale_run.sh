@@ -17,11 +17,11 @@ run() {   # run <n> <tag> [env...]
   local n=$1 tag=$2; shift 2
   local port=$((29600 + RANDOM % 300))
   if [ "$n" = 1 ]; then
-    env "$@" python bench.py --gpus 1 --steps "$STEPS" --warmup "$WARM" --no-extra-legs \
+    env "$@" python bench.py --gpus 1 --steps "$STEPS" --warmup "$WARM" --full --no-extra-legs \
       > "$OUT/$tag.log" 2> "$OUT/$tag.err"
   else
     env "$@" python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 \
-      --master-port "$port" bench.py --gpus "$n" --steps "$STEPS" --warmup "$WARM" --no-extra-legs \
+      --master-port "$port" bench.py --gpus "$n" --steps "$STEPS" --warmup "$WARM" --full --no-extra-legs \
       > "$OUT/$tag.log" 2> "$OUT/$tag.err"
   fi
   echo "== $tag (rc=$?)"; tail -1 "$OUT/$tag.log" | cut -c1-400
