@@ -168,7 +168,6 @@ class SepInception(_Emitter):
     def _emit(self, run, x):
         N, _, T, H, W = x.shape
         odim = (T, H, W)          # every branch preserves the extent
-        run.lanes_on = engine.lanes_for(run, odim)
         block = run.empty(N, self.out_channels, *odim)
         dst, c0 = [], 0
         for width in self._widths:
@@ -179,7 +178,7 @@ class SepInception(_Emitter):
         head_units = [(b0.conv, b0.bn, None if self.gating else dst[0]), (b1a.conv, b1a.bn, None),
                       (b2a.conv, b2a.bn, None)]
         tails = (None, self.branch1[1], self.branch2[1])
-        if engine.PAIR_UNITS and not self.gating and not run.lanes_on:
+        if engine.PAIR_UNITS and not self.gating:
             # Sibling units in lockstep, one launch per step of the pair (engine.drive_pair):
             #   * the fused heads and the pool branch's 1x1x1 convolution (both pointwise, both on the block's
             #     map: x and the pooled x), then their four BatchNorm units;
@@ -194,17 +193,13 @@ class SepInception(_Emitter):
         heads = engine.pointwise_group(run, x, head_units)
         if self.gating:
             getattr(self, "gating_b0")._emit(run, heads[0], out=dst[0])
-        # the separable tails of branch 1 / 2 and the pool branch are independent of each other:
-        # one lane (HIP stream) each, joined before the block output is consumed
         for i in (1, 2, 3):
-            with run.lane(i):
-                if i == 3:
-                    y = self.branch3._emit(run, x, out=None if self.gating else dst[3])
-                else:
-                    y = tails[i]._emit(run, heads[i], out=None if self.gating else dst[i])
-                if self.gating:
-                    getattr(self, "gating_b%d" % i)._emit(run, y, out=dst[i])
-        run.join_lanes()
+            if i == 3:
+                y = self.branch3._emit(run, x, out=None if self.gating else dst[3])
+            else:
+                y = tails[i]._emit(run, heads[i], out=None if self.gating else dst[i])
+            if self.gating:
+                getattr(self, "gating_b%d" % i)._emit(run, y, out=dst[i])
         return engine.Val(block)
 
 
@@ -282,18 +277,6 @@ class S3D(_Emitter):
                 grp.__dict__["_coclr_defer_join"] = True
         return groups
 
-    def _late_split(self):
-        """(everything up to MaxPool_4a, Mixed_4b..Mixed_5c): the second part is the launch-bound one
-        that engine.GRAPH_LATE replays from a hipGraph."""
-        pair = self.__dict__.get("_coclr_late_split")
-        if pair is None:
-            b4 = list(self.block4)
-            front = _Group(list(self.block1) + list(self.block2) + list(self.block3) + b4[:1])
-            late = _Group(b4[1:] + list(self.block5))
-            late.__dict__["_coclr_graph_late"] = True
-            pair = self.__dict__["_coclr_late_split"] = (front, late)
-        return pair
-
     def forward(self, x, n_index=None):
         """One autograd node per stage, like the reference's forward (backbone/s3dg.py:211-217).  With
         gradients enabled this lets the gradients of the late stages -- 216 of the 231 backbone tensors
@@ -301,11 +284,6 @@ class S3D(_Emitter):
         backward: its bucket all-reduce then overlaps the weight-gradient stream instead of forming a
         tail after the whole backward."""
         if not (torch.is_grad_enabled() and _split_stages()):
-            if engine.GRAPH_LATE and torch.is_grad_enabled():
-                front, late = self._late_split()
-                x = engine.run_module(front, x, n_index=n_index) if n_index is not None \
-                    else engine.run_module(front, x)
-                return engine.run_module(late, x)
             return engine.run_module(self, x, n_index=n_index) if n_index is not None \
                 else engine.run_module(self, x)
         groups = self._stage_groups()

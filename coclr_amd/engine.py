@@ -14,7 +14,7 @@ What that buys on MI355X:
     streaming pass, its backward one reduce + one apply pass
   * data gradients of fan-out nodes accumulate in place (accumulate flag on the
     kernel) instead of separate add kernels
-  * the launch sequence is static per input shape (hipGraph-capturable)
+  * the launch sequence is static per input shape: launch plans re-issue it (coclr_amd/plan.py)
 """
 import os
 import weakref
@@ -30,28 +30,6 @@ _PACK_STORE = {}      # id(weight) -> (weakref, {use -> packed buffer})
 # of ~80 five-microsecond launches threaded between the convolutions.
 BATCH_PACK = os.environ.get("COCLR_BATCH_PACK", "1") != "0"
 WGRAD_STREAM = os.environ.get("COCLR_WGRAD_STREAM", "1") != "0"
-# Inception branches on their own streams: correct (GPU tier passes with it on) but SLOWER on
-# MI355X -- 47.3 vs 43.3 ms/step: ~160 fork/join points per step cost more in cross-queue
-# event latency than the overlap of the small branch kernels wins.  Off unless asked for.
-# COCLR_LANES: "1" everywhere; "small" only in blocks on maps of 8x8 and below (stages 4 and 5, whose
-# 10-40 us kernels leave most of the chip idle); "graph" only while the pass is being captured into a
-# hipGraph (the forks become graph branches, no host-issued cross-queue events); "small+graph" both.
-LANES_MODE = os.environ.get("COCLR_LANES", "0")
-LANES = LANES_MODE != "0"
-
-
-def lanes_for(run, dims):
-    """Should the inception block on a map of extent `dims` run its branches on lane streams?"""
-    if not LANES or run.device.type != "cuda":
-        return False
-    if LANES_MODE == "1":
-        return True
-    ok = True
-    if "small" in LANES_MODE:
-        ok = ok and dims[1] <= 8
-    if "graph" in LANES_MODE:
-        ok = ok and torch.cuda.is_current_stream_capturing()
-    return ok
 # Test instrumentation (tests/_decisions.py): when set, called as DECISION_PROBE("relu", bn, mask) for
 # every differentiated BatchNorm+ReLU unit (mask = the unit's ReLU decisions, exactly the predicate the
 # kernels evaluate: fma(y, scale, shift) (+ residual) > 0) and DECISION_PROBE("pool", None, argmax) for
@@ -97,8 +75,7 @@ def side_stream_of(device):
 def side_events_for(params):
     """Events on the weight-gradient stream that the gradients of `params` are complete behind (duplicates
     removed).  Parameters without an entry were not written by a node that deferred its join -- the
-    projection head (main stream), a node that joined, a graph replay (joins inside the graph): the main
-    stream orders them."""
+    projection head (main stream), a node that joined: the main stream orders them."""
     evs = []
     for p in params:
         ev = _SIDE_EVENTS.pop(id(p), None)
@@ -124,7 +101,6 @@ def _end_of_backward(device):
 _SIDE_PRIORITY = int(os.environ.get("COCLR_WGRAD_PRIORITY", "-1"))
 # weight-gradient closures per release window (Run.side_stream); 0 = hold everything until join_side
 _SIDE_WINDOW = int(os.environ.get("COCLR_SIDE_WINDOW", "12"))
-_LANES = {}
 
 
 # Parameter -> the view of DistributedDataParallel's gradient bucket that holds its gradient
@@ -177,36 +153,6 @@ def grad_out_for(p):
             _HEAD_SLOTS_OUT.add(id(p))
             return v.view_as(v)
     return torch.empty_like(p)
-
-
-class _Lane:
-    def __init__(self, run, idx):
-        self.run, self.idx, self.ctx = run, idx, None
-
-    def __enter__(self):
-        run = self.run
-        if run.cur_lane is not None or run._in_lane:
-            raise RuntimeError("coclr_amd: lanes do not nest")
-        run._in_lane = True
-        if run.lanes_on:
-            st, parent = run._lane_stream(self.idx)
-            st.wait_stream(parent)
-            run._parent = parent
-            run._open.append(st)
-            self.ctx = torch.cuda.stream(st)
-            self.ctx.__enter__()
-            run.cur_lane = self.idx          # closures recorded inside replay on the lane's stream
-        else:
-            run.cur_lane = None
-        self.entered = True
-        return self
-
-    def __exit__(self, *exc):
-        self.run.cur_lane = None
-        self.run._in_lane = False
-        if self.ctx is not None:
-            self.ctx.__exit__(*exc)
-        return False
 
 
 class PackPlan:
@@ -263,17 +209,10 @@ class PackPlan:
         return True
 
 
-# While a differentiated pass is being captured into a hipGraph (GRAPH_QUERY below) the capture stream
-# stands for the stream the graph will be replayed on: packed-operand buffers and re-layout plans
-# recorded by the eager passes on that stream are the ones the captured kernels use.
-_STREAM_ALIAS = {}
-
-
 def _stream_key(device):
     if device.type != "cuda":
         return 0
-    st = torch.cuda.current_stream(device).cuda_stream
-    return _STREAM_ALIAS.get(st, st)
+    return torch.cuda.current_stream(device).cuda_stream
 
 
 def _plan_for(module, save, device):
@@ -337,7 +276,7 @@ class Run:
         self.device = device
         self.save = save
         self.need_input_grad = need_input_grad
-        # (closure, lane) in emission order.  Closures take the run as their ARGUMENT and must not
+        # closures in emission order.  Closures take the run as their ARGUMENT and must not
         # capture it: run -> tape -> closure -> run would be a cycle that only the cyclic gc frees,
         # one backbone stage per collection (each stage's tape holds the previous stage's output,
         # whose grad_fn owns that stage's run) -- GBs of activations parked behind gc's schedule.
@@ -347,11 +286,6 @@ class Run:
         self.bn_src = {}       # id(unit output) -> (y, scale, shift, mean, invstd, relu) of a training unit
         self.bn_parts = {}     # id(unit output) -> [(partial sums, slots per channel)] left by that writer
         self.grad_writes = {}  # id(activation) -> writers of its gradient so far (grad_target)
-        self.cur_lane = None
-        self.lanes_on = False  # set per inception block (lanes_for)
-        self._in_lane = False
-        self._parent = None
-        self._open = []
         self.grads = {}        # id(base tensor) -> grad tensor
         self.param_grads = {}  # id(param) -> grad tensor
         self._slots_out = set()   # parameters whose bucket view has been handed out in this run
@@ -419,61 +353,16 @@ class Run:
             _plan.active().taint("a parameter used twice in one pass (its gradients are added by an ATen launch)")
         self.param_grads[id(p)] = g if old is None else old.add_(g)
 
-    # -- lanes: independent sub-graphs (inception branches) on their own streams ------
-    def record(self, fn):
-        self.tape.append((fn, self.cur_lane))
-
-    def _lane_stream(self, lane):
-        parent = torch.cuda.current_stream(self.device) if self.cur_lane is None else self._parent
-        key = (self.device, parent.cuda_stream, lane)
-        st = _LANES.get(key)
-        if st is None:
-            st = _LANES[key] = torch.cuda.Stream(device=self.device)
-        return st, parent
-
-    def lane(self, idx):
-        """Context: kernels emitted inside run on lane stream `idx`, ordered after everything
-        queued on the parent stream so far.  The caller closes the region with join_lanes()."""
-        return _Lane(self, idx)
-
-    def join_lanes(self):
-        if self._open:
-            cur = torch.cuda.current_stream(self.device)
-            for st in self._open:
-                cur.wait_stream(st)
-            self._open = []
-
     # -- backward ----------------------------------------------------------------
+    def record(self, fn):
+        self.tape.append(fn)
+
     def backward(self, dout, defer_join=False):
         """defer_join: this node may leave the weight-gradient stream un-joined (see defer_side)."""
         out = self.out
         self.grads[id(out.base)] = dout.contiguous()
-        # closures run in reverse emission order; closures of different lanes between two
-        # main-stream closures are independent of each other, so each lane replays on its own
-        # stream (entered after the main stream's work so far) and the next main-stream
-        # closure joins them
-        started = {}
-        while self.tape:
-            fn, lane = self.tape.pop()
-            if lane is None:
-                if started:
-                    cur = torch.cuda.current_stream(self.device)
-                    for st in started.values():
-                        cur.wait_stream(st)
-                    started = {}
-                _run_closure(fn, self)
-            else:
-                st = started.get(lane)
-                if st is None:
-                    st, parent = self._lane_stream(lane)
-                    st.wait_stream(parent)
-                    started[lane] = st
-                with torch.cuda.stream(st):
-                    _run_closure(fn, self)
-        if started:
-            cur = torch.cuda.current_stream(self.device)
-            for st in started.values():
-                cur.wait_stream(st)
+        while self.tape:                 # reverse emission order
+            _run_closure(self.tape.pop(), self)
         if defer_join and self._side_used and self.param_grads and \
                 all(k in self._slots_out and k in _SLOTS_VERIFIED for k in self.param_grads):
             self.defer_side()
@@ -586,15 +475,7 @@ class Run:
             if len(_PACK_STORE) > 4096:
                 for k_ in [k_ for k_, v_ in _PACK_STORE.items() if v_[0]() is None]:
                     del _PACK_STORE[k_]
-        if self.device.type != "cuda":
-            stream = 0
-        elif self.cur_lane is not None and self._parent is not None:
-            # inside a lane: the buffers (and the batch re-layout that fills them) belong to the parent
-            # stream, which the lane stream waited for when it forked
-            stream = _STREAM_ALIAS.get(self._parent.cuda_stream, self._parent.cuda_stream)
-        else:
-            stream = _stream_key(self.device)
-        key = (tag, n, stream, self.device)
+        key = (tag, n, _stream_key(self.device), self.device)
         buf = store[1].get(key)
         if buf is None:
             buf = (torch.zeros if zero else torch.empty)(n, dtype=torch.float32, device=self.device)
@@ -835,14 +716,9 @@ def drive_pair(run, ga, gb):
             i = 0 if not done[0] else 1
             advance(i, False, _exec(reqs[i]))
     ta, tb = tapes
-    for i in range(max(len(ta), len(tb))):
-        if i < len(ta) and i < len(tb) and ta[i][1] is None and tb[i][1] is None:
-            main_tape.append((_PairedBackward(ta[i][0], tb[i][0]), None))
-        else:
-            if i < len(ta):
-                main_tape.append(ta[i])
-            if i < len(tb):
-                main_tape.append(tb[i])
+    n = min(len(ta), len(tb))
+    main_tape.extend(_PairedBackward(fa, fb) for fa, fb in zip(ta, tb))
+    main_tape.extend(ta[n:] + tb[n:])      # the longer tape's tail (only one of the two is non-empty)
     return vals[0], vals[1]
 
 
@@ -1325,222 +1201,25 @@ class EngineFn(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------------
-# hipGraph replay of a DIFFERENTIATED pass (the query encoder's forward and backward)
-# ---------------------------------------------------------------------------------
-# The launch sequence of a module pass is static per input shape: ~330 launches forward, ~600
-# backward, ~18 ms of host work per training step between them (bench.py `host_floor_ms_per_step`).
-# With COCLR_GRAPH_QUERY=1 a module that has been run eagerly a few times with an unchanged signature is
-# captured -- forward and, at the first backward after that, its tape -- into two hipGraphs that share
-# one private memory pool, and every later step is: copy the input into the graph's static buffer,
-# replay, hand autograd fresh aliases of the static outputs / gradients.  Gradients that live in
-# DistributedDataParallel's buckets (grad_out) are written there by the captured kernels as well.
-# Same kernels, same order, same operands as the eager pass: results are bit-identical
-# (tests/test_gpu_model.py::test_graphed_query_encoder_matches_eager).
-# COCLR_GRAPH_QUERY=late captures only modules flagged `_coclr_graph_late` -- the 8x8x8 / 4x4x4 stages
-# of S3D (Mixed_4b..5c: 60 % of the step's launches, 10-40 us kernels that the host cannot feed fast
-# enough at the START of backward, when it has no lead) -- and leaves the large early stages eager.
-_GRAPH_MODE = os.environ.get("COCLR_GRAPH_QUERY", "0")
-GRAPH_QUERY = _GRAPH_MODE == "1"
-GRAPH_LATE = _GRAPH_MODE == "late"
-_GRAPH_WARMUP = 2           # eager passes with an unchanged signature before capturing
-_STATIC_PTRS = set()        # addresses of static graph outputs (a later stage takes them in place)
-_CAPTURE_STREAMS = {}
-
-
-class _GraphEntry:
-    __slots__ = ("sig", "seen", "fwd", "bwd", "pool", "x", "out", "dout", "grads", "dx", "run", "xin",
-                 "version", "params", "need_dx", "disabled", "static_in", "static_dout")
-
-    def __init__(self, sig):
-        self.sig, self.seen = sig, 0
-        self.fwd = self.bwd = self.pool = None
-        self.version = 0
-        self.disabled = False
-        self.grads = self.dx = self.run = self.xin = self.x = self.out = self.dout = None
-        self.static_in = self.static_dout = None
-        self.params, self.need_dx = (), False
-
-
-def _graph_signature(module, x, params, kwargs):
-    bns = module.__dict__.get("_coclr_bn_list")
-    if bns is None:
-        bns = module.__dict__["_coclr_bn_list"] = [
-            m for m in module.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
-    slots = tuple(_GRAD_SLOTS[id(p)][1].data_ptr() if id(p) in _GRAD_SLOTS else 0 for p in params)
-    return (tuple(x.shape), x.dtype, x.device, bool(x.requires_grad), tuple(sorted(kwargs)),
-            tuple(p.data_ptr() for p in params), tuple(bool(p.requires_grad) for p in params), slots,
-            tuple((m.training, m.momentum, m.eps, m.running_mean.data_ptr()) for m in bns))
-
-
-def _capture_stream(device):
-    st = _CAPTURE_STREAMS.get(device)
-    if st is None:
-        st = _CAPTURE_STREAMS[device] = torch.cuda.Stream(device=device)
-    return st
-
-
-def _copy_rows(src, dst):
-    """dst (dense) <- src (dense rows, possibly strided along dim 0) as one kernel."""
-    ident = _IDENT.get((src.device, src.shape[0]))
-    if ident is None:
-        ident = _IDENT[(src.device, src.shape[0])] = torch.arange(src.shape[0], device=src.device)
-    ops.gather_rows(src, ident, dst)
-
-
-_IDENT = {}
-
-
-def _graph_entry(module, x, params, kwargs):
-    """The captured entry to replay for this call, or None (run eagerly)."""
-    if kwargs or not x.is_cuda or x.dim() != 5 or torch.cuda.is_current_stream_capturing():
-        return None
-    store = module.__dict__.get("_coclr_graph_entries")
-    if store is None:
-        store = module.__dict__["_coclr_graph_entries"] = {}
-    sig = _graph_signature(module, x, params, kwargs)
-    key = (tuple(x.shape), bool(x.requires_grad))
-    ent = store.get(key)
-    if ent is None or ent.sig != sig:
-        if ent is not None:                      # its static buffers go away with it
-            for t in (ent.out, ent.dx):
-                if t is not None:
-                    _STATIC_PTRS.discard(t.data_ptr())
-        ent = store[key] = _GraphEntry(sig)      # new shape / moved storage / flags changed: start over
-    if ent.disabled:
-        return None
-    ent.seen += 1
-    if ent.seen <= _GRAPH_WARMUP:
-        return None
-    if ent.fwd is None:
-        try:
-            _capture_forward(module, x, params, ent)
-        except (RuntimeError, ValueError) as e:
-            # e.g. an input whose rows are not dense: this (module, shape) stays on the eager path
-            ent.disabled = True
-            import warnings
-            warnings.warn("coclr_amd: hipGraph capture of %s failed (%s); running it eagerly"
-                          % (type(module).__name__, e))
-            return None
-    return ent
-
-
-def _capture_forward(module, x, params, ent):
-    dev = x.device
-    need_dx = bool(x.requires_grad)
-    cap = _capture_stream(dev)
-    cur = torch.cuda.current_stream(dev)
-    # the input of a later stage is the previous stage's static output: same address every step
-    if _dense5(x) and x.data_ptr() in _STATIC_PTRS:
-        static_x, ent.static_in = x.detach(), True
-    else:
-        static_x, ent.static_in = torch.empty(x.shape, dtype=x.dtype, device=dev), None
-        _copy_rows(x.detach(), static_x)
-    cur.synchronize()
-    pool = torch.cuda.graph_pool_handle()
-    g = torch.cuda.CUDAGraph()
-    _STREAM_ALIAS[cap.cuda_stream] = cur.cuda_stream
-    try:
-        with torch.cuda.graph(g, pool=pool, stream=cap, capture_error_mode="thread_local"):
-            run = Run(dev, save=True, need_input_grad=need_dx)
-            xin = Val(static_x)
-            if not need_dx:
-                run.no_grad_bases.add(id(xin.base))
-            run.begin(module)
-            run.out = module._emit(run, xin)
-            out = run.out.view()
-    finally:
-        _STREAM_ALIAS.pop(cap.cuda_stream, None)
-    ent.fwd, ent.pool, ent.x, ent.out, ent.run, ent.xin = g, pool, static_x, out, run, xin
-    ent.params, ent.need_dx = params, need_dx
-    ent.bwd = None
-    _STATIC_PTRS.add(out.data_ptr())
-
-
-class GraphedFn(torch.autograd.Function):
-    """EngineFn whose forward and backward are hipGraph replays (see GRAPH_QUERY)."""
-
-    @staticmethod
-    def forward(ctx, ent, x, *params):
-        new_pass(x.device)
-        if ent.static_in is None or x.data_ptr() != ent.x.data_ptr():
-            _copy_rows(x.detach(), ent.x)
-        ent.fwd.replay()
-        ent.version += 1
-        ctx.ent, ctx.version = ent, ent.version
-        return ent.out.detach()
-
-    @staticmethod
-    def backward(ctx, dout):
-        ent = ctx.ent
-        if ctx.version != ent.version:
-            raise RuntimeError(
-                "coclr_amd: backward through a graph-replayed encoder pass whose activations a later "
-                "forward has overwritten (two forwards, then two backwards); set COCLR_GRAPH_QUERY=0")
-        ctx.ent = None
-        params = ent.params
-        # A caller that accumulates gradients still holds last step's `.grad`, which aliases the static
-        # buffer this replay overwrites: give it its own memory first (rare: zero_grad() sets None)
-        if ent.grads is not None:
-            for p, g in zip(params, ent.grads):
-                if g is not None and p.grad is not None and p.grad.data_ptr() == g.data_ptr():
-                    p.grad = p.grad.clone()
-        if ent.bwd is None:
-            _capture_backward(ent, dout)
-        elif ent.static_dout is None or dout.data_ptr() != ent.dout.data_ptr():
-            ent.dout.copy_(dout)
-        ent.bwd.replay()
-        grads = tuple(None if g is None else g.view_as(g) for g in ent.grads)
-        dx = ent.dx.view_as(ent.dx) if ent.dx is not None else None
-        return (None, dx) + grads
-
-
-def _capture_backward(ent, dout):
-    dev = dout.device
-    cap = _capture_stream(dev)
-    cur = torch.cuda.current_stream(dev)
-    # the gradient of an earlier stage's output is a later stage's static dx: same address every step
-    if dout.is_contiguous() and dout.data_ptr() in _STATIC_PTRS:
-        static_dout, ent.static_dout = dout.detach(), True
-    else:
-        static_dout, ent.static_dout = torch.empty(ent.out.shape, dtype=dout.dtype, device=dev), None
-        static_dout.copy_(dout)
-    cur.synchronize()
-    run = ent.run
-    g = torch.cuda.CUDAGraph()
-    _STREAM_ALIAS[cap.cuda_stream] = cur.cuda_stream
-    try:
-        with torch.cuda.graph(g, pool=ent.pool, stream=cap, capture_error_mode="thread_local"):
-            run.backward(static_dout)
-            dx = run.grads.pop(id(ent.xin.base), None) if ent.need_dx else None
-            grads = tuple(run.param_grads.pop(id(p), None) if p.requires_grad else None
-                          for p in ent.params)
-            run.param_grads.clear()
-            run.grads.clear()
-    finally:
-        _STREAM_ALIAS.pop(cap.cuda_stream, None)
-    ent.bwd, ent.dout, ent.grads, ent.dx = g, static_dout, grads, dx
-    ent.run = None           # the tape has been consumed; its tensors live on in the graphs' pool
-    if dx is not None:
-        _STATIC_PTRS.add(dx.data_ptr())
-
-
-# ---------------------------------------------------------------------------------
 # Launch-plan replay of a DIFFERENTIATED pass (coclr_amd/plan.py)
 # ---------------------------------------------------------------------------------
-# Same idea as the hipGraph replay above -- the launch sequence of a node is static per signature -- without
-# its device-side cost: the recorded C-ABI calls are re-issued as ordinary launches on the ordinary streams.
+# The launch sequence of a node is static per signature: its recorded C-ABI calls are re-issued as ordinary
+# launches on the ordinary streams, without the host work of the interpreted pass in between.
 # After _PLAN_WARMUP interpreted passes with an unchanged signature the node's forward is run once more with
 # its allocations in a private torch.cuda.MemPool while every call it makes is logged; its tape is kept (the
 # tensors it references now have addresses nobody else is given) and logged the same way at the first backward.
 # From then on a step of the node is: patch the two places that hold the input's address if the caller's
 # tensor moved, re-issue the forward log; copy dout into its recorded place, re-issue the backward log, hand
 # autograd fresh aliases of the recorded gradient tensors (DDP bucket views where DDP has them).
-# COCLR_PLAN=0 switches it off (the interpreted pass); hipGraph replay (COCLR_GRAPH_QUERY) takes precedence.
+# COCLR_PLAN=0 switches it off (the interpreted pass).
 PLAN = os.environ.get("COCLR_PLAN", "1") != "0" and hasattr(torch.cuda, "MemPool") and \
     hasattr(torch.cuda, "use_mem_pool")        # (a torch without private pools: every pass stays interpreted)
 _PLAN_WARMUP = 4            # interpreted passes first: one-time allocations, DDP's bucket rebuild, slot verification
 _PLAN_MAX_SHAPES = 3        # input shapes per node that get a plan (and a pool of activations) of their own
 PLAN_STATS = {"recorded": 0, "replayed": 0, "disabled": []}
+# addresses of recorded outputs and input gradients, fixed for the life of their plan: when the node one stage
+# later hands its recorded dx back as this node's dout, the backward log reads it in place instead of a copy
+_STATIC_PTRS = set()
 
 
 class _PlanEntry:
@@ -1563,8 +1242,15 @@ class _PlanEntry:
 
 
 def _plan_signature(module, x, params):
-    return _graph_signature(module, x, params, {}) + (
-        tuple(x.stride()), WGRAD_STREAM, DEFER_JOIN, PAIR_UNITS, FUSE_BN_REDUCE, LAZY_APPLY, POOLED_BACKWARD,
+    bns = module.__dict__.get("_coclr_bn_list")
+    if bns is None:
+        bns = module.__dict__["_coclr_bn_list"] = [
+            m for m in module.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
+    slots = tuple(_GRAD_SLOTS[id(p)][1].data_ptr() if id(p) in _GRAD_SLOTS else 0 for p in params)
+    return (tuple(x.shape), x.dtype, x.device, bool(x.requires_grad),
+            tuple(p.data_ptr() for p in params), tuple(bool(p.requires_grad) for p in params), slots,
+            tuple((m.training, m.momentum, m.eps, m.running_mean.data_ptr()) for m in bns),
+            tuple(x.stride()), WGRAD_STREAM, DEFER_JOIN, PAIR_UNITS, FUSE_BN_REDUCE, LAZY_APPLY, POOLED_BACKWARD,
         BATCH_PACK, tuple(id(p) in _SLOTS_VERIFIED for p in params))
 
 
@@ -1576,7 +1262,7 @@ def _plan_drop(ent):
 
 def _plan_entry(module, x, params, kwargs):
     """The node's plan entry when this call can go through it (recording or replaying), else None."""
-    if kwargs or not x.is_cuda or x.dim() != 5 or not _dense5(x) or LANES or DECISION_PROBE is not None or \
+    if kwargs or not x.is_cuda or x.dim() != 5 or not _dense5(x) or DECISION_PROBE is not None or \
             torch.cuda.is_current_stream_capturing():
         return None
     store = module.__dict__.get("_coclr_plan_entries")
@@ -1733,11 +1419,7 @@ def run_module(module, x, **kwargs):
     if params is None:
         params = module.__dict__["_coclr_params"] = list(module.parameters())
     if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
-        if GRAPH_QUERY or (GRAPH_LATE and module.__dict__.get("_coclr_graph_late")):
-            ent = _graph_entry(module, x, params, kwargs)
-            if ent is not None:
-                return GraphedFn.apply(ent, x, *params)
-        elif PLAN:
+        if PLAN:
             ent = _plan_entry(module, x, params, kwargs)
             if ent is not None:
                 return PlanFn.apply(ent, module, x, *params)
