@@ -12,13 +12,31 @@
 //   p  = p - (lr/(1-b1^t)) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
 // with the step counters t kept on the device (one float per group, torch's fused/capturable
 // state format), so a step never touches the host.
+//
+// The classifier's fine-tuning loop (eval/main_classifier.py:159, --optim sgd) builds one param group
+// per tensor too and calls torch.optim.SGD(momentum=0.9).step().  coclr_sgd_step is that step as one
+// pointer-table launch (reads p, g, buf and writes p, buf once = 20 B per parameter; no step
+// counter).  Arithmetic follows torch.optim.SGD's foreach path (_multi_tensor_sgd, the CUDA/ROCm
+// default), one ATen elementwise op per line.  ATen's ROCm build contracts `a + alpha*b` (every add
+// with an alpha) into one fused multiply-add, so those lines are fmaf here; the multiply of
+// _foreach_mul_ is rounded on its own:
+//   g   = maximize ? -g : g                                      (_foreach_neg: exact)
+//   g   = fma(wd, p, g)                              if wd != 0  (_foreach_add, alpha=wd)
+//   buf = first ? g : fma(1-dampening, g, buf*mom)   if mom != 0 (clone / _foreach_mul_ then
+//                                                                 _foreach_add_, alpha=1-dampening)
+//   g   = nesterov ? fma(mom, buf, g) : buf          if mom != 0 (_foreach_add_, alpha=mom)
+//   p   = fma(-lr, g, p)                                         (_foreach_add_, alpha=-lr)
+// Every scalar is the double torch holds (the Python float, 1-dampening formed in double) rounded
+// once to fp32, as ATen rounds a Scalar alpha to the fp32 op-math type.  "first" is torch's
+// momentum_buffer-is-None step of that parameter: the buffer is written, never read.
 #include "common.h"
 #include "../../include/coclr_hip.h"
 #include <math.h>
 
 // Every operation below is rounded on its own, as the separate ATen kernels of torch.optim.Adam and
 // of the reference's momentum update are: no fused multiply-add contraction in this file (HIP's
-// default is -ffp-contract=fast, and __fmul_rn / __fadd_rn are plain operators on AMD).
+// default is -ffp-contract=fast, and __fmul_rn / __fadd_rn are plain operators on AMD).  The SGD
+// kernel's fused multiply-adds are explicit (__builtin_fmaf), where ATen's own kernels have them.
 #pragma clang fp contract(off)
 
 namespace {
@@ -118,6 +136,56 @@ adam_multi_kernel(const int64_t* __restrict__ table, const double* __restrict__ 
   }
 }
 
+// table row: int64[8] = {p, g, momentum_buffer (0: momentum == 0), count, slot, first, -, -}
+// hyper row: double[8] = {lr, momentum, dampening, weight_decay, nesterov, maximize, -, -}
+__global__ void __launch_bounds__(256)
+sgd_multi_kernel(const int64_t* __restrict__ table, const double* __restrict__ hyper) {
+  const int64_t* ent = table + 8 * (long)blockIdx.x;
+  float* p = reinterpret_cast<float*>(ent[0]);
+  const float* g = reinterpret_cast<const float*>(ent[1]);
+  float* buf = reinterpret_cast<float*>(ent[2]);
+  const int cnt = (int)ent[3];
+  const double* h = hyper + 8 * ent[4];
+  const bool first = ent[5] != 0;
+  const float neg_lr = (float)(-h[0]), mom = (float)h[1], damp_w = (float)(1.0 - h[2]);
+  const float wd = (float)h[3];
+  const bool decay = h[3] != 0.0, nesterov = h[4] != 0.0, maximize = h[5] != 0.0;
+
+  auto update = [&](float pv, float gv, float& bv) -> float {
+    if (maximize) gv = -gv;
+    if (decay) gv = __builtin_fmaf(wd, pv, gv);
+    if (buf) {
+      bv = first ? gv : __builtin_fmaf(damp_w, gv, __fmul_rn(bv, mom));
+      gv = nesterov ? __builtin_fmaf(mom, bv, gv) : bv;
+    }
+    return __builtin_fmaf(neg_lr, gv, pv);
+  };
+
+  const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) == 0);
+  int done = 0;
+  if (vec) {
+    const int n4 = cnt >> 2;
+    for (int i = threadIdx.x; i < n4; i += 256) {
+      float4 pv = reinterpret_cast<float4*>(p)[i];
+      const float4 gv = reinterpret_cast<const float4*>(g)[i];
+      float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (buf && !first) bv = reinterpret_cast<float4*>(buf)[i];
+      pv.x = update(pv.x, gv.x, bv.x);
+      pv.y = update(pv.y, gv.y, bv.y);
+      pv.z = update(pv.z, gv.z, bv.z);
+      pv.w = update(pv.w, gv.w, bv.w);
+      reinterpret_cast<float4*>(p)[i] = pv;
+      if (buf) reinterpret_cast<float4*>(buf)[i] = bv;
+    }
+    done = n4 << 2;
+  }
+  for (int i = done + threadIdx.x; i < cnt; i += 256) {
+    float bv = (buf && !first) ? buf[i] : 0.f;
+    p[i] = update(p[i], g[i], bv);
+    if (buf) buf[i] = bv;
+  }
+}
+
 // steps[groups[i]] += 1 for the groups that took part in the launch above
 __global__ void adam_advance_kernel(float* steps, const int32_t* __restrict__ groups, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -145,6 +213,13 @@ extern "C" int coclr_adam_step(const int64_t* table, int nchunks, const double* 
   COCLR_LAUNCH_CHECK();
   hipLaunchKernelGGL(adam_advance_kernel, dim3(cdiv(ngroups, 256)), dim3(256), 0, stream, steps,
                      groups, ngroups);
+  COCLR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int coclr_sgd_step(const int64_t* table, int nchunks, const double* hyper, void* stream) {
+  if (nchunks <= 0 || !table || !hyper) return COCLR_EINVAL;
+  hipLaunchKernelGGL(sgd_multi_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table, hyper);
   COCLR_LAUNCH_CHECK();
   return 0;
 }

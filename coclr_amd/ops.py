@@ -847,6 +847,13 @@ def adam_step(table, nchunks, hyper, steps, groups, ngroups, mom_m=0.0, mom_1m=0
                "adam_step")
 
 
+def sgd_step(table, nchunks, hyper, keep=None):
+    """One multi-tensor SGD launch (csrc/optim.hip).  `keep`: the tensors the table points at,
+    referenced while the launch is queued."""
+    _lib.check(_L().coclr_sgd_step(_p(table, torch.int64), nchunks, _p(hyper, torch.float64), _stream()),
+               "sgd_step")
+
+
 def nce_loss_fwd(logits, mask, target, rowstats, flags, scalars, mode, drop_self=False, k1=1, k2=5):
     B, N1 = logits.shape
     _lib.check(_L().coclr_nce_loss_fwd(

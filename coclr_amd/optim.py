@@ -1,4 +1,4 @@
-"""torch.optim.Adam for the launch scripts' parameter structure, as one HIP launch.
+"""torch.optim.Adam / torch.optim.SGD for the launch scripts' parameter structure, as one HIP launch.
 
 main_nce.py:190-200 / main_coclr.py:205-213 build ONE param group per tensor (470 groups for
 S3D InfoNCE, 235 of them with gradients) and call `optimizer.step()` (main_nce.py:331): torch's
@@ -12,6 +12,11 @@ single pointer-table kernel over every tensor (`coclr_adam_step`, csrc/optim.hip
 kernel does not cover (CPU parameters, amsgrad, maximize, sparse or non-fp32 tensors, a closure
 that needs foreach semantics) goes to torch's own implementation unchanged; for CUDA fp32
 parameters there is no silent fallback -- a missing library raises.
+
+`SGD` is the same scheme for the classifier's fine-tuning loop (eval/main_classifier.py:134-140,159:
+one param group per tensor, `optim.SGD(params, lr, weight_decay, momentum=0.9)`) over
+`coclr_sgd_step`; `install()` (also called by the `model.classifier` shim) resolves `torch.optim.SGD`
+to its scoped form unless COCLR_PATCH_SGD=0.
 """
 import os
 import weakref
@@ -23,6 +28,7 @@ from . import ops
 
 _CHUNK = 32768          # elements per workgroup
 _TorchAdam = torch.optim.Adam
+_TorchSGD = torch.optim.SGD
 _MOMENTUM_MODELS = weakref.WeakSet()
 
 
@@ -38,8 +44,9 @@ def register_momentum_model(model):
 
 def register_model(model):
     """Any module of this package whose parameters the single-launch step may take (the linear-probe
-    classifier).  `torch.optim.Adam` resolves to the subclass process-wide once `model.pretrain` is
-    imported; optimisers over parameters that belong to NO registered module behave exactly as torch's."""
+    classifier).  `torch.optim.Adam` / `torch.optim.SGD` resolve to the subclasses process-wide once
+    `model.pretrain` or `model.classifier` is imported; optimisers over parameters that belong to NO
+    registered module behave exactly as torch's."""
     _OWN_MODELS.add(model)
 
 
@@ -50,6 +57,34 @@ def _owns_any(params):
             if id(p) in ids:
                 return True
     return False
+
+
+def _upload_table(plan, gptrs):
+    """Launch table of a plan = its static template with this step's gradient addresses in column 1,
+    written into one of two pinned host buffers and copied to the device on the current stream
+    (the other buffer may still be read by the previous step's copy)."""
+    f = plan["flip"]
+    ev = plan["events"][f]
+    if ev is not None:
+        ev.synchronize()                 # the copy that last read this pinned buffer
+    tab = plan["host"][f].numpy()
+    tab[:] = plan["template"]
+    tab[:, 1] = np.asarray(gptrs, dtype=np.int64)[plan["row_param"]] + plan["row_off"]
+    plan["table"].copy_(plan["host"][f], non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record()
+    plan["events"][f] = ev
+    plan["flip"] = 1 - f
+    plan["gptrs"] = gptrs
+
+
+def _kernel_param(p, dev):
+    """p (which has a gradient) can be read by the optimiser kernels as flat fp32 memory on `dev`
+    (None: not decided yet)."""
+    gr = p.grad
+    return p.is_cuda and p.dtype == torch.float32 and not gr.is_sparse and \
+        gr.dtype == torch.float32 and p.is_contiguous() and gr.is_contiguous() and \
+        gr.device == p.device and (dev is None or p.device == dev)
 
 
 class Adam(_TorchAdam):
@@ -92,17 +127,11 @@ class Adam(_TorchAdam):
                 return None       # options the kernel does not implement, or an explicit torch path
             ps = []
             for p in g["params"]:
-                gr = p.grad
-                if gr is None:
+                if p.grad is None:
                     continue
-                if not p.is_cuda or p.dtype != torch.float32 or gr.is_sparse or \
-                        gr.dtype != torch.float32 or not p.is_contiguous() or \
-                        not gr.is_contiguous() or gr.device != p.device:
-                    return None       # the kernel reads p and p.grad as flat fp32 memory
-                if dev is None:
-                    dev = p.device
-                elif p.device != dev:
-                    return None
+                if not _kernel_param(p, dev):
+                    return None       # the kernel reads p and p.grad as flat fp32 memory, one device
+                dev = p.device
                 ps.append(p)
             if ps:
                 out.append((g, ps))
@@ -235,19 +264,7 @@ class Adam(_TorchAdam):
         # None); the caching allocator usually returns the same blocks, so this rarely uploads
         gptrs = [p.grad.data_ptr() for p in params]
         if gptrs != plan["gptrs"]:
-            f = plan["flip"]
-            ev = plan["events"][f]
-            if ev is not None:
-                ev.synchronize()                 # the copy that last read this pinned buffer
-            tab = plan["host"][f].numpy()
-            tab[:] = plan["template"]
-            tab[:, 1] = np.asarray(gptrs, dtype=np.int64)[plan["row_param"]] + plan["row_off"]
-            plan["table"].copy_(plan["host"][f], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            plan["events"][f] = ev
-            plan["flip"] = 1 - f
-            plan["gptrs"] = gptrs
+            _upload_table(plan, gptrs)
         model = plan["fold"]() if plan["fold"] is not None else None
         m = float(model.m) if model is not None else 0.0
         ops.adam_step(plan["table"], plan["table"].shape[0], plan["hyper"], plan["steps"],
@@ -267,17 +284,179 @@ class ScopedAdam(Adam):
     _scoped = True
 
 
+class SGD(_TorchSGD):
+    """torch.optim.SGD with a single-launch `step()` on MI355X (`coclr_sgd_step`, csrc/optim.hip).
+
+    eval/main_classifier.py:134-140,159 fine-tunes with one param group per tensor (the backbone at
+    lr/10) and `optim.SGD(params, lr, weight_decay, momentum=0.9)`: torch's implementation runs its
+    per-group loop over ~233 groups per step.  Same constructor, same `state_dict()` (per-parameter
+    `momentum_buffer`, only when momentum != 0), same arithmetic as torch's foreach path.  Anything
+    the kernel does not cover (CPU parameters, sparse or non-fp32 gradients, parameters on several
+    devices, a tensor lr / weight decay, an explicit `foreach` / `fused`, `differentiable`) runs
+    torch's own implementation on the same state; momentum buffers carry over both ways."""
+
+    _scoped = False     # ScopedSGD: the native step only for parameters of this package's modules
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, **kw):
+        super().__init__(params, lr=lr, momentum=momentum, dampening=dampening,
+                         weight_decay=weight_decay, nesterov=nesterov, **kw)
+        self._plan = None
+        self._ours = None       # decided at the first step: do these parameters belong to this package?
+
+    def _native_groups(self):
+        """[(group, [params with grad])] if every parameter that has a gradient can take the
+        kernel, else None (torch's implementation runs instead)."""
+        if self._ours is None:
+            self._ours = not self._scoped or _owns_any(p for g in self.param_groups for p in g["params"])
+        if not self._ours or getattr(self, "grad_scale", None) is not None or \
+                getattr(self, "found_inf", None) is not None:
+            return None
+        out = []
+        dev = None
+        for g in self.param_groups:
+            if g.get("differentiable") or g.get("fused") or g.get("foreach") is not None or \
+                    any(torch.is_tensor(g[k]) for k in ("lr", "momentum", "dampening", "weight_decay")):
+                return None
+            ps = []
+            for p in g["params"]:
+                if p.grad is None:
+                    continue
+                if not _kernel_param(p, dev):
+                    return None       # the kernel reads p and p.grad as flat fp32 memory, one device
+                dev = p.device
+                ps.append(p)
+            if ps:
+                out.append((g, ps))
+        return out if out else None
+
+    def _build_plan(self, groups):
+        dev = groups[0][1][0].device
+        params, hyper_of, bufs, rows, row_param, row_off = [], [], [], [], [], []
+        first = False
+        for gi, (g, ps) in enumerate(groups):
+            for p in ps:
+                buf = None
+                fresh = 0
+                if g["momentum"] != 0:
+                    st = self.state[p]
+                    buf = st.get("momentum_buffer")
+                    if buf is None:
+                        # torch's first step clones d_p into the buffer: the launch below writes it
+                        buf = torch.empty_like(p, memory_format=torch.contiguous_format)
+                        fresh = 1
+                    elif buf.device != p.device or buf.dtype != torch.float32 or not buf.is_contiguous():
+                        buf = buf.to(device=p.device, dtype=torch.float32).contiguous()
+                    st["momentum_buffer"] = buf
+                i = len(params)
+                params.append(p)
+                hyper_of.append(gi)
+                bufs.append(buf)
+                first = first or bool(fresh)
+                numel = p.numel()
+                for off in range(0, numel, _CHUNK):
+                    rows.append((p.data_ptr() + 4 * off, 0, 0 if buf is None else buf.data_ptr() + 4 * off,
+                                 min(_CHUNK, numel - off), i, fresh, 0, 0))
+                    row_param.append(i)
+                    row_off.append(4 * off)
+        n = len(params)
+        self._plan = {
+            "params": params, "hyper_of": hyper_of, "bufs": bufs,
+            "sig": [(p.data_ptr(), 0 if b is None else b.data_ptr()) for p, b in zip(params, bufs)],
+            "template": np.array(rows, dtype=np.int64).reshape(-1, 8),
+            "row_param": np.array(row_param, dtype=np.int64), "row_off": np.array(row_off, dtype=np.int64),
+            "host": [torch.empty(len(rows), 8, dtype=torch.int64).pin_memory() for _ in range(2)],
+            "events": [None, None], "flip": 0, "gptrs": None, "first": first,
+            "table": torch.empty(len(rows), 8, dtype=torch.int64, device=dev),
+            # one hyper row per PARAMETER slot (the group's values repeated)
+            "hyper": torch.empty(n, 8, dtype=torch.float64, device=dev), "hyper_sig": None, "n": n,
+            "keep": [b for b in bufs if b is not None],
+        }
+
+    def _plan_valid(self, plan, groups, params):
+        """Same parameter objects at the same addresses, the same momentum buffers in the state
+        (load_state_dict / torch's own step replace them), momentum switched on for the same ones."""
+        if plan is None or len(plan["params"]) != len(params):
+            return False
+        i = 0
+        for g, ps in groups:
+            mom = g["momentum"] != 0
+            for p in ps:
+                pp, bp = plan["sig"][i]
+                if plan["params"][i] is not p or p.data_ptr() != pp or mom != (bp != 0):
+                    return False
+                if mom:
+                    buf = self.state[p].get("momentum_buffer")
+                    if buf is None or buf.data_ptr() != bp:
+                        return False
+                i += 1
+        return True
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        groups = self._native_groups()
+        if groups is None:
+            self._plan = None       # torch's step may replace or create momentum buffers
+            super().step()
+            return loss
+        params = [p for _, ps in groups for p in ps]
+        plan = self._plan
+        if not self._plan_valid(plan, groups, params):
+            self._build_plan(groups)
+            plan = self._plan
+        if plan["template"].shape[0] == 0:
+            return loss             # only empty tensors: nothing to update
+        # hyper-parameters: uploaded when a group's values change (adjust_learning_rate)
+        hsig = tuple((g["lr"], g["momentum"], g["dampening"], g["weight_decay"], bool(g["nesterov"]),
+                      bool(g["maximize"])) for g, _ in groups)
+        if hsig != plan["hyper_sig"]:
+            rows = np.zeros((plan["n"], 8), dtype=np.float64)
+            for i, gi in enumerate(plan["hyper_of"]):
+                rows[i, :6] = hsig[gi]
+            plan["hyper"].copy_(torch.from_numpy(rows))
+            plan["hyper_sig"] = hsig
+        gptrs = [p.grad.data_ptr() for p in params]
+        if gptrs != plan["gptrs"]:
+            _upload_table(plan, gptrs)
+        ops.sgd_step(plan["table"], plan["table"].shape[0], plan["hyper"], keep=plan["keep"])
+        if plan["first"]:
+            # the buffers exist now: later steps read them (the table is re-uploaded once)
+            plan["template"][:, 5] = 0
+            plan["first"] = False
+            plan["gptrs"] = None
+        return loss
+
+
+class ScopedSGD(SGD):
+    """What `torch.optim.SGD` resolves to after `install()`: `SGD`, except that an optimiser over
+    parameters that belong to NO module of this package is torch's own implementation, step for step
+    (the ScopedAdam rule)."""
+    _scoped = True
+
+
+def _notice(msg):
+    if os.environ.get("COCLR_QUIET", "0") != "1":
+        import sys
+        print(msg, file=sys.stderr)
+
+
 def install():
-    """Make `torch.optim.Adam` (what main_nce.py:200 / main_coclr.py:213 construct) resolve to the
-    single-launch subclass, scoped to this package's models (ScopedAdam).  Idempotent;
-    COCLR_PATCH_ADAM=0 leaves torch untouched."""
+    """Make `torch.optim.Adam` (what main_nce.py:200 / main_coclr.py:213 / eval/main_classifier.py:157
+    construct) and `torch.optim.SGD` (eval/main_classifier.py:159) resolve to the single-launch
+    subclasses, scoped to this package's models (ScopedAdam / ScopedSGD).  Idempotent;
+    COCLR_PATCH_ADAM=0 / COCLR_PATCH_SGD=0 leave the respective torch class untouched.  Returns
+    whether Adam is patched."""
+    if os.environ.get("COCLR_PATCH_SGD", "1") != "0" and torch.optim.SGD is not ScopedSGD:
+        torch.optim.SGD = ScopedSGD
+        _notice("coclr_amd: torch.optim.SGD resolves to the single-launch subclass for parameters of "
+                "this package's modules (COCLR_PATCH_SGD=0 opts out)")
     if os.environ.get("COCLR_PATCH_ADAM", "1") == "0":
         return False
     if torch.optim.Adam is not ScopedAdam:
         torch.optim.Adam = ScopedAdam
-        if os.environ.get("COCLR_QUIET", "0") != "1":
-            import sys
-            print("coclr_amd: torch.optim.Adam resolves to the single-launch subclass for parameters of "
-                  "InfoNCE / UberNCE / CoCLR / LinearClassifier modules (COCLR_PATCH_ADAM=0 opts out)",
-                  file=sys.stderr)
+        _notice("coclr_amd: torch.optim.Adam resolves to the single-launch subclass for parameters of "
+                "InfoNCE / UberNCE / CoCLR / LinearClassifier modules (COCLR_PATCH_ADAM=0 opts out)")
     return True

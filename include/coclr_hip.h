@@ -477,6 +477,18 @@ int coclr_plane_dot(const float* a, const float* b, float* out, int N, int C, in
 int coclr_adam_step(const int64_t* table, int nchunks, const double* hyper, float* steps,
                     const int32_t* groups, int ngroups, float mom_m, float mom_1m, void* stream);
 
+/* torch.optim.SGD.step() over a one-group-per-tensor parameter list as ONE launch: the classifier
+ * fine-tuning loop's optimizer (eval/main_classifier.py:159, `optim.SGD(params, lr, weight_decay,
+ * momentum=0.9)`; eval/feature_linear_probe.py:121 constructs the same class), operation for operation
+ * torch.optim.SGD's foreach arithmetic (momentum, dampening, nesterov, weight_decay, maximize).
+ *   table  int64[nchunks][8] on device: {param, grad, momentum_buffer or 0 (momentum == 0), count
+ *          (<= 32768 elements of the tensor), slot, first, 0, 0}; first != 0: the parameter's first
+ *          step with momentum (torch's momentum_buffer is None): buffer = d_p, not read
+ *   hyper  double[.][8] on device, one row per slot: {lr, momentum, dampening, weight_decay,
+ *          nesterov (0/1), maximize (0/1), 0, 0} (doubles: torch forms 1-dampening from Python floats)
+ * No step counter: nothing is written but the parameters and their momentum buffers. */
+int coclr_sgd_step(const int64_t* table, int nchunks, const double* hyper, void* stream);
+
 /* Loss + accuracy over logits[B][N1] in one pass, results as device scalars:
  *   mode 0  nn.CrossEntropyLoss(logits, target)                         (main_nce.py:315)
  *   mode 1  multi_nce_loss: -log(sum_j softmax_j*mask_j)                (main_coclr.py:343-346);
