@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COCLR_LIB_PATH") or os.path.join(_HERE, "libcoclr_hip.so")
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 i32, i64, f32, f64, vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
 
@@ -129,6 +129,8 @@ _SIGNATURES = {
     "coclr_bn1d_stats": [vp, vp, vp, i32, i32, vp],
     "coclr_center_rows": [vp, vp, vp, i32, i32, vp],
     "coclr_retrieval_hits": [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, vp],
+    "coclr_segment_softmax_accum": [vp, _P(i32), _P(f32), vp, i32, i32, i32, i32, vp],
+    "coclr_segment_accum": [vp, _P(i32), _P(f32), vp, i32, i32, i32, i32, vp],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -6,6 +6,9 @@
 //     similar training clips of the test clip's class": one kernel selects the top-kmax of every
 //     similarity row IN ORDER and compares labels on the way, instead of five torch.topk calls
 //     over the full (n_test, n_train) matrix
+//   * video-level scores of the test modes (eval/main_classifier.py:488,533,637,673): clips of one video are
+//     rows of a fixed-size batch; per video, out += weight * sum over its rows of softmax(row) (or of the row
+//     itself, for features) -- a segmented accumulate, because a batch cuts across video boundaries
 #include "common.h"
 #include "../../include/coclr_hip.h"
 #include <math.h>
@@ -117,6 +120,93 @@ retrieval_hits_kernel(const float* __restrict__ sim, const int64_t* __restrict__
   }
 }
 
+// ---- segmented accumulate -------------------------------------------------------------------------------
+// The segments of one launch travel by value in the kernel arguments (1 KB): the host validates them and
+// nothing is copied to the device.  No two segments of one launch write the same output row.
+#define COCLR_SEG_MAX 64
+#define COCLR_SEG_MAX_C 4096
+struct SegBatch {
+  int first[COCLR_SEG_MAX];
+  int rows[COCLR_SEG_MAX];
+  int out[COCLR_SEG_MAX];
+  float w[COCLR_SEG_MAX];
+};
+
+template <int VEC> struct SegVec;
+template <> struct SegVec<1> { using T = float; };
+template <> struct SegVec<4> { using T = f32x4; };
+
+__device__ __forceinline__ float seg_hmax(float v) { return v; }
+__device__ __forceinline__ float seg_hmax(f32x4 v) { return fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)); }
+__device__ __forceinline__ float seg_hsum(float v) { return v; }
+__device__ __forceinline__ float seg_hsum(f32x4 v) { return (v.x + v.y) + (v.z + v.w); }
+__device__ __forceinline__ float seg_exp(float v, float m) { return expf(v - m); }
+__device__ __forceinline__ f32x4 seg_exp(f32x4 v, float m) {
+  f32x4 e;
+  e.x = expf(v.x - m); e.y = expf(v.y - m); e.z = expf(v.z - m); e.w = expf(v.w - m);
+  return e;
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+  return v;
+}
+
+// One workgroup per segment: out[o][:] += w * sum_{r ascending} f(x[first + r][:]), f = softmax or identity.
+// A thread owns the columns (tid + 256 k) * VEC .. + VEC of every row, so the per-column sums are formed by
+// one thread in row order (fp32): the result does not depend on scheduling.  VEC = 4: 16-byte loads and stores
+// (C % 4 == 0, 16-byte aligned bases).  Softmax keeps the running sums and the row in LDS (2 * C floats).
+template <int VEC, bool SOFTMAX>
+__global__ void __launch_bounds__(256)
+segment_accum_kernel(const float* __restrict__ x, float* __restrict__ out, int C, SegBatch sb) {
+  using T = typename SegVec<VEC>::T;
+  extern __shared__ __attribute__((aligned(16))) float seg_lds[];
+  __shared__ float red_max[4], red_sum[4];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const int first = sb.first[s], rows = sb.rows[s];
+  const float wgt = sb.w[s];
+  const int CV = C / VEC;                       // columns in units of T
+  T* o = reinterpret_cast<T*>(out + (long)sb.out[s] * C);
+  if (!SOFTMAX) {
+    for (int c = tid; c < CV; c += 256) {
+      T acc = T(0.f);
+      for (int r = 0; r < rows; ++r)
+        acc += reinterpret_cast<const T*>(x + (long)(first + r) * C)[c];
+      o[c] += wgt * acc;
+    }
+    return;
+  }
+  T* acc = reinterpret_cast<T*>(seg_lds);
+  T* row = reinterpret_cast<T*>(seg_lds + C);
+  for (int c = tid; c < CV; c += 256) acc[c] = T(0.f);
+  for (int r = 0; r < rows; ++r) {
+    const T* xr = reinterpret_cast<const T*>(x + (long)(first + r) * C);
+    float m = -INFINITY;
+    for (int c = tid; c < CV; c += 256) {
+      const T v = xr[c];
+      row[c] = v;
+      m = fmaxf(m, seg_hmax(v));
+    }
+    m = wave_max(m);
+    if ((tid & 63) == 0) red_max[tid >> 6] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(red_max[0], red_max[1]), fmaxf(red_max[2], red_max[3]));
+    float sum = 0.f;
+    for (int c = tid; c < CV; c += 256) {
+      const T e = seg_exp(row[c], m);
+      row[c] = e;
+      sum += seg_hsum(e);
+    }
+    sum = wave_sum(sum);
+    if ((tid & 63) == 0) red_sum[tid >> 6] = sum;
+    __syncthreads();
+    sum = (red_sum[0] + red_sum[1]) + (red_sum[2] + red_sum[3]);
+    for (int c = tid; c < CV; c += 256) acc[c] += row[c] / sum;
+  }
+  for (int c = tid; c < CV; c += 256) o[c] += wgt * acc[c];
+}
+
 }  // namespace
 
 extern "C" int coclr_colstats_workspace(int rows, int cols, int64_t* elems) {
@@ -176,4 +266,48 @@ extern "C" int coclr_retrieval_hits(const float* sim, const int64_t* train_label
                      test_label, ks, nk, kmax, hits, topidx, N, use_lds);
   COCLR_LAUNCH_CHECK();
   return 0;
+}
+
+template <bool SOFTMAX>
+static int segment_accum(const float* x, const int32_t* segs, const float* weight, float* out, int R, int C,
+                         int S, int V, hipStream_t stream) {
+  if (!x || !segs || !weight || !out || R <= 0 || S <= 0 || V <= 0 || C < 1 || C > COCLR_SEG_MAX_C)
+    return COCLR_EINVAL;
+  for (int s = 0; s < S; ++s) {                 // everything is checked before anything is launched
+    const long first = segs[3 * s], rows = segs[3 * s + 1], o = segs[3 * s + 2];
+    if (first < 0 || rows < 1 || first + rows > R || o < 0 || o >= V) return COCLR_EINVAL;
+  }
+  const bool vec = C % 4 == 0 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0;
+  const size_t lds = SOFTMAX ? (size_t)2 * C * sizeof(float) : 0;
+  SegBatch sb;
+  int n = 0;
+  for (int s = 0; s <= S; ++s) {
+    bool flush = s == S || n == COCLR_SEG_MAX;
+    // a second segment of the same output row (another crop of the video in this batch) goes into the
+    // next launch: the stream orders the two read-modify-writes
+    for (int j = 0; j < n && !flush; ++j) flush = sb.out[j] == segs[3 * s + 2];
+    if (flush && n > 0) {
+      if (vec)
+        hipLaunchKernelGGL((segment_accum_kernel<4, SOFTMAX>), dim3(n), dim3(256), lds, stream, x, out, C, sb);
+      else
+        hipLaunchKernelGGL((segment_accum_kernel<1, SOFTMAX>), dim3(n), dim3(256), lds, stream, x, out, C, sb);
+      COCLR_LAUNCH_CHECK();
+      n = 0;
+    }
+    if (s == S) break;
+    sb.first[n] = segs[3 * s]; sb.rows[n] = segs[3 * s + 1]; sb.out[n] = segs[3 * s + 2];
+    sb.w[n] = weight[s];
+    ++n;
+  }
+  return 0;
+}
+
+extern "C" int coclr_segment_softmax_accum(const float* logits, const int32_t* segs, const float* weight,
+                                           float* out, int R, int C, int S, int V, void* stream) {
+  return segment_accum<true>(logits, segs, weight, out, R, C, S, V, (hipStream_t)stream);
+}
+
+extern "C" int coclr_segment_accum(const float* x, const int32_t* segs, const float* weight, float* out,
+                                   int R, int C, int S, int V, void* stream) {
+  return segment_accum<false>(x, segs, weight, out, R, C, S, V, (hipStream_t)stream);
 }

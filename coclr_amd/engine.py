@@ -1216,7 +1216,7 @@ PLAN = os.environ.get("COCLR_PLAN", "1") != "0" and hasattr(torch.cuda, "MemPool
     hasattr(torch.cuda, "use_mem_pool")        # (a torch without private pools: every pass stays interpreted)
 _PLAN_WARMUP = 4            # interpreted passes first: one-time allocations, DDP's bucket rebuild, slot verification
 _PLAN_MAX_SHAPES = 3        # input shapes per node that get a plan (and a pool of activations) of their own
-PLAN_STATS = {"recorded": 0, "replayed": 0, "disabled": []}
+PLAN_STATS = {"recorded": 0, "replayed": 0, "disabled": [], "infer_recorded": 0, "infer_replayed": 0}
 # addresses of recorded outputs and input gradients, fixed for the life of their plan: when the node one stage
 # later hands its recorded dx back as this node's dout, the backward log reads it in place instead of a copy
 _STATIC_PTRS = set()
@@ -1413,6 +1413,131 @@ def _dense5(t):
     return s[4] == 1 and s[3] == w and s[2] == h * w and s[1] == d * h * w
 
 
+# ---------------------------------------------------------------------------------
+# Launch-plan replay of a GRADIENT-FREE pass (linear probe, validation, the test modes, feature extraction)
+# ---------------------------------------------------------------------------------
+# The same mechanism without a tape: after _PLAN_WARMUP interpreted passes of one (input shape, BatchNorm modes)
+# the pass is recorded once into a private memory pool and re-issued from its log.  Only modules that opted in
+# (enable_inference_plans: LinearClassifier's backbone) take part; the pretraining models' key encoders keep
+# their own paths.  Every value the pass uses -- the eval-mode BatchNorm affine, the packed weight operands --
+# is produced by a launch INSIDE the log, so parameter and buffer values may change in place between replays
+# (an optimiser step, load_state_dict); moved storages change the signature and the entry starts over.  The
+# caller receives a CLONE of the recorded output: a gradient-free pass has always returned memory of its own.
+# COCLR_PLAN_INFER=0 switches it off.
+PLAN_INFER = os.environ.get("COCLR_PLAN_INFER", "1") != "0" and hasattr(torch.cuda, "MemPool") and \
+    hasattr(torch.cuda, "use_mem_pool")
+_INFER_MAX_SHAPES = 3       # (input shape, BatchNorm modes) per module that get a plan and a pool; no eviction
+_INFER_STORE = "_coclr_infer_plans"
+
+
+class _InferEntry:
+    __slots__ = ("sig", "seen", "pool", "fwd", "out", "x_ptr", "x_refs", "x_fixed", "disabled", "stream", "keep")
+
+    def __init__(self, sig):
+        self.sig, self.seen = sig, 0
+        self.pool = self.fwd = self.out = self.x_refs = self.keep = None
+        self.x_ptr, self.x_fixed = 0, False
+        self.disabled = False
+        self.stream = 0
+
+
+def enable_inference_plans(module):
+    """Opt `module` (anything run_module takes) in: its gradient-free passes are recorded and replayed."""
+    module.__dict__.setdefault(_INFER_STORE, {})
+    return module
+
+
+def release_inference_plans(module):
+    """Drop the module's recorded gradient-free passes and their memory pools (it stays opted in)."""
+    store = module.__dict__.get(_INFER_STORE)
+    if store:
+        store.clear()
+
+
+def inference_plan_pools(module):
+    """How many memory pools the module's inference plans hold (at most _INFER_MAX_SHAPES)."""
+    return sum(1 for e in module.__dict__.get(_INFER_STORE, {}).values() if e.pool is not None)
+
+
+def _bn_list(module):
+    bns = module.__dict__.get("_coclr_bn_list")
+    if bns is None:
+        bns = module.__dict__["_coclr_bn_list"] = [
+            m for m in module.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
+    return bns
+
+
+def _infer_signature(module, x, params, bns):
+    """_plan_signature without the gradient slots (and with the one switch only tape-free passes read)."""
+    return (x.dtype, x.device, tuple(p.data_ptr() for p in params),
+            tuple((m.momentum, m.eps, m.running_mean.data_ptr(), m.running_var.data_ptr()) for m in bns),
+            PAIR_UNITS, LAZY_APPLY, IN_AFFINE, BATCH_PACK)
+
+
+def _infer_record(ent, module, x):
+    dev = x.device
+    pool = torch.cuda.MemPool()
+    ent.stream = torch.cuda.current_stream(dev).cuda_stream
+    rec = _plan.Recorder(ent.stream)
+    ent.disabled = True          # until the recording has come through
+    with torch.cuda.use_mem_pool(pool, device=dev), rec:
+        run = Run(dev, save=False)
+        run.begin(module)
+        out = module._emit(run, Val(x)).view()
+        if not out.is_contiguous():
+            rec.taint("the module's output is a channel slice")
+    PLAN_STATS["infer_recorded"] += 1
+    if rec.tainted:
+        PLAN_STATS["disabled"].append(rec.tainted)
+        return out.contiguous()
+    n, c, t, h, w = x.shape
+    lo = x.data_ptr()
+    hi = lo + ((n - 1) * x.stride(0) + c * t * h * w) * x.element_size()     # samples may be strided (a batch view)
+    ent.x_ptr, ent.x_refs, ent.x_fixed = lo, rec.plan.pointer_refs(lo, hi), rec.plan.embedded_refs(lo, hi)
+    ent.fwd, ent.out, ent.pool = rec.plan, out, pool
+    # the batch re-layout launch in the log reads the pack plan's tables: they live as long as the log
+    ent.keep = None if run.plan is None else (run.plan.table, run.plan.blockmap)
+    ent.disabled = False
+    return out.clone()
+
+
+def _infer_pass(module, x, params):
+    """The result of a gradient-free pass through the module's inference plan, or None when this call has to
+    run interpreted (warm-up, a shape beyond the cap, a capture in progress, another stream, ...).  `x` is dense
+    in (C, T, H, W) (run_module has made it so, in front of the log); its sample stride is frozen into the
+    logged calls, so it is part of the key: a batch view and a contiguous tensor of one shape get a plan each."""
+    if not x.is_cuda or DECISION_PROBE is not None or _plan._ACTIVE is not None or \
+            torch.cuda.is_current_stream_capturing():
+        return None
+    store = module.__dict__[_INFER_STORE]
+    bns = _bn_list(module)
+    key = (tuple(x.shape), tuple(x.stride()), tuple(m.training for m in bns))
+    sig = _infer_signature(module, x, params, bns)
+    ent = store.get(key)
+    if ent is None and len(store) >= _INFER_MAX_SHAPES:
+        return None                              # every entry keeps a memory pool: odd shapes run interpreted
+    if ent is None or ent.sig != sig:
+        ent = store[key] = _InferEntry(sig)      # new shape / moved storage / switches changed: start over
+    if ent.disabled:
+        return None
+    ent.seen += 1
+    if ent.seen <= _PLAN_WARMUP:
+        return None
+    if ent.fwd is None:
+        return _infer_record(ent, module, x)
+    if torch.cuda.current_stream(x.device).cuda_stream != ent.stream:
+        return None                              # recorded on another stream: this call runs interpreted
+    p = x.data_ptr()
+    if p != ent.x_ptr:
+        if ent.x_fixed:
+            return None                          # the address sits inside a multi-problem table: interpreted
+        ent.fwd.patch(ent.x_refs, p)
+        ent.x_ptr = p
+    ent.fwd.replay()
+    PLAN_STATS["infer_replayed"] += 1
+    return ent.out.clone()
+
+
 def run_module(module, x, **kwargs):
     """Forward `module` (anything with `_emit(run, val, **kw)`) on x."""
     params = module.__dict__.get("_coclr_params")
@@ -1424,8 +1549,14 @@ def run_module(module, x, **kwargs):
             if ent is not None:
                 return PlanFn.apply(ent, module, x, *params)
         return EngineFn.apply(module, kwargs, x, *params)
+    if not _dense5(x):
+        x = x.contiguous()
+    if PLAN_INFER and not kwargs and _INFER_STORE in module.__dict__:
+        out = _infer_pass(module, x, params)
+        if out is not None:
+            return out
     run = Run(x.device, save=False)
-    xin = Val(x if _dense5(x) else x.contiguous())
+    xin = Val(x)
     run.begin(module)
     out = module._emit(run, xin, **kwargs).view()
     plan = run.plan

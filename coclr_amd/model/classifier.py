@@ -10,7 +10,7 @@ as the contrastive head -- no ATen op computes anything.
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import engine, ops
 from ..backbone.select_backbone import select_backbone
 from .pretrain import _AvgPoolFn, _L2NormFn, _PointwiseFn
 
@@ -136,6 +136,8 @@ class LinearClassifier(nn.Module):
         print(message)
 
         self.backbone, self.param = select_backbone(network)
+        # frozen-backbone training, validation and the test modes re-issue a recorded launch plan (engine.PLAN_INFER)
+        engine.enable_inference_plans(self.backbone)
         fs = self.param['feature_size']
 
         if use_final_bn:

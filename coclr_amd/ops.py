@@ -913,3 +913,35 @@ def retrieval_hits(sim, train_label, test_label, ks, hits, topidx=None):
         _p(sim), _p(train_label, torch.int64), _p(test_label, torch.int64), _p(ks, torch.int32),
         ks.shape[0], _p(hits), _p(topidx, torch.int32), B, N, kmax, _stream()),
         "retrieval_hits")
+
+
+SEGMENT_MAX_C = 4096      # widest row the segmented accumulate takes (COCLR_SEG_MAX_C)
+
+
+def _segment_call(name, x, segs, weight, out):
+    R, C_ = x.shape
+    V = out.shape[0]
+    if out.dim() != 2 or out.shape[1] != C_ or not x.is_contiguous() or not out.is_contiguous():
+        raise ValueError("coclr_amd: %s takes dense (R, C) rows and a dense (V, C) output" % name)
+    if not 1 <= C_ <= SEGMENT_MAX_C:
+        raise ValueError("coclr_amd: %s takes rows of 1..%d columns, got %d" % (name, SEGMENT_MAX_C, C_))
+    segs = [tuple(int(v) for v in sg) for sg in segs]
+    weight = [float(w) for w in weight]
+    S = len(segs)
+    if S == 0 or len(weight) != S or any(len(sg) != 3 for sg in segs):
+        raise ValueError("coclr_amd: %s needs S >= 1 segments (first row, rows, out row) and S weights" % name)
+    seg_arr = (C.c_int32 * (3 * S))(*[v for sg in segs for v in sg])
+    w_arr = (C.c_float * S)(*weight)
+    _lib.check(getattr(_L(), "coclr_" + name)(_p(x), seg_arr, w_arr, _p(out), R, C_, S, V, _stream()), name,
+               segs)
+
+
+def segment_softmax_accum(logits, segs, weight, out):
+    """out[o] += weight[s] * sum_{rows of s} softmax(logits[row]) for every segment s = (first row, rows, o).
+    `segs` and `weight` are HOST sequences; nothing is copied to the device and nothing synchronises."""
+    _segment_call("segment_softmax_accum", logits, segs, weight, out)
+
+
+def segment_accum(x, segs, weight, out):
+    """segment_softmax_accum without the softmax (per-video feature sums)."""
+    _segment_call("segment_accum", x, segs, weight, out)

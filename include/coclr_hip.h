@@ -536,6 +536,18 @@ int coclr_retrieval_hits(const float* sim, const int64_t* train_label, const int
                          const int32_t* ks, int nk, float* hits, int32_t* topidx, int B, int N,
                          int kmax, void* stream);
 
+/* Video-level scores of the test modes (eval/main_classifier.py:488,533): for every segment s = {first row,
+ * rows, out row} of logits[R][C],  out[out row][:] += weight[s] * sum over its rows of softmax(row), rows
+ * added in ascending order in fp32 (no atomics: results are run-to-run identical).  `segs` (S x 3 int32) and
+ * `weight` (S floats) are HOST arrays read at call time; out is [V][C] on the device and is accumulated
+ * into.  Segments naming the same out row are applied in the order given.  1 <= C <= 4096;
+ * COCLR_EINVAL for an empty or out-of-range segment (nothing is launched then). */
+int coclr_segment_softmax_accum(const float* logits, const int32_t* segs, const float* weight, float* out,
+                                int R, int C, int S, int V, void* stream);
+/* The same without the softmax: per-video feature sums (eval/main_classifier.py:637,673). */
+int coclr_segment_accum(const float* x, const int32_t* segs, const float* weight, float* out, int R, int C,
+                        int S, int V, void* stream);
+
 /* Library/ABI version, bumped when a signature changes. */
 int coclr_abi_version(void);
 
