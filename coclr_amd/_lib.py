@@ -125,6 +125,8 @@ _SIGNATURES = {
     "coclr_nce_loss_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "coclr_nce_loss_bwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "coclr_stage_clips": [vp, i32, vp, i32, i32, i32, i64, _P(f32), _P(f32), vp],
+    "coclr_stage_crops": [vp, i32, i32, i32, vp, i32, i32, _P(i32), i32, i32, i32, i32, vp, vp, i32, vp, vp, i32,
+                          _P(f32), _P(f32), vp, vp],
     "coclr_colstats_workspace": [i32, i32, _P(i64)],
     "coclr_bn1d_stats": [vp, vp, vp, i32, i32, vp],
     "coclr_center_rows": [vp, vp, vp, i32, i32, vp],

@@ -76,7 +76,150 @@ stage_clips_kernel(const StageArgs a) {
   }
 }
 
+// ---- five/ten-crop test clips from raw frames (eval/main_classifier.py:453-469; utils/augmentation.py:21-43,
+// 61-88,149-177,347-350) -----------------------------------------------------------------------------------
+// flip -> FiveCrop -> Scale(BICUBIC) -> ToTensor -> Normalize -> (crop, clip, 3, T, S, S), one launch per video.
+// Scale is PIL's Image.resize on 8-bit pixels: separable, horizontal pass first, 22-bit fixed-point
+// coefficients, (2^21 + sum K*src) >> 22 clamped to uint8 after EACH pass -- integer arithmetic, so the result is
+// PIL's bit for bit given PIL's coefficient tables (built on the host in double: coclr_amd/staging.py).
+// One workgroup per (band of R output rows, slot = (clip, t), crop): the horizontal pass of the band's source
+// rows goes to LDS as uint8 [row][c][Sp], four results per lane and one 4-byte LDS store; after the barrier the
+// vertical pass reads one 4-byte LDS word per tap, converts with the arithmetic of stage_clips_kernel above and
+// stores 16 bytes along x.  A flipped crop reads source column W-1-(x0+j) with the SAME tables.
+// Every table-derived index is clamped (v_med3) into the crop box / the staged rows: the tables are device
+// data, and zero-padded taps point past the box.
+struct CropArgs {
+  const uint8_t* frames; const int32_t* slot_frame;
+  const int32_t *xmin, *xk, *ymin, *yk;      // [Sp], [taps][Sp]
+  float* out;
+  int crop[16][3];                           // x0, y0, flip
+  float mean[3], std[3];
+  int F, H, W, T, n_clips, cw, ch, S, Sp, xtaps, ytaps, R, cap_rows;
+};
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+__device__ __forceinline__ unsigned fix8(int acc) {       // PIL's clip8 of a 22-bit fixed-point sum
+  const int t = max(acc + (1 << 21), 0);                  // negative sums clip to 0, so the shift can be logical
+  return min((unsigned)t >> 22, 255u);
+}
+
+__global__ void __launch_bounds__(256)
+stage_crops_kernel(const CropArgs a) {
+  extern __shared__ __align__(16) uint8_t hrows[];      // [rows][3][Sp]
+  const int tid = threadIdx.x;
+  const int band = blockIdx.x, slot = blockIdx.y, crop = blockIdx.z;
+  const int r0 = band * a.R, r1 = min(r0 + a.R, a.S);                  // output rows [r0, r1)
+  const int x0 = a.crop[crop][0], y0 = a.crop[crop][1], flip = a.crop[crop][2];
+  const int f = clampi(a.slot_frame[slot], 0, a.F - 1);
+  const int ylo = clampi(a.ymin[r0], 0, a.ch - 1);
+  const int rows = min(clampi(a.ymin[r1 - 1] + a.ytaps, ylo + 1, a.ch) - ylo, a.cap_rows);
+  const int Sp = a.Sp, nxg = Sp >> 2;
+  // byte offset of crop column j, channel 0, within a frame row: xb + xs*j
+  const int xb = flip ? (a.W - 1 - x0) * 3 : x0 * 3, xs = flip ? -3 : 3;
+  const uint8_t* fr = a.frames + ((long)f * a.H + (y0 + ylo)) * (long)a.W * 3;
+
+  // horizontal pass: item = (row, c, xg), xg fastest
+  for (int it = tid; it < rows * 3 * nxg; it += 256) {
+    const int xg = it % nxg, rc = it / nxg;
+    const int c = rc % 3, row = rc / 3;
+    const uint8_t* src = fr + (long)row * a.W * 3 + xb + c;
+    const int4 xm = reinterpret_cast<const int4*>(a.xmin)[xg];
+    int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+    for (int i = 0; i < a.xtaps; ++i) {
+      const int4 k = reinterpret_cast<const int4*>(a.xk + (long)i * Sp)[xg];
+      a0 += k.x * (int)src[xs * clampi(xm.x + i, 0, a.cw - 1)];
+      a1 += k.y * (int)src[xs * clampi(xm.y + i, 0, a.cw - 1)];
+      a2 += k.z * (int)src[xs * clampi(xm.z + i, 0, a.cw - 1)];
+      a3 += k.w * (int)src[xs * clampi(xm.w + i, 0, a.cw - 1)];
+    }
+    reinterpret_cast<unsigned*>(hrows)[(row * 3 + c) * nxg + xg] =
+        fix8(a0) | (fix8(a1) << 8) | (fix8(a2) << 16) | (fix8(a3) << 24);
+  }
+  __syncthreads();
+
+  // vertical pass: item = (r, c, xg), xg fastest
+  const int clip = slot / a.T, t = slot % a.T;
+  const bool vec = (a.S & 3) == 0 && (((uintptr_t)a.out) & 15) == 0;
+  for (int it = tid; it < (r1 - r0) * 3 * nxg; it += 256) {
+    const int xg = it % nxg, rc = it / nxg;
+    const int c = rc % 3, r = r0 + rc / 3;
+    const int ym = a.ymin[r] - ylo;
+    int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+    for (int i = 0; i < a.ytaps; ++i) {
+      const int k = a.yk[(long)i * Sp + r];
+      const unsigned w = reinterpret_cast<const unsigned*>(hrows)[(clampi(ym + i, 0, rows - 1) * 3 + c) * nxg + xg];
+      a0 += k * (int)(w & 255u);
+      a1 += k * (int)((w >> 8) & 255u);
+      a2 += k * (int)((w >> 16) & 255u);
+      a3 += k * (int)(w >> 24);
+    }
+    const float mean = a.mean[c], std = a.std[c];
+    float4 o;
+    o.x = norm1(__fdiv_rn((float)fix8(a0), 255.f), mean, std);
+    o.y = norm1(__fdiv_rn((float)fix8(a1), 255.f), mean, std);
+    o.z = norm1(__fdiv_rn((float)fix8(a2), 255.f), mean, std);
+    o.w = norm1(__fdiv_rn((float)fix8(a3), 255.f), mean, std);
+    float* dst = a.out + (((((long)crop * a.n_clips + clip) * 3 + c) * a.T + t) * a.S + r) * (long)a.S + xg * 4;
+    if (vec) {
+      *reinterpret_cast<float4*>(dst) = o;
+    } else {
+      const float v[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (xg * 4 + j < a.S) dst[j] = v[j];
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" int coclr_stage_crops(const uint8_t* frames, int F, int H, int W, const int32_t* slot_frame,
+                                 int n_clips, int T, const int32_t* crops, int n_crops, int cw, int ch, int S,
+                                 const int32_t* xmin, const int32_t* xk, int xtaps, const int32_t* ymin,
+                                 const int32_t* yk, int ytaps, const float* mean, const float* std, float* out,
+                                 void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!frames || !slot_frame || !crops || !xmin || !xk || !ymin || !yk || !mean || !std || !out)
+    return COCLR_EINVAL;
+  if (F < 1 || H < 1 || W < 1 || T < 1 || n_clips < 1 || S < 1 || S > 512 || cw < 1 || ch < 1)
+    return COCLR_EINVAL;
+  if (n_crops < 1 || n_crops > 16 || xtaps < 1 || xtaps > 64 || ytaps < 1 || ytaps > 64)
+    return COCLR_EINVAL;
+  if ((long)W * 3 * H > 0x7fffffffL || (long)n_clips * T > 65535) return COCLR_EINVAL;
+  CropArgs a;
+  for (int k = 0; k < n_crops; ++k) {
+    const int x0 = crops[3 * k], y0 = crops[3 * k + 1], flip = crops[3 * k + 2];
+    if (x0 < 0 || y0 < 0 || (long)x0 + cw > W || (long)y0 + ch > H || (flip != 0 && flip != 1))
+      return COCLR_EINVAL;
+    a.crop[k][0] = x0; a.crop[k][1] = y0; a.crop[k][2] = flip;
+  }
+  for (int c = 0; c < 3; ++c) {
+    a.mean[c] = mean[c]; a.std[c] = std[c];             // host arrays, read at call time
+    if (a.std[c] == 0.f) return COCLR_EINVAL;
+  }
+  // band height: the most output rows whose source rows fit the LDS budget.  ymin is non-decreasing and
+  // advances by at most ch/S (+1 from truncation) per output row, so a band of R rows spans at most
+  // floor((R-1)*ch/S) + ytaps + 1 source rows; the kernel clamps to cap_rows whatever the tables say.
+  const int Sp = (S + 3) & ~3;
+  int R = 32, cap = 0;
+  for (;; R >>= 1) {
+    cap = (int)(((long)(R - 1) * ch) / S) + ytaps + 2;
+    if (cap > ch) cap = ch;
+    const long bytes = (long)cap * 3 * Sp;
+    if (bytes <= (R > 1 ? 32768 : 65536)) break;
+    if (R == 1) return COCLR_EINVAL;                   // one output row's taps do not fit 64 KiB of LDS
+  }
+  const long bands = (S + R - 1) / R;
+  if (bands * n_clips * T * n_crops * 256 >= (1L << 32)) return COCLR_EINVAL;
+  a.frames = frames; a.slot_frame = slot_frame; a.xmin = xmin; a.xk = xk; a.ymin = ymin; a.yk = yk; a.out = out;
+  a.F = F; a.H = H; a.W = W; a.T = T; a.n_clips = n_clips; a.cw = cw; a.ch = ch; a.S = S; a.Sp = Sp;
+  a.xtaps = xtaps; a.ytaps = ytaps; a.R = R; a.cap_rows = cap;
+  dim3 grid((unsigned)bands, (unsigned)(n_clips * T), (unsigned)n_crops);
+  hipLaunchKernelGGL(stage_crops_kernel, grid, dim3(256), (size_t)cap * 3 * Sp, stream, a);
+  COCLR_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int coclr_stage_clips(const void* frames, int from_u8, float* out, int B, int C, int S,
                                  int64_t THW, const float* mean, const float* std, void* stream_) {

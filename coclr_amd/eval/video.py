@@ -18,6 +18,10 @@ import torch
 
 from .. import loss as _loss
 from .. import ops
+from .. import staging
+
+# the reference's aug_list / flip_list (eval/main_classifier.py:431-442), in its order: flips outermost
+CROP_MODES = {"center": ((5,), (0,)), "five": ((5, 1, 2, 3, 4), (0,)), "ten": ((5, 1, 2, 3, 4), (0, 1))}
 
 VideoScores = collections.namedtuple("VideoScores", "probs features labels top1 top5")
 
@@ -81,6 +85,48 @@ class VideoEvaluator:
             done += k
             if self._fill == self.batch_clips:
                 self._flush()
+        return video
+
+    def add_frames(self, frames_u8, frame_index, label=None, crops="ten", crop_size=224, out_size=128,
+                   max_stage_bytes=256 << 20):
+        """One video from its decoded frames: `frames_u8` (F, H, W, 3) uint8, host or device, uploaded ONCE;
+        `frame_index` (n_clips, T) the frame of every clip position (staging.test_frame_index).  `crops`:
+        "center", "five" or "ten" -- the reference's --center_crop / --five_crop / --ten_crop, centre first and
+        the flipped five last.  Every crop is staged on the GPU (staging.stage_crops: flip, FiveCrop(crop_size),
+        Scale(out_size) in PIL's bicubic, ToTensor, Normalize; the reference's random test-time ColorJitter is
+        left out) and handed to add() as a further crop of one video, whose index is returned.  Whole crops are
+        staged in chunks of at most `max_stage_bytes`."""
+        if crops not in CROP_MODES:
+            raise ValueError("coclr_amd: crops must be one of %s, got %r" % (sorted(CROP_MODES), crops))
+        if frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or frames_u8.dtype != torch.uint8:
+            raise ValueError("coclr_amd: frames must be uint8 (F, H, W, 3), got %s %s" %
+                             (frames_u8.dtype, tuple(frames_u8.shape)))
+        where, flip_list = CROP_MODES[crops]
+        F, H, W = frames_u8.shape[:3]
+        crop_size, S = int(crop_size), int(out_size)
+        boxes = staging.five_crop_boxes(W, H, crop_size, where)
+        todo = staging.check_crops(boxes * len(flip_list), [f for f in flip_list for _ in boxes],
+                                   crop_size, crop_size, W, H)
+        idx = staging.check_frame_index(frame_index, F)
+        n, T = idx.shape
+        per_crop = n * 3 * T * S * S * 4
+        if per_crop > max_stage_bytes:
+            raise ValueError("coclr_amd: one crop of this video is %d bytes, max_stage_bytes is %d" %
+                             (per_crop, max_stage_bytes))
+        if self._buf is not None and (3, T, S, S) != tuple(self._buf.shape[1:]):
+            raise ValueError("coclr_amd: clip size %s differs from the evaluator's %s" %
+                             ((3, T, S, S), tuple(self._buf.shape[1:])))
+        frames = frames_u8.contiguous().to(self.device)
+        idx = idx.to(self.device)
+        chunk = min(len(todo), 16, max_stage_bytes // per_crop)
+        buf = torch.empty(chunk, n, 3, T, S, S, dtype=torch.float32, device=self.device)
+        video = None
+        for k in range(0, len(todo), chunk):
+            part = todo[k:k + chunk]
+            staged = staging.stage_crops_on_device(frames, idx, part, crop_size, crop_size, S, out=buf[:len(part)])
+            for clips in staged:
+                # (add() copies the crop into the batch on this stream before the next chunk overwrites `buf`)
+                video = self.add(clips, label=label if video is None else None, video=video)
         return video
 
     def _flush(self):

@@ -883,6 +883,37 @@ def stage_clips(frames, out, S, mean, std):
                "stage_clips")
 
 
+def stage_crops(frames, slot_frame, crops, cw, ch, S, xmin, xk, ymin, yk, mean, std, out):
+    """frames (F, H, W, 3) uint8, slot_frame (n_clips, T) int32 (validated by the caller: the kernel reads it
+    on the device), crops [(x0, y0, flip)] -> out (n_crops, n_clips, 3, T, S, S) fp32.  Tables: xmin (Sp,),
+    xk (xtaps, Sp) int32 with Sp = S rounded up to a multiple of 4, the same for y (include/coclr_hip.h)."""
+    if frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise ValueError("coclr_amd: frames must be contiguous (F, H, W, 3), got %s" % (tuple(frames.shape),))
+    F, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
+    n_clips, T = slot_frame.shape
+    Sp = (S + 3) & ~3
+    if tuple(xmin.shape) != (Sp,) or xk.dim() != 2 or xk.shape[1] != Sp or \
+            tuple(ymin.shape) != (Sp,) or yk.dim() != 2 or yk.shape[1] != Sp:
+        raise ValueError("coclr_amd: resampling tables must be (Sp,) and (taps, Sp) with Sp = %d" % Sp)
+    if tuple(out.shape) != (len(crops), n_clips, 3, T, S, S) or not out.is_contiguous():
+        raise ValueError("coclr_amd: out must be contiguous %s, got %s" %
+                         ((len(crops), n_clips, 3, T, S, S), tuple(out.shape)))
+    for t in (slot_frame, xmin, xk, ymin, yk):
+        if not t.is_contiguous():
+            raise ValueError("coclr_amd: stage_crops needs contiguous index and table tensors")
+    flat = [int(v) for c in crops for v in c]
+    if len(flat) != 3 * len(crops) or not crops:
+        raise ValueError("coclr_amd: crops must be (x0, y0, flip) triples")
+    box = (C.c_int32 * len(flat))(*flat)
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    s = (C.c_float * 3)(*[float(v) for v in std])
+    i32 = torch.int32
+    _lib.check(_L().coclr_stage_crops(
+        _p(frames, torch.uint8), F, H, W, _p(slot_frame, i32), n_clips, T, box, len(crops), cw, ch, S,
+        _p(xmin, i32), _p(xk, i32), xk.shape[0], _p(ymin, i32), _p(yk, i32), yk.shape[0], m, s, _p(out),
+        _stream()), "stage_crops")
+
+
 # ---- evaluation consumers ---------------------------------------------------------------
 
 def colstats_workspace(rows, cols):

@@ -12,7 +12,15 @@ normalisation and the re-layout in ONE kernel (csrc/staging.hip) and also accept
 frames as uint8 (what they are before ToTensor: 4x less PCIe traffic), bit-identical to
 `ToTensor` + `Normalize` on the same bytes.  The model already consumes `block[:, i]` as strided
 views, so nothing else is copied.
+
+The test protocol's input (eval/main_classifier.py:453-469) is staged here too: `stage_crops` turns ONE
+video's raw uint8 frames into every crop x flip x clip the five/ten-crop test feeds the classifier, in one
+launch, bit-identical to the reference's PIL chain (flip -> FiveCrop -> Scale(BICUBIC) -> ToTensor) plus
+Normalize; `resample_tables`, `five_crop_boxes` and `test_frame_index` are the host-side restatements it needs.
 """
+import math
+
+import numpy as np
 import torch
 
 from . import ops
@@ -89,3 +97,170 @@ class ClipStager:
         ev.record(main)
         self.read_done[f] = ev
         return out
+
+
+# ---- five/ten-crop test clips from raw frames ---------------------------------------------------------------
+
+def _cubic(x, a=-0.5):
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0
+    if x < 2.0:
+        return (((x - 5.0) * x + 8.0) * x - 4.0) * a
+    return 0.0
+
+
+def resample_tables(n_in, n_out):
+    """PIL's BICUBIC coefficients for one axis of `Image.resize` on 8-bit pixels, n_in samples -> n_out:
+    (xmin int32 (n_out,), K int32 (n_out, taps)) with result[xx] = clip8((2^21 + sum_i K[xx, i] *
+    src[xmin[xx] + i]) >> 22).  Computed in Python floats (IEEE doubles) in PIL's order of operations; rows
+    with fewer than `taps` = 2*ceil(support) + 1 samples are padded with zero taps."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError("coclr_amd: resample_tables needs n_in, n_out >= 1")
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = 2.0 * fs
+    ss = 1.0 / fs
+    taps = int(math.ceil(support)) * 2 + 1
+    xmin = np.zeros(n_out, dtype=np.int32)
+    K = np.zeros((n_out, taps), dtype=np.int32)
+    for xx in range(n_out):
+        center = (xx + 0.5) * scale
+        lo = max(int(center - support + 0.5), 0)
+        hi = min(int(center + support + 0.5), n_in)
+        w = [_cubic((i + lo - center + 0.5) * ss) for i in range(hi - lo)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        xmin[xx] = lo
+        for i, v in enumerate(w):
+            k = v / ww if ww != 0.0 else v
+            K[xx, i] = int(k * 4194304.0 + 0.5) if k >= 0 else int(k * 4194304.0 - 0.5)
+    return xmin, K
+
+
+def five_crop_boxes(W, H, size, where=(5, 1, 2, 3, 4)):
+    """Top-left corners [(x0, y0)] of FiveCrop(size, where=k) on a W x H frame for every k of `where`
+    (utils/augmentation.py:61-88: 1 = top left, 2 = top right, 3 = bottom left, 4 = bottom right, 5 = centre,
+    with Python's round-half-to-even for the centre).  Square crops only."""
+    W, H, size = int(W), int(H), int(size)
+    if size < 1 or size > H or size > W:
+        raise ValueError("coclr_amd: requested crop size %d is bigger than input size %s" % (size, (H, W)))
+    at = {1: (0, 0), 2: (W - size, 0), 3: (0, H - size), 4: (W - size, H - size),
+          5: (int(round((W - size) / 2.)), int(round((H - size) / 2.)))}
+    out = []
+    for k in where:
+        if k not in at:
+            raise ValueError("coclr_amd: FiveCrop has no position %r" % (k,))
+        out.append(at[k])
+    return out
+
+
+def test_frame_index(total, num_frames, ds=1):
+    """Frame indices of the test-mode clips of a video of `total` frames (dataset/lmdb_dataset.py:111-122):
+    int64 (n_clips, num_frames).  Clips of num_frames*ds frames start every num_frames*ds//2 - 1 frames; a
+    video no longer than one clip gives ONE clip, right-aligned and left-padded with frame 0."""
+    total, num_frames, ds = int(total), int(num_frames), int(ds)
+    if total < 1 or num_frames < 1 or ds < 1:
+        raise ValueError("coclr_amd: test_frame_index needs total, num_frames, ds >= 1")
+    step = num_frames * ds // 2 - 1
+    if step < 1:
+        raise ValueError("coclr_amd: clips of %d frames at stride %d give a window step of %d" %
+                         (num_frames, ds, step))
+    seq = np.arange(num_frames, dtype=np.int64) * ds
+    if total - num_frames * ds <= 0:
+        idx = np.zeros_like(seq)
+        keep = seq[seq < total]
+        idx[len(idx) - len(keep):] = keep
+        return idx[None, :]
+    start = np.arange(0, total - num_frames * ds + 1, step, dtype=np.int64)
+    return seq[None, :] + start[:, None]
+
+
+test_frame_index.__test__ = False        # (a product function whose name pytest would collect)
+
+_TABLES = {}        # (cw, ch, S, device) -> (xmin, xk, ymin, yk) on the device, in the kernel's layout
+
+
+def _device_tables(cw, ch, S, device):
+    key = (cw, ch, S, str(device))
+    if key not in _TABLES:
+        Sp = (S + 3) & ~3
+        tabs = []
+        for n_in in (cw, ch):
+            lo, K = resample_tables(n_in, S)
+            lo_p = np.zeros(Sp, dtype=np.int32)
+            lo_p[:S] = lo
+            K_p = np.zeros((K.shape[1], Sp), dtype=np.int32)       # tap-major: one 16-byte load per tap
+            K_p[:, :S] = K.T
+            tabs += [torch.from_numpy(lo_p).to(device), torch.from_numpy(K_p).to(device)]
+        _TABLES[key] = tuple(tabs)
+    return _TABLES[key]
+
+
+def _crop_wh(crop_size):
+    cw, ch = (crop_size, crop_size) if isinstance(crop_size, int) else crop_size
+    return int(cw), int(ch)
+
+
+def check_frame_index(frame_index, F):
+    """`frame_index` (n_clips, T) of anything array-like -> int32 host tensor, refused here, on the host, when
+    an index is outside [0, F): the kernel reads the indices on the device."""
+    idx = torch.as_tensor(np.asarray(frame_index.cpu() if torch.is_tensor(frame_index) else frame_index))
+    if idx.dim() != 2 or idx.numel() == 0 or idx.is_floating_point():
+        raise ValueError("coclr_amd: frame_index must be integers of shape (n_clips, T), got %s %s" %
+                         (idx.dtype, tuple(idx.shape)))
+    lo, hi = int(idx.min()), int(idx.max())
+    if lo < 0 or hi >= F:
+        raise IndexError("coclr_amd: frame_index spans %d..%d but the video has %d frames" % (lo, hi, F))
+    return idx.to(torch.int32).contiguous()
+
+
+def check_crops(boxes, flips, cw, ch, W, H):
+    boxes, flips = list(boxes), list(flips)
+    if not boxes or len(boxes) != len(flips):
+        raise ValueError("coclr_amd: need one flip per crop box, got %d boxes and %d flips" %
+                         (len(boxes), len(flips)))
+    crops = []
+    for (x0, y0), fl in zip(boxes, flips):
+        x0, y0, fl = int(x0), int(y0), int(fl)
+        if x0 < 0 or y0 < 0 or x0 + cw > W or y0 + ch > H or fl not in (0, 1):
+            raise ValueError("coclr_amd: crop (%d, %d, flip %d) of %dx%d leaves the %dx%d frame" %
+                             (x0, y0, fl, cw, ch, W, H))
+        crops.append((x0, y0, fl))
+    return crops
+
+
+def stage_crops_on_device(frames, slot_frame, crops, cw, ch, S, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
+    """The launch alone: `frames` (F, H, W, 3) uint8 and `slot_frame` (n_clips, T) int32 already on the device
+    and checked (check_frame_index, check_crops).  Up to 16 crops per launch; more are cut into launches."""
+    n_clips, T = slot_frame.shape
+    if out is None:
+        out = torch.empty(len(crops), n_clips, 3, T, S, S, dtype=torch.float32, device=frames.device)
+    xmin, xk, ymin, yk = _device_tables(cw, ch, S, frames.device)
+    for k in range(0, len(crops), 16):
+        ops.stage_crops(frames, slot_frame, crops[k:k + 16], cw, ch, S, xmin, xk, ymin, yk, mean, std,
+                        out[k:k + 16])
+    return out
+
+
+def stage_crops(frames_u8, frame_index, boxes, flips, crop_size, out_size, mean=IMAGENET_MEAN, std=IMAGENET_STD,
+                out=None, device=None):
+    """One video's decoded frames -> every crop x clip of the test protocol, (n_crops, n_clips, 3, T, S, S)
+    fp32 on the device: per crop `flip the frame -> crop the box at boxes[k] -> Image.resize((S, S), BICUBIC)
+    -> ToTensor -> Normalize`, bit-identical to that chain (its random ColorJitter left out).
+    frames_u8: (F, H, W, 3) uint8 on the host (uploaded once) or the device.  frame_index: (n_clips, T) frame
+    of every clip position, checked on the host.  boxes: [(x0, y0)] in the FLIPPED frame where flips[k] is 1.
+    crop_size: int or (width, height).  `device` defaults to the frames' device, or the current GPU."""
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or frames_u8.dtype != torch.uint8:
+        raise ValueError("coclr_amd: frames must be uint8 (F, H, W, 3), got %s %s" %
+                         (frames_u8.dtype, tuple(frames_u8.shape)))
+    F, H, W = frames_u8.shape[:3]
+    cw, ch = _crop_wh(crop_size)
+    crops = check_crops(boxes, flips, cw, ch, W, H)
+    idx = check_frame_index(frame_index, F)
+    if device is None:
+        device = frames_u8.device if frames_u8.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    frames = frames_u8.contiguous().to(device)
+    return stage_crops_on_device(frames, idx.to(device), crops, cw, ch, int(out_size), mean, std, out)

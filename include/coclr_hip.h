@@ -514,6 +514,26 @@ int coclr_nce_loss_bwd(const float* logits, const uint8_t* mask, const int64_t* 
 int coclr_stage_clips(const void* frames, int from_u8, float* out, int B, int C, int S, int64_t THW,
                       const float* mean, const float* std, void* stream);
 
+/* Five/ten-crop test clips of ONE video from its raw frames in one launch (eval/main_classifier.py:453-469;
+ * utils/augmentation.py:21-43,61-88,149-177,347-350): for every crop k = {x0, y0, flip} and slot (clip, t),
+ *   flip the frame (flip = 1) -> crop the cw x ch box at (x0, y0) OF THE FLIPPED FRAME -> PIL's
+ *   Image.resize((S, S), BICUBIC) on 8-bit pixels -> / 255 -> (x - mean[c]) / std[c]
+ * into out[n_crops][n_clips][3][T][S][S] fp32, bit-identical to that chain.  The random test-time ColorJitter
+ * of the reference is not part of it.
+ * frames: uint8 [F][H][W][3] (interleaved RGB), device.  slot_frame: int32 [n_clips*T], device: the frame of
+ * every (clip, t); frames may repeat.  crops: HOST int32 [n_crops][3], read at call time.  The resampling
+ * tables (device, int32) are PIL's precomputed coefficients per axis, in its 22-bit fixed point:
+ * xmin[Sp], xk[xtaps][Sp] with Sp = S rounded up to a multiple of 4 (tap-major; rows shorter than xtaps and
+ * the columns past S are zero); the same for y.  A flipped crop uses the same tables on mirrored columns.
+ * COCLR_EINVAL before any launch: a null pointer; F, H, W, T, n_clips, S, cw, ch < 1; S > 512; n_crops
+ * outside 1..16; taps outside 1..64; a box that leaves the frame; flip not 0/1; std == 0; n_clips*T > 65535
+ * or a grid over the launch limits; an output row whose ytaps source rows (3*Sp bytes each) exceed 64 KiB.
+ * Frame indices outside [0, F) are the CALLER's to refuse (they live on the device). */
+int coclr_stage_crops(const uint8_t* frames, int F, int H, int W, const int32_t* slot_frame, int n_clips,
+                      int T, const int32_t* crops, int n_crops, int cw, int ch, int S, const int32_t* xmin,
+                      const int32_t* xk, int xtaps, const int32_t* ymin, const int32_t* yk, int ytaps,
+                      const float* mean, const float* std, float* out, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* Evaluation consumers (model/classifier.py:47-61; eval/main_classifier.py) */
 /* ------------------------------------------------------------------------ */
