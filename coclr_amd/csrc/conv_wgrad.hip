@@ -1068,6 +1068,7 @@ struct WPlan {
   // second-generation kernel
   int v2;            // 0: not applicable, else variant id (6: temporal Winograd form of id 2)
   int pw;            // pointwise: 16-byte-DMA GEMM kernel applicable
+  int rebox;         // id 7: the 32 x 2 box was re-cut to 16 x 4
   ConvPlan p2;
   int S2, planeP2, mt2, ct2;
   size_t lds2;
@@ -1094,6 +1095,7 @@ inline int wgrad_order_env() {
 // stem: (1,7,7) over 3 channels -> conv_wgrad_stem_kernel; fills the v2 plan fields
 int pick_stem(const coclr_conv_desc* d, WPlan* w) {
   w->pw = 0;
+  w->rebox = 0;
   if (!(d->kt == 1 && d->kh == 7 && d->kw == 7 && d->Cin == 3)) return 0;
   ConvPlan& p = w->p2;
   conv_normalise(d, &p);
@@ -1125,6 +1127,7 @@ int pick_v2(const coclr_conv_desc* d, WPlan* w) {
   const int kt = d->kt, kh = d->kh, kw = d->kw;
   int MB = 1, NB = 1, id = 0;
   w->pw = 0;
+  w->rebox = 0;
   if (kt == 1 && kh == 3 && kw == 3) id = 1;
   else if (kt == 3 && kh == 1 && kw == 1) id = 2;
   else if (kt == 7 && kh == 1 && kw == 1) id = 3;
@@ -1185,6 +1188,7 @@ int pick_v2(const coclr_conv_desc* d, WPlan* w) {
       q.WH = 3 + 3; q.WW = 15 + 3;
       q.plane1 = q.WT * q.WH * q.WW;
       q.plane = q.plane1;
+      w->rebox = 1;
     }
     const int planeP = q.plane | 1;
     const size_t stage = ((size_t)32 * 65 + (size_t)64 * planeP) * sizeof(float);
@@ -1203,6 +1207,7 @@ int pick_v2(const coclr_conv_desc* d, WPlan* w) {
       w->S2 = xcd_round(S);
       return 7;
     }
+    w->rebox = 0;
   }
   conv_pick_box(&p, 6, kt, kh, kw);
   if ((id == 4 || id == 5) && p.Ti == 1 && p.Hi == 1 && p.lTW == 6 && p.lTN == 0 &&
@@ -1240,10 +1245,12 @@ int pick_v2(const coclr_conv_desc* d, WPlan* w) {
 // per XCD (Conv_2c.conv2 0.898 -> 0.863 ms, Conv_1a.conv2 1.051 -> 0.992); below it every L2 ends up
 // holding the whole sample either way and the launch grid's own order dispatches a few percent better
 // (128->128 (3,1,1) on 8x8x8: 0.023 vs 0.027 ms).
+inline int wgrad_tile_default(const coclr_conv_desc* d) {
+  return (double)d->Cin * d->Ti * d->Hi * d->Wi * 4.0 >= 4.0 * 1024 * 1024;
+}
 inline int wgrad_tile_fastest(const coclr_conv_desc* d) {
   const int forced = wgrad_order_env();
-  if (forced >= 0) return forced;
-  return (double)d->Cin * d->Ti * d->Hi * d->Wi * 4.0 >= 4.0 * 1024 * 1024;
+  return forced >= 0 ? forced : wgrad_tile_default(d);
 }
 
 int plan_wgrad(const coclr_conv_desc* d, WPlan* w) {
@@ -1283,6 +1290,49 @@ int plan_wgrad(const coclr_conv_desc* d, WPlan* w) {
   return 0;
 }
 
+// LDS of the stem kernel's two stages in the BNA form
+inline size_t stem_bna_lds(const WPlan& w) {
+  return 2 * ((size_t)2 * 64 * 129 + 128 + (size_t)3 * w.planeP2) * sizeof(float);
+}
+// the stem kernel that applies BatchNorm's backward while it loads exists for this plan (see _bn_ok)
+inline bool stem_bn_ok(const WPlan& w) { return w.v2 == 9 && stem_bna_lds(w) <= (size_t)160 * 1024; }
+
+// Which kernel instantiation a planned launch runs: the ONE place that decides it (wgrad_run launches what
+// this says, coclr_conv3d_wgrad_plan reports it, coclr_conv3d_wgrad_workspace sizes the slices by it).
+enum { WF_GEN1 = 0, WF_WAVE = 1, WF_STEM = 2, WF_PWDMA = 3 };
+struct WSel {
+  int family;   // WF_*
+  int id;       // WF_WAVE: 1-7; WF_PWDMA: 4 (128 x 128 tile) or 5 (64 x 64); WF_STEM: 9; WF_GEN1: 0
+  int pch;      // template PCH (0: the kernel has none)
+  int bj;       // WF_GEN1: template BJ
+  int slices;   // workspace slices one split writes
+};
+inline WSel select_wgrad(const WPlan& w, bool aligned16) {
+  WSel s = {WF_GEN1, 0, 0, 0, 1};
+  if (!w.v2) {
+    static const int pch_of[4] = {2, 4, 8, 20};
+    s.pch = pch_of[w.variant];
+    s.bj = w.BJ;
+    return s;
+  }
+  const int pch = cdiv(w.p2.plane, 64);
+  s.id = w.v2;
+  if (w.v2 == 9) {
+    s.family = WF_STEM; s.pch = 20; s.slices = 4;
+  } else if (w.pw && aligned16) {
+    s.family = WF_PWDMA;
+  } else {
+    s.family = WF_WAVE;
+    switch (w.v2) {
+      case 1: case 7: s.pch = pch <= 2 ? 2 : 3; break;
+      case 3: s.pch = 4; break;
+      default: s.pch = 2;
+    }
+    if (w.v2 == 7) s.slices = 2;
+  }
+  return s;
+}
+
 template <int BJ, int PCH>
 int launch_wgrad(WgradArgs& a, const WPlan& w, hipStream_t stream) {
   const size_t lds = ((size_t)64 * 129 + 128 + (size_t)w.nci_max * a.planeP) * sizeof(float);
@@ -1311,8 +1361,29 @@ extern "C" int coclr_conv3d_wgrad_workspace(const coclr_conv_desc* d, int64_t* e
   int rc = plan_wgrad(d, &w);
   if (rc) return rc;
   // split slices: the stem kernel writes four per split (one per matrix wave), the F(2x2,3x3) form two
-  *elems = (int64_t)(w.v2 ? w.S2 * (w.v2 == 9 ? 4 : (w.v2 == 7 ? 2 : 1)) : w.S) * d->Cout * d->Cin * d->kt *
-           d->kh * d->kw;
+  *elems = (int64_t)(w.v2 ? w.S2 : w.S) * select_wgrad(w, true).slices * d->Cout * d->Cin * d->kt * d->kh *
+           d->kw;
+  return 0;
+}
+
+extern "C" int coclr_conv3d_wgrad_plan(const coclr_conv_desc* d, int operands_16B_aligned, int32_t out[16]) {
+  if (!d || !out) return COCLR_EINVAL;
+  WPlan w;
+  int rc = plan_wgrad(d, &w);
+  if (rc) return rc;
+  const WSel s = select_wgrad(w, operands_16B_aligned != 0);
+  const ConvPlan& p = w.v2 ? w.p2 : w.p;
+  out[0] = s.family; out[1] = s.id; out[2] = s.pch; out[3] = s.bj;
+  out[4] = w.v2 ? w.S2 : w.S;
+  out[5] = s.slices;
+  out[6] = w.v2 ? w.ct2 : w.jtiles;
+  out[7] = w.v2 ? w.mt2 : w.mtiles;
+  out[8] = p.lTW; out[9] = p.lTH; out[10] = p.lTT; out[11] = p.lTN;
+  out[12] = p.ntiles;
+  // only the wave-specialised and pointwise-DMA kernels consult the order (wgrad_tile)
+  out[13] = (s.family == WF_WAVE || s.family == WF_PWDMA) ? wgrad_tile_default(d) : 0;
+  out[14] = stem_bn_ok(w) ? 1 : 0;
+  out[15] = w.rebox;
   return 0;
 }
 
@@ -1324,10 +1395,6 @@ struct WgradBn {
   long y_nstride;
   int relu;
 };
-// LDS of the stem kernel's two stages in the BNA form
-inline size_t stem_bna_lds(const WPlan& w) {
-  return 2 * ((size_t)2 * 64 * 129 + 128 + (size_t)3 * w.planeP2) * sizeof(float);
-}
 int wgrad_run(const coclr_conv_desc* d, const float* x, const float* dy, const WgradBn* bn,
               float* const* dw_list, const int32_t* row_end, int nseg, float* workspace,
               int64_t w_co_stride, int64_t w_ci_stride, int tap_base, int accumulate, void* stream_);
@@ -1357,7 +1424,7 @@ extern "C" int coclr_conv3d_wgrad_bn_ok(const coclr_conv_desc* d, int* ok) {
   WPlan w;
   int rc = plan_wgrad(d, &w);
   if (rc) return rc;
-  *ok = (w.v2 == 9 && stem_bna_lds(w) <= (size_t)160 * 1024) ? 1 : 0;
+  *ok = stem_bn_ok(w) ? 1 : 0;
   return 0;
 }
 
@@ -1390,7 +1457,7 @@ int wgrad_run(const coclr_conv_desc* d, const float* x, const float* dy, const W
   WPlan w;
   int rc = plan_wgrad(d, &w);
   if (rc) return rc;
-  if (bn && !(w.v2 == 9 && stem_bna_lds(w) <= (size_t)160 * 1024)) return COCLR_EINVAL;   // see _bn_ok
+  if (bn && !stem_bn_ok(w)) return COCLR_EINVAL;   // see _bn_ok
   const int taps = d->kt * d->kh * d->kw;
   int S_used;
   if (w.v2) {
@@ -1415,10 +1482,9 @@ int wgrad_run(const coclr_conv_desc* d, const float* x, const float* dy, const W
     a.bn_y = bn ? bn->y : nullptr; a.bn_coef = bn ? bn->coef : nullptr;
     a.bn_y_nstride = bn ? bn->y_nstride : 0; a.bn_relu = bn ? bn->relu : 0;
     if (w.v2 == 6) a.dy_cstride = d->To * p.Ho * p.Wo;     // p.To counts pairs there
-    const int pch = cdiv(p.plane, 64);
-    const bool pw = w.pw && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0;
-    if (pw) {
-      const bool big = w.v2 == 4;
+    const WSel sel = select_wgrad(w, ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0);
+    if (sel.family == WF_PWDMA) {
+      const bool big = sel.id == 4;
       const size_t lds = (size_t)2 * (big ? 256 : 128) * 64 * sizeof(float);
       if (big) {
         auto kern = conv_wgrad_pw_kernel<2, 2>;
@@ -1433,41 +1499,39 @@ int wgrad_run(const coclr_conv_desc* d, const float* x, const float* dy, const W
       }
       COCLR_LAUNCH_CHECK();
       rc = 0;
+    } else if (sel.family == WF_STEM) {
+      if (bn) {
+        auto kern = conv_wgrad_stem_kernel<7, 7, 3, 20, true>;
+        static std::atomic<uint64_t> attr_done{0};
+        COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
+        hipLaunchKernelGGL(kern, dim3(w.S2, 1, w.mt2), dim3(512), stem_bna_lds(w), stream, a);
+      } else {
+        auto kern = conv_wgrad_stem_kernel<7, 7, 3, 20>;
+        static std::atomic<uint64_t> attr_done{0};
+        COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
+        hipLaunchKernelGGL(kern, dim3(w.S2, 1, w.mt2), dim3(512), w.lds2, stream, a);
+      }
+      COCLR_LAUNCH_CHECK();
+      rc = 0;
     } else
-    switch (w.v2) {
-      case 1: rc = pch <= 2 ? launch_wgrad2<1, 3, 3, 1, 1, 2>(a, w, stream)
-                            : launch_wgrad2<1, 3, 3, 1, 1, 3>(a, w, stream); break;
+    switch (sel.id * 8 + sel.pch) {
+      case 1 * 8 + 2: rc = launch_wgrad2<1, 3, 3, 1, 1, 2>(a, w, stream); break;
+      case 1 * 8 + 3: rc = launch_wgrad2<1, 3, 3, 1, 1, 3>(a, w, stream); break;
       // the temporal forms are loader-bound with four loader waves (3 or 4 MFMAs per four LDS-DMA
       // pieces): EIGHT loader waves beside the four matrix waves (768 threads; 48-64 accumulator
       // registers leave room for three waves per SIMD): direct 1.20 -> 1.05 ms, Winograd 1.07 ->
       // 0.90 ms on Conv_2c.conv2.  (7,1,1) (112 accumulators) and (1,3,3) (144) keep four.
-      case 2: rc = launch_wgrad2<3, 1, 1, 1, 1, 2, false, 8>(a, w, stream); break;
-      case 3: rc = launch_wgrad2<7, 1, 1, 1, 1, 4>(a, w, stream); break;
-      case 4: rc = launch_wgrad2<1, 1, 1, 2, 2, 2>(a, w, stream); break;
-      case 5: rc = launch_wgrad2<1, 1, 1, 1, 1, 2>(a, w, stream); break;
-      case 6: rc = launch_wgrad2<4, 1, 1, 1, 1, 2, true, 8>(a, w, stream); break;
-      case 7: rc = pch <= 2 ? launch_wgrad2<1, 3, 3, 1, 1, 2, false, 4, true>(a, w, stream)
-                            : launch_wgrad2<1, 3, 3, 1, 1, 3, false, 4, true>(a, w, stream); break;
-      case 9: {
-        if (bn) {
-          auto kern = conv_wgrad_stem_kernel<7, 7, 3, 20, true>;
-          static std::atomic<uint64_t> attr_done{0};
-          COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
-          hipLaunchKernelGGL(kern, dim3(w.S2, 1, w.mt2), dim3(512), stem_bna_lds(w), stream, a);
-        } else {
-          auto kern = conv_wgrad_stem_kernel<7, 7, 3, 20>;
-          static std::atomic<uint64_t> attr_done{0};
-          COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
-          hipLaunchKernelGGL(kern, dim3(w.S2, 1, w.mt2), dim3(512), w.lds2, stream, a);
-        }
-        COCLR_LAUNCH_CHECK();
-        rc = 0;
-        break;
-      }
+      case 2 * 8 + 2: rc = launch_wgrad2<3, 1, 1, 1, 1, 2, false, 8>(a, w, stream); break;
+      case 3 * 8 + 4: rc = launch_wgrad2<7, 1, 1, 1, 1, 4>(a, w, stream); break;
+      case 4 * 8 + 2: rc = launch_wgrad2<1, 1, 1, 2, 2, 2>(a, w, stream); break;
+      case 5 * 8 + 2: rc = launch_wgrad2<1, 1, 1, 1, 1, 2>(a, w, stream); break;
+      case 6 * 8 + 2: rc = launch_wgrad2<4, 1, 1, 1, 1, 2, true, 8>(a, w, stream); break;
+      case 7 * 8 + 2: rc = launch_wgrad2<1, 3, 3, 1, 1, 2, false, 4, true>(a, w, stream); break;
+      case 7 * 8 + 3: rc = launch_wgrad2<1, 3, 3, 1, 1, 3, false, 4, true>(a, w, stream); break;
       default: rc = COCLR_EINVAL;
     }
     if (rc) return rc;
-    S_used = w.S2 * (w.v2 == 9 ? 4 : (w.v2 == 7 ? 2 : 1));
+    S_used = w.S2 * sel.slices;
   } else {
     const ConvPlan& p = w.p;
     WgradArgs a;
@@ -1484,12 +1548,16 @@ int wgrad_run(const coclr_conv_desc* d, const float* x, const float* dy, const W
     a.WT = p.WT; a.WH = p.WH; a.WW = p.WW; a.plane1 = p.plane1; a.plane = p.plane;
     a.planeP = w.planeP; a.pch = w.pch;
     a.ntiles = p.ntiles; a.S = w.S; a.jtiles = w.jtiles; a.mtiles = w.mtiles;
-    const bool pw = w.BJ == 64;
-    switch (w.variant) {
-      case 0: rc = pw ? launch_wgrad<64, 2>(a, w, stream) : launch_wgrad<128, 2>(a, w, stream); break;
-      case 1: rc = pw ? launch_wgrad<64, 4>(a, w, stream) : launch_wgrad<128, 4>(a, w, stream); break;
-      case 2: rc = pw ? launch_wgrad<64, 8>(a, w, stream) : launch_wgrad<128, 8>(a, w, stream); break;
-      case 3: rc = pw ? launch_wgrad<64, 20>(a, w, stream) : launch_wgrad<128, 20>(a, w, stream); break;
+    const WSel sel = select_wgrad(w, false);
+    switch (sel.bj * 32 + sel.pch) {
+      case 64 * 32 + 2: rc = launch_wgrad<64, 2>(a, w, stream); break;
+      case 64 * 32 + 4: rc = launch_wgrad<64, 4>(a, w, stream); break;
+      case 64 * 32 + 8: rc = launch_wgrad<64, 8>(a, w, stream); break;
+      case 64 * 32 + 20: rc = launch_wgrad<64, 20>(a, w, stream); break;
+      case 128 * 32 + 2: rc = launch_wgrad<128, 2>(a, w, stream); break;
+      case 128 * 32 + 4: rc = launch_wgrad<128, 4>(a, w, stream); break;
+      case 128 * 32 + 8: rc = launch_wgrad<128, 8>(a, w, stream); break;
+      case 128 * 32 + 20: rc = launch_wgrad<128, 20>(a, w, stream); break;
       default: rc = COCLR_EINVAL;
     }
     if (rc) return rc;

@@ -280,6 +280,20 @@ class ConvGeom:
             v = self._cache["wgws"] = out.value
         return v
 
+    def wgrad_plan(self, aligned=True, x_nstride=None, y_nstride=None):
+        """What conv_wgrad would launch for this geometry, from the launcher's own planner (nothing is launched).
+        aligned: x and dy both 16-byte aligned (the pointwise 16-byte-DMA kernels need it); x_nstride / y_nstride:
+        the operands' sample strides (default: dense tensors)."""
+        d = ConvDesc.from_buffer_copy(self.desc)
+        d.x_nstride = x_nstride or self.Cin * self.idim[0] * self.idim[1] * self.idim[2]
+        d.y_nstride = y_nstride or self.Cout * self.odim[0] * self.odim[1] * self.odim[2]
+        out = (C.c_int32 * 16)()
+        _lib.check(_L().coclr_conv3d_wgrad_plan(C.byref(d), int(bool(aligned)), out), "conv3d_wgrad_plan", self)
+        family = ("gen1", "wave", "stem", "pwdma")[out[0]]
+        return dict(family=family, id=out[1], pch=out[2], bj=out[3], split=out[4], slices=out[5], ct=out[6],
+                    mt=out[7], lTW=out[8], lTH=out[9], lTT=out[10], lTN=out[11], ntiles=out[12],
+                    tile_order=bool(out[13]), bn=bool(out[14]), rebox=bool(out[15]))
+
     def __repr__(self):
         return "ConvGeom(N=%d, %d->%d, in=%s, out=%s, k=%s, s=%s, p=%s, d=%s)" % (
             self.N, self.Cin, self.Cout, self.idim, self.odim, self.k, self.s, self.p, self.d)

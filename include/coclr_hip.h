@@ -172,6 +172,26 @@ int coclr_conv3d_bwd_sums_ok(const coclr_conv_desc* d, int* ok);
 /* Split-K workspace (fp32 elements) for coclr_conv3d_wgrad. */
 int coclr_conv3d_wgrad_workspace(const coclr_conv_desc* d, int64_t* elems);
 
+/* What coclr_conv3d_wgrad would launch for this descriptor; launches nothing.  Comes from the launcher's own
+ * planner and kernel selection, so a test can assert which instantiation a geometry reaches.
+ * operands_16B_aligned: whether x and dy will both be 16-byte aligned (the launcher checks the pointers; the
+ * 16-byte-DMA pointwise kernels need it).  out:
+ *   [0] family: 0 first-generation kernel, 1 wave-specialised kernel, 2 (1,7,7) stem kernel,
+ *               3 16-byte-DMA pointwise kernel
+ *   [1] id: wave-specialised 1 (1,3,3), 2 (3,1,1), 3 (7,1,1), 4 / 5 pointwise 128 x 128 / 64 x 64 tile,
+ *           6 (3,1,1) in the F(2,3) domain, 7 (1,3,3) in the F(2x2,3x3) domain; pointwise-DMA 4 big / 5 small;
+ *           stem 9; first generation 0
+ *   [2] template PCH (64-element window chunks per channel; 0: the kernel has none)
+ *   [3] template BJ (first generation only, else 0)
+ *   [4] split count   [5] workspace slices per split (1, 2 or 4)
+ *   [6] ct: input-channel (first generation: j) tiles   [7] mt: output-channel tiles
+ *   [8..11] box log2 extents lTW, lTH, lTT, lTN   [12] ntiles (boxes)
+ *   [13] workgroup order of the default rule: 1 tile-fastest, 0 split-fastest (COCLR_WGRAD_ORDER=split|tile
+ *        overrides it per call; only families 1 and 3 have an order)
+ *   [14] 1 if coclr_conv3d_wgrad_bn has a kernel for it (the rule of coclr_conv3d_wgrad_bn_ok)
+ *   [15] 1 if id 7 re-cut its 32 x 2 boxes (34 x 4 windows) to 16 x 4 (18 x 6) */
+int coclr_conv3d_wgrad_plan(const coclr_conv_desc* d, int operands_16B_aligned, int32_t out[16]);
+
 /* dw[co][ci][tap] (+)= sum_{n,o} dy[n][co][o] * x[n][ci][o*s - p + tap]: the wgrad
  * half of aten::convolution_backward.  dw is addressed as
  * dw[co*w_co_stride + ci*w_ci_stride + tap_base + tap]. */
