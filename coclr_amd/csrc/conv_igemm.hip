@@ -80,7 +80,7 @@ struct ConvArgs {
   int xcd;                // remap workgroup ids so that an XCD owns contiguous tiles
   int To_full;            // F(4,3) / F(2,4) temporal kernels: output frames of the launch (a.To counts groups)
   // the input is the raw output of a BatchNorm(+ReLU) unit: x' = max?(x * in_scale[ci] + in_shift[ci], 0) is
-  // applied while the kernel reads (conv_poly7_body INAFF), zero padding stays zero
+  // applied while the kernel reads (conv_wino_tf_body INAFF), zero padding stays zero
   const float* in_scale;
   const float* in_shift;
   int in_relu;
@@ -918,31 +918,23 @@ conv_wino_t_pair_kernel(const ConvArgs a0, const ConvArgs a1, const int nb0) {
   else conv_wino_t_body<CC, BM, BNP, PCH, XV4>(a1, (int)blockIdx.x - nb0, (int)gridDim.x - nb0);
 }
 
-struct PairSlot;
-template <int CC, int BM, int BNP, int PCH, bool XV4, int OCC>
-int wino_t_single(const ConvArgs& a, long blocks, size_t lds, hipStream_t stream) {
-  auto kern = conv_wino_t_kernel<CC, BM, BNP, PCH, XV4, OCC>;
-  static std::atomic<uint64_t> attr_done{0};
-  COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, stream, a);
-  COCLR_LAUNCH_CHECK();
-  return 0;
-}
-
-template <int CC, int BM, int BNP, int PCH, bool XV4, int OCC>
-int wino_t_pair(const ConvArgs& a0, const ConvArgs& a1, long b0, long b1, size_t lds, hipStream_t stream) {
-  auto kern = conv_wino_t_pair_kernel<CC, BM, BNP, PCH, XV4, OCC>;
-  static std::atomic<uint64_t> attr_done{0};
-  COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
-  hipLaunchKernelGGL(kern, dim3((unsigned)(b0 + b1)), dim3(256), lds, stream, a0, a1, (int)b0);
-  COCLR_LAUNCH_CHECK();
-  return 0;
-}
-
-template <int CC, int BM, int BNP, int PCH, bool XV4, int OCC = 1>
-int launch_wino_t(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot = nullptr);
-
 // ------------------------------------------------------------------------------------
+// The temporal Winograd family: one kernel body, conv_wino_tf_body, over three FORMS.  Same structure as
+// conv_wino_t_body: a (TAPS,1,1) stencil with temporal stride STEP over output "positions" (groups of FO output
+// frames), TAPS accumulator sets per 32x32 block, the epilogue emits FO frames per position.  A form gives
+//     TAPS           channel contractions (accumulator sets) = window frames read per lane
+//     FO             output frames per position
+//     STEP, ORG      window frames per position and the window origin: frame  position * STEP - ORG
+//     input()        d[TAPS] window frames -> D[TAPS] transformed operands
+//     output()       element i of the m[TAPS] contractions -> v[FO] output frames
+//     LATTICE        the destination is a lattice along T (a.yst, a.yot) and the frame count arrives in a.To_full;
+//                    without it the frame count arrives in a.yst and the frame pitch is 1
+//     PAIR           a two-problem kernel exists (coclr_conv3d_fwd_multi)
+// The arithmetic of the transforms (fmaf nesting, parentheses) and the order in which the epilogue adds frames
+// into the statistics are part of the result: outputs and BatchNorm sums are held bit for bit.  output() reads the
+// accumulators in place for the same reason: staged through a scalar array the epilogue vectorises differently,
+// and which of its multiply-adds get fused changes with it.
+
 // Temporal (3,1,1) stride-1 convolutions through Winograd F(4,3) along T (coclr_conv_desc.algo = 2).
 //
 // A QUAD of output frames (4p .. 4p+3) needs input frames d0..d5 = 4p-1 .. 4p+4 and SIX channel
@@ -957,659 +949,49 @@ int launch_wino_t(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot =
 // rounding error of the direct fp32 convolution (L2 7e-7 against 2e-7 at 192 channels; F(2,3): 2.7e-7) --
 // three orders of magnitude inside the 1e-3 the path is held to.
 //
-// Same structure as conv_wino_t_body: a (6,1,1) stencil with temporal stride 4 over "quad positions", six
-// accumulator sets per 32x32 block (96 registers: three workgroups per CU), the epilogue emits four frames.
+// A (6,1,1) stencil with temporal stride 4 over "quad positions", six accumulator sets per 32x32 block
+// (96 registers: three workgroups per CU), the epilogue emits four frames.
 // 2x fewer MFMAs than the direct form, 1.33x fewer than F(2,3).
-template <int CC, int BM, int BNQ, int PCH, bool XV4>
-__device__ __forceinline__ void conv_wino_t4_body(const ConvArgs& a, int bid, const int nblocks) {
-  constexpr int TAPS = 6;
-  constexpr int WM = 2, WN = 2;
-  constexpr int MF = BM / (WM * 32), NF = BNQ / (WN * 32);
-  constexpr int RPP = 256 / BM;
-  constexpr int WPIECES = TAPS * CC / RPP;
-  static_assert(CC % RPP == 0 && CC % 4 == 0, "chunk shape");
-  constexpr int W_FLOATS = TAPS * CC * BM;
-
-  extern __shared__ __align__(16) float smem[];
-  const int planeS = a.planeS;
-  const int stage_floats = W_FLOATS + CC * planeS;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int half = lane >> 5, l31 = lane & 31;
-  const int wm = wave >> 1, wn = wave & 1;
-
-  if (a.xcd) {                        // XCD-aware tile ids (see conv_igemm_body)
-    const int per = nblocks >> 3;
-    if (bid < (per << 3)) bid = (bid & 7) * per + (bid >> 3);
+struct WinoF43 {
+  static constexpr int TAPS = 6, FO = 4, STEP = 4, ORG = 1;
+  static constexpr bool LATTICE = true, PAIR = true;
+  static __device__ __forceinline__ void input(const float (&d)[TAPS], float (&D)[TAPS]) {
+    const float d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3], d4 = d[4], d5 = d[5];
+    const float t1 = fmaf(-4.f, d2, d4), t2 = fmaf(-4.f, d1, d3);
+    const float u1 = d4 - d2, v = d3 - d1;
+    D[0] = fmaf(4.f, d0, fmaf(-5.f, d2, d4)); D[1] = t1 + t2; D[2] = t1 - t2; D[3] = fmaf(2.f, v, u1);
+    D[4] = fmaf(-2.f, v, u1); D[5] = fmaf(4.f, d1, fmaf(-5.f, d3, d5));
   }
-  const int mt = bid % a.mtiles;
-  const int ntile = bid / a.mtiles;
-  int r = ntile;
-  const int bw_ = r % a.nbw; r /= a.nbw;
-  const int bh_ = r % a.nbh; r /= a.nbh;
-  const int bt_ = r % a.nbt; r /= a.nbt;
-  const int n0 = r << a.lTN;
-  const int ow0 = bw_ << a.lTW, oh0 = bh_ << a.lTH, ot0 = bt_ << a.lTT;   // ot0: QUAD index
-  const int cout0 = mt * BM;
-  const int vt0 = ot0 * 4 - 1, vh0 = oh0, vw0 = ow0;                      // window origin
-  const int plane = a.plane;
-
-  const float* xbase = a.x + (long)n0 * a.x_nstride;
-  const __amdgpu_buffer_rsrc_t rx =
-      __builtin_amdgcn_make_buffer_rsrc((void*)xbase, 0, BUF_RANGE, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rw =
-      __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, BUF_RANGE, 0x00020000);
-  float* ybase = a.y + (long)n0 * a.y_nstride;
-  const __amdgpu_buffer_rsrc_t ry =
-      __builtin_amdgcn_make_buffer_rsrc((void*)ybase, 0, BUF_RANGE, 0x00020000);
-
-  unsigned goff[XV4 ? 1 : PCH];
-  if (!XV4) {
-    const int hw = a.WH * a.WW;
-#pragma unroll
-    for (int j = 0; j < PCH; ++j) {
-      const int e = j * 64 + lane;
-      unsigned off = OOB;
-      if (e < plane) {
-        const int wn_ = fdiv(e, a.inv_plane1);
-        int q = e - wn_ * a.plane1;
-        const int wt = fdiv(q, a.inv_hw); q -= wt * hw;
-        const int wh = fdiv(q, a.inv_ww);
-        const int ww = q - wh * a.WW;
-        const int n = n0 + wn_;
-        const int it = vt0 + wt, ih = vh0 + wh, iw = vw0 + ww;
-        if (n < a.N && it >= 0 && it < a.Ti && ih < a.Hi && iw < a.Wi)
-          off = (unsigned)(((long)wn_ * a.x_nstride + ((long)it * a.Hi + ih) * a.Wi + iw) * 4);
-      }
-      goff[j] = off;
-    }
+  static __device__ __forceinline__ void output(const f32x16 (&m)[TAPS], int i, float (&v)[FO]) {
+    const float m0 = m[0][i], m1 = m[1][i], m2 = m[2][i], m3 = m[3][i], m4 = m[4][i], m5 = m[5][i];
+    const float sa = m1 + m2, sb = m1 - m2, sc_ = m3 + m4, sd = m3 - m4;
+    v[0] = (m0 + sa) + sc_; v[1] = fmaf(2.f, sd, sb); v[2] = fmaf(4.f, sc_, sa); v[3] = fmaf(8.f, sd, sb) + m5;
   }
-  const unsigned wvoff = (unsigned)((((lane * 4) / BM) * a.CoutP + (lane * 4) % BM) * 4);
+};
 
-  // XV4: 16-byte DMA of the halo-free window, 1 KiB pieces across channel rows (see conv_wino_t_body)
-  constexpr int PV = (CC * PCH * 64 / 256 + 3) / 4;
-  unsigned xvoff[PV];
-  int xvc[PV];
-  if (XV4) {
-#pragma unroll
-    for (int jj = 0; jj < PV; ++jj) {
-      const int flat = (wave + 4 * jj) * 256 + lane * 4;
-      const int c = flat / plane, e = flat - c * plane;
-      unsigned off = OOB;
-      if (c < CC) {
-        const int wn_ = fdiv(e, a.inv_plane1);
-        const int q = e - wn_ * a.plane1;
-        const int wt = fdiv(q, a.inv_ww);              // WH == 1 here
-        const int ww = q - wt * a.WW;
-        const int n = n0 + wn_, it = vt0 + wt, iw = vw0 + ww;
-        if (n < a.N && it >= 0 && it < a.Ti && iw < a.Wi)
-          off = (unsigned)(((long)wn_ * a.x_nstride + (long)it * a.Wi + iw + (long)c * a.x_cstride) * 4);
-      }
-      xvoff[jj] = off;
-      xvc[jj] = c;
-    }
-  }
-
-  // quad position of this lane: window offset of its frame d0 (d1..d5 follow at +WH*WW each)
-  int lanebase[NF];
-  const int fstride = a.WH * a.WW;
-#pragma unroll
-  for (int nf = 0; nf < NF; ++nf) {
-    const int p = wn * (BNQ / WN) + nf * 32 + l31;
-    const int tw = p & ((1 << a.lTW) - 1);
-    const int th = (p >> a.lTW) & ((1 << a.lTH) - 1);
-    const int tt = (p >> (a.lTW + a.lTH)) & ((1 << a.lTT) - 1);
-    const int tn = p >> (a.lTW + a.lTH + a.lTT);
-    lanebase[nf] = W_FLOATS + tn * a.plane1 + ((tt * 4) * a.WH + th) * a.WW + tw + half * planeS;
-  }
-  const int abase = half * BM + wm * (BM / WM) + l31;
-
-  f32x16 acc[MF][NF][6];
-#pragma unroll
-  for (int mf = 0; mf < MF; ++mf)
-#pragma unroll
-    for (int nf = 0; nf < NF; ++nf)
-#pragma unroll
-      for (int t = 0; t < 6; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[mf][nf][t][i] = 0.f;
-
-  auto stage = [&](int cin0, float* sbase) {
-    for (int p = wave; p < WPIECES; p += 4) {
-      const int row0 = p * RPP;
-      const int tap = row0 / CC, c0 = row0 % CC;
-      const unsigned soff = (unsigned)((((long)tap * a.CinP + cin0 + c0) * a.CoutP + cout0) * 4);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, LDS_PTR(sbase + p * 256), 16, wvoff, soff, 0, 0);
-    }
-    float* xs = sbase + W_FLOATS;
-    if (XV4) {
-      const unsigned soff = (unsigned)cin0 * (unsigned)a.x_cstride * 4u;
-#pragma unroll
-      for (int jj = 0; jj < PV; ++jj) {
-        const int j = wave + 4 * jj;
-        if (j * 256 < CC * plane && xvc[jj] < CC) {   // exec-masked: lanes past the image write nothing
-          const unsigned vo = cin0 + xvc[jj] < a.Cin ? xvoff[jj] : OOB;
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, LDS_PTR(xs + j * 256), 16, vo, soff, 0, 0);
-        }
-      }
-    } else
-#pragma unroll
-    for (int ci = 0; ci < CC / 4; ++ci) {
-      const int c = ci * 4 + wave;
-      const int cin = cin0 + c;
-      if (cin < a.Cin) {
-        const unsigned soff = (unsigned)cin * (unsigned)a.x_cstride * 4u;
-#pragma unroll
-        for (int j = 0; j < PCH; ++j)
-          if (j * 64 < plane)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, LDS_PTR(xs + c * planeS + j * 64), 4,
-                                                     goff[XV4 ? 0 : j], soff, 0, 0);
-      } else {
-#pragma unroll
-        for (int j = 0; j < PCH; ++j)
-          if (j * 64 < plane) xs[c * planeS + j * 64 + lane] = 0.f;
-      }
-    }
-  };
-
-  const int nchunks = a.nchunks;
-  stage(0, smem);
-  for (int ch = 0; ch < nchunks; ++ch) {
-    const float* cur = smem + (ch & 1) * stage_floats;
-    __builtin_amdgcn_s_waitcnt(0x0f70);
-    __syncthreads();
-    if (ch + 1 < nchunks) stage((ch + 1) * CC, smem + ((ch + 1) & 1) * stage_floats);
-
-    constexpr int QS = CC / 2;
-    // step q: channel pair (2q, 2q+1); operands of step q+1 are fetched under the MFMAs of q
-    auto fetch = [&](int q, float (&av)[MF][6], float (&dv)[NF][6]) {
-#pragma unroll
-      for (int t = 0; t < 6; ++t)
-#pragma unroll
-        for (int mf = 0; mf < MF; ++mf) av[mf][t] = cur[abase + (t * CC + 2 * q) * BM + mf * 32];
-#pragma unroll
-      for (int nf = 0; nf < NF; ++nf)
-#pragma unroll
-        for (int k = 0; k < 6; ++k) dv[nf][k] = cur[lanebase[nf] + k * fstride + 2 * q * planeS];
-    };
-    float av[2][MF][6], dv[2][NF][6];
-    fetch(0, av[0], dv[0]);
-#pragma unroll
-    for (int q = 0; q < QS; ++q) {
-      if (q + 1 < QS) fetch(q + 1, av[(q + 1) & 1], dv[(q + 1) & 1]);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int nf = 0; nf < NF; ++nf) {
-        const float d0 = dv[q & 1][nf][0], d1 = dv[q & 1][nf][1], d2 = dv[q & 1][nf][2],
-                    d3 = dv[q & 1][nf][3], d4 = dv[q & 1][nf][4], d5 = dv[q & 1][nf][5];
-        const float t1 = fmaf(-4.f, d2, d4), t2 = fmaf(-4.f, d1, d3);
-        const float u1 = d4 - d2, v = d3 - d1;
-        const float D[6] = {fmaf(4.f, d0, fmaf(-5.f, d2, d4)), t1 + t2, t1 - t2, fmaf(2.f, v, u1),
-                            fmaf(-2.f, v, u1), fmaf(4.f, d1, fmaf(-5.f, d3, d5))};
-#pragma unroll
-        for (int t = 0; t < 6; ++t)
-#pragma unroll
-          for (int mf = 0; mf < MF; ++mf)
-            acc[mf][nf][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q & 1][mf][t], D[t],
-                                                                  acc[mf][nf][t], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-
-  // ---- epilogue: four frames per quad position ---------------------------------------------------
-  unsigned yvoff[NF];
-  int nvalid[NF];                 // valid frames of the quad (0 = position outside the tensor)
-  const unsigned half_rows = (unsigned)half * 4u * (unsigned)a.y_cstride * 4u;
-  // destination lattice along T (one phase of a strided data gradient): output frame o lands on frame
-  // o * yst + yot of the destination tensor; dense: yst = 1, yot = 0
-  const unsigned frame_bytes = (unsigned)(a.yHf * a.yWf) * 4u * (unsigned)a.yst;
-  const int To_full = a.To_full;
-#pragma unroll
-  for (int nf = 0; nf < NF; ++nf) {
-    const int p = wn * (BNQ / WN) + nf * 32 + l31;
-    const int tw = p & ((1 << a.lTW) - 1);
-    const int th = (p >> a.lTW) & ((1 << a.lTH) - 1);
-    const int tt = (p >> (a.lTW + a.lTH)) & ((1 << a.lTT) - 1);
-    const int tn = p >> (a.lTW + a.lTH + a.lTT);
-    const int n = n0 + tn, tp = ot0 + tt, oh = oh0 + th, ow = ow0 + tw;
-    const bool ok = n < a.N && 4 * tp < To_full && oh < a.Ho && ow < a.Wo;
-    int nv = To_full - 4 * tp;
-    nvalid[nf] = ok ? (nv > 4 ? 4 : nv) : 0;
-    const long e = (long)tn * a.y_nstride + ((long)(4 * tp * a.yst + a.yot) * a.yHf + oh) * a.yWf + ow;
-    yvoff[nf] = ok ? (unsigned)(e * 4) + half_rows : OOB;
-  }
-
-  const bool want_stats = a.stats != nullptr;
-  float* red = smem;
-  if (want_stats) __syncthreads();
-
-  auto emit = [&](auto acc_tag, auto fancy_tag) {       // FANCY: see conv_igemm_body
-    constexpr bool ACCUM = decltype(acc_tag)::value;
-    constexpr bool FANCY = decltype(fancy_tag)::value;
-#pragma unroll
-    for (int mf = 0; mf < MF; ++mf) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int rowu = wm * (BM / WM) + mf * 32 + (i & 3) + 8 * (i >> 2);
-        const int ml = rowu + 4 * half;
-        const int co = cout0 + ml;
-        const bool cok = co < a.Cout;
-        const unsigned soff = (unsigned)(cout0 + rowu) * (unsigned)a.y_cstride * 4u;
-        float s = 0.f, ss = 0.f;
-        float bia = 0.f, sc = 1.f, sf = 0.f;
-        if (FANCY) {
-          if (a.bias && cok) bia = a.bias[co];
-          if (a.ep_scale && cok) { sc = a.ep_scale[co]; sf = a.ep_shift[co]; }
-        }
-#pragma unroll
-        for (int nf = 0; nf < NF; ++nf) {
-          const float m0 = acc[mf][nf][0][i], m1 = acc[mf][nf][1][i], m2 = acc[mf][nf][2][i],
-                      m3 = acc[mf][nf][3][i], m4 = acc[mf][nf][4][i], m5 = acc[mf][nf][5][i];
-          const float sa = m1 + m2, sb = m1 - m2, sc_ = m3 + m4, sd = m3 - m4;
-          float v[4] = {(m0 + sa) + sc_, fmaf(2.f, sd, sb), fmaf(4.f, sc_, sa), fmaf(8.f, sd, sb) + m5};
-#pragma unroll
-          for (int f = 0; f < 4; ++f) {
-            const bool fv = f < nvalid[nf];
-            const unsigned vo = (cok && fv) ? yvoff[nf] + (unsigned)f * frame_bytes : OOB;
-            if (ACCUM) v[f] += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ry, vo, soff, 0));
-            const float u = fv ? v[f] : 0.f;
-            s += u; ss += u * u;
-            if (FANCY) {
-              v[f] = (v[f] + bia) * sc + sf;
-              if (a.relu) v[f] = fmaxf(v[f], 0.f);
-            }
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[f]), ry, vo, soff, 0);
-          }
-        }
-        if (want_stats) {
-          s = row16_sum(s);
-          ss = row16_sum(ss);
-          if ((lane & 15) == 0) {
-            const int slot = wn * 2 + (l31 >> 4);
-            red[(slot * BM + ml) * 2 + 0] = s;
-            red[(slot * BM + ml) * 2 + 1] = ss;
-          }
-        }
-      }
-    }
-  };
-  const bool fancy = a.bias || a.ep_scale || a.relu;
-  if (fancy) { if (a.accumulate) emit(std::true_type{}, std::true_type{}); else emit(std::false_type{}, std::true_type{}); }
-  else if (a.accumulate) emit(std::true_type{}, std::false_type{});
-  else emit(std::false_type{}, std::false_type{});
-
-  if (want_stats) {
-    __syncthreads();
-    if (tid < BM) {
-      const int co = cout0 + tid;
-      if (co < a.Cout) {
-        float s = 0.f, ss = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          s += red[(k * BM + tid) * 2];
-          ss += red[(k * BM + tid) * 2 + 1];
-        }
-        a.stats[(long)co * a.ntiles + ntile] = s;
-        a.stats[((long)a.Cout + co) * a.ntiles + ntile] = ss;
-      }
-    }
-  }
-}
-
-template <int CC, int BM, int BNQ, int PCH, bool XV4, int OCC = 1>
-__global__ void __launch_bounds__(256, OCC)
-conv_wino_t4_kernel(const ConvArgs a) {
-  conv_wino_t4_body<CC, BM, BNQ, PCH, XV4>(a, (int)blockIdx.x, (int)gridDim.x);
-}
-
-// two problems in one launch, see conv_igemm_pair_kernel
-template <int CC, int BM, int BNQ, int PCH, bool XV4, int OCC = 1>
-__global__ void __launch_bounds__(256, OCC)
-conv_wino_t4_pair_kernel(const ConvArgs a0, const ConvArgs a1, const int nb0) {
-  if ((int)blockIdx.x < nb0) conv_wino_t4_body<CC, BM, BNQ, PCH, XV4>(a0, (int)blockIdx.x, nb0);
-  else conv_wino_t4_body<CC, BM, BNQ, PCH, XV4>(a1, (int)blockIdx.x - nb0, (int)gridDim.x - nb0);
-}
-
-template <int CC, int BM, int BNQ, int PCH, bool XV4, int OCC>
-int wino_t4_single(const ConvArgs& a, long blocks, size_t lds, hipStream_t stream) {
-  auto kern = conv_wino_t4_kernel<CC, BM, BNQ, PCH, XV4, OCC>;
-  static std::atomic<uint64_t> attr_done{0};
-  COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, stream, a);
-  COCLR_LAUNCH_CHECK();
-  return 0;
-}
-
-template <int CC, int BM, int BNQ, int PCH, bool XV4, int OCC>
-int wino_t4_pair(const ConvArgs& a0, const ConvArgs& a1, long b0, long b1, size_t lds, hipStream_t stream) {
-  auto kern = conv_wino_t4_pair_kernel<CC, BM, BNQ, PCH, XV4, OCC>;
-  static std::atomic<uint64_t> attr_done{0};
-  COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
-  hipLaunchKernelGGL(kern, dim3((unsigned)(b0 + b1)), dim3(256), lds, stream, a0, a1, (int)b0);
-  COCLR_LAUNCH_CHECK();
-  return 0;
-}
-
-template <int CC, int BM, int BNQ, int PCH, bool XV4, int OCC = 1>
-int launch_wino_t4(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot = nullptr);
-
-// ------------------------------------------------------------------------------------
 // A 4-tap temporal stencil (4,1,1) / stride 1 / pad (1,0,0) through Winograd F(2,4) (coclr_conv_desc.algo = 2
 // on that stencil): the odd phase of the strided stem conv's data gradient (ConvGeom.dgrad_phases).  A PAIR of
 // output frames (2p, 2p+1) needs input frames o0..o4 = 2p-1 .. 2p+3 and FIVE channel contractions instead of
-// eight (points 0, 1, -1, 2, inf; the same transform as the even-tap half of conv_poly7_body):
+// eight (points 0, 1, -1, 2, inf; the same transform as the even-tap half of StemPoly7):
 //     O = (2(o0-o2)+(o3-o1), -2o1-o2+o3, 2o1-3o2+o3, o3-o1, 2(o1-o3)+(o4-o2))
 //     U = (b0/2, -(b0+b1+b2+b3)/2, (-b0+b1-b2+b3)/6, (b0+2b1+4b2+8b3)/6, b3)
 //     y[2p] = n0+n1+n2+n3        y[2p+1] = n1-n2+2n3+n4
-// Writes through the destination lattice along T like conv_wino_t4_body.
-template <int CC, int BM, int BNQ, int PCH, bool XV4>
-__device__ __forceinline__ void conv_wino_t24_body(const ConvArgs& a, int bid, const int nblocks) {
-  constexpr int TAPS = 5;
-  constexpr int WM = 2, WN = 2;
-  constexpr int MF = BM / (WM * 32), NF = BNQ / (WN * 32);
-  constexpr int RPP = 256 / BM;
-  constexpr int WPIECES = TAPS * CC / RPP;
-  static_assert(CC % RPP == 0 && CC % 4 == 0, "chunk shape");
-  constexpr int W_FLOATS = TAPS * CC * BM;
-
-  extern __shared__ __align__(16) float smem[];
-  const int planeS = a.planeS;
-  const int stage_floats = W_FLOATS + CC * planeS;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int half = lane >> 5, l31 = lane & 31;
-  const int wm = wave >> 1, wn = wave & 1;
-
-  if (a.xcd) {                        // XCD-aware tile ids (see conv_igemm_body)
-    const int per = nblocks >> 3;
-    if (bid < (per << 3)) bid = (bid & 7) * per + (bid >> 3);
+// Writes through the destination lattice along T like WinoF43.
+struct WinoF24 {
+  static constexpr int TAPS = 5, FO = 2, STEP = 2, ORG = 1;
+  static constexpr bool LATTICE = true, PAIR = false;
+  static __device__ __forceinline__ void input(const float (&d)[TAPS], float (&D)[TAPS]) {
+    const float o0 = d[0], o1 = d[1], o2 = d[2], o3 = d[3], o4 = d[4];
+    const float oa = o3 - o2, o31 = o3 - o1;
+    D[0] = fmaf(2.f, o0 - o2, o31); D[1] = fmaf(-2.f, o1, oa); D[2] = fmaf(2.f, o1, fmaf(-2.f, o2, oa)); D[3] = o31;
+    D[4] = fmaf(-2.f, o31, o4 - o2);
   }
-  const int mt = bid % a.mtiles;
-  const int ntile = bid / a.mtiles;
-  int r = ntile;
-  const int bw_ = r % a.nbw; r /= a.nbw;
-  const int bh_ = r % a.nbh; r /= a.nbh;
-  const int bt_ = r % a.nbt; r /= a.nbt;
-  const int n0 = r << a.lTN;
-  const int ow0 = bw_ << a.lTW, oh0 = bh_ << a.lTH, ot0 = bt_ << a.lTT;   // ot0: PAIR index
-  const int cout0 = mt * BM;
-  const int vt0 = ot0 * 2 - 1, vh0 = oh0, vw0 = ow0;                      // window origin
-  const int plane = a.plane;
-
-  const float* xbase = a.x + (long)n0 * a.x_nstride;
-  const __amdgpu_buffer_rsrc_t rx =
-      __builtin_amdgcn_make_buffer_rsrc((void*)xbase, 0, BUF_RANGE, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rw =
-      __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, BUF_RANGE, 0x00020000);
-  float* ybase = a.y + (long)n0 * a.y_nstride;
-  const __amdgpu_buffer_rsrc_t ry =
-      __builtin_amdgcn_make_buffer_rsrc((void*)ybase, 0, BUF_RANGE, 0x00020000);
-
-  unsigned goff[XV4 ? 1 : PCH];
-  if (!XV4) {
-    const int hw = a.WH * a.WW;
-#pragma unroll
-    for (int j = 0; j < PCH; ++j) {
-      const int e = j * 64 + lane;
-      unsigned off = OOB;
-      if (e < plane) {
-        const int wn_ = fdiv(e, a.inv_plane1);
-        int q = e - wn_ * a.plane1;
-        const int wt = fdiv(q, a.inv_hw); q -= wt * hw;
-        const int wh = fdiv(q, a.inv_ww);
-        const int ww = q - wh * a.WW;
-        const int n = n0 + wn_;
-        const int it = vt0 + wt, ih = vh0 + wh, iw = vw0 + ww;
-        if (n < a.N && it >= 0 && it < a.Ti && ih < a.Hi && iw < a.Wi)
-          off = (unsigned)(((long)wn_ * a.x_nstride + ((long)it * a.Hi + ih) * a.Wi + iw) * 4);
-      }
-      goff[j] = off;
-    }
+  static __device__ __forceinline__ void output(const f32x16 (&m)[TAPS], int i, float (&v)[FO]) {
+    const float n0_ = m[0][i], n1 = m[1][i], n2 = m[2][i], n3 = m[3][i], n4 = m[4][i];
+    v[0] = (n0_ + n1) + (n2 + n3); v[1] = (n1 - n2) + fmaf(2.f, n3, n4);
   }
-  const unsigned wvoff = (unsigned)((((lane * 4) / BM) * a.CoutP + (lane * 4) % BM) * 4);
+};
 
-  // XV4: 16-byte DMA of the halo-free window, 1 KiB pieces across channel rows (see conv_wino_t_body)
-  constexpr int PV = (CC * PCH * 64 / 256 + 3) / 4;
-  unsigned xvoff[PV];
-  int xvc[PV];
-  if (XV4) {
-#pragma unroll
-    for (int jj = 0; jj < PV; ++jj) {
-      const int flat = (wave + 4 * jj) * 256 + lane * 4;
-      const int c = flat / plane, e = flat - c * plane;
-      unsigned off = OOB;
-      if (c < CC) {
-        const int wn_ = fdiv(e, a.inv_plane1);
-        const int q = e - wn_ * a.plane1;
-        const int wt = fdiv(q, a.inv_ww);              // WH == 1 here
-        const int ww = q - wt * a.WW;
-        const int n = n0 + wn_, it = vt0 + wt, iw = vw0 + ww;
-        if (n < a.N && it >= 0 && it < a.Ti && iw < a.Wi)
-          off = (unsigned)(((long)wn_ * a.x_nstride + (long)it * a.Wi + iw + (long)c * a.x_cstride) * 4);
-      }
-      xvoff[jj] = off;
-      xvc[jj] = c;
-    }
-  }
-
-  // pair position of this lane: window offset of its frame o0 (o1..o4 follow at +WH*WW each)
-  int lanebase[NF];
-  const int fstride = a.WH * a.WW;
-#pragma unroll
-  for (int nf = 0; nf < NF; ++nf) {
-    const int p = wn * (BNQ / WN) + nf * 32 + l31;
-    const int tw = p & ((1 << a.lTW) - 1);
-    const int th = (p >> a.lTW) & ((1 << a.lTH) - 1);
-    const int tt = (p >> (a.lTW + a.lTH)) & ((1 << a.lTT) - 1);
-    const int tn = p >> (a.lTW + a.lTH + a.lTT);
-    lanebase[nf] = W_FLOATS + tn * a.plane1 + ((tt * 2) * a.WH + th) * a.WW + tw + half * planeS;
-  }
-  const int abase = half * BM + wm * (BM / WM) + l31;
-
-  f32x16 acc[MF][NF][5];
-#pragma unroll
-  for (int mf = 0; mf < MF; ++mf)
-#pragma unroll
-    for (int nf = 0; nf < NF; ++nf)
-#pragma unroll
-      for (int t = 0; t < 5; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[mf][nf][t][i] = 0.f;
-
-  auto stage = [&](int cin0, float* sbase) {
-    for (int p = wave; p < WPIECES; p += 4) {
-      const int row0 = p * RPP;
-      const int tap = row0 / CC, c0 = row0 % CC;
-      const unsigned soff = (unsigned)((((long)tap * a.CinP + cin0 + c0) * a.CoutP + cout0) * 4);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, LDS_PTR(sbase + p * 256), 16, wvoff, soff, 0, 0);
-    }
-    float* xs = sbase + W_FLOATS;
-    if (XV4) {
-      const unsigned soff = (unsigned)cin0 * (unsigned)a.x_cstride * 4u;
-#pragma unroll
-      for (int jj = 0; jj < PV; ++jj) {
-        const int j = wave + 4 * jj;
-        if (j * 256 < CC * plane && xvc[jj] < CC) {   // exec-masked: lanes past the image write nothing
-          const unsigned vo = cin0 + xvc[jj] < a.Cin ? xvoff[jj] : OOB;
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, LDS_PTR(xs + j * 256), 16, vo, soff, 0, 0);
-        }
-      }
-    } else
-#pragma unroll
-    for (int ci = 0; ci < CC / 4; ++ci) {
-      const int c = ci * 4 + wave;
-      const int cin = cin0 + c;
-      if (cin < a.Cin) {
-        const unsigned soff = (unsigned)cin * (unsigned)a.x_cstride * 4u;
-#pragma unroll
-        for (int j = 0; j < PCH; ++j)
-          if (j * 64 < plane)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, LDS_PTR(xs + c * planeS + j * 64), 4,
-                                                     goff[XV4 ? 0 : j], soff, 0, 0);
-      } else {
-#pragma unroll
-        for (int j = 0; j < PCH; ++j)
-          if (j * 64 < plane) xs[c * planeS + j * 64 + lane] = 0.f;
-      }
-    }
-  };
-
-  const int nchunks = a.nchunks;
-  stage(0, smem);
-  for (int ch = 0; ch < nchunks; ++ch) {
-    const float* cur = smem + (ch & 1) * stage_floats;
-    __builtin_amdgcn_s_waitcnt(0x0f70);
-    __syncthreads();
-    if (ch + 1 < nchunks) stage((ch + 1) * CC, smem + ((ch + 1) & 1) * stage_floats);
-
-    constexpr int QS = CC / 2;
-    // step q: channel pair (2q, 2q+1); operands of step q+1 are fetched under the MFMAs of q
-    auto fetch = [&](int q, float (&av)[MF][5], float (&dv)[NF][5]) {
-#pragma unroll
-      for (int t = 0; t < 5; ++t)
-#pragma unroll
-        for (int mf = 0; mf < MF; ++mf) av[mf][t] = cur[abase + (t * CC + 2 * q) * BM + mf * 32];
-#pragma unroll
-      for (int nf = 0; nf < NF; ++nf)
-#pragma unroll
-        for (int k = 0; k < 5; ++k) dv[nf][k] = cur[lanebase[nf] + k * fstride + 2 * q * planeS];
-    };
-    float av[2][MF][5], dv[2][NF][5];
-    fetch(0, av[0], dv[0]);
-#pragma unroll
-    for (int q = 0; q < QS; ++q) {
-      if (q + 1 < QS) fetch(q + 1, av[(q + 1) & 1], dv[(q + 1) & 1]);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int nf = 0; nf < NF; ++nf) {
-        const float o0 = dv[q & 1][nf][0], o1 = dv[q & 1][nf][1], o2 = dv[q & 1][nf][2],
-                    o3 = dv[q & 1][nf][3], o4 = dv[q & 1][nf][4];
-        const float oa = o3 - o2, o31 = o3 - o1;
-        const float D[5] = {fmaf(2.f, o0 - o2, o31), fmaf(-2.f, o1, oa), fmaf(2.f, o1, fmaf(-2.f, o2, oa)), o31,
-                            fmaf(-2.f, o31, o4 - o2)};
-#pragma unroll
-        for (int t = 0; t < 5; ++t)
-#pragma unroll
-          for (int mf = 0; mf < MF; ++mf)
-            acc[mf][nf][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q & 1][mf][t], D[t],
-                                                                  acc[mf][nf][t], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-
-  // ---- epilogue: two frames per pair position -----------------------------------------------------
-  unsigned yvoff[NF];
-  int nvalid[NF];                 // valid frames of the quad (0 = position outside the tensor)
-  const unsigned half_rows = (unsigned)half * 4u * (unsigned)a.y_cstride * 4u;
-  // destination lattice along T (one phase of a strided data gradient): output frame o lands on frame
-  // o * yst + yot of the destination tensor; dense: yst = 1, yot = 0
-  const unsigned frame_bytes = (unsigned)(a.yHf * a.yWf) * 4u * (unsigned)a.yst;
-  const int To_full = a.To_full;
-#pragma unroll
-  for (int nf = 0; nf < NF; ++nf) {
-    const int p = wn * (BNQ / WN) + nf * 32 + l31;
-    const int tw = p & ((1 << a.lTW) - 1);
-    const int th = (p >> a.lTW) & ((1 << a.lTH) - 1);
-    const int tt = (p >> (a.lTW + a.lTH)) & ((1 << a.lTT) - 1);
-    const int tn = p >> (a.lTW + a.lTH + a.lTT);
-    const int n = n0 + tn, tp = ot0 + tt, oh = oh0 + th, ow = ow0 + tw;
-    const bool ok = n < a.N && 2 * tp < To_full && oh < a.Ho && ow < a.Wo;
-    int nv = To_full - 2 * tp;
-    nvalid[nf] = ok ? (nv > 2 ? 2 : nv) : 0;
-    const long e = (long)tn * a.y_nstride + ((long)(2 * tp * a.yst + a.yot) * a.yHf + oh) * a.yWf + ow;
-    yvoff[nf] = ok ? (unsigned)(e * 4) + half_rows : OOB;
-  }
-
-  const bool want_stats = a.stats != nullptr;
-  float* red = smem;
-  if (want_stats) __syncthreads();
-
-  auto emit = [&](auto acc_tag, auto fancy_tag) {       // FANCY: see conv_igemm_body
-    constexpr bool ACCUM = decltype(acc_tag)::value;
-    constexpr bool FANCY = decltype(fancy_tag)::value;
-#pragma unroll
-    for (int mf = 0; mf < MF; ++mf) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int rowu = wm * (BM / WM) + mf * 32 + (i & 3) + 8 * (i >> 2);
-        const int ml = rowu + 4 * half;
-        const int co = cout0 + ml;
-        const bool cok = co < a.Cout;
-        const unsigned soff = (unsigned)(cout0 + rowu) * (unsigned)a.y_cstride * 4u;
-        float s = 0.f, ss = 0.f;
-        float bia = 0.f, sc = 1.f, sf = 0.f;
-        if (FANCY) {
-          if (a.bias && cok) bia = a.bias[co];
-          if (a.ep_scale && cok) { sc = a.ep_scale[co]; sf = a.ep_shift[co]; }
-        }
-#pragma unroll
-        for (int nf = 0; nf < NF; ++nf) {
-          const float n0_ = acc[mf][nf][0][i], n1 = acc[mf][nf][1][i], n2 = acc[mf][nf][2][i],
-                      n3 = acc[mf][nf][3][i], n4 = acc[mf][nf][4][i];
-          float v[2] = {(n0_ + n1) + (n2 + n3), (n1 - n2) + fmaf(2.f, n3, n4)};
-#pragma unroll
-          for (int f = 0; f < 2; ++f) {
-            const bool fv = f < nvalid[nf];
-            const unsigned vo = (cok && fv) ? yvoff[nf] + (unsigned)f * frame_bytes : OOB;
-            if (ACCUM) v[f] += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ry, vo, soff, 0));
-            const float u = fv ? v[f] : 0.f;
-            s += u; ss += u * u;
-            if (FANCY) {
-              v[f] = (v[f] + bia) * sc + sf;
-              if (a.relu) v[f] = fmaxf(v[f], 0.f);
-            }
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[f]), ry, vo, soff, 0);
-          }
-        }
-        if (want_stats) {
-          s = row16_sum(s);
-          ss = row16_sum(ss);
-          if ((lane & 15) == 0) {
-            const int slot = wn * 2 + (l31 >> 4);
-            red[(slot * BM + ml) * 2 + 0] = s;
-            red[(slot * BM + ml) * 2 + 1] = ss;
-          }
-        }
-      }
-    }
-  };
-  const bool fancy = a.bias || a.ep_scale || a.relu;
-  if (fancy) { if (a.accumulate) emit(std::true_type{}, std::true_type{}); else emit(std::false_type{}, std::true_type{}); }
-  else if (a.accumulate) emit(std::true_type{}, std::false_type{});
-  else emit(std::false_type{}, std::false_type{});
-
-  if (want_stats) {
-    __syncthreads();
-    if (tid < BM) {
-      const int co = cout0 + tid;
-      if (co < a.Cout) {
-        float s = 0.f, ss = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          s += red[(k * BM + tid) * 2];
-          ss += red[(k * BM + tid) * 2 + 1];
-        }
-        a.stats[(long)co * a.ntiles + ntile] = s;
-        a.stats[((long)a.Cout + co) * a.ntiles + ntile] = ss;
-      }
-    }
-  }
-}
-
-
-template <int CC, int BM, int BNQ, int PCH, bool XV4, int OCC = 1>
-__global__ void __launch_bounds__(256, OCC)
-conv_wino_t24_kernel(const ConvArgs a) {
-  conv_wino_t24_body<CC, BM, BNQ, PCH, XV4>(a, (int)blockIdx.x, (int)gridDim.x);
-}
-
-// ------------------------------------------------------------------------------------
 // The temporal stem conv (7,1,1) / stride 2 / pad 3 (STConv3d's second half in Conv_1a, backbone/s3dg.py:41,145)
 // in POLYPHASE Winograd form (coclr_conv_desc.algo = 1 on that stencil).
 //
@@ -1625,11 +1007,32 @@ conv_wino_t24_kernel(const ConvArgs a) {
 //     O = (2(o0-o2)+(o3-o1), -2o1-o2+o3, 2o1-3o2+o3, o3-o1, 2(o1-o3)+(o4-o2))
 //     U_o = (b0/2, -(b0+b1+b2+b3)/2, (-b0+b1-b2+b3)/6, (b0+2b1+4b2+8b3)/6, b3)
 //     y[2p] = (m0+m1+m2) + (n0+n1+n2+n3)        y[2p+1] = (m1-m2-m3) + (n1-n2+2n3+n4)
-// Same structure as the temporal Winograd kernels above: a (9,1,1) stencil with temporal stride 4 over output-pair
-// positions, nine accumulator sets per 32x32 block (144 registers: two workgroups per CU).
-template <int CC, int BM, int BNQ, int PCH, bool XV4, bool INAFF = false>
-__device__ __forceinline__ void conv_poly7_body(const ConvArgs& a, int bid, const int nblocks) {
-  constexpr int TAPS = 9;
+// A (9,1,1) stencil with temporal stride 4 over output-pair positions, nine accumulator sets per 32x32 block
+// (144 registers: two workgroups per CU).  The only form with the optional affine(+ReLU) on load (INAFF).
+struct StemPoly7 {
+  static constexpr int TAPS = 9, FO = 2, STEP = 4, ORG = 3;
+  static constexpr bool LATTICE = false, PAIR = false;
+  static __device__ __forceinline__ void input(const float (&r_)[TAPS], float (&D)[TAPS]) {
+    // odd taps (w1, w3, w5) on frames r1, r3, r5, r7: F(2,3); even taps (w0, w2, w4, w6) on r0, r2, r4, r6, r8: F(2,4)
+    const float e0 = r_[1], e1 = r_[3], e2 = r_[5], e3 = r_[7];
+    const float o0 = r_[0], o1 = r_[2], o2 = r_[4], o3 = r_[6], o4 = r_[8];
+    const float oa = o3 - o2, o31 = o3 - o1;
+    D[0] = e0 - e2; D[1] = e1 + e2; D[2] = e2 - e1; D[3] = e1 - e3;
+    D[4] = fmaf(2.f, o0 - o2, o31); D[5] = fmaf(-2.f, o1, oa); D[6] = fmaf(2.f, o1, fmaf(-2.f, o2, oa)); D[7] = o31;
+    D[8] = fmaf(-2.f, o31, o4 - o2);
+  }
+  static __device__ __forceinline__ void output(const f32x16 (&m)[TAPS], int i, float (&v)[FO]) {
+    const float m0 = m[0][i], m1 = m[1][i], m2 = m[2][i], m3 = m[3][i];
+    const float n0_ = m[4][i], n1 = m[5][i], n2 = m[6][i], n3 = m[7][i], n4 = m[8][i];
+    v[0] = ((m0 + m1) + m2) + ((n0_ + n1) + (n2 + n3));
+    v[1] = ((m1 - m2) - m3) + ((n1 - n2) + fmaf(2.f, n3, n4));
+  }
+};
+
+template <typename Form, int CC, int BM, int BNQ, int PCH, bool XV4, bool INAFF = false>
+__device__ __forceinline__ void conv_wino_tf_body(const ConvArgs& a, int bid, const int nblocks) {
+  constexpr int TAPS = Form::TAPS, FO = Form::FO;
+  static_assert(!INAFF || (TAPS == 9 && Form::ORG == 3), "the frame masks of INAFF are those of the stem window");
   constexpr int WM = 2, WN = 2;
   constexpr int MF = BM / (WM * 32), NF = BNQ / (WN * 32);
   constexpr int RPP = 256 / BM;
@@ -1658,9 +1061,9 @@ __device__ __forceinline__ void conv_poly7_body(const ConvArgs& a, int bid, cons
   const int bh_ = r % a.nbh; r /= a.nbh;
   const int bt_ = r % a.nbt; r /= a.nbt;
   const int n0 = r << a.lTN;
-  const int ow0 = bw_ << a.lTW, oh0 = bh_ << a.lTH, ot0 = bt_ << a.lTT;   // ot0: output-PAIR index
+  const int ow0 = bw_ << a.lTW, oh0 = bh_ << a.lTH, ot0 = bt_ << a.lTT;   // ot0: POSITION index
   const int cout0 = mt * BM;
-  const int vt0 = ot0 * 4 - 3, vh0 = oh0, vw0 = ow0;                      // window origin: frame 4p - 3
+  const int vt0 = ot0 * Form::STEP - Form::ORG, vh0 = oh0, vw0 = ow0;     // window origin
   const int plane = a.plane;
 
   const float* xbase = a.x + (long)n0 * a.x_nstride;
@@ -1719,7 +1122,7 @@ __device__ __forceinline__ void conv_poly7_body(const ConvArgs& a, int bid, cons
     }
   }
 
-  // pair position of this lane: window offset of its frame r0 (r1..r8 follow at +WH*WW each)
+  // position of this lane: window offset of its first frame (the others follow at +WH*WW each)
   int lanebase[NF];
   const int fstride = a.WH * a.WW;
 #pragma unroll
@@ -1729,7 +1132,7 @@ __device__ __forceinline__ void conv_poly7_body(const ConvArgs& a, int bid, cons
     const int th = (p >> a.lTW) & ((1 << a.lTH) - 1);
     const int tt = (p >> (a.lTW + a.lTH)) & ((1 << a.lTT) - 1);
     const int tn = p >> (a.lTW + a.lTH + a.lTT);
-    lanebase[nf] = W_FLOATS + tn * a.plane1 + ((tt * 4) * a.WH + th) * a.WW + tw + half * planeS;
+    lanebase[nf] = W_FLOATS + tn * a.plane1 + ((tt * Form::STEP) * a.WH + th) * a.WW + tw + half * planeS;
   }
   const int abase = half * BM + wm * (BM / WM) + l31;
 
@@ -1757,13 +1160,13 @@ __device__ __forceinline__ void conv_poly7_body(const ConvArgs& a, int bid, cons
     }
   }
 
-  f32x16 acc[MF][NF][9];
+  f32x16 acc[MF][NF][TAPS];
 #pragma unroll
   for (int mf = 0; mf < MF; ++mf)
 #pragma unroll
     for (int nf = 0; nf < NF; ++nf)
 #pragma unroll
-      for (int t = 0; t < 9; ++t)
+      for (int t = 0; t < TAPS; ++t)
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[mf][nf][t][i] = 0.f;
 
@@ -1815,17 +1218,17 @@ __device__ __forceinline__ void conv_poly7_body(const ConvArgs& a, int bid, cons
 
     constexpr int QS = CC / 2;
     // step q: channel pair (2q, 2q+1); operands of step q+1 are fetched under the MFMAs of q
-    auto fetch = [&](int q, float (&av)[MF][9], float (&dv)[NF][9]) {
+    auto fetch = [&](int q, float (&av)[MF][TAPS], float (&dv)[NF][TAPS]) {
 #pragma unroll
-      for (int t = 0; t < 9; ++t)
+      for (int t = 0; t < TAPS; ++t)
 #pragma unroll
         for (int mf = 0; mf < MF; ++mf) av[mf][t] = cur[abase + (t * CC + 2 * q) * BM + mf * 32];
 #pragma unroll
       for (int nf = 0; nf < NF; ++nf)
 #pragma unroll
-        for (int k = 0; k < 9; ++k) dv[nf][k] = cur[lanebase[nf] + k * fstride + 2 * q * planeS];
+        for (int k = 0; k < TAPS; ++k) dv[nf][k] = cur[lanebase[nf] + k * fstride + 2 * q * planeS];
     };
-    float av[2][MF][9], dv[2][NF][9];
+    float av[2][MF][TAPS], dv[2][NF][TAPS];
     fetch(0, av[0], dv[0]);
 #pragma unroll
     for (int q = 0; q < QS; ++q) {
@@ -1833,8 +1236,8 @@ __device__ __forceinline__ void conv_poly7_body(const ConvArgs& a, int bid, cons
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int nf = 0; nf < NF; ++nf) {
-        float* r_ = dv[q & 1][nf];
-        if (INAFF) {
+        float (&r_)[TAPS] = dv[q & 1][nf];
+        if constexpr (INAFF) {
           const int c = ch * CC + 2 * q + half;
           const float sc = aff[c], sh = aff[a.CinP + c];
 #pragma unroll
@@ -1846,15 +1249,10 @@ __device__ __forceinline__ void conv_poly7_body(const ConvArgs& a, int bid, cons
           r_[0] *= fm[nf][0]; r_[1] *= fm[nf][1]; r_[2] *= fm[nf][2];
           r_[5] *= fm[nf][3]; r_[6] *= fm[nf][4]; r_[7] *= fm[nf][5]; r_[8] *= fm[nf][6];
         }
-        // odd taps (w1, w3, w5) on frames r1, r3, r5, r7: F(2,3); even taps (w0, w2, w4, w6) on r0, r2, r4, r6, r8: F(2,4)
-        const float e0 = r_[1], e1 = r_[3], e2 = r_[5], e3 = r_[7];
-        const float o0 = r_[0], o1 = r_[2], o2 = r_[4], o3 = r_[6], o4 = r_[8];
-        const float oa = o3 - o2, o31 = o3 - o1;
-        const float D[9] = {e0 - e2, e1 + e2, e2 - e1, e1 - e3,
-                            fmaf(2.f, o0 - o2, o31), fmaf(-2.f, o1, oa), fmaf(2.f, o1, fmaf(-2.f, o2, oa)), o31,
-                            fmaf(-2.f, o31, o4 - o2)};
+        float D[TAPS];
+        Form::input(r_, D);
 #pragma unroll
-        for (int t = 0; t < 9; ++t)
+        for (int t = 0; t < TAPS; ++t)
 #pragma unroll
           for (int mf = 0; mf < MF; ++mf)
             acc[mf][nf][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q & 1][mf][t], D[t],
@@ -1864,12 +1262,15 @@ __device__ __forceinline__ void conv_poly7_body(const ConvArgs& a, int bid, cons
     }
   }
 
-  // ---- epilogue: two frames per pair position -----------------------------------------------------
+  // ---- epilogue: FO frames per position ------------------------------------------------------------
   unsigned yvoff[NF];
-  int nvalid[NF];                 // valid frames of the pair (0 = position outside the tensor)
+  int nvalid[NF];                 // valid frames of the position (0 = position outside the tensor)
   const unsigned half_rows = (unsigned)half * 4u * (unsigned)a.y_cstride * 4u;
-  const unsigned frame_bytes = (unsigned)(a.yHf * a.yWf) * 4u;
-  const int To_full = a.yst;     // launcher passes the un-grouped frame count here
+  // LATTICE: destination lattice along T (one phase of a strided data gradient): output frame o lands on frame
+  // o * yst + yot of the destination tensor; dense: yst = 1, yot = 0.  Otherwise the destination is dense and
+  // the launcher passes the un-grouped frame count in yst
+  const unsigned frame_bytes = (unsigned)(a.yHf * a.yWf) * 4u * (Form::LATTICE ? (unsigned)a.yst : 1u);
+  const int To_full = Form::LATTICE ? a.To_full : a.yst;
 #pragma unroll
   for (int nf = 0; nf < NF; ++nf) {
     const int p = wn * (BNQ / WN) + nf * 32 + l31;
@@ -1878,10 +1279,11 @@ __device__ __forceinline__ void conv_poly7_body(const ConvArgs& a, int bid, cons
     const int tt = (p >> (a.lTW + a.lTH)) & ((1 << a.lTT) - 1);
     const int tn = p >> (a.lTW + a.lTH + a.lTT);
     const int n = n0 + tn, tp = ot0 + tt, oh = oh0 + th, ow = ow0 + tw;
-    const bool ok = n < a.N && 2 * tp < To_full && oh < a.Ho && ow < a.Wo;
-    int nv = To_full - 2 * tp;
-    nvalid[nf] = ok ? (nv > 2 ? 2 : nv) : 0;
-    const long e = (long)tn * a.y_nstride + ((long)(2 * tp) * a.yHf + oh) * a.yWf + ow;
+    const bool ok = n < a.N && FO * tp < To_full && oh < a.Ho && ow < a.Wo;
+    int nv = To_full - FO * tp;
+    nvalid[nf] = ok ? (nv > FO ? FO : nv) : 0;
+    const int yt = Form::LATTICE ? FO * tp * a.yst + a.yot : FO * tp;
+    const long e = (long)tn * a.y_nstride + ((long)yt * a.yHf + oh) * a.yWf + ow;
     yvoff[nf] = ok ? (unsigned)(e * 4) + half_rows : OOB;
   }
 
@@ -1909,14 +1311,10 @@ __device__ __forceinline__ void conv_poly7_body(const ConvArgs& a, int bid, cons
         }
 #pragma unroll
         for (int nf = 0; nf < NF; ++nf) {
-          const float m0 = acc[mf][nf][0][i], m1 = acc[mf][nf][1][i], m2 = acc[mf][nf][2][i],
-                      m3 = acc[mf][nf][3][i];
-          const float n0_ = acc[mf][nf][4][i], n1 = acc[mf][nf][5][i], n2 = acc[mf][nf][6][i],
-                      n3 = acc[mf][nf][7][i], n4 = acc[mf][nf][8][i];
-          float v[2] = {((m0 + m1) + m2) + ((n0_ + n1) + (n2 + n3)),
-                        ((m1 - m2) - m3) + ((n1 - n2) + fmaf(2.f, n3, n4))};
+          float v[FO];
+          Form::output(acc[mf][nf], i, v);
 #pragma unroll
-          for (int f = 0; f < 2; ++f) {
+          for (int f = 0; f < FO; ++f) {                 // frame by frame: the order of the sums into s / ss
             const bool fv = f < nvalid[nf];
             const unsigned vo = (cok && fv) ? yvoff[nf] + (unsigned)f * frame_bytes : OOB;
             if (ACCUM) v[f] += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ry, vo, soff, 0));
@@ -1964,13 +1362,19 @@ __device__ __forceinline__ void conv_poly7_body(const ConvArgs& a, int bid, cons
   }
 }
 
-
-template <int CC, int BM, int BNQ, int PCH, bool XV4, int OCC = 1, bool INAFF = false>
+template <typename Form, int CC, int BM, int BNQ, int PCH, bool XV4, int OCC = 1, bool INAFF = false>
 __global__ void __launch_bounds__(256, OCC)
-conv_poly7_kernel(const ConvArgs a) {
-  conv_poly7_body<CC, BM, BNQ, PCH, XV4, INAFF>(a, (int)blockIdx.x, (int)gridDim.x);
+conv_wino_tf_kernel(const ConvArgs a) {
+  conv_wino_tf_body<Form, CC, BM, BNQ, PCH, XV4, INAFF>(a, (int)blockIdx.x, (int)gridDim.x);
 }
 
+// two problems in one launch, see conv_igemm_pair_kernel
+template <typename Form, int CC, int BM, int BNQ, int PCH, bool XV4, int OCC = 1>
+__global__ void __launch_bounds__(256, OCC)
+conv_wino_tf_pair_kernel(const ConvArgs a0, const ConvArgs a1, const int nb0) {
+  if ((int)blockIdx.x < nb0) conv_wino_tf_body<Form, CC, BM, BNQ, PCH, XV4>(a0, (int)blockIdx.x, nb0);
+  else conv_wino_tf_body<Form, CC, BM, BNQ, PCH, XV4>(a1, (int)blockIdx.x - nb0, (int)gridDim.x - nb0);
+}
 
 // ------------------------------------------------------------------------------------
 // Spatial (1,3,3) stride-1 pad-1 convolutions through Winograd F(2x2,3x3).
@@ -3309,7 +2713,7 @@ __device__ __forceinline__ void pack_element(const PackDesc& d, long e) {
                           : j == 2 ? 0.5f * ((col[0] - col[1]) + col[2]) : col[2];
     }
   } else if (d.wino && taps == 9) {
-    // polyphase Winograd operand of the 7-tap stride-2 temporal stem conv (see conv_poly7_body): matrices 0..3 =
+    // polyphase Winograd operand of the 7-tap stride-2 temporal stem conv (see StemPoly7): matrices 0..3 =
     // F(2,3) of the odd taps (w1, w3, w5), 4..8 = F(2,4) of the even taps (w0, w2, w4, w6)
     if (rr < Cin && c < Cout) {
       const float* src = w + c * co_stride + rr * ci_stride + tap_base;
@@ -3327,7 +2731,7 @@ __device__ __forceinline__ void pack_element(const PackDesc& d, long e) {
         : w6;
     }
   } else if (d.wino && taps == 5) {
-    // 5 transformed matrices of a 4-tap temporal stencil, F(2,4) (see conv_wino_t24_body); the data gradient
+    // 5 transformed matrices of a 4-tap temporal stencil, F(2,4) (see WinoF24); the data gradient
     // uses the flipped stencil
     const bool ok = transpose ? (rr < Cout && c < Cin) : (rr < Cin && c < Cout);
     if (ok) {
@@ -3344,7 +2748,7 @@ __device__ __forceinline__ void pack_element(const PackDesc& d, long e) {
         : b3;
     }
   } else if (d.wino && taps == 6) {
-    // 6 transformed matrices of a 3-tap temporal stencil, F(4,3) (see conv_wino_t4_body); the data
+    // 6 transformed matrices of a 3-tap temporal stencil, F(4,3) (see WinoF43); the data
     // gradient uses the flipped stencil
     const bool ok = transpose ? (rr < Cout && c < Cin) : (rr < Cin && c < Cout);
     if (ok) {
@@ -3426,7 +2830,7 @@ inline int granule_count(const ConvPlan& p) {
 }
 
 // A launch that coclr_conv3d_fwd_multi may fuse with its neighbour: the launcher fills the slot instead of
-// launching; two slots with the same `pair` function are the same kernel variant.
+// launching; two slots with the same `single` function are the same kernel variant.
 typedef int (*SingleFn)(const ConvArgs&, long, size_t, hipStream_t);
 typedef int (*PairFn)(const ConvArgs&, const ConvArgs&, long, long, size_t, hipStream_t);
 struct PairSlot {
@@ -3438,24 +2842,26 @@ struct PairSlot {
   bool pending;
 };
 
-template <int KT, int KH, int KW, int CC, int BM, int BN, int PCH, bool XV4, bool XG>
-int variant_single(const ConvArgs& a, long blocks, size_t lds, hipStream_t stream) {
-  auto kern = conv_igemm_kernel<KT, KH, KW, CC, BM, BN, PCH, XV4, XG>;
+// Raise the dynamic-LDS limit of kernel `Kern` once, launch it on 256-thread blocks, check.  One instantiation,
+// hence one `attr_done` flag, per kernel.
+template <auto Kern, typename... Args>
+int launch_dyn_lds(long blocks, size_t lds, hipStream_t stream, const Args&... args) {
   static std::atomic<uint64_t> attr_done{0};
-  COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, stream, a);
+  COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(Kern), 160 * 1024, attr_done));
+  hipLaunchKernelGGL(Kern, dim3((unsigned)blocks), dim3(256), lds, stream, args...);
   COCLR_LAUNCH_CHECK();
   return 0;
 }
 
-template <int KT, int KH, int KW, int CC, int BM, int BN, int PCH, bool XV4, bool XG>
-int variant_pair(const ConvArgs& a0, const ConvArgs& a1, long b0, long b1, size_t lds, hipStream_t stream) {
-  auto kern = conv_igemm_pair_kernel<KT, KH, KW, CC, BM, BN, PCH, XV4, XG>;
-  static std::atomic<uint64_t> attr_done{0};
-  COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
-  hipLaunchKernelGGL(kern, dim3((unsigned)(b0 + b1)), dim3(256), lds, stream, a0, a1, (int)b0);
-  COCLR_LAUNCH_CHECK();
-  return 0;
+// the SingleFn / PairFn of a kernel: one function per kernel, so comparing pointers compares kernel variants
+template <auto Kern>
+int launch_single(const ConvArgs& a, long blocks, size_t lds, hipStream_t stream) {
+  return launch_dyn_lds<Kern>(blocks, lds, stream, a);
+}
+
+template <auto Kern>
+int launch_pair(const ConvArgs& a0, const ConvArgs& a1, long b0, long b1, size_t lds, hipStream_t stream) {
+  return launch_dyn_lds<Kern>(b0 + b1, lds, stream, a0, a1, (int)b0);
 }
 
 // Two DIFFERENT variants of the (1,3,3) small-map kernel in one launch: on the first 8x8x8 blocks the wide
@@ -3470,21 +2876,11 @@ conv_igemm_133_mixed_kernel(const ConvArgs a0, const ConvArgs a1, const int nb0)
     conv_igemm_body<1, 3, 3, 8, 64, BNB, 3, false, true>(a1, (int)blockIdx.x - nb0, (int)gridDim.x - nb0);
 }
 
-template <int BNA, int BNB>
-int mixed_pair_launch(const ConvArgs& a0, const ConvArgs& a1, long b0, long b1, size_t lds, hipStream_t stream) {
-  auto kern = conv_igemm_133_mixed_kernel<BNA, BNB>;
-  static std::atomic<uint64_t> attr_done{0};
-  COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
-  hipLaunchKernelGGL(kern, dim3((unsigned)(b0 + b1)), dim3(256), lds, stream, a0, a1, (int)b0);
-  COCLR_LAUNCH_CHECK();
-  return 0;
-}
-
 inline PairFn mixed_pair(SingleFn f0, SingleFn f1) {
-  const SingleFn wide = &variant_single<1, 3, 3, 8, 64, 128, 3, false, true>;
-  const SingleFn narrow = &variant_single<1, 3, 3, 8, 64, 64, 3, false, true>;
-  if (f0 == wide && f1 == narrow) return &mixed_pair_launch<128, 64>;
-  if (f0 == narrow && f1 == wide) return &mixed_pair_launch<64, 128>;
+  const SingleFn wide = &launch_single<conv_igemm_kernel<1, 3, 3, 8, 64, 128, 3, false, true>>;
+  const SingleFn narrow = &launch_single<conv_igemm_kernel<1, 3, 3, 8, 64, 64, 3, false, true>>;
+  if (f0 == wide && f1 == narrow) return &launch_pair<conv_igemm_133_mixed_kernel<128, 64>>;
+  if (f0 == narrow && f1 == wide) return &launch_pair<conv_igemm_133_mixed_kernel<64, 128>>;
   return nullptr;
 }
 
@@ -3518,15 +2914,15 @@ int launch_variant(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot 
   constexpr bool PAIRABLE = KT == 1 && ((KH == 3 && KW == 3) || (KH == 1 && KW == 1 && XV4));
   if (slot && PAIRABLE) {
     slot->args = a; slot->blocks = blocks; slot->lds = lds; slot->pending = true;
-    slot->single = &variant_single<KT, KH, KW, CC, BM, BN, PCH, XV4, XG>;
-    if constexpr (PAIRABLE) slot->pair = &variant_pair<KT, KH, KW, CC, BM, BN, PCH, XV4, XG>;
+    slot->single = &launch_single<conv_igemm_kernel<KT, KH, KW, CC, BM, BN, PCH, XV4, XG>>;
+    if constexpr (PAIRABLE) slot->pair = &launch_pair<conv_igemm_pair_kernel<KT, KH, KW, CC, BM, BN, PCH, XV4, XG>>;
     return 0;
   }
-  return variant_single<KT, KH, KW, CC, BM, BN, PCH, XV4, XG>(a, blocks, lds, stream);
+  return launch_single<conv_igemm_kernel<KT, KH, KW, CC, BM, BN, PCH, XV4, XG>>(a, blocks, lds, stream);
 }
 
-template <int CC, int BM, int BNP, int PCH, bool XV4, int OCC>
-int launch_wino_t(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot) {
+template <int CC, int BM, int BNP, int PCH, bool XV4, int OCC = 1>
+int launch_wino_t(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot = nullptr) {
   if (p.plane > PCH * 64) return COCLR_EINVAL;
   a.mtiles = cdiv(a.Cout, BM);
   // 16-byte staging packs the channel rows back to back
@@ -3540,72 +2936,37 @@ int launch_wino_t(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot) 
   const long blocks = (long)a.mtiles * a.ntiles;
   if (slot) {
     slot->args = a; slot->blocks = blocks; slot->lds = lds; slot->pending = true;
-    slot->single = &wino_t_single<CC, BM, BNP, PCH, XV4, OCC>;
-    slot->pair = &wino_t_pair<CC, BM, BNP, PCH, XV4, OCC>;
+    slot->single = &launch_single<conv_wino_t_kernel<CC, BM, BNP, PCH, XV4, OCC>>;
+    slot->pair = &launch_pair<conv_wino_t_pair_kernel<CC, BM, BNP, PCH, XV4, OCC>>;
     return 0;
   }
-  return wino_t_single<CC, BM, BNP, PCH, XV4, OCC>(a, blocks, lds, stream);
+  return launch_single<conv_wino_t_kernel<CC, BM, BNP, PCH, XV4, OCC>>(a, blocks, lds, stream);
 }
 
-template <int CC, int BM, int BNQ, int PCH, bool XV4, int OCC>
-int launch_wino_t4(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot) {
+// the temporal Winograd family (conv_wino_tf_body): Form::TAPS weight matrices per stage, the affine table of
+// INAFF behind the stages; a slot is filled only where the form has a pair kernel
+template <typename Form, int CC, int BM, int BNQ, int PCH, bool XV4, int OCC, bool INAFF = false>
+int launch_wino_tf(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot = nullptr) {
   if (p.plane > PCH * 64) return COCLR_EINVAL;
   a.mtiles = cdiv(a.Cout, BM);
   a.planeS = XV4 ? p.plane : cdiv(p.plane, 64) * 64;
   a.nchunks = cdiv(a.Cin, CC);
-  const size_t stage = ((size_t)6 * CC * BM + (size_t)CC * a.planeS) * sizeof(float);
-  const size_t lds_main = stage * (a.nchunks > 1 ? 2 : 1);
-  const size_t lds_red = (size_t)4 * BM * 2 * sizeof(float);
-  const size_t lds = lds_main > lds_red ? lds_main : lds_red;
-  if (lds > 160 * 1024) return COCLR_EINVAL;
-  const long blocks = (long)a.mtiles * a.ntiles;
-  if (slot) {
-    slot->args = a; slot->blocks = blocks; slot->lds = lds; slot->pending = true;
-    slot->single = &wino_t4_single<CC, BM, BNQ, PCH, XV4, OCC>;
-    slot->pair = &wino_t4_pair<CC, BM, BNQ, PCH, XV4, OCC>;
-    return 0;
-  }
-  return wino_t4_single<CC, BM, BNQ, PCH, XV4, OCC>(a, blocks, lds, stream);
-}
-
-template <int CC, int BM, int BNQ, int PCH, bool XV4, int OCC>
-int launch_wino_t24(ConvArgs& a, ConvPlan& p, hipStream_t stream) {
-  if (p.plane > PCH * 64) return COCLR_EINVAL;
-  a.mtiles = cdiv(a.Cout, BM);
-  a.planeS = XV4 ? p.plane : cdiv(p.plane, 64) * 64;
-  a.nchunks = cdiv(a.Cin, CC);
-  const size_t stage = ((size_t)5 * CC * BM + (size_t)CC * a.planeS) * sizeof(float);
-  const size_t lds_main = stage * (a.nchunks > 1 ? 2 : 1);
-  const size_t lds_red = (size_t)4 * BM * 2 * sizeof(float);
-  const size_t lds = lds_main > lds_red ? lds_main : lds_red;
-  if (lds > 160 * 1024) return COCLR_EINVAL;
-  const long blocks = (long)a.mtiles * a.ntiles;
-  auto kern = conv_wino_t24_kernel<CC, BM, BNQ, PCH, XV4, OCC>;
-  static std::atomic<uint64_t> attr_done{0};
-  COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, stream, a);
-  COCLR_LAUNCH_CHECK();
-  return 0;
-}
-
-template <int CC, int BM, int BNQ, int PCH, bool XV4, int OCC, bool INAFF = false>
-int launch_poly7(ConvArgs& a, ConvPlan& p, hipStream_t stream) {
-  if (p.plane > PCH * 64) return COCLR_EINVAL;
-  a.mtiles = cdiv(a.Cout, BM);
-  a.planeS = XV4 ? p.plane : cdiv(p.plane, 64) * 64;
-  a.nchunks = cdiv(a.Cin, CC);
-  const size_t stage = ((size_t)9 * CC * BM + (size_t)CC * a.planeS) * sizeof(float);
+  const size_t stage = ((size_t)Form::TAPS * CC * BM + (size_t)CC * a.planeS) * sizeof(float);
   const size_t lds_main = stage * (a.nchunks > 1 ? 2 : 1) + (INAFF ? (size_t)2 * a.CinP * sizeof(float) : 0);
   const size_t lds_red = (size_t)4 * BM * 2 * sizeof(float);
   const size_t lds = lds_main > lds_red ? lds_main : lds_red;
   if (lds > 160 * 1024) return COCLR_EINVAL;
   const long blocks = (long)a.mtiles * a.ntiles;
-  auto kern = conv_poly7_kernel<CC, BM, BNQ, PCH, XV4, OCC, INAFF>;
-  static std::atomic<uint64_t> attr_done{0};
-  COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, stream, a);
-  COCLR_LAUNCH_CHECK();
-  return 0;
+  constexpr SingleFn single = &launch_single<conv_wino_tf_kernel<Form, CC, BM, BNQ, PCH, XV4, OCC, INAFF>>;
+  if constexpr (Form::PAIR && !INAFF) {
+    if (slot) {
+      slot->args = a; slot->blocks = blocks; slot->lds = lds; slot->pending = true;
+      slot->single = single;
+      slot->pair = &launch_pair<conv_wino_tf_pair_kernel<Form, CC, BM, BNQ, PCH, XV4, OCC>>;
+      return 0;
+    }
+  }
+  return single(a, blocks, lds, stream);
 }
 
 // efficiency of covering Cout with tiles of BM rows
@@ -4004,11 +3365,11 @@ int conv3d_fwd_impl(const coclr_conv_desc* d, const float* x, const float* w_pac
                        (p.plane % 4) == 0;
       if (n_index) return COCLR_EINVAL;
       if (variant == 52) {
-        if (xv4) return launch_wino_t24<8, 64, 64, 4, true, 3>(a, p, stream);
-        return launch_wino_t24<8, 64, 64, 4, false, 3>(a, p, stream);
+        if (xv4) return launch_wino_tf<WinoF24, 8, 64, 64, 4, true, 3>(a, p, stream);
+        return launch_wino_tf<WinoF24, 8, 64, 64, 4, false, 3>(a, p, stream);
       }
-      if (xv4) return launch_wino_t4<8, 64, 64, 6, true, 3>(a, p, stream, slot && !lattice ? slot : nullptr);
-      return launch_wino_t4<8, 64, 64, 6, false, 3>(a, p, stream);
+      if (xv4) return launch_wino_tf<WinoF43, 8, 64, 64, 6, true, 3>(a, p, stream, slot && !lattice ? slot : nullptr);
+      return launch_wino_tf<WinoF43, 8, 64, 64, 6, false, 3>(a, p, stream);
     }
     case 60: {
       // a.Ho/Wo = 2x2 blocks; the destination keeps its full row pitch
@@ -4068,10 +3429,10 @@ int conv3d_fwd_impl(const coclr_conv_desc* d, const float* x, const float* w_pac
                         (p.plane % 4) == 0;
       if (n_index) return COCLR_EINVAL;
       if (a.in_scale)
-        return xv4p ? launch_poly7<8, 64, 64, 6, true, 2, true>(a, p, stream)
-                    : launch_poly7<8, 64, 64, 6, false, 2, true>(a, p, stream);
-      if (xv4p) return launch_poly7<8, 64, 64, 6, true, 2>(a, p, stream);
-      return launch_poly7<8, 64, 64, 6, false, 2>(a, p, stream);
+        return xv4p ? launch_wino_tf<StemPoly7, 8, 64, 64, 6, true, 2, true>(a, p, stream)
+                    : launch_wino_tf<StemPoly7, 8, 64, 64, 6, false, 2, true>(a, p, stream);
+      if (xv4p) return launch_wino_tf<StemPoly7, 8, 64, 64, 6, true, 2>(a, p, stream);
+      return launch_wino_tf<StemPoly7, 8, 64, 64, 6, false, 2>(a, p, stream);
     }
     case 40: return xv4 ? launch_variant<7, 1, 1, 4, 64, 128, 8, true>(a, p, stream)
                         : launch_variant<7, 1, 1, 8, 64, 128, 8>(a, p, stream);
