@@ -91,7 +91,8 @@ stage_clips_kernel(const StageArgs a) {
 struct CropArgs {
   const uint8_t* frames; const int32_t* slot_frame;
   const int32_t *xmin, *xk, *ymin, *yk;      // [Sp], [taps][Sp]
-  float* out;
+  float* out;                                // fp32 form: [crop][clip][3][T][S][S], normalised
+  uint8_t* out8;                             // uint8 form: [crop][clip*T][S][S][3], the resized bytes themselves
   int crop[16][3];                           // x0, y0, flip
   float mean[3], std[3];
   int F, H, W, T, n_clips, cw, ch, S, Sp, xtaps, ytaps, R, cap_rows;
@@ -104,6 +105,7 @@ __device__ __forceinline__ unsigned fix8(int acc) {       // PIL's clip8 of a 22
   return min((unsigned)t >> 22, 255u);
 }
 
+template <bool U8OUT>
 __global__ void __launch_bounds__(256)
 stage_crops_kernel(const CropArgs a) {
   extern __shared__ __align__(16) uint8_t hrows[];      // [rows][3][Sp]
@@ -154,6 +156,14 @@ stage_crops_kernel(const CropArgs a) {
       a2 += k * (int)((w >> 16) & 255u);
       a3 += k * (int)(w >> 24);
     }
+    if (U8OUT) {
+      const unsigned v[4] = {fix8(a0), fix8(a1), fix8(a2), fix8(a3)};
+      uint8_t* dst = a.out8 + ((((long)crop * gridDim.y + slot) * a.S + r) * (long)a.S + xg * 4) * 3 + c;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (xg * 4 + j < a.S) dst[3 * j] = (uint8_t)v[j];
+      continue;
+    }
     const float mean = a.mean[c], std = a.std[c];
     float4 o;
     o.x = norm1(__fdiv_rn((float)fix8(a0), 255.f), mean, std);
@@ -172,15 +182,201 @@ stage_crops_kernel(const CropArgs a) {
   }
 }
 
+// ---- ColorJitter / RandomGray on uint8 frames (utils/augmentation.py:179-320, through torchvision 0.5's
+// functional on PIL: ImageEnhance.Brightness/Contrast/Color, convert('HSV') + uint8 add + convert('RGB')) ----------
+// One workgroup owns one frame and runs its group's program (up to 8 ops, device tables) on the frame's bytes in
+// PIL's own arithmetic, every operation rounded on its own: integers for L, fp32 for Image.blend, fp32 and double
+// for the HSV round trip exactly where PIL's C uses float and double.  A lane always works on the same items
+// (four consecutive pixels = three dwords), so pointwise ops chain in registers with no barrier.  Only contrast
+// needs the whole frame -- the mean of L over the frame AS IT IS at that point of the program -- so the program
+// is cut at every contrast op: a pass applies the ops up to the next contrast, parks the bytes in LDS
+// ([item][3] dwords: a lane's stride of 3 dwords is odd, no bank conflict) while summing L in integers (exact and
+// order-independent: sum < 2^24 for H*W <= 224*224), and after one workgroup reduction the next pass starts with
+// that contrast.  The last pass converts with the arithmetic of stage_crops_kernel and stores 16 bytes along x
+// into (clip, 3, T, H, W).  A program without contrast is one pass, global to global, and asks for no LDS.
+// The tables are device data: an unknown kind does nothing, a gray channel is clamped, a hue shift is taken mod
+// 256, and contrast is ignored when the launch brought no LDS -- whatever they hold, nothing is out of bounds.
+enum { JIT_NOP = 0, JIT_BRIGHTNESS = 1, JIT_CONTRAST = 2, JIT_SATURATION = 3, JIT_HUE = 4, JIT_GRAY = 5 };
+constexpr int kJitThreads = 512;
+constexpr int kJitMaxPixels = 224 * 224;
+
+struct JitterArgs {
+  const uint8_t* frames; const int32_t* kinds; const float* params; float* out;
+  float mean[3], std[3];
+  int HW, T, P, G, group_size, items, vec, use_lds;
+};
+
+__device__ __forceinline__ int lum8(int r, int g, int b) {          // PIL's convert('L')
+  return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16;
+}
+
+// Image.blend(degenerate d, image i, alpha a): one fp32 multiply and one fp32 add; PIL truncates when
+// 0 <= a <= 1 (`inside`) and clips otherwise.
+__device__ __forceinline__ int blend8(int d, int i, float a, bool inside) {
+  const float t = __fadd_rn((float)d, __fmul_rn(a, (float)(i - d)));
+  if (inside) return (int)t;
+  return t <= 0.f ? 0 : t >= 255.f ? 255 : (int)t;
+}
+
+// convert('HSV'), h = (h + shift) & 255, convert('RGB')
+__device__ __forceinline__ void hue8(int& r, int& g, int& b, int shift) {
+  const int maxc = max(r, max(g, b)), minc = min(r, min(g, b));
+  const int v = maxc;
+  int uh = 0, us = 0;
+  if (minc != maxc) {
+    const float cr = (float)(maxc - minc);
+    const float s = __fdiv_rn(cr, (float)maxc);
+    const float rc = __fdiv_rn((float)(maxc - r), cr);
+    const float gc = __fdiv_rn((float)(maxc - g), cr);
+    const float bc = __fdiv_rn((float)(maxc - b), cr);
+    float h;
+    if (r == maxc) h = __fsub_rn(bc, gc);
+    else if (g == maxc) h = (float)(2.0 + (double)rc - (double)bc);
+    else h = (float)(4.0 + (double)gc - (double)rc);
+    const double x = (double)h / 6.0 + 1.0;                 // in [5/6, 11/6]: x - floor(x) is fmod(x, 1.0), exactly
+    h = (float)(x - floor(x));
+    uh = clampi((int)((double)h * 255.0), 0, 255);
+    us = clampi((int)((double)s * 255.0), 0, 255);
+  }
+  uh = (uh + shift) & 255;
+  if (us == 0) { r = g = b = v; return; }
+  const double h6 = (double)uh * 6.0 / 255.0;
+  const double fl = floor(h6);
+  const float f = (float)(h6 - fl);
+  const float fs = (float)((double)us / 255.0);
+  const double vd = (double)v;
+  const int p = clampi((int)round(vd * (1.0 - (double)fs)), 0, 255);
+  const int q = clampi((int)round(vd * (1.0 - (double)fs * (double)f)), 0, 255);
+  const int t = clampi((int)round(vd * (1.0 - (double)fs * (1.0 - (double)f))), 0, 255);
+  switch ((int)fl % 6) {
+    case 0: r = v; g = t; b = p; break;
+    case 1: r = q; g = v; b = p; break;
+    case 2: r = p; g = v; b = t; break;
+    case 3: r = p; g = q; b = v; break;
+    case 4: r = t; g = p; b = v; break;
+    default: r = v; g = p; b = q; break;
+  }
+}
+
+__global__ void __launch_bounds__(kJitThreads)
+color_jitter_kernel(const JitterArgs a) {
+  extern __shared__ __align__(16) unsigned parked[];      // [items][3]: four RGB pixels, as they lie in memory
+  __shared__ unsigned red[kJitThreads / 64];
+  const int tid = threadIdx.x, n = blockIdx.x;
+  const int grp = min(n / a.group_size, a.G - 1);
+  const int32_t* kinds = a.kinds + (long)grp * a.P;
+  const float* params = a.params + (long)grp * a.P;
+  const uint8_t* src = a.frames + (long)n * a.HW * 3;
+  const bool src4 = (((uintptr_t)src) & 3) == 0;
+  const long plane = (long)a.T * a.HW;                              // one channel of one clip
+  float* dst = a.out + (long)(n / a.T) * 3 * plane + (long)(n % a.T) * a.HW;
+  int op = 0, m = 0;
+  for (int pass = 0;; ++pass) {
+    // this pass runs ops [op, end): a contrast op ends a pass and, with its mean `m` known, begins the next
+    int end = op + (pass > 0);
+    while (end < a.P && !(a.use_lds && kinds[end] == JIT_CONTRAST)) ++end;
+    const bool last = end >= a.P;
+    unsigned sum = 0;
+    for (int it = tid; it < a.items; it += kJitThreads) {
+      const bool full = it * 4 + 3 < a.HW;
+      unsigned w[3] = {0u, 0u, 0u};
+      if (pass > 0) {
+        w[0] = parked[it * 3]; w[1] = parked[it * 3 + 1]; w[2] = parked[it * 3 + 2];
+      } else if (src4 && full) {
+        const unsigned* s4 = reinterpret_cast<const unsigned*>(src) + (long)it * 3;
+        w[0] = s4[0]; w[1] = s4[1]; w[2] = s4[2];
+      } else {
+#pragma unroll
+        for (int k = 0; k < 12; ++k)
+          if (it * 4 + k / 3 < a.HW) w[k >> 2] |= (unsigned)src[(long)it * 12 + k] << (8 * (k & 3));
+      }
+      int c[12];
+#pragma unroll
+      for (int k = 0; k < 12; ++k) c[k] = (int)((w[k >> 2] >> (8 * (k & 3))) & 255u);
+      for (int j = op; j < end; ++j) {
+        const int kind = kinds[j];
+        const float prm = params[j];
+        const bool inside = prm >= 0.f && prm <= 1.f;
+        if (kind == JIT_BRIGHTNESS) {
+#pragma unroll
+          for (int k = 0; k < 12; ++k) c[k] = blend8(0, c[k], prm, inside);
+        } else if (kind == JIT_CONTRAST) {
+          if (pass > 0 && j == op) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) c[k] = blend8(m, c[k], prm, inside);
+          }
+        } else if (kind == JIT_SATURATION) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int L = lum8(c[3 * q], c[3 * q + 1], c[3 * q + 2]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) c[3 * q + k] = blend8(L, c[3 * q + k], prm, inside);
+          }
+        } else if (kind == JIT_HUE) {
+          const int shift = (int)prm & 255;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) hue8(c[3 * q], c[3 * q + 1], c[3 * q + 2], shift);
+        } else if (kind == JIT_GRAY) {
+          const int ch = clampi((int)prm, 0, 2);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int v = ch == 0 ? c[3 * q] : ch == 1 ? c[3 * q + 1] : c[3 * q + 2];
+            c[3 * q] = c[3 * q + 1] = c[3 * q + 2] = v;
+          }
+        }
+      }
+      if (!last) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (it * 4 + q < a.HW) sum += (unsigned)lum8(c[3 * q], c[3 * q + 1], c[3 * q + 2]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          parked[it * 3 + k] = (unsigned)c[4 * k] | ((unsigned)c[4 * k + 1] << 8) | ((unsigned)c[4 * k + 2] << 16) |
+                               ((unsigned)c[4 * k + 3] << 24);
+      } else {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+          const float mean = a.mean[ch], std = a.std[ch];
+          float4 o;
+          o.x = norm1(__fdiv_rn((float)c[ch], 255.f), mean, std);
+          o.y = norm1(__fdiv_rn((float)c[3 + ch], 255.f), mean, std);
+          o.z = norm1(__fdiv_rn((float)c[6 + ch], 255.f), mean, std);
+          o.w = norm1(__fdiv_rn((float)c[9 + ch], 255.f), mean, std);
+          float* d = dst + ch * plane + (long)it * 4;
+          if (a.vec) {
+            *reinterpret_cast<float4*>(d) = o;
+          } else {
+            const float v[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+              if (it * 4 + q < a.HW) d[q] = v[q];
+          }
+        }
+      }
+    }
+    if (last) break;
+    // m = int(sum / count + 0.5) = (2*sum + count) / (2*count): sum <= 255 * 224 * 224 < 2^24
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    __syncthreads();                                       // the previous pass's readers of red[] are done
+    if ((tid & 63) == 0) red[tid >> 6] = sum;
+    __syncthreads();
+    unsigned total = 0;
+#pragma unroll
+    for (int k = 0; k < kJitThreads / 64; ++k) total += red[k];
+    m = (int)((2u * total + (unsigned)a.HW) / (2u * (unsigned)a.HW));
+    op = end;
+  }
+}
+
 }  // namespace
 
-extern "C" int coclr_stage_crops(const uint8_t* frames, int F, int H, int W, const int32_t* slot_frame,
-                                 int n_clips, int T, const int32_t* crops, int n_crops, int cw, int ch, int S,
-                                 const int32_t* xmin, const int32_t* xk, int xtaps, const int32_t* ymin,
-                                 const int32_t* yk, int ytaps, const float* mean, const float* std, float* out,
-                                 void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (!frames || !slot_frame || !crops || !xmin || !xk || !ymin || !yk || !mean || !std || !out)
+// The launch both crop entry points share: `out` (fp32, with mean / std) or `out8` (the resized bytes).
+static int launch_crops(const uint8_t* frames, int F, int H, int W, const int32_t* slot_frame, int n_clips, int T,
+                        const int32_t* crops, int n_crops, int cw, int ch, int S, const int32_t* xmin,
+                        const int32_t* xk, int xtaps, const int32_t* ymin, const int32_t* yk, int ytaps,
+                        const float* mean, const float* std, float* out, uint8_t* out8, hipStream_t stream) {
+  if (!frames || !slot_frame || !crops || !xmin || !xk || !ymin || !yk || (!out && !out8) || (out && (!mean || !std)))
     return COCLR_EINVAL;
   if (F < 1 || H < 1 || W < 1 || T < 1 || n_clips < 1 || S < 1 || S > 512 || cw < 1 || ch < 1)
     return COCLR_EINVAL;
@@ -195,7 +391,7 @@ extern "C" int coclr_stage_crops(const uint8_t* frames, int F, int H, int W, con
     a.crop[k][0] = x0; a.crop[k][1] = y0; a.crop[k][2] = flip;
   }
   for (int c = 0; c < 3; ++c) {
-    a.mean[c] = mean[c]; a.std[c] = std[c];             // host arrays, read at call time
+    a.mean[c] = out ? mean[c] : 0.f; a.std[c] = out ? std[c] : 1.f;      // host arrays, read at call time
     if (a.std[c] == 0.f) return COCLR_EINVAL;
   }
   // band height: the most output rows whose source rows fit the LDS budget.  ymin is non-decreasing and
@@ -212,11 +408,72 @@ extern "C" int coclr_stage_crops(const uint8_t* frames, int F, int H, int W, con
   }
   const long bands = (S + R - 1) / R;
   if (bands * n_clips * T * n_crops * 256 >= (1L << 32)) return COCLR_EINVAL;
-  a.frames = frames; a.slot_frame = slot_frame; a.xmin = xmin; a.xk = xk; a.ymin = ymin; a.yk = yk; a.out = out;
+  a.frames = frames; a.slot_frame = slot_frame; a.xmin = xmin; a.xk = xk; a.ymin = ymin; a.yk = yk;
+  a.out = out; a.out8 = out8;
   a.F = F; a.H = H; a.W = W; a.T = T; a.n_clips = n_clips; a.cw = cw; a.ch = ch; a.S = S; a.Sp = Sp;
   a.xtaps = xtaps; a.ytaps = ytaps; a.R = R; a.cap_rows = cap;
   dim3 grid((unsigned)bands, (unsigned)(n_clips * T), (unsigned)n_crops);
-  hipLaunchKernelGGL(stage_crops_kernel, grid, dim3(256), (size_t)cap * 3 * Sp, stream, a);
+  if (out) hipLaunchKernelGGL(stage_crops_kernel<false>, grid, dim3(256), (size_t)cap * 3 * Sp, stream, a);
+  else hipLaunchKernelGGL(stage_crops_kernel<true>, grid, dim3(256), (size_t)cap * 3 * Sp, stream, a);
+  COCLR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int coclr_stage_crops(const uint8_t* frames, int F, int H, int W, const int32_t* slot_frame,
+                                 int n_clips, int T, const int32_t* crops, int n_crops, int cw, int ch, int S,
+                                 const int32_t* xmin, const int32_t* xk, int xtaps, const int32_t* ymin,
+                                 const int32_t* yk, int ytaps, const float* mean, const float* std, float* out,
+                                 void* stream_) {
+  if (!out || !mean || !std) return COCLR_EINVAL;
+  return launch_crops(frames, F, H, W, slot_frame, n_clips, T, crops, n_crops, cw, ch, S, xmin, xk, xtaps, ymin,
+                      yk, ytaps, mean, std, out, nullptr, (hipStream_t)stream_);
+}
+
+extern "C" int coclr_resize_crops_u8(const uint8_t* frames, int F, int H, int W, const int32_t* slot_frame,
+                                     int n_clips, int T, const int32_t* crops, int n_crops, int cw, int ch, int S,
+                                     const int32_t* xmin, const int32_t* xk, int xtaps, const int32_t* ymin,
+                                     const int32_t* yk, int ytaps, uint8_t* out, void* stream_) {
+  if (!out) return COCLR_EINVAL;
+  return launch_crops(frames, F, H, W, slot_frame, n_clips, T, crops, n_crops, cw, ch, S, xmin, xk, xtaps, ymin,
+                      yk, ytaps, nullptr, nullptr, nullptr, out, (hipStream_t)stream_);
+}
+
+extern "C" int coclr_color_jitter_clips(const uint8_t* frames, int N, int H, int W, int T, const int32_t* kinds,
+                                        const float* params, const int32_t* kinds_host, const float* params_host,
+                                        int G, int P, int group_size, const float* mean, const float* std,
+                                        float* out, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!frames || !kinds || !params || !kinds_host || !params_host || !mean || !std || !out) return COCLR_EINVAL;
+  if (N < 1 || H < 1 || W < 1 || T < 1 || G < 1 || P < 1 || P > 8 || group_size < 1) return COCLR_EINVAL;
+  if (N % T != 0 || (long)G * group_size < N) return COCLR_EINVAL;
+  if ((long)H * W > kJitMaxPixels) return COCLR_EINVAL;     // the frame's bytes must fit one workgroup's LDS
+  bool contrast = false;
+  for (long i = 0; i < (long)G * P; ++i) {
+    const int kind = kinds_host[i];
+    const float v = params_host[i];
+    if (kind < JIT_NOP || kind > JIT_GRAY) return COCLR_EINVAL;
+    if (kind >= JIT_BRIGHTNESS && kind <= JIT_SATURATION && !(v - v == 0.f)) return COCLR_EINVAL;   // NaN, inf
+    if (kind == JIT_HUE && !(v >= 0.f && v <= 255.f && v == (float)(int)v)) return COCLR_EINVAL;
+    if (kind == JIT_GRAY && !(v == 0.f || v == 1.f || v == 2.f)) return COCLR_EINVAL;
+    contrast = contrast || kind == JIT_CONTRAST;
+  }
+  JitterArgs a;
+  for (int c = 0; c < 3; ++c) {
+    a.mean[c] = mean[c]; a.std[c] = std[c];             // host arrays, read at call time
+    if (a.std[c] == 0.f) return COCLR_EINVAL;
+  }
+  a.frames = frames; a.kinds = kinds; a.params = params; a.out = out;
+  a.HW = H * W; a.T = T; a.P = P; a.G = G; a.group_size = group_size;
+  a.items = (a.HW + 3) / 4;
+  a.vec = (W & 3) == 0 && (((uintptr_t)out) & 15) == 0;
+  a.use_lds = contrast ? 1 : 0;
+  const size_t lds = contrast ? (size_t)a.items * 12 : 0;
+  if (contrast) {                                        // 224 x 224 x 3 = 147 KiB of the CU's 160
+    static std::atomic<uint64_t> attr_done{0};
+    COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(color_jitter_kernel), kJitMaxPixels * 3,
+                                   attr_done));
+  }
+  hipLaunchKernelGGL(color_jitter_kernel, dim3((unsigned)N), dim3(kJitThreads), lds, stream, a);
   COCLR_LAUNCH_CHECK();
   return 0;
 }

@@ -13,6 +13,7 @@ Nothing is read back and nothing synchronises before `finish()`, whose results a
 over as HOST tensors are copied before `add()` returns, so the caller may reuse its staging buffer).
 """
 import collections
+import random
 
 import torch
 
@@ -88,14 +89,16 @@ class VideoEvaluator:
         return video
 
     def add_frames(self, frames_u8, frame_index, label=None, crops="ten", crop_size=224, out_size=128,
-                   max_stage_bytes=256 << 20):
+                   max_stage_bytes=256 << 20, jitter=None, rng=random):
         """One video from its decoded frames: `frames_u8` (F, H, W, 3) uint8, host or device, uploaded ONCE;
         `frame_index` (n_clips, T) the frame of every clip position (staging.test_frame_index).  `crops`:
         "center", "five" or "ten" -- the reference's --center_crop / --five_crop / --ten_crop, centre first and
         the flipped five last.  Every crop is staged on the GPU (staging.stage_crops: flip, FiveCrop(crop_size),
-        Scale(out_size) in PIL's bicubic, ToTensor, Normalize; the reference's random test-time ColorJitter is
-        left out) and handed to add() as a further crop of one video, whose index is returned.  Whole crops are
-        staged in chunks of at most `max_stage_bytes`."""
+        Scale(out_size) in PIL's bicubic, ColorJitter, ToTensor, Normalize) and handed to add() as a further crop
+        of one video, whose index is returned.  Whole crops are staged in chunks of at most `max_stage_bytes`.
+        `jitter`: a staging.ColorJitter, e.g. the reference's ColorJitter(0.2, 0.2, 0.2, 0.1, p=0.3); it is drawn
+        from `rng` once per crop, in staging order, before anything is staged (the chunking does not show in the
+        draws).  None leaves the jitter out."""
         if crops not in CROP_MODES:
             raise ValueError("coclr_amd: crops must be one of %s, got %r" % (sorted(CROP_MODES), crops))
         if frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or frames_u8.dtype != torch.uint8:
@@ -120,10 +123,16 @@ class VideoEvaluator:
         idx = idx.to(self.device)
         chunk = min(len(todo), 16, max_stage_bytes // per_crop)
         buf = torch.empty(chunk, n, 3, T, S, S, dtype=torch.float32, device=self.device)
+        programs = None if jitter is None else [jitter.draw(rng, 1)[0] for _ in todo]
         video = None
         for k in range(0, len(todo), chunk):
             part = todo[k:k + chunk]
-            staged = staging.stage_crops_on_device(frames, idx, part, crop_size, crop_size, S, out=buf[:len(part)])
+            if programs is None:
+                staged = staging.stage_crops_on_device(frames, idx, part, crop_size, crop_size, S,
+                                                       out=buf[:len(part)])
+            else:
+                staged = staging.stage_crops_on_device(frames, idx, part, crop_size, crop_size, S,
+                                                       out=buf[:len(part)], jitter=programs[k:k + chunk])
             for clips in staged:
                 # (add() copies the crop into the batch on this stream before the next chunk overwrites `buf`)
                 video = self.add(clips, label=label if video is None else None, video=video)

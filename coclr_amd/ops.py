@@ -928,6 +928,61 @@ def stage_crops(frames, slot_frame, crops, cw, ch, S, xmin, xk, ymin, yk, mean, 
         _stream()), "stage_crops")
 
 
+def resize_crops_u8(frames, slot_frame, crops, cw, ch, S, xmin, xk, ymin, yk, out):
+    """stage_crops up to the resized bytes: out (n_crops, n_clips*T, S, S, 3) uint8, one image per slot."""
+    if frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise ValueError("coclr_amd: frames must be contiguous (F, H, W, 3), got %s" % (tuple(frames.shape),))
+    F, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
+    n_clips, T = slot_frame.shape
+    Sp = (S + 3) & ~3
+    if tuple(xmin.shape) != (Sp,) or xk.dim() != 2 or xk.shape[1] != Sp or \
+            tuple(ymin.shape) != (Sp,) or yk.dim() != 2 or yk.shape[1] != Sp:
+        raise ValueError("coclr_amd: resampling tables must be (Sp,) and (taps, Sp) with Sp = %d" % Sp)
+    if tuple(out.shape) != (len(crops), n_clips * T, S, S, 3) or not out.is_contiguous():
+        raise ValueError("coclr_amd: out must be contiguous %s, got %s" %
+                         ((len(crops), n_clips * T, S, S, 3), tuple(out.shape)))
+    for t in (slot_frame, xmin, xk, ymin, yk):
+        if not t.is_contiguous():
+            raise ValueError("coclr_amd: resize_crops_u8 needs contiguous index and table tensors")
+    flat = [int(v) for c in crops for v in c]
+    if len(flat) != 3 * len(crops) or not crops:
+        raise ValueError("coclr_amd: crops must be (x0, y0, flip) triples")
+    box = (C.c_int32 * len(flat))(*flat)
+    i32 = torch.int32
+    _lib.check(_L().coclr_resize_crops_u8(
+        _p(frames, torch.uint8), F, H, W, _p(slot_frame, i32), n_clips, T, box, len(crops), cw, ch, S,
+        _p(xmin, i32), _p(xk, i32), xk.shape[0], _p(ymin, i32), _p(yk, i32), yk.shape[0], _p(out, torch.uint8),
+        _stream()), "resize_crops_u8")
+
+
+def color_jitter_clips(frames, kinds, params, group_size, T, mean, std, out, host_tables=None):
+    """frames (N, H, W, 3) uint8 -> out (N/T, 3, T, H, W) fp32; frame n runs program n // group_size of the
+    device tables kinds int32 (G, P) / params fp32 (G, P) (include/coclr_hip.h).  `host_tables`: the same two
+    tables on the host, which the entry point validates (read back from the device when not given)."""
+    if frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise ValueError("coclr_amd: frames must be contiguous (N, H, W, 3), got %s" % (tuple(frames.shape),))
+    N, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
+    if kinds.dim() != 2 or kinds.shape != params.shape or not kinds.is_contiguous() or not params.is_contiguous():
+        raise ValueError("coclr_amd: kinds and params must be contiguous (G, P) tables, got %s and %s" %
+                         (tuple(kinds.shape), tuple(params.shape)))
+    G, P = kinds.shape
+    T = int(T)
+    if T < 1 or N % T != 0:
+        raise ValueError("coclr_amd: %d frames do not make clips of %d" % (N, T))
+    if tuple(out.shape) != (N // T, 3, T, H, W) or not out.is_contiguous():
+        raise ValueError("coclr_amd: out must be contiguous %s, got %s" % ((N // T, 3, T, H, W), tuple(out.shape)))
+    hk, hp = host_tables if host_tables is not None else (kinds.cpu(), params.cpu())
+    if hk.shape != kinds.shape or hp.shape != params.shape or hk.is_cuda or hp.is_cuda or \
+            not hk.is_contiguous() or not hp.is_contiguous() or hk.dtype != torch.int32 or hp.dtype != torch.float32:
+        raise ValueError("coclr_amd: host_tables must be contiguous host copies of kinds and params")
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    s = (C.c_float * 3)(*[float(v) for v in std])
+    _lib.check(_L().coclr_color_jitter_clips(
+        _p(frames, torch.uint8), N, H, W, T, _p(kinds, torch.int32), _p(params),
+        C.cast(hk.data_ptr(), C.POINTER(C.c_int32)), C.cast(hp.data_ptr(), C.POINTER(C.c_float)), G, P,
+        int(group_size), m, s, _p(out), _stream()), "color_jitter_clips")
+
+
 # ---- evaluation consumers ---------------------------------------------------------------
 
 def colstats_workspace(rows, cols):

@@ -17,8 +17,13 @@ The test protocol's input (eval/main_classifier.py:453-469) is staged here too: 
 video's raw uint8 frames into every crop x flip x clip the five/ten-crop test feeds the classifier, in one
 launch, bit-identical to the reference's PIL chain (flip -> FiveCrop -> Scale(BICUBIC) -> ToTensor) plus
 Normalize; `resample_tables`, `five_crop_boxes` and `test_frame_index` are the host-side restatements it needs.
+The chain's ColorJitter (utils/augmentation.py:219-320) is `ColorJitter` below: it draws from the generator as
+the reference does and hands the kernel one small program per group of frames (`color_jitter`,
+`stage_crops(jitter=...)`), bit-identical to torchvision 0.5's functional ops on PIL images.
 """
 import math
+import numbers
+import random
 
 import numpy as np
 import torch
@@ -232,13 +237,151 @@ def check_crops(boxes, flips, cw, ch, W, H):
     return crops
 
 
-def stage_crops_on_device(frames, slot_frame, crops, cw, ch, S, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
+# ---- ColorJitter (utils/augmentation.py:219-320) ------------------------------------------------------------
+
+# op kinds of a program, as csrc/staging.hip takes them: [(kind, parameter)] in order of application
+JITTER_NOP, JITTER_BRIGHTNESS, JITTER_CONTRAST, JITTER_SATURATION, JITTER_HUE, JITTER_GRAY = range(6)
+JITTER_MAX_OPS = 8
+JITTER_MAX_PIXELS = 224 * 224        # one workgroup holds the frame in LDS
+
+
+def hue_shift_byte(hue_factor):
+    """What torchvision 0.5's adjust_hue adds to the uint8 H channel, `np.uint8(hue_factor * 255)`: truncated
+    toward zero, modulo 256 (a negative factor wraps round)."""
+    return int(hue_factor * 255) % 256
+
+
+class ColorJitter:
+    """The reference's ColorJitter as a source of programs: same argument checks, same ranges, and `draw`
+    consumes the generator exactly as its `__call__` + `get_params` do, so with the same seed in front it yields
+    what the reference applies.  `consistent=True` is draw(rng, 1) for the whole item, `seq_len=k` is
+    draw(rng, n_frames / k) with group_size k, per-frame jitter is draw(rng, n_frames) with group_size 1."""
+
+    def __init__(self, brightness=0, contrast=0, saturation=0, hue=0, p=1.0):
+        self.brightness = self._check_input(brightness, 'brightness')
+        self.contrast = self._check_input(contrast, 'contrast')
+        self.saturation = self._check_input(saturation, 'saturation')
+        self.hue = self._check_input(hue, 'hue', center=0, bound=(-0.5, 0.5), clip_first_on_zero=False)
+        self.p = p
+
+    @staticmethod
+    def _check_input(value, name, center=1, bound=(0, float('inf')), clip_first_on_zero=True):
+        if isinstance(value, numbers.Number):
+            if value < 0:
+                raise ValueError("coclr_amd: if %s is a single number, it must be non negative" % name)
+            value = [center - value, center + value]
+            if clip_first_on_zero:
+                value[0] = max(value[0], 0)
+        elif isinstance(value, (tuple, list)) and len(value) == 2:
+            if not bound[0] <= value[0] <= value[1] <= bound[1]:
+                raise ValueError("coclr_amd: %s values should be between %s" % (name, (bound,)))
+        else:
+            raise TypeError("coclr_amd: %s should be a single number or a list/tuple of length 2" % name)
+        if value[0] == value[1] == center:          # nothing to draw: the op is dropped
+            value = None
+        return value
+
+    def draw(self, rng=random, n_groups=1):
+        """`n_groups` programs.  One `rng.random() < p` for the call; then per group a `rng.uniform` for
+        brightness, contrast, saturation and hue in that order (those enabled) and one `rng.shuffle`."""
+        if not rng.random() < self.p:
+            return [[] for _ in range(n_groups)]
+        programs = []
+        for _ in range(n_groups):
+            ops_ = []
+            if self.brightness is not None:
+                ops_.append((JITTER_BRIGHTNESS, rng.uniform(self.brightness[0], self.brightness[1])))
+            if self.contrast is not None:
+                ops_.append((JITTER_CONTRAST, rng.uniform(self.contrast[0], self.contrast[1])))
+            if self.saturation is not None:
+                ops_.append((JITTER_SATURATION, rng.uniform(self.saturation[0], self.saturation[1])))
+            if self.hue is not None:
+                ops_.append((JITTER_HUE, hue_shift_byte(rng.uniform(self.hue[0], self.hue[1]))))
+            rng.shuffle(ops_)
+            programs.append(ops_)
+        return programs
+
+
+def program_tables(programs):
+    """[[(kind, parameter)]] -> host tables (kinds int32 (G, P), params fp32 (G, P)), P = the longest program
+    (at least 1), shorter ones padded with no-ops.  Refuses what the kernel does not know."""
+    programs = [list(prog) for prog in programs]
+    if not programs:
+        raise ValueError("coclr_amd: need at least one jitter program")
+    P = max(1, max(len(prog) for prog in programs))
+    if P > JITTER_MAX_OPS:
+        raise ValueError("coclr_amd: a jitter program has %d ops, the kernel takes %d" % (P, JITTER_MAX_OPS))
+    kinds = torch.zeros(len(programs), P, dtype=torch.int32)
+    params = torch.zeros(len(programs), P, dtype=torch.float32)
+    for g, prog in enumerate(programs):
+        for j, (kind, value) in enumerate(prog):
+            if kind not in range(6) or isinstance(kind, bool) or int(kind) != kind:
+                raise ValueError("coclr_amd: no jitter op kind %r" % (kind,))
+            value = float(value)
+            if kind == JITTER_HUE and not (0 <= value <= 255 and value == int(value)):
+                raise ValueError("coclr_amd: a hue shift is a byte (hue_shift_byte), got %r" % (value,))
+            if kind == JITTER_GRAY and value not in (0.0, 1.0, 2.0):
+                raise ValueError("coclr_amd: gray takes channel 0, 1 or 2, got %r" % (value,))
+            if not math.isfinite(value):
+                raise ValueError("coclr_amd: jitter factor %r is not finite" % (value,))
+            kinds[g, j], params[g, j] = int(kind), value
+    return kinds, params
+
+
+def color_jitter(frames_u8, programs, group_size, T, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None, device=None):
+    """ColorJitter / RandomGray -> ToTensor -> Normalize of `frames_u8` (N, H, W, 3) uint8 (host or device) in ONE
+    launch: (N/T, 3, T, H, W) fp32 on the device, frame n at clip n // T, position n % T, after running program
+    n // group_size of `programs` ([[(kind, parameter)]], e.g. ColorJitter.draw).  Bit-identical to the
+    reference's PIL ops; an empty program is ToTensor + Normalize alone.  Frames up to 224 x 224."""
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or frames_u8.dtype != torch.uint8:
+        raise ValueError("coclr_amd: frames must be uint8 (N, H, W, 3), got %s %s" %
+                         (frames_u8.dtype, tuple(frames_u8.shape)))
+    N, H, W = frames_u8.shape[:3]
+    group_size, T = int(group_size), int(T)
+    if N < 1 or T < 1 or N % T != 0:
+        raise ValueError("coclr_amd: %d frames do not make clips of %d" % (N, T))
+    if H * W > JITTER_MAX_PIXELS or H * W < 1:
+        raise ValueError("coclr_amd: color_jitter takes frames of up to 224 x 224 pixels, got %d x %d" % (H, W))
+    kinds, params = program_tables(programs)
+    if group_size < 1 or kinds.shape[0] * group_size < N:
+        raise ValueError("coclr_amd: %d programs for groups of %d frames do not cover %d frames" %
+                         (kinds.shape[0], group_size, N))
+    if device is None:
+        device = frames_u8.device if frames_u8.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    frames = frames_u8.contiguous().to(device)
+    if out is None:
+        out = torch.empty(N // T, 3, T, H, W, dtype=torch.float32, device=frames.device)
+    ops.color_jitter_clips(frames, kinds.to(device), params.to(device), group_size, T, mean, std, out,
+                           host_tables=(kinds, params))
+    return out
+
+
+def stage_crops_on_device(frames, slot_frame, crops, cw, ch, S, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None,
+                          jitter=None):
     """The launch alone: `frames` (F, H, W, 3) uint8 and `slot_frame` (n_clips, T) int32 already on the device
-    and checked (check_frame_index, check_crops).  Up to 16 crops per launch; more are cut into launches."""
+    and checked (check_frame_index, check_crops).  Up to 16 crops per launch; more are cut into launches.
+    `jitter`: one program per crop; the crops are then resized to bytes and jittered in one further launch."""
     n_clips, T = slot_frame.shape
     if out is None:
         out = torch.empty(len(crops), n_clips, 3, T, S, S, dtype=torch.float32, device=frames.device)
     xmin, xk, ymin, yk = _device_tables(cw, ch, S, frames.device)
+    if jitter is not None:
+        jitter = list(jitter)
+        if len(jitter) != len(crops):
+            raise ValueError("coclr_amd: need one jitter program per crop, got %d programs and %d crops" %
+                             (len(jitter), len(crops)))
+        if tuple(out.shape) != (len(crops), n_clips, 3, T, S, S) or not out.is_contiguous():
+            raise ValueError("coclr_amd: out must be contiguous %s, got %s" %
+                             ((len(crops), n_clips, 3, T, S, S), tuple(out.shape)))
+        if S * S > JITTER_MAX_PIXELS:
+            raise ValueError("coclr_amd: color_jitter takes frames of up to 224 x 224 pixels, got %d x %d" % (S, S))
+        program_tables(jitter)                            # refuse a bad program before anything is launched
+        u8 = torch.empty(len(crops), n_clips * T, S, S, 3, dtype=torch.uint8, device=frames.device)
+        for k in range(0, len(crops), 16):
+            ops.resize_crops_u8(frames, slot_frame, crops[k:k + 16], cw, ch, S, xmin, xk, ymin, yk, u8[k:k + 16])
+        color_jitter(u8.view(-1, S, S, 3), jitter, n_clips * T, T, mean, std,
+                     out=out.view(len(crops) * n_clips, 3, T, S, S), device=frames.device)
+        return out
     for k in range(0, len(crops), 16):
         ops.stage_crops(frames, slot_frame, crops[k:k + 16], cw, ch, S, xmin, xk, ymin, yk, mean, std,
                         out[k:k + 16])
@@ -246,10 +389,12 @@ def stage_crops_on_device(frames, slot_frame, crops, cw, ch, S, mean=IMAGENET_ME
 
 
 def stage_crops(frames_u8, frame_index, boxes, flips, crop_size, out_size, mean=IMAGENET_MEAN, std=IMAGENET_STD,
-                out=None, device=None):
+                out=None, device=None, jitter=None):
     """One video's decoded frames -> every crop x clip of the test protocol, (n_crops, n_clips, 3, T, S, S)
     fp32 on the device: per crop `flip the frame -> crop the box at boxes[k] -> Image.resize((S, S), BICUBIC)
-    -> ToTensor -> Normalize`, bit-identical to that chain (its random ColorJitter left out).
+    -> ColorJitter -> ToTensor -> Normalize`, bit-identical to that chain.  `jitter=None` (one launch) leaves
+    the ColorJitter out; otherwise it is one program per crop (ColorJitter.draw(rng)[0] for each crop in turn:
+    the reference jitters all frames of a crop alike) and the call is two launches, resize then jitter.
     frames_u8: (F, H, W, 3) uint8 on the host (uploaded once) or the device.  frame_index: (n_clips, T) frame
     of every clip position, checked on the host.  boxes: [(x0, y0)] in the FLIPPED frame where flips[k] is 1.
     crop_size: int or (width, height).  `device` defaults to the frames' device, or the current GPU."""
@@ -263,4 +408,6 @@ def stage_crops(frames_u8, frame_index, boxes, flips, crop_size, out_size, mean=
     if device is None:
         device = frames_u8.device if frames_u8.is_cuda else torch.device("cuda", torch.cuda.current_device())
     frames = frames_u8.contiguous().to(device)
-    return stage_crops_on_device(frames, idx.to(device), crops, cw, ch, int(out_size), mean, std, out)
+    if jitter is None:
+        return stage_crops_on_device(frames, idx.to(device), crops, cw, ch, int(out_size), mean, std, out)
+    return stage_crops_on_device(frames, idx.to(device), crops, cw, ch, int(out_size), mean, std, out, jitter)

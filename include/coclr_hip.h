@@ -539,7 +539,7 @@ int coclr_stage_clips(const void* frames, int from_u8, float* out, int B, int C,
  *   flip the frame (flip = 1) -> crop the cw x ch box at (x0, y0) OF THE FLIPPED FRAME -> PIL's
  *   Image.resize((S, S), BICUBIC) on 8-bit pixels -> / 255 -> (x - mean[c]) / std[c]
  * into out[n_crops][n_clips][3][T][S][S] fp32, bit-identical to that chain.  The random test-time ColorJitter
- * of the reference is not part of it.
+ * of the reference is not part of it: coclr_resize_crops_u8 + coclr_color_jitter_clips below are.
  * frames: uint8 [F][H][W][3] (interleaved RGB), device.  slot_frame: int32 [n_clips*T], device: the frame of
  * every (clip, t); frames may repeat.  crops: HOST int32 [n_crops][3], read at call time.  The resampling
  * tables (device, int32) are PIL's precomputed coefficients per axis, in its 22-bit fixed point:
@@ -553,6 +553,36 @@ int coclr_stage_crops(const uint8_t* frames, int F, int H, int W, const int32_t*
                       int T, const int32_t* crops, int n_crops, int cw, int ch, int S, const int32_t* xmin,
                       const int32_t* xk, int xtaps, const int32_t* ymin, const int32_t* yk, int ytaps,
                       const float* mean, const float* std, float* out, void* stream);
+
+/* The resize of coclr_stage_crops alone: same arguments without mean / std, same flip, box, tables, integer
+ * passes and clamps, but the resized BYTES go out as uint8 out[n_crops][n_clips*T][S][S][3] (one image per slot,
+ * interleaved RGB like `frames`) -- the input of coclr_color_jitter_clips.  Same refusals. */
+int coclr_resize_crops_u8(const uint8_t* frames, int F, int H, int W, const int32_t* slot_frame, int n_clips,
+                          int T, const int32_t* crops, int n_crops, int cw, int ch, int S, const int32_t* xmin,
+                          const int32_t* xk, int xtaps, const int32_t* ymin, const int32_t* yk, int ytaps,
+                          uint8_t* out, void* stream);
+
+/* The reference's ColorJitter / RandomGray (utils/augmentation.py:179-320, i.e. torchvision 0.5's functional on
+ * PIL images) on uint8 frames, then / 255 and (x - mean[c]) / std[c], in one launch: frames uint8 [N][H][W][3]
+ * (device) -> out fp32 [N/T][3][T][H][W], frame n at clip n / T, position n % T.  Frame n runs program
+ * n / group_size of kinds int32 [G][P] and params fp32 [G][P] (DEVICE tables, P <= 8), its ops in order on the
+ * frame's RGB bytes, bit-identical to PIL:
+ *   0 nothing (padding)
+ *   1 brightness  ImageEnhance.Brightness(img).enhance(param)
+ *   2 contrast    ImageEnhance.Contrast(img).enhance(param); the mean of L is that of THIS frame at this point
+ *   3 saturation  ImageEnhance.Color(img).enhance(param)
+ *   4 hue         convert('HSV'), h = (h + param) & 255, convert('RGB'); param an integer 0..255
+ *   5 gray        all three channels = channel param (0..2) (RandomGray.grayscale)
+ * An all-zero program gives coclr_stage_clips' arithmetic on the bytes.  kinds_host / params_host are the SAME
+ * tables on the HOST, read at call time: the entry point validates them, the kernel reads the device copies
+ * (and stays in bounds whatever those hold).  mean / std: HOST arrays of 3 floats.
+ * COCLR_EINVAL before any launch: a null pointer; N, H, W, T, G, group_size < 1; P outside 1..8; N % T != 0;
+ * G * group_size < N; H * W > 224 * 224 (one workgroup holds the frame in LDS); std == 0; a kind outside 0..5;
+ * a non-finite factor; a hue shift that is no integer in 0..255; a gray channel outside 0..2. */
+int coclr_color_jitter_clips(const uint8_t* frames, int N, int H, int W, int T, const int32_t* kinds,
+                             const float* params, const int32_t* kinds_host, const float* params_host, int G,
+                             int P, int group_size, const float* mean, const float* std, float* out,
+                             void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Evaluation consumers (model/classifier.py:47-61; eval/main_classifier.py) */
