@@ -35,6 +35,7 @@
 //     output channel for train-mode BatchNorm, reduced with DPP row operations
 //     and written without atomics as [2][Cout][ntiles].
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "common.h"
@@ -85,6 +86,27 @@ struct ConvArgs {
   const float* in_shift;
   int in_relu;
 };
+
+// Which kernel instantiation a planned forward / data-gradient launch runs, and with what launch geometry: the
+// ONE place that decides it (conv3d_fwd_impl launches what this says, coclr_conv3d_fwd_plan reports it).
+enum { FF_IGEMM = 0, FF_WINO_T = 1, FF_WINO_TF = 2, FF_WINO_HW = 3, FF_WINO_HW8 = 4, FF_STEM = 5 };
+struct FwdQuery {
+  bool x16;        // x is 16-byte aligned
+  bool y8;         // y is 8-byte aligned
+  bool n_index, in_affine, slot, bwd_sums;
+};
+struct FwdSel {
+  int family;      // FF_*
+  int form;        // FF_WINO_TF: matrices of the form (6: F(4,3), 5: F(2,4), 9: polyphase stem); 0 otherwise
+  int KT, KH, KW, CC, BM, BN, PCH, OCC;   // template numbers (0: the kernel has none)
+  bool XV4, XG, X16, INAFF, lattice, pairable;
+  // what the launcher derives: the window as the kernel sees it (16-byte-granule forms widen it), tiles, LDS, grid
+  int WW, plane, planeS, mtiles, nchunks, threads;
+  long lds, grid;
+};
+
+// a launcher's own tile / LDS / grid arithmetic against the selection it was called for, BEFORE it launches
+inline bool sel_agrees(const FwdSel* s, const ConvArgs& a, size_t lds, long grid, int threads);
 
 // sum over each 16-lane row (result in every lane of the row)
 __device__ __forceinline__ float row16_sum(float v) {
@@ -1830,7 +1852,7 @@ conv_wino_hw_kernel(const ConvArgs a, const int total_tiles) {
 }
 
 template <int CC, int PCH, bool X16 = false, int ABL = 0>
-int launch_wino_hw(ConvArgs& a, ConvPlan& p, hipStream_t stream) {
+int launch_wino_hw(ConvArgs& a, ConvPlan& p, hipStream_t stream, const FwdSel* sel = nullptr) {
   if (p.WW > 255 || p.WH > 255 || p.WT > 255 || p.lTN > 7) return COCLR_EINVAL;
   a.mtiles = cdiv(a.Cout, 64);
   if (X16) {
@@ -1858,6 +1880,7 @@ int launch_wino_hw(ConvArgs& a, ConvPlan& p, hipStream_t stream) {
   COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
   const long total = (long)a.mtiles * a.ntiles;
   const int grid = total < kWinoGrid ? (int)total : kWinoGrid;
+  if (!sel_agrees(sel, a, lds, grid, 256)) return (int)hipErrorUnknown;   // launcher and select_forward disagree
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, stream, a, (int)total);
   COCLR_LAUNCH_CHECK();
   return 0;
@@ -2290,7 +2313,7 @@ conv_wino_hw8_kernel(const ConvArgs a, const int total_tiles) {
 }
 
 template <int CC, int PCH>
-int launch_wino_hw8(ConvArgs& a, ConvPlan& p, hipStream_t stream) {
+int launch_wino_hw8(ConvArgs& a, ConvPlan& p, hipStream_t stream, const FwdSel* sel = nullptr) {
   if (p.WW > 255 || p.WH > 255 || p.WT > 255 || p.lTN > 7 || a.Cin % CC) return COCLR_EINVAL;
   a.mtiles = cdiv(a.Cout, 64);
   const int wwp = 2 * (1 << p.lTW) + 8;
@@ -2324,6 +2347,7 @@ int launch_wino_hw8(ConvArgs& a, ConvPlan& p, hipStream_t stream) {
   COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
   const long total = (long)a.mtiles * a.ntiles;
   const int grid = total < kWinoGrid ? (int)total : kWinoGrid;
+  if (!sel_agrees(sel, a, lds, grid, 512)) return (int)hipErrorUnknown;   // launcher and select_forward disagree
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, stream, a, (int)total);
   COCLR_LAUNCH_CHECK();
   return 0;
@@ -2648,7 +2672,7 @@ conv_stem_kernel(const ConvArgs a, const int nboxes) {
 constexpr int kStemGrid = 512;   // persistent workgroups of the stem kernel (2 per CU)
 
 template <int KH, int KW, int CIN, int PCH>
-int launch_stem(ConvArgs& a, ConvPlan& p, hipStream_t stream) {
+int launch_stem(ConvArgs& a, ConvPlan& p, hipStream_t stream, const FwdSel* sel = nullptr) {
   constexpr int KROWS = CIN * KH * ((KW + 1) & ~1);
   constexpr int W_FLOATS = ((KROWS * 64 + 255) / 256) * 256;
   if (p.plane > PCH * 64 || a.Cin != CIN) return COCLR_EINVAL;
@@ -2661,6 +2685,7 @@ int launch_stem(ConvArgs& a, ConvPlan& p, hipStream_t stream) {
   auto kern = conv_stem_kernel<KH, KW, CIN, PCH>;
   static std::atomic<uint64_t> attr_done{0};
   COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
+  if (!sel_agrees(sel, a, lds, (long)a.ntiles * a.mtiles, 256)) return (int)hipErrorUnknown;   // launcher and select_forward disagree
   hipLaunchKernelGGL(kern, dim3((unsigned)a.ntiles, (unsigned)a.mtiles), dim3(256), lds, stream, a,
                      p.nboxes);
   COCLR_LAUNCH_CHECK();
@@ -2885,7 +2910,8 @@ inline PairFn mixed_pair(SingleFn f0, SingleFn f1) {
 }
 
 template <int KT, int KH, int KW, int CC, int BM, int BN, int PCH, bool XV4 = false, bool XG = false>
-int launch_variant(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot = nullptr) {
+int launch_variant(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot = nullptr,
+                   const FwdSel* sel = nullptr) {
   constexpr int TAPS = KT * KH * KW;
   a.mtiles = cdiv(a.Cout, BM);
   if (XG) {
@@ -2909,6 +2935,7 @@ int launch_variant(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot 
   const size_t lds = lds_main > lds_red ? lds_main : lds_red;
   if (lds > 160 * 1024) return COCLR_EINVAL;
   const long blocks = (long)a.mtiles * a.ntiles;
+  if (!sel_agrees(sel, a, lds, blocks, 256)) return (int)hipErrorUnknown;   // launcher and select_forward disagree
   // pair kernels exist for the stencils sibling units of an inception block share: (1,3,3) of the two
   // separable branches, 16-byte-staged (1,1,1) of the fused heads and the pool branch
   constexpr bool PAIRABLE = KT == 1 && ((KH == 3 && KW == 3) || (KH == 1 && KW == 1 && XV4));
@@ -2922,7 +2949,8 @@ int launch_variant(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot 
 }
 
 template <int CC, int BM, int BNP, int PCH, bool XV4, int OCC = 1>
-int launch_wino_t(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot = nullptr) {
+int launch_wino_t(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot = nullptr,
+                  const FwdSel* sel = nullptr) {
   if (p.plane > PCH * 64) return COCLR_EINVAL;
   a.mtiles = cdiv(a.Cout, BM);
   // 16-byte staging packs the channel rows back to back
@@ -2934,6 +2962,7 @@ int launch_wino_t(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot =
   const size_t lds = lds_main > lds_red ? lds_main : lds_red;
   if (lds > 160 * 1024) return COCLR_EINVAL;
   const long blocks = (long)a.mtiles * a.ntiles;
+  if (!sel_agrees(sel, a, lds, blocks, 256)) return (int)hipErrorUnknown;   // launcher and select_forward disagree
   if (slot) {
     slot->args = a; slot->blocks = blocks; slot->lds = lds; slot->pending = true;
     slot->single = &launch_single<conv_wino_t_kernel<CC, BM, BNP, PCH, XV4, OCC>>;
@@ -2946,7 +2975,8 @@ int launch_wino_t(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot =
 // the temporal Winograd family (conv_wino_tf_body): Form::TAPS weight matrices per stage, the affine table of
 // INAFF behind the stages; a slot is filled only where the form has a pair kernel
 template <typename Form, int CC, int BM, int BNQ, int PCH, bool XV4, int OCC, bool INAFF = false>
-int launch_wino_tf(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot = nullptr) {
+int launch_wino_tf(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot = nullptr,
+                   const FwdSel* sel = nullptr) {
   if (p.plane > PCH * 64) return COCLR_EINVAL;
   a.mtiles = cdiv(a.Cout, BM);
   a.planeS = XV4 ? p.plane : cdiv(p.plane, 64) * 64;
@@ -2957,6 +2987,7 @@ int launch_wino_tf(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot 
   const size_t lds = lds_main > lds_red ? lds_main : lds_red;
   if (lds > 160 * 1024) return COCLR_EINVAL;
   const long blocks = (long)a.mtiles * a.ntiles;
+  if (!sel_agrees(sel, a, lds, blocks, 256)) return (int)hipErrorUnknown;   // launcher and select_forward disagree
   constexpr SingleFn single = &launch_single<conv_wino_tf_kernel<Form, CC, BM, BNQ, PCH, XV4, OCC, INAFF>>;
   if constexpr (Form::PAIR && !INAFF) {
     if (slot) {
@@ -3226,6 +3257,208 @@ inline bool bwd_sums_variant(int variant) {
   return variant != 60 && variant != 31 && variant != 51 && variant != 52 && variant != 41;
 }
 
+inline bool sel_agrees(const FwdSel* s, const ConvArgs& a, size_t lds, long grid, int threads) {
+  return !s || (a.mtiles == s->mtiles && a.nchunks == s->nchunks && a.planeS == s->planeS && a.WW == s->WW &&
+                a.plane == s->plane && (long)lds == s->lds && grid == s->grid && threads == s->threads);
+}
+
+// stages of the chunked kernels (direct, F(2,3), the temporal Winograd family): `taps` weight matrices and a
+// window per chunk, double buffered when there is more than one chunk, `extra` bytes behind them
+inline int sel_staged(FwdSel& s, const ConvPlan& p, int taps, size_t extra) {
+  s.mtiles = cdiv(p.Cout, s.BM);
+  if (s.XG) {
+    const int wwp = (1 << p.lTW) + 8;
+    s.WW = wwp;
+    s.plane = ((p.WT * p.WH * wwp) << p.lTN) / 4;
+    if (s.plane > s.PCH * 64) return COCLR_EINVAL;
+    s.planeS = cdiv(s.plane, 64) * 256;
+  } else {
+    if (p.plane > s.PCH * 64) return COCLR_EINVAL;
+    s.planeS = s.XV4 ? p.plane : cdiv(p.plane, 64) * 64;
+  }
+  s.nchunks = cdiv(p.Cin, s.CC);
+  const size_t stage = ((size_t)taps * s.CC * s.BM + (size_t)s.CC * s.planeS) * sizeof(float);
+  const size_t lds_main = stage * (s.nchunks > 1 ? 2 : 1) + extra;
+  const size_t lds_red = (size_t)4 * s.BM * 2 * sizeof(float);
+  s.lds = (long)(lds_main > lds_red ? lds_main : lds_red);
+  if (s.lds > 160 * 1024) return COCLR_EINVAL;
+  s.grid = (long)s.mtiles * p.ntiles;
+  s.threads = 256;
+  return 0;
+}
+
+// the persistent F(2x2,3x3) kernels: one wave per SIMD (hw, 4- or 16-byte window staging) or two (hw8)
+inline int sel_wino_hw(FwdSel& s, const ConvPlan& p, bool hw8) {
+  if (p.WW > 255 || p.WH > 255 || p.WT > 255 || p.lTN > 7) return COCLR_EINVAL;
+  if (hw8 && p.Cin % s.CC) return COCLR_EINVAL;
+  s.mtiles = cdiv(p.Cout, 64);
+  if (s.X16) {
+    const int wwp = 2 * (1 << p.lTW) + 8;
+    s.WW = wwp;
+    s.plane = ((p.WT * p.WH * wwp) << p.lTN) / 4;
+    if (s.plane > s.PCH * 64) return COCLR_EINVAL;
+    s.planeS = cdiv(s.plane, 64) * 256 + (hw8 ? 32 : 0);
+  } else {
+    if (p.plane > s.PCH * 64) return COCLR_EINVAL;
+    s.planeS = cdiv(p.plane, 64) * 64;
+  }
+  s.nchunks = hw8 ? p.Cin / s.CC : cdiv(p.Cin, s.CC);
+  const size_t stage = ((size_t)16 * s.CC * 64 + (size_t)s.CC * s.planeS) * sizeof(float);
+  s.lds = (long)(2 * stage + (size_t)2 * 64 * 64 * sizeof(float) +
+                 (size_t)s.PCH * (hw8 ? 64 : 256) * sizeof(unsigned));
+  if (s.lds > 160 * 1024) return COCLR_EINVAL;
+  const long total = (long)s.mtiles * p.ntiles;
+  s.grid = total < kWinoGrid ? total : kWinoGrid;
+  s.threads = hw8 ? 512 : 256;
+  return 0;
+}
+
+inline int sel_stem(FwdSel& s, const ConvPlan& p) {
+  const int krows = s.CC * s.KH * ((s.KW + 1) & ~1);
+  const int w_floats = ((krows * 64 + 255) / 256) * 256;
+  if (p.plane > s.PCH * 64 || p.Cin != s.CC) return COCLR_EINVAL;
+  if (p.WT > 255 || p.WH > 255 || p.WW > 255 || (1 << p.lTN) > 255) return COCLR_EINVAL;
+  s.mtiles = cdiv(p.Cout, 64);
+  s.planeS = cdiv(p.plane, 64) * 64;
+  s.nchunks = 1;
+  s.lds = (long)(((size_t)w_floats + 2 * (size_t)s.CC * s.planeS) * sizeof(float));
+  if (s.lds > 160 * 1024) return COCLR_EINVAL;
+  s.grid = (long)p.ntiles * s.mtiles;
+  s.threads = 256;
+  return 0;
+}
+
+inline void sel_kernel(FwdSel& s, int family, int KT, int KH, int KW, int CC, int BM, int BN, int PCH, int OCC) {
+  s.family = family;
+  s.KT = KT; s.KH = KH; s.KW = KW; s.CC = CC; s.BM = BM; s.BN = BN; s.PCH = PCH; s.OCC = OCC;
+}
+
+// Everything conv3d_fwd_impl decides between plan_forward and the launch: the refusals, the 16-byte staging
+// predicates, the two-wave F(2x2,3x3) kernel and its fall-through, the launchers' tile / LDS arithmetic and
+// their refusals.  Returns what the launch returns before it launches.
+int select_forward(const coclr_conv_desc* d, const ConvPlan& p, int variant, const FwdQuery& q, FwdSel* out) {
+  FwdSel s;
+  memset(&s, 0, sizeof(s));
+  s.WW = p.WW; s.plane = p.plane;
+  s.lattice = d->ys_t > 0;
+  // backward sums: only in the kernels whose epilogue forms them
+  if (q.bwd_sums && (!bwd_sums_variant(variant) || q.n_index)) return COCLR_EINVAL;
+  // consumer-side BatchNorm apply: only the kernel that has the operand path for it, never with a gather
+  if (q.in_affine && (variant != 41 || q.n_index)) return COCLR_EINVAL;
+  const int x_cstride = p.Ti * p.Hi * p.Wi;
+  const int y_cstride = s.lattice ? d->yT * d->yH * d->yW : p.To * p.Ho * p.Wo;
+  const int CinP = pad_to(p.Cin, 32), CoutP = pad_to(p.Cout, 128);
+  // every byte offset a workgroup forms must stay below the descriptors' 2 GiB range
+  const double lim = 2147483648.0;
+  const double xs = q.n_index ? (double)(d->Nx > 0 ? d->Nx : p.N) : (double)(1 << p.lTN);
+  if ((xs * (double)d->x_nstride + (double)p.Cin * x_cstride) * 4.0 >= lim) return COCLR_EINVAL;
+  if (((double)(1 << p.lTN) * (double)d->y_nstride + (double)(p.Cout + 128) * y_cstride) * 4.0 >= lim)
+    return COCLR_EINVAL;
+  if ((double)d->kt * d->kh * d->kw * CinP * CoutP * 4.0 >= lim) return COCLR_EINVAL;
+  const bool xalign = (p.Wi % 4) == 0 && (x_cstride % 4) == 0 && (d->x_nstride % 4) == 0 && q.x16;
+  // stencils with no reach along the flattened (H,W) axis, everything 16-byte aligned:
+  // 16-byte LDS-DMA for the input window too
+  const bool xv4 = d->kh == 1 && d->kw == 1 && p.Hi == 1 && p.WH == 1 && p.sw == 1 && p.lTW >= 2 &&
+                   p.dt == 1 && p.dh == 1 && p.dw == 1 && (p.plane % 4) == 0 && xalign;
+  // (1,3,3) stride-1 pad-1 undilated stencils on rows of whole 16-byte granules: 16-byte window DMA
+  static const bool xg_off = getenv("COCLR_CONV_XG") && atoi(getenv("COCLR_CONV_XG")) == 0;
+  const bool xg = !xg_off && d->kt == 1 && d->kh == 3 && d->kw == 3 && p.sw == 1 && p.sh == 1 &&
+                  p.st == 1 && p.pw == 1 && p.dt == 1 && p.dh == 1 && p.dw == 1 && p.lTW >= 2 &&
+                  xalign && granule_count(p) <= 192;
+  // the temporal Winograd kernels: the same staging, their planners have checked stride and dilation
+  const bool xv4t = p.Hi == 1 && p.WH == 1 && p.lTW >= 2 && (p.plane % 4) == 0 && xalign;
+  int rc = COCLR_EINVAL;
+  switch (variant) {
+    // 16-byte-staged kernels run with HALF the channel chunk of their 4-byte forms: the chunk is what
+    // sizes the LDS stages, and two or three workgroups per CU became five or six.  Measured at B=32
+    // (same box, alternating): Conv_2b 0.082 -> 0.070 ms forward / 0.070 -> 0.059 data gradient, the
+    // fused heads of Mixed_3c 0.223 -> 0.20 / 0.19 -> 0.195, of Mixed_4b 0.058 -> 0.054 / 0.060 ->
+    // 0.051, Conv_1a.conv2 1.36 -> 1.31; the (1,3,3) small-map kernel did not move and keeps 8.
+    case 0: s.XV4 = xv4; sel_kernel(s, FF_IGEMM, 1, 1, 1, 32, 128, 128, 2, 0); break;
+    case 1: s.XV4 = xv4; sel_kernel(s, FF_IGEMM, 1, 1, 1, xv4 ? 16 : 32, 64, 128, 2, 0); break;
+    case 2: s.XV4 = xv4; sel_kernel(s, FF_IGEMM, 1, 1, 1, xv4 ? 16 : 32, 64, 64, 1, 0); break;
+    case 3: sel_kernel(s, FF_IGEMM, 1, 1, 1, 16, 64, 64, 4, 0); break;
+    case 10: s.XG = xg; sel_kernel(s, FF_IGEMM, 1, 3, 3, 4, 128, 128, xg ? 3 : 4, 0); break;
+    case 11: s.XG = xg; sel_kernel(s, FF_IGEMM, 1, 3, 3, 8, 64, 128, xg ? 3 : 4, 0); break;
+    case 12: s.XG = xg; sel_kernel(s, FF_IGEMM, 1, 3, 3, 8, 64, 64, xg ? 3 : 4, 0); break;
+    case 13: s.XG = xg; sel_kernel(s, FF_IGEMM, 1, 3, 3, 8, 64, 64, xg ? 3 : 8, 0); break;
+    case 20: s.XV4 = xv4; sel_kernel(s, FF_IGEMM, 3, 1, 1, 4, 128, 128, 4, 0); break;
+    case 21: s.XV4 = xv4; sel_kernel(s, FF_IGEMM, 3, 1, 1, 8, 64, 128, 4, 0); break;
+    case 22: s.XV4 = xv4; sel_kernel(s, FF_IGEMM, 3, 1, 1, 8, 64, 64, 4, 0); break;
+    case 25: s.XV4 = xv4; sel_kernel(s, FF_IGEMM, 4, 1, 1, 8, 64, 128, 4, 0); break;
+    case 30: sel_kernel(s, FF_IGEMM, 1, 7, 7, 4, 64, 128, 20, 0); break;
+    case 40: s.XV4 = xv4; sel_kernel(s, FF_IGEMM, 7, 1, 1, xv4 ? 4 : 8, 64, 128, 8, 0); break;
+    case 31: sel_kernel(s, FF_STEM, 1, 7, 7, 3, 64, 128, 20, 0); rc = sel_stem(s, p); break;
+    case 50:
+      // conv_wino_t_body has no gather path (it would read sample n where n_index[n] is meant): refuse, like the
+      // other Winograd forms
+      if (q.n_index) return COCLR_EINVAL;
+      // 8-channel chunks and a four-workgroups-per-CU register budget (accumulators in arch VGPRs,
+      // 99 registers; 27 KB of LDS): four waves per SIMD instead of three.  Measured at B=32 against
+      // the 16-channel / three-wave form: Conv_2c.conv2 1.02-1.06 -> 0.99 ms forward, 0.907 -> 0.874
+      // data gradient; Mixed_3c.b1.conv2 0.212 -> 0.204 / 0.205 -> 0.200; the 8x8x8 layers unchanged.
+      s.XV4 = xv4t;
+      sel_kernel(s, FF_WINO_T, 3, 1, 1, xv4t ? 8 : 16, 64, 64, 4, xv4t ? 4 : 1);
+      rc = sel_staged(s, p, 4, 0);
+      s.pairable = xv4t;
+      break;
+    case 51:
+    case 52:
+      if (q.n_index) return COCLR_EINVAL;
+      s.XV4 = xv4t;
+      s.form = variant == 52 ? 5 : 6;
+      sel_kernel(s, FF_WINO_TF, variant == 52 ? 4 : 3, 1, 1, 8, 64, 64, variant == 52 ? 4 : 6, 3);
+      rc = sel_staged(s, p, s.form, 0);
+      s.pairable = variant == 51 && xv4t && !s.lattice;
+      break;
+    case 41:
+      if (q.n_index) return COCLR_EINVAL;
+      s.XV4 = xv4t; s.INAFF = q.in_affine;
+      s.form = 9;
+      sel_kernel(s, FF_WINO_TF, 7, 1, 1, 8, 64, 64, 6, 2);
+      rc = sel_staged(s, p, 9, q.in_affine ? (size_t)2 * CinP * sizeof(float) : 0);
+      break;
+    case 60: {
+      if (q.n_index || !q.y8 || (d->y_nstride % 2) != 0) return COCLR_EINVAL;
+      // the destination keeps its full row pitch
+      const double ycs = (double)d->To * d->Ho * d->Wo;
+      if (((double)(1 << p.lTN) * (double)d->y_nstride + (double)(p.Cout + 128) * ycs) * 4.0 >= lim)
+        return COCLR_EINVAL;
+      if (16.0 * CinP * CoutP * 4.0 >= lim) return COCLR_EINVAL;
+      // 16-byte window DMA when every granule of an input row is 16-byte aligned and the widened
+      // window still fits three pieces per channel (LDS: 2 x (32 + 24) KiB of stages)
+      static const bool x16_off = getenv("COCLR_WINO_X16") && atoi(getenv("COCLR_WINO_X16")) == 0;
+      const int gran = ((p.WT * p.WH * (2 * (1 << p.lTW) + 8)) << p.lTN) / 4;
+      const bool x16 = !x16_off && p.lTW >= 1 && xalign && gran <= 192;
+      // two waves per SIMD (conv_wino_hw8_kernel) wherever it applies; COCLR_WINO_W8=0 (read per call:
+      // an A/B and test switch) keeps the one-wave kernel
+      const char* w8env = getenv("COCLR_WINO_W8");
+      const bool w8 = !(w8env && w8env[0] == '0');
+      s.X16 = x16;
+      if (x16 && w8) {
+        sel_kernel(s, FF_WINO_HW8, 1, 3, 3, 8, 64, 64, 3, 0);
+        rc = sel_wino_hw(s, p, true);
+      }
+      if (rc == COCLR_EINVAL) {
+        s.WW = p.WW; s.plane = p.plane;
+        sel_kernel(s, FF_WINO_HW, 1, 3, 3, 8, 64, 64, x16 ? 3 : (p.plane <= 384 ? 6 : 10), 0);
+        rc = sel_wino_hw(s, p, false);
+      }
+      break;
+    }
+    default: return COCLR_EINVAL;
+  }
+  if (s.family == FF_IGEMM) {
+    rc = sel_staged(s, p, s.KT * s.KH * s.KW, 0);
+    // pair kernels exist for the stencils sibling units of an inception block share: (1,3,3) of the two
+    // separable branches, 16-byte-staged (1,1,1) of the fused heads and the pool branch
+    s.pairable = s.KT == 1 && ((s.KH == 3 && s.KW == 3) || (s.KH == 1 && s.KW == 1 && s.XV4));
+  }
+  if (rc) return rc;
+  *out = s;
+  return 0;
+}
+
 // The launch behind coclr_conv3d_fwd.  With `slot`, variants that have a pair kernel fill it instead of
 // launching (see PairSlot).
 int conv3d_fwd_impl(const coclr_conv_desc* d, const float* x, const float* w_packed, float* y,
@@ -3288,67 +3521,60 @@ int conv3d_fwd_impl(const coclr_conv_desc* d, const float* x, const float* w_pac
     static const bool xcd_off = getenv("COCLR_XCD_MAP") && atoi(getenv("COCLR_XCD_MAP")) == 0;
     a.xcd = !xcd_off;
   }
-  // every byte offset a workgroup forms must stay below the descriptors' 2 GiB range
-  const double lim = 2147483648.0;
-  const double xs = n_index ? (double)(d->Nx > 0 ? d->Nx : p.N) : (double)(1 << p.lTN);
-  if ((xs * (double)a.x_nstride + (double)a.Cin * a.x_cstride) * 4.0 >= lim) return COCLR_EINVAL;
-  if (((double)(1 << p.lTN) * (double)a.y_nstride + (double)(a.Cout + 128) * a.y_cstride) * 4.0 >= lim)
-    return COCLR_EINVAL;
-  if ((double)d->kt * d->kh * d->kw * a.CinP * a.CoutP * 4.0 >= lim) return COCLR_EINVAL;
-  // stencils with no reach along the flattened (H,W) axis, everything 16-byte aligned:
-  // 16-byte LDS-DMA for the input window too
-  const bool xv4 = d->kh == 1 && d->kw == 1 && p.Hi == 1 && p.WH == 1 && p.sw == 1 && p.lTW >= 2 &&
-                   p.dt == 1 && p.dh == 1 && p.dw == 1 && (p.Wi % 4) == 0 && (p.plane % 4) == 0 &&
-                   (a.x_cstride % 4) == 0 && (a.x_nstride % 4) == 0 && ((uintptr_t)x % 16) == 0;
-  // (1,3,3) stride-1 pad-1 undilated stencils on rows of whole 16-byte granules: 16-byte window DMA
-  static const bool xg_off = getenv("COCLR_CONV_XG") && atoi(getenv("COCLR_CONV_XG")) == 0;
-  const bool xg = !xg_off && d->kt == 1 && d->kh == 3 && d->kw == 3 && p.sw == 1 && p.sh == 1 &&
-                  p.st == 1 && p.pw == 1 && p.dt == 1 && p.dh == 1 && p.dw == 1 && p.lTW >= 2 &&
-                  (p.Wi % 4) == 0 && (a.x_cstride % 4) == 0 && (a.x_nstride % 4) == 0 &&
-                  ((uintptr_t)x % 16) == 0 && granule_count(p) <= 192;
+  // the refusals, the staging predicates, the kernel and its launch geometry: select_forward
+  FwdQuery q;
+  q.x16 = ((uintptr_t)x % 16) == 0; q.y8 = ((uintptr_t)y % 8) == 0;
+  q.n_index = n_index != nullptr; q.in_affine = a.in_scale != nullptr; q.slot = slot != nullptr;
+  q.bwd_sums = a.bwd_y != nullptr;
+  FwdSel s;
+  rc = select_forward(d, p, variant, q, &s);
+  if (rc) return rc;
+  const bool xv4 = s.XV4, xg = s.XG;
+  PairSlot* const pslot = s.pairable ? slot : nullptr;
+  rc = COCLR_EINVAL;
   switch (variant) {
-    case 0:  return xv4 ? launch_variant<1, 1, 1, 32, 128, 128, 2, true>(a, p, stream, slot)
-                        : launch_variant<1, 1, 1, 32, 128, 128, 2>(a, p, stream);
-    // 16-byte-staged kernels run with HALF the channel chunk of their 4-byte forms: the chunk is what
-    // sizes the LDS stages, and two or three workgroups per CU became five or six.  Measured at B=32
-    // (same box, alternating): Conv_2b 0.082 -> 0.070 ms forward / 0.070 -> 0.059 data gradient, the
-    // fused heads of Mixed_3c 0.223 -> 0.20 / 0.19 -> 0.195, of Mixed_4b 0.058 -> 0.054 / 0.060 ->
-    // 0.051, Conv_1a.conv2 1.36 -> 1.31; the (1,3,3) small-map kernel did not move and keeps 8.
-    case 1:  return xv4 ? launch_variant<1, 1, 1, 16, 64, 128, 2, true>(a, p, stream, slot)
-                        : launch_variant<1, 1, 1, 32, 64, 128, 2>(a, p, stream);
-    case 2:  return xv4 ? launch_variant<1, 1, 1, 16, 64, 64, 1, true>(a, p, stream, slot)
-                        : launch_variant<1, 1, 1, 32, 64, 64, 1>(a, p, stream);
-    case 3:  return launch_variant<1, 1, 1, 16, 64, 64, 4>(a, p, stream);
-    case 10: return xg ? launch_variant<1, 3, 3, 4, 128, 128, 3, false, true>(a, p, stream, slot)
-                       : launch_variant<1, 3, 3, 4, 128, 128, 4>(a, p, stream, slot);
-    case 11: return xg ? launch_variant<1, 3, 3, 8, 64, 128, 3, false, true>(a, p, stream, slot)
-                       : launch_variant<1, 3, 3, 8, 64, 128, 4>(a, p, stream, slot);
-    case 12: return xg ? launch_variant<1, 3, 3, 8, 64, 64, 3, false, true>(a, p, stream, slot)
-                       : launch_variant<1, 3, 3, 8, 64, 64, 4>(a, p, stream, slot);
-    case 13: return xg ? launch_variant<1, 3, 3, 8, 64, 64, 3, false, true>(a, p, stream, slot)
-                       : launch_variant<1, 3, 3, 8, 64, 64, 8>(a, p, stream, slot);
-    case 20: return xv4 ? launch_variant<3, 1, 1, 4, 128, 128, 4, true>(a, p, stream)
-                        : launch_variant<3, 1, 1, 4, 128, 128, 4>(a, p, stream);
-    case 21: return xv4 ? launch_variant<3, 1, 1, 8, 64, 128, 4, true>(a, p, stream)
-                        : launch_variant<3, 1, 1, 8, 64, 128, 4>(a, p, stream);
-    case 22: return xv4 ? launch_variant<3, 1, 1, 8, 64, 64, 4, true>(a, p, stream)
-                        : launch_variant<3, 1, 1, 8, 64, 64, 4>(a, p, stream);
-    case 25: return xv4 ? launch_variant<4, 1, 1, 8, 64, 128, 4, true>(a, p, stream)
-                        : launch_variant<4, 1, 1, 8, 64, 128, 4>(a, p, stream);
+    case 0:  rc = xv4 ? launch_variant<1, 1, 1, 32, 128, 128, 2, true>(a, p, stream, pslot, &s)
+                      : launch_variant<1, 1, 1, 32, 128, 128, 2>(a, p, stream, nullptr, &s);
+             break;
+    case 1:  rc = xv4 ? launch_variant<1, 1, 1, 16, 64, 128, 2, true>(a, p, stream, pslot, &s)
+                      : launch_variant<1, 1, 1, 32, 64, 128, 2>(a, p, stream, nullptr, &s);
+             break;
+    case 2:  rc = xv4 ? launch_variant<1, 1, 1, 16, 64, 64, 1, true>(a, p, stream, pslot, &s)
+                      : launch_variant<1, 1, 1, 32, 64, 64, 1>(a, p, stream, nullptr, &s);
+             break;
+    case 3:  rc = launch_variant<1, 1, 1, 16, 64, 64, 4>(a, p, stream, nullptr, &s); break;
+    case 10: rc = xg ? launch_variant<1, 3, 3, 4, 128, 128, 3, false, true>(a, p, stream, pslot, &s)
+                     : launch_variant<1, 3, 3, 4, 128, 128, 4>(a, p, stream, pslot, &s);
+             break;
+    case 11: rc = xg ? launch_variant<1, 3, 3, 8, 64, 128, 3, false, true>(a, p, stream, pslot, &s)
+                     : launch_variant<1, 3, 3, 8, 64, 128, 4>(a, p, stream, pslot, &s);
+             break;
+    case 12: rc = xg ? launch_variant<1, 3, 3, 8, 64, 64, 3, false, true>(a, p, stream, pslot, &s)
+                     : launch_variant<1, 3, 3, 8, 64, 64, 4>(a, p, stream, pslot, &s);
+             break;
+    case 13: rc = xg ? launch_variant<1, 3, 3, 8, 64, 64, 3, false, true>(a, p, stream, pslot, &s)
+                     : launch_variant<1, 3, 3, 8, 64, 64, 8>(a, p, stream, pslot, &s);
+             break;
+    case 20: rc = xv4 ? launch_variant<3, 1, 1, 4, 128, 128, 4, true>(a, p, stream, nullptr, &s)
+                      : launch_variant<3, 1, 1, 4, 128, 128, 4>(a, p, stream, nullptr, &s);
+             break;
+    case 21: rc = xv4 ? launch_variant<3, 1, 1, 8, 64, 128, 4, true>(a, p, stream, nullptr, &s)
+                      : launch_variant<3, 1, 1, 8, 64, 128, 4>(a, p, stream, nullptr, &s);
+             break;
+    case 22: rc = xv4 ? launch_variant<3, 1, 1, 8, 64, 64, 4, true>(a, p, stream, nullptr, &s)
+                      : launch_variant<3, 1, 1, 8, 64, 64, 4>(a, p, stream, nullptr, &s);
+             break;
+    case 25: rc = xv4 ? launch_variant<4, 1, 1, 8, 64, 128, 4, true>(a, p, stream, nullptr, &s)
+                      : launch_variant<4, 1, 1, 8, 64, 128, 4>(a, p, stream, nullptr, &s);
+             break;
     case 50: {
       // a.To = frame pairs; the kernel finds the frame count in yst and the plane pitch in yHf/yWf
       a.yst = d->To; a.yHf = p.Ho; a.yWf = p.Wo;
       a.y_cstride = d->To * p.Ho * p.Wo;
       a.st = 1;
-      const bool xv4 = p.Hi == 1 && p.WH == 1 && p.lTW >= 2 && (p.Wi % 4) == 0 &&
-                       (a.x_cstride % 4) == 0 && (a.x_nstride % 4) == 0 && ((uintptr_t)x % 16) == 0 &&
-                       (p.plane % 4) == 0;
-      // 8-channel chunks and a four-workgroups-per-CU register budget (accumulators in arch VGPRs,
-      // 99 registers; 27 KB of LDS): four waves per SIMD instead of three.  Measured at B=32 against
-      // the 16-channel / three-wave form: Conv_2c.conv2 1.02-1.06 -> 0.99 ms forward, 0.907 -> 0.874
-      // data gradient; Mixed_3c.b1.conv2 0.212 -> 0.204 / 0.205 -> 0.200; the 8x8x8 layers unchanged.
-      if (xv4) return launch_wino_t<8, 64, 64, 4, true, 4>(a, p, stream, slot);
-      return launch_wino_t<16, 64, 64, 4, false>(a, p, stream);
+      rc = xv4 ? launch_wino_t<8, 64, 64, 4, true, 4>(a, p, stream, pslot, &s)
+               : launch_wino_t<16, 64, 64, 4, false>(a, p, stream, nullptr, &s);
+      break;
     }
     case 51:
     case 52: {
@@ -3360,87 +3586,88 @@ int conv3d_fwd_impl(const coclr_conv_desc* d, const float* x, const float* w_pac
         a.y_cstride = d->To * p.Ho * p.Wo;
       }
       a.st = 1;
-      const bool xv4 = p.Hi == 1 && p.WH == 1 && p.lTW >= 2 && (p.Wi % 4) == 0 &&
-                       (a.x_cstride % 4) == 0 && (a.x_nstride % 4) == 0 && ((uintptr_t)x % 16) == 0 &&
-                       (p.plane % 4) == 0;
-      if (n_index) return COCLR_EINVAL;
-      if (variant == 52) {
-        if (xv4) return launch_wino_tf<WinoF24, 8, 64, 64, 4, true, 3>(a, p, stream);
-        return launch_wino_tf<WinoF24, 8, 64, 64, 4, false, 3>(a, p, stream);
-      }
-      if (xv4) return launch_wino_tf<WinoF43, 8, 64, 64, 6, true, 3>(a, p, stream, slot && !lattice ? slot : nullptr);
-      return launch_wino_tf<WinoF43, 8, 64, 64, 6, false, 3>(a, p, stream);
+      if (variant == 52)
+        rc = xv4 ? launch_wino_tf<WinoF24, 8, 64, 64, 4, true, 3>(a, p, stream, nullptr, &s)
+                 : launch_wino_tf<WinoF24, 8, 64, 64, 4, false, 3>(a, p, stream, nullptr, &s);
+      else
+        rc = xv4 ? launch_wino_tf<WinoF43, 8, 64, 64, 6, true, 3>(a, p, stream, pslot, &s)
+                 : launch_wino_tf<WinoF43, 8, 64, 64, 6, false, 3>(a, p, stream, nullptr, &s);
+      break;
     }
     case 60: {
       // a.Ho/Wo = 2x2 blocks; the destination keeps its full row pitch
-      if (n_index || ((uintptr_t)y % 8) != 0 || (a.y_nstride % 2) != 0) return COCLR_EINVAL;
       a.yHf = d->Ho; a.yWf = d->Wo;
       a.y_cstride = d->To * d->Ho * d->Wo;
-      if ((((double)(1 << p.lTN)) * (double)a.y_nstride + (double)(a.Cout + 128) * a.y_cstride) * 4.0 >= lim)
-        return COCLR_EINVAL;
-      if (16.0 * a.CinP * a.CoutP * 4.0 >= lim) return COCLR_EINVAL;
-      {
-        // 16-byte window DMA when every granule of an input row is 16-byte aligned and the widened
-        // window still fits three pieces per channel (LDS: 2 x (32 + 24) KiB of stages)
-        static const bool x16_off = getenv("COCLR_WINO_X16") && atoi(getenv("COCLR_WINO_X16")) == 0;
-        const int gran = ((p.WT * p.WH * (2 * (1 << p.lTW) + 8)) << p.lTN) / 4;
-        const bool x16 = !x16_off && p.lTW >= 1 && (p.Wi % 4) == 0 && (a.x_cstride % 4) == 0 &&
-                         (a.x_nstride % 4) == 0 && ((uintptr_t)x % 16) == 0 && gran <= 192;
-        // two waves per SIMD (conv_wino_hw8_kernel) wherever it applies; COCLR_WINO_W8=0 (read per call:
-        // an A/B and test switch) keeps the one-wave kernel
-        const char* w8env = getenv("COCLR_WINO_W8");
-        const bool w8 = !(w8env && w8env[0] == '0');
-        if (x16 && w8) {
-          int rc8 = launch_wino_hw8<8, 3>(a, p, stream);
-          if (rc8 != COCLR_EINVAL) return rc8;
-        }
-        if (x16) {
+      if (s.family == FF_WINO_HW8) { rc = launch_wino_hw8<8, 3>(a, p, stream, &s); break; }
+      if (s.X16) {
 #ifdef COCLR_WINO_ABLATE
-          // timing ablations (wrong results by design; build with -DCOCLR_WINO_ABLATE, tools/wino_ablate.sh):
-          // 1 no window DMA, 2 no weight DMA, 8 no statistics, 16 no patch reads + input transform,
-          // 32 no weight reads.  Measured at B=32 on Conv_2c.conv1 forward (0.797 ms): 1 -> 0.737,
-          // 2 -> 0.782, 3 -> 0.673, 8 -> 0.785, 16 -> 0.682, 32 -> 0.755, 48 -> 0.555.
-          static const int abl = getenv("COCLR_WINO_ABL") ? atoi(getenv("COCLR_WINO_ABL")) : 0;
-          switch (abl) {
-            case 1: return launch_wino_hw<8, 3, true, 1>(a, p, stream);
-            case 2: return launch_wino_hw<8, 3, true, 2>(a, p, stream);
-            case 3: return launch_wino_hw<8, 3, true, 3>(a, p, stream);
-            case 8: return launch_wino_hw<8, 3, true, 8>(a, p, stream);
-            case 16: return launch_wino_hw<8, 3, true, 16>(a, p, stream);
-            case 32: return launch_wino_hw<8, 3, true, 32>(a, p, stream);
-            case 48: return launch_wino_hw<8, 3, true, 48>(a, p, stream);
-            default: break;
-          }
-#endif
-          return launch_wino_hw<8, 3, true>(a, p, stream);
+        // timing ablations (wrong results by design; build with -DCOCLR_WINO_ABLATE, tools/wino_ablate.sh):
+        // 1 no window DMA, 2 no weight DMA, 8 no statistics, 16 no patch reads + input transform,
+        // 32 no weight reads.  Measured at B=32 on Conv_2c.conv1 forward (0.797 ms): 1 -> 0.737,
+        // 2 -> 0.782, 3 -> 0.673, 8 -> 0.785, 16 -> 0.682, 32 -> 0.755, 48 -> 0.555.
+        static const int abl = getenv("COCLR_WINO_ABL") ? atoi(getenv("COCLR_WINO_ABL")) : 0;
+        switch (abl) {
+          case 1: return launch_wino_hw<8, 3, true, 1>(a, p, stream, &s);
+          case 2: return launch_wino_hw<8, 3, true, 2>(a, p, stream, &s);
+          case 3: return launch_wino_hw<8, 3, true, 3>(a, p, stream, &s);
+          case 8: return launch_wino_hw<8, 3, true, 8>(a, p, stream, &s);
+          case 16: return launch_wino_hw<8, 3, true, 16>(a, p, stream, &s);
+          case 32: return launch_wino_hw<8, 3, true, 32>(a, p, stream, &s);
+          case 48: return launch_wino_hw<8, 3, true, 48>(a, p, stream, &s);
+          default: break;
         }
+#endif
+        rc = launch_wino_hw<8, 3, true>(a, p, stream, &s);
+        break;
       }
-      return p.plane <= 384 ? launch_wino_hw<8, 6>(a, p, stream) : launch_wino_hw<8, 10>(a, p, stream);
+      rc = s.PCH == 6 ? launch_wino_hw<8, 6>(a, p, stream, &s) : launch_wino_hw<8, 10>(a, p, stream, &s);
+      break;
     }
-    case 30: return launch_variant<1, 7, 7, 4, 64, 128, 20>(a, p, stream);
-    case 31: return launch_stem<7, 7, 3, 20>(a, p, stream);
+    case 30: rc = launch_variant<1, 7, 7, 4, 64, 128, 20>(a, p, stream, nullptr, &s); break;
+    case 31: rc = launch_stem<7, 7, 3, 20>(a, p, stream, &s); break;
     case 41: {
       // a.To = output pairs; the kernel finds the frame count in yst and the plane pitch in yHf/yWf
       a.yst = d->To; a.yHf = p.Ho; a.yWf = p.Wo;
       a.y_cstride = d->To * p.Ho * p.Wo;
       a.st = 1; a.pt = 3;
-      const bool xv4p = p.Hi == 1 && p.WH == 1 && p.lTW >= 2 && (p.Wi % 4) == 0 &&
-                        (a.x_cstride % 4) == 0 && (a.x_nstride % 4) == 0 && ((uintptr_t)x % 16) == 0 &&
-                        (p.plane % 4) == 0;
-      if (n_index) return COCLR_EINVAL;
-      if (a.in_scale)
-        return xv4p ? launch_wino_tf<StemPoly7, 8, 64, 64, 6, true, 2, true>(a, p, stream)
-                    : launch_wino_tf<StemPoly7, 8, 64, 64, 6, false, 2, true>(a, p, stream);
-      if (xv4p) return launch_wino_tf<StemPoly7, 8, 64, 64, 6, true, 2>(a, p, stream);
-      return launch_wino_tf<StemPoly7, 8, 64, 64, 6, false, 2>(a, p, stream);
+      if (s.INAFF)
+        rc = xv4 ? launch_wino_tf<StemPoly7, 8, 64, 64, 6, true, 2, true>(a, p, stream, nullptr, &s)
+                 : launch_wino_tf<StemPoly7, 8, 64, 64, 6, false, 2, true>(a, p, stream, nullptr, &s);
+      else
+        rc = xv4 ? launch_wino_tf<StemPoly7, 8, 64, 64, 6, true, 2>(a, p, stream, nullptr, &s)
+                 : launch_wino_tf<StemPoly7, 8, 64, 64, 6, false, 2>(a, p, stream, nullptr, &s);
+      break;
     }
-    case 40: return xv4 ? launch_variant<7, 1, 1, 4, 64, 128, 8, true>(a, p, stream)
-                        : launch_variant<7, 1, 1, 8, 64, 128, 8>(a, p, stream);
+    case 40: rc = xv4 ? launch_variant<7, 1, 1, 4, 64, 128, 8, true>(a, p, stream, nullptr, &s)
+                      : launch_variant<7, 1, 1, 8, 64, 128, 8>(a, p, stream, nullptr, &s);
+             break;
   }
-  return COCLR_EINVAL;
+  if (rc) return rc;
+  return 0;
 }
 
 }  // namespace
+
+extern "C" int coclr_conv3d_fwd_plan(const coclr_conv_desc* d, int flags, int32_t out[40]) {
+  if (!d || !out) return COCLR_EINVAL;
+  ConvPlan p;
+  int variant;
+  int rc = plan_forward(d, &p, &variant);
+  if (rc) return rc;
+  FwdQuery q;
+  q.x16 = (flags & 1) != 0; q.y8 = (flags & 2) != 0; q.n_index = (flags & 4) != 0;
+  q.in_affine = (flags & 8) != 0; q.slot = (flags & 16) != 0; q.bwd_sums = (flags & 32) != 0;
+  FwdSel s;
+  rc = select_forward(d, p, variant, q, &s);
+  if (rc) return rc;
+  const int32_t v[40] = {variant, s.family, s.form, s.KT, s.KH, s.KW, s.CC, s.BM, s.BN, s.PCH,
+                         s.OCC, s.XV4, s.XG, s.X16, s.INAFF, s.lattice, s.pairable, p.lTW, p.lTH, p.lTT,
+                         p.lTN, p.WT, p.WH, s.WW, s.plane, p.ntiles, s.mtiles, s.nchunks, s.planeS, (int32_t)s.lds,
+                         (int32_t)s.grid, s.threads, s.pairable && q.slot, p.nboxes, p.nbw, p.nbh, p.nbt, p.nbn,
+                         bwd_sums_variant(variant), 0};
+  for (int i = 0; i < 40; ++i) out[i] = v[i];
+  return 0;
+}
 
 extern "C" int coclr_conv3d_fwd(const coclr_conv_desc* d, const float* x, const float* w_packed,
                                 float* y, float* stats, const float* bias, const float* ep_scale,

@@ -759,8 +759,8 @@ def conv_bn_act_gen(run, x, conv, bn, relu=True, out=None, residual=None, n_inde
         geoms = _sliced_geoms(N, Cin, Cout, idim, k, s, p)
     else:
         geoms = [ops.conv_geom(N, Cin, Cout, idim, k, s, p)]
-        if n_index is not None and geoms[0].algo and k[1] > 1:
-            geoms = [ops.ConvGeom(N, Cin, Cout, idim, k, s, p)]    # the gather lives in the direct kernel
+        if n_index is not None and geoms[0].algo:
+            geoms = [ops.ConvGeom(N, Cin, Cout, idim, k, s, p)]    # the gather lives in the direct kernels
     # The input is a BatchNorm unit whose apply pass has not run (Val.lazy) and this convolution's kernel can apply
     # relu(y * scale + shift) while it reads (the polyphase temporal stem conv): the normalised tensor -- 1 GB at
     # B = 32 behind Conv_1a.conv1 -- is never written or re-read.  Only in passes that keep no tape: the weight

@@ -294,6 +294,36 @@ class ConvGeom:
                     mt=out[7], lTW=out[8], lTH=out[9], lTT=out[10], lTN=out[11], ntiles=out[12],
                     tile_order=bool(out[13]), bn=bool(out[14]), rebox=bool(out[15]))
 
+    _FWD_FAMILIES = ("igemm", "wino_t", "wino_tf", "wino_hw", "wino_hw8", "stem")
+    _FWD_FIELDS = ("variant", "family", "form", "KT", "KH", "KW", "CC", "BM", "BN", "PCH", "OCC", "XV4", "XG",
+                   "X16", "INAFF", "lattice", "pairable", "lTW", "lTH", "lTT", "lTN", "WT", "WH", "WW", "plane",
+                   "ntiles", "mtiles", "nchunks", "planeS", "lds", "grid", "threads", "slot_filled", "nboxes",
+                   "nbw", "nbh", "nbt", "nbn", "bwd_sums_ok")
+
+    def fwd_plan(self, x_aligned=True, y_aligned=True, n_index=False, in_affine=False, slot=False,
+                 bwd_sums=False, x_nstride=None, y_nstride=None, Nx=None):
+        """What conv_fwd / conv_fwd_multi would launch for this geometry, from the launcher's own planner and
+        kernel selection (nothing is launched): a dict of the fields of coclr_conv3d_fwd_plan, `family` by name,
+        the flags as bools.  x_aligned: x is 16-byte aligned; y_aligned: y is 8-byte aligned; x_nstride /
+        y_nstride / Nx: the operands' sample strides and the samples behind an n_index (default: dense tensors).
+        A combination the launch refuses raises HipLibraryError exactly as the launch would."""
+        d = ConvDesc.from_buffer_copy(self.desc)
+        d.x_nstride = x_nstride or self.Cin * self.idim[0] * self.idim[1] * self.idim[2]
+        if y_nstride is None:
+            full = self.lattice[2] if self.lattice is not None else self.odim
+            y_nstride = self.Cout * full[0] * full[1] * full[2]
+        d.y_nstride = y_nstride
+        d.Nx = Nx or self.N
+        flags = (1 * bool(x_aligned) | 2 * bool(y_aligned) | 4 * bool(n_index) | 8 * bool(in_affine) |
+                 16 * bool(slot) | 32 * bool(bwd_sums))
+        out = (C.c_int32 * 40)()
+        _lib.check(_L().coclr_conv3d_fwd_plan(C.byref(d), flags, out), "conv3d_fwd_plan", self)
+        r = dict(zip(self._FWD_FIELDS, out))
+        r["family"] = self._FWD_FAMILIES[r["family"]]
+        for k in ("XV4", "XG", "X16", "INAFF", "lattice", "pairable", "slot_filled", "bwd_sums_ok"):
+            r[k] = bool(r[k])
+        return r
+
     def __repr__(self):
         return "ConvGeom(N=%d, %d->%d, in=%s, out=%s, k=%s, s=%s, p=%s, d=%s)" % (
             self.N, self.Cin, self.Cout, self.idim, self.odim, self.k, self.s, self.p, self.d)

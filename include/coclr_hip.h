@@ -55,7 +55,7 @@ typedef struct coclr_conv_desc {
   int32_t Nx;              /* samples addressable through n_index (0: N) */
   int32_t algo;            /* 0: direct; 1: Winograd, w_packed must then be the transform-domain
                               operand made by coclr_conv_pack_weights(transpose | 2):
-                              (3,1,1) stencil, stride 1, pad (1,0,0): F(2,3) along T, taps = 4;
+                              (3,1,1) stencil, stride 1, pad (1,0,0), no n_index: F(2,3) along T, taps = 4;
                               (1,3,3) stencil, stride 1, pad (0,1,1), even Ho/Wo >= 4, dense
                               destination, no n_index: F(2x2,3x3), taps = 16;
                               (7,1,1) stencil, stride (2,1,1), pad (3,0,0), Ti = 2 To, >= 8 output
@@ -116,7 +116,8 @@ int coclr_conv3d_ntiles(const coclr_conv_desc* d, int* ntiles);
  * sum / sum-of-squares of the raw conv output for train-mode BatchNorm
  * (backbone/s3dg.py:16,46-47).  n_index (optional): x sample n is read from
  * sample n_index[n] -- the shuffle-BN row gather of model/pretrain.py:124
- * folded into the first conv. */
+ * folded into the first conv.  Only the direct kernels gather: COCLR_EINVAL with
+ * algo >= 1. */
 int coclr_conv3d_fwd(const coclr_conv_desc* d, const float* x, const float* w_packed, float* y,
                      float* stats, const float* bias, const float* ep_scale,
                      const float* ep_shift, const int64_t* n_index, int relu, int accumulate,
@@ -168,6 +169,29 @@ typedef struct coclr_conv_call {
 } coclr_conv_call;
 int coclr_conv3d_fwd_multi(const coclr_conv_call* calls, int n, void* stream);
 int coclr_conv3d_bwd_sums_ok(const coclr_conv_desc* d, int* ok);
+
+/* What coclr_conv3d_fwd / coclr_conv3d_fwd_multi would launch for this descriptor (x_nstride, y_nstride and Nx
+ * filled in as for the launch); launches nothing (ABI 24).  Comes from the launcher's own planner and kernel
+ * selection, so a test can assert which instantiation a geometry reaches.  Returns what the launch would return
+ * before launching (COCLR_EINVAL for a refused combination).
+ * flags: 1 x is 16-byte aligned, 2 y is 8-byte aligned, 4 an n_index is given, 8 an in-affine (in_scale) is given,
+ *        16 the call sits in a pair slot of coclr_conv3d_fwd_multi, 32 backward sums (bwd_y) are asked for.
+ * out:
+ *   [0]  planner variant
+ *   [1]  kernel family: 0 conv_igemm_kernel, 1 conv_wino_t_kernel (F(2,3)), 2 conv_wino_tf_kernel,
+ *        3 conv_wino_hw_kernel, 4 conv_wino_hw8_kernel, 5 conv_stem_kernel
+ *   [2]  family 2: matrices of the form (6: F(4,3), 5: F(2,4), 9: polyphase stem); 0 otherwise
+ *   [3..10]  template numbers KT KH KW CC BM BN PCH OCC (0: the kernel has none)
+ *   [11..16] XV4, XG, X16, INAFF, destination lattice, pairable (a two-problem kernel exists and would be used)
+ *   [17..20] log2 box extents lTW lTH lTT lTN
+ *   [21..24] window WT WH WW (floats; widened to whole granules by XG / X16) and plane (floats; granules with
+ *            XG / X16)
+ *   [25..28] ntiles, mtiles, nchunks, planeS (LDS pitch of a staged channel)
+ *   [29..31] dynamic LDS bytes, workgroups, threads per workgroup
+ *   [32] 1 if this call would fill its pair slot instead of launching
+ *   [33..37] boxes covering the output and their count per axis (w, h, t, n)
+ *   [38] 1 if the kernel can form backward sums (coclr_conv3d_bwd_sums_ok) */
+int coclr_conv3d_fwd_plan(const coclr_conv_desc* d, int flags, int32_t out[40]);
 
 /* Split-K workspace (fp32 elements) for coclr_conv3d_wgrad. */
 int coclr_conv3d_wgrad_workspace(const coclr_conv_desc* d, int64_t* elems);
