@@ -182,6 +182,84 @@ stage_crops_kernel(const CropArgs a) {
   }
 }
 
+// ---- RandomSizedCrop boxes of a training batch (utils/augmentation.py:90-138) ---------------------------------------
+// crop (x0, y0, w, h) -> Image.resize((S, S), BICUBIC): the body of stage_crops_kernel<true> with the box, its SIZE and
+// its tables per output clip.  A descriptor per clip (device data, int32 x BOX_FIELDS) names the clip's first frame,
+// its box and where its tables start in the two concatenated table buffers: per box and axis `min[Sp]` followed by
+// `k[taps][Sp]`.  No flip here: the reference flips after the resize (kind 7 of the augment kernel below).
+// The descriptors are device data like the tables: every field is clamped into the frame / the table buffers, so
+// whatever they hold nothing is out of bounds (the entry point validates the host copy before the launch).
+enum { BOX_FIRST = 0, BOX_FRAMES, BOX_X0, BOX_Y0, BOX_W, BOX_H, BOX_XOFF, BOX_YOFF, BOX_XTAPS, BOX_YTAPS, BOX_FIELDS };
+
+struct BoxArgs {
+  const uint8_t* frames; const int32_t* desc;
+  const int32_t *xtab, *ytab;                // per box: min[Sp], k[taps][Sp]
+  uint8_t* out8;                             // [n_clips*T][S][S][3]
+  int F, H, W, T, S, Sp, R, cap_rows, xlen, ylen;
+};
+
+__global__ void __launch_bounds__(256)
+resize_boxes_kernel(const BoxArgs a) {
+  extern __shared__ __align__(16) uint8_t hrows[];      // [rows][3][Sp]
+  const int tid = threadIdx.x;
+  const int band = blockIdx.x, slot = blockIdx.y;
+  const int clip = slot / a.T, t = slot % a.T;
+  const int32_t* d = a.desc + (long)clip * BOX_FIELDS;
+  const int Sp = a.Sp, nxg = Sp >> 2;
+  const int f = clampi(d[BOX_FIRST] + t, 0, a.F - 1);
+  const int x0 = clampi(d[BOX_X0], 0, a.W - 1), y0 = clampi(d[BOX_Y0], 0, a.H - 1);
+  const int cw = clampi(d[BOX_W], 1, a.W - x0), ch = clampi(d[BOX_H], 1, a.H - y0);
+  const int xtaps = clampi(d[BOX_XTAPS], 1, min(64, a.xlen / Sp - 1));
+  const int ytaps = clampi(d[BOX_YTAPS], 1, min(64, a.ylen / Sp - 1));
+  const int32_t* xmin = a.xtab + clampi(d[BOX_XOFF] & ~3, 0, a.xlen - Sp * (1 + xtaps));
+  const int32_t* ymin = a.ytab + clampi(d[BOX_YOFF] & ~3, 0, a.ylen - Sp * (1 + ytaps));
+  const int32_t *xk = xmin + Sp, *yk = ymin + Sp;
+  const int r0 = band * a.R, r1 = min(r0 + a.R, a.S);                  // output rows [r0, r1)
+  const int ylo = clampi(ymin[r0], 0, ch - 1);
+  const int rows = min(clampi(ymin[r1 - 1] + ytaps, ylo + 1, ch) - ylo, a.cap_rows);
+  const uint8_t* fr = a.frames + ((long)f * a.H + (y0 + ylo)) * (long)a.W * 3 + x0 * 3;
+
+  // horizontal pass: item = (row, c, xg), xg fastest
+  for (int it = tid; it < rows * 3 * nxg; it += 256) {
+    const int xg = it % nxg, rc = it / nxg;
+    const int c = rc % 3, row = rc / 3;
+    const uint8_t* src = fr + (long)row * a.W * 3 + c;
+    const int4 xm = reinterpret_cast<const int4*>(xmin)[xg];
+    int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+    for (int i = 0; i < xtaps; ++i) {
+      const int4 k = reinterpret_cast<const int4*>(xk + (long)i * Sp)[xg];
+      a0 += k.x * (int)src[3 * clampi(xm.x + i, 0, cw - 1)];
+      a1 += k.y * (int)src[3 * clampi(xm.y + i, 0, cw - 1)];
+      a2 += k.z * (int)src[3 * clampi(xm.z + i, 0, cw - 1)];
+      a3 += k.w * (int)src[3 * clampi(xm.w + i, 0, cw - 1)];
+    }
+    reinterpret_cast<unsigned*>(hrows)[(row * 3 + c) * nxg + xg] =
+        fix8(a0) | (fix8(a1) << 8) | (fix8(a2) << 16) | (fix8(a3) << 24);
+  }
+  __syncthreads();
+
+  // vertical pass: item = (r, c, xg), xg fastest
+  for (int it = tid; it < (r1 - r0) * 3 * nxg; it += 256) {
+    const int xg = it % nxg, rc = it / nxg;
+    const int c = rc % 3, r = r0 + rc / 3;
+    const int ym = ymin[r] - ylo;
+    int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+    for (int i = 0; i < ytaps; ++i) {
+      const int k = yk[(long)i * Sp + r];
+      const unsigned w = reinterpret_cast<const unsigned*>(hrows)[(clampi(ym + i, 0, rows - 1) * 3 + c) * nxg + xg];
+      a0 += k * (int)(w & 255u);
+      a1 += k * (int)((w >> 8) & 255u);
+      a2 += k * (int)((w >> 16) & 255u);
+      a3 += k * (int)(w >> 24);
+    }
+    const unsigned v[4] = {fix8(a0), fix8(a1), fix8(a2), fix8(a3)};
+    uint8_t* dst = a.out8 + ((((long)slot * a.S + r) * (long)a.S + xg * 4) * 3 + c);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (xg * 4 + j < a.S) dst[3 * j] = (uint8_t)v[j];
+  }
+}
+
 // ---- ColorJitter / RandomGray on uint8 frames (utils/augmentation.py:179-320, through torchvision 0.5's
 // functional on PIL: ImageEnhance.Brightness/Contrast/Color, convert('HSV') + uint8 add + convert('RGB')) ----------
 // One workgroup owns one frame and runs its group's program (up to 8 ops, device tables) on the frame's bytes in
@@ -196,14 +274,34 @@ stage_crops_kernel(const CropArgs a) {
 // into (clip, 3, T, H, W).  A program without contrast is one pass, global to global, and asks for no LDS.
 // The tables are device data: an unknown kind does nothing, a gray channel is clamped, a hue shift is taken mod
 // 256, and contrast is ignored when the launch brought no LDS -- whatever they hold, nothing is out of bounds.
-enum { JIT_NOP = 0, JIT_BRIGHTNESS = 1, JIT_CONTRAST = 2, JIT_SATURATION = 3, JIT_HUE = 4, JIT_GRAY = 5 };
+//
+// The augment form (AUG, coclr_augment_clips) adds the two ops the training transform needs:
+//   blur  ImageFilter.GaussianBlur on 8-bit pixels = three box blurs along x, then three along y, each rounded to
+//         bytes: out = (ww * sum_{|d| <= r} x[i+d] + fw * (x[i-r-1] + x[i+r+1]) + 2^23) >> 24 in uint32, indices
+//         clamped to the line (PIL's edge replication), r = int(r_f), ww = uint32(2^24 / (2 r_f + 1)) in fp32,
+//         fw = (2^24 - (2r+1) ww) / 2; the parameter is r_f, the fp32 box radius the host derived from sigma.
+//         It is a whole-frame op like contrast: the program is cut there too, the bytes are parked, and six line
+//         passes run on the parked frame IN PLACE -- a lane computes all its items (up to 13 x 3 dwords at
+//         224 x 224) into registers, barrier, writes them, barrier: the frame fills the LDS, there is no second
+//         buffer.  A lane keeps its items (four pixels consecutive along x) in BOTH directions, so its LDS address
+//         is 12 * lane + a wave-uniform offset per tap: 3 dwords between lanes, odd, conflict-free for the byte
+//         reads of the horizontal pass and the dword reads of the vertical one (W % 4 == 0: the rows above and
+//         below an item are whole items; otherwise bytes).
+//   flip  transpose(FLIP_LEFT_RIGHT).  It commutes with every other op bit for bit (pointwise ops and whole-frame
+//         sums do not see the column; the blur's clamping is symmetric and its sums are integers), so an odd
+//         number of flips in the program mirrors the column of the final store and nothing else.
+enum { JIT_NOP = 0, JIT_BRIGHTNESS = 1, JIT_CONTRAST = 2, JIT_SATURATION = 3, JIT_HUE = 4, JIT_GRAY = 5, JIT_BLUR = 6,
+       JIT_FLIP = 7 };
 constexpr int kJitThreads = 512;
 constexpr int kJitMaxPixels = 224 * 224;
+constexpr int kAugThreads = 1024;            // the augment form: 13 items a lane to hold across the blur's barrier
+constexpr int kBlurMaxIter = (kJitMaxPixels / 4 + kAugThreads - 1) / kAugThreads;
+constexpr float kBlurMaxRadius = 16.f;
 
 struct JitterArgs {
   const uint8_t* frames; const int32_t* kinds; const float* params; float* out;
   float mean[3], std[3];
-  int HW, T, P, G, group_size, items, vec, use_lds;
+  int HW, T, P, G, group_size, items, vec, use_lds, H, W;
 };
 
 __device__ __forceinline__ int lum8(int r, int g, int b) {          // PIL's convert('L')
@@ -258,10 +356,70 @@ __device__ __forceinline__ void hue8(int& r, int& g, int& b, int shift) {
   }
 }
 
-__global__ void __launch_bounds__(kJitThreads)
+// One of PIL's six box-blur line passes over the parked frame (bytes as they lie in memory), in place.
+__device__ __forceinline__ void blur_pass(unsigned* parked, int tid, int items, int HW, int H, int W, bool vertical,
+                                          int r, unsigned ww, unsigned fw) {
+  const uint8_t* px = reinterpret_cast<const uint8_t*>(parked);
+  // the six passes share every lane's pixel coordinates; held across all of them they cost more registers than the
+  // divisions they save, so each pass derives its own from a width the compiler cannot see through
+  asm volatile("" : "+s"(W));
+  const bool rows_are_items = vertical && (W & 3) == 0;
+  unsigned keep[kBlurMaxIter][3];
+#pragma unroll
+  for (int k = 0; k < kBlurMaxIter; ++k) {
+    const int it = tid + k * kAugThreads;
+    keep[k][0] = keep[k][1] = keep[k][2] = 0u;
+    if (it < items) {
+      unsigned acc[12];
+#pragma unroll
+      for (int e = 0; e < 12; ++e) acc[e] = 1u << 23;
+      int y = (it * 4) / W, x = it * 4 - y * W;
+      if (rows_are_items) {
+        for (int d = -r - 1; d <= r + 1; ++d) {
+          const unsigned wgt = (d == -r - 1 || d == r + 1) ? fw : ww;
+          const unsigned* s = parked + (long)((clampi(y + d, 0, H - 1) * W + x) >> 2) * 3;
+          const unsigned w[3] = {s[0], s[1], s[2]};
+#pragma unroll
+          for (int e = 0; e < 12; ++e) acc[e] += wgt * ((w[e >> 2] >> (8 * (e & 3))) & 255u);
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          while (x >= W) { x -= W; ++y; }
+          if (it * 4 + q < HW) {
+            const int n = vertical ? H : W, i = vertical ? y : x;
+            const int stride = vertical ? W * 3 : 3, base = vertical ? x * 3 : y * W * 3;
+            for (int d = -r - 1; d <= r + 1; ++d) {
+              const unsigned wgt = (d == -r - 1 || d == r + 1) ? fw : ww;
+              const uint8_t* s = px + base + clampi(i + d, 0, n - 1) * stride;
+              acc[3 * q] += wgt * s[0]; acc[3 * q + 1] += wgt * s[1]; acc[3 * q + 2] += wgt * s[2];
+            }
+          }
+          ++x;
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 3; ++e)
+        keep[k][e] = (acc[4 * e] >> 24) | ((acc[4 * e + 1] >> 24) << 8) | ((acc[4 * e + 2] >> 24) << 16) |
+                     ((acc[4 * e + 3] >> 24) << 24);
+    }
+    __builtin_amdgcn_sched_barrier(0);     // one item at a time: only the packed results stay live
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < kBlurMaxIter; ++k) {
+    const int it = tid + k * kAugThreads;
+    if (it < items) { parked[it * 3] = keep[k][0]; parked[it * 3 + 1] = keep[k][1]; parked[it * 3 + 2] = keep[k][2]; }
+  }
+  __syncthreads();
+}
+
+template <bool AUG>
+__global__ void __launch_bounds__(AUG ? kAugThreads : kJitThreads)
 color_jitter_kernel(const JitterArgs a) {
   extern __shared__ __align__(16) unsigned parked[];      // [items][3]: four RGB pixels, as they lie in memory
-  __shared__ unsigned red[kJitThreads / 64];
+  constexpr int NT = AUG ? kAugThreads : kJitThreads;
+  __shared__ unsigned red[NT / 64];
   const int tid = threadIdx.x, n = blockIdx.x;
   const int grp = min(n / a.group_size, a.G - 1);
   const int32_t* kinds = a.kinds + (long)grp * a.P;
@@ -270,14 +428,19 @@ color_jitter_kernel(const JitterArgs a) {
   const bool src4 = (((uintptr_t)src) & 3) == 0;
   const long plane = (long)a.T * a.HW;                              // one channel of one clip
   float* dst = a.out + (long)(n / a.T) * 3 * plane + (long)(n % a.T) * a.HW;
+  bool mirror = false;
+  if (AUG)
+    for (int j = 0; j < a.P; ++j) mirror ^= kinds[j] == JIT_FLIP;
   int op = 0, m = 0;
+  bool lead = false;                       // ops[op] is a contrast whose mean `m` is known
   for (int pass = 0;; ++pass) {
-    // this pass runs ops [op, end): a contrast op ends a pass and, with its mean `m` known, begins the next
-    int end = op + (pass > 0);
-    while (end < a.P && !(a.use_lds && kinds[end] == JIT_CONTRAST)) ++end;
+    // this pass runs ops [op, end): a contrast op ends a pass and, with its mean `m` known, begins the next; a
+    // blur ends a pass, runs on the parked bytes, and the next pass begins behind it
+    int end = op + (lead ? 1 : 0);
+    while (end < a.P && !(a.use_lds && (kinds[end] == JIT_CONTRAST || (AUG && kinds[end] == JIT_BLUR)))) ++end;
     const bool last = end >= a.P;
     unsigned sum = 0;
-    for (int it = tid; it < a.items; it += kJitThreads) {
+    for (int it = tid; it < a.items; it += NT) {
       const bool full = it * 4 + 3 < a.HW;
       unsigned w[3] = {0u, 0u, 0u};
       if (pass > 0) {
@@ -301,7 +464,7 @@ color_jitter_kernel(const JitterArgs a) {
 #pragma unroll
           for (int k = 0; k < 12; ++k) c[k] = blend8(0, c[k], prm, inside);
         } else if (kind == JIT_CONTRAST) {
-          if (pass > 0 && j == op) {
+          if (lead && j == op) {
 #pragma unroll
             for (int k = 0; k < 12; ++k) c[k] = blend8(m, c[k], prm, inside);
           }
@@ -343,7 +506,21 @@ color_jitter_kernel(const JitterArgs a) {
           o.z = norm1(__fdiv_rn((float)c[6 + ch], 255.f), mean, std);
           o.w = norm1(__fdiv_rn((float)c[9 + ch], 255.f), mean, std);
           float* d = dst + ch * plane + (long)it * 4;
-          if (a.vec) {
+          if (AUG && mirror) {
+            const float v[4] = {o.x, o.y, o.z, o.w};
+            if (a.vec) {                   // W % 4 == 0: the four pixels share a row and land on 16 aligned bytes
+              const int y = (it * 4) / a.W, x = it * 4 - y * a.W;
+              o.x = v[3]; o.y = v[2]; o.z = v[1]; o.w = v[0];
+              *reinterpret_cast<float4*>(dst + ch * plane + (long)y * a.W + (a.W - 4 - x)) = o;
+            } else {
+#pragma unroll
+              for (int q = 0; q < 4; ++q)
+                if (it * 4 + q < a.HW) {
+                  const int y = (it * 4 + q) / a.W, x = it * 4 + q - y * a.W;
+                  dst[ch * plane + (long)y * a.W + (a.W - 1 - x)] = v[q];
+                }
+            }
+          } else if (a.vec) {
             *reinterpret_cast<float4*>(d) = o;
           } else {
             const float v[4] = {o.x, o.y, o.z, o.w};
@@ -355,6 +532,17 @@ color_jitter_kernel(const JitterArgs a) {
       }
     }
     if (last) break;
+    if (AUG && kinds[end] == JIT_BLUR) {
+      const float rf = fminf(fmaxf(params[end], 0.f), kBlurMaxRadius);       // NaN -> 0
+      const int r = (int)rf;
+      const unsigned ww = (unsigned)__fdiv_rn(16777216.f, __fadd_rn(__fmul_rn(rf, 2.f), 1.f));
+      const unsigned fw = ((1u << 24) - (unsigned)(2 * r + 1) * ww) >> 1;
+      __syncthreads();                                     // every lane's bytes are parked
+      for (int k = 0; k < 6; ++k) blur_pass(parked, tid, a.items, a.HW, a.H, a.W, k >= 3, r, ww, fw);
+      op = end + 1;
+      lead = false;
+      continue;
+    }
     // m = int(sum / count + 0.5) = (2*sum + count) / (2*count): sum <= 255 * 224 * 224 < 2^24
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
@@ -363,9 +551,10 @@ color_jitter_kernel(const JitterArgs a) {
     __syncthreads();
     unsigned total = 0;
 #pragma unroll
-    for (int k = 0; k < kJitThreads / 64; ++k) total += red[k];
+    for (int k = 0; k < NT / 64; ++k) total += red[k];
     m = (int)((2u * total + (unsigned)a.HW) / (2u * (unsigned)a.HW));
     op = end;
+    lead = true;
   }
 }
 
@@ -438,24 +627,24 @@ extern "C" int coclr_resize_crops_u8(const uint8_t* frames, int F, int H, int W,
                       yk, ytaps, nullptr, nullptr, nullptr, out, (hipStream_t)stream_);
 }
 
-extern "C" int coclr_color_jitter_clips(const uint8_t* frames, int N, int H, int W, int T, const int32_t* kinds,
-                                        const float* params, const int32_t* kinds_host, const float* params_host,
-                                        int G, int P, int group_size, const float* mean, const float* std,
-                                        float* out, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+// The launch both program entry points share; `aug` admits kinds 6 (blur) and 7 (flip) and runs the augment form.
+static int launch_jitter(bool aug, const uint8_t* frames, int N, int H, int W, int T, const int32_t* kinds,
+                         const float* params, const int32_t* kinds_host, const float* params_host, int G, int P,
+                         int group_size, const float* mean, const float* std, float* out, hipStream_t stream) {
   if (!frames || !kinds || !params || !kinds_host || !params_host || !mean || !std || !out) return COCLR_EINVAL;
   if (N < 1 || H < 1 || W < 1 || T < 1 || G < 1 || P < 1 || P > 8 || group_size < 1) return COCLR_EINVAL;
   if (N % T != 0 || (long)G * group_size < N) return COCLR_EINVAL;
   if ((long)H * W > kJitMaxPixels) return COCLR_EINVAL;     // the frame's bytes must fit one workgroup's LDS
-  bool contrast = false;
+  bool whole = false;                                       // an op that needs the whole frame: contrast, blur
   for (long i = 0; i < (long)G * P; ++i) {
     const int kind = kinds_host[i];
     const float v = params_host[i];
-    if (kind < JIT_NOP || kind > JIT_GRAY) return COCLR_EINVAL;
+    if (kind < JIT_NOP || kind > (aug ? JIT_FLIP : JIT_GRAY)) return COCLR_EINVAL;
     if (kind >= JIT_BRIGHTNESS && kind <= JIT_SATURATION && !(v - v == 0.f)) return COCLR_EINVAL;   // NaN, inf
     if (kind == JIT_HUE && !(v >= 0.f && v <= 255.f && v == (float)(int)v)) return COCLR_EINVAL;
     if (kind == JIT_GRAY && !(v == 0.f || v == 1.f || v == 2.f)) return COCLR_EINVAL;
-    contrast = contrast || kind == JIT_CONTRAST;
+    if (kind == JIT_BLUR && !(v >= 0.f && v <= kBlurMaxRadius)) return COCLR_EINVAL;                // NaN too
+    whole = whole || kind == JIT_CONTRAST || kind == JIT_BLUR;
   }
   JitterArgs a;
   for (int c = 0; c < 3; ++c) {
@@ -463,17 +652,84 @@ extern "C" int coclr_color_jitter_clips(const uint8_t* frames, int N, int H, int
     if (a.std[c] == 0.f) return COCLR_EINVAL;
   }
   a.frames = frames; a.kinds = kinds; a.params = params; a.out = out;
-  a.HW = H * W; a.T = T; a.P = P; a.G = G; a.group_size = group_size;
+  a.HW = H * W; a.T = T; a.P = P; a.G = G; a.group_size = group_size; a.H = H; a.W = W;
   a.items = (a.HW + 3) / 4;
   a.vec = (W & 3) == 0 && (((uintptr_t)out) & 15) == 0;
-  a.use_lds = contrast ? 1 : 0;
-  const size_t lds = contrast ? (size_t)a.items * 12 : 0;
-  if (contrast) {                                        // 224 x 224 x 3 = 147 KiB of the CU's 160
-    static std::atomic<uint64_t> attr_done{0};
-    COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(color_jitter_kernel), kJitMaxPixels * 3,
-                                   attr_done));
+  a.use_lds = whole ? 1 : 0;
+  const size_t lds = whole ? (size_t)a.items * 12 : 0;
+  if (whole) {                                           // 224 x 224 x 3 = 147 KiB of the CU's 160
+    static std::atomic<uint64_t> attr_done{0}, attr_done_aug{0};
+    if (aug)
+      COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(color_jitter_kernel<true>), kJitMaxPixels * 3,
+                                     attr_done_aug));
+    else
+      COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(color_jitter_kernel<false>), kJitMaxPixels * 3,
+                                     attr_done));
   }
-  hipLaunchKernelGGL(color_jitter_kernel, dim3((unsigned)N), dim3(kJitThreads), lds, stream, a);
+  if (aug) hipLaunchKernelGGL(color_jitter_kernel<true>, dim3((unsigned)N), dim3(kAugThreads), lds, stream, a);
+  else hipLaunchKernelGGL(color_jitter_kernel<false>, dim3((unsigned)N), dim3(kJitThreads), lds, stream, a);
+  COCLR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int coclr_color_jitter_clips(const uint8_t* frames, int N, int H, int W, int T, const int32_t* kinds,
+                                        const float* params, const int32_t* kinds_host, const float* params_host,
+                                        int G, int P, int group_size, const float* mean, const float* std,
+                                        float* out, void* stream_) {
+  return launch_jitter(false, frames, N, H, W, T, kinds, params, kinds_host, params_host, G, P, group_size, mean, std,
+                       out, (hipStream_t)stream_);
+}
+
+extern "C" int coclr_augment_clips(const uint8_t* frames, int N, int H, int W, int T, const int32_t* kinds,
+                                   const float* params, const int32_t* kinds_host, const float* params_host, int G,
+                                   int P, int group_size, const float* mean, const float* std, float* out,
+                                   void* stream_) {
+  return launch_jitter(true, frames, N, H, W, T, kinds, params, kinds_host, params_host, G, P, group_size, mean, std,
+                       out, (hipStream_t)stream_);
+}
+
+extern "C" int coclr_resize_boxes_u8(const uint8_t* frames, int F, int H, int W, const int32_t* desc,
+                                     const int32_t* desc_host, int n_clips, int T, int S, const int32_t* xtab,
+                                     int64_t xlen, const int32_t* ytab, int64_t ylen, uint8_t* out, void* stream_) {
+  if (!frames || !desc || !desc_host || !xtab || !ytab || !out) return COCLR_EINVAL;
+  if (F < 1 || H < 1 || W < 1 || T < 1 || n_clips < 1 || S < 1 || S > 512) return COCLR_EINVAL;
+  if ((long)W * 3 * H > 0x7fffffffL || (long)n_clips * T > 65535) return COCLR_EINVAL;
+  if ((((uintptr_t)xtab) & 15) || (((uintptr_t)ytab) & 15)) return COCLR_EINVAL;       // 16-byte table loads
+  const int Sp = (S + 3) & ~3;
+  if (xlen < 2 * Sp || ylen < 2 * Sp || xlen > 0x7fffffffL || ylen > 0x7fffffffL) return COCLR_EINVAL;
+  int hmax = 0, ytmax = 0;
+  for (int k = 0; k < n_clips; ++k) {
+    const int32_t* d = desc_host + (long)k * BOX_FIELDS;
+    if (d[BOX_FIRST] < 0 || d[BOX_FRAMES] != T || (long)d[BOX_FIRST] + T > F) return COCLR_EINVAL;
+    if (d[BOX_X0] < 0 || d[BOX_Y0] < 0 || d[BOX_W] < 1 || d[BOX_H] < 1 || (long)d[BOX_X0] + d[BOX_W] > W ||
+        (long)d[BOX_Y0] + d[BOX_H] > H)
+      return COCLR_EINVAL;
+    if (d[BOX_XTAPS] < 1 || d[BOX_XTAPS] > 64 || d[BOX_YTAPS] < 1 || d[BOX_YTAPS] > 64) return COCLR_EINVAL;
+    if (d[BOX_XOFF] < 0 || (d[BOX_XOFF] & 3) || (long)d[BOX_XOFF] + (long)Sp * (1 + d[BOX_XTAPS]) > xlen)
+      return COCLR_EINVAL;
+    if (d[BOX_YOFF] < 0 || (d[BOX_YOFF] & 3) || (long)d[BOX_YOFF] + (long)Sp * (1 + d[BOX_YTAPS]) > ylen)
+      return COCLR_EINVAL;
+    hmax = d[BOX_H] > hmax ? d[BOX_H] : hmax;
+    ytmax = d[BOX_YTAPS] > ytmax ? d[BOX_YTAPS] : ytmax;
+  }
+  // band height as in launch_crops, for the tallest box and the most taps of the launch: a band of any box then
+  // spans no more source rows than that; the kernel clamps to cap_rows whatever the tables say
+  int R = 32, cap = 0;
+  for (;; R >>= 1) {
+    cap = (int)(((long)(R - 1) * hmax) / S) + ytmax + 2;
+    if (cap > hmax) cap = hmax;
+    const long bytes = (long)cap * 3 * Sp;
+    if (bytes <= (R > 1 ? 32768 : 65536)) break;
+    if (R == 1) return COCLR_EINVAL;                   // one output row's taps do not fit 64 KiB of LDS
+  }
+  const long bands = (S + R - 1) / R;
+  if (bands * n_clips * T * 256 >= (1L << 32)) return COCLR_EINVAL;
+  BoxArgs a;
+  a.frames = frames; a.desc = desc; a.xtab = xtab; a.ytab = ytab; a.out8 = out;
+  a.F = F; a.H = H; a.W = W; a.T = T; a.S = S; a.Sp = Sp; a.R = R; a.cap_rows = cap;
+  a.xlen = (int)xlen; a.ylen = (int)ylen;
+  hipLaunchKernelGGL(resize_boxes_kernel, dim3((unsigned)bands, (unsigned)(n_clips * T)), dim3(256),
+                     (size_t)cap * 3 * Sp, (hipStream_t)stream_, a);
   COCLR_LAUNCH_CHECK();
   return 0;
 }

@@ -989,6 +989,37 @@ def color_jitter_clips(frames, kinds, params, group_size, T, mean, std, out, hos
     """frames (N, H, W, 3) uint8 -> out (N/T, 3, T, H, W) fp32; frame n runs program n // group_size of the
     device tables kinds int32 (G, P) / params fp32 (G, P) (include/coclr_hip.h).  `host_tables`: the same two
     tables on the host, which the entry point validates (read back from the device when not given)."""
+    _program_call("color_jitter_clips", frames, kinds, params, group_size, T, mean, std, out, host_tables)
+
+
+def augment_clips(frames, kinds, params, group_size, T, mean, std, out, host_tables=None):
+    """color_jitter_clips with kinds 6 (blur, parameter = PIL's fp32 box radius) and 7 (flip) admitted."""
+    _program_call("augment_clips", frames, kinds, params, group_size, T, mean, std, out, host_tables)
+
+
+def resize_boxes_u8(frames, desc, desc_host, xtab, ytab, T, S, out):
+    """frames (F, H, W, 3) uint8; desc int32 (n_clips, 10) on the device and desc_host, the same on the host
+    (include/coclr_hip.h); xtab / ytab the concatenated per-box tables, int32, device -> out (n_clips*T, S, S, 3)
+    uint8: every clip's own box of its T frames resized to S x S."""
+    if frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise ValueError("coclr_amd: frames must be contiguous (F, H, W, 3), got %s" % (tuple(frames.shape),))
+    F, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
+    if desc.dim() != 2 or desc.shape[1] != 10 or desc.shape != desc_host.shape or desc_host.is_cuda or \
+            desc_host.dtype != torch.int32 or not desc.is_contiguous() or not desc_host.is_contiguous():
+        raise ValueError("coclr_amd: box descriptors must be contiguous int32 (n_clips, 10), device and host")
+    n_clips, T, S = desc.shape[0], int(T), int(S)
+    if xtab.dim() != 1 or ytab.dim() != 1 or not xtab.is_contiguous() or not ytab.is_contiguous():
+        raise ValueError("coclr_amd: resize_boxes_u8 needs flat contiguous table buffers")
+    if tuple(out.shape) != (n_clips * T, S, S, 3) or not out.is_contiguous():
+        raise ValueError("coclr_amd: out must be contiguous %s, got %s" % ((n_clips * T, S, S, 3), tuple(out.shape)))
+    i32 = torch.int32
+    _lib.check(_L().coclr_resize_boxes_u8(
+        _p(frames, torch.uint8), F, H, W, _p(desc, i32), C.cast(desc_host.data_ptr(), C.POINTER(C.c_int32)), n_clips,
+        T, S, _p(xtab, i32), xtab.numel(), _p(ytab, i32), ytab.numel(), _p(out, torch.uint8), _stream()),
+        "resize_boxes_u8")
+
+
+def _program_call(name, frames, kinds, params, group_size, T, mean, std, out, host_tables):
     if frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
         raise ValueError("coclr_amd: frames must be contiguous (N, H, W, 3), got %s" % (tuple(frames.shape),))
     N, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
@@ -1007,10 +1038,10 @@ def color_jitter_clips(frames, kinds, params, group_size, T, mean, std, out, hos
         raise ValueError("coclr_amd: host_tables must be contiguous host copies of kinds and params")
     m = (C.c_float * 3)(*[float(v) for v in mean])
     s = (C.c_float * 3)(*[float(v) for v in std])
-    _lib.check(_L().coclr_color_jitter_clips(
+    _lib.check(getattr(_L(), "coclr_" + name)(
         _p(frames, torch.uint8), N, H, W, T, _p(kinds, torch.int32), _p(params),
         C.cast(hk.data_ptr(), C.POINTER(C.c_int32)), C.cast(hp.data_ptr(), C.POINTER(C.c_float)), G, P,
-        int(group_size), m, s, _p(out), _stream()), "color_jitter_clips")
+        int(group_size), m, s, _p(out), _stream()), name)
 
 
 # ---- evaluation consumers ---------------------------------------------------------------

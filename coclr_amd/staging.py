@@ -20,6 +20,9 @@ Normalize; `resample_tables`, `five_crop_boxes` and `test_frame_index` are the h
 The chain's ColorJitter (utils/augmentation.py:219-320) is `ColorJitter` below: it draws from the generator as
 the reference does and hands the kernel one small program per group of frames (`color_jitter`,
 `stage_crops(jitter=...)`), bit-identical to torchvision 0.5's functional ops on PIL images.
+The training transform (main_nce.py:366-392) is `TrainTransform` + `stage_train_clips` at the end of this file: the
+reference's draws on the host, then every clip's RandomSizedCrop box and its ColorJitter / RandomGray / GaussianBlur
+/ RandomHorizontalFlip program in two launches, bit-identical to the reference's classes.
 """
 import math
 import numbers
@@ -411,3 +414,348 @@ def stage_crops(frames_u8, frame_index, boxes, flips, crop_size, out_size, mean=
     if jitter is None:
         return stage_crops_on_device(frames, idx.to(device), crops, cw, ch, int(out_size), mean, std, out)
     return stage_crops_on_device(frames, idx.to(device), crops, cw, ch, int(out_size), mean, std, out, jitter)
+
+
+# ---- the training transform (main_nce.py:366-392; utils/augmentation.py:90-216,357-444) -----------------------------
+
+AUGMENT_BLUR, AUGMENT_FLIP = 6, 7       # the two kinds coclr_augment_clips adds to the six of the jitter
+BLUR_MAX_RADIUS = 16.0                  # the kernel's design limit; the reference's sigma in [0.1, 2] needs 1.375
+PLAN_HEAD = 5                           # packed plan, per clip: half, x0, y0, w, h, then T x 8 kinds, T x 8 parameters
+
+
+def blur_box_radius(sigma):
+    """ImageFilter.GaussianBlur(radius=sigma) as PIL runs it: three box blurs of this (fractional) radius per
+    direction -- the number the kernel takes (kind 6).  PIL's C evaluates the formula in `float` variables (sigma
+    itself arrives as one) with the square root and the floor in double, and the last bit matters: the same
+    formula in doubles gives another fp32 radius for four sigmas in ten and other bytes for about one in 250
+    (1.4 is one).  So every float operation below is a numpy float32 operation of its own."""
+    sigma = float(sigma)
+    if not sigma >= 0.0 or not math.isfinite(sigma):
+        raise ValueError("coclr_amd: a blur sigma is a finite number >= 0, got %r" % (sigma,))
+    f = np.float32
+    r = f(sigma)
+    s2 = r * r / f(3)
+    L = f(math.sqrt(12.0 * float(s2) + 1.0))
+    l = f(math.floor((float(L) - 1.0) / 2.0))
+    a = (f(2) * l + f(1)) * (l * (l + f(1)) - f(3) * s2)
+    a = a / (f(6) * (s2 - (l + f(1)) * (l + f(1))))
+    out = l + a
+    assert out.dtype == np.float32
+    return float(out)
+
+
+def _check_augment_op(kind, value):
+    """One op of an augment program -> (kind, parameter as the kernel takes it); the rules of program_tables for
+    kinds 0..5."""
+    if isinstance(kind, bool) or kind not in range(8) or int(kind) != kind:
+        raise ValueError("coclr_amd: no augment op kind %r" % (kind,))
+    kind, value = int(kind), float(value)
+    if kind == AUGMENT_FLIP:
+        return kind, 0.0
+    if kind == AUGMENT_BLUR:
+        if not 0.0 <= value <= BLUR_MAX_RADIUS:
+            raise ValueError("coclr_amd: a blur box radius lies in [0, %g] (blur_box_radius), got %r" %
+                             (BLUR_MAX_RADIUS, value))
+    elif kind == JITTER_HUE and not (0 <= value <= 255 and value == int(value)):
+        raise ValueError("coclr_amd: a hue shift is a byte (hue_shift_byte), got %r" % (value,))
+    elif kind == JITTER_GRAY and value not in (0.0, 1.0, 2.0):
+        raise ValueError("coclr_amd: gray takes channel 0, 1 or 2, got %r" % (value,))
+    elif not math.isfinite(value):
+        raise ValueError("coclr_amd: jitter factor %r is not finite" % (value,))
+    return kind, value
+
+
+def augment_tables(programs):
+    """program_tables for coclr_augment_clips: kinds 0..5 as there, plus (6, r_f) -- blur, r_f from blur_box_radius,
+    0 <= r_f <= 16 -- and (7, anything) -- horizontal flip.  A batch names few distinct programs (one per clip, or
+    per frame of a gray clip), so each is checked once."""
+    programs = [list(prog) for prog in programs]
+    if not programs:
+        raise ValueError("coclr_amd: need at least one program")
+    P = max(1, max(len(prog) for prog in programs))
+    if P > JITTER_MAX_OPS:
+        raise ValueError("coclr_amd: a program has %d ops, the kernel takes %d" % (P, JITTER_MAX_OPS))
+    rows, kinds, params = {}, [], []
+    for prog in programs:
+        key = tuple(tuple(op) for op in prog)
+        if key not in rows:
+            checked = [_check_augment_op(kind, value) for kind, value in prog] + [(0, 0.0)] * (P - len(prog))
+            rows[key] = ([k for k, _ in checked], [v for _, v in checked])
+        kinds.append(rows[key][0])
+        params.append(rows[key][1])
+    return torch.tensor(kinds, dtype=torch.int32), torch.tensor(params, dtype=torch.float32)
+
+
+def augment(frames_u8, programs, group_size, T, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None, device=None):
+    """color_jitter with the blur and the flip admitted (augment_tables): `frames_u8` (N, H, W, 3) uint8 ->
+    (N/T, 3, T, H, W) fp32 on the device in one launch, frame n running program n // group_size."""
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or frames_u8.dtype != torch.uint8:
+        raise ValueError("coclr_amd: frames must be uint8 (N, H, W, 3), got %s %s" %
+                         (frames_u8.dtype, tuple(frames_u8.shape)))
+    N, H, W = frames_u8.shape[:3]
+    group_size, T = int(group_size), int(T)
+    if N < 1 or T < 1 or N % T != 0:
+        raise ValueError("coclr_amd: %d frames do not make clips of %d" % (N, T))
+    if H * W > JITTER_MAX_PIXELS or H * W < 1:
+        raise ValueError("coclr_amd: augment takes frames of up to 224 x 224 pixels, got %d x %d" % (H, W))
+    kinds, params = augment_tables(programs)
+    if group_size < 1 or kinds.shape[0] * group_size < N:
+        raise ValueError("coclr_amd: %d programs for groups of %d frames do not cover %d frames" %
+                         (kinds.shape[0], group_size, N))
+    if device is None:
+        device = frames_u8.device if frames_u8.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    frames = frames_u8.contiguous().to(device)
+    if out is None:
+        out = torch.empty(N // T, 3, T, H, W, dtype=torch.float32, device=frames.device)
+    ops.augment_clips(frames, kinds.to(device), params.to(device), group_size, T, mean, std, out,
+                      host_tables=(kinds, params))
+    return out
+
+
+class TrainTransform:
+    """The reference's training transform (main_nce.py:366-390, the same chain in main_coclr.py) as a source of
+    PLANS: `draw` consumes `random` and `np.random` exactly as `transform(seq)` does on 2 * seq_len frames and says
+    what it would do; stage_train_clips does it on the GPU.  A plan is a dict
+        half      (a, b): which half of the 2T frames clip 0 / clip 1 reads (0 or 1)
+        box       ((x0, y0, w, h), (x0, y0, w, h)): RandomSizedCrop's box per clip (the whole frame when its draw
+                  does not fit)
+        programs  per clip T programs [(kind, parameter)], one per frame: ColorJitter's ops in their shuffled
+                  order, gray (the channel differs from frame to frame), blur (6, box radius), flip (7, 0)."""
+
+    def __init__(self, img_dim, seq_len, bottom_area=0.2, jitter=(0.4, 0.4, 0.4, 0.1), p_jitter=0.8, p_gray=0.2,
+                 blur_sigma=(0.1, 2.0), p_blur=0.5, p_flip=0.5, p_base=0.3, weights=(0.5, 0.5), consistent=False, p=1.0):
+        if consistent:
+            raise ValueError("coclr_amd: RandomSizedCrop(consistent=True) retries and falls back to another resample; "
+                             "the training scripts never use it")
+        if p != 1.0:
+            raise ValueError("coclr_amd: RandomSizedCrop(p != 1.0) centre-crops without a resize; the training "
+                             "scripts never use it")
+        self.img_dim, self.seq_len = int(img_dim), int(seq_len)
+        if self.img_dim < 1 or self.seq_len < 1:
+            raise ValueError("coclr_amd: img_dim and seq_len must be >= 1")
+        self.bottom_area = bottom_area
+        self.jitter = ColorJitter(*jitter, p=1.0)
+        self.p_jitter, self.p_gray, self.p_blur, self.p_flip, self.p_base = p_jitter, p_gray, p_blur, p_flip, p_base
+        self.blur_sigma = tuple(blur_sigma)
+        blur_box_radius(self.blur_sigma[0]), blur_box_radius(self.blur_sigma[1])
+        if blur_box_radius(max(self.blur_sigma)) > BLUR_MAX_RADIUS:
+            raise ValueError("coclr_amd: blur sigma %r needs a box radius over %g" % (blur_sigma, BLUR_MAX_RADIUS))
+        self.weights = list(weights)
+
+    def _crop(self, W, H, rng):
+        rng.random()                                            # `random.random() < p`, p = 1.0
+        target_area = rng.uniform(self.bottom_area, 1) * (W * H)
+        aspect_ratio = rng.uniform(3. / 4, 4. / 3)
+        w = int(round(math.sqrt(target_area * aspect_ratio)))
+        h = int(round(math.sqrt(target_area / aspect_ratio)))
+        if rng.random() < 0.5:
+            w, h = h, w
+        if w <= W and h <= H:
+            if w < 1 or h < 1:
+                raise ValueError("coclr_amd: RandomSizedCrop drew an empty %d x %d box" % (w, h))
+            x1 = rng.randint(0, W - w)
+            y1 = rng.randint(0, H - h)
+            return (x1, y1, w, h)
+        return (0, 0, W, H)                                     # no retry in this mode: the frame as it is
+
+    def _flip(self, rng):
+        return [(AUGMENT_FLIP, 0.0)] if rng.random() < self.p_flip else []
+
+    def _null(self, W, H, rng, np_rng):
+        box = self._crop(W, H, rng)
+        return box, [self._flip(rng)] * self.seq_len
+
+    def _base(self, W, H, rng, np_rng):
+        box = self._crop(W, H, rng)
+        prog = []
+        if not self.p_jitter < rng.random():                    # transforms.RandomApply
+            prog += self.jitter.draw(rng, 1)[0]
+        gray = None
+        if rng.random() < self.p_gray:
+            gray = [int(np_rng.choice(3)) for _ in range(self.seq_len)]
+        tail = []
+        if not self.p_blur < rng.random():
+            tail.append((AUGMENT_BLUR, blur_box_radius(rng.uniform(self.blur_sigma[0], self.blur_sigma[1]))))
+        tail += self._flip(rng)
+        if gray is None:
+            return box, [prog + tail] * self.seq_len
+        return box, [prog + [(JITTER_GRAY, ch)] + tail for ch in gray]
+
+    def draw(self, W, H, rng=random, np_rng=np.random):
+        """The plan of one sample of 2 * seq_len frames of W x H."""
+        W, H = int(W), int(H)
+        if W < 1 or H < 1:
+            raise ValueError("coclr_amd: frames of %d x %d" % (W, H))
+        if rng.choices(range(2), weights=self.weights)[0] == 0:             # TwoClipTransform
+            tr1 = self._base if rng.random() < self.p_base else self._null
+            tr2 = self._base if rng.random() < self.p_base else self._null
+            half = (0, 1)
+        else:                                                               # OneClipTransform
+            tr1, tr2 = (self._base, self._null) if rng.random() < 0.5 else (self._null, self._base)
+            half = (0, 0) if rng.random() < 0.5 else (1, 1)
+        box1, progs1 = tr1(W, H, rng, np_rng)
+        box2, progs2 = tr2(W, H, rng, np_rng)
+        return {"half": half, "box": (box1, box2), "programs": ([list(p) for p in progs1], [list(p) for p in progs2])}
+
+
+def pack_plan(plan, T):
+    """A plan as ONE tensor of fixed shape, float64 (2, 5 + 16 T): per clip half, x0, y0, w, h, then T x 8 op kinds
+    and T x 8 parameters (doubles hold both exactly).  What a dataset returns beside its frames: the default
+    collate stacks it, and stage_train_clips takes the stacked (B, 2, 5 + 16 T) tensor as `plans`."""
+    T = int(T)
+    t = torch.zeros(2, PLAN_HEAD + 2 * T * JITTER_MAX_OPS, dtype=torch.float64)
+    for c in range(2):
+        progs = plan["programs"][c]
+        if len(progs) != T:
+            raise ValueError("coclr_amd: a plan has one program per frame, got %d for T = %d" % (len(progs), T))
+        t[c, 0] = plan["half"][c]
+        t[c, 1:PLAN_HEAD] = torch.tensor([float(v) for v in plan["box"][c]], dtype=torch.float64)
+        kinds, params = t[c, PLAN_HEAD:].view(2, T, JITTER_MAX_OPS)
+        for f, prog in enumerate(progs):
+            if len(prog) > JITTER_MAX_OPS:
+                raise ValueError("coclr_amd: a program has %d ops, the kernel takes %d" % (len(prog), JITTER_MAX_OPS))
+            for j, (kind, value) in enumerate(prog):
+                kinds[f, j], params[f, j] = kind, value
+    return t
+
+
+def unpack_plan(packed):
+    """The plan pack_plan packed (no-ops dropped)."""
+    if packed.dim() != 2 or packed.shape[0] != 2 or (packed.shape[1] - PLAN_HEAD) % (2 * JITTER_MAX_OPS) != 0 or \
+            packed.shape[1] <= PLAN_HEAD:
+        raise ValueError("coclr_amd: a packed plan is (2, 5 + 16 T), got %s" % (tuple(packed.shape),))
+    T = (packed.shape[1] - PLAN_HEAD) // (2 * JITTER_MAX_OPS)
+    packed = packed.detach().cpu().to(torch.float64)
+    half, box, programs = [], [], []
+    for c in range(2):
+        head = packed[c, :PLAN_HEAD].tolist()
+        if any(v != int(v) for v in head):
+            raise ValueError("coclr_amd: a packed plan's half and box are integers, got %r" % (head,))
+        half.append(int(head[0]))
+        box.append(tuple(int(v) for v in head[1:]))
+        rows = packed[c, PLAN_HEAD:].view(2, T, JITTER_MAX_OPS)
+        same = bool((rows == rows[:, :1]).all())               # one program for the clip: read it once
+        kinds, params = (rows[:, :1] if same else rows).tolist()
+        progs = [[(int(k) if k == int(k) else k, v) for k, v in zip(kk, vv) if k != 0] for kk, vv in zip(kinds, params)]
+        programs.append([list(progs[0]) for _ in range(T)] if same else progs)
+    return {"half": tuple(half), "box": tuple(box), "programs": tuple(programs)}
+
+
+_BOX_TABLES = {}        # (n_in, S) -> int32 (1 + taps, Sp): min then k, in the kernel's layout
+
+
+def _box_table(n_in, S):
+    key = (n_in, S)
+    if key not in _BOX_TABLES:
+        Sp = (S + 3) & ~3
+        lo, K = resample_tables(n_in, S)
+        t = np.zeros((1 + K.shape[1], Sp), dtype=np.int32)
+        t[0, :S] = lo
+        t[1:, :S] = K.T
+        _BOX_TABLES[key] = t
+    return _BOX_TABLES[key]
+
+
+def check_train_plans(plans, B, T, W, H):
+    """`plans` (a list of B plans, or the stacked packed tensor) -> (descriptor rows without table fields, per-frame
+    programs of all B * 2 clips), refused here, on the host, when a plan is not one the kernels take."""
+    if torch.is_tensor(plans):
+        if plans.dim() == 2:
+            plans = plans[None]
+        plans = [unpack_plan(p) for p in plans]
+    plans = list(plans)
+    if len(plans) != B:
+        raise ValueError("coclr_amd: %d plans for %d samples" % (len(plans), B))
+    rows, programs = [], []
+    for b, plan in enumerate(plans):
+        if len(plan["half"]) != 2 or len(plan["box"]) != 2 or len(plan["programs"]) != 2:
+            raise ValueError("coclr_amd: a plan names two clips")
+        for c in range(2):
+            half = plan["half"][c]
+            x0, y0, w, h = plan["box"][c]
+            if half not in (0, 1) or isinstance(half, bool):
+                raise ValueError("coclr_amd: a clip reads half 0 or 1 of the frames, got %r" % (half,))
+            if any(int(v) != v for v in (x0, y0, w, h)) or x0 < 0 or y0 < 0 or w < 1 or h < 1 or x0 + w > W or y0 + h > H:
+                raise ValueError("coclr_amd: box (%r, %r, %r, %r) leaves the %d x %d frame" % (x0, y0, w, h, W, H))
+            progs = [list(p) for p in plan["programs"][c]]
+            if len(progs) != T:
+                raise ValueError("coclr_amd: a plan has one program per frame, got %d for T = %d" % (len(progs), T))
+            rows.append((b * 2 * T + int(half) * T, T, int(x0), int(y0), int(w), int(h)))
+            programs.append(progs)
+    distinct = {tuple(tuple(op) for op in p) for progs in programs for p in progs}
+    augment_tables([list(p) for p in distinct])                    # refuses a bad op
+    return rows, programs
+
+
+def train_tables(plans, B, T, W, H, S):
+    """The host side of stage_train_clips for B samples of 2 T frames of W x H staged to S x S: checks the plans and
+    returns (desc int32 (2B, 10), xtab, ytab int32, kinds int32 (G, P), params fp32 (G, P), group_size) as the
+    two entry points take them, all on the host.  May be computed ahead (stage_train_clips(tables=))."""
+    rows, programs = check_train_plans(plans, B, T, W, H)
+    # the tables of every distinct box width / height once, one after the other
+    bufs, at = ([], []), ({}, {})
+    fill = [0, 0]
+    full = []
+    for row in rows:
+        offs = []
+        for axis, n_in in ((0, row[4]), (1, row[5])):
+            if n_in not in at[axis]:
+                t = _box_table(n_in, S)
+                if t.shape[0] - 1 > 64:
+                    raise ValueError("coclr_amd: a box side of %d to %d needs %d taps, the kernel takes 64" %
+                                     (n_in, S, t.shape[0] - 1))
+                at[axis][n_in] = (fill[axis], t.shape[0] - 1)
+                bufs[axis].append(t.reshape(-1))
+                fill[axis] += t.size
+            offs.append(at[axis][n_in])
+        full.append(list(row) + [offs[0][0], offs[1][0], offs[0][1], offs[1][1]])
+    desc = torch.tensor(full, dtype=torch.int32)
+    # one program per clip where its frames agree, else (a gray clip: the channel is per frame) one per frame
+    per_clip = all(all(p == progs[0] for p in progs) for progs in programs)
+    flat = [progs[0] for progs in programs] if per_clip else [p for progs in programs for p in progs]
+    kinds, params = augment_tables(flat)
+    return (desc, torch.from_numpy(np.concatenate(bufs[0])), torch.from_numpy(np.concatenate(bufs[1])), kinds, params,
+            T if per_clip else 1)
+
+
+def stage_train_clips(frames_u8, plans, out_size, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None, device=None,
+                      tables=None):
+    """Raw frames + the reference's draws -> the model's input, in TWO launches (coclr_resize_boxes_u8, then
+    coclr_augment_clips): per clip `crop the box -> Image.resize((S, S), BICUBIC) -> ColorJitter -> RandomGray ->
+    GaussianBlur -> RandomHorizontalFlip -> ToTensor -> Normalize`, bit-identical to the reference's classes.
+    frames_u8: (B, 2T, H, W, 3) or (2T, H, W, 3) uint8, on the host (uploaded once, as bytes) or the device.
+    plans: B plans of TrainTransform.draw, or their pack_plan tensors stacked (B, 2, 5 + 16 T).
+    Returns (B, 2, 3, T, S, S) fp32 on the device: what `model(...)` takes after the script's `tr()`.
+    A bad plan is refused here before anything is launched.  S up to 224 (the augment kernel's frame limit).
+    `tables`: train_tables(plans, ...) computed ahead; `plans` is then not read."""
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() not in (4, 5) or frames_u8.shape[-1] != 3:
+        raise ValueError("coclr_amd: frames must be uint8 (B, 2T, H, W, 3) or (2T, H, W, 3), got %s %s" %
+                         (frames_u8.dtype, tuple(frames_u8.shape)))
+    if frames_u8.dim() == 4:
+        frames_u8 = frames_u8[None]
+        if isinstance(plans, dict):
+            plans = [plans]
+    B, T2, H, W = frames_u8.shape[:4]
+    if B < 1 or T2 < 2 or T2 % 2 != 0 or H < 1 or W < 1:
+        raise ValueError("coclr_amd: a sample is 2 T frames, got %s" % (tuple(frames_u8.shape),))
+    T, S = T2 // 2, int(out_size)
+    if S < 1 or S * S > JITTER_MAX_PIXELS:
+        raise ValueError("coclr_amd: stage_train_clips takes an output size of 1..224, got %d" % S)
+    if tables is None:
+        tables = train_tables(plans, B, T, W, H, S)
+    desc, xtab, ytab, kinds, params, group_size = tables
+    if tuple(desc.shape) != (2 * B, 10):
+        raise ValueError("coclr_amd: tables for %d clips, frames for %d" % (desc.shape[0], 2 * B))
+    if out is not None and (tuple(out.shape) != (B, 2, 3, T, S, S) or not out.is_contiguous()):
+        raise ValueError("coclr_amd: out must be contiguous %s, got %s" % ((B, 2, 3, T, S, S), tuple(out.shape)))
+    if device is None:
+        device = frames_u8.device if frames_u8.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    frames = frames_u8.contiguous().to(device).view(B * T2, H, W, 3)
+    u8 = torch.empty(B * 2 * T, S, S, 3, dtype=torch.uint8, device=device)
+    if out is None:
+        out = torch.empty(B, 2, 3, T, S, S, dtype=torch.float32, device=device)
+    ops.resize_boxes_u8(frames, desc.to(device), desc, xtab.to(device), ytab.to(device), T, S, u8)
+    ops.augment_clips(u8, kinds.to(device), params.to(device), group_size, T, mean, std,
+                      out.view(B * 2, 3, T, S, S), host_tables=(kinds, params))
+    return out

@@ -608,6 +608,38 @@ int coclr_color_jitter_clips(const uint8_t* frames, int N, int H, int W, int T, 
                              int P, int group_size, const float* mean, const float* std, float* out,
                              void* stream);
 
+/* The training transform's ops on uint8 frames (main_nce.py:366-392; utils/augmentation.py:149-216,357-369): a
+ * superset of coclr_color_jitter_clips -- same arguments, same layouts, same validated host copies, kinds 0..5 as
+ * there -- with the two ops the pretraining chain adds:
+ *   6 blur  img.filter(ImageFilter.GaussianBlur(sigma)) on 8-bit pixels, bit-identical to PIL: three box blurs
+ *           along x, three along y, rounded to bytes after each.  param = r_f, PIL's fp32 box radius for sigma
+ *           (computed on the host in PIL's own float arithmetic: staging.blur_box_radius), 0 <= r_f <= 16; r_f = 0 is the identity.
+ *   7 flip  transpose(FLIP_LEFT_RIGHT); param unused.
+ * COCLR_EINVAL as coclr_color_jitter_clips, with kinds 0..7 admitted, and for a blur radius outside [0, 16] or NaN.
+ * Additive: coclr_color_jitter_clips keeps refusing kinds 6 and 7, and the ABI number stays 24 -- no existing
+ * signature or behaviour changed. */
+int coclr_augment_clips(const uint8_t* frames, int N, int H, int W, int T, const int32_t* kinds,
+                        const float* params, const int32_t* kinds_host, const float* params_host, int G, int P,
+                        int group_size, const float* mean, const float* std, float* out, void* stream);
+
+/* RandomSizedCrop's boxes of a whole batch in one launch (utils/augmentation.py:90-138): for output clip k and
+ * t < T, crop the w x h box at (x0, y0) of frame first + t and Image.resize((S, S), BICUBIC) it on 8-bit pixels,
+ * as coclr_resize_crops_u8 does for one box size, into uint8 out[n_clips*T][S][S][3] -- the input of
+ * coclr_augment_clips.  No flip (the reference flips after the resize: kind 7 above).
+ * frames: uint8 [F][H][W][3], device.  desc: int32 [n_clips][10], DEVICE:
+ *   {first frame, frames (= T), x0, y0, w, h, x-table offset, y-table offset, xtaps, ytaps};
+ * desc_host: the same on the HOST, read at call time and validated (the kernel reads the device copy and stays in
+ * bounds whatever that holds).  xtab / ytab: int32 device buffers of xlen / ylen elements, 16-byte aligned, the
+ * per-box tables of each axis one after the other: at a box's offset (a multiple of 4) min[Sp] then k[taps][Sp],
+ * laid out as coclr_stage_crops takes them (Sp = S rounded up to a multiple of 4).  Boxes may share tables.
+ * COCLR_EINVAL before any launch: a null or misaligned pointer; F, H, W, T, n_clips, S < 1; S > 512; a descriptor
+ * whose frames != T, whose frames leave [0, F), whose box leaves the frame, whose taps are outside 1..64 or whose
+ * tables leave their buffer; n_clips*T > 65535 or a grid over the launch limits; an output row of the tallest
+ * box whose source rows (3*Sp bytes each) exceed 64 KiB. */
+int coclr_resize_boxes_u8(const uint8_t* frames, int F, int H, int W, const int32_t* desc,
+                          const int32_t* desc_host, int n_clips, int T, int S, const int32_t* xtab, int64_t xlen,
+                          const int32_t* ytab, int64_t ylen, uint8_t* out, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* Evaluation consumers (model/classifier.py:47-61; eval/main_classifier.py) */
 /* ------------------------------------------------------------------------ */
