@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COCLR_LIB_PATH") or os.path.join(_HERE, "libcoclr_hip.so")
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 i32, i64, f32, f64, vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
 
@@ -96,6 +96,9 @@ _SIGNATURES = {
     "coclr_bn_act_backward_pooled": [_P(PoolDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64,
                                      i32, i32, vp],
     "coclr_bn_act_backward_pooled_fits": [_P(PoolDesc), _P(i32)],
+    "coclr_pool_plan": [_P(PoolDesc), i32, i64, i64, _P(i32)],
+    "coclr_bn_multi_plan": [_P(BnFwdCall), _P(BnBwdCall), i32, _P(i32)],
+    "coclr_bn_plan": [i32, i32, i64, i64, i64, i64, i64, i64, i32, i32, i32, _P(i32)],
     "coclr_global_avgpool_fwd": [vp, vp, i64, i64, vp],
     "coclr_global_avgpool_bwd": [vp, vp, i64, i64, vp],
     "coclr_gemm_workspace": [i32, i32, i32, i32, _P(i64)],

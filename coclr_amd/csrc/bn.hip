@@ -715,6 +715,75 @@ inline int reduce_groups(int N, int S) {
   return g < 1 ? 1 : g;
 }
 
+// Route of one BatchNorm pass.  The launchers below switch on this struct and coclr_bn_plan reports it without
+// launching, so there is one copy of the rules.
+struct BnRoute {
+  int one_wg;        // one workgroup per channel, one launch (small layers)
+  int vec;           // 16-byte accesses
+  int nt;            // non-temporal streaming passes (vector form only)
+  int groups;        // sample groups of the backward reduce (0: no reduce pass)
+  int gx, gy;        // plane_grid of the streaming apply pass (0 when one_wg)
+};
+
+inline bool bn_vec(long S, long a, long b, long c = 0, long d = 0, long e = 0) {
+  return S % 4 == 0 && a % 4 == 0 && b % 4 == 0 && c % 4 == 0 && d % 4 == 0 && e % 4 == 0;
+}
+
+// small_ok: the caller has a one-workgroup form for this pass (no residual / z / dres, not from partials)
+inline BnRoute bn_route(int N, int C, long S, bool vec, bool small_ok, bool reduce) {
+  BnRoute r;
+  r.one_wg = small_ok && (long)N * S <= kSmallChannel;
+  r.vec = vec;
+  r.nt = 0; r.groups = 0; r.gx = r.gy = 0;
+  if (r.one_wg) return r;
+  static const long nt_bytes = bn_nt_bytes();
+  r.nt = vec && nt_bytes >= 0 && (long)N * C * S * 4 >= nt_bytes;
+  if (reduce) r.groups = reduce_groups(N, (int)S);
+  const dim3 grid = plane_grid(N, C, (int)S);
+  r.gx = (int)grid.x; r.gy = (int)grid.y;
+  return r;
+}
+
+// How the multi launchers cut a call into launches: the run that starts at unit i is up to four consecutive units
+// that each take the one-workgroup route (bn_route), share a vector width and (backward) carry no partial sums;
+// COCLR_PAIR=0 keeps every unit alone.  Returns the run's length (0: unit i itself does not fuse; a run of 0 or 1
+// goes through the single-unit entry point), -1 for an invalid unit among those looked at.  coclr_bn_multi_plan
+// reports the same cut.
+inline bool bn_multi_fuse() {
+  const char* env = getenv("COCLR_PAIR");
+  return !(env && env[0] == '0');
+}
+
+inline int bn_fwd_run(const coclr_bn_fwd_call* calls, int n, int i, bool* vec0) {
+  const bool fuse = bn_multi_fuse();
+  int len = 0;
+  for (int j = i; j < n && len < 4; ++j) {
+    const coclr_bn_fwd_call& c = calls[j];
+    if (c.C <= 0 || c.ntiles <= 0 || c.N <= 0 || c.S <= 0 || !c.y || !c.z) return -1;
+    const bool vec = bn_vec((long)c.S, (long)c.y_nstride, (long)c.z_nstride);
+    if (!bn_route(c.N, c.C, (long)c.S, vec, true, false).one_wg || !fuse) break;
+    if (len == 0) *vec0 = vec;
+    else if (vec != *vec0) break;
+    ++len;
+  }
+  return len;
+}
+
+inline int bn_bwd_run(const coclr_bn_bwd_call* calls, int n, int i, bool* vec0) {
+  const bool fuse = bn_multi_fuse();
+  int len = 0;
+  for (int j = i; j < n && len < 4; ++j) {
+    const coclr_bn_bwd_call& c = calls[j];
+    if (c.N <= 0 || c.C <= 0 || c.S <= 0 || !c.dz || !c.y || !c.dy) return -1;
+    const bool vec = bn_vec((long)c.S, (long)c.dz_nstride, (long)c.y_nstride, (long)c.dy_nstride);
+    if (!bn_route(c.N, c.C, (long)c.S, vec, true, true).one_wg || !fuse || c.part[0]) break;
+    if (len == 0) *vec0 = vec;
+    else if (vec != *vec0) break;
+    ++len;
+  }
+  return len;
+}
+
 }  // namespace
 
 extern "C" int coclr_bn_finalize(const float* sum, const float* sumsq, int C, int ntiles,
@@ -739,7 +808,8 @@ extern "C" int coclr_bn_finalize_apply(const float* sum, const float* sumsq, int
                                        int64_t z_nstride, int relu, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (C <= 0 || ntiles <= 0 || N <= 0 || S <= 0 || !y || !z) return COCLR_EINVAL;
-  if ((long)N * S > kSmallChannel) {
+  const BnRoute rt = bn_route(N, C, (long)S, bn_vec((long)S, (long)y_nstride, (long)z_nstride), true, false);
+  if (!rt.one_wg) {
     // large layers: statistics in one launch, the streaming apply pass in another
     int rc = coclr_bn_finalize(sum, sumsq, C, ntiles, count, gamma, beta, running_mean, running_var,
                                num_batches_tracked, momentum, eps, mean, invstd, scale, shift, stream_);
@@ -747,8 +817,7 @@ extern "C" int coclr_bn_finalize_apply(const float* sum, const float* sumsq, int
     return coclr_bn_act_apply(y, scale, shift, nullptr, z, N, C, S, y_nstride, z_nstride, 0, relu,
                               stream_);
   }
-  const bool vec = (S % 4 == 0) && (y_nstride % 4 == 0) && (z_nstride % 4 == 0);
-  if (vec)
+  if (rt.vec)
     hipLaunchKernelGGL(bn_fwd_fused_kernel<true>, dim3(C), dim3(256), 0, stream, sum, sumsq, ntiles,
                        count, gamma, beta, running_mean, running_var, num_batches_tracked, momentum,
                        eps, mean, invstd, scale, shift, y, z, N, (int)S, (long)y_nstride,
@@ -765,24 +834,18 @@ extern "C" int coclr_bn_finalize_apply(const float* sum, const float* sumsq, int
 extern "C" int coclr_bn_finalize_apply_multi(const coclr_bn_fwd_call* calls, int n, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!calls || n < 1) return COCLR_EINVAL;
-  const char* env = getenv("COCLR_PAIR");
-  const bool fuse = !(env && env[0] == '0');
   int i = 0;
   while (i < n) {
     // a run of up to four small units (one workgroup per channel) with the same vector width
+    bool vec0 = false;
+    const int len = bn_fwd_run(calls, n, i, &vec0);
+    if (len < 0) return COCLR_EINVAL;
     BnFwdTable t;
     t.n = 0;
     long blocks = 0;
-    bool vec0 = false;
-    int j = i;
-    for (; j < n && t.n < 4; ++j) {
-      const coclr_bn_fwd_call& c = calls[j];
-      if (c.C <= 0 || c.ntiles <= 0 || c.N <= 0 || c.S <= 0 || !c.y || !c.z) return COCLR_EINVAL;
-      const bool small = (long)c.N * c.S <= kSmallChannel;
-      const bool vec = (c.S % 4 == 0) && (c.y_nstride % 4 == 0) && (c.z_nstride % 4 == 0);
-      if (!small || !fuse) break;
-      if (t.n == 0) vec0 = vec;
-      else if (vec != vec0) break;
+    const int j = i + len;
+    for (int q = i; q < j && len >= 2; ++q) {
+      const coclr_bn_fwd_call& c = calls[q];
       BnFwdUnit& u = t.u[t.n++];
       u.sum = c.sum; u.sumsq = c.sumsq; u.gamma = c.gamma; u.beta = c.beta;
       u.running_mean = c.running_mean; u.running_var = c.running_var; u.nbt = c.num_batches_tracked;
@@ -828,16 +891,16 @@ extern "C" int coclr_bn_act_apply(const float* y, const float* scale, const floa
                                   int64_t y_nstride, int64_t z_nstride, int64_t res_nstride,
                                   int relu, void* stream) {
   if (N <= 0 || C <= 0 || S <= 0) return COCLR_EINVAL;
-  const bool vec = (S % 4 == 0) && (y_nstride % 4 == 0) && (z_nstride % 4 == 0) &&
-                   (!residual || res_nstride % 4 == 0);
-  dim3 grid = plane_grid(N, C, (int)S);
+  const BnRoute rt = bn_route(N, C, (long)S, bn_vec((long)S, (long)y_nstride, (long)z_nstride,
+                                                     residual ? (long)res_nstride : 0), false, false);
+  const bool vec = rt.vec;
+  const dim3 grid(rt.gx, rt.gy);
   // Non-temporal loads / stores in the streaming BatchNorm passes: they move tensors of up to 2 GB through a chip
   // whose other streams run MFMA-bound kernels that live on what they keep re-reading from L2 / the 256 MB
   // infinity cache (weights, stencil windows, split-K partials).  Measured inside the step, same box, alternating
   // x4 (profiles/r06_bn_nontemporal_ab.txt): +1.3 % with every such pass non-temporal, +0.9 % with only the
   // tensors above 200 MB.  COCLR_BN_NT_MB=<MB> sets the size from which a pass is non-temporal, -1 switches it off.
-  static const long nt_bytes = bn_nt_bytes();
-  if (vec && nt_bytes >= 0 && (long)N * C * S * 4 >= nt_bytes)
+  if (rt.nt)
     hipLaunchKernelGGL((bn_act_apply_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, y, scale,
                        shift, residual, z, N, C, (int)S, (long)y_nstride, (long)z_nstride,
                        (long)res_nstride, relu);
@@ -868,10 +931,12 @@ extern "C" int coclr_bn_act_backward(const float* dz, const float* y, const floa
                                      int training, int dres_accumulate, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (N <= 0 || C <= 0 || S <= 0) return COCLR_EINVAL;
-  const bool vec = (S % 4 == 0) && (dz_nstride % 4 == 0) && (y_nstride % 4 == 0) &&
-                   (dy_nstride % 4 == 0) && (!z || z_nstride % 4 == 0) &&
-                   (!dres || dres_nstride % 4 == 0);
-  if (!z && !dres && (long)N * S <= kSmallChannel) {
+  const BnRoute rt = bn_route(N, C, (long)S,
+                              bn_vec((long)S, (long)dz_nstride, (long)y_nstride, (long)dy_nstride,
+                                     z ? (long)z_nstride : 0, dres ? (long)dres_nstride : 0),
+                              !z && !dres, true);
+  const bool vec = rt.vec;
+  if (rt.one_wg) {
     // small layers: one workgroup per channel, one launch (the workspace is not used)
     if (vec)
       hipLaunchKernelGGL(bn_bwd_fused_kernel<true>, dim3(C), dim3(256), 0, stream, dz, y, scale, shift,
@@ -884,11 +949,10 @@ extern "C" int coclr_bn_act_backward(const float* dz, const float* y, const floa
     COCLR_LAUNCH_CHECK();
     return 0;
   }
-  static const long nt_bytes_b = bn_nt_bytes();          // see coclr_bn_act_apply
   relu = relu ? 1 : 0;
-  if (nt_bytes_b >= 0 && vec && (long)N * C * S * 4 >= nt_bytes_b) relu |= 2;   // bit 1: non-temporal passes
+  if (rt.nt) relu |= 2;                                  // bit 1: non-temporal passes (see coclr_bn_act_apply)
   // pass 1: per (channel, sample group) partial sums of g and g*xhat
-  const int groups = reduce_groups(N, (int)S);
+  const int groups = rt.groups;
   dim3 rgrid(C, groups);
   if (vec)
     hipLaunchKernelGGL(bn_act_bwd_reduce_kernel<true>, rgrid, dim3(256), 0, stream, dz, y, z, scale,
@@ -901,7 +965,7 @@ extern "C" int coclr_bn_act_backward(const float* dz, const float* y, const floa
   COCLR_LAUNCH_CHECK();
   // pass 2: fold the partials, coefficients, dy (+ dres), dgamma / dbeta
   const double count = (double)N * (double)S;
-  dim3 grid = plane_grid(N, C, (int)S);
+  const dim3 grid(rt.gx, rt.gy);
   if (vec)
     hipLaunchKernelGGL(bn_act_bwd_apply_kernel<true>, grid, dim3(256), 0, stream, dz, y, z, scale,
                        shift, mean, invstd, sums_ws, groups, count, training, dgamma, dbeta, dy, dres,
@@ -923,11 +987,11 @@ extern "C" int coclr_bn_act_backward_coeffs(const float* dz, const float* y, con
                                             int relu, int training, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (N <= 0 || C <= 0 || S <= 0 || !coef || !sums_ws) return COCLR_EINVAL;
-  const bool vec = (S % 4 == 0) && (dz_nstride % 4 == 0) && (y_nstride % 4 == 0);
-  static const long nt_bytes_c = bn_nt_bytes();          // see coclr_bn_act_apply
+  const BnRoute rt = bn_route(N, C, (long)S, bn_vec((long)S, (long)dz_nstride, (long)y_nstride), false, true);
+  const bool vec = rt.vec;
   relu = relu ? 1 : 0;
-  if (nt_bytes_c >= 0 && vec && (long)N * C * S * 4 >= nt_bytes_c) relu |= 2;
-  const int groups = reduce_groups(N, (int)S);
+  if (rt.nt) relu |= 2;
+  const int groups = rt.groups;
   dim3 rgrid(C, groups);
   const float* noz = nullptr;
   if (vec)
@@ -952,10 +1016,12 @@ int bn_backward_from_partials(const coclr_bn_bwd_call& c, hipStream_t stream) {
   hipLaunchKernelGGL(bn_bwd_fold_kernel, dim3(c.C), dim3(256), 0, stream, c.part[0], c.part_ntiles[0],
                      c.part[1], c.part[1] ? c.part_ntiles[1] : 0, c.C, c.sums_ws);
   COCLR_LAUNCH_CHECK();
-  const bool vec = (c.S % 4 == 0) && (c.dz_nstride % 4 == 0) && (c.y_nstride % 4 == 0) &&
-                   (c.dy_nstride % 4 == 0);
+  const BnRoute rt = bn_route(c.N, c.C, (long)c.S,
+                              bn_vec((long)c.S, (long)c.dz_nstride, (long)c.y_nstride, (long)c.dy_nstride),
+                              false, false);
+  const bool vec = rt.vec;
   const double count = (double)c.N * (double)c.S;
-  dim3 grid = plane_grid(c.N, c.C, (int)c.S);
+  const dim3 grid(rt.gx, rt.gy);
   const float* nof = nullptr;
   float* nod = nullptr;
   if (vec)
@@ -976,24 +1042,17 @@ int bn_backward_from_partials(const coclr_bn_bwd_call& c, hipStream_t stream) {
 extern "C" int coclr_bn_act_backward_multi(const coclr_bn_bwd_call* calls, int n, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!calls || n < 1) return COCLR_EINVAL;
-  const char* env = getenv("COCLR_PAIR");
-  const bool fuse = !(env && env[0] == '0');
   int i = 0;
   while (i < n) {
+    bool vec0 = false;
+    const int len = bn_bwd_run(calls, n, i, &vec0);
+    if (len < 0) return COCLR_EINVAL;
     BnBwdTable t;
     t.n = 0;
     long blocks = 0;
-    bool vec0 = false;
-    int j = i;
-    for (; j < n && t.n < 4; ++j) {
-      const coclr_bn_bwd_call& c = calls[j];
-      if (c.N <= 0 || c.C <= 0 || c.S <= 0 || !c.dz || !c.y || !c.dy) return COCLR_EINVAL;
-      const bool small = (long)c.N * c.S <= kSmallChannel;
-      const bool vec = (c.S % 4 == 0) && (c.dz_nstride % 4 == 0) && (c.y_nstride % 4 == 0) &&
-                       (c.dy_nstride % 4 == 0);
-      if (!small || !fuse || c.part[0]) break;
-      if (t.n == 0) vec0 = vec;
-      else if (vec != vec0) break;
+    const int j = i + len;
+    for (int q = i; q < j && len >= 2; ++q) {
+      const coclr_bn_bwd_call& c = calls[q];
       BnBwdUnit& u = t.u[t.n++];
       u.dz = c.dz; u.y = c.y; u.scale = c.scale; u.shift = c.shift; u.mean = c.mean; u.invstd = c.invstd;
       u.dgamma = c.dgamma; u.dbeta = c.dbeta; u.dy = c.dy;
@@ -1023,5 +1082,53 @@ extern "C" int coclr_bn_act_backward_multi(const coclr_bn_bwd_call* calls, int n
     if (rc) return rc;
     ++i;
   }
+  return 0;
+}
+
+// The routes the entry points above take for one unit, nothing launched (usable without a device).  Forward:
+// coclr_bn_finalize_apply with y / z at y_nstride / z_nstride.  Backward: coclr_bn_act_backward with dz, y, dy
+// (and z / dres when has_z / has_dres) at their strides, or the from-partials form of coclr_bn_act_backward_multi
+// when has_partials.  out: 0 forward one-workgroup, 1 forward vector, 2 forward non-temporal, 3 forward grid x,
+// 4 forward grid y, 5 backward one-workgroup, 6 backward vector, 7 backward non-temporal, 8 reduce groups (0: no
+// reduce pass), 9 backward grid x, 10 backward grid y, 11 backward from partials.
+extern "C" int coclr_bn_plan(int N, int C, int64_t S, int64_t y_nstride, int64_t z_nstride, int64_t dz_nstride,
+                             int64_t dy_nstride, int64_t dres_nstride, int has_z, int has_dres,
+                             int has_partials, int32_t out[16]) {
+  if (N <= 0 || C <= 0 || S <= 0 || !out) return COCLR_EINVAL;
+  if (has_partials && (has_z || has_dres)) return COCLR_EINVAL;
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  const BnRoute f = bn_route(N, C, (long)S, bn_vec((long)S, (long)y_nstride, (long)z_nstride), true, false);
+  out[0] = f.one_wg; out[1] = f.vec; out[2] = f.nt; out[3] = f.gx; out[4] = f.gy;
+  BnRoute b;
+  if (has_partials)
+    b = bn_route(N, C, (long)S, bn_vec((long)S, (long)dz_nstride, (long)y_nstride, (long)dy_nstride), false, false);
+  else
+    b = bn_route(N, C, (long)S,
+                 bn_vec((long)S, (long)dz_nstride, (long)y_nstride, (long)dy_nstride, has_z ? (long)z_nstride : 0,
+                        has_dres ? (long)dres_nstride : 0),
+                 !has_z && !has_dres, true);
+  if (has_partials) b.nt = 0;      // the apply pass behind partial sums streams with temporal accesses
+  out[5] = b.one_wg; out[6] = b.vec; out[7] = b.nt; out[8] = b.groups; out[9] = b.gx; out[10] = b.gy;
+  out[11] = has_partials ? 1 : 0;
+  return 0;
+}
+
+// The launches coclr_bn_finalize_apply_multi (fwd given) or coclr_bn_act_backward_multi (bwd given) would make for
+// these n units, nothing launched: run_len[k] = units of launch k (>= 2: one fused multi launch; 1: the unit goes
+// through the single-unit entry point, or its from-partials form), terminated by 0; run_len holds n + 1 entries.
+// Only the units' shapes, strides, part[0] and the non-nullness of their operands are read.
+extern "C" int coclr_bn_multi_plan(const coclr_bn_fwd_call* fwd, const coclr_bn_bwd_call* bwd, int n,
+                                   int32_t* run_len) {
+  if ((fwd == nullptr) == (bwd == nullptr) || n < 1 || !run_len) return COCLR_EINVAL;
+  int k = 0;
+  for (int i = 0; i < n;) {
+    bool vec0 = false;
+    int len = fwd ? bn_fwd_run(fwd, n, i, &vec0) : bn_bwd_run(bwd, n, i, &vec0);
+    if (len < 0) return COCLR_EINVAL;
+    if (len < 2) len = 1;
+    run_len[k++] = len;
+    i += len;
+  }
+  run_len[k] = 0;
   return 0;
 }

@@ -142,7 +142,8 @@ maxpool3d_bwd_kernel(const float* __restrict__ dy, const int* __restrict__ idx, 
 template <int KT, int KH, int KW, int ST, int SH, int SW, int WPT, bool WITH_IDX>
 __global__ void __launch_bounds__(256)
 maxpool3d_tiled_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
-                           int* __restrict__ idx, const PoolGeom g, int G, int planes, int tfold) {
+                           int* __restrict__ idx, const PoolGeom g, int G, int planes, int tfold,
+                           int vec) {
   extern __shared__ float tile[];   // [G][Si]
   const int Si = g.Ti * g.Hi * g.Wi, So = g.To * g.Ho * g.Wo;
   const int pl0 = blockIdx.x * G;
@@ -154,7 +155,7 @@ maxpool3d_tiled_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
     const float* xp = x + (long)n * g.x_nstride + (long)c * Si;
     float* tp = tile + gi * Si;
     const int ch = c / g.tfold;          // channel of the un-folded tensor
-    if ((Si & 3) == 0 && ((g.x_nstride & 3) == 0)) {
+    if (vec) {      // PoolFwdPlan::vec: Si % 4 == 0 and x_nstride % 4 == 0
       for (int i = threadIdx.x; i < (Si >> 2); i += 256) {
         float4 v = pool_ld4(xp, i, g.nt != 0);
         v.x = pool_in(g, v.x, ch); v.y = pool_in(g, v.y, ch);
@@ -329,7 +330,7 @@ template <int PT, int PH, int PW, int KQ>
 __global__ void __launch_bounds__(256)
 maxpool3d_tiled_bwd_kernel(const float* __restrict__ dy, const int* __restrict__ idx, float* dx,
                            const PoolGeom g, long dy_nstride, long dx_nstride, int accumulate,
-                           int G, int planes, int tfold) {
+                           int G, int planes, int tfold, int vec) {
   extern __shared__ float tile[];   // [G][Si]
   const int Si = g.Ti * g.Hi * g.Wi, So = g.To * g.Ho * g.Wo;
   const int pl0 = blockIdx.x * G;
@@ -349,7 +350,7 @@ maxpool3d_tiled_bwd_kernel(const float* __restrict__ dy, const int* __restrict__
     const int n = pl / g.C, c = pl - n * g.C;
     float* dxp = dx + (long)n * dx_nstride + (long)c * Si;
     const float* tp = tile + gi * Si;
-    if ((Si & 3) == 0 && ((dx_nstride & 3) == 0)) {
+    if (vec) {      // PoolBwdPlan::vec: Si % 4 == 0 and dx_nstride % 4 == 0
       for (int i = threadIdx.x; i < (Si >> 2); i += 256) {
         float4 v = reinterpret_cast<const float4*>(tp)[i];
         if (accumulate) {
@@ -383,7 +384,7 @@ __device__ __forceinline__ void pool_take(PoolBest& b, float cv, int ci) {
 template <bool WITH_IDX, int TT>
 __global__ void __launch_bounds__(256)
 maxpool333_kernel(const float* __restrict__ x, float* __restrict__ y, int* __restrict__ idx,
-                  const PoolGeom g, int planes, int lW, int lHW) {
+                  const PoolGeom g, int planes, int lW, int lHW, int vec) {
   extern __shared__ float lds[];
   const int T = TT > 0 ? TT : g.Ti;                  // compile-time frame count: the t loops unroll
   const int W = 1 << lW, HW = 1 << lHW, H = HW >> lW;
@@ -394,7 +395,7 @@ maxpool333_kernel(const float* __restrict__ x, float* __restrict__ y, int* __res
   const int tid = threadIdx.x;
   const int pl0 = blockIdx.x * PG;
   const int gcount = min(PG, planes - pl0);
-  if ((g.x_nstride & 3) == 0) {
+  if (vec) {        // PoolFwdPlan::vec: x_nstride % 4 == 0 (S is a multiple of 16)
     // [PG][S] is one run of <= 1024 float4 slots: all of a thread's loads in flight at once
     const int S4 = S >> 2, total4 = gcount * S4;
     for (int e0 = tid; e0 < total4; e0 += 4 * 256) {
@@ -550,7 +551,7 @@ bn_pool_bwd_apply_kernel(const float* __restrict__ pdy, const int* __restrict__ 
                          const float* __restrict__ invstd, const double* __restrict__ sums, int groups,
                          double count, int training, float* dgamma, float* dbeta, float* dy,
                          const PoolGeom g, long pdy_nstride, long y_nstride, long dy_nstride, int relu,
-                         int G, int planes, int tfold) {
+                         int G, int planes, int tfold, int vec) {
   extern __shared__ float tile[];   // [G][Si]
   __shared__ double tot[2];
   __shared__ float coef[8][4];      // per volume of the group: A, B, D, (unused)
@@ -614,7 +615,7 @@ bn_pool_bwd_apply_kernel(const float* __restrict__ pdy, const int* __restrict__ 
     const float* yp = y + (long)n * y_nstride + (long)c * Si;
     float* dyp = dy + (long)n * dy_nstride + (long)c * Si;
     const float* tp = tile + gi * Si;
-    if ((Si & 3) == 0 && ((y_nstride | dy_nstride) & 3) == 0) {
+    if (vec) {      // PooledBnPlan::vec: Si % 4 == 0 and y_nstride, dy_nstride % 4 == 0
       for (int i = threadIdx.x; i < (Si >> 2); i += 256) {
         float4 gq = reinterpret_cast<const float4*>(tp)[i];
         const float4 v = pool_ld4(yp, i, g.nt != 0);
@@ -645,7 +646,7 @@ bn_pool_bwd_apply_kernel(const float* __restrict__ pdy, const int* __restrict__ 
 __global__ void __launch_bounds__(256)
 maxpool333_bwd_kernel(const float* __restrict__ dy, const int* __restrict__ idx, float* dx,
                       const PoolGeom g, long dy_nstride, long dx_nstride, int accumulate, int G,
-                      int planes, int lW, int lHW) {
+                      int planes, int lW, int lHW, int vec) {
   extern __shared__ float lds[];
   const int T = g.Ti, W = 1 << lW, HW = 1 << lHW, H = HW >> lW;
   const int S = T << lHW;
@@ -658,7 +659,10 @@ maxpool333_bwd_kernel(const float* __restrict__ dy, const int* __restrict__ idx,
     const int n = pl / g.C, c = pl - n * g.C;
     const float* dyp = dy + (long)n * dy_nstride + (long)c * S;
     const int* ip = idx + (long)pl * S;
-    if ((dy_nstride & 3) == 0) {
+    // PoolBwdPlan::vec: 16-byte staging needs whole float4 slots per volume, (S & 3) == 0 as well as
+    // (dy_nstride & 3) == 0: with S % 4 != 0 (H*W = 1 or 2 and few frames) the last S % 4 elements would stay
+    // unstaged and dyp / ip sit off 16 bytes for odd planes
+    if (vec) {
       for (int i = threadIdx.x; i < (S >> 2); i += 256) {
         reinterpret_cast<float4*>(dys + gi * S)[i] = reinterpret_cast<const float4*>(dyp)[i];
         reinterpret_cast<int4*>(ids + gi * S)[i] = reinterpret_cast<const int4*>(ip)[i];
@@ -710,19 +714,19 @@ inline int pick_group(int planes, int Si) {
 
 template <int KT, int KH, int KW, int ST, int SH, int SW, int WPT>
 int launch_tiled_fwd(const PoolGeom& g, const float* x, float* y, int* idx, int G, int planes,
-                     int tfold, hipStream_t stream) {
+                     int tfold, int vec, hipStream_t stream) {
   const size_t lds = (size_t)G * g.Ti * g.Hi * g.Wi * sizeof(float);
   const int blocks = (planes + G - 1) / G;
   if (idx) {
     auto k = maxpool3d_tiled_fwd_kernel<KT, KH, KW, ST, SH, SW, WPT, true>;
     static std::atomic<uint64_t> done{0};
     COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(k), kTileFloats * 4, done));
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds, stream, x, y, idx, g, G, planes, tfold);
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds, stream, x, y, idx, g, G, planes, tfold, vec);
   } else {
     auto k = maxpool3d_tiled_fwd_kernel<KT, KH, KW, ST, SH, SW, WPT, false>;
     static std::atomic<uint64_t> done{0};
     COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(k), kTileFloats * 4, done));
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds, stream, x, y, idx, g, G, planes, tfold);
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds, stream, x, y, idx, g, G, planes, tfold, vec);
   }
   COCLR_LAUNCH_CHECK();
   return 0;
@@ -791,6 +795,87 @@ static inline int ilog2_exact(int v) {
   return (1 << l) == v ? l : -1;
 }
 
+// ---------------------------------------------------------------------------
+// Dispatch plans.  Every launcher below switches on one of these structs and coclr_pool_plan reports the same
+// structs without launching, so the tests' view of "which kernel does this shape reach" is the launchers' own.
+// ---------------------------------------------------------------------------
+namespace {
+
+enum { kFwdGeneric = 0, kFwdSep333 = 1, kFwdTiled = 2 };
+enum { kBwdGeneric = 0, kBwdGather333 = 1, kBwdClasses = 2 };
+
+inline bool is_333_s1_p1(const PoolGeom& g) {
+  return g.kt == 3 && g.kh == 3 && g.kw == 3 && g.st == 1 && g.sh == 1 && g.sw == 1 && g.pt == 1 && g.ph == 1 &&
+         g.pw == 1;
+}
+
+struct PoolFwdPlan {
+  int family;        // kFwd*
+  int tmpl;          // separable: TT (0: run-time frame count); tiled: row of the template table; generic: 0
+  int G;             // volumes per workgroup (PG of the separable kernel)
+  int gx, gy;        // grid
+  int tfold;
+  int vec;           // 16-byte staging of x
+  int lds;           // dynamic LDS bytes
+  int lW, lHW;       // separable kernel only
+  int planes;        // (folded) volumes
+  PoolGeom g;        // the geometry the kernel gets (T folded into the planes for the tiled family)
+};
+
+inline PoolFwdPlan plan_pool_fwd(const PoolGeom& g, bool with_idx) {
+  PoolFwdPlan p;
+  p.family = kFwdGeneric; p.tmpl = 0; p.G = 1; p.tfold = 1; p.vec = 0; p.lds = 0; p.lW = p.lHW = 0;
+  p.planes = g.N * g.C;
+  p.g = g;
+  if (is_333_s1_p1(g)) {
+    // inception pool branch: separable scan, thread = (volume, h, w)
+    const int lW = ilog2_exact(g.Wi), lHW = ilog2_exact(g.Hi * g.Wi);
+    if (lW >= 0 && lHW >= 4 && lHW <= 8 && g.Ti <= 32) {
+      const int PG = 256 >> lHW, S = g.Ti << lHW;
+      const size_t lds = (size_t)PG * S * 4 * (with_idx ? 3 : 2);
+      if (lds <= 64 * 1024) {
+        p.family = kFwdSep333;
+        p.tmpl = (g.Ti == 16 || g.Ti == 8 || g.Ti == 4) ? g.Ti : 0;
+        p.G = PG; p.gx = cdiv(p.planes, PG); p.gy = 1;
+        p.vec = (g.x_nstride & 3) == 0;
+        p.lds = (int)lds; p.lW = lW; p.lHW = lHW;
+        return p;
+      }
+    }
+  }
+  {
+    // LDS-tiled fast paths; T is folded into the plane count when the stencil ignores it
+    const PoolGeom f = fold_time(g);
+    const int Si = f.Ti * f.Hi * f.Wi;
+    const int planes = f.N * f.C;
+    const int G = pick_group(planes, Si);
+    if (G > 0) {
+      const int k[3] = {f.kt, f.kh, f.kw}, s[3] = {f.st, f.sh, f.sw};
+#define POOL_IS(a, b, c, e, ff, gg) (k[0] == a && k[1] == b && k[2] == c && s[0] == e && s[1] == ff && s[2] == gg)
+      int row = -1;
+      if (POOL_IS(1, 3, 3, 1, 2, 2)) row = 0;
+      else if (POOL_IS(3, 3, 3, 1, 1, 1)) row = 1;
+      else if (POOL_IS(3, 3, 3, 2, 2, 2)) row = 2;
+      else if (POOL_IS(2, 2, 2, 2, 2, 2)) row = 3;
+#undef POOL_IS
+      if (row >= 0) {
+        p.family = kFwdTiled; p.tmpl = row; p.G = G; p.gx = (planes + G - 1) / G; p.gy = 1;
+        p.tfold = f.Ti == g.Ti ? 1 : g.Ti;
+        p.vec = (Si & 3) == 0 && (f.x_nstride & 3) == 0;
+        p.lds = (int)((size_t)G * Si * sizeof(float));
+        p.planes = planes;
+        p.g = f;
+        return p;
+      }
+    }
+  }
+  const dim3 grid = pool_grid(g.N * g.C, g.To * g.Ho * g.Wo);
+  p.gx = (int)grid.x; p.gy = (int)grid.y;
+  return p;
+}
+
+}  // namespace
+
 extern "C" int coclr_maxpool3d_fwd(const coclr_pool_desc* d, const float* x, float* y,
                                    int32_t* indices, const float* in_scale, const float* in_shift,
                                    int in_relu, void* stream) {
@@ -799,52 +884,34 @@ extern "C" int coclr_maxpool3d_fwd(const coclr_pool_desc* d, const float* x, flo
   if ((in_scale == nullptr) != (in_shift == nullptr)) return COCLR_EINVAL;
   PoolGeom g = to_geom(d);
   g.in_scale = in_scale; g.in_shift = in_shift; g.in_relu = in_relu;
-  if (g.kt == 3 && g.kh == 3 && g.kw == 3 && g.st == 1 && g.sh == 1 && g.sw == 1 && g.pt == 1 &&
-      g.ph == 1 && g.pw == 1) {
-    // inception pool branch: separable scan, thread = (volume, h, w)
-    const int lW = ilog2_exact(g.Wi), lHW = ilog2_exact(g.Hi * g.Wi);
-    if (lW >= 0 && lHW >= 4 && lHW <= 8 && g.Ti <= 32) {
-      const int PG = 256 >> lHW, S = g.Ti << lHW;
-      const int planes = g.N * g.C;
-      const size_t lds = (size_t)PG * S * 4 * (indices ? 3 : 2);
-      if (lds <= 64 * 1024) {
-        const dim3 grid(cdiv(planes, PG));
-        hipStream_t st = (hipStream_t)stream;
+  const PoolFwdPlan p = plan_pool_fwd(g, indices != nullptr);
+  hipStream_t st = (hipStream_t)stream;
+  if (p.family == kFwdSep333) {
+    const dim3 grid(p.gx);
+    const size_t lds = (size_t)p.lds;
+    const int planes = p.planes, lW = p.lW, lHW = p.lHW;
 #define POOL333(TT)                                                                                  \
-        if (indices) hipLaunchKernelGGL((maxpool333_kernel<true, TT>), grid, dim3(256), lds, st, x, y, \
-                                        indices, g, planes, lW, lHW);                                \
-        else hipLaunchKernelGGL((maxpool333_kernel<false, TT>), grid, dim3(256), lds, st, x, y,       \
-                                indices, g, planes, lW, lHW)
-        if (g.Ti == 16) { POOL333(16); }
-        else if (g.Ti == 8) { POOL333(8); }
-        else if (g.Ti == 4) { POOL333(4); }
-        else { POOL333(0); }
+    if (indices) hipLaunchKernelGGL((maxpool333_kernel<true, TT>), grid, dim3(256), lds, st, x, y, \
+                                    indices, g, planes, lW, lHW, p.vec);                         \
+    else hipLaunchKernelGGL((maxpool333_kernel<false, TT>), grid, dim3(256), lds, st, x, y,       \
+                            indices, g, planes, lW, lHW, p.vec)
+    if (p.tmpl == 16) { POOL333(16); }
+    else if (p.tmpl == 8) { POOL333(8); }
+    else if (p.tmpl == 4) { POOL333(4); }
+    else { POOL333(0); }
 #undef POOL333
-        COCLR_LAUNCH_CHECK();
-        return 0;
-      }
+    COCLR_LAUNCH_CHECK();
+    return 0;
+  }
+  if (p.family == kFwdTiled) {
+    switch (p.tmpl) {
+      case 0: return launch_tiled_fwd<1, 3, 3, 1, 2, 2, 2>(p.g, x, y, indices, p.G, p.planes, p.tfold, p.vec, st);
+      case 1: return launch_tiled_fwd<3, 3, 3, 1, 1, 1, 4>(p.g, x, y, indices, p.G, p.planes, p.tfold, p.vec, st);
+      case 2: return launch_tiled_fwd<3, 3, 3, 2, 2, 2, 2>(p.g, x, y, indices, p.G, p.planes, p.tfold, p.vec, st);
+      default: return launch_tiled_fwd<2, 2, 2, 2, 2, 2, 2>(p.g, x, y, indices, p.G, p.planes, p.tfold, p.vec, st);
     }
   }
-  {
-    // LDS-tiled fast paths; T is folded into the plane count when the stencil ignores it
-    const PoolGeom f = fold_time(g);
-    const int tfold = f.Ti == g.Ti ? 1 : g.Ti;
-    const int Si = f.Ti * f.Hi * f.Wi;
-    const int planes = f.N * f.C;
-    const int G = pick_group(planes, Si);
-    hipStream_t st = (hipStream_t)stream;
-    if (G > 0) {
-      const int k[3] = {f.kt, f.kh, f.kw}, s[3] = {f.st, f.sh, f.sw};
-#define POOL_IS(a, b, c, e, ff, gg) (k[0] == a && k[1] == b && k[2] == c && s[0] == e && s[1] == ff && s[2] == gg)
-      if (POOL_IS(1, 3, 3, 1, 2, 2)) return launch_tiled_fwd<1, 3, 3, 1, 2, 2, 2>(f, x, y, indices, G, planes, tfold, st);
-      if (POOL_IS(3, 3, 3, 1, 1, 1)) return launch_tiled_fwd<3, 3, 3, 1, 1, 1, 4>(f, x, y, indices, G, planes, tfold, st);
-      if (POOL_IS(3, 3, 3, 2, 2, 2)) return launch_tiled_fwd<3, 3, 3, 2, 2, 2, 2>(f, x, y, indices, G, planes, tfold, st);
-      if (POOL_IS(2, 2, 2, 2, 2, 2)) return launch_tiled_fwd<2, 2, 2, 2, 2, 2, 2>(f, x, y, indices, G, planes, tfold, st);
-#undef POOL_IS
-    }
-  }
-  hipLaunchKernelGGL(maxpool3d_fwd_kernel, pool_grid(g.N * g.C, g.To * g.Ho * g.Wo), dim3(256), 0,
-                     (hipStream_t)stream, x, y, indices, g);
+  hipLaunchKernelGGL(maxpool3d_fwd_kernel, dim3(p.gx, p.gy), dim3(256), 0, st, x, y, indices, g);
   COCLR_LAUNCH_CHECK();
   return 0;
 }
@@ -864,23 +931,49 @@ inline ClassShape class_shape(const PoolGeom& g, int G) {
 template <int PT, int PH, int PW, int KQ>
 int launch_tiled_bwd(const float* dy, const int32_t* indices, float* dx, const PoolGeom& g,
                      long dy_nstride, long dx_nstride, int accumulate, int G, int planes, int tfold,
-                     int Si, hipStream_t st) {
+                     int Si, int vec, hipStream_t st) {
   auto kern = maxpool3d_tiled_bwd_kernel<PT, PH, PW, KQ>;
   static std::atomic<uint64_t> done{0};
   COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), kTileFloats * 4, done));
   hipLaunchKernelGGL(kern, dim3((planes + G - 1) / G), dim3(256), (size_t)G * Si * sizeof(float), st,
-                     dy, indices, dx, g, dy_nstride, dx_nstride, accumulate, G, planes, tfold);
+                     dy, indices, dx, g, dy_nstride, dx_nstride, accumulate, G, planes, tfold, vec);
   COCLR_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" int coclr_maxpool3d_bwd(const coclr_pool_desc* d, const float* dy, const int32_t* indices,
-                                   float* dx, int64_t dy_nstride, int64_t dx_nstride,
-                                   int accumulate, void* stream) {
-  if (!d || d->N <= 0 || d->C <= 0) return COCLR_EINVAL;
-  const PoolGeom g0 = to_geom(d);
-  if (g0.kt == 3 && g0.kh == 3 && g0.kw == 3 && g0.st == 1 && g0.sh == 1 && g0.sw == 1 &&
-      g0.pt == 1 && g0.ph == 1 && g0.pw == 1) {
+namespace {
+
+// the colour-class templates: PT, PH, PW, KQ; a pool takes the first row with its class counts and kq <= KQ,
+// else the generic form (reported as 0, 0, 0, 0)
+struct ClassTemplate { int pt, ph, pw, kq; };
+constexpr ClassTemplate kBwdTemplates[4] = {{1, 2, 2, 1}, {3, 3, 3, 1}, {2, 2, 2, 1}, {1, 1, 1, 2}};
+constexpr ClassTemplate kPooledTemplates[2] = {{1, 2, 2, 1}, {2, 2, 2, 1}};
+
+inline int pick_class_template(const ClassShape& cs, const ClassTemplate* rows, int n) {
+  for (int i = 0; i < n; ++i)
+    if (cs.pt == rows[i].pt && cs.ph == rows[i].ph && cs.pw == rows[i].pw && cs.kq <= rows[i].kq) return i;
+  return -1;
+}
+
+struct PoolBwdPlan {
+  int family;        // kBwd*
+  int tmpl;          // colour classes: row of kBwdTemplates, -1: generic form
+  int G, kq;         // volumes per workgroup; outputs per thread and class for that G (colour classes)
+  int gx, gy;
+  int tfold;
+  int vec;           // 333 gather: 16-byte staging of dy / indices; colour classes: 16-byte stores of dx
+  int lds;
+  int lW, lHW;       // 333 gather only
+  int planes, Si;
+  PoolGeom g;
+};
+
+inline PoolBwdPlan plan_pool_bwd(const PoolGeom& g0, long dy_nstride, long dx_nstride) {
+  PoolBwdPlan p;
+  p.family = kBwdGeneric; p.tmpl = -1; p.G = 1; p.kq = 0; p.tfold = 1; p.vec = 0; p.lds = 0; p.lW = p.lHW = 0;
+  p.planes = g0.N * g0.C; p.Si = g0.Ti * g0.Hi * g0.Wi;
+  p.g = g0;
+  if (is_333_s1_p1(g0)) {
     const int lW = ilog2_exact(g0.Wi), lHW = ilog2_exact(g0.Hi * g0.Wi);
     const int S = g0.Ti * g0.Hi * g0.Wi;
     // measured (B=32): 4x4x4 volumes 0.027 ms gather vs 0.055 colour classes; 8x8x8 0.084 vs 0.075;
@@ -890,48 +983,102 @@ extern "C" int coclr_maxpool3d_bwd(const coclr_pool_desc* d, const float* dy, co
       int G = 2048 / S;              // ~16 KiB of LDS (dy + indices): 8 workgroups per CU
       if (G < 1) G = 1;
       while (G > 1 && (planes + G - 1) / G < 2048) G >>= 1;
-      hipLaunchKernelGGL(maxpool333_bwd_kernel, dim3((planes + G - 1) / G), dim3(256),
-                         (size_t)G * S * 8, (hipStream_t)stream, dy, indices, dx, g0,
-                         (long)dy_nstride, (long)dx_nstride, accumulate, G, planes, lW, lHW);
-      COCLR_LAUNCH_CHECK();
-      return 0;
+      p.family = kBwdGather333; p.G = G; p.gx = (planes + G - 1) / G; p.gy = 1;
+      p.vec = (S & 3) == 0 && (dy_nstride & 3) == 0;
+      p.lds = G * S * 8; p.lW = lW; p.lHW = lHW;
+      return p;
     }
   }
   {
     const PoolGeom g = fold_time(g0);
-    const int tfold = g.Ti == g0.Ti ? 1 : g0.Ti;
     const int Si = g.Ti * g.Hi * g.Wi;
     const int planes = g.N * g.C;
-    int G = pick_group(planes, Si);
-    if (G > 0) {
+    if (pick_group(planes, Si) > 0) {
       // a colour class holds ~1/27 of a volume's outputs: keep enough volumes per workgroup for its
       // 256 threads (1024 workgroups still fill the chip four deep)
-      G = 4096 / Si > 0 ? 4096 / Si : 1;
+      int G = 4096 / Si > 0 ? 4096 / Si : 1;
       while (G > 1 && (planes + G - 1) / G < 1024) G >>= 1;
       const ClassShape cs = class_shape(g, G);
-      hipStream_t st = (hipStream_t)stream;
-#define POOL_BWD(a, b, c, q)                                                                         \
-  if (cs.pt == a && cs.ph == b && cs.pw == c && cs.kq <= q)                                          \
-    return launch_tiled_bwd<a, b, c, q>(dy, indices, dx, g, (long)dy_nstride, (long)dx_nstride,      \
-                                        accumulate, G, planes, tfold, Si, st);
-      POOL_BWD(1, 2, 2, 1) POOL_BWD(3, 3, 3, 1) POOL_BWD(2, 2, 2, 1) POOL_BWD(1, 1, 1, 2)
-#undef POOL_BWD
-      return launch_tiled_bwd<0, 0, 0, 0>(dy, indices, dx, g, (long)dy_nstride, (long)dx_nstride,
-                                          accumulate, G, planes, tfold, Si, st);
+      p.family = kBwdClasses; p.tmpl = pick_class_template(cs, kBwdTemplates, 4);
+      p.G = G; p.kq = cs.kq; p.gx = (planes + G - 1) / G; p.gy = 1;
+      p.tfold = g.Ti == g0.Ti ? 1 : g0.Ti;
+      p.vec = (Si & 3) == 0 && (dx_nstride & 3) == 0;
+      p.lds = (int)((size_t)G * Si * sizeof(float));
+      p.planes = planes; p.Si = Si;
+      p.g = g;
+      return p;
     }
   }
-  const PoolGeom& g = g0;
-  hipLaunchKernelGGL(maxpool3d_bwd_kernel, pool_grid(g.N * g.C, g.Ti * g.Hi * g.Wi), dim3(256), 0,
-                     (hipStream_t)stream, dy, indices, dx, g, (long)dy_nstride, (long)dx_nstride,
-                     accumulate);
+  const dim3 grid = pool_grid(g0.N * g0.C, g0.Ti * g0.Hi * g0.Wi);
+  p.gx = (int)grid.x; p.gy = (int)grid.y;
+  return p;
+}
+
+struct PooledBnPlan {
+  int fits;
+  int tmpl;          // row of kPooledTemplates, -1: generic form
+  int G, kq, blocks, tfold, vec, lds, planes, Si;
+  PoolGeom g;
+};
+
+inline PooledBnPlan plan_pooled_bn(const PoolGeom& g0, long y_nstride, long dy_nstride) {
+  PooledBnPlan p;
+  const PoolGeom g = fold_time(g0);
+  p.g = g;
+  p.tfold = g.Ti == g0.Ti ? 1 : g0.Ti;
+  p.Si = g.Ti * g.Hi * g.Wi;
+  p.planes = g.N * g.C;
+  p.fits = p.Si <= kTileFloats;
+  p.tmpl = -1; p.G = 0; p.kq = 0; p.blocks = 0; p.vec = 0; p.lds = 0;
+  if (!p.fits) return p;
+  int G = 4096 / p.Si > 0 ? 4096 / p.Si : 1;
+  if (G > 8) G = 8;                // coef[8][4] of the apply kernel
+  while (G > 1 && (p.planes + G - 1) / G < 1024) G >>= 1;
+  const ClassShape cs = class_shape(g, G);
+  p.tmpl = pick_class_template(cs, kPooledTemplates, 2);
+  p.G = G; p.kq = cs.kq; p.blocks = (p.planes + G - 1) / G;
+  p.vec = (p.Si & 3) == 0 && ((y_nstride | dy_nstride) & 3) == 0;
+  p.lds = (int)((size_t)G * p.Si * sizeof(float));
+  return p;
+}
+
+}  // namespace
+
+extern "C" int coclr_maxpool3d_bwd(const coclr_pool_desc* d, const float* dy, const int32_t* indices,
+                                   float* dx, int64_t dy_nstride, int64_t dx_nstride,
+                                   int accumulate, void* stream) {
+  if (!d || d->N <= 0 || d->C <= 0) return COCLR_EINVAL;
+  const PoolGeom g0 = to_geom(d);
+  const PoolBwdPlan p = plan_pool_bwd(g0, (long)dy_nstride, (long)dx_nstride);
+  hipStream_t st = (hipStream_t)stream;
+  if (p.family == kBwdGather333) {
+    hipLaunchKernelGGL(maxpool333_bwd_kernel, dim3(p.gx), dim3(256), (size_t)p.lds, st, dy, indices, dx, g0,
+                       (long)dy_nstride, (long)dx_nstride, accumulate, p.G, p.planes, p.lW, p.lHW, p.vec);
+    COCLR_LAUNCH_CHECK();
+    return 0;
+  }
+  if (p.family == kBwdClasses) {
+#define POOL_BWD(a, b, c, q)                                                                         \
+    return launch_tiled_bwd<a, b, c, q>(dy, indices, dx, p.g, (long)dy_nstride, (long)dx_nstride,    \
+                                        accumulate, p.G, p.planes, p.tfold, p.Si, p.vec, st)
+    switch (p.tmpl) {           // rows of kBwdTemplates
+      case 0: POOL_BWD(1, 2, 2, 1);
+      case 1: POOL_BWD(3, 3, 3, 1);
+      case 2: POOL_BWD(2, 2, 2, 1);
+      case 3: POOL_BWD(1, 1, 1, 2);
+      default: POOL_BWD(0, 0, 0, 0);
+    }
+#undef POOL_BWD
+  }
+  hipLaunchKernelGGL(maxpool3d_bwd_kernel, dim3(p.gx, p.gy), dim3(256), 0, st, dy, indices, dx, g0,
+                     (long)dy_nstride, (long)dx_nstride, accumulate);
   COCLR_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int coclr_bn_act_backward_pooled_fits(const coclr_pool_desc* d, int* fits) {
   if (!d || !fits || d->N <= 0 || d->C <= 0) return COCLR_EINVAL;
-  const PoolGeom g = fold_time(to_geom(d));
-  *fits = g.Ti * g.Hi * g.Wi <= kTileFloats;
+  *fits = plan_pooled_bn(to_geom(d), 0, 0).fits;
   return 0;
 }
 
@@ -944,14 +1091,10 @@ extern "C" int coclr_bn_act_backward_pooled(const coclr_pool_desc* d, const floa
                                             int64_t dy_nstride, int relu, int training, void* stream) {
   if (!d || d->N <= 0 || d->C <= 0 || !pool_dy || !pool_idx || !y || !sums || !dy) return COCLR_EINVAL;
   const PoolGeom g0 = to_geom(d);
-  const PoolGeom g = fold_time(g0);
-  const int tfold = g.Ti == g0.Ti ? 1 : g0.Ti;
-  const int Si = g.Ti * g.Hi * g.Wi;
-  const int planes = g.N * g.C;
-  if (Si > kTileFloats) return COCLR_EINVAL;          // see coclr_bn_act_backward_pooled_fits
-  int G = 4096 / Si > 0 ? 4096 / Si : 1;
-  if (G > 8) G = 8;
-  while (G > 1 && (planes + G - 1) / G < 1024) G >>= 1;
+  const PooledBnPlan p = plan_pooled_bn(g0, (long)y_nstride, (long)dy_nstride);
+  if (!p.fits) return COCLR_EINVAL;                   // see coclr_bn_act_backward_pooled_fits
+  const PoolGeom& g = p.g;
+  const int tfold = p.tfold, Si = p.Si, planes = p.planes, G = p.G;
   hipStream_t st = (hipStream_t)stream;
   const int So0 = g0.To * g0.Ho * g0.Wo, Si0 = g0.Ti * g0.Hi * g0.Wi;
   hipLaunchKernelGGL(bn_pool_bwd_reduce_kernel, dim3(g0.C, g0.N), dim3(256), 0, st, pool_dy, pool_idx,
@@ -959,23 +1102,49 @@ extern "C" int coclr_bn_act_backward_pooled(const coclr_pool_desc* d, const floa
                      (long)y_nstride, relu);
   COCLR_LAUNCH_CHECK();
   const double count = (double)g0.N * Si0;
-  const ClassShape cs = class_shape(g, G);
 #define BN_POOL_BWD(a, b, c, q)                                                                      \
   do {                                                                                               \
     auto kern = bn_pool_bwd_apply_kernel<a, b, c, q>;                                                \
     static std::atomic<uint64_t> done{0};                                                            \
     COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), kTileFloats * 4, done));      \
-    hipLaunchKernelGGL(kern, dim3((planes + G - 1) / G), dim3(256), (size_t)G * Si * sizeof(float),  \
+    hipLaunchKernelGGL(kern, dim3(p.blocks), dim3(256), (size_t)G * Si * sizeof(float),              \
                        st, pool_dy, pool_idx, y, scale, shift, mean, invstd, sums, g0.N, count,      \
                        training, dgamma, dbeta, dy, g, (long)pool_dy_nstride, (long)y_nstride,       \
-                       (long)dy_nstride, relu, G, planes, tfold);                                    \
+                       (long)dy_nstride, relu, G, planes, tfold, p.vec);                             \
     COCLR_LAUNCH_CHECK();                                                                            \
     return 0;                                                                                        \
   } while (0)
-  if (cs.pt == 1 && cs.ph == 2 && cs.pw == 2 && cs.kq <= 1) BN_POOL_BWD(1, 2, 2, 1);
-  if (cs.pt == 2 && cs.ph == 2 && cs.pw == 2 && cs.kq <= 1) BN_POOL_BWD(2, 2, 2, 1);
+  if (p.tmpl == 0) BN_POOL_BWD(1, 2, 2, 1);           // rows of kPooledTemplates
+  if (p.tmpl == 1) BN_POOL_BWD(2, 2, 2, 1);
   BN_POOL_BWD(0, 0, 0, 0);
 #undef BN_POOL_BWD
+}
+
+// What the three launchers above would do for this descriptor, nothing launched (usable without a device).
+// dy_nstride / dx_nstride: sample strides of the backward's operands, 0: dense.  The pooled BatchNorm backward is
+// planned with y at the descriptor's x_nstride and its dy at dx_nstride (they have x's and dx's layout).
+extern "C" int coclr_pool_plan(const coclr_pool_desc* d, int with_indices, int64_t dy_nstride,
+                               int64_t dx_nstride, int32_t out[32]) {
+  if (!d || !out || d->N <= 0 || d->C <= 0) return COCLR_EINVAL;
+  if (d->pt * 2 > d->kt || d->ph * 2 > d->kh || d->pw * 2 > d->kw) return COCLR_EINVAL;
+  const PoolGeom g = to_geom(d);
+  if (!dy_nstride) dy_nstride = (int64_t)d->C * d->To * d->Ho * d->Wo;
+  if (!dx_nstride) dx_nstride = (int64_t)d->C * d->Ti * d->Hi * d->Wi;
+  for (int i = 0; i < 32; ++i) out[i] = 0;
+  const PoolFwdPlan f = plan_pool_fwd(g, with_indices != 0);
+  out[0] = f.family; out[1] = f.tmpl; out[2] = f.G; out[3] = f.gx; out[4] = f.gy; out[5] = f.tfold;
+  out[6] = f.vec; out[7] = f.lds;
+  const PoolBwdPlan b = plan_pool_bwd(g, (long)dy_nstride, (long)dx_nstride);
+  const ClassTemplate none = {0, 0, 0, 0};
+  const ClassTemplate bt = b.tmpl >= 0 ? kBwdTemplates[b.tmpl] : none;
+  out[8] = b.family; out[9] = bt.pt; out[10] = bt.ph; out[11] = bt.pw; out[12] = bt.kq; out[13] = b.G;
+  out[14] = b.kq; out[15] = b.gx; out[16] = b.gy; out[17] = b.tfold; out[18] = b.vec; out[19] = b.lds;
+  const PooledBnPlan q = plan_pooled_bn(g, (long)d->x_nstride, (long)dx_nstride);
+  const ClassTemplate qt = q.tmpl >= 0 ? kPooledTemplates[q.tmpl] : none;
+  out[20] = q.fits; out[21] = q.G; out[22] = qt.pt; out[23] = qt.ph; out[24] = qt.pw; out[25] = qt.kq;
+  out[26] = q.kq; out[27] = q.blocks; out[28] = q.tfold; out[29] = q.vec; out[30] = q.lds;
+  out[31] = g.nt;
+  return 0;
 }
 
 extern "C" int coclr_global_avgpool_fwd(const float* x, float* y, int64_t planes, int64_t S,

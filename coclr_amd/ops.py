@@ -371,6 +371,37 @@ class PoolGeom:
         self.desc_bw = None
         self._pooled_fits = None
 
+    _FWD_FAMILIES = ("generic", "sep333", "tiled")
+    _FWD_TILED = ((1, 3, 3, 1, 2, 2, 2), (3, 3, 3, 1, 1, 1, 4), (3, 3, 3, 2, 2, 2, 2), (2, 2, 2, 2, 2, 2, 2))
+    _BWD_FAMILIES = ("generic", "gather333", "classes")
+
+    def plan(self, with_indices=True, x_nstride=None, y_nstride=None, dy_nstride=None, dx_nstride=None):
+        """What maxpool_fwd, maxpool_bwd and bn_act_backward_pooled would launch for this geometry, from the
+        launchers' own plan structs (nothing is launched): dict(fwd=..., bwd=..., pooled=..., nt=...).  The strides
+        are the operands' sample strides (default: dense tensors); the pooled BatchNorm backward is planned with
+        y at x_nstride and its dy at dx_nstride.  The `vec` flags are what the launchers hand the kernels.  `template` is TT for the separable forward, the (KT, KH, KW, ST, SH, SW, WPT) row
+        for the tiled forward and (PT, PH, PW, KQ) for the colour-class forms, (0, 0, 0, 0) the generic form."""
+        d = PoolDesc.from_buffer_copy(self.desc)
+        si = self.idim[0] * self.idim[1] * self.idim[2]
+        so = self.odim[0] * self.odim[1] * self.odim[2]
+        d.x_nstride = x_nstride or self.C * si
+        d.y_nstride = y_nstride or self.C * so
+        out = (C.c_int32 * 32)()
+        _lib.check(_L().coclr_pool_plan(C.byref(d), int(bool(with_indices)), dy_nstride or 0, dx_nstride or 0,
+                                        out), "pool_plan", self)
+        fam = self._FWD_FAMILIES[out[0]]
+        fwd = dict(family=fam, G=out[2], grid=(out[3], out[4]), tfold=out[5], vec=bool(out[6]), lds=out[7],
+                   template=None if fam == "generic" else out[1] if fam == "sep333" else self._FWD_TILED[out[1]])
+        bfam = self._BWD_FAMILIES[out[8]]
+        bwd = dict(family=bfam, template=tuple(out[9:13]) if bfam == "classes" else None, G=out[13], kq=out[14],
+                   grid=(out[15], out[16]), tfold=out[17], vec=bool(out[18]), lds=out[19])
+        pooled = dict(fits=bool(out[20]), G=out[21], template=tuple(out[22:26]) if out[20] else None, kq=out[26],
+                      blocks=out[27], tfold=out[28], vec=bool(out[29]), lds=out[30])
+        return dict(fwd=fwd, bwd=bwd, pooled=pooled, nt=bool(out[31]))
+
+    def __repr__(self):
+        return "PoolGeom(N=%d, C=%d, in=%s, k=%s, s=%s, p=%s)" % (self.N, self.C, self.idim, self.k, self.s, self.p)
+
 
 # ---- convolution ---------------------------------------------------------------
 
@@ -609,6 +640,49 @@ def bn_act_apply(y, scale, shift, residual, z, relu):
         _p(y), _p(scale), _p(shift), _p(residual), _p(z), N, C_, S, _chk5(y, "y"), _chk5(z, "z"),
         _chk5(residual, "residual") if residual is not None else 0, int(relu), _stream()),
         "bn_act_apply")
+
+
+def bn_plan(N, C_, S, y_nstride=None, z_nstride=None, dz_nstride=None, dy_nstride=None, dres_nstride=None,
+            has_z=False, has_dres=False, has_partials=False):
+    """The routes of one BatchNorm unit, from the launchers' own route struct (nothing is launched):
+    dict(fwd=..., bwd=...), each with one_wg (one workgroup per channel), vec, nt and the streaming pass's
+    plane grid; bwd also has `groups` (sample groups of the reduce pass, 0: none) and `partials`.  Strides
+    default to dense tensors."""
+    dense = C_ * S
+    out = (C.c_int32 * 16)()
+    _lib.check(_L().coclr_bn_plan(N, C_, S, y_nstride or dense, z_nstride or dense, dz_nstride or dense,
+                                  dy_nstride or dense, dres_nstride or dense, int(bool(has_z)),
+                                  int(bool(has_dres)), int(bool(has_partials)), out), "bn_plan")
+    return dict(fwd=dict(one_wg=bool(out[0]), vec=bool(out[1]), nt=bool(out[2]), grid=(out[3], out[4])),
+                bwd=dict(one_wg=bool(out[5]), vec=bool(out[6]), nt=bool(out[7]), groups=out[8],
+                         grid=(out[9], out[10]), partials=bool(out[11])))
+
+
+def bn_multi_plan(units, backward=False):
+    """How bn_finalize_apply_multi (or, with backward, bn_act_backward_multi) would cut these units into launches,
+    from the launchers' own run-cutting function (nothing is launched): a list of run lengths (>= 2: one fused
+    launch, 1: the unit goes alone).  units: [dict(N, C, S, y_nstride, z_nstride)] or, backward,
+    [dict(N, C, S, dz_nstride, y_nstride, dy_nstride, partials=False)]; strides default to dense."""
+    n = len(units)
+    arr = ((BnBwdCall if backward else BnFwdCall) * n)()
+    for a, u in zip(arr, units):
+        dense = u["C"] * u["S"]
+        a.N, a.C, a.S = u["N"], u["C"], u["S"]
+        a.y = 16                      # operands only have to be non-null: nothing is dereferenced
+        a.y_nstride = u.get("y_nstride") or dense
+        if backward:
+            a.dz = a.dy = 16
+            a.dz_nstride, a.dy_nstride = u.get("dz_nstride") or dense, u.get("dy_nstride") or dense
+            if u.get("partials"):
+                a.part[0] = 16
+                a.part_ntiles[0] = 1
+        else:
+            a.z, a.ntiles = 16, 1
+            a.z_nstride = u.get("z_nstride") or dense
+    out = (C.c_int32 * (n + 1))()
+    _lib.check(_L().coclr_bn_multi_plan(None if backward else arr, arr if backward else None, n, out),
+               "bn_multi_plan")
+    return [v for v in out[:n] if v]
 
 
 def bn_backward_workspace(N, C_):

@@ -292,6 +292,18 @@ int coclr_bn_act_apply(const float* y, const float* scale, const float* shift,
  * pair per (channel, sample) -- coclr_bn_backward_workspace doubles; no zero-fill needed,
  * no atomics (run-to-run deterministic). */
 int coclr_bn_backward_workspace(int N, int C, int64_t* doubles);
+/* The routes of one BatchNorm unit; launches nothing and needs no device (ABI 25).  Answered by the route struct
+ * the launchers switch on.  Forward: coclr_bn_finalize_apply with y / z at y_nstride / z_nstride.  Backward:
+ * coclr_bn_act_backward with dz, y, dy (and z / dres when has_z / has_dres) at their strides, or the
+ * from-partials form of coclr_bn_act_backward_multi when has_partials.
+ *  out[0] forward one workgroup per channel    out[1] forward 16-byte    out[2] forward non-temporal
+ *  out[3], out[4] forward plane grid x, y (0 for the one-workgroup form)
+ *  out[5] backward one workgroup per channel   out[6] backward 16-byte   out[7] backward non-temporal
+ *  out[8] sample groups of the reduce pass (0: none)    out[9], out[10] backward plane grid x, y
+ *  out[11] from partials */
+int coclr_bn_plan(int N, int C, int64_t S, int64_t y_nstride, int64_t z_nstride, int64_t dz_nstride,
+                  int64_t dy_nstride, int64_t dres_nstride, int has_z, int has_dres, int has_partials,
+                  int32_t out[16]);
 int coclr_bn_act_backward(const float* dz, const float* y, const float* z, const float* scale,
                           const float* shift, const float* mean, const float* invstd,
                           double* sums_ws, float* dy, float* dres, float* dgamma, float* dbeta,
@@ -363,6 +375,13 @@ typedef struct coclr_bn_bwd_call {
 } coclr_bn_bwd_call;
 int coclr_bn_finalize_apply_multi(const coclr_bn_fwd_call* calls, int n, void* stream);
 int coclr_bn_act_backward_multi(const coclr_bn_bwd_call* calls, int n, void* stream);
+/* The launches the two entry points above would make for these n units (exactly one of fwd / bwd given); launches
+ * nothing and needs no device (ABI 25).  Answered by the run-cutting function the launchers themselves call: a run
+ * is up to four consecutive units that take the one-workgroup route, share a vector width and (backward) carry no
+ * partial sums; COCLR_PAIR=0 keeps every unit alone.  run_len[k] = units of launch k (>= 2: one fused launch, 1: the
+ * unit goes alone), terminated by 0: n + 1 entries.  Reads only shapes, strides, part[0] and whether the operand
+ * pointers are null (COCLR_EINVAL as the launch). */
+int coclr_bn_multi_plan(const coclr_bn_fwd_call* fwd, const coclr_bn_bwd_call* bwd, int n, int32_t* run_len);
 
 /* BatchNorm(+ReLU) backward of a unit whose only consumer is the max-pool described by `d` that
  * applied the unit's affine + ReLU while reading (coclr_maxpool3d_fwd with in_scale / in_shift): the
@@ -381,6 +400,28 @@ int coclr_bn_act_backward_pooled(const coclr_pool_desc* d, const float* pool_dy,
                                  int64_t pool_dy_nstride, int64_t y_nstride, int64_t dy_nstride,
                                  int relu, int training, void* stream);
 int coclr_bn_act_backward_pooled_fits(const coclr_pool_desc* d, int* fits);
+
+/* What coclr_maxpool3d_fwd, coclr_maxpool3d_bwd and coclr_bn_act_backward_pooled would launch for this descriptor
+ * (x_nstride / y_nstride filled in as for the launch); launches nothing and needs no device (ABI 25).  Answered
+ * by the plan structs the launchers themselves switch on.  with_indices: the forward writes arg-max indices.
+ * dy_nstride / dx_nstride: sample strides of the backward's operands, 0: dense.  The pooled BatchNorm backward
+ * is planned with y at x_nstride and its dy at dx_nstride.  The 16-byte flags (out[6], out[18], out[29]) are the
+ * values the launchers pass to the kernels, which branch on nothing else.
+ *  out[0]  forward family: 0 generic, 1 separable 3x3x3/1/1, 2 LDS-tiled
+ *  out[1]  forward template: separable TT (0: run-time frame count); tiled row 0 (1,3,3)/(1,2,2) WPT 2,
+ *          1 (3,3,3)/(1,1,1) WPT 4, 2 (3,3,3)/(2,2,2) WPT 2, 3 (2,2,2)/(2,2,2) WPT 2
+ *  out[2]  volumes per workgroup (PG / G)    out[3], out[4] grid x, y    out[5] tfold
+ *  out[6]  16-byte staging of x              out[7] dynamic LDS bytes
+ *  out[8]  backward family: 0 generic gather, 1 3x3x3/1/1 gather, 2 colour-class tiled
+ *  out[9..12] colour-class template PT, PH, PW, KQ (all 0: the generic form)
+ *  out[13] G    out[14] outputs per thread and class for that G (kq)    out[15], out[16] grid x, y
+ *  out[17] tfold    out[18] 16-byte staging of dy / indices (gather) or stores of dx (tiled)    out[19] LDS bytes
+ *  out[20] pooled BatchNorm backward fits    out[21] G    out[22..25] template PT, PH, PW, KQ (0: generic form)
+ *  out[26] kq    out[27] workgroups    out[28] tfold    out[29] 16-byte apply pass    out[30] LDS bytes
+ *  out[31] non-temporal streaming (COCLR_BN_NT_MB)
+ * COCLR_EINVAL for a null argument or a descriptor the forward refuses. */
+int coclr_pool_plan(const coclr_pool_desc* d, int with_indices, int64_t dy_nstride, int64_t dx_nstride,
+                    int32_t out[32]);
 /* aten::adaptive_avg_pool3d(x, (1,1,1)) and its backward; planes = N*C. */
 int coclr_global_avgpool_fwd(const float* x, float* y, int64_t planes, int64_t S, void* stream);
 int coclr_global_avgpool_bwd(const float* dy, float* dx, int64_t planes, int64_t S, void* stream);

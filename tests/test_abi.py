@@ -78,6 +78,20 @@ def test_planning_entry_points():
     assert ops.conv_packed_size(3, 64, 49, False) == 49 * 32 * 128
     assert ops.conv_packed_size(3, 64, 49, True) == 49 * 64 * 128
     assert ops.gemm_workspace(32, 128, 16384, 128) == 128 * 32 * 128
+    # MaxPool_2a behind Conv_1a at the benchmark size, and the inception pool branch of Mixed_3b
+    pl = ops.PoolGeom(32, 64, (16, 64, 64), (1, 3, 3), (1, 2, 2), (0, 1, 1)).plan()
+    assert pl["fwd"]["family"] == "tiled" and pl["fwd"]["tfold"] == 16 and pl["fwd"]["G"] == 1 and pl["fwd"]["vec"]
+    assert pl["bwd"]["family"] == "classes" and pl["bwd"]["template"] == (1, 2, 2, 1)
+    assert pl["pooled"]["fits"] and pl["pooled"]["template"] == (1, 2, 2, 1)
+    pl = ops.PoolGeom(32, 192, (16, 16, 16), (3, 3, 3), (1, 1, 1), (1, 1, 1)).plan()
+    assert (pl["fwd"]["family"], pl["fwd"]["template"], pl["fwd"]["G"]) == ("sep333", 16, 1)
+    assert pl["bwd"]["family"] == "classes" and pl["bwd"]["template"] == (3, 3, 3, 1)
+    # a 1x1x1 map (Mixed_5b/5c at 32x32 input): the gather backward without 16-byte staging
+    pl = ops.PoolGeom(32, 832, (1, 1, 1), (3, 3, 3), (1, 1, 1), (1, 1, 1)).plan()
+    assert pl["bwd"]["family"] == "gather333" and not pl["bwd"]["vec"] and pl["bwd"]["G"] > 1
+    bp = ops.bn_plan(32, 64, 16 * 64 * 64)
+    assert not bp["fwd"]["one_wg"] and bp["bwd"]["groups"] == 32 and bp["bwd"]["vec"]
+    assert ops.bn_plan(32, 832, 64)["bwd"]["one_wg"]
 
 
 def test_rejected_arguments():
