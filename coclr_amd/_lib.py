@@ -138,6 +138,8 @@ _SIGNATURES = {
                                  vp, vp],
     "coclr_augment_clips": [vp, i32, i32, i32, i32, vp, vp, _P(i32), _P(f32), i32, i32, i32, _P(f32), _P(f32), vp, vp],
     "coclr_resize_boxes_u8": [vp, i32, i32, i32, vp, _P(i32), i32, i32, i32, vp, i64, vp, i64, vp, vp],
+    "coclr_resize2_boxes": [vp, i32, i32, i32, vp, _P(i32), i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, i32, _P(f32),
+                            _P(f32), vp, vp, vp],
     "coclr_colstats_workspace": [i32, i32, _P(i64)],
     "coclr_bn1d_stats": [vp, vp, vp, i32, i32, vp],
     "coclr_center_rows": [vp, vp, vp, i32, i32, vp],

@@ -260,6 +260,163 @@ resize_boxes_kernel(const BoxArgs a) {
   }
 }
 
+// ---- the classifier's crop chain (eval/main_classifier.py:729-744; utils/augmentation.py:21-58,90-146) -------------
+// RandomSizedCrop(size, consistent=True) -> Scale(img_dim): TWO of PIL's 8-bit resizes per frame, the first either of
+// a drawn box to size x size or (the fallback, after ten draws that do not fit) of the whole frame to (ow, oh) of which
+// CenterCrop keeps a size x size window.  Both are "resample region (x0, y0, w, h) and keep size columns / rows of the
+// result": the window is in the TABLES (the host hands over the window's columns / rows of resample_tables(w, ow) /
+// (h, oh)), so the kernel sees one form.  The second resize is size -> S on both axes, one table for every clip.
+// Four passes, each rounded and clamped to bytes on its own as PIL does: H1, V1 (the size x size image), H2, V2.
+// One workgroup per (band of R rows of the S x S output, slot = (clip, t)) with everything between the source frame
+// and the output in LDS:
+//   one   [rows1][3][P]   H1 of the source rows the band's intermediate rows need (P = size rounded up to 4)
+//   mid   [arows][3][P]   V1: the band's rows of the size x size image
+//   one   [arows][3][Sp]  H2 of those rows (`one` again: H1's rows are dead after V1)
+// and V2 stores bytes (the input of coclr_augment_clips) or normalised fp32 with the arithmetic of stage_crops_kernel.
+// The descriptors and all tables are device data: every index derived from them is clamped into the region, the
+// staged rows or the table buffers (the entry point validates the host copy of the descriptors before the launch).
+enum { CLS_FIRST = 0, CLS_FRAMES, CLS_X0, CLS_Y0, CLS_W, CLS_H, CLS_OW, CLS_OH, CLS_CX, CLS_CY, CLS_XOFF, CLS_YOFF,
+       CLS_XTAPS, CLS_YTAPS, CLS_FIELDS };
+constexpr int kClsThreads = 512;
+constexpr int kClsMaxSide = 224;             // size and S: what coclr_augment_clips takes
+constexpr int kClsLdsTwo = 80 * 1024;        // a band's footprint that leaves room for two workgroups per CU
+constexpr int kClsLdsMax = 160 * 1024;
+
+struct Resize2Args {
+  const uint8_t* frames; const int32_t* desc;
+  const int32_t *xtab, *ytab;                // stage 1, per clip: min[P], k[taps][P] of the window's columns / rows
+  const int32_t* tab2;                       // stage 2, shared: min[Sp], k[taps2][Sp]
+  uint8_t* out8;                             // [n_clips*T][S][S][3]
+  float* out;                                // [n_clips][3][T][S][S], normalised
+  float mean[3], std[3];
+  int F, H, W, T, size, P, S, Sp, taps2, R, cap1, capA, xlen, ylen;
+};
+
+template <bool U8OUT>
+__global__ void __launch_bounds__(kClsThreads)
+resize2_boxes_kernel(const Resize2Args a) {
+  extern __shared__ __align__(16) uint8_t lds2[];
+  const int tid = threadIdx.x;
+  const int band = blockIdx.x, slot = blockIdx.y;
+  const int clip = slot / a.T, t = slot % a.T;
+  const int32_t* d = a.desc + (long)clip * CLS_FIELDS;
+  const int P = a.P, nx1 = P >> 2, Sp = a.Sp, nx2 = Sp >> 2, size = a.size;
+  const int f = clampi(d[CLS_FIRST] + t, 0, a.F - 1);
+  const int x0 = clampi(d[CLS_X0], 0, a.W - 1), y0 = clampi(d[CLS_Y0], 0, a.H - 1);
+  const int cw = clampi(d[CLS_W], 1, a.W - x0), ch = clampi(d[CLS_H], 1, a.H - y0);
+  const int xtaps = clampi(d[CLS_XTAPS], 1, min(64, a.xlen / P - 1));
+  const int ytaps = clampi(d[CLS_YTAPS], 1, min(64, a.ylen / P - 1));
+  const int32_t* xmin = a.xtab + clampi(d[CLS_XOFF] & ~3, 0, a.xlen - P * (1 + xtaps));
+  const int32_t* ymin = a.ytab + clampi(d[CLS_YOFF] & ~3, 0, a.ylen - P * (1 + ytaps));
+  const int32_t *xk = xmin + P, *yk = ymin + P;
+  const int32_t *min2 = a.tab2, *k2 = a.tab2 + Sp;
+  const int taps2 = a.taps2;
+  const int r0 = band * a.R, r1 = min(r0 + a.R, a.S);                  // output rows [r0, r1)
+  // the band's rows [alo, alo + arows) of the size x size image, and their source rows [ylo, ylo + rows1) of the region
+  const int alo = clampi(min2[r0], 0, size - 1);
+  const int arows = min(clampi(min2[r1 - 1] + taps2, alo + 1, size) - alo, a.capA);
+  const int ylo = clampi(ymin[alo], 0, ch - 1);
+  const int rows1 = min(clampi(ymin[alo + arows - 1] + ytaps, ylo + 1, ch) - ylo, a.cap1);
+  unsigned* one = reinterpret_cast<unsigned*>(lds2);
+  const int one_bytes = max(a.cap1 * 3 * P, a.capA * 3 * Sp);
+  unsigned* mid = reinterpret_cast<unsigned*>(lds2 + one_bytes);
+  const uint8_t* fr = a.frames + ((long)f * a.H + (y0 + ylo)) * (long)a.W * 3 + x0 * 3;
+
+  // H1: item = (row, c, xg), xg fastest
+  for (int it = tid; it < rows1 * 3 * nx1; it += kClsThreads) {
+    const int xg = it % nx1, rc = it / nx1;
+    const int c = rc % 3, row = rc / 3;
+    const uint8_t* src = fr + (long)row * a.W * 3 + c;
+    const int4 xm = reinterpret_cast<const int4*>(xmin)[xg];
+    int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+    for (int i = 0; i < xtaps; ++i) {
+      const int4 k = reinterpret_cast<const int4*>(xk + (long)i * P)[xg];
+      a0 += k.x * (int)src[3 * clampi(xm.x + i, 0, cw - 1)];
+      a1 += k.y * (int)src[3 * clampi(xm.y + i, 0, cw - 1)];
+      a2 += k.z * (int)src[3 * clampi(xm.z + i, 0, cw - 1)];
+      a3 += k.w * (int)src[3 * clampi(xm.w + i, 0, cw - 1)];
+    }
+    one[(row * 3 + c) * nx1 + xg] = fix8(a0) | (fix8(a1) << 8) | (fix8(a2) << 16) | (fix8(a3) << 24);
+  }
+  __syncthreads();
+
+  // V1: item = (ar, c, xg)
+  for (int it = tid; it < arows * 3 * nx1; it += kClsThreads) {
+    const int xg = it % nx1, rc = it / nx1;
+    const int c = rc % 3, ar = rc / 3;
+    const int ym = ymin[alo + ar] - ylo;
+    int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+    for (int i = 0; i < ytaps; ++i) {
+      const int k = yk[(long)i * P + alo + ar];
+      const unsigned w = one[(clampi(ym + i, 0, rows1 - 1) * 3 + c) * nx1 + xg];
+      a0 += k * (int)(w & 255u);
+      a1 += k * (int)((w >> 8) & 255u);
+      a2 += k * (int)((w >> 16) & 255u);
+      a3 += k * (int)(w >> 24);
+    }
+    mid[(ar * 3 + c) * nx1 + xg] = fix8(a0) | (fix8(a1) << 8) | (fix8(a2) << 16) | (fix8(a3) << 24);
+  }
+  __syncthreads();                                         // and H1's rows are dead: `one` is free
+
+  // H2: item = (ar, c, xg) over the S output columns
+  const uint8_t* midb = reinterpret_cast<const uint8_t*>(mid);
+  for (int it = tid; it < arows * 3 * nx2; it += kClsThreads) {
+    const int xg = it % nx2, rc = it / nx2;
+    const uint8_t* src = midb + rc * P;
+    const int4 xm = reinterpret_cast<const int4*>(min2)[xg];
+    int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+    for (int i = 0; i < taps2; ++i) {
+      const int4 k = reinterpret_cast<const int4*>(k2 + (long)i * Sp)[xg];
+      a0 += k.x * (int)src[clampi(xm.x + i, 0, size - 1)];
+      a1 += k.y * (int)src[clampi(xm.y + i, 0, size - 1)];
+      a2 += k.z * (int)src[clampi(xm.z + i, 0, size - 1)];
+      a3 += k.w * (int)src[clampi(xm.w + i, 0, size - 1)];
+    }
+    one[rc * nx2 + xg] = fix8(a0) | (fix8(a1) << 8) | (fix8(a2) << 16) | (fix8(a3) << 24);
+  }
+  __syncthreads();
+
+  // V2: item = (r, c, xg)
+  const bool vec = (a.S & 3) == 0 && (((uintptr_t)a.out) & 15) == 0;
+  for (int it = tid; it < (r1 - r0) * 3 * nx2; it += kClsThreads) {
+    const int xg = it % nx2, rc = it / nx2;
+    const int c = rc % 3, r = r0 + rc / 3;
+    const int ym = min2[r] - alo;
+    int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+    for (int i = 0; i < taps2; ++i) {
+      const int k = k2[(long)i * Sp + r];
+      const unsigned w = one[(clampi(ym + i, 0, arows - 1) * 3 + c) * nx2 + xg];
+      a0 += k * (int)(w & 255u);
+      a1 += k * (int)((w >> 8) & 255u);
+      a2 += k * (int)((w >> 16) & 255u);
+      a3 += k * (int)(w >> 24);
+    }
+    if (U8OUT) {
+      const unsigned v[4] = {fix8(a0), fix8(a1), fix8(a2), fix8(a3)};
+      uint8_t* dst = a.out8 + ((((long)slot * a.S + r) * (long)a.S + xg * 4) * 3 + c);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (xg * 4 + j < a.S) dst[3 * j] = (uint8_t)v[j];
+      continue;
+    }
+    const float mean = a.mean[c], std = a.std[c];
+    float4 o;
+    o.x = norm1(__fdiv_rn((float)fix8(a0), 255.f), mean, std);
+    o.y = norm1(__fdiv_rn((float)fix8(a1), 255.f), mean, std);
+    o.z = norm1(__fdiv_rn((float)fix8(a2), 255.f), mean, std);
+    o.w = norm1(__fdiv_rn((float)fix8(a3), 255.f), mean, std);
+    float* dst = a.out + ((((long)clip * 3 + c) * a.T + t) * a.S + r) * (long)a.S + xg * 4;
+    if (vec) {
+      *reinterpret_cast<float4*>(dst) = o;
+    } else {
+      const float v[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (xg * 4 + j < a.S) dst[j] = v[j];
+    }
+  }
+}
+
 // ---- ColorJitter / RandomGray on uint8 frames (utils/augmentation.py:179-320, through torchvision 0.5's
 // functional on PIL: ImageEnhance.Brightness/Contrast/Color, convert('HSV') + uint8 add + convert('RGB')) ----------
 // One workgroup owns one frame and runs its group's program (up to 8 ops, device tables) on the frame's bytes in
@@ -730,6 +887,82 @@ extern "C" int coclr_resize_boxes_u8(const uint8_t* frames, int F, int H, int W,
   a.xlen = (int)xlen; a.ylen = (int)ylen;
   hipLaunchKernelGGL(resize_boxes_kernel, dim3((unsigned)bands, (unsigned)(n_clips * T)), dim3(256),
                      (size_t)cap * 3 * Sp, (hipStream_t)stream_, a);
+  COCLR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int coclr_resize2_boxes(const uint8_t* frames, int F, int H, int W, const int32_t* desc,
+                                   const int32_t* desc_host, int n_clips, int T, int size, int S, const int32_t* xtab,
+                                   int64_t xlen, const int32_t* ytab, int64_t ylen, const int32_t* tab2, int64_t len2,
+                                   int taps2, const float* mean, const float* std, uint8_t* out8, float* out,
+                                   void* stream_) {
+  if (!frames || !desc || !desc_host || !xtab || !ytab || !tab2) return COCLR_EINVAL;
+  if ((out8 == nullptr) == (out == nullptr) || (out && (!mean || !std))) return COCLR_EINVAL;     // one of the two forms
+  if (F < 1 || H < 1 || W < 1 || T < 1 || n_clips < 1 || S < 1 || size < 1) return COCLR_EINVAL;
+  if (S > kClsMaxSide || size > kClsMaxSide) return COCLR_EINVAL;
+  if ((long)W * 3 * H > 0x7fffffffL || (long)n_clips * T > 65535) return COCLR_EINVAL;
+  if ((((uintptr_t)xtab) & 15) || (((uintptr_t)ytab) & 15) || (((uintptr_t)tab2) & 15)) return COCLR_EINVAL;
+  const int P = (size + 3) & ~3, Sp = (S + 3) & ~3;
+  if (xlen < 2 * P || ylen < 2 * P || xlen > 0x7fffffffL || ylen > 0x7fffffffL) return COCLR_EINVAL;
+  if (taps2 < 1 || taps2 > 64 || len2 < (int64_t)Sp * (1 + taps2)) return COCLR_EINVAL;
+  Resize2Args a;
+  for (int c = 0; c < 3; ++c) {
+    a.mean[c] = out ? mean[c] : 0.f; a.std[c] = out ? std[c] : 1.f;      // host arrays, read at call time
+    if (a.std[c] == 0.f) return COCLR_EINVAL;
+  }
+  for (int k = 0; k < n_clips; ++k) {
+    const int32_t* d = desc_host + (long)k * CLS_FIELDS;
+    if (d[CLS_FIRST] < 0 || d[CLS_FRAMES] != T || (long)d[CLS_FIRST] + T > F) return COCLR_EINVAL;
+    if (d[CLS_X0] < 0 || d[CLS_Y0] < 0 || d[CLS_W] < 1 || d[CLS_H] < 1 || (long)d[CLS_X0] + d[CLS_W] > W ||
+        (long)d[CLS_Y0] + d[CLS_H] > H)
+      return COCLR_EINVAL;
+    if (d[CLS_CX] < 0 || d[CLS_CY] < 0 || d[CLS_OW] < 1 || d[CLS_OH] < 1 || (long)d[CLS_CX] + size > d[CLS_OW] ||
+        (long)d[CLS_CY] + size > d[CLS_OH])
+      return COCLR_EINVAL;                                               // the window leaves the resampled region
+    if (d[CLS_XTAPS] < 1 || d[CLS_XTAPS] > 64 || d[CLS_YTAPS] < 1 || d[CLS_YTAPS] > 64) return COCLR_EINVAL;
+    if (d[CLS_XOFF] < 0 || (d[CLS_XOFF] & 3) || (long)d[CLS_XOFF] + (long)P * (1 + d[CLS_XTAPS]) > xlen)
+      return COCLR_EINVAL;
+    if (d[CLS_YOFF] < 0 || (d[CLS_YOFF] & 3) || (long)d[CLS_YOFF] + (long)P * (1 + d[CLS_YTAPS]) > ylen)
+      return COCLR_EINVAL;
+  }
+  // Band height: the most output rows whose three LDS images fit.  Both row tables are non-decreasing and advance by
+  // at most n_in / n_out (+1 from truncation) per row: a band of R output rows spans at most floor((R-1) size / S) +
+  // taps2 + 2 rows of the size x size image, and capA of those at most floor((capA-1) h / oh) + ytaps + 2 source rows
+  // of a clip; the kernel clamps to both caps whatever the tables say.  Up to 80 KiB two workgroups share a CU; a
+  // single output row may take the whole 160 KiB.
+  int R = 32, cap1 = 0, capA = 0;
+  long bytes = 0;
+  for (;; R >>= 1) {
+    capA = (int)(((long)(R - 1) * size) / S) + taps2 + 2;
+    if (capA > size) capA = size;
+    cap1 = 1;
+    for (int k = 0; k < n_clips; ++k) {
+      const int32_t* d = desc_host + (long)k * CLS_FIELDS;
+      long c1 = ((long)(capA - 1) * d[CLS_H]) / d[CLS_OH] + d[CLS_YTAPS] + 2;
+      if (c1 > d[CLS_H]) c1 = d[CLS_H];
+      if (c1 > cap1) cap1 = (int)c1;
+    }
+    const long one = (long)cap1 * 3 * P > (long)capA * 3 * Sp ? (long)cap1 * 3 * P : (long)capA * 3 * Sp;
+    bytes = one + (long)capA * 3 * P;
+    if (bytes <= (R > 1 ? kClsLdsTwo : kClsLdsMax)) break;
+    if (R == 1) return COCLR_EINVAL;                   // one output row's halo does not fit the CU's LDS
+  }
+  const long bands = (S + R - 1) / R;
+  if (bands * n_clips * T * kClsThreads >= (1L << 32)) return COCLR_EINVAL;
+  a.frames = frames; a.desc = desc; a.xtab = xtab; a.ytab = ytab; a.tab2 = tab2; a.out8 = out8; a.out = out;
+  a.F = F; a.H = H; a.W = W; a.T = T; a.size = size; a.P = P; a.S = S; a.Sp = Sp; a.taps2 = taps2; a.R = R;
+  a.cap1 = cap1; a.capA = capA; a.xlen = (int)xlen; a.ylen = (int)ylen;
+  static std::atomic<uint64_t> attr_u8{0}, attr_f32{0};
+  const dim3 grid((unsigned)bands, (unsigned)(n_clips * T));
+  if (out8) {
+    if (bytes > 65536)
+      COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(resize2_boxes_kernel<true>), kClsLdsMax, attr_u8));
+    hipLaunchKernelGGL(resize2_boxes_kernel<true>, grid, dim3(kClsThreads), (size_t)bytes, (hipStream_t)stream_, a);
+  } else {
+    if (bytes > 65536)
+      COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(resize2_boxes_kernel<false>), kClsLdsMax, attr_f32));
+    hipLaunchKernelGGL(resize2_boxes_kernel<false>, grid, dim3(kClsThreads), (size_t)bytes, (hipStream_t)stream_, a);
+  }
   COCLR_LAUNCH_CHECK();
   return 0;
 }

@@ -1093,6 +1093,41 @@ def resize_boxes_u8(frames, desc, desc_host, xtab, ytab, T, S, out):
         "resize_boxes_u8")
 
 
+def resize2_boxes(frames, desc, desc_host, xtab, ytab, tab2, T, size, S, out, mean=None, std=None):
+    """The classifier's crop chain in one launch (include/coclr_hip.h: coclr_resize2_boxes): frames (F, H, W, 3) uint8;
+    desc int32 (n_clips, 14) on the device and desc_host, the same on the host; xtab / ytab the clips' stage-1 tables
+    one after the other, tab2 (1 + taps2, Sp) the shared size -> S table, all int32 on the device.  `out` uint8
+    (n_clips*T, S, S, 3) takes the resized bytes; `out` fp32 (n_clips, 3, T, S, S) takes them normalised with
+    `mean` / `std`."""
+    if frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise ValueError("coclr_amd: frames must be contiguous (F, H, W, 3), got %s" % (tuple(frames.shape),))
+    F, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
+    if desc.dim() != 2 or desc.shape[1] != 14 or desc.shape != desc_host.shape or desc_host.is_cuda or \
+            desc_host.dtype != torch.int32 or not desc.is_contiguous() or not desc_host.is_contiguous():
+        raise ValueError("coclr_amd: clip descriptors must be contiguous int32 (n_clips, 14), device and host")
+    n_clips, T, size, S = desc.shape[0], int(T), int(size), int(S)
+    Sp = (S + 3) & ~3
+    if xtab.dim() != 1 or ytab.dim() != 1 or not xtab.is_contiguous() or not ytab.is_contiguous():
+        raise ValueError("coclr_amd: resize2_boxes needs flat contiguous stage-1 table buffers")
+    if tab2.dim() != 2 or tab2.shape[0] < 2 or tab2.shape[1] != Sp or not tab2.is_contiguous():
+        raise ValueError("coclr_amd: the stage-2 table must be contiguous (1 + taps, %d), got %s" % (Sp, tuple(tab2.shape)))
+    i32 = torch.int32
+    if out.dtype == torch.uint8:
+        want, o8, of, m, s = (n_clips * T, S, S, 3), _p(out, torch.uint8), None, None, None
+    else:
+        if mean is None or std is None:
+            raise ValueError("coclr_amd: the fp32 form of resize2_boxes needs mean and std")
+        want, o8, of = (n_clips, 3, T, S, S), None, _p(out)
+        m = (C.c_float * 3)(*[float(v) for v in mean])
+        s = (C.c_float * 3)(*[float(v) for v in std])
+    if tuple(out.shape) != want or not out.is_contiguous():
+        raise ValueError("coclr_amd: out must be contiguous %s, got %s" % (want, tuple(out.shape)))
+    _lib.check(_L().coclr_resize2_boxes(
+        _p(frames, torch.uint8), F, H, W, _p(desc, i32), C.cast(desc_host.data_ptr(), C.POINTER(C.c_int32)), n_clips,
+        T, size, S, _p(xtab, i32), xtab.numel(), _p(ytab, i32), ytab.numel(), _p(tab2, i32), tab2.numel(),
+        tab2.shape[0] - 1, m, s, o8, of, _stream()), "resize2_boxes")
+
+
 def _program_call(name, frames, kinds, params, group_size, T, mean, std, out, host_tables):
     if frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
         raise ValueError("coclr_amd: frames must be contiguous (N, H, W, 3), got %s" % (tuple(frames.shape),))

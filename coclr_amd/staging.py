@@ -23,9 +23,13 @@ the reference does and hands the kernel one small program per group of frames (`
 The training transform (main_nce.py:366-392) is `TrainTransform` + `stage_train_clips` at the end of this file: the
 reference's draws on the host, then every clip's RandomSizedCrop box and its ColorJitter / RandomGray / GaussianBlur
 / RandomHorizontalFlip program in two launches, bit-identical to the reference's classes.
+The classifier's transform (eval/main_classifier.py:729-744) is `ClassifierTransform` + `stage_classifier_clips`: the
+draws of RandomSizedCrop(consistent=True) with its ten attempts and its Scale + CenterCrop fallback, then both bicubic
+resizes (to 224, then to img_dim) in ONE launch, the clip's ColorJitter and the loop's batch flip in a second.
 """
 import math
 import numbers
+import os
 import random
 
 import numpy as np
@@ -526,7 +530,7 @@ class TrainTransform:
                  blur_sigma=(0.1, 2.0), p_blur=0.5, p_flip=0.5, p_base=0.3, weights=(0.5, 0.5), consistent=False, p=1.0):
         if consistent:
             raise ValueError("coclr_amd: RandomSizedCrop(consistent=True) retries and falls back to another resample; "
-                             "the training scripts never use it")
+                             "the training scripts never use it (the classifier script does: ClassifierTransform)")
         if p != 1.0:
             raise ValueError("coclr_amd: RandomSizedCrop(p != 1.0) centre-crops without a resize; the training "
                              "scripts never use it")
@@ -758,4 +762,271 @@ def stage_train_clips(frames_u8, plans, out_size, mean=IMAGENET_MEAN, std=IMAGEN
     ops.resize_boxes_u8(frames, desc.to(device), desc, xtab.to(device), ytab.to(device), T, S, u8)
     ops.augment_clips(u8, kinds.to(device), params.to(device), group_size, T, mean, std,
                       out.view(B * 2, 3, T, S, S), host_tables=(kinds, params))
+    return out
+
+
+# ---- the classifier's transform (eval/main_classifier.py:729-744,216-220; utils/augmentation.py:21-58,90-146) --------
+
+CLS_MAX_SIDE = 224                      # size and img_dim: what coclr_resize2_boxes and coclr_augment_clips take
+CLS_MAX_TAPS = 64
+CLS_PLAN_LEN = 9 + 2 * JITTER_MAX_OPS   # packed plan: form, region (4), resample (2), window (2), 8 kinds, 8 parameters
+CLS_FORMS = ("box", "fallback")
+
+
+def cls_fused():
+    """COCLR_CLS_FUSED (default 1, read per call; PROVISIONAL: tools/cls_stage_step.py has measured one geometry,
+    DESIGN.md 4.5e): stage_classifier_clips resamples twice in ONE launch (coclr_resize2_boxes); with 0 it chains two
+    coclr_resize_boxes_u8 launches through a byte buffer, which cannot express the fallback form."""
+    return os.environ.get("COCLR_CLS_FUSED", "1") != "0"
+
+
+def draw_batch_flip(rng=random):
+    """The ONE draw of T.RandomHorizontalFlip() the fine-tuning loop makes per batch, in the main process
+    (utils/transforms.py:286-293): `flip=` of stage_classifier_clips."""
+    return rng.random() < 0.5
+
+
+def fallback_geometry(W, H, size):
+    """RandomSizedCrop's fallback, Scale(size) then CenterCrop(size) (utils/augmentation.py:21-58,140-143), on a W x H
+    frame: ((ow, oh), (cx, cy)) -- what the whole frame is resampled to (itself when its shorter side already is
+    `size`) and where the size x size window starts, with Python's round-half-to-even."""
+    W, H, size = int(W), int(H), int(size)
+    if (W <= H and W == size) or (H <= W and H == size):
+        ow, oh = W, H
+    elif W < H:
+        ow, oh = size, int(size * H / W)
+    else:
+        ow, oh = int(size * W / H), size
+    return (ow, oh), (int(round((ow - size) / 2.)), int(round((oh - size) / 2.)))
+
+
+class ClassifierTransform:
+    """The transform of the fine-tuning / linear-probe loop (eval/main_classifier.py:729-744) as a source of PLANS:
+    RandomSizedCrop(size, consistent=True, bottom_area) -> Scale(img_dim) -> ColorJitter(*jitter, p=p_jitter,
+    consistent=True) (mode "train" only; "val" crops at random too, as the reference does).  `draw` consumes the
+    generator exactly as `transform(seq)` does; stage_classifier_clips does the work on the GPU.  A plan is a dict
+        form      "box" (an attempt fitted) or "fallback" (ten did not: Scale(size) + CenterCrop(size))
+        region    (x0, y0, w, h) of the frame that is resampled: the drawn box, or the whole frame
+        resample  (ow, oh) the region is resampled to: (size, size), or Scale's size of the whole frame
+        window    (cx, cy) where the size x size window of that starts: (0, 0), or CenterCrop's corner
+        program   ColorJitter's ops [(kind, parameter)] in their shuffled order, one program for the whole clip."""
+
+    def __init__(self, img_dim, seq_len, size=224, bottom_area=0.2, jitter=(0.4, 0.4, 0.4, 0.1), p_jitter=0.3,
+                 mode="train"):
+        self.img_dim, self.seq_len, self.size = int(img_dim), int(seq_len), int(size)
+        if self.img_dim < 1 or self.seq_len < 1 or self.size < 1:
+            raise ValueError("coclr_amd: img_dim, seq_len and size must be >= 1")
+        if self.img_dim > CLS_MAX_SIDE or self.size > CLS_MAX_SIDE:
+            raise ValueError("coclr_amd: the classifier staging takes img_dim and size up to %d, got %d and %d" %
+                             (CLS_MAX_SIDE, self.img_dim, self.size))
+        if mode not in ("train", "val"):
+            raise ValueError("coclr_amd: mode is 'train' or 'val', got %r" % (mode,))
+        self.mode, self.bottom_area = mode, bottom_area
+        self.jitter = ColorJitter(*jitter, p=p_jitter)
+
+    def draw(self, W, H, rng=random):
+        """The plan of one sample of seq_len frames of W x H."""
+        W, H = int(W), int(H)
+        if W < 1 or H < 1:
+            raise ValueError("coclr_amd: frames of %d x %d" % (W, H))
+        rng.random()                                            # `random.random() < p`, p = 1.0
+        plan = None
+        for _ in range(10):
+            target_area = rng.uniform(self.bottom_area, 1) * (W * H)
+            aspect_ratio = rng.uniform(3. / 4, 4. / 3)
+            w = int(round(math.sqrt(target_area * aspect_ratio)))
+            h = int(round(math.sqrt(target_area / aspect_ratio)))
+            if rng.random() < 0.5:
+                w, h = h, w
+            if w <= W and h <= H:
+                if w < 1 or h < 1:
+                    raise ValueError("coclr_amd: RandomSizedCrop drew an empty %d x %d box" % (w, h))
+                x1 = rng.randint(0, W - w)
+                y1 = rng.randint(0, H - h)
+                plan = {"form": "box", "region": (x1, y1, w, h), "resample": (self.size, self.size), "window": (0, 0)}
+                break
+        if plan is None:                                        # the fallback draws nothing
+            resample, window = fallback_geometry(W, H, self.size)
+            plan = {"form": "fallback", "region": (0, 0, W, H), "resample": resample, "window": window}
+        plan["program"] = self.jitter.draw(rng, 1)[0] if self.mode == "train" else []
+        return plan
+
+
+def pack_cls_plan(plan):
+    """A plan of ClassifierTransform.draw as ONE tensor of fixed shape, float64 (25,): form (0 box, 1 fallback), region,
+    resample, window, then 8 op kinds and 8 parameters (doubles hold all of them exactly).  What a dataset returns
+    beside its frames: the default collate stacks it, and stage_classifier_clips takes the stacked (B, 25) tensor."""
+    if plan["form"] not in CLS_FORMS:
+        raise ValueError("coclr_amd: a plan's form is one of %r, got %r" % (CLS_FORMS, plan["form"]))
+    prog = list(plan["program"])
+    if len(prog) > JITTER_MAX_OPS:
+        raise ValueError("coclr_amd: a program has %d ops, the kernel takes %d" % (len(prog), JITTER_MAX_OPS))
+    head = [CLS_FORMS.index(plan["form"])] + list(plan["region"]) + list(plan["resample"]) + list(plan["window"])
+    if len(head) != 9:
+        raise ValueError("coclr_amd: a plan has a region of 4, a resample of 2 and a window of 2 numbers")
+    t = torch.zeros(CLS_PLAN_LEN, dtype=torch.float64)
+    t[:9] = torch.tensor([float(v) for v in head], dtype=torch.float64)
+    for j, (kind, value) in enumerate(prog):
+        t[9 + j], t[9 + JITTER_MAX_OPS + j] = kind, value
+    return t
+
+
+def unpack_cls_plan(packed):
+    """The plan pack_cls_plan packed (no-ops dropped)."""
+    if packed.dim() != 1 or packed.shape[0] != CLS_PLAN_LEN:
+        raise ValueError("coclr_amd: a packed classifier plan is (%d,), got %s" % (CLS_PLAN_LEN, tuple(packed.shape)))
+    v = packed.detach().cpu().to(torch.float64).tolist()
+    if any(x != int(x) for x in v[:9]) or int(v[0]) not in (0, 1):
+        raise ValueError("coclr_amd: a packed plan's form and geometry are integers, got %r" % (v[:9],))
+    head = [int(x) for x in v[:9]]
+    kinds, params = v[9:9 + JITTER_MAX_OPS], v[9 + JITTER_MAX_OPS:]
+    return {"form": CLS_FORMS[head[0]], "region": tuple(head[1:5]), "resample": tuple(head[5:7]),
+            "window": tuple(head[7:9]),
+            "program": [(int(k) if k == int(k) else k, p) for k, p in zip(kinds, params) if k != 0]}
+
+
+def check_cls_plans(plans, B, W, H, size):
+    """`plans` (a list of B plans, or the stacked packed tensor) -> (per clip (x0, y0, w, h, ow, oh, cx, cy), per clip
+    program), refused here, on the host, when a plan is not one the kernel takes."""
+    if torch.is_tensor(plans):
+        if plans.dim() == 1:
+            plans = plans[None]
+        plans = [unpack_cls_plan(p) for p in plans]
+    plans = list(plans)
+    if len(plans) != B:
+        raise ValueError("coclr_amd: %d plans for %d samples" % (len(plans), B))
+    rows, programs = [], []
+    for plan in plans:
+        if plan["form"] not in CLS_FORMS:
+            raise ValueError("coclr_amd: a plan's form is one of %r, got %r" % (CLS_FORMS, plan["form"]))
+        geo = tuple(plan["region"]) + tuple(plan["resample"]) + tuple(plan["window"])
+        if len(geo) != 8 or any(isinstance(v, bool) or int(v) != v for v in geo):
+            raise ValueError("coclr_amd: a plan's region, resample and window are 4 + 2 + 2 integers, got %r" % (geo,))
+        x0, y0, w, h, ow, oh, cx, cy = (int(v) for v in geo)
+        if x0 < 0 or y0 < 0 or w < 1 or h < 1 or x0 + w > W or y0 + h > H:
+            raise ValueError("coclr_amd: region (%d, %d, %d, %d) leaves the %d x %d frame" % (x0, y0, w, h, W, H))
+        if cx < 0 or cy < 0 or cx + size > ow or cy + size > oh:
+            raise ValueError("coclr_amd: a %d x %d window at (%d, %d) leaves the %d x %d resample" %
+                             (size, size, cx, cy, ow, oh))
+        if plan["form"] == "box" and (ow, oh, cx, cy) != (size, size, 0, 0):
+            raise ValueError("coclr_amd: a box plan resamples to (%d, %d) and keeps all of it, got %r" %
+                             (size, size, (ow, oh, cx, cy)))
+        rows.append((x0, y0, w, h, ow, oh, cx, cy))
+        programs.append([tuple(op) for op in plan["program"]])
+    program_tables([list(p) for p in {tuple(p) for p in programs}])            # refuses a bad op
+    return rows, programs
+
+
+_WIN_TABLES = {}        # (n_in, n_out, c0, size) -> int32 (1 + taps, P): min then k of columns c0 .. c0 + size - 1
+
+
+def _window_table(n_in, n_out, c0, size):
+    key = (n_in, n_out, c0, size)
+    if key not in _WIN_TABLES:
+        P = (size + 3) & ~3
+        lo, K = resample_tables(n_in, n_out)
+        if K.shape[1] > CLS_MAX_TAPS:
+            raise ValueError("coclr_amd: a side of %d to %d needs %d taps, the kernel takes %d" %
+                             (n_in, n_out, K.shape[1], CLS_MAX_TAPS))
+        t = np.zeros((1 + K.shape[1], P), dtype=np.int32)
+        t[0, :size] = lo[c0:c0 + size]
+        t[1:, :size] = K[c0:c0 + size].T
+        _WIN_TABLES[key] = t
+    return _WIN_TABLES[key]
+
+
+def classifier_tables(plans, B, T, W, H, img_dim, size=224, flip=False):
+    """The host side of stage_classifier_clips for B samples of T frames of W x H: checks the plans and returns
+    (desc int32 (B, 14), xtab, ytab int32, tab2 int32 (1 + taps, Sp), kinds int32 (B, P), params fp32 (B, P), direct)
+    as the entry points take them, all on the host; `direct` says that no clip has a program and `flip` is off, so
+    that one launch writes fp32.  May be computed ahead (stage_classifier_clips(tables=))."""
+    B, T, S, size = int(B), int(T), int(img_dim), int(size)
+    if S < 1 or size < 1 or S > CLS_MAX_SIDE or size > CLS_MAX_SIDE:
+        raise ValueError("coclr_amd: the classifier staging takes img_dim and size of 1..%d, got %d and %d" %
+                         (CLS_MAX_SIDE, S, size))
+    rows, programs = check_cls_plans(plans, B, W, H, size)
+    tab2 = _window_table(size, S, 0, S)                  # size -> S whole: PIL's identity when they are equal
+    bufs, at, fill, full = ([], []), ({}, {}), [0, 0], []
+    for b, (x0, y0, w, h, ow, oh, cx, cy) in enumerate(rows):
+        offs = []
+        for axis, key in ((0, (w, ow, cx)), (1, (h, oh, cy))):
+            if key not in at[axis]:
+                t = _window_table(key[0], key[1], key[2], size)
+                at[axis][key] = (fill[axis], t.shape[0] - 1)
+                bufs[axis].append(t.reshape(-1))
+                fill[axis] += t.size
+            offs.append(at[axis][key])
+        full.append([b * T, T, x0, y0, w, h, ow, oh, cx, cy, offs[0][0], offs[1][0], offs[0][1], offs[1][1]])
+    tail = [(AUGMENT_FLIP, 0.0)] if flip else []
+    kinds, params = augment_tables([list(p) + tail for p in programs])
+    direct = not flip and not any(programs)
+    return (torch.tensor(full, dtype=torch.int32), torch.from_numpy(np.concatenate(bufs[0])),
+            torch.from_numpy(np.concatenate(bufs[1])), torch.from_numpy(tab2), kinds, params, direct)
+
+
+def stage_classifier_clips(frames_u8, plans, img_dim, flip=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None,
+                           device=None, tables=None, size=224):
+    """Raw frames + the reference's draws -> the classifier's input: per clip `resample the plan's region -> keep the
+    size x size window (RandomSizedCrop(size, consistent=True), box or fallback) -> Image.resize to img_dim (Scale) ->
+    ColorJitter -> ToTensor -> RandomHorizontalFlip -> Normalize`, bit-identical to the reference's classes.
+    frames_u8: (B, T, H, W, 3) or (T, H, W, 3) uint8, on the host (uploaded once, as bytes) or the device.
+    plans: B plans of ClassifierTransform.draw, or their pack_cls_plan tensors stacked (B, 25).
+    flip: draw_batch_flip(), the loop's one draw per batch; kind 7 is appended to every clip's program.
+    Returns (B, 3, T, S, S) fp32 on the device: what `model(input_seq)` takes after the script's `tr()`.
+    TWO launches (coclr_resize2_boxes to bytes, then coclr_augment_clips with one program per clip), or ONE
+    (coclr_resize2_boxes writing fp32) when no clip has a program and `flip` is off -- validation, or a training batch
+    whose jitter draws all said no.  COCLR_CLS_FUSED=0 chains two coclr_resize_boxes_u8 launches instead of
+    coclr_resize2_boxes (box plans only).  A bad plan is refused here before anything is launched.
+    `tables`: classifier_tables(plans, ..., flip=flip) computed ahead; `plans` and `flip` are then not read."""
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() not in (4, 5) or frames_u8.shape[-1] != 3:
+        raise ValueError("coclr_amd: frames must be uint8 (B, T, H, W, 3) or (T, H, W, 3), got %s %s" %
+                         (frames_u8.dtype, tuple(frames_u8.shape)))
+    if frames_u8.dim() == 4:
+        frames_u8 = frames_u8[None]
+        if isinstance(plans, dict):
+            plans = [plans]
+    B, T, H, W = frames_u8.shape[:4]
+    S, size = int(img_dim), int(size)
+    if B < 1 or T < 1 or H < 1 or W < 1:
+        raise ValueError("coclr_amd: a sample is T frames, got %s" % (tuple(frames_u8.shape),))
+    if S < 1 or size < 1 or S > CLS_MAX_SIDE or size > CLS_MAX_SIDE:
+        raise ValueError("coclr_amd: stage_classifier_clips takes img_dim and size of 1..%d, got %d and %d" %
+                         (CLS_MAX_SIDE, S, size))
+    if tables is None:
+        tables = classifier_tables(plans, B, T, W, H, S, size, flip)
+    desc, xtab, ytab, tab2, kinds, params, direct = tables
+    if tuple(desc.shape) != (B, 14) or tuple(kinds.shape[:1]) != (B,) or tab2.shape[1] != (S + 3) & ~3:
+        raise ValueError("coclr_amd: tables for %d clips to %d, frames for %d to %d" %
+                         (desc.shape[0], tab2.shape[1], B, S))
+    if out is not None and (tuple(out.shape) != (B, 3, T, S, S) or not out.is_contiguous() or
+                            out.dtype != torch.float32):
+        raise ValueError("coclr_amd: out must be contiguous fp32 %s, got %s" % ((B, 3, T, S, S), tuple(out.shape)))
+    fused = cls_fused()
+    if not fused and bool((desc[:, 6:10] != torch.tensor([size, size, 0, 0], dtype=torch.int32)).any()):
+        raise ValueError("coclr_amd: COCLR_CLS_FUSED=0 chains two box resizes and cannot express the fallback form "
+                         "(a window of a whole-frame resample)")
+    if device is None:
+        device = frames_u8.device if frames_u8.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    frames = frames_u8.contiguous().to(device).view(B * T, H, W, 3)
+    if out is None:
+        out = torch.empty(B, 3, T, S, S, dtype=torch.float32, device=device)
+    if fused and direct:
+        ops.resize2_boxes(frames, desc.to(device), desc, xtab.to(device), ytab.to(device), tab2.to(device), T, size,
+                          S, out, mean, std)
+        return out
+    u8 = torch.empty(B * T, S, S, 3, dtype=torch.uint8, device=device)
+    if fused:
+        ops.resize2_boxes(frames, desc.to(device), desc, xtab.to(device), ytab.to(device), tab2.to(device), T, size,
+                          S, u8)
+    else:
+        # the same bytes from the entry points of the training staging: box -> size, then the whole of that -> S
+        d1 = desc[:, [0, 1, 2, 3, 4, 5, 10, 11, 12, 13]].contiguous()
+        taps2 = tab2.shape[0] - 1
+        d2 = torch.tensor([[b * T, T, 0, 0, size, size, 0, 0, taps2, taps2] for b in range(B)], dtype=torch.int32)
+        mid = torch.empty(B * T, size, size, 3, dtype=torch.uint8, device=device)
+        flat2 = tab2.reshape(-1).to(device)
+        ops.resize_boxes_u8(frames, d1.to(device), d1, xtab.to(device), ytab.to(device), T, size, mid)
+        ops.resize_boxes_u8(mid, d2.to(device), d2, flat2, flat2, T, S, u8)
+    ops.augment_clips(u8, kinds.to(device), params.to(device), T, T, mean, std, out, host_tables=(kinds, params))
     return out

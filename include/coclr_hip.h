@@ -681,6 +681,35 @@ int coclr_resize_boxes_u8(const uint8_t* frames, int F, int H, int W, const int3
                           const int32_t* desc_host, int n_clips, int T, int S, const int32_t* xtab, int64_t xlen,
                           const int32_t* ytab, int64_t ylen, uint8_t* out, void* stream);
 
+/* The crop chain of the classifier's fine-tuning / linear-probe loop in one launch (eval/main_classifier.py:729-744:
+ * A.RandomSizedCrop(size=224, consistent=True, bottom_area=0.2) then A.Scale(args.img_dim); utils/augmentation.py:
+ * 21-58 Scale and CenterCrop, 90-146 RandomSizedCrop with its ten attempts and its Scale + CenterCrop fallback): per
+ * output clip k and t < T, resample the w x h region at (x0, y0) of frame first + t to (ow, oh) with
+ * Image.resize(BICUBIC) on 8-bit pixels, keep the size x size window at (cx, cy) of that, and Image.resize it to
+ * S x S -- four 8-bit passes, each rounded and clamped on its own, the size x size image in LDS only.
+ * A drawn box is ow = oh = size, cx = cy = 0; the fallback is the whole frame with Scale's (ow, oh) and
+ * CenterCrop's window.
+ * desc: int32 [n_clips][14], DEVICE: {first frame, frames (= T), x0, y0, w, h, ow, oh, cx, cy, x-table offset,
+ *   y-table offset, xtaps, ytaps}; desc_host: the same on the HOST, read at call time and validated (the kernel
+ *   reads the device copy and stays in bounds whatever that holds).
+ * xtab / ytab: int32 device buffers of xlen / ylen elements, 16-byte aligned, the clips' stage-1 tables one after
+ *   the other: at a clip's offset (a multiple of 4) min[P] then k[taps][P], P = size rounded up to a multiple of 4,
+ *   holding columns cx .. cx+size-1 of the w -> ow tables (rows cy .. of the h -> oh tables).  Clips may share.
+ * tab2: int32 device buffer of len2 elements, 16-byte aligned: min[Sp] then k[taps2][Sp] of size -> S, used on
+ *   both axes of every clip (Sp = S rounded up to a multiple of 4).  size == S makes it PIL's identity.
+ * Exactly one output: out8 uint8 [n_clips*T][S][S][3] (the input of coclr_augment_clips), or out fp32
+ *   [n_clips][3][T][S][S] = (byte / 255 - mean[c]) / std[c] with mean / std host arrays of 3, as coclr_stage_crops.
+ * COCLR_EINVAL before any launch: a null or misaligned pointer, both or neither output, out without mean / std or
+ * with a zero std; F, H, W, T, n_clips, S, size < 1; S or size > 224; a descriptor whose frames != T, whose
+ * frames leave [0, F), whose region leaves the frame, whose window leaves (ow, oh), whose taps are outside 1..64 or
+ * whose tables leave their buffer; taps2 outside 1..64 or len2 < Sp (1 + taps2); n_clips*T > 65535; one output
+ * row whose halo of intermediate and source rows exceeds the CU's LDS.
+ * Additive: the ABI number stays 25 -- no existing signature or behaviour changed. */
+int coclr_resize2_boxes(const uint8_t* frames, int F, int H, int W, const int32_t* desc, const int32_t* desc_host,
+                        int n_clips, int T, int size, int S, const int32_t* xtab, int64_t xlen, const int32_t* ytab,
+                        int64_t ylen, const int32_t* tab2, int64_t len2, int taps2, const float* mean,
+                        const float* std, uint8_t* out8, float* out, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* Evaluation consumers (model/classifier.py:47-61; eval/main_classifier.py) */
 /* ------------------------------------------------------------------------ */
