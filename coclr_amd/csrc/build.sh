@@ -6,9 +6,9 @@ OUT=../libcoclr_hip.so
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result"
 mkdir -p build
 pids=()
-for f in conv_igemm conv_wgrad bn pool nce optim loss staging retrieval version; do
+for f in conv_igemm conv_wgrad bn pool nce optim loss staging jpeg retrieval version; do
   if [ ! -f build/$f.o ] || [ $f.hip -nt build/$f.o ] || [ common.h -nt build/$f.o ] || \
-     [ conv_geom.h -nt build/$f.o ] || [ ../../include/coclr_hip.h -nt build/$f.o ]; then
+     [ conv_geom.h -nt build/$f.o ] || [ jpeg_core.h -nt build/$f.o ] || [ ../../include/coclr_hip.h -nt build/$f.o ]; then
     # optim / staging reproduce ATen's separately rounded elementwise arithmetic bit for bit: no
     # fused multiply-add contraction there (HIP's default is -ffp-contract=fast, which the backend
     # applies to packed fp32 operations even under `#pragma clang fp contract(off)`)

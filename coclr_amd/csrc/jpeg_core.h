@@ -1,0 +1,309 @@
+// Baseline JPEG decoding, the per-symbol and per-block arithmetic (include/coclr_hip.h: coclr_jpeg_decode).
+// Everything here is `__host__ __device__` and integer only, so the SAME code runs in the gfx950 kernels of
+// jpeg.hip and in a g++ build under sanitizers (tools/jpeg_core_check.cpp).  It reproduces libjpeg(-turbo)'s
+// default decoder bit for bit: Huffman decoding with zero padding past the data, the "islow" inverse DCT with
+// its range table, "fancy" h2v1 / h2v2 chroma upsampling and the 16-bit fixed-point YCbCr -> RGB conversion.
+//
+// Arithmetic that a corrupt stream can push past 32 bits is done in uint32_t (it wraps, it is never undefined);
+// for a stream an encoder wrote, no intermediate leaves the int32 range and the result is libjpeg's.
+#pragma once
+#include <stdint.h>
+
+#ifndef __HIPCC__
+#define __host__
+#define __device__
+#endif
+#define JC_HD __host__ __device__ inline
+
+// ---- per-frame descriptor: int32 words, written by coclr_amd/jpeg.py: pack ---------------------------------------
+enum {
+  JM_OFF = 0,              // first entropy-coded byte of the frame in the shared byte buffer
+  JM_LEN = 1,              // entropy-coded bytes (up to, not including, the marker that ends the scan)
+  JM_RI = 2,               // restart interval in MCUs, 0 = none
+  JM_NSEG = 3,             // restart segments (1 without restart markers)
+  JM_QUANT = 16,           // [3][64] quantiser of component c in natural (row-major) order
+  JM_HUFF = JM_QUANT + 192,  // 6 tables of JM_HUFF_WORDS: DC of component 0..2, then AC of component 0..2
+  JM_HUFF_WORDS = 96,      //   limit[16], valoff[16], huffval[256] as 64 little-endian words
+  JM_SEG = JM_HUFF + 6 * JM_HUFF_WORDS,   // [nseg] first byte of every restart segment, relative to JM_OFF
+};
+// A code of length l+1 is recognised by peek16 < limit[l] (limit = (last code of that length + 1) << (15 - l),
+// non-decreasing in l); its value is huffval[(valoff[l] + (peek16 >> (15 - l))) & 255].
+
+enum { JC_BAD_CODE = 1, JC_BAD_RUN = 2 };   // per-frame status bits
+
+struct jc_geom {
+  int H, W, ncomp, hs, vs;     // luma sampling (hs, vs) in {(1,1), (2,1), (2,2)}; chroma is 1x1
+  int mcux, mcuy, mcu_blocks;  // MCUs per row / column, blocks per MCU
+  int bw[3], bh[3];            // blocks per row / column of every component plane (whole MCUs)
+  int boff[3];                 // first block of every component in the frame's coefficient / sample storage
+  int nblocks;                 // blocks per frame
+  int dw, dh;                  // real size of a chroma plane: ceil(W / hs), ceil(H / vs)
+};
+
+JC_HD void jc_geom_init(jc_geom& g, int H, int W, int ncomp, int hs, int vs) {
+  g.H = H; g.W = W; g.ncomp = ncomp; g.hs = hs; g.vs = vs;
+  g.mcux = (W + 8 * hs - 1) / (8 * hs);
+  g.mcuy = (H + 8 * vs - 1) / (8 * vs);
+  g.mcu_blocks = ncomp == 1 ? 1 : hs * vs + 2;
+  g.nblocks = 0;
+  for (int c = 0; c < 3; ++c) {
+    g.bw[c] = c < ncomp ? g.mcux * (c == 0 ? hs : 1) : 0;
+    g.bh[c] = c < ncomp ? g.mcuy * (c == 0 ? vs : 1) : 0;
+    g.boff[c] = g.nblocks;
+    g.nblocks += g.bw[c] * g.bh[c];
+  }
+  g.dw = (W + hs - 1) / hs;
+  g.dh = (H + vs - 1) / vs;
+}
+
+// ---- bit reader: undoes FF 00 stuffing, stops at a marker or at `end`, yields zero bits from there on ----------------
+struct jc_bits {
+  const uint8_t* p;
+  int pos, end;
+  uint64_t buf;      // the next `n` bits, left aligned
+  int n;
+  int stopped;
+};
+
+JC_HD void jc_bits_init(jc_bits& b, const uint8_t* p, int start, int end) {
+  b.p = p; b.pos = start; b.end = end; b.buf = 0; b.n = 0; b.stopped = 0;
+}
+
+// afterwards at least 57 bits are buffered: one Huffman code (<= 16) and its extra bits (<= 15) need one call
+JC_HD void jc_fill(jc_bits& b) {
+  while (b.n <= 56) {
+    uint32_t c = 0;
+    if (!b.stopped && b.pos < b.end) {
+      c = b.p[b.pos++];
+      if (c == 0xFF) {
+        if (b.pos < b.end && b.p[b.pos] == 0) {
+          b.pos++;
+        } else {
+          b.stopped = 1;
+          c = 0;
+        }
+      }
+    }
+    b.buf |= (uint64_t)c << (56 - b.n);
+    b.n += 8;
+  }
+}
+
+JC_HD uint32_t jc_take(jc_bits& b, int k) {      // 1 <= k <= 16
+  const uint32_t v = (uint32_t)(b.buf >> (64 - k));
+  b.buf <<= k;
+  b.n -= k;
+  return v;
+}
+
+JC_HD int jc_huff(const int32_t* tab, jc_bits& b, int* status) {
+  const uint32_t v = (uint32_t)(b.buf >> 48);
+  int l = 0;
+  while (l < 16 && v >= (uint32_t)tab[l]) ++l;
+  if (l == 16) {                         // no such code: flagged, decoded as 0
+    *status |= JC_BAD_CODE;
+    jc_take(b, 16);
+    return 0;
+  }
+  const uint32_t idx = ((uint32_t)tab[16 + l] + (v >> (15 - l))) & 255u;
+  jc_take(b, l + 1);
+  return (int)(((uint32_t)tab[32 + (idx >> 2)] >> ((idx & 3u) * 8u)) & 255u);
+}
+
+JC_HD int jc_extend(jc_bits& b, int t) {           // 1 <= t <= 15
+  const int v = (int)jc_take(b, t);
+  return v >= (1 << (t - 1)) ? v : v - (1 << t) + 1;
+}
+
+JC_HD int jc_zigzag(int k) {                       // zigzag position -> natural (row-major) position
+  const uint8_t zz[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                          41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                          30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+  return zz[k & 63];
+}
+
+// MCUs m0 .. m1-1 of one frame (one restart segment, or the whole scan): bytes [start, end) of `data` ->
+// dequantised coefficients, 64 per block in natural order, at coef[(boff[c] + by * bw[c] + bx) * 64].  `coef` is
+// zero-filled by the caller.  One symbol per iteration; the iteration count is bounded by the block count, every
+// read stays in [start, end) and every store inside a block of this segment, whatever the bytes and tables hold.
+// Returns the status bits.
+JC_HD int jc_decode_segment(const uint8_t* data, int start, int end, const int32_t* meta, const jc_geom& g, int m0,
+                            int m1, int16_t* coef) {
+  jc_bits b;
+  jc_bits_init(b, data, start, end);
+  int status = 0;
+  int dc[3] = {0, 0, 0};
+  int mcu = m0, blk = 0, k = 0, comp = 0;
+  int16_t* dst = coef;
+  const int32_t* q = meta + JM_QUANT;
+  const long iters = (long)(m1 - m0) * g.mcu_blocks * 64;
+  for (long it = 0; it < iters && mcu < m1; ++it) {
+    jc_fill(b);
+    if (k == 0) {
+      const int luma = g.ncomp == 1 ? 1 : g.hs * g.vs;
+      comp = blk < luma ? 0 : blk - luma + 1;
+      const int mx = mcu % g.mcux, my = mcu / g.mcux;
+      const int bx = comp == 0 ? mx * g.hs + blk % g.hs : mx;
+      const int by = comp == 0 ? my * g.vs + blk / g.hs : my;
+      dst = coef + ((long)g.boff[comp] + (long)by * g.bw[comp] + bx) * 64;
+      q = meta + JM_QUANT + comp * 64;
+      const int t = jc_huff(meta + JM_HUFF + comp * JM_HUFF_WORDS, b, &status) & 15;
+      const int diff = t ? jc_extend(b, t) : 0;
+      dc[comp] = (int16_t)(dc[comp] + diff);
+      dst[0] = (int16_t)(dc[comp] * (q[0] & 0xFFFF));
+      k = 1;
+    } else {
+      const int rs = jc_huff(meta + JM_HUFF + (3 + comp) * JM_HUFF_WORDS, b, &status);
+      const int r = rs >> 4, s = rs & 15;
+      if (s == 0) {
+        k = r == 15 ? k + 16 : 64;
+      } else {
+        k += r;
+        if (k > 63) {                     // a run past the block: libjpeg stores it at the last position
+          status |= JC_BAD_RUN;
+          k = 63;
+        }
+        const int n = jc_zigzag(k);
+        dst[n] = (int16_t)(jc_extend(b, s) * (q[n] & 0xFFFF));
+        ++k;
+      }
+      if (k >= 64) {
+        k = 0;
+        if (++blk == g.mcu_blocks) {
+          blk = 0;
+          ++mcu;
+        }
+      }
+    }
+  }
+  return status;
+}
+
+// Restart segment `seg` of the frame described by `m` (width words): its bytes [s0, s1) of the shared buffer of
+// data_len bytes and its MCUs [m0, m1).  The descriptor is NOT trusted (a kernel reads the device copy): every value
+// is clamped to the buffer, the descriptor's width, `maxseg` and the frame's MCU count.  False: no such segment.
+JC_HD bool jc_segment_range(const int32_t* m, int width, int maxseg, int data_len, int seg, const jc_geom& g, int* s0,
+                            int* s1, int* m0, int* m1) {
+  int nseg = m[JM_NSEG];
+  const int room = width - JM_SEG < maxseg ? width - JM_SEG : maxseg;
+  nseg = nseg < 1 ? 1 : nseg > room ? room : nseg;
+  if (seg < 0 || seg >= nseg) return false;
+  long lo = m[JM_OFF], hi = lo + (long)m[JM_LEN];
+  lo = lo < 0 ? 0 : lo > data_len ? data_len : lo;
+  hi = hi < lo ? lo : hi > data_len ? data_len : hi;
+  long a = lo + m[JM_SEG + seg];
+  long b = seg + 1 < nseg ? lo + m[JM_SEG + seg + 1] : hi;
+  a = a < lo ? lo : a > hi ? hi : a;
+  b = b < a ? a : b > hi ? hi : b;
+  const long total = (long)g.mcux * g.mcuy;
+  long ri = m[JM_RI];
+  if (ri < 1 || ri > total) ri = total;
+  long f = seg * ri;
+  f = f > total ? total : f;
+  long l = f + ri;
+  l = l > total ? total : l;
+  *s0 = (int)a; *s1 = (int)b; *m0 = (int)f; *m1 = (int)l;
+  return true;
+}
+
+// ---- inverse DCT: libjpeg's jpeg_idct_islow (CONST_BITS 13, PASS1_BITS 2) ---------------------------------------------
+JC_HD int32_t jc_descale(uint32_t x, int s) { return (int32_t)(x + (1u << (s - 1))) >> s; }
+
+JC_HD void jc_idct_1d(uint32_t i0, uint32_t i1, uint32_t i2, uint32_t i3, uint32_t i4, uint32_t i5, uint32_t i6,
+                      uint32_t i7, int s, int32_t* o) {
+  uint32_t z1 = (i2 + i6) * 4433u;
+  const uint32_t t2 = z1 - i6 * 15137u, t3 = z1 + i2 * 6270u;
+  const uint32_t t0 = (i0 + i4) << 13, t1 = (i0 - i4) << 13;
+  const uint32_t t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  uint32_t a0 = i7, a1 = i5, a2 = i3, a3 = i1;
+  z1 = a0 + a3;
+  uint32_t z2 = a1 + a2, z3 = a0 + a2, z4 = a1 + a3;
+  const uint32_t z5 = (z3 + z4) * 9633u;
+  a0 *= 2446u; a1 *= 16819u; a2 *= 25172u; a3 *= 12299u;
+  z1 *= (uint32_t)-7373; z2 *= (uint32_t)-20995;
+  z3 = z3 * (uint32_t)-16069 + z5;
+  z4 = z4 * (uint32_t)-3196 + z5;
+  a0 += z1 + z3; a1 += z2 + z4; a2 += z2 + z3; a3 += z1 + z4;
+  o[0] = jc_descale(t10 + a3, s); o[7] = jc_descale(t10 - a3, s);
+  o[1] = jc_descale(t11 + a2, s); o[6] = jc_descale(t11 - a2, s);
+  o[2] = jc_descale(t12 + a1, s); o[5] = jc_descale(t12 - a1, s);
+  o[3] = jc_descale(t13 + a0, s); o[4] = jc_descale(t13 - a0, s);
+}
+
+JC_HD uint8_t jc_range_limit(int32_t x) {          // libjpeg's range table (centre 128), not a clamp
+  const int idx = x & 1023;
+  return (uint8_t)(idx < 128 ? idx + 128 : idx < 512 ? 255 : idx < 896 ? 0 : idx - 896);
+}
+
+// 64 dequantised coefficients in natural order -> 8 x 8 samples at out[y * stride + x]
+JC_HD void jc_idct_block(const int16_t* in, uint8_t* out, long stride) {
+  int32_t ws[64], o[8];
+  for (int c = 0; c < 8; ++c) {
+    jc_idct_1d((uint32_t)in[c], (uint32_t)in[8 + c], (uint32_t)in[16 + c], (uint32_t)in[24 + c], (uint32_t)in[32 + c],
+               (uint32_t)in[40 + c], (uint32_t)in[48 + c], (uint32_t)in[56 + c], 11, o);
+    for (int r = 0; r < 8; ++r) ws[r * 8 + c] = o[r];
+  }
+  for (int r = 0; r < 8; ++r) {
+    const int32_t* w = ws + r * 8;
+    jc_idct_1d((uint32_t)w[0], (uint32_t)w[1], (uint32_t)w[2], (uint32_t)w[3], (uint32_t)w[4], (uint32_t)w[5],
+               (uint32_t)w[6], (uint32_t)w[7], 18, o);
+    for (int c = 0; c < 8; ++c) out[r * stride + c] = jc_range_limit(o[c]);
+  }
+}
+
+// ---- chroma upsampling (libjpeg-turbo's "fancy" h2v1 / h2v2) and colour conversion ------------------------------------
+// Sample of a chroma plane `p` (row stride `pw`, real size dw x dh) at output pixel (x, y), 0 <= x < W, 0 <= y < H.
+JC_HD int jc_chroma(const uint8_t* p, long pw, int dw, int dh, int hs, int vs, int x, int y) {
+  if (hs == 1) return p[(long)y * pw + x];
+  const int c = x >> 1;
+  if (vs == 1) {
+    const uint8_t* row = p + (long)y * pw;
+    if (x == 0) return row[0];
+    if (x == 2 * dw - 1) return row[dw - 1];
+    return (x & 1) ? (3 * row[c] + row[c + 1] + 2) >> 2 : (3 * row[c] + row[c - 1] + 1) >> 2;
+  }
+  const int r = y >> 1;
+  int nb = (y & 1) ? r + 1 : r - 1;
+  nb = nb < 0 ? 0 : nb > dh - 1 ? dh - 1 : nb;
+  const uint8_t* a = p + (long)r * pw;
+  const uint8_t* n = p + (long)nb * pw;
+  const int cs = 3 * a[c] + n[c];
+  if (x == 0) return (4 * cs + 8) >> 4;
+  if (x == 2 * dw - 1) return (4 * cs + 7) >> 4;
+  if (x & 1) return (3 * cs + 3 * a[c + 1] + n[c + 1] + 7) >> 4;
+  return (3 * cs + 3 * a[c - 1] + n[c - 1] + 8) >> 4;
+}
+
+JC_HD uint8_t jc_clamp8(int v) { return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); }
+
+JC_HD void jc_ycc_rgb(int y, int cb, int cr, uint8_t* rgb) {
+  cb -= 128;
+  cr -= 128;
+  rgb[0] = jc_clamp8(y + ((91881 * cr + 32768) >> 16));
+  rgb[1] = jc_clamp8(y + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
+  rgb[2] = jc_clamp8(y + ((116130 * cb + 32768) >> 16));
+}
+
+// One output pixel of a frame from its sample planes (component c at planes + poff[c], row stride pw[c]).
+JC_HD void jc_pixel(const uint8_t* planes, const jc_geom& g, int x, int y, uint8_t* rgb) {
+  const long pw0 = (long)g.bw[0] * 8;
+  const int Y = planes[(long)y * pw0 + x];
+  if (g.ncomp == 1) {
+    rgb[0] = rgb[1] = rgb[2] = (uint8_t)Y;
+    return;
+  }
+  const long pw1 = (long)g.bw[1] * 8;
+  const uint8_t* pb = planes + (long)g.boff[1] * 64;
+  const uint8_t* pr = planes + (long)g.boff[2] * 64;
+  jc_ycc_rgb(Y, jc_chroma(pb, pw1, g.dw, g.dh, g.hs, g.vs, x, y), jc_chroma(pr, pw1, g.dw, g.dh, g.hs, g.vs, x, y),
+             rgb);
+}
+
+// where block `blk` (0 <= blk < g.nblocks, coefficient order) puts its samples: offset into the frame's planes
+JC_HD long jc_block_samples(const jc_geom& g, int blk, long* stride) {
+  const int c = blk >= g.boff[2] && g.ncomp == 3 ? 2 : blk >= g.boff[1] && g.ncomp == 3 ? 1 : 0;
+  const int i = blk - g.boff[c];
+  const int by = i / g.bw[c], bx = i % g.bw[c];
+  *stride = (long)g.bw[c] * 8;
+  return (long)g.boff[c] * 64 + (long)by * 8 * *stride + bx * 8;
+}

@@ -1,0 +1,356 @@
+"""Baseline JPEG frames decoded on the GPU, bit-identical to PIL (dataset/lmdb_dataset.py:37-38 of the reference:
+`Image.open(BytesIO(raw)).convert('RGB')` with libjpeg-turbo).
+
+    worker:  data, meta = jpeg.pack(raws)                 # headers parsed, tables derived; compressed bytes travel
+    collate: data, meta = jpeg.cat(packs)
+    loop:    frames = jpeg.decode(data, meta)             # (F, H, W, 3) uint8 on the device
+
+`frames` is what stage_train_clips, stage_classifier_clips, stage_crops and VideoEvaluator.add_frames take.
+
+Scope: baseline / extended sequential Huffman (SOF0, SOF1), 8-bit, one interleaved scan, one component or YCbCr with
+luma sampled 1x1, 2x1 or 2x2, optional restart intervals -- what ffmpeg, cv2.imwrite and PIL write by default.
+Anything else is refused by `parse` on the host with `Unsupported` (a ValueError naming the reason) before a byte is
+uploaded, so a caller can fall back to PIL for that video.
+
+The entropy stage is serial inside a restart segment: a frame WITHOUT restart markers is decoded by one GPU lane
+(64 frames per wave); with markers every segment is a lane of its own."""
+import numpy as np
+import torch
+
+from . import ops
+
+META_QUANT, META_HUFF, HUFF_WORDS = 16, 208, 96
+META_SEG = META_HUFF + 6 * HUFF_WORDS           # csrc/jpeg_core.h: JM_*
+MAX_SIDE = 8192
+
+_SOF_NAMES = {0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)", 0xC5: "differential sequential (SOF5)",
+              0xC6: "differential progressive (SOF6)", 0xC7: "differential lossless (SOF7)",
+              0xC9: "arithmetic coding (SOF9)", 0xCA: "arithmetic coding, progressive (SOF10)",
+              0xCB: "arithmetic coding, lossless (SOF11)", 0xCD: "arithmetic coding, differential (SOF13)",
+              0xCE: "arithmetic coding, differential progressive (SOF14)",
+              0xCF: "arithmetic coding, differential lossless (SOF15)"}
+
+ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13,
+                   6, 7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45,
+                   38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63])
+
+
+class Unsupported(ValueError):
+    """A file this decoder does not take; the message names the reason."""
+
+
+def _u16(b, at):
+    return (b[at] << 8) | b[at + 1]
+
+
+def parse(raw):
+    """The headers of one JPEG file, host only -> dict:
+      width, height, ncomp, sampling (hs, vs) of the luma (chroma is 1x1),
+      quant: per component its (64,) uint8 table in natural order,
+      dc, ac: per component its Huffman table as (bits[16], vals),
+      quant_tables, dc_tables, ac_tables: the ids the file defined,
+      restart_interval (MCUs, 0 = none), scan = (start, end) byte range of the entropy-coded data,
+      segments: offset of every restart segment relative to scan[0].
+    Raises Unsupported for everything outside the scope in the module docstring."""
+    b = bytes(raw)
+    n = len(b)
+    if n < 4 or b[0] != 0xFF or b[1] != 0xD8:
+        raise Unsupported("not a JPEG file (no SOI)")
+    qt, dct, act = {}, {}, {}
+    ri, frame, adobe, jfif = 0, None, None, False
+    at = 2
+    while True:
+        if at + 4 > n:
+            raise Unsupported("a segment runs past the buffer (file cut before SOS)")
+        if b[at] != 0xFF:
+            raise Unsupported("garbage between segments at byte %d" % at)
+        mk = b[at + 1]
+        if mk == 0xFF:                                   # fill byte
+            at += 1
+            continue
+        if mk == 0xD9:
+            raise Unsupported("EOI before any scan")
+        ln = _u16(b, at + 2)
+        if ln < 2 or at + 2 + ln > n:
+            raise Unsupported("a segment runs past the buffer (marker FF%02X at byte %d)" % (mk, at))
+        seg = b[at + 4:at + 2 + ln]
+        if mk in (0xC0, 0xC1):
+            if frame is not None:
+                raise Unsupported("several frames (a second SOF)")
+            if len(seg) < 6 or len(seg) < 6 + 3 * seg[5]:
+                raise Unsupported("a short SOF segment")
+            if seg[0] != 8:
+                raise Unsupported("%d-bit samples" % seg[0])
+            frame = {"height": _u16(seg, 1), "width": _u16(seg, 3),
+                     "comps": [(seg[6 + 3 * i], seg[7 + 3 * i] >> 4, seg[7 + 3 * i] & 15, seg[8 + 3 * i])
+                               for i in range(seg[5])]}
+        elif mk in _SOF_NAMES:
+            raise Unsupported(_SOF_NAMES[mk])
+        elif mk == 0xCC:
+            raise Unsupported("arithmetic coding (DAC)")
+        elif mk == 0xDB:
+            i = 0
+            while i < len(seg):
+                pq, tq = seg[i] >> 4, seg[i] & 15
+                if pq != 0:
+                    raise Unsupported("16-bit quantisation table")
+                if tq > 3 or i + 65 > len(seg):
+                    raise Unsupported("a bad DQT segment")
+                t = np.zeros(64, dtype=np.uint8)
+                t[ZIGZAG] = np.frombuffer(seg, dtype=np.uint8, count=64, offset=i + 1)
+                qt[tq] = t
+                i += 65
+        elif mk == 0xC4:
+            i = 0
+            while i < len(seg):
+                if i + 17 > len(seg):
+                    raise Unsupported("a bad DHT segment")
+                tc, th = seg[i] >> 4, seg[i] & 15
+                bits = np.frombuffer(seg, dtype=np.uint8, count=16, offset=i + 1).astype(np.int64)
+                cnt = int(bits.sum())
+                if tc > 1 or th > 3 or cnt > 256 or i + 17 + cnt > len(seg):
+                    raise Unsupported("a bad DHT segment")
+                code = 0
+                for l in range(16):                       # the code space must not overflow
+                    code = (code + int(bits[l])) << 1
+                    if code > (2 << (l + 1)):
+                        raise Unsupported("a Huffman table with too many codes")
+                vals = np.frombuffer(seg, dtype=np.uint8, count=cnt, offset=i + 17).copy()
+                (act if tc else dct)[th] = (bits.copy(), vals)
+                i += 17 + cnt
+        elif mk == 0xDD:
+            if len(seg) != 2:
+                raise Unsupported("a bad DRI segment")
+            ri = _u16(seg, 0)
+        elif mk == 0xEE and len(seg) >= 12 and seg[:5] == b"Adobe":
+            adobe = seg[11]
+        elif mk == 0xE0 and seg[:5] == b"JFIF\0":
+            jfif = True
+        elif mk == 0xDC:
+            raise Unsupported("DNL (the height is defined after the scan)")
+        elif mk == 0xDA:
+            break
+        at += 2 + ln
+    if frame is None:
+        raise Unsupported("SOS before any SOF")
+    comps, W, H = frame["comps"], frame["width"], frame["height"]
+    if len(comps) not in (1, 3):
+        raise Unsupported("%d components" % len(comps))
+    if H == 0:
+        raise Unsupported("DNL (the height is defined after the scan)")
+    if W < 1 or W > MAX_SIDE or H > MAX_SIDE:
+        raise Unsupported("a %d x %d image (the limit is %d)" % (W, H, MAX_SIDE))
+    if len(comps) == 3:
+        if adobe == 0:
+            raise Unsupported("Adobe APP14 with transform 0 (RGB stored as is)")
+        if adobe is None and not jfif and [c[0] for c in comps] == [82, 71, 66]:
+            raise Unsupported("components named R, G, B (RGB stored as is)")
+        hs, vs = comps[0][1], comps[0][2]
+        if (hs, vs) not in ((1, 1), (2, 1), (2, 2)) or any((c[1], c[2]) != (1, 1) for c in comps[1:]):
+            raise Unsupported("sampling factors %s" % ", ".join("%dx%d" % (c[1], c[2]) for c in comps))
+    else:
+        hs, vs = 1, 1                                    # one component is never interleaved: its factors are moot
+    # the scan header
+    if len(seg) < 1 or len(seg) != 4 + 2 * seg[0]:
+        raise Unsupported("a bad SOS segment")
+    if seg[0] != len(comps):
+        raise Unsupported("several scans (the first holds %d of %d components)" % (seg[0], len(comps)))
+    quant, dc, ac = [], [], []
+    for i, c in enumerate(comps):
+        if seg[1 + 2 * i] != c[0]:
+            raise Unsupported("scan components out of frame order")
+        td, ta = seg[2 + 2 * i] >> 4, seg[2 + 2 * i] & 15
+        if c[3] not in qt:
+            raise Unsupported("missing quantisation table %d" % c[3])
+        if td not in dct:
+            raise Unsupported("missing DC Huffman table %d" % td)
+        if ta not in act:
+            raise Unsupported("missing AC Huffman table %d" % ta)
+        quant.append(qt[c[3]])
+        dc.append(dct[td])
+        ac.append(act[ta])
+    ss, se, ah_al = seg[-3], seg[-2], seg[-1]
+    if (ss, se, ah_al) != (0, 63, 0):
+        raise Unsupported("a scan of part of the spectrum (progressive parameters)")
+    start = at + 2 + ln
+    # the marker that ends the scan: FF followed by anything but 00, a restart marker or a fill FF
+    arr = np.frombuffer(b, dtype=np.uint8, offset=start)
+    ff = np.flatnonzero(arr[:-1] == 0xFF) if len(arr) > 1 else np.zeros(0, dtype=np.int64)
+    nxt = arr[ff + 1]
+    stop = ff[(nxt != 0) & ((nxt < 0xD0) | (nxt > 0xD7)) & (nxt != 0xFF)]
+    if len(stop) == 0:
+        raise Unsupported("no EOI")
+    end = start + int(stop[0])
+    last = b[end + 1]
+    if last == 0xDC:
+        raise Unsupported("DNL (the height is defined after the scan)")
+    if last != 0xD9:
+        raise Unsupported("several scans (marker FF%02X after the first)" % last)
+    rst = ff[(nxt >= 0xD0) & (nxt <= 0xD7) & (ff < end - start)]
+    segments = np.concatenate([[0], rst + 2]).astype(np.int64)
+    mcus = -(-W // (8 * hs)) * -(-H // (8 * vs))
+    want = 1 if ri == 0 else -(-mcus // ri)
+    if len(segments) != want:
+        raise Unsupported("%d restart segments where the interval of %d MCUs asks for %d" % (len(segments), ri, want))
+    return {"width": W, "height": H, "ncomp": len(comps), "sampling": (hs, vs), "quant": quant, "dc": dc, "ac": ac,
+            "quant_tables": sorted(qt), "dc_tables": sorted(dct), "ac_tables": sorted(act), "restart_interval": ri,
+            "scan": (start, end), "segments": segments}
+
+
+def _huff_words(table):
+    """(bits, vals) -> the 96 words the kernel reads: limit[16], valoff[16], 256 values packed four to a word."""
+    bits, vals = table
+    w = np.zeros(HUFF_WORDS, dtype=np.int64)
+    code, k = 0, 0
+    for l in range(16):
+        w[16 + l] = k - code                             # value index of a code = valoff + the code itself
+        code += int(bits[l])
+        k += int(bits[l])
+        w[l] = min(code << (15 - l), 65536)
+        code <<= 1
+    hv = np.zeros(256, dtype=np.uint8)
+    hv[:len(vals)] = vals
+    w[32:] = hv.view("<u4")
+    return w
+
+
+def _meta_row(info, offset, width):
+    m = np.zeros(width, dtype=np.int64)
+    m[0], m[1] = offset, info["scan"][1] - info["scan"][0]
+    m[2], m[3] = info["restart_interval"], len(info["segments"])
+    for c in range(info["ncomp"]):
+        m[META_QUANT + 64 * c:META_QUANT + 64 * (c + 1)] = info["quant"][c]
+        m[META_HUFF + HUFF_WORDS * c:META_HUFF + HUFF_WORDS * (c + 1)] = _huff_words(info["dc"][c])
+        m[META_HUFF + HUFF_WORDS * (3 + c):META_HUFF + HUFF_WORDS * (4 + c)] = _huff_words(info["ac"][c])
+    m[META_SEG:META_SEG + len(info["segments"])] = info["segments"]
+    # the packed value words are unsigned; store their bit patterns
+    return (m & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+
+
+def pack(raws):
+    """JPEG files (bytes-like) of ONE size and sampling -> (data, meta): data uint8 (n,) every frame's entropy-coded
+    bytes, meta int32 (F, 8 + width): per frame the kernel's descriptor (include/coclr_hip.h: coclr_jpeg_decode)
+    behind 8 words that carry the pack's geometry {8 + width, H, W, components, hs, vs, 0, 0} through a collate.
+    Runs in the Dataset worker in place of the PIL decode; raises Unsupported as parse does."""
+    raws = list(raws)
+    if not raws:
+        raise ValueError("coclr_amd: pack needs at least one frame")
+    infos = [parse(r) for r in raws]
+    key = lambda i: (i["height"], i["width"], i["ncomp"], i["sampling"])     # noqa: E731
+    if any(key(i) != key(infos[0]) for i in infos):
+        raise Unsupported("frames of one pack differ in size, components or sampling: %s" %
+                          sorted(set(key(i) for i in infos)))
+    H, W, ncomp, (hs, vs) = key(infos[0])
+    width = META_SEG + max(len(i["segments"]) for i in infos)
+    meta = np.zeros((len(raws), 8 + width), dtype=np.int32)
+    meta[:, :8] = [8 + width, H, W, ncomp, hs, vs, 0, 0]
+    chunks, offset = [], 0
+    for f, (raw, info) in enumerate(zip(raws, infos)):
+        meta[f, 8:] = _meta_row(info, offset, width)
+        chunks.append(np.frombuffer(bytes(raw), dtype=np.uint8)[info["scan"][0]:info["scan"][1]])
+        offset += len(chunks[-1])
+    if offset > 0x7fffffff:
+        raise ValueError("coclr_amd: a pack holds up to 2 GiB of compressed bytes")
+    data = np.concatenate(chunks) if offset else np.zeros(0, dtype=np.uint8)
+    return torch.from_numpy(data.copy()), torch.from_numpy(meta)
+
+
+def _geometry(meta):
+    if not isinstance(meta, torch.Tensor) or meta.dtype != torch.int32 or meta.dim() != 2 or meta.is_cuda or \
+            meta.shape[0] < 1 or meta.shape[1] <= 8 + META_SEG:
+        raise ValueError("coclr_amd: meta must be the host int32 (F, width) tensor of jpeg.pack")
+    head = meta[:, :8]
+    if not bool((head == head[0]).all()):
+        raise ValueError("coclr_amd: the frames of one decode share size, components and sampling")
+    width, H, W, ncomp, hs, vs = [int(v) for v in head[0, :6]]
+    if width != meta.shape[1]:
+        raise ValueError("coclr_amd: meta is %d words wide and says %d" % (meta.shape[1], width))
+    ops.jpeg_workspace(H, W, ncomp, hs, vs)                               # refuses a geometry the kernels do not take
+    return H, W, ncomp, hs, vs
+
+
+def cat(packs):
+    """The packs of a batch -> one (data, meta): the default collate cannot stack ragged bytes.  Byte offsets are
+    shifted, and descriptors are padded to the widest pack (the one with the most restart segments)."""
+    packs = list(packs)
+    if not packs:
+        raise ValueError("coclr_amd: cat needs at least one pack")
+    geo = [_geometry(m) for _, m in packs]
+    if any(g != geo[0] for g in geo):
+        raise Unsupported("packs differ in size, components or sampling: %s" % sorted(set(geo)))
+    width = max(m.shape[1] for _, m in packs)
+    rows, offset = [], 0
+    for data, m in packs:
+        r = torch.zeros(m.shape[0], width, dtype=torch.int32)
+        r[:, :m.shape[1]] = m
+        r[:, 0] = width
+        r[:, 8] += offset
+        offset += data.numel()
+        rows.append(r)
+    if offset > 0x7fffffff:
+        raise ValueError("coclr_amd: one decode takes up to 2 GiB of compressed bytes")
+    return torch.cat([d for d, _ in packs]), torch.cat(rows)
+
+
+def check_meta(data, meta):
+    """What coclr_jpeg_decode checks, said in words, before anything is uploaded."""
+    H, W, ncomp, hs, vs = _geometry(meta)
+    if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() != 1:
+        raise ValueError("coclr_amd: data must be the flat uint8 tensor of jpeg.pack")
+    m = meta[:, 8:].to(torch.int64)
+    n, width = data.numel(), m.shape[1]
+    mcus = -(-W // (8 * hs)) * -(-H // (8 * vs))
+    off, ln, ri, nseg = m[:, 0], m[:, 1], m[:, 2], m[:, 3]
+    if bool(((off < 0) | (ln < 0) | (off + ln > n)).any()):
+        raise ValueError("coclr_amd: a frame's bytes leave the buffer of %d bytes" % n)
+    want = torch.where(ri > 0, -(-mcus // ri.clamp(min=1)), torch.ones_like(ri))
+    if bool(((ri < 0) | (nseg != want) | (nseg > width - META_SEG)).any()):
+        raise ValueError("coclr_amd: a frame's restart segments do not match its interval (%d MCUs per frame)" % mcus)
+    seg = m[:, META_SEG:]
+    live = torch.arange(seg.shape[1])[None, :] < nseg[:, None]
+    prev = torch.cat([torch.zeros_like(seg[:, :1]), seg[:, :-1]], 1)
+    if bool((live & ((seg < prev) | (seg > ln[:, None]))).any()):
+        raise ValueError("coclr_amd: a restart segment's offset decreases or leaves its frame's bytes")
+    q = m[:, META_QUANT:META_QUANT + 64 * ncomp]
+    if bool(((q < 0) | (q > 255)).any()):
+        raise ValueError("coclr_amd: a quantiser outside 0..255")
+    return H, W, ncomp, hs, vs
+
+
+def decode(data, meta, out=None, device=None, max_stage_bytes=256 << 20, return_status=False):
+    """(data, meta) of pack / cat -> (F, H, W, 3) uint8 on the device, the bytes PIL's convert('RGB') returns.
+    A bad `meta` is refused on the host; the bytes are uploaded once; whole frames are decoded `max_stage_bytes` of
+    intermediate storage (coefficients + sample planes) at a time.  `out`: a contiguous (F, H, W, 3) uint8 device
+    tensor to fill (a view into a larger buffer will do).  The per-frame int32 status (0 = clean; 1: a bit pattern
+    that is no Huffman code, 2: a run past the block -- a damaged file) is returned with return_status=True and
+    kept in `decode.last_status` otherwise."""
+    H, W, ncomp, hs, vs = check_meta(data, meta)
+    F = meta.shape[0]
+    if device is None:
+        device = out.device if out is not None else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if out is None:
+        out = torch.empty(F, H, W, 3, dtype=torch.uint8, device=device)
+    elif tuple(out.shape) != (F, H, W, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError("coclr_amd: out must be a contiguous uint8 device tensor %s" % ((F, H, W, 3),))
+    cb, pb = ops.jpeg_workspace(H, W, ncomp, hs, vs)
+    per = max(1, min(F, int(max_stage_bytes) // (cb + pb)))
+    host = meta[:, 8:].contiguous()
+    d_data, d_meta = data.contiguous().to(device), host.to(device)
+    coefs = torch.empty(per * cb // 2, dtype=torch.int16, device=device)
+    planes = torch.empty(per * pb, dtype=torch.uint8, device=device)
+    status = torch.empty(F, dtype=torch.int32, device=device)
+    for k in range(0, F, per):
+        e = min(F, k + per)
+        ops.jpeg_decode(d_data, d_meta[k:e], host[k:e], H, W, ncomp, hs, vs, coefs, planes, out[k:e], status[k:e])
+    decode.last_status = status
+    return (out, status) if return_status else out
+
+
+decode.last_status = None
+
+
+def decode_frames(raws, out=None, device=None, max_stage_bytes=256 << 20):
+    """pack followed by decode: JPEG files of one size and sampling -> (F, H, W, 3) uint8 on the device."""
+    data, meta = pack(raws)
+    return decode(data, meta, out=out, device=device, max_stage_bytes=max_stage_bytes)

@@ -1128,6 +1128,38 @@ def resize2_boxes(frames, desc, desc_host, xtab, ytab, tab2, T, size, S, out, me
         tab2.shape[0] - 1, m, s, o8, of, _stream()), "resize2_boxes")
 
 
+def jpeg_workspace(H, W, ncomp, hs, vs):
+    """Bytes per frame of the coefficient and sample-plane workspaces of jpeg_decode (no device needed)."""
+    a, b = C.c_int64(0), C.c_int64(0)
+    rc = _lib.load().coclr_jpeg_workspace(int(H), int(W), int(ncomp), int(hs), int(vs), C.byref(a), C.byref(b))
+    if rc != 0:
+        raise ValueError("coclr_amd: no JPEG workspace for %d x %d frames of %d components sampled %d x %d" %
+                         (W, H, ncomp, hs, vs))
+    return a.value, b.value
+
+
+def jpeg_decode(data, meta, meta_host, H, W, ncomp, hs, vs, coefs, planes, out, status, stages=7):
+    """data uint8 (n,), meta int32 (F, width) on the device and meta_host, the same on the host (include/coclr_hip.h:
+    coclr_jpeg_decode) -> out uint8 (F, H, W, 3), status int32 (F,).  coefs int16 / planes uint8: flat workspaces of
+    F times jpeg_workspace().  `stages`: 1 entropy, 2 inverse DCT, 4 colour; 7 = all three."""
+    if meta.dim() != 2 or meta.shape != meta_host.shape or meta_host.is_cuda or meta_host.dtype != torch.int32 or \
+            not meta.is_contiguous() or not meta_host.is_contiguous():
+        raise ValueError("coclr_amd: frame descriptors must be contiguous int32 (F, width), device and host")
+    F, width = meta.shape
+    cb, pb = jpeg_workspace(H, W, ncomp, hs, vs)
+    if data.dim() != 1 or not data.is_contiguous() or coefs.numel() * 2 < F * cb or planes.numel() < F * pb or \
+            not coefs.is_contiguous() or not planes.is_contiguous():
+        raise ValueError("coclr_amd: jpeg_decode needs flat bytes and workspaces of %d + %d bytes per frame" % (cb, pb))
+    if tuple(out.shape) != (F, H, W, 3) or not out.is_contiguous():
+        raise ValueError("coclr_amd: out must be contiguous %s, got %s" % ((F, H, W, 3), tuple(out.shape)))
+    if tuple(status.shape) != (F,) or not status.is_contiguous():
+        raise ValueError("coclr_amd: status must be contiguous (%d,), got %s" % (F, tuple(status.shape)))
+    _lib.check(_L().coclr_jpeg_decode(
+        _p(data, torch.uint8), data.numel(), _p(meta, torch.int32), C.cast(meta_host.data_ptr(), C.POINTER(C.c_int32)),
+        F, width, int(H), int(W), int(ncomp), int(hs), int(vs), int(stages), _p(coefs, torch.int16),
+        _p(planes, torch.uint8), _p(out, torch.uint8), _p(status, torch.int32), _stream()), "jpeg_decode")
+
+
 def _program_call(name, frames, kinds, params, group_size, T, mean, std, out, host_tables):
     if frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
         raise ValueError("coclr_amd: frames must be contiguous (N, H, W, 3), got %s" % (tuple(frames.shape),))

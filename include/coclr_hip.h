@@ -710,6 +710,38 @@ int coclr_resize2_boxes(const uint8_t* frames, int F, int H, int W, const int32_
                         int64_t ylen, const int32_t* tab2, int64_t len2, int taps2, const float* mean,
                         const float* std, uint8_t* out8, float* out, void* stream);
 
+/* Baseline JPEG frames -> the uint8 [F][H][W][3] frames the staging entry points above take, bit-identical to
+ * Image.open(BytesIO(raw)).convert('RGB') with libjpeg-turbo (dataset/lmdb_dataset.py:37-38): Huffman decoding,
+ * libjpeg's "islow" inverse DCT, "fancy" chroma upsampling, 16-bit fixed-point YCbCr -> RGB.  All frames of a call
+ * share (H, W), the component count (1, or 3 = YCbCr) and the luma sampling hs x vs in {1x1, 2x1, 2x2} (chroma 1x1;
+ * one component: 1x1); tables, restart interval and byte counts are per frame.  The headers are parsed on the host
+ * (coclr_amd/jpeg.py: parse / pack), which refuses every other kind of file.
+ * Workspace, answered without a device: bytes PER FRAME of `coefs` (int16, 64 per 8x8 block) and `planes` (uint8). */
+int coclr_jpeg_workspace(int H, int W, int ncomp, int hs, int vs, int64_t* coef_bytes, int64_t* plane_bytes);
+/* data: the frames' entropy-coded bytes one after the other, data_len of them (< 2^31), device.
+ * meta: int32 [F][width], DEVICE, one descriptor per frame (word offsets as in csrc/jpeg_core.h):
+ *   0 offset of the frame's bytes in data, 1 their count, 2 restart interval in MCUs (0 = none), 3 restart segments,
+ *   16 [3][64] quantisers per component, natural order; 208 six Huffman tables of 96 words (DC of component 0..2,
+ *   AC of component 0..2: limit[16], valoff[16], 256 values in 64 words); 784 [segments] first byte of every restart
+ *   segment relative to word 0.  width >= 784 + the most segments of any frame.
+ * meta_host: the same on the HOST, read at call time and validated; the kernels read the device copy and stay in
+ *   bounds -- reads inside data, stores inside the frame's own storage, loops bounded by the block count -- whatever
+ *   the device copy and the bytes hold.  Past the end of its bytes a frame reads zero bits, as libjpeg pads.
+ * stages: bit mask of what to launch, in order: 1 entropy (zero-fills coefs and status, then one lane per (frame,
+ *   restart segment): a frame without restart markers is decoded by ONE lane), 2 inverse DCT (one lane per block,
+ *   coefs -> planes), 4 upsampling + colour + crop (planes -> out).  7 decodes; the parts exist to be timed.
+ * coefs / planes: F times the workspace sizes, 16-byte aligned.  out: uint8 [F][H][W][3].
+ * status: int32 [F], 0 = clean; bit 0 a bit pattern that is no Huffman code (decoded as 0), bit 1 a zero run past
+ *   the 64th coefficient.
+ * COCLR_EINVAL before any launch: a null or misaligned pointer; F < 1; H or W outside 1..8192; another component
+ * count or sampling; stages outside 1..7; data_len outside 0..2^31-1; a descriptor whose bytes leave data, whose
+ * segment count is not ceil(MCUs / interval) or exceeds width - 784, whose segment offsets decrease or leave its
+ * bytes, whose quantisers leave 0..255 or whose code limits decrease or leave 0..65536.
+ * Additive: the ABI number stays 25 -- no existing signature or behaviour changed. */
+int coclr_jpeg_decode(const uint8_t* data, int64_t data_len, const int32_t* meta, const int32_t* meta_host, int F,
+                      int width, int H, int W, int ncomp, int hs, int vs, int stages, int16_t* coefs,
+                      uint8_t* planes, uint8_t* out, int32_t* status, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* Evaluation consumers (model/classifier.py:47-61; eval/main_classifier.py) */
 /* ------------------------------------------------------------------------ */
