@@ -25,9 +25,18 @@ __device__ __forceinline__ float block256_max(float v, float* red) {
   return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
-// row statistics: float[8] = {loss, lse, aux, hit@k1, hit@k2, self hit@k1, self hit@k2, rowmax}
+// row statistics: float[8] = {loss, lse, aux, lse_lo, aux_lo, 0, 0, rowmax}
 //   aux = modes 0/1: log-sum-exp over the positives used by the loss; mode 2: their number.
-// flags[b] bit 0: column 0 was dropped from this row's loss mask (mode 1, drop_self).
+//   lse_lo / aux_lo: on WIDE rows (below) what the fp32 rounding of lse / aux (a maximum plus a small logarithm)
+//   dropped, so that the backward's exp(v - lse) and exp(v - aux) keep their relative accuracy when the logits are
+//   large: lse + lse_lo == rowmax + log(sum exp(v - rowmax)) to the accuracy of the logarithm alone.  0 otherwise.
+// A row is WIDE when |rowmax| >= 64 or its best positive lies 64 or more below rowmax.  Up to there the plain forms
+// lse - lsp and exp(v - lse) are good to half an ulp of 128 (3.8e-6, inside the backward's 1e-5) and exp(v - rowmax)
+// of a positive is a normal fp32 number (exp(-64) = 1.6e-28), and they are kept bit for bit: unit-norm features give
+// |logit| <= 1 / T, so training never leaves them.  Beyond, exp(v - rowmax) of every positive can underflow (log(0):
+// an infinite loss where the loss is finite) and the rounding of lse becomes the error of the gradient.
+// flags[b] bit 0: column 0 was dropped from this row's loss mask (mode 1, drop_self);
+//          bits 1..4: hit@k1, hit@k2, self hit@k1, self hit@k2.
 __global__ void __launch_bounds__(256)
 nce_loss_rows_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ mask,
                      const int64_t* __restrict__ target, float* __restrict__ rowstats,
@@ -40,19 +49,24 @@ nce_loss_rows_kernel(const float* __restrict__ logits, const uint8_t* __restrict
   const int tcol = mode == 0 ? (int)target[b] : 0;
 
   // pass 1: row max, best positive, number of positives
-  float vmax = -INFINITY, pmax = -INFINITY;
+  float vmax = -INFINITY, pmax = -INFINITY, pmax_rest = -INFINITY;   // _rest: positives other than column 0
   int npos = 0;
   for (int j = tid; j < N1; j += 256) {
     const float v = row[j];
     vmax = fmaxf(vmax, v);
     const bool pos = mode == 0 ? (j == tcol) : (mrow[j] != 0);
     if (pos) { pmax = fmaxf(pmax, v); ++npos; }
+    if (pos && j > 0) pmax_rest = fmaxf(pmax_rest, v);
   }
   vmax = block256_max(vmax, redf);
   pmax = block256_max(pmax, redf);
+  pmax_rest = block256_max(pmax_rest, redf);
   const int npos_all = (int)(block256_sum_d((double)npos, redd) + 0.5);
   const float l0 = row[0];
   const bool drop0 = mode == 1 && drop_self && npos_all != 1 && mrow[0] != 0;
+  // wide rows: the positives' exp-sum is taken against THEIR maximum, not the row's
+  const float lmax = drop0 ? pmax_rest : pmax;
+  const bool wide = fabsf(vmax) >= 64.f || !(vmax - lmax < 64.f);
 
   // pass 2: exp sums and rank counts
   double se = 0.0, pe = 0.0, ps = 0.0;
@@ -63,7 +77,7 @@ nce_loss_rows_kernel(const float* __restrict__ logits, const uint8_t* __restrict
     se += e;
     bool pos = mode == 0 ? (j == tcol) : (mrow[j] != 0);
     if (drop0 && j == 0) pos = false;
-    if (pos) { pe += e; ps += v; }
+    if (pos) { pe += wide ? expf(v - lmax) : e; ps += v; }
     gt_p += v > pmax;
     gt_0 += v > l0;
   }
@@ -73,34 +87,43 @@ nce_loss_rows_kernel(const float* __restrict__ logits, const uint8_t* __restrict
   const int cgp = (int)(block256_sum_d((double)gt_p, redd) + 0.5);
   const int cg0 = (int)(block256_sum_d((double)gt_0, redd) + 0.5);
   if (tid == 0) {
-    const float lse = vmax + logf((float)se);
+    // wide rows form the loss from the DIFFERENCES (of the maxima, of the logs): lse - lsp would carry the rounding
+    // of two numbers of the logits' magnitude into a loss that may be far smaller
+    const float lz = logf((float)se);
+    const float lse = vmax + lz;
     const int npos_eff = npos_all - (drop0 ? 1 : 0);
-    float loss, aux;
+    float loss, aux, aux_lo = 0.f;
     if (mode == 2) {            // -(sum_pos log_softmax) / n_pos
       aux = (float)npos_eff;
-      loss = lse - (float)(ps / (double)npos_eff);
-    } else {                    // -log(sum_pos softmax); mode 0 is the one-positive case
+      loss = wide ? (float)((double)vmax - ps / (double)npos_eff) + lz : lse - (float)(ps / (double)npos_eff);
+    } else if (wide) {          // -log(sum_pos softmax); mode 0 is the one-positive case
+      const float lp = logf((float)pe);
+      aux = lmax + lp;
+      aux_lo = (lmax - aux) + lp;
+      loss = (vmax - lmax) + (lz - lp);
+    } else {
       const float lsp = vmax + logf((float)pe);
       aux = lsp;
       loss = lse - lsp;
     }
     float* o = rowstats + 8 * (long)b;
     o[0] = loss; o[1] = lse; o[2] = aux;
-    o[3] = cgp < k1 ? 1.f : 0.f; o[4] = cgp < k2 ? 1.f : 0.f;
-    o[5] = cg0 < k1 ? 1.f : 0.f; o[6] = cg0 < k2 ? 1.f : 0.f;
+    o[3] = wide ? (vmax - lse) + lz : 0.f; o[4] = aux_lo;
+    o[5] = 0.f; o[6] = 0.f;
     o[7] = vmax;
-    flags[b] = drop0 ? 1 : 0;
+    flags[b] = (uint8_t)((drop0 ? 1 : 0) | (cgp < k1 ? 2 : 0) | (cgp < k2 ? 4 : 0) | (cg0 < k1 ? 8 : 0) |
+                         (cg0 < k2 ? 16 : 0));
   }
 }
 
 // scalars[0..4] = mean over rows of {loss, hit@k1, hit@k2, self hit@k1, self hit@k2}
 __global__ void __launch_bounds__(256)
-nce_loss_fold_kernel(const float* __restrict__ rowstats, float* __restrict__ scalars, int B) {
+nce_loss_fold_kernel(const float* __restrict__ rowstats, const uint8_t* __restrict__ flags,
+                     float* __restrict__ scalars, int B) {
   __shared__ double red[4];
-  const int fields[5] = {0, 3, 4, 5, 6};
   for (int f = 0; f < 5; ++f) {
     double s = 0.0;
-    for (int b = threadIdx.x; b < B; b += 256) s += rowstats[8 * (long)b + fields[f]];
+    for (int b = threadIdx.x; b < B; b += 256) s += f == 0 ? rowstats[8 * (long)b] : (float)((flags[b] >> f) & 1);
     s = block256_sum_d(s, red);
     if (threadIdx.x == 0) scalars[f] = (float)(s / B);
   }
@@ -114,9 +137,9 @@ nce_loss_bwd_kernel(const float* __restrict__ logits, const uint8_t* __restrict_
                     float* __restrict__ dlogits, int B, int N1, int mode) {
   const int b = blockIdx.y;
   const float* st = rowstats + 8 * (long)b;
-  const float lse = st[1], aux = st[2];
+  const float lse = st[1], aux = st[2], lse_lo = st[3], aux_lo = st[4];
   const float gs = dloss[0] / (float)B;
-  const bool drop0 = flags[b] != 0;
+  const bool drop0 = (flags[b] & 1) != 0;
   const int tcol = mode == 0 ? (int)target[b] : 0;
   const float* row = logits + (long)b * N1;
   const uint8_t* mrow = mask ? mask + (long)b * N1 : nullptr;
@@ -127,9 +150,9 @@ nce_loss_bwd_kernel(const float* __restrict__ logits, const uint8_t* __restrict_
     if (mode == 0) {
       w = j == tcol ? 1.f : 0.f;
     } else if (mrow[j] != 0 && !(drop0 && j == 0)) {
-      w = mode == 1 ? expf(v - aux) : 1.f / aux;
+      w = mode == 1 ? expf((v - aux) - aux_lo) : 1.f / aux;
     }
-    drow[j] = gs * (expf(v - lse) - w);
+    drow[j] = gs * (expf((v - lse) - lse_lo) - w);
   }
 }
 
@@ -145,7 +168,7 @@ extern "C" int coclr_nce_loss_fwd(const float* logits, const uint8_t* mask, cons
   hipLaunchKernelGGL(nce_loss_rows_kernel, dim3(B), dim3(256), 0, stream, logits, mask, target,
                      rowstats, flags, N1, mode, drop_self, k1, k2);
   COCLR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(nce_loss_fold_kernel, dim3(1), dim3(256), 0, stream, rowstats, scalars, B);
+  hipLaunchKernelGGL(nce_loss_fold_kernel, dim3(1), dim3(256), 0, stream, rowstats, flags, scalars, B);
   COCLR_LAUNCH_CHECK();
   return 0;
 }

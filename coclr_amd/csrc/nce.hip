@@ -611,7 +611,9 @@ gather_rows_kernel(const float* __restrict__ in, const int64_t* __restrict__ idx
   const long r = blockIdx.y;
   const float* src = in + idx[r] * in_row_stride;
   float* dst = out + r * row_elems;
-  if (((row_elems | in_row_stride) & 3) == 0) {
+  // 16-byte lanes need every row of both operands on a 16-byte boundary: sizes alone do not say that (a view
+  // that starts one float into a buffer has the same strides)
+  if (((row_elems | in_row_stride) & 3) == 0 && ((((uintptr_t)in) | ((uintptr_t)out)) & 15) == 0) {
     const long n4 = row_elems >> 2;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256)
       reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(src)[i];

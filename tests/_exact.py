@@ -1,5 +1,5 @@
 """Shared pieces of the exact pooling / BatchNorm GPU tests (tests/test_gpu_pool_exact.py,
-tests/test_gpu_bn_exact.py): operand placement with guards, exact comparison, and the BatchNorm backward reference
+tests/test_gpu_bn_exact.py) and of the contrastive head (tests/test_gpu_head_exact.py, tests/test_gpu_loss_exact.py): operand placement with guards, exact comparison, and the BatchNorm backward reference
 in float64 with fp32 roundings at the points the kernels determine."""
 import pytest
 import torch
@@ -54,6 +54,29 @@ def source(t, extra=0, pad=0):
     """A read-only operand: its surroundings hold OUTSIDE."""
     dtype = torch.int32 if t.dtype in (torch.int32, torch.int64) else torch.float32
     return Placed(tuple(t.shape), extra, pad, fill=0, around=OUTSIDE, dtype=dtype).put(t)
+
+
+class Placed2D(Placed):
+    """A (rows, cols) row-major operand whose rows are `pad` floats further apart than their length, starting `shift`
+    floats past a 16-byte boundary, between two guard runs; the row padding holds `around` as well.  `view` is the
+    operand, `ld` its leading dimension."""
+
+    def __init__(self, rows, cols, pad=0, shift=0, fill=NAN, around=GUARD, dtype=torch.float32):
+        self.ld = cols + pad
+        self.buf = torch.full((2 * PAD + shift + rows * self.ld,), around, device="cuda", dtype=dtype)
+        self.view = self.buf.as_strided((rows, cols), (self.ld, 1), PAD + shift)
+        self.view.fill_(fill)
+        self.around = around
+
+
+def source2d(t, pad=0, shift=0, transposed=False):
+    """A read-only (R, C) matrix with padded rows, its surroundings and padding holding OUTSIDE.  `transposed`: the
+    matrix is stored column-major ((C, R) rows in memory, each padded) and returned as the (R, C) view of that."""
+    dtype = t.dtype if t.dtype in (torch.int32, torch.int64, torch.uint8) else torch.float32
+    src = t.t() if transposed else t
+    v = Placed2D(src.shape[0], src.shape[1], pad, shift, fill=0, around=OUTSIDE if dtype != torch.uint8 else 77,
+                 dtype=dtype).put(src)
+    return v.t() if transposed else v
 
 
 def vector(t):
