@@ -142,6 +142,8 @@ _SIGNATURES = {
                             _P(f32), vp, vp, vp],
     "coclr_jpeg_workspace": [i32, i32, i32, i32, i32, _P(i64), _P(i64)],
     "coclr_jpeg_decode": [vp, i64, vp, _P(i32), i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp],
+    "coclr_jpeg_decode_split": [vp, i64, vp, _P(i32), i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32,
+                                vp],
     "coclr_colstats_workspace": [i32, i32, _P(i64)],
     "coclr_bn1d_stats": [vp, vp, vp, i32, i32, vp],
     "coclr_center_rows": [vp, vp, vp, i32, i32, vp],

@@ -4,7 +4,10 @@
 //   1 entropy   one lane per (frame, restart segment): Huffman -> dequantised int16 coefficients
 //   2 idct      one lane per 8x8 block: coefficients -> sample planes at the component's own resolution
 //   4 colour    one lane per 16 output pixels of a row: chroma upsampling, YCbCr -> RGB, crop to (H, W)
-// Huffman decoding is serial inside a restart segment, so a frame without restart markers is ONE lane of stage 1.
+// Huffman decoding is serial inside a restart segment.  A frame without restart markers is one lane of
+// jpeg_entropy_kernel, or, with coclr_jpeg_decode_split's chunk_bytes > 0, one workgroup of
+// jpeg_entropy_split_kernel: one lane per chunk of its bytes, decoded from guessed states until every chunk's
+// entry is its predecessor's exit (jpeg_core.h), which is the serial decoder's result for any bytes.
 #include "../../include/coclr_hip.h"
 #include "common.h"
 #include "jpeg_core.h"
@@ -16,18 +19,123 @@ constexpr int JPEG_MAX_SIDE = 8192;
 // one wave per workgroup: with one lane per frame, 64 frames are all a CU gets, so the waves spread over the CUs
 __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restrict__ data, int data_len,
                                                           const int32_t* __restrict__ meta, int width, int F,
-                                                          int maxseg, jc_geom g, int16_t* __restrict__ coef,
-                                                          int32_t* __restrict__ status) {
+                                                          int maxseg, int multi_only, jc_geom g,
+                                                          int16_t* __restrict__ coef, int32_t* __restrict__ status) {
   const long id = (long)blockIdx.x * 64 + threadIdx.x;
   const long f = id / maxseg;
   const int seg = (int)(id % maxseg);
   if (f >= F) return;
   const int32_t* m = meta + f * width;
+  if (multi_only && jc_segment_count(m, width, maxseg) == 1) return;      // jpeg_entropy_split_kernel's frames
   int s0, s1, m0, m1;
   if (!jc_segment_range(m, width, maxseg, data_len, seg, g, &s0, &s1, &m0, &m1)) return;
   const int st = jc_decode_segment(data, s0, s1, m, g, m0, m1, coef + f * (long)g.nblocks * 64);
   if (st) atomicOr(&status[f], st);
 }
+
+// One workgroup per frame of ONE segment (the others return at once), one lane per chunk of chunk_bytes raw bytes; a
+// frame with more chunks than lanes is done in windows of blockDim.x chunks, in order, each starting from the
+// converged exit of the one before.  Per window:
+//   relaxation  every lane scans its chunk from a guessed state (lane 0 from the true one); then rounds: read the
+//               left neighbour's exit, and scan again if it is not the entry this lane used.  A round in which no
+//               lane changed has reached the serial decoder's states; blockDim.x rounds always suffice.
+//   scan        exclusive prefix of blocks completed and DC sums over the lanes (Hillis-Steele in LDS)
+//   write       every lane decodes its chunk once more from its true state, to jc_decode_segment's addresses
+// Dynamic LDS: the descriptor's tables (JM_SEG words), per lane an exit state (2 words) and a scan element (4),
+// and the window's carry (8): split_lds_bytes().  Every barrier is on a workgroup-uniform path.
+__global__ __launch_bounds__(1024) void jpeg_entropy_split_kernel(const uint8_t* __restrict__ data, int data_len,
+                                                                  const int32_t* __restrict__ meta, int width,
+                                                                  int maxseg, int chunk_bytes, jc_geom g,
+                                                                  int16_t* __restrict__ coef,
+                                                                  int32_t* __restrict__ status) {
+  extern __shared__ int32_t split_lds[];
+  const int t = threadIdx.x, L = blockDim.x;
+  const long f = blockIdx.x;
+  const int32_t* m = meta + f * width;
+  if (jc_segment_count(m, width, maxseg) != 1) return;                     // uniform: jpeg_entropy_kernel's frame
+  int s0, s1, m0, m1;
+  if (!jc_segment_range(m, width, maxseg, data_len, 0, g, &s0, &s1, &m0, &m1)) return;
+  int32_t* tab = split_lds;                                                // quantisers and Huffman tables
+  int32_t* ex = tab + JM_SEG;                                              // [L][2] exit states
+  uint32_t* ps = reinterpret_cast<uint32_t*>(ex + 2 * L);                  // [L][4] blocks, DC sums
+  int32_t* carry = reinterpret_cast<int32_t*>(ps + 4 * L);                 // state (2), blocks, DC predictors (3)
+  for (int i = t; i < JM_SEG; i += L) tab[i] = m[i];
+  if (t == 0) {
+    carry[0] = s0;
+    carry[1] = carry[2] = carry[3] = carry[4] = carry[5] = 0;
+  }
+  __syncthreads();
+  const long nchunks = jc_chunk_count(s0, s1, chunk_bytes);
+  const uint32_t total = (uint32_t)((long)(m1 - m0) * g.mcu_blocks);
+  int16_t* dst = coef + f * (long)g.nblocks * 64;
+  int st = 0;
+  for (long w0 = 0; w0 < nchunks; w0 += L) {
+    const jc_state first = jc_state_unpack(carry[0], carry[1], g);
+    if (first.pos == JC_PAST) break;                                       // uniform: nothing but zero bits is left
+    const uint32_t block0 = (uint32_t)carry[2];
+    const uint32_t dc0[3] = {(uint32_t)carry[3], (uint32_t)carry[4], (uint32_t)carry[5]};
+    const bool live = w0 + t < nchunks;
+    const int cend = live ? jc_chunk_end(s0, s1, chunk_bytes, w0 + t) : s1;
+    jc_state in = t == 0 ? first : live ? jc_chunk_cold(data, s0, s1, chunk_bytes, w0 + t) : jc_state_past();
+    jc_state out = in;
+    int blocks = 0;
+    uint32_t dcs[3] = {0, 0, 0};
+    if (live) jc_chunk_scan(data, s1, cend, chunk_bytes, tab, g, in, &out, &blocks, dcs);
+    ex[2 * t] = out.pos;
+    ex[2 * t + 1] = jc_state_word(out);
+    __syncthreads();
+    for (int r = 0; r < L; ++r) {
+      int changed = 0;
+      jc_state left = in;
+      if (live && t > 0) {
+        left = jc_state_unpack(ex[2 * t - 2], ex[2 * t - 1], g);
+        changed = left.pos != in.pos || jc_state_word(left) != jc_state_word(in);
+      }
+      __syncthreads();                                                     // all have read the previous round's exits
+      if (changed) {
+        in = left;
+        jc_chunk_scan(data, s1, cend, chunk_bytes, tab, g, in, &out, &blocks, dcs);
+        ex[2 * t] = out.pos;
+        ex[2 * t + 1] = jc_state_word(out);
+      }
+      if (!__syncthreads_or(changed)) break;
+    }
+    uint32_t v[4] = {(uint32_t)blocks > total ? total : (uint32_t)blocks, dcs[0], dcs[1], dcs[2]};
+    for (int i = 0; i < 4; ++i) ps[4 * t + i] = v[i];
+    __syncthreads();
+    for (int d = 1; d < L; d <<= 1) {                                      // inclusive prefix
+      uint32_t a[4] = {0, 0, 0, 0};
+      if (t >= d)
+        for (int i = 0; i < 4; ++i) a[i] = ps[4 * (t - d) + i];
+      __syncthreads();
+      if (t >= d) {
+        v[0] = jc_blocks_add(a[0], v[0], total);
+        for (int i = 1; i < 4; ++i) v[i] += a[i];
+        for (int i = 0; i < 4; ++i) ps[4 * t + i] = v[i];
+      }
+      __syncthreads();
+    }
+    uint32_t e[4] = {0, 0, 0, 0};                                          // exclusive: the left neighbour's
+    if (t > 0)
+      for (int i = 0; i < 4; ++i) e[i] = ps[4 * (t - 1) + i];
+    if (live) {
+      const int dc[3] = {(int16_t)(dc0[0] + e[1]), (int16_t)(dc0[1] + e[2]), (int16_t)(dc0[2] + e[3])};
+      st |= jc_chunk_write(data, s1, cend, chunk_bytes, tab, g, in, (long)jc_blocks_add(block0, e[0], total), dc, m0,
+                           m1, dst);
+    }
+    __syncthreads();                                                       // the carry and the scan have been read
+    if (t == L - 1) {
+      carry[0] = out.pos;
+      carry[1] = jc_state_word(out);
+      carry[2] = (int32_t)jc_blocks_add(block0, v[0], total);
+      for (int i = 0; i < 3; ++i) carry[3 + i] = (int32_t)(dc0[i] + v[1 + i]);
+    }
+    __syncthreads();
+  }
+  if (st) atomicOr(&status[f], st);
+}
+
+size_t split_lds_bytes(int lanes) { return ((size_t)JM_SEG + 6 * (size_t)lanes + 8) * 4; }
 
 __global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restrict__ coef, long n, jc_geom g,
                                                         uint8_t* __restrict__ planes) {
@@ -121,9 +229,11 @@ extern "C" int coclr_jpeg_workspace(int H, int W, int ncomp, int hs, int vs, int
   return 0;
 }
 
-extern "C" int coclr_jpeg_decode(const uint8_t* data, int64_t data_len, const int32_t* meta, const int32_t* meta_host,
-                                 int F, int width, int H, int W, int ncomp, int hs, int vs, int stages, int16_t* coefs,
-                                 uint8_t* planes, uint8_t* out, int32_t* status, void* stream) {
+namespace {
+
+int jpeg_decode_impl(const uint8_t* data, int64_t data_len, const int32_t* meta, const int32_t* meta_host, int F,
+                     int width, int H, int W, int ncomp, int hs, int vs, int stages, int16_t* coefs, uint8_t* planes,
+                     uint8_t* out, int32_t* status, int chunk_bytes, void* stream) {
   if (!data || !meta || !meta_host || !coefs || !planes || !out || !status) return COCLR_EINVAL;
   if (F < 1 || width <= JM_SEG || data_len < 0 || data_len > 0x7fffffff || stages < 1 || stages > 7)
     return COCLR_EINVAL;
@@ -132,17 +242,40 @@ extern "C" int coclr_jpeg_decode(const uint8_t* data, int64_t data_len, const in
   jc_geom_init(g, H, W, ncomp, hs, vs);
   int maxseg = 1;
   if (!meta_ok(meta_host, F, width, data_len, g, &maxseg)) return COCLR_EINVAL;
+  if (chunk_bytes != 0 && (chunk_bytes < 8 || chunk_bytes > 65536)) return COCLR_EINVAL;
   const int groups = (W + 15) / 16;
   const long lanes1 = (long)F * maxseg, lanes2 = (long)F * g.nblocks, lanes3 = (long)F * H * groups;
   const long limit = 0x7fffffffL;        // workgroups of one launch
   if (lanes1 / 64 >= limit || lanes2 / 256 >= limit || lanes3 / 256 >= limit) return COCLR_EINVAL;
+  // who decodes what: frames of one segment go to the split kernel when chunk_bytes asks for it; its workgroup has
+  // a lane per chunk of the call's longest such frame, up to 1024
+  long single = 0, most_chunks = 1;
+  if (chunk_bytes)
+    for (int f = 0; f < F; ++f) {
+      const int32_t* m = meta_host + (long)f * width;
+      int s0, s1, m0, m1;
+      if (jc_segment_count(m, width, maxseg) != 1 ||
+          !jc_segment_range(m, width, maxseg, (int)data_len, 0, g, &s0, &s1, &m0, &m1))
+        continue;
+      ++single;
+      const long n = jc_chunk_count(s0, s1, chunk_bytes);
+      if (n > most_chunks) most_chunks = n;
+    }
   hipStream_t s = (hipStream_t)stream;
   if (stages & 1) {
     COCLR_RETURN_IF(hipMemsetAsync(coefs, 0, (size_t)F * g.nblocks * 128, s));
     COCLR_RETURN_IF(hipMemsetAsync(status, 0, (size_t)F * 4, s));
-    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(cdiv(lanes1, 64)), dim3(64), 0, s, data, (int)data_len, meta, width,
-                       F, maxseg, g, coefs, status);
-    COCLR_LAUNCH_CHECK();
+    if (single < F) {
+      hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(cdiv(lanes1, 64)), dim3(64), 0, s, data, (int)data_len, meta, width,
+                         F, maxseg, single > 0 ? 1 : 0, g, coefs, status);
+      COCLR_LAUNCH_CHECK();
+    }
+    if (single > 0) {
+      const int lanes = most_chunks > 1024 ? 1024 : (int)((most_chunks + 63) / 64 * 64);
+      hipLaunchKernelGGL(jpeg_entropy_split_kernel, dim3(F), dim3(lanes), split_lds_bytes(lanes), s, data,
+                         (int)data_len, meta, width, maxseg, chunk_bytes, g, coefs, status);
+      COCLR_LAUNCH_CHECK();
+    }
   }
   if (stages & 2) {
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3(cdiv(lanes2, 256)), dim3(256), 0, s, coefs, lanes2, g, planes);
@@ -155,4 +288,21 @@ extern "C" int coclr_jpeg_decode(const uint8_t* data, int64_t data_len, const in
     COCLR_LAUNCH_CHECK();
   }
   return 0;
+}
+
+}  // namespace
+
+extern "C" int coclr_jpeg_decode(const uint8_t* data, int64_t data_len, const int32_t* meta, const int32_t* meta_host,
+                                 int F, int width, int H, int W, int ncomp, int hs, int vs, int stages, int16_t* coefs,
+                                 uint8_t* planes, uint8_t* out, int32_t* status, void* stream) {
+  return jpeg_decode_impl(data, data_len, meta, meta_host, F, width, H, W, ncomp, hs, vs, stages, coefs, planes, out,
+                          status, 0, stream);
+}
+
+extern "C" int coclr_jpeg_decode_split(const uint8_t* data, int64_t data_len, const int32_t* meta,
+                                       const int32_t* meta_host, int F, int width, int H, int W, int ncomp, int hs,
+                                       int vs, int stages, int16_t* coefs, uint8_t* planes, uint8_t* out,
+                                       int32_t* status, int chunk_bytes, void* stream) {
+  return jpeg_decode_impl(data, data_len, meta, meta_host, F, width, H, W, ncomp, hs, vs, stages, coefs, planes, out,
+                          status, chunk_bytes, stream);
 }

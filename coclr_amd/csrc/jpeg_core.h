@@ -182,11 +182,15 @@ JC_HD int jc_decode_segment(const uint8_t* data, int start, int end, const int32
 // Restart segment `seg` of the frame described by `m` (width words): its bytes [s0, s1) of the shared buffer of
 // data_len bytes and its MCUs [m0, m1).  The descriptor is NOT trusted (a kernel reads the device copy): every value
 // is clamped to the buffer, the descriptor's width, `maxseg` and the frame's MCU count.  False: no such segment.
+JC_HD int jc_segment_count(const int32_t* m, int width, int maxseg) {      // the clamped count: who decodes the frame
+  const int nseg = m[JM_NSEG];
+  const int room = width - JM_SEG < maxseg ? width - JM_SEG : maxseg;
+  return nseg < 1 ? 1 : nseg > room ? room : nseg;
+}
+
 JC_HD bool jc_segment_range(const int32_t* m, int width, int maxseg, int data_len, int seg, const jc_geom& g, int* s0,
                             int* s1, int* m0, int* m1) {
-  int nseg = m[JM_NSEG];
-  const int room = width - JM_SEG < maxseg ? width - JM_SEG : maxseg;
-  nseg = nseg < 1 ? 1 : nseg > room ? room : nseg;
+  const int nseg = jc_segment_count(m, width, maxseg);
   if (seg < 0 || seg >= nseg) return false;
   long lo = m[JM_OFF], hi = lo + (long)m[JM_LEN];
   lo = lo < 0 ? 0 : lo > data_len ? data_len : lo;
@@ -306,4 +310,240 @@ JC_HD long jc_block_samples(const jc_geom& g, int blk, long* stride) {
   const int by = i / g.bw[c], bx = i % g.bw[c];
   *stride = (long)g.bw[c] * 8;
   return (long)g.boff[c] * 64 + (long)by * 8 * *stride + bx * 8;
+}
+
+// ---- one restart-less segment on many lanes: chunks of raw bytes, decoded from guessed states until they agree ------
+// A segment's bytes [s0, s1) are cut into chunks of `chunk_bytes` RAW bytes; a symbol (a Huffman code and its extra
+// bits) belongs to the chunk that holds the raw byte of its first bit (the 00 of an FF 00 pair carries no bits).
+// Every chunk is scanned from a guessed entry state; each chunk's exit state then becomes the next chunk's entry and
+// the chunks whose entry changed are scanned again, until a round changes nothing.  Chunk 0 starts from the true
+// state, so after round r chunks 0..r hold the serial decoder's states, and a round without a change has reached
+// them everywhere: the result is jc_decode_segment's for ANY bytes, in at most as many rounds as there are chunks.
+// jpeg.hip's jpeg_entropy_split_kernel and tools/jpeg_split_check.cpp (host, under sanitizers) drive these functions.
+enum { JC_PAST = 0x7fffffff };   // jc_state.pos once the reader has hit `end` or a marker: only zero bits follow
+
+struct jc_state {                // the serial decoder at a symbol boundary, output position aside
+  int pos, bit;                  // raw byte that holds the next bit, and the bit within it (0 = the top one)
+  int blk, k;                    // block within the MCU (selects the component, so the tables); zigzag index
+};
+
+JC_HD jc_state jc_state_make(int pos, int bit, int blk, int k) {
+  jc_state s;
+  s.pos = pos; s.bit = bit; s.blk = blk; s.k = k;
+  return s;
+}
+
+JC_HD jc_state jc_state_past() { return jc_state_make(JC_PAST, 0, 0, 0); }
+
+// two words per state, as the kernel keeps them in LDS; states are equal iff their words are
+JC_HD int32_t jc_state_word(const jc_state& s) {
+  return (int32_t)((uint32_t)s.bit | (uint32_t)s.blk << 3 | (uint32_t)s.k << 8);
+}
+
+JC_HD jc_state jc_state_unpack(int32_t pos, int32_t word, const jc_geom& g) {
+  const int blk = (word >> 3) & 7;
+  return jc_state_make(pos, word & 7, blk < g.mcu_blocks ? blk : 0, (word >> 8) & 63);
+}
+
+// jc_bits that also knows which raw byte its next bit came from: per buffered byte one bit "was an FF 00 pair"
+// (newest byte = bit 0), and the count of zero bytes pushed behind the end of the real bits (always the newest).
+struct jc_cbits : jc_bits {
+  uint32_t stuffed;
+  int npad;
+};
+
+JC_HD void jc_cfill(jc_cbits& b) {                 // the bit stream of jc_fill, byte for byte
+  while (b.n <= 56) {
+    uint32_t c = 0, s = 0;
+    bool real = !b.stopped && b.pos < b.end;
+    if (real) {
+      c = b.p[b.pos];
+      if (c == 0xFF) {
+        if (b.pos + 1 < b.end && b.p[b.pos + 1] == 0) {
+          s = 1;
+        } else {
+          b.stopped = 1;
+          real = false;
+          c = 0;
+        }
+      }
+    }
+    if (real) b.pos += 1 + (int)s;
+    else if (b.npad < 8) ++b.npad;
+    b.stuffed = b.stuffed << 1 | s;
+    b.buf |= (uint64_t)c << (56 - b.n);
+    b.n += 8;
+  }
+}
+
+JC_HD void jc_cbits_init(jc_cbits& b, const uint8_t* p, const jc_state& s, int end) {
+  jc_bits_init(b, p, s.pos, end);
+  b.stuffed = 0;
+  b.npad = 0;
+  jc_cfill(b);
+  if (s.bit) jc_take(b, s.bit);
+}
+
+// raw byte of the next bit, JC_PAST when that bit is padding; call after jc_cfill (then 57..64 bits are buffered)
+JC_HD int jc_cbits_pos(const jc_cbits& b, int* bit) {
+  const int nb = (b.n + 7) >> 3;
+  *bit = (8 - (b.n & 7)) & 7;
+  if (nb <= b.npad) return JC_PAST;
+  const uint32_t pairs = b.stuffed & ((1u << nb) - 1u);
+  int cnt = 0;
+  for (uint32_t v = pairs; v; v &= v - 1) ++cnt;
+  return b.pos - (nb - b.npad) - cnt;
+}
+
+// One symbol at zigzag index k of a block of component `comp`, exactly as jc_decode_segment reads it: the next k
+// (64: the block is complete), the zigzag index *at the value *val belongs to (0: a DC difference, -1: none).
+JC_HD int jc_symbol(const int32_t* meta, jc_cbits& b, int comp, int k, int* at, int* val, int* status) {
+  if (k == 0) {
+    const int t = jc_huff(meta + JM_HUFF + comp * JM_HUFF_WORDS, b, status) & 15;
+    *val = t ? jc_extend(b, t) : 0;
+    *at = 0;
+    return 1;
+  }
+  const int rs = jc_huff(meta + JM_HUFF + (3 + comp) * JM_HUFF_WORDS, b, status);
+  const int r = rs >> 4, s = rs & 15;
+  *at = -1;
+  *val = 0;
+  if (s == 0) {
+    k = r == 15 ? k + 16 : 64;
+  } else {
+    k += r;
+    if (k > 63) {
+      *status |= JC_BAD_RUN;
+      k = 63;
+    }
+    *at = k;
+    *val = jc_extend(b, s);
+    ++k;
+  }
+  return k >= 64 ? 64 : k;
+}
+
+JC_HD long jc_chunk_count(int s0, int s1, int chunk_bytes) {       // at least one: an empty segment still decodes
+  const long n = ((long)s1 - s0 + chunk_bytes - 1) / chunk_bytes;
+  return n < 1 ? 1 : n;
+}
+
+JC_HD int jc_chunk_end(int s0, int s1, int chunk_bytes, long i) {
+  const long e = s0 + (i + 1) * chunk_bytes;
+  return e > s1 ? s1 : (int)e;
+}
+
+// the guess a chunk is first scanned from: bit 0 of its first byte (behind the 00 of an FF 00 pair), block 0, k = 0;
+// for chunk 0 this is the true state
+JC_HD jc_state jc_chunk_cold(const uint8_t* data, int s0, int s1, int chunk_bytes, long i) {
+  long c = s0 + i * chunk_bytes;
+  c = c > s1 ? s1 : c;
+  if (i > 0 && c < s1 && data[c] == 0 && data[c - 1] == 0xFF) ++c;
+  return jc_state_make((int)c, 0, 0, 0);
+}
+
+JC_HD int jc_block_comp(const jc_geom& g, int blk) {
+  const int luma = g.ncomp == 1 ? 1 : g.hs * g.vs;
+  return blk < luma ? 0 : blk - luma + 1;
+}
+
+// The symbols that chunk [.., cend) owns, read from entry state `in` (bytes up to `end`, the segment's): the state at
+// the first symbol of a later chunk, the blocks completed and, per component, the sum of the DC differences
+// (mod 2^16 it is what the serial decoder's int16 predictor gains).  At most 8 * chunk_bytes + 1 symbols.  No status:
+// a guessed state meets invalid codes that the real decode never sees.
+JC_HD void jc_chunk_scan(const uint8_t* data, int end, int cend, int chunk_bytes, const int32_t* meta, const jc_geom& g,
+                         const jc_state& in, jc_state* out, int* blocks, uint32_t* dcsum) {
+  *out = in;
+  *blocks = 0;
+  dcsum[0] = dcsum[1] = dcsum[2] = 0;
+  if (in.pos == JC_PAST) return;
+  jc_cbits b;
+  jc_cbits_init(b, data, in, end);
+  int blk = in.blk, k = in.k, ignored = 0;
+  const long iters = 8L * chunk_bytes + 1;
+  for (long it = 0; it < iters; ++it) {
+    jc_cfill(b);
+    int bit;
+    const int pos = jc_cbits_pos(b, &bit);
+    if (pos == JC_PAST) break;
+    if (pos >= cend) {
+      *out = jc_state_make(pos, bit, blk, k);
+      return;
+    }
+    const int comp = jc_block_comp(g, blk);
+    int at, val;
+    const int next = jc_symbol(meta, b, comp, k, &at, &val, &ignored);
+    if (k == 0) dcsum[comp] += (uint32_t)val;
+    k = next;
+    if (k == 64) {
+      k = 0;
+      ++*blocks;
+      if (++blk >= g.mcu_blocks) blk = 0;
+    }
+  }
+  *out = jc_state_past();
+}
+
+// The same symbols, written: `in` is the chunk's TRUE entry state, `block` the blocks of the segment completed before
+// it and dc_in the three DC predictors there.  Coefficients land at jc_decode_segment's addresses with its values
+// (coef zero-filled by the caller); the status bits of the owned symbols are returned.  The chunk whose symbols reach
+// the end of the real bits carries on over zero bits to the segment's last MCU, as the serial decoder does; a chunk
+// entered behind that point writes nothing.  Every store lands inside a block of MCUs [m0, m1).
+JC_HD int jc_chunk_write(const uint8_t* data, int end, int cend, int chunk_bytes, const int32_t* meta, const jc_geom& g,
+                         const jc_state& in, long block, const int* dc_in, int m0, int m1, int16_t* coef) {
+  const long total = (long)(m1 - m0) * g.mcu_blocks;
+  if (in.pos == JC_PAST || block < 0 || block >= total) return 0;
+  jc_cbits b;
+  jc_cbits_init(b, data, in, end);
+  int status = 0;
+  int dc[3] = {dc_in[0], dc_in[1], dc_in[2]};
+  int mcu = m0 + (int)(block / g.mcu_blocks), blk = (int)(block % g.mcu_blocks), k = in.k, comp = 0;
+  int16_t* dst = coef;
+  const int32_t* q = meta + JM_QUANT;
+  bool tail = false, place = true;
+  const long iters = 8L * chunk_bytes + 1 + (total - block) * 64;
+  for (long it = 0; it < iters && mcu < m1; ++it) {
+    jc_cfill(b);
+    if (!tail) {
+      int bit;
+      const int pos = jc_cbits_pos(b, &bit);
+      if (pos == JC_PAST) tail = true;
+      else if (pos >= cend) break;
+    }
+    if (place) {
+      comp = jc_block_comp(g, blk);
+      const int mx = mcu % g.mcux, my = mcu / g.mcux;
+      const int bx = comp == 0 ? mx * g.hs + blk % g.hs : mx;
+      const int by = comp == 0 ? my * g.vs + blk / g.hs : my;
+      dst = coef + ((long)g.boff[comp] + (long)by * g.bw[comp] + bx) * 64;
+      q = meta + JM_QUANT + comp * 64;
+      place = false;
+    }
+    int at, val;
+    const int next = jc_symbol(meta, b, comp, k, &at, &val, &status);
+    if (k == 0) {
+      dc[comp] = (int16_t)(dc[comp] + val);
+      dst[0] = (int16_t)(dc[comp] * (q[0] & 0xFFFF));
+    } else if (at >= 0) {
+      const int n = jc_zigzag(at);
+      dst[n] = (int16_t)(val * (q[n] & 0xFFFF));
+    }
+    k = next;
+    if (k == 64) {
+      k = 0;
+      place = true;
+      if (++blk >= g.mcu_blocks) {
+        blk = 0;
+        ++mcu;
+      }
+    }
+  }
+  return status;
+}
+
+// what the chunks of one window are summed with, in the kernel's scan and on the host alike: block counts saturate at
+// the segment's block count (a stream may hold more symbols than the frame has room for), DC sums wrap
+JC_HD uint32_t jc_blocks_add(uint32_t a, uint32_t b, uint32_t total) {
+  const uint32_t s = (a > total ? total : a) + (b > total ? total : b);
+  return s > total ? total : s;
 }

@@ -12,8 +12,14 @@ luma sampled 1x1, 2x1 or 2x2, optional restart intervals -- what ffmpeg, cv2.imw
 Anything else is refused by `parse` on the host with `Unsupported` (a ValueError naming the reason) before a byte is
 uploaded, so a caller can fall back to PIL for that video.
 
-The entropy stage is serial inside a restart segment: a frame WITHOUT restart markers is decoded by one GPU lane
-(64 frames per wave); with markers every segment is a lane of its own."""
+The entropy stage is serial inside a restart segment; with markers every segment is a lane of its own.  A frame
+WITHOUT restart markers is one GPU lane (64 frames per wave) on the serial path, `chunk_bytes=0`, or one workgroup with
+a lane per chunk of `chunk_bytes` raw bytes: every chunk is decoded from a guessed state and decoded again while its
+predecessor's exit state differs from the entry it used, which ends in the serial decoder's own states, so the
+frames, `status` and `last_status` are the same bit for bit.  `chunk_bytes=None` takes the policy from the
+environment, read per call: COCLR_JPEG_SPLIT=0 serial, =n that chunk size (8..65536); unset is DEFAULT_SPLIT."""
+import os
+
 import numpy as np
 import torch
 
@@ -22,6 +28,7 @@ from . import ops
 META_QUANT, META_HUFF, HUFF_WORDS = 16, 208, 96
 META_SEG = META_HUFF + 6 * HUFF_WORDS           # csrc/jpeg_core.h: JM_*
 MAX_SIDE = 8192
+DEFAULT_SPLIT = 64                               # chunk size when COCLR_JPEG_SPLIT is unset
 
 _SOF_NAMES = {0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)", 0xC5: "differential sequential (SOF5)",
               0xC6: "differential progressive (SOF6)", 0xC7: "differential lossless (SOF7)",
@@ -317,13 +324,41 @@ def check_meta(data, meta):
     return H, W, ncomp, hs, vs
 
 
-def decode(data, meta, out=None, device=None, max_stage_bytes=256 << 20, return_status=False):
+def split_policy(chunk_bytes=None):
+    """The chunk size of a decode call: `chunk_bytes` if given, else COCLR_JPEG_SPLIT, else DEFAULT_SPLIT.  0 is the
+    serial path; anything but 0 or 8..65536 is a ValueError."""
+    what = "chunk_bytes"
+    if chunk_bytes is None:
+        text = os.environ.get("COCLR_JPEG_SPLIT")
+        if text is None or text.strip() == "":
+            return DEFAULT_SPLIT
+        what = "COCLR_JPEG_SPLIT"
+        try:
+            chunk_bytes = int(text)
+        except ValueError:
+            raise ValueError("coclr_amd: COCLR_JPEG_SPLIT must be 0 or a chunk size in 8..65536, got %r" % text)
+    try:
+        whole = not isinstance(chunk_bytes, bool) and int(chunk_bytes) == chunk_bytes
+    except (TypeError, ValueError):
+        whole = False
+    if not whole:
+        raise ValueError("coclr_amd: %s must be an integer, got %r" % (what, chunk_bytes))
+    chunk_bytes = int(chunk_bytes)
+    if chunk_bytes != 0 and not 8 <= chunk_bytes <= 65536:
+        raise ValueError("coclr_amd: %s must be 0 or a chunk size in 8..65536, got %d" % (what, chunk_bytes))
+    return chunk_bytes
+
+
+def decode(data, meta, out=None, device=None, max_stage_bytes=256 << 20, return_status=False, chunk_bytes=None):
     """(data, meta) of pack / cat -> (F, H, W, 3) uint8 on the device, the bytes PIL's convert('RGB') returns.
     A bad `meta` is refused on the host; the bytes are uploaded once; whole frames are decoded `max_stage_bytes` of
     intermediate storage (coefficients + sample planes) at a time.  `out`: a contiguous (F, H, W, 3) uint8 device
     tensor to fill (a view into a larger buffer will do).  The per-frame int32 status (0 = clean; 1: a bit pattern
     that is no Huffman code, 2: a run past the block -- a damaged file) is returned with return_status=True and
-    kept in `decode.last_status` otherwise."""
+    kept in `decode.last_status` otherwise.  `chunk_bytes`: how frames without restart markers are entropy-decoded
+    (module docstring): 0 one lane per frame, 8..65536 one lane per chunk of that many bytes, None the policy of
+    COCLR_JPEG_SPLIT; the result does not depend on it."""
+    chunk_bytes = split_policy(chunk_bytes)
     H, W, ncomp, hs, vs = check_meta(data, meta)
     F = meta.shape[0]
     if device is None:
@@ -342,7 +377,8 @@ def decode(data, meta, out=None, device=None, max_stage_bytes=256 << 20, return_
     status = torch.empty(F, dtype=torch.int32, device=device)
     for k in range(0, F, per):
         e = min(F, k + per)
-        ops.jpeg_decode(d_data, d_meta[k:e], host[k:e], H, W, ncomp, hs, vs, coefs, planes, out[k:e], status[k:e])
+        ops.jpeg_decode(d_data, d_meta[k:e], host[k:e], H, W, ncomp, hs, vs, coefs, planes, out[k:e], status[k:e],
+                        chunk_bytes=chunk_bytes)
     decode.last_status = status
     return (out, status) if return_status else out
 
@@ -350,7 +386,8 @@ def decode(data, meta, out=None, device=None, max_stage_bytes=256 << 20, return_
 decode.last_status = None
 
 
-def decode_frames(raws, out=None, device=None, max_stage_bytes=256 << 20):
+def decode_frames(raws, out=None, device=None, max_stage_bytes=256 << 20, chunk_bytes=None):
     """pack followed by decode: JPEG files of one size and sampling -> (F, H, W, 3) uint8 on the device."""
+    chunk_bytes = split_policy(chunk_bytes)
     data, meta = pack(raws)
-    return decode(data, meta, out=out, device=device, max_stage_bytes=max_stage_bytes)
+    return decode(data, meta, out=out, device=device, max_stage_bytes=max_stage_bytes, chunk_bytes=chunk_bytes)

@@ -1138,10 +1138,15 @@ def jpeg_workspace(H, W, ncomp, hs, vs):
     return a.value, b.value
 
 
-def jpeg_decode(data, meta, meta_host, H, W, ncomp, hs, vs, coefs, planes, out, status, stages=7):
+def jpeg_decode(data, meta, meta_host, H, W, ncomp, hs, vs, coefs, planes, out, status, stages=7, chunk_bytes=0):
     """data uint8 (n,), meta int32 (F, width) on the device and meta_host, the same on the host (include/coclr_hip.h:
     coclr_jpeg_decode) -> out uint8 (F, H, W, 3), status int32 (F,).  coefs int16 / planes uint8: flat workspaces of
-    F times jpeg_workspace().  `stages`: 1 entropy, 2 inverse DCT, 4 colour; 7 = all three."""
+    F times jpeg_workspace().  `stages`: 1 entropy, 2 inverse DCT, 4 colour; 7 = all three.  `chunk_bytes`: 0, or
+    8..65536 to decode frames without restart markers on a lane per chunk of that many bytes
+    (coclr_jpeg_decode_split); the results are the same bit for bit."""
+    chunk_bytes = int(chunk_bytes)
+    if chunk_bytes != 0 and not 8 <= chunk_bytes <= 65536:
+        raise ValueError("coclr_amd: chunk_bytes must be 0 or in 8..65536, got %d" % chunk_bytes)
     if meta.dim() != 2 or meta.shape != meta_host.shape or meta_host.is_cuda or meta_host.dtype != torch.int32 or \
             not meta.is_contiguous() or not meta_host.is_contiguous():
         raise ValueError("coclr_amd: frame descriptors must be contiguous int32 (F, width), device and host")
@@ -1154,10 +1159,14 @@ def jpeg_decode(data, meta, meta_host, H, W, ncomp, hs, vs, coefs, planes, out, 
         raise ValueError("coclr_amd: out must be contiguous %s, got %s" % ((F, H, W, 3), tuple(out.shape)))
     if tuple(status.shape) != (F,) or not status.is_contiguous():
         raise ValueError("coclr_amd: status must be contiguous (%d,), got %s" % (F, tuple(status.shape)))
-    _lib.check(_L().coclr_jpeg_decode(
-        _p(data, torch.uint8), data.numel(), _p(meta, torch.int32), C.cast(meta_host.data_ptr(), C.POINTER(C.c_int32)),
-        F, width, int(H), int(W), int(ncomp), int(hs), int(vs), int(stages), _p(coefs, torch.int16),
-        _p(planes, torch.uint8), _p(out, torch.uint8), _p(status, torch.int32), _stream()), "jpeg_decode")
+    args = (_p(data, torch.uint8), data.numel(), _p(meta, torch.int32),
+            C.cast(meta_host.data_ptr(), C.POINTER(C.c_int32)), F, width, int(H), int(W), int(ncomp), int(hs), int(vs),
+            int(stages), _p(coefs, torch.int16), _p(planes, torch.uint8), _p(out, torch.uint8),
+            _p(status, torch.int32))
+    if chunk_bytes:
+        _lib.check(_L().coclr_jpeg_decode_split(*args, chunk_bytes, _stream()), "jpeg_decode_split")
+    else:
+        _lib.check(_L().coclr_jpeg_decode(*args, _stream()), "jpeg_decode")
 
 
 def _program_call(name, frames, kinds, params, group_size, T, mean, std, out, host_tables):

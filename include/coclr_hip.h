@@ -728,8 +728,9 @@ int coclr_jpeg_workspace(int H, int W, int ncomp, int hs, int vs, int64_t* coef_
  *   bounds -- reads inside data, stores inside the frame's own storage, loops bounded by the block count -- whatever
  *   the device copy and the bytes hold.  Past the end of its bytes a frame reads zero bits, as libjpeg pads.
  * stages: bit mask of what to launch, in order: 1 entropy (zero-fills coefs and status, then one lane per (frame,
- *   restart segment): a frame without restart markers is decoded by ONE lane), 2 inverse DCT (one lane per block,
- *   coefs -> planes), 4 upsampling + colour + crop (planes -> out).  7 decodes; the parts exist to be timed.
+ *   restart segment): here a frame without restart markers is one lane; coclr_jpeg_decode_split below gives it a
+ *   workgroup), 2 inverse DCT (one lane per block, coefs -> planes), 4 upsampling + colour + crop (planes -> out).
+ *   7 decodes; the parts exist to be timed.
  * coefs / planes: F times the workspace sizes, 16-byte aligned.  out: uint8 [F][H][W][3].
  * status: int32 [F], 0 = clean; bit 0 a bit pattern that is no Huffman code (decoded as 0), bit 1 a zero run past
  *   the 64th coefficient.
@@ -741,6 +742,20 @@ int coclr_jpeg_workspace(int H, int W, int ncomp, int hs, int vs, int64_t* coef_
 int coclr_jpeg_decode(const uint8_t* data, int64_t data_len, const int32_t* meta, const int32_t* meta_host, int F,
                       int width, int H, int W, int ncomp, int hs, int vs, int stages, int16_t* coefs,
                       uint8_t* planes, uint8_t* out, int32_t* status, void* stream);
+/* coclr_jpeg_decode with intra-frame parallel Huffman decoding for the frames of ONE restart segment (no restart
+ * markers: what ffmpeg, cv2.imwrite and PIL write by default).  chunk_bytes == 0 is exactly coclr_jpeg_decode.
+ * 8 <= chunk_bytes <= 65536: such a frame is one workgroup, one lane per chunk of chunk_bytes raw bytes (up to 1024
+ * lanes, sized by the call's longest frame; longer frames take several windows of chunks in order).  Every chunk is
+ * decoded from a guessed state, each chunk's exit state becomes the next chunk's entry, and chunks whose entry
+ * changed are decoded again until nothing changes: chunk 0 starts from the true state, so this reaches the serial
+ * decoder's states for ANY bytes in at most as many rounds as there are chunks, and coefs, out and status are
+ * bit for bit those of coclr_jpeg_decode.  Frames WITH restart markers keep the lane per segment of
+ * coclr_jpeg_decode in the same call.  No workspace beyond coclr_jpeg_decode's; the same bounds hold.
+ * COCLR_EINVAL before any launch: everything coclr_jpeg_decode refuses; chunk_bytes other than 0 or 8..65536.
+ * Additive: the ABI number stays 25 -- no existing signature or behaviour changed. */
+int coclr_jpeg_decode_split(const uint8_t* data, int64_t data_len, const int32_t* meta, const int32_t* meta_host,
+                            int F, int width, int H, int W, int ncomp, int hs, int vs, int stages, int16_t* coefs,
+                            uint8_t* planes, uint8_t* out, int32_t* status, int chunk_bytes, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Evaluation consumers (model/classifier.py:47-61; eval/main_classifier.py) */
