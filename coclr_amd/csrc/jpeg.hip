@@ -16,20 +16,95 @@ namespace {
 
 constexpr int JPEG_MAX_SIDE = 8192;
 
+// Where a kernel gets a frame's geometry and storage from.  one_geom: the call's single geometry, by value, frame f
+// at f times the per-frame sizes (coclr_jpeg_decode, coclr_jpeg_decode_split); the kernels read it where it lies, in
+// the kernel arguments (a copy would cost LDS or scratch: it is indexed by component), and `store` is empty.
+// ragged_geom: per frame from the device table of coclr_jpeg_decode_ragged, built into the caller's `store`; a lane
+// finds its frame by binary search over the prefix of lane counts.  False: skip.
+// frame():  frame f -> its first block and first output byte
+// block():  lane id of the inverse DCT -> its frame's first block, and the block within the frame
+// group():  lane id of the colour stage -> first block, the frame's first output byte, row and row group
+// geom():   the geometry these found
+struct one_geom {
+  static constexpr bool ragged = false;
+  struct store {};
+  jc_geom g;
+  __device__ const jc_geom& geom(const store&) const { return g; }
+  __device__ bool frame(long f, store&, long* cb, long* ob) const {
+    *cb = f * (long)g.nblocks;
+    *ob = f * (long)g.H * g.W * 3;
+    return true;
+  }
+  __device__ bool block(long id, store&, long* cb, int* blk) const {
+    const long f = id / g.nblocks;
+    *blk = (int)(id % g.nblocks);
+    *cb = f * (long)g.nblocks;
+    return true;
+  }
+  __device__ bool group(long id, int groups, store&, long* cb, long* ob, int* y, int* xg) const {
+    *xg = (int)(id % groups);
+    const long row = id / groups;
+    *y = (int)(row % g.H);
+    const long f = row / g.H;
+    *cb = f * (long)g.nblocks;
+    *ob = f * (long)g.H * g.W * 3;
+    return true;
+  }
+  __device__ bool vec_ok(const jc_geom&, long) const { return true; }
+};
+
+struct ragged_geom {
+  static constexpr bool ragged = true;
+  typedef jc_geom store;
+  const int64_t* tab;        // [F][JR_FIELDS]
+  const int64_t* blocks;     // [F + 1] prefix of blocks
+  const int64_t* rows;       // [F + 1] prefix of row groups
+  long F, coef_blocks, out_bytes;
+  __device__ const jc_geom& geom(const store& o) const { return o; }
+  __device__ bool frame(long f, store& o, long* cb, long* ob) const {
+    return jc_ragged_frame(tab, f, coef_blocks, out_bytes, JPEG_MAX_SIDE, o, cb, ob);
+  }
+  __device__ bool block(long id, store& o, long* cb, int* blk) const {
+    const long f = jc_find_frame(blocks, F, id);
+    long ob;
+    if (!frame(f, o, cb, &ob)) return false;
+    const long local = id - blocks[f];
+    if (local < 0 || local >= o.nblocks) return false;
+    *blk = (int)local;
+    return true;
+  }
+  __device__ bool group(long id, int, store& o, long* cb, long* ob, int* y, int* xg) const {
+    const long f = jc_find_frame(rows, F, id);
+    if (!frame(f, o, cb, ob)) return false;
+    const long local = id - rows[f];
+    if (local < 0 || local >= jc_row_groups(o)) return false;
+    const int groups = (o.W + 15) / 16;
+    *xg = (int)(local % groups);
+    *y = (int)(local / groups);
+    return true;
+  }
+  __device__ bool vec_ok(const jc_geom& g, long ob) const { return g.W % 16 == 0 && (ob & 15) == 0; }
+};
+
 // one wave per workgroup: with one lane per frame, 64 frames are all a CU gets, so the waves spread over the CUs
+template <class GS>
 __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restrict__ data, int data_len,
                                                           const int32_t* __restrict__ meta, int width, int F,
-                                                          int maxseg, int multi_only, jc_geom g,
+                                                          int maxseg, int multi_only, GS gs,
                                                           int16_t* __restrict__ coef, int32_t* __restrict__ status) {
   const long id = (long)blockIdx.x * 64 + threadIdx.x;
   const long f = id / maxseg;
   const int seg = (int)(id % maxseg);
   if (f >= F) return;
+  typename GS::store gst;
+  long cb, ob;
+  if (!gs.frame(f, gst, &cb, &ob)) return;
+  const jc_geom& g = gs.geom(gst);
   const int32_t* m = meta + f * width;
   if (multi_only && jc_segment_count(m, width, maxseg) == 1) return;      // jpeg_entropy_split_kernel's frames
   int s0, s1, m0, m1;
   if (!jc_segment_range(m, width, maxseg, data_len, seg, g, &s0, &s1, &m0, &m1)) return;
-  const int st = jc_decode_segment(data, s0, s1, m, g, m0, m1, coef + f * (long)g.nblocks * 64);
+  const int st = jc_decode_segment(data, s0, s1, m, g, m0, m1, coef + cb * 64);
   if (st) atomicOr(&status[f], st);
 }
 
@@ -43,14 +118,33 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
 //   write       every lane decodes its chunk once more from its true state, to jc_decode_segment's addresses
 // Dynamic LDS: the descriptor's tables (JM_SEG words), per lane an exit state (2 words) and a scan element (4),
 // and the window's carry (8): split_lds_bytes().  Every barrier is on a workgroup-uniform path.
+template <class GS>
 __global__ __launch_bounds__(1024) void jpeg_entropy_split_kernel(const uint8_t* __restrict__ data, int data_len,
                                                                   const int32_t* __restrict__ meta, int width,
-                                                                  int maxseg, int chunk_bytes, jc_geom g,
+                                                                  int maxseg, int chunk_bytes, GS gs,
                                                                   int16_t* __restrict__ coef,
                                                                   int32_t* __restrict__ status) {
   extern __shared__ int32_t split_lds[];
   const int t = threadIdx.x, L = blockDim.x;
   const long f = blockIdx.x;
+  // the whole workgroup is frame f: the ragged form builds its geometry once, in LDS, where the lanes can index it
+  const jc_geom* gp;
+  long cb, ob;
+  if constexpr (GS::ragged) {
+    __shared__ jc_geom frame_geom;
+    __shared__ long frame_cb;
+    __shared__ int frame_ok;
+    if (t == 0) frame_ok = gs.frame(f, frame_geom, &frame_cb, &ob);
+    __syncthreads();
+    if (!frame_ok) return;                                                 // uniform
+    gp = &frame_geom;
+    cb = frame_cb;
+  } else {
+    typename GS::store none;
+    gs.frame(f, none, &cb, &ob);
+    gp = &gs.geom(none);
+  }
+  const jc_geom& g = *gp;
   const int32_t* m = meta + f * width;
   if (jc_segment_count(m, width, maxseg) != 1) return;                     // uniform: jpeg_entropy_kernel's frame
   int s0, s1, m0, m1;
@@ -67,7 +161,7 @@ __global__ __launch_bounds__(1024) void jpeg_entropy_split_kernel(const uint8_t*
   __syncthreads();
   const long nchunks = jc_chunk_count(s0, s1, chunk_bytes);
   const uint32_t total = (uint32_t)((long)(m1 - m0) * g.mcu_blocks);
-  int16_t* dst = coef + f * (long)g.nblocks * 64;
+  int16_t* dst = coef + cb * 64;
   int st = 0;
   for (long w0 = 0; w0 < nchunks; w0 += L) {
     const jc_state first = jc_state_unpack(carry[0], carry[1], g);
@@ -137,34 +231,42 @@ __global__ __launch_bounds__(1024) void jpeg_entropy_split_kernel(const uint8_t*
 
 size_t split_lds_bytes(int lanes) { return ((size_t)JM_SEG + 6 * (size_t)lanes + 8) * 4; }
 
-__global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restrict__ coef, long n, jc_geom g,
+template <class GS>
+__global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restrict__ coef, long n, GS gs,
                                                         uint8_t* __restrict__ planes) {
   const long id = (long)blockIdx.x * 256 + threadIdx.x;
   if (id >= n) return;
-  const long f = id / g.nblocks;
-  const int blk = (int)(id % g.nblocks);
+  typename GS::store gst;
+  long cb;
+  int blk;
+  if (!gs.block(id, gst, &cb, &blk)) return;
+  const jc_geom& g = gs.geom(gst);
   __attribute__((aligned(16))) int16_t in[64];
-  const uint4* src = reinterpret_cast<const uint4*>(coef + id * 64);      // 128 bytes per block, 16-byte aligned
+  const uint4* src = reinterpret_cast<const uint4*>(coef + (cb + blk) * 64);   // 128 bytes per block, 16-byte aligned
 #pragma unroll
   for (int i = 0; i < 8; ++i) reinterpret_cast<uint4*>(in)[i] = src[i];
   long stride;
   const long at = jc_block_samples(g, blk, &stride);
-  jc_idct_block(in, planes + f * (long)g.nblocks * 64 + at, stride);
+  jc_idct_block(in, planes + cb * 64 + at, stride);
 }
 
-// vec: W % 16 == 0 and `out` 16-byte aligned, so every group of 16 pixels is three aligned 16-byte stores
+// vec: W % 16 == 0 and the frame's first byte 16-byte aligned, so every group of 16 pixels is three aligned 16-byte
+// stores.  One geometry: the host decides for the call (`aligned`).  Ragged: `aligned` says that `out` itself is,
+// and every frame answers for its own width and offset.
+template <class GS>
 __global__ __launch_bounds__(256) void jpeg_colour_kernel(const uint8_t* __restrict__ planes, long n, int groups,
-                                                          jc_geom g, int vec, uint8_t* __restrict__ out) {
+                                                          GS gs, int aligned, uint8_t* __restrict__ out) {
   const long id = (long)blockIdx.x * 256 + threadIdx.x;
   if (id >= n) return;
-  const int xg = (int)(id % groups);
-  const long row = id / groups;
-  const int y = (int)(row % g.H);
-  const long f = row / g.H;
-  const uint8_t* p = planes + f * (long)g.nblocks * 64;
-  uint8_t* o = out + (row * g.W + (long)xg * 16) * 3;
+  typename GS::store gst;
+  long cb, ob;
+  int y, xg;
+  if (!gs.group(id, groups, gst, &cb, &ob, &y, &xg)) return;
+  const jc_geom& g = gs.geom(gst);
+  const uint8_t* p = planes + cb * 64;
+  uint8_t* o = out + ob + ((long)y * g.W + (long)xg * 16) * 3;
   const int x0 = xg * 16;
-  if (vec) {
+  if (aligned && gs.vec_ok(g, ob)) {
     __attribute__((aligned(16))) uint8_t px[48];
 #pragma unroll
     for (int i = 0; i < 16; ++i) jc_pixel(p, g, x0 + i, y, px + 3 * i);
@@ -183,9 +285,7 @@ __global__ __launch_bounds__(256) void jpeg_colour_kernel(const uint8_t* __restr
 }
 
 bool geometry_ok(int H, int W, int ncomp, int hs, int vs) {
-  if (H < 1 || W < 1 || H > JPEG_MAX_SIDE || W > JPEG_MAX_SIDE) return false;
-  if (ncomp == 1) return hs == 1 && vs == 1;
-  return ncomp == 3 && ((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2));
+  return jc_geometry_ok(H, W, ncomp, hs, vs, JPEG_MAX_SIDE);
 }
 
 // what the kernels rely on, checked on the host copy of the descriptors
@@ -262,29 +362,30 @@ int jpeg_decode_impl(const uint8_t* data, int64_t data_len, const int32_t* meta,
       if (n > most_chunks) most_chunks = n;
     }
   hipStream_t s = (hipStream_t)stream;
+  const one_geom gs = {g};
   if (stages & 1) {
     COCLR_RETURN_IF(hipMemsetAsync(coefs, 0, (size_t)F * g.nblocks * 128, s));
     COCLR_RETURN_IF(hipMemsetAsync(status, 0, (size_t)F * 4, s));
     if (single < F) {
-      hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(cdiv(lanes1, 64)), dim3(64), 0, s, data, (int)data_len, meta, width,
-                         F, maxseg, single > 0 ? 1 : 0, g, coefs, status);
+      hipLaunchKernelGGL(jpeg_entropy_kernel<one_geom>, dim3(cdiv(lanes1, 64)), dim3(64), 0, s, data, (int)data_len,
+                         meta, width, F, maxseg, single > 0 ? 1 : 0, gs, coefs, status);
       COCLR_LAUNCH_CHECK();
     }
     if (single > 0) {
       const int lanes = most_chunks > 1024 ? 1024 : (int)((most_chunks + 63) / 64 * 64);
-      hipLaunchKernelGGL(jpeg_entropy_split_kernel, dim3(F), dim3(lanes), split_lds_bytes(lanes), s, data,
-                         (int)data_len, meta, width, maxseg, chunk_bytes, g, coefs, status);
+      hipLaunchKernelGGL(jpeg_entropy_split_kernel<one_geom>, dim3(F), dim3(lanes), split_lds_bytes(lanes), s, data,
+                         (int)data_len, meta, width, maxseg, chunk_bytes, gs, coefs, status);
       COCLR_LAUNCH_CHECK();
     }
   }
   if (stages & 2) {
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3(cdiv(lanes2, 256)), dim3(256), 0, s, coefs, lanes2, g, planes);
+    hipLaunchKernelGGL(jpeg_idct_kernel<one_geom>, dim3(cdiv(lanes2, 256)), dim3(256), 0, s, coefs, lanes2, gs, planes);
     COCLR_LAUNCH_CHECK();
   }
   if (stages & 4) {
     const int vec = W % 16 == 0 && ((uintptr_t)out & 15) == 0;
-    hipLaunchKernelGGL(jpeg_colour_kernel, dim3(cdiv(lanes3, 256)), dim3(256), 0, s, planes, lanes3, groups, g, vec,
-                       out);
+    hipLaunchKernelGGL(jpeg_colour_kernel<one_geom>, dim3(cdiv(lanes3, 256)), dim3(256), 0, s, planes, lanes3, groups,
+                       gs, vec, out);
     COCLR_LAUNCH_CHECK();
   }
   return 0;
@@ -305,4 +406,92 @@ extern "C" int coclr_jpeg_decode_split(const uint8_t* data, int64_t data_len, co
                                        int32_t* status, int chunk_bytes, void* stream) {
   return jpeg_decode_impl(data, data_len, meta, meta_host, F, width, H, W, ncomp, hs, vs, stages, coefs, planes, out,
                           status, chunk_bytes, stream);
+}
+
+// Frames of differing geometry in one call: the stages of jpeg_decode_impl with the geometry, the first coefficient
+// block and the first output byte per frame (jpeg_core.h: JR_*).  Everything is checked on the host copies first.
+extern "C" int coclr_jpeg_decode_ragged(const uint8_t* data, int64_t data_len, const int32_t* meta,
+                                        const int32_t* meta_host, int F, int width, const int64_t* geom,
+                                        const int64_t* geom_host, const int64_t* prefix, const int64_t* prefix_host,
+                                        int stages, int16_t* coefs, uint8_t* planes, int64_t coef_blocks, uint8_t* out,
+                                        int64_t out_bytes, int32_t* status, int chunk_bytes, void* stream) {
+  if (!data || !meta || !meta_host || !geom || !geom_host || !prefix || !prefix_host || !coefs || !planes || !out ||
+      !status)
+    return COCLR_EINVAL;
+  if (F < 1 || width <= JM_SEG || data_len < 0 || data_len > 0x7fffffff || stages < 1 || stages > 7)
+    return COCLR_EINVAL;
+  if (((uintptr_t)coefs & 15) || ((uintptr_t)planes & 15) || ((uintptr_t)out & 15) || ((uintptr_t)meta & 3) ||
+      ((uintptr_t)geom & 7) || ((uintptr_t)prefix & 7))
+    return COCLR_EINVAL;
+  if (coef_blocks < 1 || out_bytes < 1) return COCLR_EINVAL;
+  if (chunk_bytes != 0 && (chunk_bytes < 8 || chunk_bytes > 65536)) return COCLR_EINVAL;
+  const int64_t* pblocks = prefix_host;
+  const int64_t* prows = prefix_host + F + 1;
+  if (pblocks[0] != 0 || prows[0] != 0) return COCLR_EINVAL;
+  int maxseg = 1;
+  long single = 0, most_chunks = 1, cend = 0, oend = 0;
+  for (int f = 0; f < F; ++f) {
+    const int64_t* t = geom_host + (long)f * JR_FIELDS;
+    if (!jc_geometry_ok(t[JR_H], t[JR_W], t[JR_NCOMP], t[JR_HS], t[JR_VS], JPEG_MAX_SIDE)) return COCLR_EINVAL;
+    jc_geom g;
+    jc_geom_init(g, (int)t[JR_H], (int)t[JR_W], (int)t[JR_NCOMP], (int)t[JR_HS], (int)t[JR_VS]);
+    // storage: in frame order, no overlap, inside the buffers; an output frame starts 16-byte aligned
+    const long cb = t[JR_CBLOCK], ob = t[JR_OBYTE];
+    if (cb < cend || cb > coef_blocks - g.nblocks) return COCLR_EINVAL;
+    if (ob < oend || (ob & 15) || ob > out_bytes - (long)g.H * g.W * 3) return COCLR_EINVAL;
+    cend = cb + g.nblocks;
+    oend = ob + (long)g.H * g.W * 3;
+    if (pblocks[f + 1] - pblocks[f] != g.nblocks || prows[f + 1] - prows[f] != jc_row_groups(g)) return COCLR_EINVAL;
+    const int32_t* m = meta_host + (long)f * width;
+    int segs = 1;
+    if (!meta_ok(m, 1, width, data_len, g, &segs)) return COCLR_EINVAL;
+    if (segs > maxseg) maxseg = segs;
+  }
+  // who decodes what, as in jpeg_decode_impl; maxseg is the call's, as the kernels clamp with it
+  if (chunk_bytes)
+    for (int f = 0; f < F; ++f) {
+      const int64_t* t = geom_host + (long)f * JR_FIELDS;
+      jc_geom g;
+      jc_geom_init(g, (int)t[JR_H], (int)t[JR_W], (int)t[JR_NCOMP], (int)t[JR_HS], (int)t[JR_VS]);
+      const int32_t* m = meta_host + (long)f * width;
+      int s0, s1, m0, m1;
+      if (jc_segment_count(m, width, maxseg) != 1 ||
+          !jc_segment_range(m, width, maxseg, (int)data_len, 0, g, &s0, &s1, &m0, &m1))
+        continue;
+      ++single;
+      const long n = jc_chunk_count(s0, s1, chunk_bytes);
+      if (n > most_chunks) most_chunks = n;
+    }
+  const long lanes1 = (long)F * maxseg, lanes2 = pblocks[F], lanes3 = prows[F];
+  const long limit = 0x7fffffffL;        // workgroups of one launch
+  if (lanes1 / 64 >= limit || lanes2 / 256 >= limit || lanes3 / 256 >= limit) return COCLR_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const ragged_geom gs = {geom, prefix, prefix + F + 1, F, coef_blocks, out_bytes};
+  if (stages & 1) {
+    const long first = geom_host[JR_CBLOCK];
+    COCLR_RETURN_IF(hipMemsetAsync(coefs + first * 64, 0, (size_t)(cend - first) * 128, s));
+    COCLR_RETURN_IF(hipMemsetAsync(status, 0, (size_t)F * 4, s));
+    if (single < F) {
+      hipLaunchKernelGGL(jpeg_entropy_kernel<ragged_geom>, dim3(cdiv(lanes1, 64)), dim3(64), 0, s, data, (int)data_len,
+                         meta, width, F, maxseg, single > 0 ? 1 : 0, gs, coefs, status);
+      COCLR_LAUNCH_CHECK();
+    }
+    if (single > 0) {
+      const int lanes = most_chunks > 1024 ? 1024 : (int)((most_chunks + 63) / 64 * 64);
+      hipLaunchKernelGGL(jpeg_entropy_split_kernel<ragged_geom>, dim3(F), dim3(lanes), split_lds_bytes(lanes), s, data,
+                         (int)data_len, meta, width, maxseg, chunk_bytes, gs, coefs, status);
+      COCLR_LAUNCH_CHECK();
+    }
+  }
+  if (stages & 2) {
+    hipLaunchKernelGGL(jpeg_idct_kernel<ragged_geom>, dim3(cdiv(lanes2, 256)), dim3(256), 0, s, coefs, lanes2, gs,
+                       planes);
+    COCLR_LAUNCH_CHECK();
+  }
+  if (stages & 4) {
+    hipLaunchKernelGGL(jpeg_colour_kernel<ragged_geom>, dim3(cdiv(lanes3, 256)), dim3(256), 0, s, planes, lanes3, 0, gs,
+                       1, out);
+    COCLR_LAUNCH_CHECK();
+  }
+  return 0;
 }

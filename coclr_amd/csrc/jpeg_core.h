@@ -547,3 +547,45 @@ JC_HD uint32_t jc_blocks_add(uint32_t a, uint32_t b, uint32_t total) {
   const uint32_t s = (a > total ? total : a) + (b > total ? total : b);
   return s > total ? total : s;
 }
+
+// ---- frames of differing geometry in one call (coclr_jpeg_decode_ragged) ---------------------------------------------
+// Per frame JR_FIELDS int64 words; `prefix` arrays of F + 1 words hold the lanes (blocks, or row groups of 16 pixels)
+// of all frames before each one.  Both are device data to a kernel: nothing read from them is trusted.
+enum { JR_H = 0, JR_W, JR_NCOMP, JR_HS, JR_VS, JR_CBLOCK, JR_OBYTE, JR_FIELDS = 8 };
+
+// The frame lane `id` belongs to: the last f in [0, F) with prefix[f] <= id (0 when there is none).  The result is a
+// valid frame whatever `prefix` holds; the caller checks id - prefix[f] against the frame's own lane count, which
+// also turns away ids past the end.
+JC_HD long jc_find_frame(const int64_t* prefix, long F, long id) {
+  long lo = 0, hi = F - 1;
+  while (lo < hi) {
+    const long mid = lo + (hi - lo + 1) / 2;
+    if (prefix[mid] <= id) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+JC_HD bool jc_geometry_ok(long H, long W, long ncomp, long hs, long vs, long max_side) {
+  if (H < 1 || W < 1 || H > max_side || W > max_side) return false;
+  if (ncomp == 1) return hs == 1 && vs == 1;
+  return ncomp == 3 && ((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2));
+}
+
+// Frame f of the table `tab`: its geometry, its first block in the coefficient / sample storage of coef_blocks blocks
+// and its first byte in the output of out_bytes bytes.  False (the frame is skipped) unless the geometry is one the
+// kernels take and both ranges lie inside their buffers, so every address derived from a frame that passes is inside.
+JC_HD bool jc_ragged_frame(const int64_t* tab, long f, long coef_blocks, long out_bytes, long max_side, jc_geom& g,
+                           long* cblock, long* obyte) {
+  const int64_t* t = tab + f * JR_FIELDS;
+  if (!jc_geometry_ok(t[JR_H], t[JR_W], t[JR_NCOMP], t[JR_HS], t[JR_VS], max_side)) return false;
+  jc_geom_init(g, (int)t[JR_H], (int)t[JR_W], (int)t[JR_NCOMP], (int)t[JR_HS], (int)t[JR_VS]);
+  const long cb = t[JR_CBLOCK], ob = t[JR_OBYTE];
+  if (cb < 0 || cb > coef_blocks - g.nblocks) return false;
+  if (ob < 0 || ob > out_bytes - (long)g.H * g.W * 3) return false;
+  *cblock = cb;
+  *obyte = ob;
+  return true;
+}
+
+JC_HD long jc_row_groups(const jc_geom& g) { return (long)g.H * ((g.W + 15) / 16); }   // colour lanes of a frame

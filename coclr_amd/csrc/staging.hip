@@ -191,24 +191,56 @@ stage_crops_kernel(const CropArgs a) {
 // whatever they hold nothing is out of bounds (the entry point validates the host copy before the launch).
 enum { BOX_FIRST = 0, BOX_FRAMES, BOX_X0, BOX_Y0, BOX_W, BOX_H, BOX_XOFF, BOX_YOFF, BOX_XTAPS, BOX_YTAPS, BOX_FIELDS };
 
+// The RAGGED forms of the two box kernels (coclr_resize_boxes_ragged_u8, coclr_resize2_boxes_ragged): the frames lie in
+// one flat byte buffer and differ in size from clip to clip.  A ragged descriptor is the plain one followed by
+// RAG_FIELDS words: the byte offset of the clip's first frame (64 bits, low word first) and the W and H of its frames,
+// which follow each other at W * H * 3 bytes rounded up to 16 (every frame starts aligned); `first` is not read.  The box is clamped to the clip's OWN frame, and a
+// clip whose T frames do not lie inside the buffer of `nbytes` is skipped, so nothing is read outside it.
+enum { RAG_OFF_LO = 0, RAG_OFF_HI, RAG_W, RAG_H, RAG_FIELDS };
+constexpr int kRagMaxSide = 32768;
+
+struct RagFrame { const uint8_t* base; int W, H; };
+
+template <bool RAGGED>
+__device__ __forceinline__ bool clip_frame(const uint8_t* frames, long nbytes, int F, int H, int W, const int32_t* d,
+                                           const int32_t* rag, int T, int t, RagFrame& o) {
+  if (RAGGED) {
+    o.W = clampi(rag[RAG_W], 1, kRagMaxSide);
+    o.H = clampi(rag[RAG_H], 1, kRagMaxSide);
+    const long fb = (long)o.W * o.H * 3, step = (fb + 15) & ~15L;
+    const long off = (long)(((unsigned long)(unsigned)rag[RAG_OFF_HI] << 32) | (unsigned)rag[RAG_OFF_LO]);
+    if (off < 0 || off > nbytes - (step * (T - 1) + fb)) return false;
+    o.base = frames + off + step * t;
+  } else {
+    o.W = W;
+    o.H = H;
+    o.base = frames + (long)clampi(d[0] + t, 0, F - 1) * H * (long)W * 3;
+  }
+  return true;
+}
+
 struct BoxArgs {
   const uint8_t* frames; const int32_t* desc;
   const int32_t *xtab, *ytab;                // per box: min[Sp], k[taps][Sp]
   uint8_t* out8;                             // [n_clips*T][S][S][3]
+  long nbytes;                               // ragged: bytes of `frames`
   int F, H, W, T, S, Sp, R, cap_rows, xlen, ylen;
 };
 
+template <bool RAGGED>
 __global__ void __launch_bounds__(256)
 resize_boxes_kernel(const BoxArgs a) {
   extern __shared__ __align__(16) uint8_t hrows[];      // [rows][3][Sp]
   const int tid = threadIdx.x;
   const int band = blockIdx.x, slot = blockIdx.y;
   const int clip = slot / a.T, t = slot % a.T;
-  const int32_t* d = a.desc + (long)clip * BOX_FIELDS;
+  constexpr int fields = BOX_FIELDS + (RAGGED ? RAG_FIELDS : 0);
+  const int32_t* d = a.desc + (long)clip * fields;
   const int Sp = a.Sp, nxg = Sp >> 2;
-  const int f = clampi(d[BOX_FIRST] + t, 0, a.F - 1);
-  const int x0 = clampi(d[BOX_X0], 0, a.W - 1), y0 = clampi(d[BOX_Y0], 0, a.H - 1);
-  const int cw = clampi(d[BOX_W], 1, a.W - x0), ch = clampi(d[BOX_H], 1, a.H - y0);
+  RagFrame fm;
+  if (!clip_frame<RAGGED>(a.frames, a.nbytes, a.F, a.H, a.W, d, d + BOX_FIELDS, a.T, t, fm)) return;   // uniform
+  const int x0 = clampi(d[BOX_X0], 0, fm.W - 1), y0 = clampi(d[BOX_Y0], 0, fm.H - 1);
+  const int cw = clampi(d[BOX_W], 1, fm.W - x0), ch = clampi(d[BOX_H], 1, fm.H - y0);
   const int xtaps = clampi(d[BOX_XTAPS], 1, min(64, a.xlen / Sp - 1));
   const int ytaps = clampi(d[BOX_YTAPS], 1, min(64, a.ylen / Sp - 1));
   const int32_t* xmin = a.xtab + clampi(d[BOX_XOFF] & ~3, 0, a.xlen - Sp * (1 + xtaps));
@@ -217,13 +249,13 @@ resize_boxes_kernel(const BoxArgs a) {
   const int r0 = band * a.R, r1 = min(r0 + a.R, a.S);                  // output rows [r0, r1)
   const int ylo = clampi(ymin[r0], 0, ch - 1);
   const int rows = min(clampi(ymin[r1 - 1] + ytaps, ylo + 1, ch) - ylo, a.cap_rows);
-  const uint8_t* fr = a.frames + ((long)f * a.H + (y0 + ylo)) * (long)a.W * 3 + x0 * 3;
+  const uint8_t* fr = fm.base + (long)(y0 + ylo) * fm.W * 3 + x0 * 3;
 
   // horizontal pass: item = (row, c, xg), xg fastest
   for (int it = tid; it < rows * 3 * nxg; it += 256) {
     const int xg = it % nxg, rc = it / nxg;
     const int c = rc % 3, row = rc / 3;
-    const uint8_t* src = fr + (long)row * a.W * 3 + c;
+    const uint8_t* src = fr + (long)row * fm.W * 3 + c;
     const int4 xm = reinterpret_cast<const int4*>(xmin)[xg];
     int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
     for (int i = 0; i < xtaps; ++i) {
@@ -289,21 +321,24 @@ struct Resize2Args {
   uint8_t* out8;                             // [n_clips*T][S][S][3]
   float* out;                                // [n_clips][3][T][S][S], normalised
   float mean[3], std[3];
+  long nbytes;                               // ragged: bytes of `frames`
   int F, H, W, T, size, P, S, Sp, taps2, R, cap1, capA, xlen, ylen;
 };
 
-template <bool U8OUT>
+template <bool U8OUT, bool RAGGED>
 __global__ void __launch_bounds__(kClsThreads)
 resize2_boxes_kernel(const Resize2Args a) {
   extern __shared__ __align__(16) uint8_t lds2[];
   const int tid = threadIdx.x;
   const int band = blockIdx.x, slot = blockIdx.y;
   const int clip = slot / a.T, t = slot % a.T;
-  const int32_t* d = a.desc + (long)clip * CLS_FIELDS;
+  constexpr int fields = CLS_FIELDS + (RAGGED ? RAG_FIELDS : 0);
+  const int32_t* d = a.desc + (long)clip * fields;
   const int P = a.P, nx1 = P >> 2, Sp = a.Sp, nx2 = Sp >> 2, size = a.size;
-  const int f = clampi(d[CLS_FIRST] + t, 0, a.F - 1);
-  const int x0 = clampi(d[CLS_X0], 0, a.W - 1), y0 = clampi(d[CLS_Y0], 0, a.H - 1);
-  const int cw = clampi(d[CLS_W], 1, a.W - x0), ch = clampi(d[CLS_H], 1, a.H - y0);
+  RagFrame fm;
+  if (!clip_frame<RAGGED>(a.frames, a.nbytes, a.F, a.H, a.W, d, d + CLS_FIELDS, a.T, t, fm)) return;   // uniform
+  const int x0 = clampi(d[CLS_X0], 0, fm.W - 1), y0 = clampi(d[CLS_Y0], 0, fm.H - 1);
+  const int cw = clampi(d[CLS_W], 1, fm.W - x0), ch = clampi(d[CLS_H], 1, fm.H - y0);
   const int xtaps = clampi(d[CLS_XTAPS], 1, min(64, a.xlen / P - 1));
   const int ytaps = clampi(d[CLS_YTAPS], 1, min(64, a.ylen / P - 1));
   const int32_t* xmin = a.xtab + clampi(d[CLS_XOFF] & ~3, 0, a.xlen - P * (1 + xtaps));
@@ -320,13 +355,13 @@ resize2_boxes_kernel(const Resize2Args a) {
   unsigned* one = reinterpret_cast<unsigned*>(lds2);
   const int one_bytes = max(a.cap1 * 3 * P, a.capA * 3 * Sp);
   unsigned* mid = reinterpret_cast<unsigned*>(lds2 + one_bytes);
-  const uint8_t* fr = a.frames + ((long)f * a.H + (y0 + ylo)) * (long)a.W * 3 + x0 * 3;
+  const uint8_t* fr = fm.base + (long)(y0 + ylo) * fm.W * 3 + x0 * 3;
 
   // H1: item = (row, c, xg), xg fastest
   for (int it = tid; it < rows1 * 3 * nx1; it += kClsThreads) {
     const int xg = it % nx1, rc = it / nx1;
     const int c = rc % 3, row = rc / 3;
-    const uint8_t* src = fr + (long)row * a.W * 3 + c;
+    const uint8_t* src = fr + (long)row * fm.W * 3 + c;
     const int4 xm = reinterpret_cast<const int4*>(xmin)[xg];
     int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
     for (int i = 0; i < xtaps; ++i) {
@@ -845,19 +880,44 @@ extern "C" int coclr_augment_clips(const uint8_t* frames, int N, int H, int W, i
                        out, (hipStream_t)stream_);
 }
 
-extern "C" int coclr_resize_boxes_u8(const uint8_t* frames, int F, int H, int W, const int32_t* desc,
-                                     const int32_t* desc_host, int n_clips, int T, int S, const int32_t* xtab,
-                                     int64_t xlen, const int32_t* ytab, int64_t ylen, uint8_t* out, void* stream_) {
+// What the ragged part of host descriptor `rag` must hold for a clip of T frames in a buffer of nbytes: an offset
+// that is a multiple of 16 and T frames of a positive size inside the buffer.  Clips may share frames.
+static bool rag_ok(const int32_t* rag, int T, int64_t nbytes, int* W, int* H) {
+  const long off = (long)(((unsigned long)(unsigned)rag[RAG_OFF_HI] << 32) | (unsigned)rag[RAG_OFF_LO]);
+  const int w = rag[RAG_W], h = rag[RAG_H];
+  if (w < 1 || h < 1 || w > kRagMaxSide || h > kRagMaxSide || (long)w * 3 * h > 0x7fffffffL) return false;
+  const long fb = (long)w * h * 3, step = (fb + 15) & ~15L;
+  if (off < 0 || (off & 15) || off > nbytes - (step * (T - 1) + fb)) return false;
+  *W = w;
+  *H = h;
+  return true;
+}
+
+// The launch both box entry points share.  ragged: `desc` rows carry RAG_FIELDS more words, F / H / W are not used.
+static int launch_boxes(bool ragged, const uint8_t* frames, int64_t nbytes, int F, int H, int W, const int32_t* desc,
+                        const int32_t* desc_host, int n_clips, int T, int S, const int32_t* xtab, int64_t xlen,
+                        const int32_t* ytab, int64_t ylen, uint8_t* out, void* stream_) {
   if (!frames || !desc || !desc_host || !xtab || !ytab || !out) return COCLR_EINVAL;
-  if (F < 1 || H < 1 || W < 1 || T < 1 || n_clips < 1 || S < 1 || S > 512) return COCLR_EINVAL;
-  if ((long)W * 3 * H > 0x7fffffffL || (long)n_clips * T > 65535) return COCLR_EINVAL;
+  if (T < 1 || n_clips < 1 || S < 1 || S > 512) return COCLR_EINVAL;
+  if (ragged) {
+    if (nbytes < 1 || (((uintptr_t)frames) & 15) || (((uintptr_t)desc) & 3)) return COCLR_EINVAL;
+  } else if (F < 1 || H < 1 || W < 1 || (long)W * 3 * H > 0x7fffffffL) {
+    return COCLR_EINVAL;
+  }
+  if ((long)n_clips * T > 65535) return COCLR_EINVAL;
+  const int fields = BOX_FIELDS + (ragged ? RAG_FIELDS : 0);
   if ((((uintptr_t)xtab) & 15) || (((uintptr_t)ytab) & 15)) return COCLR_EINVAL;       // 16-byte table loads
   const int Sp = (S + 3) & ~3;
   if (xlen < 2 * Sp || ylen < 2 * Sp || xlen > 0x7fffffffL || ylen > 0x7fffffffL) return COCLR_EINVAL;
   int hmax = 0, ytmax = 0;
   for (int k = 0; k < n_clips; ++k) {
-    const int32_t* d = desc_host + (long)k * BOX_FIELDS;
-    if (d[BOX_FIRST] < 0 || d[BOX_FRAMES] != T || (long)d[BOX_FIRST] + T > F) return COCLR_EINVAL;
+    const int32_t* d = desc_host + (long)k * fields;
+    if (d[BOX_FRAMES] != T) return COCLR_EINVAL;
+    if (ragged) {
+      if (!rag_ok(d + BOX_FIELDS, T, nbytes, &W, &H)) return COCLR_EINVAL;      // the box is held to the clip's own frame
+    } else if (d[BOX_FIRST] < 0 || (long)d[BOX_FIRST] + T > F) {
+      return COCLR_EINVAL;
+    }
     if (d[BOX_X0] < 0 || d[BOX_Y0] < 0 || d[BOX_W] < 1 || d[BOX_H] < 1 || (long)d[BOX_X0] + d[BOX_W] > W ||
         (long)d[BOX_Y0] + d[BOX_H] > H)
       return COCLR_EINVAL;
@@ -884,23 +944,46 @@ extern "C" int coclr_resize_boxes_u8(const uint8_t* frames, int F, int H, int W,
   BoxArgs a;
   a.frames = frames; a.desc = desc; a.xtab = xtab; a.ytab = ytab; a.out8 = out;
   a.F = F; a.H = H; a.W = W; a.T = T; a.S = S; a.Sp = Sp; a.R = R; a.cap_rows = cap;
-  a.xlen = (int)xlen; a.ylen = (int)ylen;
-  hipLaunchKernelGGL(resize_boxes_kernel, dim3((unsigned)bands, (unsigned)(n_clips * T)), dim3(256),
-                     (size_t)cap * 3 * Sp, (hipStream_t)stream_, a);
+  a.xlen = (int)xlen; a.ylen = (int)ylen; a.nbytes = (long)nbytes;
+  const dim3 grid((unsigned)bands, (unsigned)(n_clips * T));
+  if (ragged)
+    hipLaunchKernelGGL(resize_boxes_kernel<true>, grid, dim3(256), (size_t)cap * 3 * Sp, (hipStream_t)stream_, a);
+  else
+    hipLaunchKernelGGL(resize_boxes_kernel<false>, grid, dim3(256), (size_t)cap * 3 * Sp, (hipStream_t)stream_, a);
   COCLR_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" int coclr_resize2_boxes(const uint8_t* frames, int F, int H, int W, const int32_t* desc,
-                                   const int32_t* desc_host, int n_clips, int T, int size, int S, const int32_t* xtab,
-                                   int64_t xlen, const int32_t* ytab, int64_t ylen, const int32_t* tab2, int64_t len2,
-                                   int taps2, const float* mean, const float* std, uint8_t* out8, float* out,
-                                   void* stream_) {
+extern "C" int coclr_resize_boxes_u8(const uint8_t* frames, int F, int H, int W, const int32_t* desc,
+                                     const int32_t* desc_host, int n_clips, int T, int S, const int32_t* xtab,
+                                     int64_t xlen, const int32_t* ytab, int64_t ylen, uint8_t* out, void* stream_) {
+  return launch_boxes(false, frames, 0, F, H, W, desc, desc_host, n_clips, T, S, xtab, xlen, ytab, ylen, out, stream_);
+}
+
+extern "C" int coclr_resize_boxes_ragged_u8(const uint8_t* frames, int64_t nbytes, const int32_t* desc,
+                                            const int32_t* desc_host, int n_clips, int T, int S, const int32_t* xtab,
+                                            int64_t xlen, const int32_t* ytab, int64_t ylen, uint8_t* out,
+                                            void* stream_) {
+  return launch_boxes(true, frames, nbytes, 0, 0, 0, desc, desc_host, n_clips, T, S, xtab, xlen, ytab, ylen, out,
+                      stream_);
+}
+
+// The launch both classifier entry points share.  ragged: as launch_boxes.
+static int launch_resize2(bool ragged, const uint8_t* frames, int64_t nbytes, int F, int H, int W, const int32_t* desc,
+                          const int32_t* desc_host, int n_clips, int T, int size, int S, const int32_t* xtab,
+                          int64_t xlen, const int32_t* ytab, int64_t ylen, const int32_t* tab2, int64_t len2,
+                          int taps2, const float* mean, const float* std, uint8_t* out8, float* out, void* stream_) {
   if (!frames || !desc || !desc_host || !xtab || !ytab || !tab2) return COCLR_EINVAL;
   if ((out8 == nullptr) == (out == nullptr) || (out && (!mean || !std))) return COCLR_EINVAL;     // one of the two forms
-  if (F < 1 || H < 1 || W < 1 || T < 1 || n_clips < 1 || S < 1 || size < 1) return COCLR_EINVAL;
+  if (T < 1 || n_clips < 1 || S < 1 || size < 1) return COCLR_EINVAL;
+  if (ragged) {
+    if (nbytes < 1 || (((uintptr_t)frames) & 15) || (((uintptr_t)desc) & 3)) return COCLR_EINVAL;
+  } else if (F < 1 || H < 1 || W < 1 || (long)W * 3 * H > 0x7fffffffL) {
+    return COCLR_EINVAL;
+  }
   if (S > kClsMaxSide || size > kClsMaxSide) return COCLR_EINVAL;
-  if ((long)W * 3 * H > 0x7fffffffL || (long)n_clips * T > 65535) return COCLR_EINVAL;
+  if ((long)n_clips * T > 65535) return COCLR_EINVAL;
+  const int fields = CLS_FIELDS + (ragged ? RAG_FIELDS : 0);
   if ((((uintptr_t)xtab) & 15) || (((uintptr_t)ytab) & 15) || (((uintptr_t)tab2) & 15)) return COCLR_EINVAL;
   const int P = (size + 3) & ~3, Sp = (S + 3) & ~3;
   if (xlen < 2 * P || ylen < 2 * P || xlen > 0x7fffffffL || ylen > 0x7fffffffL) return COCLR_EINVAL;
@@ -911,8 +994,13 @@ extern "C" int coclr_resize2_boxes(const uint8_t* frames, int F, int H, int W, c
     if (a.std[c] == 0.f) return COCLR_EINVAL;
   }
   for (int k = 0; k < n_clips; ++k) {
-    const int32_t* d = desc_host + (long)k * CLS_FIELDS;
-    if (d[CLS_FIRST] < 0 || d[CLS_FRAMES] != T || (long)d[CLS_FIRST] + T > F) return COCLR_EINVAL;
+    const int32_t* d = desc_host + (long)k * fields;
+    if (d[CLS_FRAMES] != T) return COCLR_EINVAL;
+    if (ragged) {
+      if (!rag_ok(d + CLS_FIELDS, T, nbytes, &W, &H)) return COCLR_EINVAL;      // the region is held to the clip's own frame
+    } else if (d[CLS_FIRST] < 0 || (long)d[CLS_FIRST] + T > F) {
+      return COCLR_EINVAL;
+    }
     if (d[CLS_X0] < 0 || d[CLS_Y0] < 0 || d[CLS_W] < 1 || d[CLS_H] < 1 || (long)d[CLS_X0] + d[CLS_W] > W ||
         (long)d[CLS_Y0] + d[CLS_H] > H)
       return COCLR_EINVAL;
@@ -937,7 +1025,7 @@ extern "C" int coclr_resize2_boxes(const uint8_t* frames, int F, int H, int W, c
     if (capA > size) capA = size;
     cap1 = 1;
     for (int k = 0; k < n_clips; ++k) {
-      const int32_t* d = desc_host + (long)k * CLS_FIELDS;
+      const int32_t* d = desc_host + (long)k * fields;
       long c1 = ((long)(capA - 1) * d[CLS_H]) / d[CLS_OH] + d[CLS_YTAPS] + 2;
       if (c1 > d[CLS_H]) c1 = d[CLS_H];
       if (c1 > cap1) cap1 = (int)c1;
@@ -951,20 +1039,40 @@ extern "C" int coclr_resize2_boxes(const uint8_t* frames, int F, int H, int W, c
   if (bands * n_clips * T * kClsThreads >= (1L << 32)) return COCLR_EINVAL;
   a.frames = frames; a.desc = desc; a.xtab = xtab; a.ytab = ytab; a.tab2 = tab2; a.out8 = out8; a.out = out;
   a.F = F; a.H = H; a.W = W; a.T = T; a.size = size; a.P = P; a.S = S; a.Sp = Sp; a.taps2 = taps2; a.R = R;
-  a.cap1 = cap1; a.capA = capA; a.xlen = (int)xlen; a.ylen = (int)ylen;
-  static std::atomic<uint64_t> attr_u8{0}, attr_f32{0};
+  a.cap1 = cap1; a.capA = capA; a.xlen = (int)xlen; a.ylen = (int)ylen; a.nbytes = (long)nbytes;
+  static std::atomic<uint64_t> attr_u8{0}, attr_f32{0}, attr_rag_u8{0}, attr_rag_f32{0};
   const dim3 grid((unsigned)bands, (unsigned)(n_clips * T));
-  if (out8) {
-    if (bytes > 65536)
-      COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(resize2_boxes_kernel<true>), kClsLdsMax, attr_u8));
-    hipLaunchKernelGGL(resize2_boxes_kernel<true>, grid, dim3(kClsThreads), (size_t)bytes, (hipStream_t)stream_, a);
-  } else {
-    if (bytes > 65536)
-      COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(resize2_boxes_kernel<false>), kClsLdsMax, attr_f32));
-    hipLaunchKernelGGL(resize2_boxes_kernel<false>, grid, dim3(kClsThreads), (size_t)bytes, (hipStream_t)stream_, a);
-  }
+  const void* fn = ragged ? (out8 ? reinterpret_cast<const void*>(resize2_boxes_kernel<true, true>)
+                                  : reinterpret_cast<const void*>(resize2_boxes_kernel<false, true>))
+                          : (out8 ? reinterpret_cast<const void*>(resize2_boxes_kernel<true, false>)
+                                  : reinterpret_cast<const void*>(resize2_boxes_kernel<false, false>));
+  std::atomic<uint64_t>& done = ragged ? (out8 ? attr_rag_u8 : attr_rag_f32) : (out8 ? attr_u8 : attr_f32);
+  if (bytes > 65536) COCLR_RETURN_IF(ensure_dyn_lds(fn, kClsLdsMax, done));
+  const hipStream_t st = (hipStream_t)stream_;
+  if (ragged && out8) hipLaunchKernelGGL((resize2_boxes_kernel<true, true>), grid, dim3(kClsThreads), (size_t)bytes, st, a);
+  else if (ragged) hipLaunchKernelGGL((resize2_boxes_kernel<false, true>), grid, dim3(kClsThreads), (size_t)bytes, st, a);
+  else if (out8) hipLaunchKernelGGL((resize2_boxes_kernel<true, false>), grid, dim3(kClsThreads), (size_t)bytes, st, a);
+  else hipLaunchKernelGGL((resize2_boxes_kernel<false, false>), grid, dim3(kClsThreads), (size_t)bytes, st, a);
   COCLR_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int coclr_resize2_boxes(const uint8_t* frames, int F, int H, int W, const int32_t* desc,
+                                   const int32_t* desc_host, int n_clips, int T, int size, int S, const int32_t* xtab,
+                                   int64_t xlen, const int32_t* ytab, int64_t ylen, const int32_t* tab2, int64_t len2,
+                                   int taps2, const float* mean, const float* std, uint8_t* out8, float* out,
+                                   void* stream_) {
+  return launch_resize2(false, frames, 0, F, H, W, desc, desc_host, n_clips, T, size, S, xtab, xlen, ytab, ylen, tab2,
+                        len2, taps2, mean, std, out8, out, stream_);
+}
+
+extern "C" int coclr_resize2_boxes_ragged(const uint8_t* frames, int64_t nbytes, const int32_t* desc,
+                                          const int32_t* desc_host, int n_clips, int T, int size, int S,
+                                          const int32_t* xtab, int64_t xlen, const int32_t* ytab, int64_t ylen,
+                                          const int32_t* tab2, int64_t len2, int taps2, const float* mean,
+                                          const float* std, uint8_t* out8, float* out, void* stream_) {
+  return launch_resize2(true, frames, nbytes, 0, 0, 0, desc, desc_host, n_clips, T, size, S, xtab, xlen, ytab, ylen,
+                        tab2, len2, taps2, mean, std, out8, out, stream_);
 }
 
 extern "C" int coclr_stage_clips(const void* frames, int from_u8, float* out, int B, int C, int S,

@@ -6,6 +6,9 @@
     loop:    frames = jpeg.decode(data, meta)             # (F, H, W, 3) uint8 on the device
 
 `frames` is what stage_train_clips, stage_classifier_clips, stage_crops and VideoEvaluator.add_frames take.
+A batch whose videos differ in frame size (kinetics400-256 keeps every video's aspect ratio) goes through
+`cat_ragged` and `decode_ragged` instead, to a staging.RaggedFrames that stage_train_clips_ragged and
+stage_classifier_clips_ragged take; `pack`, per video, is the same.
 
 Scope: baseline / extended sequential Huffman (SOF0, SOF1), 8-bit, one interleaved scan, one component or YCbCr with
 luma sampled 1x1, 2x1 or 2x2, optional restart intervals -- what ffmpeg, cv2.imwrite and PIL write by default.
@@ -324,6 +327,67 @@ def check_meta(data, meta):
     return H, W, ncomp, hs, vs
 
 
+def cat_ragged(packs):
+    """`cat` for packs that DIFFER in size, components or sampling (videos that keep their own aspect ratio): byte
+    offsets are shifted and descriptors padded to the widest pack as there, and every row keeps its own 8-word
+    geometry head, which is what decode_ragged reads.  Packs of one geometry give exactly `cat`'s result."""
+    packs = list(packs)
+    if not packs:
+        raise ValueError("coclr_amd: cat_ragged needs at least one pack")
+    for _, m in packs:
+        _geometry(m)                                     # each pack on its own is one `pack` wrote
+    width = max(m.shape[1] for _, m in packs)
+    rows, offset = [], 0
+    for data, m in packs:
+        r = torch.zeros(m.shape[0], width, dtype=torch.int32)
+        r[:, :m.shape[1]] = m
+        r[:, 0] = width
+        r[:, 8] += offset
+        offset += data.numel()
+        rows.append(r)
+    if offset > 0x7fffffff:
+        raise ValueError("coclr_amd: one decode takes up to 2 GiB of compressed bytes")
+    return torch.cat([d for d, _ in packs]), torch.cat(rows)
+
+
+def check_meta_ragged(data, meta):
+    """check_meta for the rows of cat_ragged, each against its OWN geometry head -> int64 (F, 5): H, W, components,
+    hs, vs per frame."""
+    if not isinstance(meta, torch.Tensor) or meta.dtype != torch.int32 or meta.dim() != 2 or meta.is_cuda or \
+            meta.shape[0] < 1 or meta.shape[1] <= 8 + META_SEG:
+        raise ValueError("coclr_amd: meta must be the host int32 (F, width) tensor of jpeg.pack / jpeg.cat_ragged")
+    if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() != 1:
+        raise ValueError("coclr_amd: data must be the flat uint8 tensor of jpeg.pack")
+    head = meta[:, :8].to(torch.int64)
+    if bool((head[:, 0] != meta.shape[1]).any()):
+        raise ValueError("coclr_amd: meta is %d words wide and a row says otherwise" % meta.shape[1])
+    if bool((head[:, 6:] != 0).any()):
+        raise ValueError("coclr_amd: a row's geometry head is not one jpeg.pack wrote")
+    geo = head[:, 1:6]
+    for g in sorted(set(tuple(r) for r in geo.tolist())):
+        ops.jpeg_workspace(*g)                           # refuses a geometry the kernels do not take
+    H, W, ncomp, hs, vs = geo.unbind(1)
+    m = meta[:, 8:].to(torch.int64)
+    n, width = data.numel(), m.shape[1]
+    mcus = -(-W // (8 * hs)) * -(-H // (8 * vs))
+    off, ln, ri, nseg = m[:, 0], m[:, 1], m[:, 2], m[:, 3]
+    if bool(((off < 0) | (ln < 0) | (off + ln > n)).any()):
+        raise ValueError("coclr_amd: a frame's bytes leave the buffer of %d bytes" % n)
+    want = torch.where(ri > 0, -(-mcus // ri.clamp(min=1)), torch.ones_like(ri))
+    if bool(((ri < 0) | (nseg != want) | (nseg > width - META_SEG)).any()):
+        raise ValueError("coclr_amd: a frame's restart segments do not match its interval and its own MCU count")
+    seg = m[:, META_SEG:]
+    live = torch.arange(seg.shape[1])[None, :] < nseg[:, None]
+    prev = torch.cat([torch.zeros_like(seg[:, :1]), seg[:, :-1]], 1)
+    if bool((live & ((seg < prev) | (seg > ln[:, None]))).any()):
+        raise ValueError("coclr_amd: a restart segment's offset decreases or leaves its frame's bytes")
+    q = m[:, META_QUANT:META_QUANT + 192]
+    used = torch.arange(192)[None, :] < 64 * ncomp[:, None]
+    if bool((used & ((q < 0) | (q > 255))).any()):
+        raise ValueError("coclr_amd: a quantiser outside 0..255")
+    return geo.contiguous()
+
+
 def split_policy(chunk_bytes=None):
     """The chunk size of a decode call: `chunk_bytes` if given, else COCLR_JPEG_SPLIT, else DEFAULT_SPLIT.  0 is the
     serial path; anything but 0 or 8..65536 is a ValueError."""
@@ -384,6 +448,82 @@ def decode(data, meta, out=None, device=None, max_stage_bytes=256 << 20, return_
 
 
 decode.last_status = None
+
+
+def ragged_plan(geo, max_stage_bytes):
+    """Host tables of decode_ragged for frames of geometry `geo` (int64 (F, 5)): the output layout -- every frame in
+    batch order, each starting 16-byte aligned -- and the stages: runs of whole frames whose workspace (coefficients
+    + sample planes) stays within max_stage_bytes, one frame at least.  Returns (offset, total bytes, stages, blocks):
+    a stage is (first frame, end frame, geom int64 (n, 8), prefix int64 (2, n + 1)), `blocks` the largest stage's."""
+    F = geo.shape[0]
+    g = geo.tolist()
+    nblocks, rows, size = [], [], []
+    for H, W, ncomp, hs, vs in g:
+        mx, my = -(-W // (8 * hs)), -(-H // (8 * vs))
+        nblocks.append(mx * my * (1 if ncomp == 1 else hs * vs + 2))
+        rows.append(H * -(-W // 16))
+        size.append(3 * H * W)
+    offset, at = [], 0
+    for n in size:
+        offset.append(at)
+        at = (at + n + 15) & ~15
+    total = offset[-1] + size[-1]
+    stages, k, most = [], 0, 1
+    limit = max(1, int(max_stage_bytes))
+    while k < F:
+        e, used = k, 0
+        while e < F and (e == k or used + nblocks[e] * 192 <= limit):
+            used += nblocks[e] * 192
+            e += 1
+        geom = torch.zeros(e - k, ops.JR_FIELDS, dtype=torch.int64)
+        prefix = torch.zeros(2, e - k + 1, dtype=torch.int64)
+        geom[:, :5] = geo[k:e]
+        nb = torch.tensor(nblocks[k:e], dtype=torch.int64)
+        prefix[0, 1:] = nb.cumsum(0)
+        prefix[1, 1:] = torch.tensor(rows[k:e], dtype=torch.int64).cumsum(0)
+        geom[:, 5] = prefix[0, :-1]
+        geom[:, 6] = torch.tensor(offset[k:e], dtype=torch.int64)
+        most = max(most, int(prefix[0, -1]))
+        stages.append((k, e, geom, prefix))
+        k = e
+    return torch.tensor(offset, dtype=torch.int64), total, stages, most
+
+
+def decode_ragged(data, meta, device=None, max_stage_bytes=256 << 20, return_status=False, chunk_bytes=None):
+    """(data, meta) of cat_ragged -> staging.RaggedFrames: every frame at its own size, the bytes PIL's convert('RGB')
+    returns, in ONE flat device buffer in batch order -- what stage_train_clips_ragged and
+    stage_classifier_clips_ragged take.  One call may mix sizes, gray and YCbCr and the three samplings; the stages
+    are still one launch each for the whole batch (coclr_jpeg_decode_ragged).  A bad `meta` is refused on the host,
+    row by row against the row's own geometry; status, `decode_ragged.last_status` and `chunk_bytes` as in `decode`.
+    Whole frames are decoded `max_stage_bytes` of intermediate storage at a time; the result depends on neither."""
+    from . import staging
+    chunk_bytes = split_policy(chunk_bytes)
+    geo = check_meta_ragged(data, meta)
+    F = meta.shape[0]
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    offset, total, stages, blocks = ragged_plan(geo, max_stage_bytes)
+    host = meta[:, 8:].contiguous()
+    d_data, d_meta = data.contiguous().to(device), host.to(device)
+    tables = torch.cat([t.reshape(-1) for _, _, geom, prefix in stages for t in (geom, prefix)])
+    d_tables = tables.to(device)                                             # every stage's tables in one upload
+    pixels = torch.empty((total + 15) & ~15, dtype=torch.uint8, device=device)
+    coefs = torch.empty(blocks * 64, dtype=torch.int16, device=device)
+    planes = torch.empty(blocks * 64, dtype=torch.uint8, device=device)
+    status = torch.empty(F, dtype=torch.int32, device=device)
+    at = 0
+    for k, e, geom, prefix in stages:
+        d_geom = d_tables[at:at + geom.numel()].view(geom.shape)
+        at += geom.numel()
+        d_prefix = d_tables[at:at + prefix.numel()].view(prefix.shape)
+        at += prefix.numel()
+        ops.jpeg_decode_ragged(d_data, d_meta[k:e], host[k:e], d_geom, geom, d_prefix, prefix, coefs, planes, pixels,
+                               status[k:e], chunk_bytes=chunk_bytes)
+    decode_ragged.last_status = status
+    frames = staging.RaggedFrames(pixels, offset, geo[:, 0].to(torch.int32), geo[:, 1].to(torch.int32))
+    return (frames, status) if return_status else frames
+
+
+decode_ragged.last_status = None
 
 
 def decode_frames(raws, out=None, device=None, max_stage_bytes=256 << 20, chunk_bytes=None):

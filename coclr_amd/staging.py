@@ -1030,3 +1030,272 @@ def stage_classifier_clips(frames_u8, plans, img_dim, flip=False, mean=IMAGENET_
         ops.resize_boxes_u8(mid, d2.to(device), d2, flat2, flat2, T, S, u8)
     ops.augment_clips(u8, kinds.to(device), params.to(device), T, T, mean, std, out, host_tables=(kinds, params))
     return out
+
+
+# ---- batches whose videos differ in frame size (kinetics400-256: a 256-pixel short side, the video's own aspect) -------
+
+RAGGED_ALIGN = 16        # every frame starts on a multiple of this in RaggedFrames.pixels
+
+
+class RaggedFrames:
+    """Frames of differing sizes in ONE flat uint8 device buffer, in batch order: what jpeg.decode_ragged returns and
+    the *_ragged staging functions take.
+      pixels  flat uint8 on the device
+      offset  int64 (F,), host: frame i is pixels[offset[i] : offset[i] + 3 * H[i] * W[i]] viewed as (H, W, 3);
+              64-bit (a batch may exceed 2 GiB), increasing, and a multiple of 16 so that the kernels' 16-byte
+              accesses keep their aligned forms
+      height, width  int32 (F,), host"""
+
+    def __init__(self, pixels, offset, height, width):
+        if not torch.is_tensor(pixels) or pixels.dtype != torch.uint8 or pixels.dim() != 1 or not pixels.is_contiguous():
+            raise ValueError("coclr_amd: RaggedFrames.pixels is a flat contiguous uint8 tensor")
+        offset = torch.as_tensor(offset, dtype=torch.int64).cpu().contiguous()
+        height = torch.as_tensor(height, dtype=torch.int32).cpu().contiguous()
+        width = torch.as_tensor(width, dtype=torch.int32).cpu().contiguous()
+        F = offset.numel()
+        if F < 1 or offset.dim() != 1 or tuple(height.shape) != (F,) or tuple(width.shape) != (F,):
+            raise ValueError("coclr_amd: RaggedFrames takes offset, height and width of one length F >= 1")
+        if bool((height < 1).any()) or bool((width < 1).any()):
+            raise ValueError("coclr_amd: RaggedFrames holds frames of at least 1 x 1")
+        end = offset + 3 * height.to(torch.int64) * width.to(torch.int64)
+        if int(offset[0]) < 0 or bool((offset % RAGGED_ALIGN != 0).any()) or bool((offset[1:] < end[:-1]).any()) or \
+                int(end[-1]) > pixels.numel():
+            raise ValueError("coclr_amd: RaggedFrames offsets are multiples of %d, increasing, and the frames neither "
+                             "overlap nor leave the %d bytes of pixels" % (RAGGED_ALIGN, pixels.numel()))
+        self.pixels, self.offset, self.height, self.width = pixels, offset, height, width
+
+    def __len__(self):
+        return self.offset.numel()
+
+    def frame(self, i):
+        """Frame i as a (H, W, 3) view of `pixels`."""
+        i = int(i)
+        if not 0 <= i < len(self):
+            raise IndexError("coclr_amd: frame %d of %d" % (i, len(self)))
+        o, H, W = int(self.offset[i]), int(self.height[i]), int(self.width[i])
+        return self.pixels[o:o + 3 * H * W].view(H, W, 3)
+
+
+def ragged_from_frames(frames, device=None):
+    """uint8 tensors (n_i, H_i, W_i, 3) (or (H_i, W_i, 3)), on the host or the device, in batch order -> RaggedFrames
+    with ONE upload: for callers who decode elsewhere."""
+    frames = list(frames)
+    if not frames:
+        raise ValueError("coclr_amd: ragged_from_frames needs at least one tensor")
+    offset, height, width, parts, at = [], [], [], [], 0
+    for t in frames:
+        if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() not in (3, 4) or t.shape[-1] != 3 or t.numel() == 0:
+            raise ValueError("coclr_amd: ragged_from_frames takes uint8 (n, H, W, 3) tensors")
+        t = t[None] if t.dim() == 3 else t
+        n, H, W = t.shape[:3]
+        for k in range(n):
+            pad = -at % RAGGED_ALIGN
+            if pad:
+                parts.append(torch.zeros(pad, dtype=torch.uint8, device=t.device))
+                at += pad
+            offset.append(at)
+            height.append(H)
+            width.append(W)
+            parts.append(t[k].contiguous().view(-1))
+            at += 3 * H * W
+    if device is None:
+        on = [t.device for t in frames if t.is_cuda]
+        device = on[0] if on else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if all(p.device == device for p in parts):
+        pixels = torch.cat(parts)
+    else:
+        pixels = torch.cat([p.cpu() for p in parts]).to(device)
+    return RaggedFrames(pixels, offset, height, width)
+
+
+def _ragged_samples(frames, B, n, first):
+    """Per sample its first frame, checked: frames first[b] .. first[b] + n - 1 exist, share one size and follow each
+    other at 3 H W bytes rounded up to 16, which is how the kernels step through a clip and how decode_ragged and
+    ragged_from_frames lay frames out.  Returns [(byte offset, W, H)] per sample."""
+    if not isinstance(frames, RaggedFrames):
+        raise ValueError("coclr_amd: the ragged staging takes a RaggedFrames (jpeg.decode_ragged, ragged_from_frames)")
+    F = len(frames)
+    first = [b * n for b in range(B)] if first is None else [int(v) for v in torch.as_tensor(first).reshape(-1).tolist()]
+    if len(first) != B:
+        raise ValueError("coclr_amd: %d first frames for %d samples" % (len(first), B))
+    off, Hs, Ws = frames.offset.tolist(), frames.height.tolist(), frames.width.tolist()
+    out = []
+    for b, f0 in enumerate(first):
+        if f0 < 0 or f0 + n > F:
+            raise ValueError("coclr_amd: sample %d reads frames %d..%d of %d" % (b, f0, f0 + n - 1, F))
+        H, W = Hs[f0], Ws[f0]
+        if any(Hs[f] != H or Ws[f] != W for f in range(f0, f0 + n)):
+            raise ValueError("coclr_amd: the frames of sample %d differ in size; one sample is one video" % b)
+        stride = (3 * H * W + RAGGED_ALIGN - 1) & ~(RAGGED_ALIGN - 1)
+        if any(off[f0 + k] != off[f0] + k * stride for k in range(n)):
+            raise ValueError("coclr_amd: the frames of sample %d do not follow each other at %d bytes" % (b, stride))
+        out.append((off[f0], W, H))
+    return out
+
+
+def _rag_words(offset, W, H):
+    """The four trailing words of a ragged descriptor: the 64-bit byte offset as two int32 (low first), W, H."""
+    lo = offset & 0xffffffff
+    return [lo - (1 << 32) if lo >= 1 << 31 else lo, offset >> 32, W, H]
+
+
+def train_tables_ragged(plans, samples, T, S):
+    """train_tables for samples of differing frame sizes: `samples` [(byte offset of the sample's first frame, W, H)];
+    every plan is checked against its own sample's (W, H).  Returns (desc int32 (2B, 14), xtab, ytab, kinds, params,
+    group_size) as coclr_resize_boxes_ragged_u8 and coclr_augment_clips take them, all on the host."""
+    B = len(samples)
+    if torch.is_tensor(plans):
+        plans = [unpack_plan(p) for p in (plans[None] if plans.dim() == 2 else plans)]
+    plans = list(plans)
+    if len(plans) != B:
+        raise ValueError("coclr_amd: %d plans for %d samples" % (len(plans), B))
+    rows, programs = [], []
+    for b, (plan, (offset, W, H)) in enumerate(zip(plans, samples)):
+        r, p = check_train_plans([plan], 1, T, W, H)
+        for row in r:                                            # row[0]: the clip's first frame within its sample
+            stride = (3 * H * W + RAGGED_ALIGN - 1) & ~(RAGGED_ALIGN - 1)
+            rows.append((row, _rag_words(offset + row[0] * stride, W, H)))
+        programs.extend(p)
+    bufs, at, fill, full = ([], []), ({}, {}), [0, 0], []
+    for row, rag in rows:
+        offs = []
+        for axis, n_in in ((0, row[4]), (1, row[5])):
+            if n_in not in at[axis]:
+                t = _box_table(n_in, S)
+                if t.shape[0] - 1 > 64:
+                    raise ValueError("coclr_amd: a box side of %d to %d needs %d taps, the kernel takes 64" %
+                                     (n_in, S, t.shape[0] - 1))
+                at[axis][n_in] = (fill[axis], t.shape[0] - 1)
+                bufs[axis].append(t.reshape(-1))
+                fill[axis] += t.size
+            offs.append(at[axis][n_in])
+        full.append([0] + list(row[1:]) + [offs[0][0], offs[1][0], offs[0][1], offs[1][1]] + rag)
+    per_clip = all(all(p == progs[0] for p in progs) for progs in programs)
+    flat = [progs[0] for progs in programs] if per_clip else [p for progs in programs for p in progs]
+    kinds, params = augment_tables(flat)
+    return (torch.tensor(full, dtype=torch.int32), torch.from_numpy(np.concatenate(bufs[0])),
+            torch.from_numpy(np.concatenate(bufs[1])), kinds, params, T if per_clip else 1)
+
+
+def stage_train_clips_ragged(frames, plans, out_size, first=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
+    """stage_train_clips for a batch whose samples differ in frame size, still TWO launches
+    (coclr_resize_boxes_ragged_u8, then coclr_augment_clips on the S x S bytes, unchanged).
+    frames: RaggedFrames.  Sample b is frames first[b] .. first[b] + 2T - 1 (default first[b] = 2 T b), which share
+    one size; T comes from the plans.  plans: B plans of TrainTransform.draw(W_b, H_b), or their pack_plan tensors
+    stacked.  Returns (B, 2, 3, T, S, S) fp32 on the device, each sample bit-identical to stage_train_clips on it."""
+    if torch.is_tensor(plans):
+        plans = [unpack_plan(p) for p in (plans[None] if plans.dim() == 2 else plans)]
+    plans = [plans] if isinstance(plans, dict) else list(plans)
+    B, S = len(plans), int(out_size)
+    if B < 1:
+        raise ValueError("coclr_amd: stage_train_clips_ragged needs at least one plan")
+    T = len(plans[0]["programs"][0])
+    if T < 1:
+        raise ValueError("coclr_amd: a plan has one program per frame")
+    if S < 1 or S * S > JITTER_MAX_PIXELS:
+        raise ValueError("coclr_amd: stage_train_clips_ragged takes an output size of 1..224, got %d" % S)
+    samples = _ragged_samples(frames, B, 2 * T, first)
+    pixels = frames.pixels
+    desc, xtab, ytab, kinds, params, group_size = train_tables_ragged(plans, samples, T, S)
+    if out is not None and (tuple(out.shape) != (B, 2, 3, T, S, S) or not out.is_contiguous()):
+        raise ValueError("coclr_amd: out must be contiguous %s, got %s" % ((B, 2, 3, T, S, S), tuple(out.shape)))
+    device = pixels.device
+    u8 = torch.empty(B * 2 * T, S, S, 3, dtype=torch.uint8, device=device)
+    if out is None:
+        out = torch.empty(B, 2, 3, T, S, S, dtype=torch.float32, device=device)
+    ops.resize_boxes_ragged_u8(pixels, desc.to(device), desc, xtab.to(device), ytab.to(device), T, S, u8)
+    ops.augment_clips(u8, kinds.to(device), params.to(device), group_size, T, mean, std,
+                      out.view(B * 2, 3, T, S, S), host_tables=(kinds, params))
+    return out
+
+
+def classifier_tables_ragged(plans, samples, T, img_dim, size=224, flip=False):
+    """classifier_tables for samples of differing frame sizes: `samples` [(byte offset, W, H)]; every plan is checked
+    against its own sample's (W, H).  Returns (desc int32 (B, 18), xtab, ytab, tab2, kinds, params, direct)."""
+    B, T, S, size = len(samples), int(T), int(img_dim), int(size)
+    if S < 1 or size < 1 or S > CLS_MAX_SIDE or size > CLS_MAX_SIDE:
+        raise ValueError("coclr_amd: the classifier staging takes img_dim and size of 1..%d, got %d and %d" %
+                         (CLS_MAX_SIDE, S, size))
+    if torch.is_tensor(plans):
+        plans = [unpack_cls_plan(p) for p in (plans[None] if plans.dim() == 1 else plans)]
+    plans = list(plans)
+    if len(plans) != B:
+        raise ValueError("coclr_amd: %d plans for %d samples" % (len(plans), B))
+    rows, programs = [], []
+    for plan, (offset, W, H) in zip(plans, samples):
+        r, p = check_cls_plans([plan], 1, W, H, size)
+        rows.append((r[0], _rag_words(offset, W, H)))
+        programs.extend(p)
+    tab2 = _window_table(size, S, 0, S)
+    bufs, at, fill, full = ([], []), ({}, {}), [0, 0], []
+    for (x0, y0, w, h, ow, oh, cx, cy), rag in rows:
+        offs = []
+        for axis, key in ((0, (w, ow, cx)), (1, (h, oh, cy))):
+            if key not in at[axis]:
+                t = _window_table(key[0], key[1], key[2], size)
+                at[axis][key] = (fill[axis], t.shape[0] - 1)
+                bufs[axis].append(t.reshape(-1))
+                fill[axis] += t.size
+            offs.append(at[axis][key])
+        full.append([0, T, x0, y0, w, h, ow, oh, cx, cy, offs[0][0], offs[1][0], offs[0][1], offs[1][1]] + rag)
+    tail = [(AUGMENT_FLIP, 0.0)] if flip else []
+    kinds, params = augment_tables([list(p) + tail for p in programs])
+    direct = not flip and not any(programs)
+    return (torch.tensor(full, dtype=torch.int32), torch.from_numpy(np.concatenate(bufs[0])),
+            torch.from_numpy(np.concatenate(bufs[1])), torch.from_numpy(tab2), kinds, params, direct)
+
+
+def stage_classifier_clips_ragged(frames, plans, img_dim, flip=False, first=None, T=None, mean=IMAGENET_MEAN,
+                                  std=IMAGENET_STD, out=None, size=224):
+    """stage_classifier_clips for a batch whose samples differ in frame size: ONE launch fused
+    (coclr_resize2_boxes_ragged) plus coclr_augment_clips when a clip has a program or `flip` is on, or two chained
+    coclr_resize_boxes_ragged_u8 / coclr_resize_boxes_u8 launches with COCLR_CLS_FUSED=0 (box plans only).
+    frames: RaggedFrames.  Sample b is frames first[b] .. first[b] + T - 1 (default first[b] = T b, T = frames / B),
+    which share one size.  plans: B plans of ClassifierTransform.draw(W_b, H_b), or their packed tensors stacked.
+    Returns (B, 3, T, S, S) fp32 on the device, each sample bit-identical to stage_classifier_clips on it."""
+    if torch.is_tensor(plans):
+        plans = [unpack_cls_plan(p) for p in (plans[None] if plans.dim() == 1 else plans)]
+    plans = [plans] if isinstance(plans, dict) else list(plans)
+    B, S, size = len(plans), int(img_dim), int(size)
+    if B < 1:
+        raise ValueError("coclr_amd: stage_classifier_clips_ragged needs at least one plan")
+    if T is None:
+        if not isinstance(frames, RaggedFrames) or first is not None or len(frames) % B != 0:
+            raise ValueError("coclr_amd: give T, the frames per sample, when `first` is given or frames / B is not whole")
+        T = len(frames) // B
+    T = int(T)
+    if T < 1:
+        raise ValueError("coclr_amd: a sample is T >= 1 frames")
+    samples = _ragged_samples(frames, B, T, first)
+    pixels = frames.pixels
+    desc, xtab, ytab, tab2, kinds, params, direct = classifier_tables_ragged(plans, samples, T, S, size, flip)
+    if out is not None and (tuple(out.shape) != (B, 3, T, S, S) or not out.is_contiguous() or
+                            out.dtype != torch.float32):
+        raise ValueError("coclr_amd: out must be contiguous fp32 %s, got %s" % ((B, 3, T, S, S), tuple(out.shape)))
+    fused = cls_fused()
+    if not fused and bool((desc[:, 6:10] != torch.tensor([size, size, 0, 0], dtype=torch.int32)).any()):
+        raise ValueError("coclr_amd: COCLR_CLS_FUSED=0 chains two box resizes and cannot express the fallback form "
+                         "(a window of a whole-frame resample)")
+    device = pixels.device
+    if out is None:
+        out = torch.empty(B, 3, T, S, S, dtype=torch.float32, device=device)
+    if fused and direct:
+        ops.resize2_boxes_ragged(pixels, desc.to(device), desc, xtab.to(device), ytab.to(device), tab2.to(device), T,
+                                 size, S, out, mean, std)
+        return out
+    u8 = torch.empty(B * T, S, S, 3, dtype=torch.uint8, device=device)
+    if fused:
+        ops.resize2_boxes_ragged(pixels, desc.to(device), desc, xtab.to(device), ytab.to(device), tab2.to(device), T,
+                                 size, S, u8)
+    else:
+        # box -> size per clip from the ragged buffer, then the whole of that -> S: the second stage has one size
+        d1 = desc[:, [0, 1, 2, 3, 4, 5, 10, 11, 12, 13, 14, 15, 16, 17]].contiguous()
+        taps2 = tab2.shape[0] - 1
+        d2 = torch.tensor([[b * T, T, 0, 0, size, size, 0, 0, taps2, taps2] for b in range(B)], dtype=torch.int32)
+        mid = torch.empty(B * T, size, size, 3, dtype=torch.uint8, device=device)
+        flat2 = tab2.reshape(-1).to(device)
+        ops.resize_boxes_ragged_u8(pixels, d1.to(device), d1, xtab.to(device), ytab.to(device), T, size, mid)
+        ops.resize_boxes_u8(mid, d2.to(device), d2, flat2, flat2, T, S, u8)
+    ops.augment_clips(u8, kinds.to(device), params.to(device), T, T, mean, std, out, host_tables=(kinds, params))
+    return out

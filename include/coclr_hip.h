@@ -757,6 +757,57 @@ int coclr_jpeg_decode_split(const uint8_t* data, int64_t data_len, const int32_t
                             int F, int width, int H, int W, int ncomp, int hs, int vs, int stages, int16_t* coefs,
                             uint8_t* planes, uint8_t* out, int32_t* status, int chunk_bytes, void* stream);
 
+/* coclr_jpeg_decode_split for a batch whose frames DIFFER in geometry (a loader batch of videos that keep their own
+ * aspect ratio: kinetics400-256): the same stages, still one launch each for the whole batch, with (H, W, components,
+ * hs, vs), the place of the coefficients and the place of the output per frame.
+ * data, meta, meta_host, width, stages, status, chunk_bytes: as coclr_jpeg_decode_split; every descriptor is held
+ *   against its OWN frame's geometry.
+ * geom: int64 [F][8], DEVICE: {H, W, components, hs, vs, first coefficient block, first output byte, 0} (csrc/
+ *   jpeg_core.h: JR_*); geom_host: the same on the HOST, read at call time and validated.
+ * prefix: int64 [2][F + 1], DEVICE, and prefix_host: the blocks, then the row groups (H * ceil(W / 16)) of all frames
+ *   before each one, [0] = 0 and [F] the total.  A lane of the inverse DCT (one per block) and of the colour stage (one
+ *   per 16 pixels of a row) finds its frame by binary search in it.
+ * coefs / planes: workspaces of coef_blocks blocks (128 / 64 bytes each), 16-byte aligned; frame f uses blocks
+ *   [first block, first block + its block count) of both.  out: out_bytes bytes, 16-byte aligned; frame f is
+ *   uint8 [H][W][3] at its first output byte.  Bytes between frames are not written.
+ * The kernels read the device copies and stay in bounds whatever those hold: a frame whose geometry is not one of the
+ * above, or whose blocks or bytes leave coef_blocks / out_bytes, is skipped, and a lane outside its frame's own count
+ * does nothing.
+ * COCLR_EINVAL before any launch: everything coclr_jpeg_decode_split refuses, per frame against its own geometry; a
+ * frame whose first block or first byte is below the end of the frame before it (overlapping or decreasing) or whose
+ * range leaves its buffer; a first output byte that is not a multiple of 16; prefix arrays that do not start at 0 or
+ * whose steps are not the frames' block and row-group counts.
+ * Additive: the ABI number stays 25 -- no existing signature or behaviour changed. */
+int coclr_jpeg_decode_ragged(const uint8_t* data, int64_t data_len, const int32_t* meta, const int32_t* meta_host,
+                             int F, int width, const int64_t* geom, const int64_t* geom_host, const int64_t* prefix,
+                             const int64_t* prefix_host, int stages, int16_t* coefs, uint8_t* planes,
+                             int64_t coef_blocks, uint8_t* out, int64_t out_bytes, int32_t* status, int chunk_bytes,
+                             void* stream);
+
+/* coclr_resize_boxes_u8 for frames that differ in size from clip to clip: `frames` is ONE flat byte buffer of nbytes
+ * bytes, 16-byte aligned, and a descriptor is int32 [14]: the ten words of coclr_resize_boxes_u8 ({first frame} is
+ * not read) followed by {byte offset of the clip's first frame, low word; high word; W; H} of the clip's T frames,
+ * which follow each other at W * H * 3 bytes rounded up to 16.  The same kernel body; the box is clamped to, and checked against, the
+ * clip's OWN frame.  Clips may share frames.  The LDS band is sized by the tallest box of the launch, as there.
+ * COCLR_EINVAL before any launch: what coclr_resize_boxes_u8 refuses; nbytes < 1; an offset that is negative, not a
+ * multiple of 16 or whose T frames leave the buffer; W or H < 1; a box that leaves its own W x H frame (whether or not
+ * it would fit a larger frame of the batch).
+ * Additive: the ABI number stays 25 -- no existing signature or behaviour changed. */
+int coclr_resize_boxes_ragged_u8(const uint8_t* frames, int64_t nbytes, const int32_t* desc, const int32_t* desc_host,
+                                 int n_clips, int T, int S, const int32_t* xtab, int64_t xlen, const int32_t* ytab,
+                                 int64_t ylen, uint8_t* out, void* stream);
+
+/* coclr_resize2_boxes for frames that differ in size from clip to clip: `frames` and the four trailing descriptor
+ * words as coclr_resize_boxes_ragged_u8 (a descriptor is int32 [18]); everything else as coclr_resize2_boxes, the
+ * region clamped to and checked against the clip's own frame.
+ * COCLR_EINVAL before any launch: what coclr_resize2_boxes refuses, and what coclr_resize_boxes_ragged_u8 refuses of
+ * the buffer, the offsets and the frame sizes.
+ * Additive: the ABI number stays 25 -- no existing signature or behaviour changed. */
+int coclr_resize2_boxes_ragged(const uint8_t* frames, int64_t nbytes, const int32_t* desc, const int32_t* desc_host,
+                               int n_clips, int T, int size, int S, const int32_t* xtab, int64_t xlen,
+                               const int32_t* ytab, int64_t ylen, const int32_t* tab2, int64_t len2, int taps2,
+                               const float* mean, const float* std, uint8_t* out8, float* out, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* Evaluation consumers (model/classifier.py:47-61; eval/main_classifier.py) */
 /* ------------------------------------------------------------------------ */
