@@ -265,10 +265,19 @@ def pack(raws):
     return torch.from_numpy(data.copy()), torch.from_numpy(meta)
 
 
-def _geometry(meta):
+def _host_meta(meta):
     if not isinstance(meta, torch.Tensor) or meta.dtype != torch.int32 or meta.dim() != 2 or meta.is_cuda or \
             meta.shape[0] < 1 or meta.shape[1] <= 8 + META_SEG:
-        raise ValueError("coclr_amd: meta must be the host int32 (F, width) tensor of jpeg.pack")
+        raise ValueError("coclr_amd: meta must be the host int32 (F, width) tensor of jpeg.pack / jpeg.cat_ragged")
+
+
+def _flat_data(data):
+    if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() != 1:
+        raise ValueError("coclr_amd: data must be the flat uint8 tensor of jpeg.pack")
+
+
+def _geometry(meta):
+    _host_meta(meta)
     head = meta[:, :8]
     if not bool((head == head[0]).all()):
         raise ValueError("coclr_amd: the frames of one decode share size, components and sampling")
@@ -279,14 +288,13 @@ def _geometry(meta):
     return H, W, ncomp, hs, vs
 
 
-def cat(packs):
-    """The packs of a batch -> one (data, meta): the default collate cannot stack ragged bytes.  Byte offsets are
-    shifted, and descriptors are padded to the widest pack (the one with the most restart segments)."""
+def _cat(packs, who, one_geometry):
+    """The body of cat and cat_ragged: each pack on its own is one `pack` wrote, and with `one_geometry` all agree."""
     packs = list(packs)
     if not packs:
-        raise ValueError("coclr_amd: cat needs at least one pack")
+        raise ValueError("coclr_amd: %s needs at least one pack" % who)
     geo = [_geometry(m) for _, m in packs]
-    if any(g != geo[0] for g in geo):
+    if one_geometry and any(g != geo[0] for g in geo):
         raise Unsupported("packs differ in size, components or sampling: %s" % sorted(set(geo)))
     width = max(m.shape[1] for _, m in packs)
     rows, offset = [], 0
@@ -302,11 +310,22 @@ def cat(packs):
     return torch.cat([d for d, _ in packs]), torch.cat(rows)
 
 
-def check_meta(data, meta):
-    """What coclr_jpeg_decode checks, said in words, before anything is uploaded."""
-    H, W, ncomp, hs, vs = _geometry(meta)
-    if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() != 1:
-        raise ValueError("coclr_amd: data must be the flat uint8 tensor of jpeg.pack")
+def cat(packs):
+    """The packs of a batch -> one (data, meta): the default collate cannot stack ragged bytes.  Byte offsets are
+    shifted, and descriptors are padded to the widest pack (the one with the most restart segments)."""
+    return _cat(packs, "cat", True)
+
+
+def cat_ragged(packs):
+    """`cat` for packs that DIFFER in size, components or sampling (videos that keep their own aspect ratio): byte
+    offsets are shifted and descriptors padded to the widest pack as there, and every row keeps its own 8-word
+    geometry head, which is what decode_ragged reads.  Packs of one geometry give exactly `cat`'s result."""
+    return _cat(packs, "cat_ragged", False)
+
+
+def _check_rows(data, meta, H, W, ncomp, hs, vs):
+    """What the decode entry points check of every frame's row, said in words, before anything is uploaded.  The
+    geometry is per frame, int64 (F,) tensors; where all frames share one, plain integers do (they broadcast)."""
     m = meta[:, 8:].to(torch.int64)
     n, width = data.numel(), m.shape[1]
     mcus = -(-W // (8 * hs)) * -(-H // (8 * vs))
@@ -315,49 +334,31 @@ def check_meta(data, meta):
         raise ValueError("coclr_amd: a frame's bytes leave the buffer of %d bytes" % n)
     want = torch.where(ri > 0, -(-mcus // ri.clamp(min=1)), torch.ones_like(ri))
     if bool(((ri < 0) | (nseg != want) | (nseg > width - META_SEG)).any()):
-        raise ValueError("coclr_amd: a frame's restart segments do not match its interval (%d MCUs per frame)" % mcus)
+        raise ValueError("coclr_amd: a frame's restart segments do not match its interval and its MCU count")
     seg = m[:, META_SEG:]
     live = torch.arange(seg.shape[1])[None, :] < nseg[:, None]
     prev = torch.cat([torch.zeros_like(seg[:, :1]), seg[:, :-1]], 1)
     if bool((live & ((seg < prev) | (seg > ln[:, None]))).any()):
         raise ValueError("coclr_amd: a restart segment's offset decreases or leaves its frame's bytes")
-    q = m[:, META_QUANT:META_QUANT + 64 * ncomp]
-    if bool(((q < 0) | (q > 255)).any()):
-        raise ValueError("coclr_amd: a quantiser outside 0..255")
-    return H, W, ncomp, hs, vs
+    q = m[:, META_QUANT:META_QUANT + 192]
+    bad = (q < 0) | (q > 255)
+    if bool(bad.any()) and bool((bad & (torch.arange(192) < 64 * torch.as_tensor(ncomp)[..., None])).any()):
+        raise ValueError("coclr_amd: a quantiser outside 0..255")       # (in a component the frame has)
 
 
-def cat_ragged(packs):
-    """`cat` for packs that DIFFER in size, components or sampling (videos that keep their own aspect ratio): byte
-    offsets are shifted and descriptors padded to the widest pack as there, and every row keeps its own 8-word
-    geometry head, which is what decode_ragged reads.  Packs of one geometry give exactly `cat`'s result."""
-    packs = list(packs)
-    if not packs:
-        raise ValueError("coclr_amd: cat_ragged needs at least one pack")
-    for _, m in packs:
-        _geometry(m)                                     # each pack on its own is one `pack` wrote
-    width = max(m.shape[1] for _, m in packs)
-    rows, offset = [], 0
-    for data, m in packs:
-        r = torch.zeros(m.shape[0], width, dtype=torch.int32)
-        r[:, :m.shape[1]] = m
-        r[:, 0] = width
-        r[:, 8] += offset
-        offset += data.numel()
-        rows.append(r)
-    if offset > 0x7fffffff:
-        raise ValueError("coclr_amd: one decode takes up to 2 GiB of compressed bytes")
-    return torch.cat([d for d, _ in packs]), torch.cat(rows)
+def check_meta(data, meta):
+    """What coclr_jpeg_decode checks, said in words, before anything is uploaded."""
+    geo = _geometry(meta)
+    _flat_data(data)
+    _check_rows(data, meta, *geo)
+    return geo
 
 
 def check_meta_ragged(data, meta):
     """check_meta for the rows of cat_ragged, each against its OWN geometry head -> int64 (F, 5): H, W, components,
     hs, vs per frame."""
-    if not isinstance(meta, torch.Tensor) or meta.dtype != torch.int32 or meta.dim() != 2 or meta.is_cuda or \
-            meta.shape[0] < 1 or meta.shape[1] <= 8 + META_SEG:
-        raise ValueError("coclr_amd: meta must be the host int32 (F, width) tensor of jpeg.pack / jpeg.cat_ragged")
-    if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() != 1:
-        raise ValueError("coclr_amd: data must be the flat uint8 tensor of jpeg.pack")
+    _host_meta(meta)
+    _flat_data(data)
     head = meta[:, :8].to(torch.int64)
     if bool((head[:, 0] != meta.shape[1]).any()):
         raise ValueError("coclr_amd: meta is %d words wide and a row says otherwise" % meta.shape[1])
@@ -366,25 +367,7 @@ def check_meta_ragged(data, meta):
     geo = head[:, 1:6]
     for g in sorted(set(tuple(r) for r in geo.tolist())):
         ops.jpeg_workspace(*g)                           # refuses a geometry the kernels do not take
-    H, W, ncomp, hs, vs = geo.unbind(1)
-    m = meta[:, 8:].to(torch.int64)
-    n, width = data.numel(), m.shape[1]
-    mcus = -(-W // (8 * hs)) * -(-H // (8 * vs))
-    off, ln, ri, nseg = m[:, 0], m[:, 1], m[:, 2], m[:, 3]
-    if bool(((off < 0) | (ln < 0) | (off + ln > n)).any()):
-        raise ValueError("coclr_amd: a frame's bytes leave the buffer of %d bytes" % n)
-    want = torch.where(ri > 0, -(-mcus // ri.clamp(min=1)), torch.ones_like(ri))
-    if bool(((ri < 0) | (nseg != want) | (nseg > width - META_SEG)).any()):
-        raise ValueError("coclr_amd: a frame's restart segments do not match its interval and its own MCU count")
-    seg = m[:, META_SEG:]
-    live = torch.arange(seg.shape[1])[None, :] < nseg[:, None]
-    prev = torch.cat([torch.zeros_like(seg[:, :1]), seg[:, :-1]], 1)
-    if bool((live & ((seg < prev) | (seg > ln[:, None]))).any()):
-        raise ValueError("coclr_amd: a restart segment's offset decreases or leaves its frame's bytes")
-    q = m[:, META_QUANT:META_QUANT + 192]
-    used = torch.arange(192)[None, :] < 64 * ncomp[:, None]
-    if bool((used & ((q < 0) | (q > 255))).any()):
-        raise ValueError("coclr_amd: a quantiser outside 0..255")
+    _check_rows(data, meta, *geo.unbind(1))
     return geo.contiguous()
 
 

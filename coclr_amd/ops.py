@@ -1071,26 +1071,61 @@ def augment_clips(frames, kinds, params, group_size, T, mean, std, out, host_tab
     _program_call("augment_clips", frames, kinds, params, group_size, T, mean, std, out, host_tables)
 
 
+def _clip_source(frames, desc, desc_host, fields, ragged):
+    """What the four resize wrappers check first: the frames -- (F, H, W, 3), or with `ragged` one flat byte buffer of
+    frames that differ in size from clip to clip -- and the descriptors, `fields` words per clip, on the device and on
+    the host.  Returns what the entry point takes beside the frames' pointer: F, H, W, or the number of bytes."""
+    if ragged:
+        if frames.dim() != 1 or frames.dtype != torch.uint8 or not frames.is_contiguous():
+            raise ValueError("coclr_amd: ragged frames are one flat contiguous uint8 buffer")
+    elif frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise ValueError("coclr_amd: frames must be contiguous (F, H, W, 3), got %s" % (tuple(frames.shape),))
+    if desc.dim() != 2 or desc.shape[1] != fields or desc.shape != desc_host.shape or desc_host.is_cuda or \
+            desc_host.dtype != torch.int32 or not desc.is_contiguous() or not desc_host.is_contiguous():
+        raise ValueError("coclr_amd: clip descriptors must be contiguous int32 (n_clips, %d), device and host" % fields)
+    return (frames.numel(),) if ragged else tuple(frames.shape[:3])
+
+
+def _resize_boxes(name, ragged, frames, desc, desc_host, xtab, ytab, T, S, out):
+    src = _clip_source(frames, desc, desc_host, 14 if ragged else 10, ragged)
+    n_clips, T, S = desc.shape[0], int(T), int(S)
+    if xtab.dim() != 1 or ytab.dim() != 1 or not xtab.is_contiguous() or not ytab.is_contiguous():
+        raise ValueError("coclr_amd: %s needs flat contiguous table buffers" % name)
+    if tuple(out.shape) != (n_clips * T, S, S, 3) or not out.is_contiguous():
+        raise ValueError("coclr_amd: out must be contiguous %s, got %s" % ((n_clips * T, S, S, 3), tuple(out.shape)))
+    i32 = torch.int32
+    _lib.check(getattr(_L(), "coclr_" + name)(
+        _p(frames, torch.uint8), *src, _p(desc, i32), C.cast(desc_host.data_ptr(), C.POINTER(C.c_int32)), n_clips,
+        T, S, _p(xtab, i32), xtab.numel(), _p(ytab, i32), ytab.numel(), _p(out, torch.uint8), _stream()), name)
+
+
+def _resize2_boxes(name, ragged, frames, desc, desc_host, xtab, ytab, tab2, T, size, S, out, mean, std):
+    src = _clip_source(frames, desc, desc_host, 18 if ragged else 14, ragged)
+    n_clips, T, size, S = desc.shape[0], int(T), int(size), int(S)
+    Sp = (S + 3) & ~3
+    if xtab.dim() != 1 or ytab.dim() != 1 or not xtab.is_contiguous() or not ytab.is_contiguous():
+        raise ValueError("coclr_amd: %s needs flat contiguous stage-1 table buffers" % name)
+    if tab2.dim() != 2 or tab2.shape[0] < 2 or tab2.shape[1] != Sp or not tab2.is_contiguous():
+        raise ValueError("coclr_amd: the stage-2 table must be contiguous (1 + taps, %d), got %s" % (Sp, tuple(tab2.shape)))
+    u8 = out.dtype == torch.uint8
+    if not u8 and (mean is None or std is None):
+        raise ValueError("coclr_amd: the fp32 form of %s needs mean and std" % name)
+    want = (n_clips * T, S, S, 3) if u8 else (n_clips, 3, T, S, S)
+    if tuple(out.shape) != want or not out.is_contiguous():
+        raise ValueError("coclr_amd: out must be contiguous %s, got %s" % (want, tuple(out.shape)))
+    m, s = (None, None) if u8 else [(C.c_float * 3)(*[float(v) for v in t]) for t in (mean, std)]
+    i32 = torch.int32
+    _lib.check(getattr(_L(), "coclr_" + name)(
+        _p(frames, torch.uint8), *src, _p(desc, i32), C.cast(desc_host.data_ptr(), C.POINTER(C.c_int32)), n_clips,
+        T, size, S, _p(xtab, i32), xtab.numel(), _p(ytab, i32), ytab.numel(), _p(tab2, i32), tab2.numel(),
+        tab2.shape[0] - 1, m, s, _p(out, torch.uint8) if u8 else None, None if u8 else _p(out), _stream()), name)
+
+
 def resize_boxes_u8(frames, desc, desc_host, xtab, ytab, T, S, out):
     """frames (F, H, W, 3) uint8; desc int32 (n_clips, 10) on the device and desc_host, the same on the host
     (include/coclr_hip.h); xtab / ytab the concatenated per-box tables, int32, device -> out (n_clips*T, S, S, 3)
     uint8: every clip's own box of its T frames resized to S x S."""
-    if frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
-        raise ValueError("coclr_amd: frames must be contiguous (F, H, W, 3), got %s" % (tuple(frames.shape),))
-    F, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
-    if desc.dim() != 2 or desc.shape[1] != 10 or desc.shape != desc_host.shape or desc_host.is_cuda or \
-            desc_host.dtype != torch.int32 or not desc.is_contiguous() or not desc_host.is_contiguous():
-        raise ValueError("coclr_amd: box descriptors must be contiguous int32 (n_clips, 10), device and host")
-    n_clips, T, S = desc.shape[0], int(T), int(S)
-    if xtab.dim() != 1 or ytab.dim() != 1 or not xtab.is_contiguous() or not ytab.is_contiguous():
-        raise ValueError("coclr_amd: resize_boxes_u8 needs flat contiguous table buffers")
-    if tuple(out.shape) != (n_clips * T, S, S, 3) or not out.is_contiguous():
-        raise ValueError("coclr_amd: out must be contiguous %s, got %s" % ((n_clips * T, S, S, 3), tuple(out.shape)))
-    i32 = torch.int32
-    _lib.check(_L().coclr_resize_boxes_u8(
-        _p(frames, torch.uint8), F, H, W, _p(desc, i32), C.cast(desc_host.data_ptr(), C.POINTER(C.c_int32)), n_clips,
-        T, S, _p(xtab, i32), xtab.numel(), _p(ytab, i32), ytab.numel(), _p(out, torch.uint8), _stream()),
-        "resize_boxes_u8")
+    _resize_boxes("resize_boxes_u8", False, frames, desc, desc_host, xtab, ytab, T, S, out)
 
 
 def resize2_boxes(frames, desc, desc_host, xtab, ytab, tab2, T, size, S, out, mean=None, std=None):
@@ -1099,33 +1134,7 @@ def resize2_boxes(frames, desc, desc_host, xtab, ytab, tab2, T, size, S, out, me
     one after the other, tab2 (1 + taps2, Sp) the shared size -> S table, all int32 on the device.  `out` uint8
     (n_clips*T, S, S, 3) takes the resized bytes; `out` fp32 (n_clips, 3, T, S, S) takes them normalised with
     `mean` / `std`."""
-    if frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
-        raise ValueError("coclr_amd: frames must be contiguous (F, H, W, 3), got %s" % (tuple(frames.shape),))
-    F, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
-    if desc.dim() != 2 or desc.shape[1] != 14 or desc.shape != desc_host.shape or desc_host.is_cuda or \
-            desc_host.dtype != torch.int32 or not desc.is_contiguous() or not desc_host.is_contiguous():
-        raise ValueError("coclr_amd: clip descriptors must be contiguous int32 (n_clips, 14), device and host")
-    n_clips, T, size, S = desc.shape[0], int(T), int(size), int(S)
-    Sp = (S + 3) & ~3
-    if xtab.dim() != 1 or ytab.dim() != 1 or not xtab.is_contiguous() or not ytab.is_contiguous():
-        raise ValueError("coclr_amd: resize2_boxes needs flat contiguous stage-1 table buffers")
-    if tab2.dim() != 2 or tab2.shape[0] < 2 or tab2.shape[1] != Sp or not tab2.is_contiguous():
-        raise ValueError("coclr_amd: the stage-2 table must be contiguous (1 + taps, %d), got %s" % (Sp, tuple(tab2.shape)))
-    i32 = torch.int32
-    if out.dtype == torch.uint8:
-        want, o8, of, m, s = (n_clips * T, S, S, 3), _p(out, torch.uint8), None, None, None
-    else:
-        if mean is None or std is None:
-            raise ValueError("coclr_amd: the fp32 form of resize2_boxes needs mean and std")
-        want, o8, of = (n_clips, 3, T, S, S), None, _p(out)
-        m = (C.c_float * 3)(*[float(v) for v in mean])
-        s = (C.c_float * 3)(*[float(v) for v in std])
-    if tuple(out.shape) != want or not out.is_contiguous():
-        raise ValueError("coclr_amd: out must be contiguous %s, got %s" % (want, tuple(out.shape)))
-    _lib.check(_L().coclr_resize2_boxes(
-        _p(frames, torch.uint8), F, H, W, _p(desc, i32), C.cast(desc_host.data_ptr(), C.POINTER(C.c_int32)), n_clips,
-        T, size, S, _p(xtab, i32), xtab.numel(), _p(ytab, i32), ytab.numel(), _p(tab2, i32), tab2.numel(),
-        tab2.shape[0] - 1, m, s, o8, of, _stream()), "resize2_boxes")
+    _resize2_boxes("resize2_boxes", False, frames, desc, desc_host, xtab, ytab, tab2, T, size, S, out, mean, std)
 
 
 def jpeg_workspace(H, W, ncomp, hs, vs):
@@ -1138,27 +1147,36 @@ def jpeg_workspace(H, W, ncomp, hs, vs):
     return a.value, b.value
 
 
-def jpeg_decode(data, meta, meta_host, H, W, ncomp, hs, vs, coefs, planes, out, status, stages=7, chunk_bytes=0):
-    """data uint8 (n,), meta int32 (F, width) on the device and meta_host, the same on the host (include/coclr_hip.h:
-    coclr_jpeg_decode) -> out uint8 (F, H, W, 3), status int32 (F,).  coefs int16 / planes uint8: flat workspaces of
-    F times jpeg_workspace().  `stages`: 1 entropy, 2 inverse DCT, 4 colour; 7 = all three.  `chunk_bytes`: 0, or
-    8..65536 to decode frames without restart markers on a lane per chunk of that many bytes
-    (coclr_jpeg_decode_split); the results are the same bit for bit."""
+def _decode_frames(chunk_bytes, meta, meta_host):
+    """What the two decode wrappers check first -> (chunk_bytes, F, width)."""
     chunk_bytes = int(chunk_bytes)
     if chunk_bytes != 0 and not 8 <= chunk_bytes <= 65536:
         raise ValueError("coclr_amd: chunk_bytes must be 0 or in 8..65536, got %d" % chunk_bytes)
     if meta.dim() != 2 or meta.shape != meta_host.shape or meta_host.is_cuda or meta_host.dtype != torch.int32 or \
             not meta.is_contiguous() or not meta_host.is_contiguous():
         raise ValueError("coclr_amd: frame descriptors must be contiguous int32 (F, width), device and host")
-    F, width = meta.shape
+    return (chunk_bytes,) + tuple(meta.shape)
+
+
+def _check_status(status, F):
+    if tuple(status.shape) != (F,) or not status.is_contiguous():
+        raise ValueError("coclr_amd: status must be contiguous (%d,), got %s" % (F, tuple(status.shape)))
+
+
+def jpeg_decode(data, meta, meta_host, H, W, ncomp, hs, vs, coefs, planes, out, status, stages=7, chunk_bytes=0):
+    """data uint8 (n,), meta int32 (F, width) on the device and meta_host, the same on the host (include/coclr_hip.h:
+    coclr_jpeg_decode) -> out uint8 (F, H, W, 3), status int32 (F,).  coefs int16 / planes uint8: flat workspaces of
+    F times jpeg_workspace().  `stages`: 1 entropy, 2 inverse DCT, 4 colour; 7 = all three.  `chunk_bytes`: 0, or
+    8..65536 to decode frames without restart markers on a lane per chunk of that many bytes
+    (coclr_jpeg_decode_split); the results are the same bit for bit."""
+    chunk_bytes, F, width = _decode_frames(chunk_bytes, meta, meta_host)
     cb, pb = jpeg_workspace(H, W, ncomp, hs, vs)
     if data.dim() != 1 or not data.is_contiguous() or coefs.numel() * 2 < F * cb or planes.numel() < F * pb or \
             not coefs.is_contiguous() or not planes.is_contiguous():
         raise ValueError("coclr_amd: jpeg_decode needs flat bytes and workspaces of %d + %d bytes per frame" % (cb, pb))
     if tuple(out.shape) != (F, H, W, 3) or not out.is_contiguous():
         raise ValueError("coclr_amd: out must be contiguous %s, got %s" % ((F, H, W, 3), tuple(out.shape)))
-    if tuple(status.shape) != (F,) or not status.is_contiguous():
-        raise ValueError("coclr_amd: status must be contiguous (%d,), got %s" % (F, tuple(status.shape)))
+    _check_status(status, F)
     args = (_p(data, torch.uint8), data.numel(), _p(meta, torch.int32),
             C.cast(meta_host.data_ptr(), C.POINTER(C.c_int32)), F, width, int(H), int(W), int(ncomp), int(hs), int(vs),
             int(stages), _p(coefs, torch.int16), _p(planes, torch.uint8), _p(out, torch.uint8),
@@ -1177,13 +1195,7 @@ def jpeg_decode_ragged(data, meta, meta_host, geom, geom_host, prefix, prefix_ho
     """jpeg_decode for frames that differ in geometry (include/coclr_hip.h: coclr_jpeg_decode_ragged): geom int64
     (F, 8) and prefix int64 (2, F + 1) on the device and the same two on the host; coefs int16 / planes uint8 flat
     workspaces of the same number of blocks; out the flat uint8 buffer every frame's first output byte points into."""
-    chunk_bytes = int(chunk_bytes)
-    if chunk_bytes != 0 and not 8 <= chunk_bytes <= 65536:
-        raise ValueError("coclr_amd: chunk_bytes must be 0 or in 8..65536, got %d" % chunk_bytes)
-    if meta.dim() != 2 or meta.shape != meta_host.shape or meta_host.is_cuda or meta_host.dtype != torch.int32 or \
-            not meta.is_contiguous() or not meta_host.is_contiguous():
-        raise ValueError("coclr_amd: frame descriptors must be contiguous int32 (F, width), device and host")
-    F, width = meta.shape
+    chunk_bytes, F, width = _decode_frames(chunk_bytes, meta, meta_host)
     for dev, host, want, what in ((geom, geom_host, (F, JR_FIELDS), "geometry table"),
                                   (prefix, prefix_host, (2, F + 1), "prefix arrays")):
         if tuple(dev.shape) != want or tuple(host.shape) != want or host.is_cuda or host.dtype != torch.int64 or \
@@ -1193,8 +1205,7 @@ def jpeg_decode_ragged(data, meta, meta_host, geom, geom_host, prefix, prefix_ho
     if data.dim() != 1 or not data.is_contiguous() or out.dim() != 1 or not out.is_contiguous() or \
             not coefs.is_contiguous() or not planes.is_contiguous() or blocks < 1:
         raise ValueError("coclr_amd: jpeg_decode_ragged needs flat bytes, flat workspaces and a flat output")
-    if tuple(status.shape) != (F,) or not status.is_contiguous():
-        raise ValueError("coclr_amd: status must be contiguous (%d,), got %s" % (F, tuple(status.shape)))
+    _check_status(status, F)
     hp = lambda t, ty: C.cast(t.data_ptr(), C.POINTER(ty))                   # noqa: E731
     _lib.check(_L().coclr_jpeg_decode_ragged(
         _p(data, torch.uint8), data.numel(), _p(meta, torch.int32), hp(meta_host, C.c_int32), F, width,
@@ -1203,57 +1214,18 @@ def jpeg_decode_ragged(data, meta, meta_host, geom, geom_host, prefix, prefix_ho
         _p(status, torch.int32), chunk_bytes, _stream()), "jpeg_decode_ragged")
 
 
-def _ragged_desc(pixels, desc, desc_host, fields):
-    if pixels.dim() != 1 or pixels.dtype != torch.uint8 or not pixels.is_contiguous():
-        raise ValueError("coclr_amd: ragged frames are one flat contiguous uint8 buffer")
-    if desc.dim() != 2 or desc.shape[1] != fields or desc.shape != desc_host.shape or desc_host.is_cuda or \
-            desc_host.dtype != torch.int32 or not desc.is_contiguous() or not desc_host.is_contiguous():
-        raise ValueError("coclr_amd: ragged descriptors must be contiguous int32 (n_clips, %d), device and host" % fields)
-
-
 def resize_boxes_ragged_u8(pixels, desc, desc_host, xtab, ytab, T, S, out):
     """resize_boxes_u8 over a flat byte buffer of frames that differ in size from clip to clip: desc int32
     (n_clips, 14), the ten words of resize_boxes_u8 then {offset low, offset high, W, H} of the clip's frames
     (include/coclr_hip.h: coclr_resize_boxes_ragged_u8)."""
-    _ragged_desc(pixels, desc, desc_host, 14)
-    n_clips, T, S = desc.shape[0], int(T), int(S)
-    if xtab.dim() != 1 or ytab.dim() != 1 or not xtab.is_contiguous() or not ytab.is_contiguous():
-        raise ValueError("coclr_amd: resize_boxes_ragged_u8 needs flat contiguous table buffers")
-    if tuple(out.shape) != (n_clips * T, S, S, 3) or not out.is_contiguous():
-        raise ValueError("coclr_amd: out must be contiguous %s, got %s" % ((n_clips * T, S, S, 3), tuple(out.shape)))
-    i32 = torch.int32
-    _lib.check(_L().coclr_resize_boxes_ragged_u8(
-        _p(pixels, torch.uint8), pixels.numel(), _p(desc, i32), C.cast(desc_host.data_ptr(), C.POINTER(C.c_int32)),
-        n_clips, T, S, _p(xtab, i32), xtab.numel(), _p(ytab, i32), ytab.numel(), _p(out, torch.uint8), _stream()),
-        "resize_boxes_ragged_u8")
+    _resize_boxes("resize_boxes_ragged_u8", True, pixels, desc, desc_host, xtab, ytab, T, S, out)
 
 
 def resize2_boxes_ragged(pixels, desc, desc_host, xtab, ytab, tab2, T, size, S, out, mean=None, std=None):
     """resize2_boxes over a flat byte buffer of frames that differ in size from clip to clip: desc int32 (n_clips, 18),
     the fourteen words of resize2_boxes then {offset low, offset high, W, H} (include/coclr_hip.h:
     coclr_resize2_boxes_ragged)."""
-    _ragged_desc(pixels, desc, desc_host, 18)
-    n_clips, T, size, S = desc.shape[0], int(T), int(size), int(S)
-    Sp = (S + 3) & ~3
-    if xtab.dim() != 1 or ytab.dim() != 1 or not xtab.is_contiguous() or not ytab.is_contiguous():
-        raise ValueError("coclr_amd: resize2_boxes_ragged needs flat contiguous stage-1 table buffers")
-    if tab2.dim() != 2 or tab2.shape[0] < 2 or tab2.shape[1] != Sp or not tab2.is_contiguous():
-        raise ValueError("coclr_amd: the stage-2 table must be contiguous (1 + taps, %d), got %s" % (Sp, tuple(tab2.shape)))
-    i32 = torch.int32
-    if out.dtype == torch.uint8:
-        want, o8, of, m, s = (n_clips * T, S, S, 3), _p(out, torch.uint8), None, None, None
-    else:
-        if mean is None or std is None:
-            raise ValueError("coclr_amd: the fp32 form of resize2_boxes_ragged needs mean and std")
-        want, o8, of = (n_clips, 3, T, S, S), None, _p(out)
-        m = (C.c_float * 3)(*[float(v) for v in mean])
-        s = (C.c_float * 3)(*[float(v) for v in std])
-    if tuple(out.shape) != want or not out.is_contiguous():
-        raise ValueError("coclr_amd: out must be contiguous %s, got %s" % (want, tuple(out.shape)))
-    _lib.check(_L().coclr_resize2_boxes_ragged(
-        _p(pixels, torch.uint8), pixels.numel(), _p(desc, i32), C.cast(desc_host.data_ptr(), C.POINTER(C.c_int32)),
-        n_clips, T, size, S, _p(xtab, i32), xtab.numel(), _p(ytab, i32), ytab.numel(), _p(tab2, i32), tab2.numel(),
-        tab2.shape[0] - 1, m, s, o8, of, _stream()), "resize2_boxes_ragged")
+    _resize2_boxes("resize2_boxes_ragged", True, pixels, desc, desc_host, xtab, ytab, tab2, T, size, S, out, mean, std)
 
 
 def _program_call(name, frames, kinds, params, group_size, T, mean, std, out, host_tables):

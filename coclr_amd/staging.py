@@ -248,6 +248,8 @@ def check_crops(boxes, flips, cw, ch, W, H):
 
 # op kinds of a program, as csrc/staging.hip takes them: [(kind, parameter)] in order of application
 JITTER_NOP, JITTER_BRIGHTNESS, JITTER_CONTRAST, JITTER_SATURATION, JITTER_HUE, JITTER_GRAY = range(6)
+AUGMENT_BLUR, AUGMENT_FLIP = 6, 7       # the two kinds coclr_augment_clips adds to the six of the jitter
+BLUR_MAX_RADIUS = 16.0                  # the kernel's design limit; the reference's sigma in [0.1, 2] needs 1.375
 JITTER_MAX_OPS = 8
 JITTER_MAX_PIXELS = 224 * 224        # one workgroup holds the frame in LDS
 
@@ -309,37 +311,71 @@ class ColorJitter:
         return programs
 
 
+def _check_op(kind, value, n_kinds, word):
+    """One op of a program -> (kind, parameter as the kernel takes it): kinds 0..5 of the jitter, and with n_kinds = 8
+    the blur and the flip of the training transform."""
+    if isinstance(kind, bool) or kind not in range(n_kinds) or int(kind) != kind:
+        raise ValueError("coclr_amd: no %s op kind %r" % (word, kind))
+    kind, value = int(kind), float(value)
+    if kind == AUGMENT_FLIP:
+        return kind, 0.0
+    if kind == AUGMENT_BLUR:
+        if not 0.0 <= value <= BLUR_MAX_RADIUS:
+            raise ValueError("coclr_amd: a blur box radius lies in [0, %g] (blur_box_radius), got %r" %
+                             (BLUR_MAX_RADIUS, value))
+    elif kind == JITTER_HUE and not (0 <= value <= 255 and value == int(value)):
+        raise ValueError("coclr_amd: a hue shift is a byte (hue_shift_byte), got %r" % (value,))
+    elif kind == JITTER_GRAY and value not in (0.0, 1.0, 2.0):
+        raise ValueError("coclr_amd: gray takes channel 0, 1 or 2, got %r" % (value,))
+    elif not math.isfinite(value):
+        raise ValueError("coclr_amd: jitter factor %r is not finite" % (value,))
+    return kind, value
+
+
+def _program_tables(programs, n_kinds, word):
+    """The body of program_tables and augment_tables.  A batch names few distinct programs (one per clip, or per frame
+    of a gray clip), so each is checked once."""
+    programs = [list(prog) for prog in programs]
+    if not programs:
+        raise ValueError("coclr_amd: need at least one %s program" % word)
+    P = max(1, max(len(prog) for prog in programs))
+    if P > JITTER_MAX_OPS:
+        raise ValueError("coclr_amd: one %s program has %d ops, the kernel takes %d" % (word, P, JITTER_MAX_OPS))
+    rows, kinds, params = {}, [], []
+    for prog in programs:
+        key = tuple(tuple(op) for op in prog)
+        if key not in rows:
+            checked = [_check_op(kind, value, n_kinds, word) for kind, value in prog] + [(0, 0.0)] * (P - len(prog))
+            rows[key] = ([k for k, _ in checked], [v for _, v in checked])
+        kinds.append(rows[key][0])
+        params.append(rows[key][1])
+    return torch.from_numpy(np.array(kinds, dtype=np.int32)), torch.from_numpy(np.array(params, dtype=np.float32))
+
+
 def program_tables(programs):
     """[[(kind, parameter)]] -> host tables (kinds int32 (G, P), params fp32 (G, P)), P = the longest program
     (at least 1), shorter ones padded with no-ops.  Refuses what the kernel does not know."""
-    programs = [list(prog) for prog in programs]
-    if not programs:
-        raise ValueError("coclr_amd: need at least one jitter program")
-    P = max(1, max(len(prog) for prog in programs))
-    if P > JITTER_MAX_OPS:
-        raise ValueError("coclr_amd: a jitter program has %d ops, the kernel takes %d" % (P, JITTER_MAX_OPS))
-    kinds = torch.zeros(len(programs), P, dtype=torch.int32)
-    params = torch.zeros(len(programs), P, dtype=torch.float32)
-    for g, prog in enumerate(programs):
-        for j, (kind, value) in enumerate(prog):
-            if kind not in range(6) or isinstance(kind, bool) or int(kind) != kind:
-                raise ValueError("coclr_amd: no jitter op kind %r" % (kind,))
-            value = float(value)
-            if kind == JITTER_HUE and not (0 <= value <= 255 and value == int(value)):
-                raise ValueError("coclr_amd: a hue shift is a byte (hue_shift_byte), got %r" % (value,))
-            if kind == JITTER_GRAY and value not in (0.0, 1.0, 2.0):
-                raise ValueError("coclr_amd: gray takes channel 0, 1 or 2, got %r" % (value,))
-            if not math.isfinite(value):
-                raise ValueError("coclr_amd: jitter factor %r is not finite" % (value,))
-            kinds[g, j], params[g, j] = int(kind), value
-    return kinds, params
+    return _program_tables(programs, 6, "jitter")
 
 
-def color_jitter(frames_u8, programs, group_size, T, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None, device=None):
-    """ColorJitter / RandomGray -> ToTensor -> Normalize of `frames_u8` (N, H, W, 3) uint8 (host or device) in ONE
-    launch: (N/T, 3, T, H, W) fp32 on the device, frame n at clip n // T, position n % T, after running program
-    n // group_size of `programs` ([[(kind, parameter)]], e.g. ColorJitter.draw).  Bit-identical to the
-    reference's PIL ops; an empty program is ToTensor + Normalize alone.  Frames up to 224 x 224."""
+def _upload(frames_u8, device):
+    """`frames_u8` contiguous on `device`, which defaults to the frames' own device, or the current GPU; a batch
+    (B, n, H, W, 3) as its B * n frames."""
+    if device is None:
+        device = frames_u8.device if frames_u8.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    frames = frames_u8.contiguous().to(device)
+    return frames.flatten(0, 1) if frames.dim() == 5 else frames
+
+
+def _check_out(out, shape, fp32=False):
+    if out is not None and (tuple(out.shape) != shape or not out.is_contiguous() or
+                            (fp32 and out.dtype != torch.float32)):
+        raise ValueError("coclr_amd: out must be contiguous %s%s, got %s" %
+                         ("fp32 " if fp32 else "", shape, tuple(out.shape)))
+
+
+def _run_programs(launch, tables, what, frames_u8, programs, group_size, T, mean, std, out, device):
+    """The body of color_jitter and augment: `tables` makes the host tables of `programs`, `launch` runs them."""
     if frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or frames_u8.dtype != torch.uint8:
         raise ValueError("coclr_amd: frames must be uint8 (N, H, W, 3), got %s %s" %
                          (frames_u8.dtype, tuple(frames_u8.shape)))
@@ -348,19 +384,26 @@ def color_jitter(frames_u8, programs, group_size, T, mean=IMAGENET_MEAN, std=IMA
     if N < 1 or T < 1 or N % T != 0:
         raise ValueError("coclr_amd: %d frames do not make clips of %d" % (N, T))
     if H * W > JITTER_MAX_PIXELS or H * W < 1:
-        raise ValueError("coclr_amd: color_jitter takes frames of up to 224 x 224 pixels, got %d x %d" % (H, W))
-    kinds, params = program_tables(programs)
+        raise ValueError("coclr_amd: %s takes frames of up to 224 x 224 pixels, got %d x %d" % (what, H, W))
+    kinds, params = tables(programs)
     if group_size < 1 or kinds.shape[0] * group_size < N:
         raise ValueError("coclr_amd: %d programs for groups of %d frames do not cover %d frames" %
                          (kinds.shape[0], group_size, N))
-    if device is None:
-        device = frames_u8.device if frames_u8.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    frames = frames_u8.contiguous().to(device)
+    frames = _upload(frames_u8, device)
     if out is None:
         out = torch.empty(N // T, 3, T, H, W, dtype=torch.float32, device=frames.device)
-    ops.color_jitter_clips(frames, kinds.to(device), params.to(device), group_size, T, mean, std, out,
-                           host_tables=(kinds, params))
+    launch(frames, kinds.to(frames.device), params.to(frames.device), group_size, T, mean, std, out,
+           host_tables=(kinds, params))
     return out
+
+
+def color_jitter(frames_u8, programs, group_size, T, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None, device=None):
+    """ColorJitter / RandomGray -> ToTensor -> Normalize of `frames_u8` (N, H, W, 3) uint8 (host or device) in ONE
+    launch: (N/T, 3, T, H, W) fp32 on the device, frame n at clip n // T, position n % T, after running program
+    n // group_size of `programs` ([[(kind, parameter)]], e.g. ColorJitter.draw).  Bit-identical to the
+    reference's PIL ops; an empty program is ToTensor + Normalize alone.  Frames up to 224 x 224."""
+    return _run_programs(ops.color_jitter_clips, program_tables, "color_jitter", frames_u8, programs, group_size, T,
+                         mean, std, out, device)
 
 
 def stage_crops_on_device(frames, slot_frame, crops, cw, ch, S, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None,
@@ -377,9 +420,7 @@ def stage_crops_on_device(frames, slot_frame, crops, cw, ch, S, mean=IMAGENET_ME
         if len(jitter) != len(crops):
             raise ValueError("coclr_amd: need one jitter program per crop, got %d programs and %d crops" %
                              (len(jitter), len(crops)))
-        if tuple(out.shape) != (len(crops), n_clips, 3, T, S, S) or not out.is_contiguous():
-            raise ValueError("coclr_amd: out must be contiguous %s, got %s" %
-                             ((len(crops), n_clips, 3, T, S, S), tuple(out.shape)))
+        _check_out(out, (len(crops), n_clips, 3, T, S, S))
         if S * S > JITTER_MAX_PIXELS:
             raise ValueError("coclr_amd: color_jitter takes frames of up to 224 x 224 pixels, got %d x %d" % (S, S))
         program_tables(jitter)                            # refuse a bad program before anything is launched
@@ -412,18 +453,12 @@ def stage_crops(frames_u8, frame_index, boxes, flips, crop_size, out_size, mean=
     cw, ch = _crop_wh(crop_size)
     crops = check_crops(boxes, flips, cw, ch, W, H)
     idx = check_frame_index(frame_index, F)
-    if device is None:
-        device = frames_u8.device if frames_u8.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    frames = frames_u8.contiguous().to(device)
-    if jitter is None:
-        return stage_crops_on_device(frames, idx.to(device), crops, cw, ch, int(out_size), mean, std, out)
-    return stage_crops_on_device(frames, idx.to(device), crops, cw, ch, int(out_size), mean, std, out, jitter)
+    frames = _upload(frames_u8, device)
+    return stage_crops_on_device(frames, idx.to(frames.device), crops, cw, ch, int(out_size), mean, std, out, jitter)
 
 
 # ---- the training transform (main_nce.py:366-392; utils/augmentation.py:90-216,357-444) -----------------------------
 
-AUGMENT_BLUR, AUGMENT_FLIP = 6, 7       # the two kinds coclr_augment_clips adds to the six of the jitter
-BLUR_MAX_RADIUS = 16.0                  # the kernel's design limit; the reference's sigma in [0.1, 2] needs 1.375
 PLAN_HEAD = 5                           # packed plan, per clip: half, x0, y0, w, h, then T x 8 kinds, T x 8 parameters
 
 
@@ -448,72 +483,17 @@ def blur_box_radius(sigma):
     return float(out)
 
 
-def _check_augment_op(kind, value):
-    """One op of an augment program -> (kind, parameter as the kernel takes it); the rules of program_tables for
-    kinds 0..5."""
-    if isinstance(kind, bool) or kind not in range(8) or int(kind) != kind:
-        raise ValueError("coclr_amd: no augment op kind %r" % (kind,))
-    kind, value = int(kind), float(value)
-    if kind == AUGMENT_FLIP:
-        return kind, 0.0
-    if kind == AUGMENT_BLUR:
-        if not 0.0 <= value <= BLUR_MAX_RADIUS:
-            raise ValueError("coclr_amd: a blur box radius lies in [0, %g] (blur_box_radius), got %r" %
-                             (BLUR_MAX_RADIUS, value))
-    elif kind == JITTER_HUE and not (0 <= value <= 255 and value == int(value)):
-        raise ValueError("coclr_amd: a hue shift is a byte (hue_shift_byte), got %r" % (value,))
-    elif kind == JITTER_GRAY and value not in (0.0, 1.0, 2.0):
-        raise ValueError("coclr_amd: gray takes channel 0, 1 or 2, got %r" % (value,))
-    elif not math.isfinite(value):
-        raise ValueError("coclr_amd: jitter factor %r is not finite" % (value,))
-    return kind, value
-
-
 def augment_tables(programs):
     """program_tables for coclr_augment_clips: kinds 0..5 as there, plus (6, r_f) -- blur, r_f from blur_box_radius,
-    0 <= r_f <= 16 -- and (7, anything) -- horizontal flip.  A batch names few distinct programs (one per clip, or
-    per frame of a gray clip), so each is checked once."""
-    programs = [list(prog) for prog in programs]
-    if not programs:
-        raise ValueError("coclr_amd: need at least one program")
-    P = max(1, max(len(prog) for prog in programs))
-    if P > JITTER_MAX_OPS:
-        raise ValueError("coclr_amd: a program has %d ops, the kernel takes %d" % (P, JITTER_MAX_OPS))
-    rows, kinds, params = {}, [], []
-    for prog in programs:
-        key = tuple(tuple(op) for op in prog)
-        if key not in rows:
-            checked = [_check_augment_op(kind, value) for kind, value in prog] + [(0, 0.0)] * (P - len(prog))
-            rows[key] = ([k for k, _ in checked], [v for _, v in checked])
-        kinds.append(rows[key][0])
-        params.append(rows[key][1])
-    return torch.tensor(kinds, dtype=torch.int32), torch.tensor(params, dtype=torch.float32)
+    0 <= r_f <= 16 -- and (7, anything) -- horizontal flip."""
+    return _program_tables(programs, 8, "augment")
 
 
 def augment(frames_u8, programs, group_size, T, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None, device=None):
     """color_jitter with the blur and the flip admitted (augment_tables): `frames_u8` (N, H, W, 3) uint8 ->
     (N/T, 3, T, H, W) fp32 on the device in one launch, frame n running program n // group_size."""
-    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or frames_u8.dtype != torch.uint8:
-        raise ValueError("coclr_amd: frames must be uint8 (N, H, W, 3), got %s %s" %
-                         (frames_u8.dtype, tuple(frames_u8.shape)))
-    N, H, W = frames_u8.shape[:3]
-    group_size, T = int(group_size), int(T)
-    if N < 1 or T < 1 or N % T != 0:
-        raise ValueError("coclr_amd: %d frames do not make clips of %d" % (N, T))
-    if H * W > JITTER_MAX_PIXELS or H * W < 1:
-        raise ValueError("coclr_amd: augment takes frames of up to 224 x 224 pixels, got %d x %d" % (H, W))
-    kinds, params = augment_tables(programs)
-    if group_size < 1 or kinds.shape[0] * group_size < N:
-        raise ValueError("coclr_amd: %d programs for groups of %d frames do not cover %d frames" %
-                         (kinds.shape[0], group_size, N))
-    if device is None:
-        device = frames_u8.device if frames_u8.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    frames = frames_u8.contiguous().to(device)
-    if out is None:
-        out = torch.empty(N // T, 3, T, H, W, dtype=torch.float32, device=frames.device)
-    ops.augment_clips(frames, kinds.to(device), params.to(device), group_size, T, mean, std, out,
-                      host_tables=(kinds, params))
-    return out
+    return _run_programs(ops.augment_clips, augment_tables, "augment", frames_u8, programs, group_size, T, mean, std,
+                         out, device)
 
 
 class TrainTransform:
@@ -653,6 +633,9 @@ def _box_table(n_in, S):
     if key not in _BOX_TABLES:
         Sp = (S + 3) & ~3
         lo, K = resample_tables(n_in, S)
+        if K.shape[1] > 64:
+            raise ValueError("coclr_amd: a box side of %d to %d needs %d taps, the kernel takes 64" %
+                             (n_in, S, K.shape[1]))
         t = np.zeros((1 + K.shape[1], Sp), dtype=np.int32)
         t[0, :S] = lo
         t[1:, :S] = K.T
@@ -660,14 +643,36 @@ def _box_table(n_in, S):
     return _BOX_TABLES[key]
 
 
+def _plan_list(plans, unpack, packed_dim):
+    """`plans` as a list of plan dicts: a list of them already, or packed tensors stacked (one alone has `packed_dim`
+    dimensions)."""
+    if torch.is_tensor(plans):
+        return [unpack(p) for p in (plans[None] if plans.dim() == packed_dim else plans)]
+    return list(plans)
+
+
+def _axis_tables(keys, make):
+    """Every distinct table of the batch once, one after the other, per axis.  keys: per clip (x key, y key);
+    make(key): the key's int32 (1 + taps, P) table.  Returns (xtab, ytab, per clip [x offset, y offset, x taps, y taps]:
+    the four table words of its descriptor)."""
+    bufs, at, fill, words = ([], []), ({}, {}), [0, 0], []
+    for pair in keys:
+        offs = []
+        for axis, key in enumerate(pair):
+            if key not in at[axis]:
+                t = make(key)
+                at[axis][key] = (fill[axis], t.shape[0] - 1)
+                bufs[axis].append(t.reshape(-1))
+                fill[axis] += t.size
+            offs.append(at[axis][key])
+        words.append([offs[0][0], offs[1][0], offs[0][1], offs[1][1]])
+    return torch.from_numpy(np.concatenate(bufs[0])), torch.from_numpy(np.concatenate(bufs[1])), words
+
+
 def check_train_plans(plans, B, T, W, H):
     """`plans` (a list of B plans, or the stacked packed tensor) -> (descriptor rows without table fields, per-frame
     programs of all B * 2 clips), refused here, on the host, when a plan is not one the kernels take."""
-    if torch.is_tensor(plans):
-        if plans.dim() == 2:
-            plans = plans[None]
-        plans = [unpack_plan(p) for p in plans]
-    plans = list(plans)
+    plans = _plan_list(plans, unpack_plan, 2)
     if len(plans) != B:
         raise ValueError("coclr_amd: %d plans for %d samples" % (len(plans), B))
     rows, programs = [], []
@@ -691,35 +696,41 @@ def check_train_plans(plans, B, T, W, H):
     return rows, programs
 
 
+def _train_tables(rows, programs, rag, T, S):
+    """The body of train_tables and train_tables_ragged: `rows` and `programs` of check_train_plans, `rag` the words
+    that follow each clip's ten (none when the batch has one frame size)."""
+    xtab, ytab, words = _axis_tables([(row[4], row[5]) for row in rows], lambda n_in: _box_table(n_in, S))
+    desc = torch.tensor([list(row) + w + r for row, w, r in zip(rows, words, rag)], dtype=torch.int32)
+    # one program per clip where its frames agree, else (a gray clip: the channel is per frame) one per frame
+    per_clip = all(all(p == progs[0] for p in progs) for progs in programs)
+    flat = [progs[0] for progs in programs] if per_clip else [p for progs in programs for p in progs]
+    kinds, params = augment_tables(flat)
+    return desc, xtab, ytab, kinds, params, T if per_clip else 1
+
+
 def train_tables(plans, B, T, W, H, S):
     """The host side of stage_train_clips for B samples of 2 T frames of W x H staged to S x S: checks the plans and
     returns (desc int32 (2B, 10), xtab, ytab int32, kinds int32 (G, P), params fp32 (G, P), group_size) as the
     two entry points take them, all on the host.  May be computed ahead (stage_train_clips(tables=))."""
     rows, programs = check_train_plans(plans, B, T, W, H)
-    # the tables of every distinct box width / height once, one after the other
-    bufs, at = ([], []), ({}, {})
-    fill = [0, 0]
-    full = []
-    for row in rows:
-        offs = []
-        for axis, n_in in ((0, row[4]), (1, row[5])):
-            if n_in not in at[axis]:
-                t = _box_table(n_in, S)
-                if t.shape[0] - 1 > 64:
-                    raise ValueError("coclr_amd: a box side of %d to %d needs %d taps, the kernel takes 64" %
-                                     (n_in, S, t.shape[0] - 1))
-                at[axis][n_in] = (fill[axis], t.shape[0] - 1)
-                bufs[axis].append(t.reshape(-1))
-                fill[axis] += t.size
-            offs.append(at[axis][n_in])
-        full.append(list(row) + [offs[0][0], offs[1][0], offs[0][1], offs[1][1]])
-    desc = torch.tensor(full, dtype=torch.int32)
-    # one program per clip where its frames agree, else (a gray clip: the channel is per frame) one per frame
-    per_clip = all(all(p == progs[0] for p in progs) for progs in programs)
-    flat = [progs[0] for progs in programs] if per_clip else [p for progs in programs for p in progs]
-    kinds, params = augment_tables(flat)
-    return (desc, torch.from_numpy(np.concatenate(bufs[0])), torch.from_numpy(np.concatenate(bufs[1])), kinds, params,
-            T if per_clip else 1)
+    return _train_tables(rows, programs, [[]] * len(rows), T, S)
+
+
+def _stage_train(resize, frames, device, tables, B, T, S, mean, std, out):
+    """The tail of stage_train_clips and stage_train_clips_ragged: `out` checked, the frames uploaded, the two
+    launches.  `frames`: (B, 2T, H, W, 3), or the flat bytes of a RaggedFrames; `resize`: the form of
+    ops.resize_boxes_u8 that takes them."""
+    desc, xtab, ytab, kinds, params, group_size = tables
+    _check_out(out, (B, 2, 3, T, S, S))
+    frames = _upload(frames, device)
+    device = frames.device
+    u8 = torch.empty(B * 2 * T, S, S, 3, dtype=torch.uint8, device=device)
+    if out is None:
+        out = torch.empty(B, 2, 3, T, S, S, dtype=torch.float32, device=device)
+    resize(frames, desc.to(device), desc, xtab.to(device), ytab.to(device), T, S, u8)
+    ops.augment_clips(u8, kinds.to(device), params.to(device), group_size, T, mean, std,
+                      out.view(B * 2, 3, T, S, S), host_tables=(kinds, params))
+    return out
 
 
 def stage_train_clips(frames_u8, plans, out_size, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None, device=None,
@@ -747,22 +758,9 @@ def stage_train_clips(frames_u8, plans, out_size, mean=IMAGENET_MEAN, std=IMAGEN
         raise ValueError("coclr_amd: stage_train_clips takes an output size of 1..224, got %d" % S)
     if tables is None:
         tables = train_tables(plans, B, T, W, H, S)
-    desc, xtab, ytab, kinds, params, group_size = tables
-    if tuple(desc.shape) != (2 * B, 10):
-        raise ValueError("coclr_amd: tables for %d clips, frames for %d" % (desc.shape[0], 2 * B))
-    if out is not None and (tuple(out.shape) != (B, 2, 3, T, S, S) or not out.is_contiguous()):
-        raise ValueError("coclr_amd: out must be contiguous %s, got %s" % ((B, 2, 3, T, S, S), tuple(out.shape)))
-    if device is None:
-        device = frames_u8.device if frames_u8.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
-    frames = frames_u8.contiguous().to(device).view(B * T2, H, W, 3)
-    u8 = torch.empty(B * 2 * T, S, S, 3, dtype=torch.uint8, device=device)
-    if out is None:
-        out = torch.empty(B, 2, 3, T, S, S, dtype=torch.float32, device=device)
-    ops.resize_boxes_u8(frames, desc.to(device), desc, xtab.to(device), ytab.to(device), T, S, u8)
-    ops.augment_clips(u8, kinds.to(device), params.to(device), group_size, T, mean, std,
-                      out.view(B * 2, 3, T, S, S), host_tables=(kinds, params))
-    return out
+    if tuple(tables[0].shape) != (2 * B, 10):
+        raise ValueError("coclr_amd: tables for %d clips, frames for %d" % (tables[0].shape[0], 2 * B))
+    return _stage_train(ops.resize_boxes_u8, frames_u8, device, tables, B, T, S, mean, std, out)
 
 
 # ---- the classifier's transform (eval/main_classifier.py:729-744,216-220; utils/augmentation.py:21-58,90-146) --------
@@ -888,11 +886,7 @@ def unpack_cls_plan(packed):
 def check_cls_plans(plans, B, W, H, size):
     """`plans` (a list of B plans, or the stacked packed tensor) -> (per clip (x0, y0, w, h, ow, oh, cx, cy), per clip
     program), refused here, on the host, when a plan is not one the kernel takes."""
-    if torch.is_tensor(plans):
-        if plans.dim() == 1:
-            plans = plans[None]
-        plans = [unpack_cls_plan(p) for p in plans]
-    plans = list(plans)
+    plans = _plan_list(plans, unpack_cls_plan, 1)
     if len(plans) != B:
         raise ValueError("coclr_amd: %d plans for %d samples" % (len(plans), B))
     rows, programs = [], []
@@ -935,33 +929,71 @@ def _window_table(n_in, n_out, c0, size):
     return _WIN_TABLES[key]
 
 
+def _cls_sides(img_dim, size, who):
+    S, size = int(img_dim), int(size)
+    if S < 1 or size < 1 or S > CLS_MAX_SIDE or size > CLS_MAX_SIDE:
+        raise ValueError("coclr_amd: %s takes img_dim and size of 1..%d, got %d and %d" % (who, CLS_MAX_SIDE, S, size))
+    return S, size
+
+
+def _classifier_tables(rows, programs, first, rag, T, S, size, flip):
+    """The body of classifier_tables and classifier_tables_ragged: `rows` and `programs` of check_cls_plans, `first`
+    each clip's first frame, `rag` the words that follow its fourteen (none when the batch has one frame size)."""
+    tab2 = _window_table(size, S, 0, S)                  # size -> S whole: PIL's identity when they are equal
+    xtab, ytab, words = _axis_tables([((w, ow, cx), (h, oh, cy)) for _, _, w, h, ow, oh, cx, cy in rows],
+                                     lambda key: _window_table(key[0], key[1], key[2], size))
+    desc = torch.tensor([[f, T] + list(row) + w + r for f, row, w, r in zip(first, rows, words, rag)], dtype=torch.int32)
+    tail = [(AUGMENT_FLIP, 0.0)] if flip else []
+    kinds, params = augment_tables([list(p) + tail for p in programs])
+    direct = not flip and not any(programs)
+    return desc, xtab, ytab, torch.from_numpy(tab2), kinds, params, direct
+
+
 def classifier_tables(plans, B, T, W, H, img_dim, size=224, flip=False):
     """The host side of stage_classifier_clips for B samples of T frames of W x H: checks the plans and returns
     (desc int32 (B, 14), xtab, ytab int32, tab2 int32 (1 + taps, Sp), kinds int32 (B, P), params fp32 (B, P), direct)
     as the entry points take them, all on the host; `direct` says that no clip has a program and `flip` is off, so
     that one launch writes fp32.  May be computed ahead (stage_classifier_clips(tables=))."""
-    B, T, S, size = int(B), int(T), int(img_dim), int(size)
-    if S < 1 or size < 1 or S > CLS_MAX_SIDE or size > CLS_MAX_SIDE:
-        raise ValueError("coclr_amd: the classifier staging takes img_dim and size of 1..%d, got %d and %d" %
-                         (CLS_MAX_SIDE, S, size))
+    B, T = int(B), int(T)
+    S, size = _cls_sides(img_dim, size, "the classifier staging")
     rows, programs = check_cls_plans(plans, B, W, H, size)
-    tab2 = _window_table(size, S, 0, S)                  # size -> S whole: PIL's identity when they are equal
-    bufs, at, fill, full = ([], []), ({}, {}), [0, 0], []
-    for b, (x0, y0, w, h, ow, oh, cx, cy) in enumerate(rows):
-        offs = []
-        for axis, key in ((0, (w, ow, cx)), (1, (h, oh, cy))):
-            if key not in at[axis]:
-                t = _window_table(key[0], key[1], key[2], size)
-                at[axis][key] = (fill[axis], t.shape[0] - 1)
-                bufs[axis].append(t.reshape(-1))
-                fill[axis] += t.size
-            offs.append(at[axis][key])
-        full.append([b * T, T, x0, y0, w, h, ow, oh, cx, cy, offs[0][0], offs[1][0], offs[0][1], offs[1][1]])
-    tail = [(AUGMENT_FLIP, 0.0)] if flip else []
-    kinds, params = augment_tables([list(p) + tail for p in programs])
-    direct = not flip and not any(programs)
-    return (torch.tensor(full, dtype=torch.int32), torch.from_numpy(np.concatenate(bufs[0])),
-            torch.from_numpy(np.concatenate(bufs[1])), torch.from_numpy(tab2), kinds, params, direct)
+    return _classifier_tables(rows, programs, [b * T for b in range(B)], [[]] * B, T, S, size, flip)
+
+
+def _stage_classifier(ragged, frames, device, tables, B, T, S, size, mean, std, out):
+    """The tail of stage_classifier_clips and stage_classifier_clips_ragged: `out` and the chained form checked, the
+    frames uploaded, the launches.  `frames`: (B, T, H, W, 3), or with `ragged` the flat bytes of a RaggedFrames."""
+    desc, xtab, ytab, tab2, kinds, params, direct = tables
+    _check_out(out, (B, 3, T, S, S), fp32=True)
+    fused = cls_fused()
+    if not fused and bool((desc[:, 6:10] != torch.tensor([size, size, 0, 0], dtype=torch.int32)).any()):
+        raise ValueError("coclr_amd: COCLR_CLS_FUSED=0 chains two box resizes and cannot express the fallback form "
+                         "(a window of a whole-frame resample)")
+    resize2, boxes = (ops.resize2_boxes_ragged, ops.resize_boxes_ragged_u8) if ragged else \
+        (ops.resize2_boxes, ops.resize_boxes_u8)
+    frames = _upload(frames, device)
+    device = frames.device
+    if out is None:
+        out = torch.empty(B, 3, T, S, S, dtype=torch.float32, device=device)
+    if fused and direct:
+        resize2(frames, desc.to(device), desc, xtab.to(device), ytab.to(device), tab2.to(device), T, size, S, out, mean,
+                std)
+        return out
+    u8 = torch.empty(B * T, S, S, 3, dtype=torch.uint8, device=device)
+    if fused:
+        resize2(frames, desc.to(device), desc, xtab.to(device), ytab.to(device), tab2.to(device), T, size, S, u8)
+    else:
+        # the same bytes from the entry points of the training staging: box -> size per clip (the table words and what
+        # follows them kept), then the whole of that, which has one size, -> S
+        d1 = desc[:, list(range(6)) + list(range(10, desc.shape[1]))].contiguous()
+        taps2 = tab2.shape[0] - 1
+        d2 = torch.tensor([[b * T, T, 0, 0, size, size, 0, 0, taps2, taps2] for b in range(B)], dtype=torch.int32)
+        mid = torch.empty(B * T, size, size, 3, dtype=torch.uint8, device=device)
+        flat2 = tab2.reshape(-1).to(device)
+        boxes(frames, d1.to(device), d1, xtab.to(device), ytab.to(device), T, size, mid)
+        ops.resize_boxes_u8(mid, d2.to(device), d2, flat2, flat2, T, S, u8)
+    ops.augment_clips(u8, kinds.to(device), params.to(device), T, T, mean, std, out, host_tables=(kinds, params))
+    return out
 
 
 def stage_classifier_clips(frames_u8, plans, img_dim, flip=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None,
@@ -986,50 +1018,16 @@ def stage_classifier_clips(frames_u8, plans, img_dim, flip=False, mean=IMAGENET_
         if isinstance(plans, dict):
             plans = [plans]
     B, T, H, W = frames_u8.shape[:4]
-    S, size = int(img_dim), int(size)
     if B < 1 or T < 1 or H < 1 or W < 1:
         raise ValueError("coclr_amd: a sample is T frames, got %s" % (tuple(frames_u8.shape),))
-    if S < 1 or size < 1 or S > CLS_MAX_SIDE or size > CLS_MAX_SIDE:
-        raise ValueError("coclr_amd: stage_classifier_clips takes img_dim and size of 1..%d, got %d and %d" %
-                         (CLS_MAX_SIDE, S, size))
+    S, size = _cls_sides(img_dim, size, "stage_classifier_clips")
     if tables is None:
         tables = classifier_tables(plans, B, T, W, H, S, size, flip)
-    desc, xtab, ytab, tab2, kinds, params, direct = tables
+    desc, tab2, kinds = tables[0], tables[3], tables[4]
     if tuple(desc.shape) != (B, 14) or tuple(kinds.shape[:1]) != (B,) or tab2.shape[1] != (S + 3) & ~3:
         raise ValueError("coclr_amd: tables for %d clips to %d, frames for %d to %d" %
                          (desc.shape[0], tab2.shape[1], B, S))
-    if out is not None and (tuple(out.shape) != (B, 3, T, S, S) or not out.is_contiguous() or
-                            out.dtype != torch.float32):
-        raise ValueError("coclr_amd: out must be contiguous fp32 %s, got %s" % ((B, 3, T, S, S), tuple(out.shape)))
-    fused = cls_fused()
-    if not fused and bool((desc[:, 6:10] != torch.tensor([size, size, 0, 0], dtype=torch.int32)).any()):
-        raise ValueError("coclr_amd: COCLR_CLS_FUSED=0 chains two box resizes and cannot express the fallback form "
-                         "(a window of a whole-frame resample)")
-    if device is None:
-        device = frames_u8.device if frames_u8.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
-    frames = frames_u8.contiguous().to(device).view(B * T, H, W, 3)
-    if out is None:
-        out = torch.empty(B, 3, T, S, S, dtype=torch.float32, device=device)
-    if fused and direct:
-        ops.resize2_boxes(frames, desc.to(device), desc, xtab.to(device), ytab.to(device), tab2.to(device), T, size,
-                          S, out, mean, std)
-        return out
-    u8 = torch.empty(B * T, S, S, 3, dtype=torch.uint8, device=device)
-    if fused:
-        ops.resize2_boxes(frames, desc.to(device), desc, xtab.to(device), ytab.to(device), tab2.to(device), T, size,
-                          S, u8)
-    else:
-        # the same bytes from the entry points of the training staging: box -> size, then the whole of that -> S
-        d1 = desc[:, [0, 1, 2, 3, 4, 5, 10, 11, 12, 13]].contiguous()
-        taps2 = tab2.shape[0] - 1
-        d2 = torch.tensor([[b * T, T, 0, 0, size, size, 0, 0, taps2, taps2] for b in range(B)], dtype=torch.int32)
-        mid = torch.empty(B * T, size, size, 3, dtype=torch.uint8, device=device)
-        flat2 = tab2.reshape(-1).to(device)
-        ops.resize_boxes_u8(frames, d1.to(device), d1, xtab.to(device), ytab.to(device), T, size, mid)
-        ops.resize_boxes_u8(mid, d2.to(device), d2, flat2, flat2, T, S, u8)
-    ops.augment_clips(u8, kinds.to(device), params.to(device), T, T, mean, std, out, host_tables=(kinds, params))
-    return out
+    return _stage_classifier(False, frames_u8, device, tables, B, T, S, size, mean, std, out)
 
 
 # ---- batches whose videos differ in frame size (kinetics400-256: a 256-pixel short side, the video's own aspect) -------
@@ -1144,38 +1142,18 @@ def train_tables_ragged(plans, samples, T, S):
     """train_tables for samples of differing frame sizes: `samples` [(byte offset of the sample's first frame, W, H)];
     every plan is checked against its own sample's (W, H).  Returns (desc int32 (2B, 14), xtab, ytab, kinds, params,
     group_size) as coclr_resize_boxes_ragged_u8 and coclr_augment_clips take them, all on the host."""
-    B = len(samples)
-    if torch.is_tensor(plans):
-        plans = [unpack_plan(p) for p in (plans[None] if plans.dim() == 2 else plans)]
-    plans = list(plans)
-    if len(plans) != B:
-        raise ValueError("coclr_amd: %d plans for %d samples" % (len(plans), B))
-    rows, programs = [], []
-    for b, (plan, (offset, W, H)) in enumerate(zip(plans, samples)):
+    plans = _plan_list(plans, unpack_plan, 2)
+    if len(plans) != len(samples):
+        raise ValueError("coclr_amd: %d plans for %d samples" % (len(plans), len(samples)))
+    rows, programs, rag = [], [], []
+    for plan, (offset, W, H) in zip(plans, samples):
         r, p = check_train_plans([plan], 1, T, W, H)
+        stride = (3 * H * W + RAGGED_ALIGN - 1) & ~(RAGGED_ALIGN - 1)
         for row in r:                                            # row[0]: the clip's first frame within its sample
-            stride = (3 * H * W + RAGGED_ALIGN - 1) & ~(RAGGED_ALIGN - 1)
-            rows.append((row, _rag_words(offset + row[0] * stride, W, H)))
+            rows.append((0,) + row[1:])
+            rag.append(_rag_words(offset + row[0] * stride, W, H))
         programs.extend(p)
-    bufs, at, fill, full = ([], []), ({}, {}), [0, 0], []
-    for row, rag in rows:
-        offs = []
-        for axis, n_in in ((0, row[4]), (1, row[5])):
-            if n_in not in at[axis]:
-                t = _box_table(n_in, S)
-                if t.shape[0] - 1 > 64:
-                    raise ValueError("coclr_amd: a box side of %d to %d needs %d taps, the kernel takes 64" %
-                                     (n_in, S, t.shape[0] - 1))
-                at[axis][n_in] = (fill[axis], t.shape[0] - 1)
-                bufs[axis].append(t.reshape(-1))
-                fill[axis] += t.size
-            offs.append(at[axis][n_in])
-        full.append([0] + list(row[1:]) + [offs[0][0], offs[1][0], offs[0][1], offs[1][1]] + rag)
-    per_clip = all(all(p == progs[0] for p in progs) for progs in programs)
-    flat = [progs[0] for progs in programs] if per_clip else [p for progs in programs for p in progs]
-    kinds, params = augment_tables(flat)
-    return (torch.tensor(full, dtype=torch.int32), torch.from_numpy(np.concatenate(bufs[0])),
-            torch.from_numpy(np.concatenate(bufs[1])), kinds, params, T if per_clip else 1)
+    return _train_tables(rows, programs, rag, T, S)
 
 
 def stage_train_clips_ragged(frames, plans, out_size, first=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
@@ -1184,9 +1162,7 @@ def stage_train_clips_ragged(frames, plans, out_size, first=None, mean=IMAGENET_
     frames: RaggedFrames.  Sample b is frames first[b] .. first[b] + 2T - 1 (default first[b] = 2 T b), which share
     one size; T comes from the plans.  plans: B plans of TrainTransform.draw(W_b, H_b), or their pack_plan tensors
     stacked.  Returns (B, 2, 3, T, S, S) fp32 on the device, each sample bit-identical to stage_train_clips on it."""
-    if torch.is_tensor(plans):
-        plans = [unpack_plan(p) for p in (plans[None] if plans.dim() == 2 else plans)]
-    plans = [plans] if isinstance(plans, dict) else list(plans)
+    plans = _plan_list([plans] if isinstance(plans, dict) else plans, unpack_plan, 2)
     B, S = len(plans), int(out_size)
     if B < 1:
         raise ValueError("coclr_amd: stage_train_clips_ragged needs at least one plan")
@@ -1196,54 +1172,24 @@ def stage_train_clips_ragged(frames, plans, out_size, first=None, mean=IMAGENET_
     if S < 1 or S * S > JITTER_MAX_PIXELS:
         raise ValueError("coclr_amd: stage_train_clips_ragged takes an output size of 1..224, got %d" % S)
     samples = _ragged_samples(frames, B, 2 * T, first)
-    pixels = frames.pixels
-    desc, xtab, ytab, kinds, params, group_size = train_tables_ragged(plans, samples, T, S)
-    if out is not None and (tuple(out.shape) != (B, 2, 3, T, S, S) or not out.is_contiguous()):
-        raise ValueError("coclr_amd: out must be contiguous %s, got %s" % ((B, 2, 3, T, S, S), tuple(out.shape)))
-    device = pixels.device
-    u8 = torch.empty(B * 2 * T, S, S, 3, dtype=torch.uint8, device=device)
-    if out is None:
-        out = torch.empty(B, 2, 3, T, S, S, dtype=torch.float32, device=device)
-    ops.resize_boxes_ragged_u8(pixels, desc.to(device), desc, xtab.to(device), ytab.to(device), T, S, u8)
-    ops.augment_clips(u8, kinds.to(device), params.to(device), group_size, T, mean, std,
-                      out.view(B * 2, 3, T, S, S), host_tables=(kinds, params))
-    return out
+    tables = train_tables_ragged(plans, samples, T, S)
+    return _stage_train(ops.resize_boxes_ragged_u8, frames.pixels, frames.pixels.device, tables, B, T, S, mean, std, out)
 
 
 def classifier_tables_ragged(plans, samples, T, img_dim, size=224, flip=False):
     """classifier_tables for samples of differing frame sizes: `samples` [(byte offset, W, H)]; every plan is checked
     against its own sample's (W, H).  Returns (desc int32 (B, 18), xtab, ytab, tab2, kinds, params, direct)."""
-    B, T, S, size = len(samples), int(T), int(img_dim), int(size)
-    if S < 1 or size < 1 or S > CLS_MAX_SIDE or size > CLS_MAX_SIDE:
-        raise ValueError("coclr_amd: the classifier staging takes img_dim and size of 1..%d, got %d and %d" %
-                         (CLS_MAX_SIDE, S, size))
-    if torch.is_tensor(plans):
-        plans = [unpack_cls_plan(p) for p in (plans[None] if plans.dim() == 1 else plans)]
-    plans = list(plans)
+    B, T = len(samples), int(T)
+    S, size = _cls_sides(img_dim, size, "the classifier staging")
+    plans = _plan_list(plans, unpack_cls_plan, 1)
     if len(plans) != B:
         raise ValueError("coclr_amd: %d plans for %d samples" % (len(plans), B))
     rows, programs = [], []
-    for plan, (offset, W, H) in zip(plans, samples):
+    for plan, (_, W, H) in zip(plans, samples):
         r, p = check_cls_plans([plan], 1, W, H, size)
-        rows.append((r[0], _rag_words(offset, W, H)))
+        rows.extend(r)
         programs.extend(p)
-    tab2 = _window_table(size, S, 0, S)
-    bufs, at, fill, full = ([], []), ({}, {}), [0, 0], []
-    for (x0, y0, w, h, ow, oh, cx, cy), rag in rows:
-        offs = []
-        for axis, key in ((0, (w, ow, cx)), (1, (h, oh, cy))):
-            if key not in at[axis]:
-                t = _window_table(key[0], key[1], key[2], size)
-                at[axis][key] = (fill[axis], t.shape[0] - 1)
-                bufs[axis].append(t.reshape(-1))
-                fill[axis] += t.size
-            offs.append(at[axis][key])
-        full.append([0, T, x0, y0, w, h, ow, oh, cx, cy, offs[0][0], offs[1][0], offs[0][1], offs[1][1]] + rag)
-    tail = [(AUGMENT_FLIP, 0.0)] if flip else []
-    kinds, params = augment_tables([list(p) + tail for p in programs])
-    direct = not flip and not any(programs)
-    return (torch.tensor(full, dtype=torch.int32), torch.from_numpy(np.concatenate(bufs[0])),
-            torch.from_numpy(np.concatenate(bufs[1])), torch.from_numpy(tab2), kinds, params, direct)
+    return _classifier_tables(rows, programs, [0] * B, [_rag_words(*sample) for sample in samples], T, S, size, flip)
 
 
 def stage_classifier_clips_ragged(frames, plans, img_dim, flip=False, first=None, T=None, mean=IMAGENET_MEAN,
@@ -1254,9 +1200,7 @@ def stage_classifier_clips_ragged(frames, plans, img_dim, flip=False, first=None
     frames: RaggedFrames.  Sample b is frames first[b] .. first[b] + T - 1 (default first[b] = T b, T = frames / B),
     which share one size.  plans: B plans of ClassifierTransform.draw(W_b, H_b), or their packed tensors stacked.
     Returns (B, 3, T, S, S) fp32 on the device, each sample bit-identical to stage_classifier_clips on it."""
-    if torch.is_tensor(plans):
-        plans = [unpack_cls_plan(p) for p in (plans[None] if plans.dim() == 1 else plans)]
-    plans = [plans] if isinstance(plans, dict) else list(plans)
+    plans = _plan_list([plans] if isinstance(plans, dict) else plans, unpack_cls_plan, 1)
     B, S, size = len(plans), int(img_dim), int(size)
     if B < 1:
         raise ValueError("coclr_amd: stage_classifier_clips_ragged needs at least one plan")
@@ -1268,34 +1212,5 @@ def stage_classifier_clips_ragged(frames, plans, img_dim, flip=False, first=None
     if T < 1:
         raise ValueError("coclr_amd: a sample is T >= 1 frames")
     samples = _ragged_samples(frames, B, T, first)
-    pixels = frames.pixels
-    desc, xtab, ytab, tab2, kinds, params, direct = classifier_tables_ragged(plans, samples, T, S, size, flip)
-    if out is not None and (tuple(out.shape) != (B, 3, T, S, S) or not out.is_contiguous() or
-                            out.dtype != torch.float32):
-        raise ValueError("coclr_amd: out must be contiguous fp32 %s, got %s" % ((B, 3, T, S, S), tuple(out.shape)))
-    fused = cls_fused()
-    if not fused and bool((desc[:, 6:10] != torch.tensor([size, size, 0, 0], dtype=torch.int32)).any()):
-        raise ValueError("coclr_amd: COCLR_CLS_FUSED=0 chains two box resizes and cannot express the fallback form "
-                         "(a window of a whole-frame resample)")
-    device = pixels.device
-    if out is None:
-        out = torch.empty(B, 3, T, S, S, dtype=torch.float32, device=device)
-    if fused and direct:
-        ops.resize2_boxes_ragged(pixels, desc.to(device), desc, xtab.to(device), ytab.to(device), tab2.to(device), T,
-                                 size, S, out, mean, std)
-        return out
-    u8 = torch.empty(B * T, S, S, 3, dtype=torch.uint8, device=device)
-    if fused:
-        ops.resize2_boxes_ragged(pixels, desc.to(device), desc, xtab.to(device), ytab.to(device), tab2.to(device), T,
-                                 size, S, u8)
-    else:
-        # box -> size per clip from the ragged buffer, then the whole of that -> S: the second stage has one size
-        d1 = desc[:, [0, 1, 2, 3, 4, 5, 10, 11, 12, 13, 14, 15, 16, 17]].contiguous()
-        taps2 = tab2.shape[0] - 1
-        d2 = torch.tensor([[b * T, T, 0, 0, size, size, 0, 0, taps2, taps2] for b in range(B)], dtype=torch.int32)
-        mid = torch.empty(B * T, size, size, 3, dtype=torch.uint8, device=device)
-        flat2 = tab2.reshape(-1).to(device)
-        ops.resize_boxes_ragged_u8(pixels, d1.to(device), d1, xtab.to(device), ytab.to(device), T, size, mid)
-        ops.resize_boxes_u8(mid, d2.to(device), d2, flat2, flat2, T, S, u8)
-    ops.augment_clips(u8, kinds.to(device), params.to(device), T, T, mean, std, out, host_tables=(kinds, params))
-    return out
+    tables = classifier_tables_ragged(plans, samples, T, S, size, flip)
+    return _stage_classifier(True, frames.pixels, frames.pixels.device, tables, B, T, S, size, mean, std, out)
