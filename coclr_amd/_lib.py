@@ -60,6 +60,13 @@ class GemmEpilogue(C.Structure):
                 ("out2", vp), ("f", f32), ("rowsum", vp)]
 
 
+class JpegStore(C.Structure):
+    """Mirror of `coclr_jpeg_store`."""
+    _fields_ = [("data", vp), ("data_bytes", i64), ("frames", vp), ("frames_host", vp), ("nframes", i64),
+                ("tables", vp), ("tables_host", vp), ("table_sets", i64), ("segs", vp), ("segs_host", vp),
+                ("nsegs", i64), ("rows", vp), ("nrows", i64), ("chunk_bytes", i32)]
+
+
 _P = C.POINTER
 _SIGNATURES = {
     "coclr_abi_version": [],
@@ -146,6 +153,9 @@ _SIGNATURES = {
                                 vp],
     "coclr_jpeg_decode_ragged": [vp, i64, vp, _P(i32), i32, i32, vp, _P(i64), vp, _P(i64), i32, vp, vp, i64, vp, i64,
                                  vp, i32, vp],
+    "coclr_jpeg_store_index": [_P(JpegStore), i64, i64, vp],
+    "coclr_jpeg_decode_store": [_P(JpegStore), vp, _P(i64), i32, vp, _P(i64), vp, _P(i64), i32, vp, vp, i64, vp, i64,
+                                vp, vp],
     "coclr_resize_boxes_ragged_u8": [vp, i64, vp, _P(i32), i32, i32, i32, vp, i64, vp, i64, vp, vp],
     "coclr_resize2_boxes_ragged": [vp, i64, vp, _P(i32), i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, i32, _P(f32),
                                    _P(f32), vp, vp, vp],

@@ -8,6 +8,9 @@
 // jpeg_entropy_kernel, or, with coclr_jpeg_decode_split's chunk_bytes > 0, one workgroup of
 // jpeg_entropy_split_kernel: one lane per chunk of its bytes, decoded from guessed states until every chunk's
 // entry is its predecessor's exit (jpeg_core.h), which is the serial decoder's result for any bytes.
+// A store (coclr_jpeg_store_index, coclr_jpeg_decode_store, at the end) finds those states once per frame and keeps
+// them: jpeg_store_index_kernel is the split kernel without its write pass, jpeg_entropy_store_kernel the write pass
+// alone, a lane per chunk of any frame of the call.
 #include "../../include/coclr_hip.h"
 #include "common.h"
 #include "jpeg_core.h"
@@ -108,6 +111,75 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
   if (st) atomicOr(&status[f], st);
 }
 
+// One window of blockDim.x chunks, from chunk w0, of a segment [s0, s1) whose tables are in LDS (`tab`), on the lanes of
+// its workgroup; `first` is the true state at the window's start.  Relaxation, then the scan (see
+// jpeg_entropy_split_kernel, which decodes from the result, and jpeg_store_index_kernel, which stores it).  Afterwards
+// `in` is the lane's TRUE entry and `out` its exit, `v` the inclusive and `e` the exclusive prefix over the window's
+// lanes of {blocks completed (saturating at total), three DC sums}.  ex: [L][2], ps: [L][4] words of LDS.  Every
+// barrier is on a workgroup-uniform path: all lanes call this together.
+struct split_lane {
+  bool live;
+  int cend;
+  jc_state in, out;
+  uint32_t v[4], e[4];
+};
+
+__device__ __forceinline__ void split_window(const uint8_t* __restrict__ data, int s0, int s1, int chunk_bytes,
+                                             const int32_t* tab, const jc_geom& g, long w0, long nchunks,
+                                             const jc_state& first, uint32_t total, int32_t* ex, uint32_t* ps,
+                                             split_lane& w) {
+  const int t = threadIdx.x, L = blockDim.x;
+  const bool live = w0 + t < nchunks;
+  const int cend = live ? jc_chunk_end(s0, s1, chunk_bytes, w0 + t) : s1;
+  jc_state in = t == 0 ? first : live ? jc_chunk_cold(data, s0, s1, chunk_bytes, w0 + t) : jc_state_past();
+  jc_state out = in;
+  int blocks = 0;
+  uint32_t dcs[3] = {0, 0, 0};
+  if (live) jc_chunk_scan(data, s1, cend, chunk_bytes, tab, g, in, &out, &blocks, dcs);
+  ex[2 * t] = out.pos;
+  ex[2 * t + 1] = jc_state_word(out);
+  __syncthreads();
+  for (int r = 0; r < L; ++r) {
+    int changed = 0;
+    jc_state left = in;
+    if (live && t > 0) {
+      left = jc_state_unpack(ex[2 * t - 2], ex[2 * t - 1], g);
+      changed = left.pos != in.pos || jc_state_word(left) != jc_state_word(in);
+    }
+    __syncthreads();                                                       // all have read the previous round's exits
+    if (changed) {
+      in = left;
+      jc_chunk_scan(data, s1, cend, chunk_bytes, tab, g, in, &out, &blocks, dcs);
+      ex[2 * t] = out.pos;
+      ex[2 * t + 1] = jc_state_word(out);
+    }
+    if (!__syncthreads_or(changed)) break;
+  }
+  uint32_t v[4] = {(uint32_t)blocks > total ? total : (uint32_t)blocks, dcs[0], dcs[1], dcs[2]};
+  for (int i = 0; i < 4; ++i) ps[4 * t + i] = v[i];
+  __syncthreads();
+  for (int d = 1; d < L; d <<= 1) {                                        // inclusive prefix
+    uint32_t a[4] = {0, 0, 0, 0};
+    if (t >= d)
+      for (int i = 0; i < 4; ++i) a[i] = ps[4 * (t - d) + i];
+    __syncthreads();
+    if (t >= d) {
+      v[0] = jc_blocks_add(a[0], v[0], total);
+      for (int i = 1; i < 4; ++i) v[i] += a[i];
+      for (int i = 0; i < 4; ++i) ps[4 * t + i] = v[i];
+    }
+    __syncthreads();
+  }
+  w.live = live;
+  w.cend = cend;
+  w.in = in;
+  w.out = out;
+  for (int i = 0; i < 4; ++i) {
+    w.v[i] = v[i];
+    w.e[i] = t > 0 ? ps[4 * (t - 1) + i] : 0;                              // exclusive: the left neighbour's
+  }
+}
+
 // One workgroup per frame of ONE segment (the others return at once), one lane per chunk of chunk_bytes raw bytes; a
 // frame with more chunks than lanes is done in windows of blockDim.x chunks, in order, each starting from the
 // converged exit of the one before.  Per window:
@@ -168,61 +240,19 @@ __global__ __launch_bounds__(1024) void jpeg_entropy_split_kernel(const uint8_t*
     if (first.pos == JC_PAST) break;                                       // uniform: nothing but zero bits is left
     const uint32_t block0 = (uint32_t)carry[2];
     const uint32_t dc0[3] = {(uint32_t)carry[3], (uint32_t)carry[4], (uint32_t)carry[5]};
-    const bool live = w0 + t < nchunks;
-    const int cend = live ? jc_chunk_end(s0, s1, chunk_bytes, w0 + t) : s1;
-    jc_state in = t == 0 ? first : live ? jc_chunk_cold(data, s0, s1, chunk_bytes, w0 + t) : jc_state_past();
-    jc_state out = in;
-    int blocks = 0;
-    uint32_t dcs[3] = {0, 0, 0};
-    if (live) jc_chunk_scan(data, s1, cend, chunk_bytes, tab, g, in, &out, &blocks, dcs);
-    ex[2 * t] = out.pos;
-    ex[2 * t + 1] = jc_state_word(out);
-    __syncthreads();
-    for (int r = 0; r < L; ++r) {
-      int changed = 0;
-      jc_state left = in;
-      if (live && t > 0) {
-        left = jc_state_unpack(ex[2 * t - 2], ex[2 * t - 1], g);
-        changed = left.pos != in.pos || jc_state_word(left) != jc_state_word(in);
-      }
-      __syncthreads();                                                     // all have read the previous round's exits
-      if (changed) {
-        in = left;
-        jc_chunk_scan(data, s1, cend, chunk_bytes, tab, g, in, &out, &blocks, dcs);
-        ex[2 * t] = out.pos;
-        ex[2 * t + 1] = jc_state_word(out);
-      }
-      if (!__syncthreads_or(changed)) break;
-    }
-    uint32_t v[4] = {(uint32_t)blocks > total ? total : (uint32_t)blocks, dcs[0], dcs[1], dcs[2]};
-    for (int i = 0; i < 4; ++i) ps[4 * t + i] = v[i];
-    __syncthreads();
-    for (int d = 1; d < L; d <<= 1) {                                      // inclusive prefix
-      uint32_t a[4] = {0, 0, 0, 0};
-      if (t >= d)
-        for (int i = 0; i < 4; ++i) a[i] = ps[4 * (t - d) + i];
-      __syncthreads();
-      if (t >= d) {
-        v[0] = jc_blocks_add(a[0], v[0], total);
-        for (int i = 1; i < 4; ++i) v[i] += a[i];
-        for (int i = 0; i < 4; ++i) ps[4 * t + i] = v[i];
-      }
-      __syncthreads();
-    }
-    uint32_t e[4] = {0, 0, 0, 0};                                          // exclusive: the left neighbour's
-    if (t > 0)
-      for (int i = 0; i < 4; ++i) e[i] = ps[4 * (t - 1) + i];
-    if (live) {
-      const int dc[3] = {(int16_t)(dc0[0] + e[1]), (int16_t)(dc0[1] + e[2]), (int16_t)(dc0[2] + e[3])};
-      st |= jc_chunk_write(data, s1, cend, chunk_bytes, tab, g, in, (long)jc_blocks_add(block0, e[0], total), dc, m0,
-                           m1, dst);
+    split_lane w;
+    split_window(data, s0, s1, chunk_bytes, tab, g, w0, nchunks, first, total, ex, ps, w);
+    if (w.live) {
+      const int dc[3] = {(int16_t)(dc0[0] + w.e[1]), (int16_t)(dc0[1] + w.e[2]), (int16_t)(dc0[2] + w.e[3])};
+      st |= jc_chunk_write(data, s1, w.cend, chunk_bytes, tab, g, w.in, (long)jc_blocks_add(block0, w.e[0], total), dc,
+                           m0, m1, dst);
     }
     __syncthreads();                                                       // the carry and the scan have been read
     if (t == L - 1) {
-      carry[0] = out.pos;
-      carry[1] = jc_state_word(out);
-      carry[2] = (int32_t)jc_blocks_add(block0, v[0], total);
-      for (int i = 0; i < 3; ++i) carry[3 + i] = (int32_t)(dc0[i] + v[1 + i]);
+      carry[0] = w.out.pos;
+      carry[1] = jc_state_word(w.out);
+      carry[2] = (int32_t)jc_blocks_add(block0, w.v[0], total);
+      for (int i = 0; i < 3; ++i) carry[3 + i] = (int32_t)(dc0[i] + w.v[1 + i]);
     }
     __syncthreads();
   }
@@ -482,6 +512,252 @@ extern "C" int coclr_jpeg_decode_ragged(const uint8_t* data, int64_t data_len, c
                          (int)data_len, meta, width, maxseg, chunk_bytes, gs, coefs, status);
       COCLR_LAUNCH_CHECK();
     }
+  }
+  if (stages & 2) {
+    hipLaunchKernelGGL(jpeg_idct_kernel<ragged_geom>, dim3(cdiv(lanes2, 256)), dim3(256), 0, s, coefs, lanes2, gs,
+                       planes);
+    COCLR_LAUNCH_CHECK();
+  }
+  if (stages & 4) {
+    hipLaunchKernelGGL(jpeg_colour_kernel<ragged_geom>, dim3(cdiv(lanes3, 256)), dim3(256), 0, s, planes, lanes3, 0, gs,
+                       1, out);
+    COCLR_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// ---- frames of a device-resident store, decoded by index ---------------------------------------------------------------
+namespace {
+
+struct store_view {          // the device side of a coclr_jpeg_store
+  const uint8_t* data;
+  long data_bytes;
+  const int64_t* frames;
+  long nframes;
+  const int32_t* tables;
+  long table_sets;
+  const int32_t* segs;
+  long nsegs;
+  uint32_t* rows;
+  long nrows;
+  int chunk_bytes;
+};
+
+// One workgroup per frame f0 + blockIdx.x of ONE segment (the others return at once): the relaxation and the scan of
+// jpeg_entropy_split_kernel, window by window, and where that kernel decodes every chunk once more from its true
+// state, this one stores the state (jc_row_pack).  Once only zero bits are left every later chunk's row says so.
+// Dynamic LDS as there (split_lds_bytes); every barrier is on a workgroup-uniform path.
+__global__ __launch_bounds__(1024) void jpeg_store_index_kernel(store_view sv, long f0) {
+  extern __shared__ int32_t index_lds[];
+  __shared__ jc_geom g;
+  const int t = threadIdx.x, L = blockDim.x;
+  const long f = f0 + blockIdx.x;
+  if (f < 0 || f >= sv.nframes) return;                                    // uniform
+  jc_store_frame fr;
+  jc_store_frame_get(sv.frames + f * JS_FIELDS, sv.data, sv.data_bytes, sv.tables, sv.table_sets, fr);
+  if (fr.nseg != 1 || !jc_geometry_ok(fr.H, fr.W, fr.ncomp, fr.hs, fr.vs, JPEG_MAX_SIDE)) return;   // uniform
+  const int chunk_bytes = sv.chunk_bytes;
+  const int s1 = fr.len;
+  const long nchunks = jc_chunk_count(0, s1, chunk_bytes);
+  if (fr.row < 0 || fr.row > sv.nrows - nchunks) return;                    // uniform
+  int32_t* tab = index_lds;                                                // quantisers and Huffman tables
+  int32_t* ex = tab + JM_SEG;                                              // [L][2] exit states
+  uint32_t* ps = reinterpret_cast<uint32_t*>(ex + 2 * L);                  // [L][4] blocks, DC sums
+  int32_t* carry = reinterpret_cast<int32_t*>(ps + 4 * L);                 // state (2), blocks, DC predictors (3)
+  for (int i = JM_QUANT + t; i < JM_SEG; i += L) tab[i] = fr.meta[i];
+  if (t == 0) {
+    jc_geom_init(g, (int)fr.H, (int)fr.W, (int)fr.ncomp, (int)fr.hs, (int)fr.vs);
+    carry[0] = carry[1] = carry[2] = carry[3] = carry[4] = carry[5] = 0;
+  }
+  __syncthreads();
+  const uint8_t* data = fr.bytes;
+  const uint32_t total = (uint32_t)((long)g.mcux * g.mcuy * g.mcu_blocks);
+  uint32_t* rows = sv.rows + fr.row * JS_ROW_WORDS;
+  long w0 = 0;
+  for (; w0 < nchunks; w0 += L) {
+    const jc_state first = jc_state_unpack(carry[0], carry[1], g);
+    if (first.pos == JC_PAST) break;                                       // uniform: nothing but zero bits is left
+    const uint32_t block0 = (uint32_t)carry[2];
+    const uint32_t dc0[3] = {(uint32_t)carry[3], (uint32_t)carry[4], (uint32_t)carry[5]};
+    split_lane w;
+    split_window(data, 0, s1, chunk_bytes, tab, g, w0, nchunks, first, total, ex, ps, w);
+    if (w.live) {
+      const uint32_t dc[3] = {dc0[0] + w.e[1], dc0[1] + w.e[2], dc0[2] + w.e[3]};
+      uint32_t row[JS_ROW_WORDS];
+      jc_row_pack(row, w.in, jc_chunk_start(s1, chunk_bytes, w0 + t), jc_blocks_add(block0, w.e[0], total), dc);
+      *reinterpret_cast<uint4*>(rows + (w0 + t) * JS_ROW_WORDS) = make_uint4(row[0], row[1], row[2], row[3]);
+    }
+    __syncthreads();                                                       // the carry and the scan have been read
+    if (t == L - 1) {
+      carry[0] = w.out.pos;
+      carry[1] = jc_state_word(w.out);
+      carry[2] = (int32_t)jc_blocks_add(block0, w.v[0], total);
+      for (int i = 0; i < 3; ++i) carry[3 + i] = (int32_t)(dc0[i] + w.v[1 + i]);
+    }
+    __syncthreads();
+  }
+  const uint32_t none[3] = {0, 0, 0};
+  for (long i = w0 + t; i < nchunks; i += L) {                             // behind the end of the real bits
+    uint32_t row[JS_ROW_WORDS];
+    jc_row_pack(row, jc_state_past(), 0, total, none);
+    *reinterpret_cast<uint4*>(rows + i * JS_ROW_WORDS) = make_uint4(row[0], row[1], row[2], row[3]);
+  }
+}
+
+// The entropy stage of coclr_jpeg_decode_store, one pass: lane id is chunk or restart segment `local` of call frame f
+// (binary search in the lane prefix), which is store frame sel[f].  The geometry and the coefficient blocks are the
+// call's (gs, checked against coef_blocks); bytes, tables and rows are the store's, clamped.
+__global__ __launch_bounds__(256) void jpeg_entropy_store_kernel(store_view sv, const int64_t* __restrict__ sel,
+                                                                 const int64_t* __restrict__ lanes, long n,
+                                                                 ragged_geom gs, int16_t* __restrict__ coef,
+                                                                 int32_t* __restrict__ status) {
+  const long id = (long)blockIdx.x * 256 + threadIdx.x;
+  if (id >= n) return;
+  const long f = jc_find_frame(lanes, gs.F, id);
+  const long local = id - lanes[f];
+  jc_geom g;
+  long cb, ob;
+  if (local < 0 || !gs.frame(f, g, &cb, &ob)) return;
+  long sf = sel[f];
+  sf = sf < 0 || sf >= sv.nframes ? 0 : sf;
+  jc_store_frame fr;
+  jc_store_frame_get(sv.frames + sf * JS_FIELDS, sv.data, sv.data_bytes, sv.tables, sv.table_sets, fr);
+  int16_t* dst = coef + cb * 64;
+  int st = 0;
+  if (fr.nseg == 1) {
+    const long at = fr.row + local;
+    if (local >= jc_chunk_count(0, fr.len, sv.chunk_bytes) || fr.row < 0 || at >= sv.nrows) return;
+    const uint4 w = *reinterpret_cast<const uint4*>(sv.rows + at * JS_ROW_WORDS);
+    const uint32_t row[JS_ROW_WORDS] = {w.x, w.y, w.z, w.w};
+    long block;
+    int dc[3];
+    const jc_state in = jc_row_unpack(row, jc_chunk_start(fr.len, sv.chunk_bytes, local), fr.len, g, &block, dc);
+    st = jc_chunk_write(fr.bytes, fr.len, jc_chunk_end(0, fr.len, sv.chunk_bytes, local), sv.chunk_bytes, fr.meta, g,
+                        in, block, dc, 0, g.mcux * g.mcuy, dst);
+  } else {
+    int s0, s1, m0, m1;
+    if (!jc_store_segment(fr, sv.segs, sv.nsegs, local, g, &s0, &s1, &m0, &m1)) return;
+    st = jc_decode_segment(fr.bytes, s0, s1, fr.meta, g, m0, m1, dst);
+  }
+  if (st) atomicOr(&status[f], st);
+}
+
+bool store_ok(const coclr_jpeg_store* st) {
+  if (!st || !st->data || !st->frames || !st->frames_host || !st->tables || !st->tables_host || !st->rows)
+    return false;
+  if (st->data_bytes < 0 || st->nframes < 1 || st->table_sets < 1 || st->nsegs < 0 || st->nrows < 1) return false;
+  if (st->nsegs > 0 && (!st->segs || !st->segs_host)) return false;
+  if (st->chunk_bytes < 8 || st->chunk_bytes > 65536) return false;
+  return !(((uintptr_t)st->frames & 7) || ((uintptr_t)st->tables & 3) || ((uintptr_t)st->segs & 3) ||
+           ((uintptr_t)st->rows & 15));
+}
+
+store_view store_device(const coclr_jpeg_store* st) {
+  return {st->data, st->data_bytes, st->frames, st->nframes, st->tables, st->table_sets,
+          st->segs,  st->nsegs,     st->rows,   st->nrows,   st->chunk_bytes};
+}
+
+// the host copy of store frame f: its buffers' bounds; with `deep` also what meta_ok checks of a descriptor
+bool store_frame_ok(const coclr_jpeg_store* st, long f, bool deep, jc_store_frame& fr, jc_geom& g) {
+  const int64_t* rec = st->frames_host + f * JS_FIELDS;
+  const int64_t base = rec[JS_BASE], len = rec[JS_LEN], nseg = rec[JS_NSEG], ri = rec[JS_RI];
+  if (base < 0 || len < 0 || len > 0x7fffffff || base > st->data_bytes - len) return false;
+  if (rec[JS_TSET] < 0 || rec[JS_TSET] >= st->table_sets || nseg < 1 || nseg > 0x7fffffff || ri < 0) return false;
+  jc_store_frame_get(rec, st->data, st->data_bytes, st->tables_host, st->table_sets, fr);
+  if (!jc_geometry_ok(fr.H, fr.W, fr.ncomp, fr.hs, fr.vs, JPEG_MAX_SIDE)) return false;
+  jc_geom_init(g, (int)fr.H, (int)fr.W, (int)fr.ncomp, (int)fr.hs, (int)fr.vs);
+  const long total = (long)g.mcux * g.mcuy;
+  if (nseg != (ri == 0 ? 1 : (total + ri - 1) / ri)) return false;
+  if (nseg == 1) {
+    if (fr.row < 0 || fr.row > st->nrows - jc_chunk_count(0, fr.len, st->chunk_bytes)) return false;
+  } else if (fr.seg < 0 || fr.seg > st->nsegs - nseg) {
+    return false;
+  }
+  if (!deep) return true;
+  long last = 0;
+  for (long s = 0; nseg > 1 && s < nseg; ++s) {
+    const long at = st->segs_host[fr.seg + s];
+    if (at < last || at > len) return false;
+    last = at;
+  }
+  for (int i = 0; i < 64 * g.ncomp; ++i)
+    if (fr.meta[JM_QUANT + i] < 0 || fr.meta[JM_QUANT + i] > 255) return false;
+  for (int t = 0; t < 6; ++t) {
+    const int32_t* h = fr.meta + JM_HUFF + t * JM_HUFF_WORDS;
+    for (int l = 0; l < 16; ++l)
+      if (h[l] < 0 || h[l] > 65536 || (l && h[l] < h[l - 1]) || h[16 + l] < -65536 || h[16 + l] > 255) return false;
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" int coclr_jpeg_store_index(const coclr_jpeg_store* st, int64_t f0, int64_t f1, void* stream) {
+  if (!store_ok(st) || f0 < 0 || f1 <= f0 || f1 > st->nframes || f1 - f0 >= 0x7fffffffL) return COCLR_EINVAL;
+  long single = 0, most_chunks = 1;
+  for (long f = f0; f < f1; ++f) {
+    jc_store_frame fr;
+    jc_geom g;
+    if (!store_frame_ok(st, f, true, fr, g)) return COCLR_EINVAL;
+    if (fr.nseg != 1) continue;
+    ++single;
+    const long n = jc_chunk_count(0, fr.len, st->chunk_bytes);
+    if (n > most_chunks) most_chunks = n;
+  }
+  if (!single) return 0;
+  const int lanes = most_chunks > 1024 ? 1024 : (int)((most_chunks + 63) / 64 * 64);
+  hipLaunchKernelGGL(jpeg_store_index_kernel, dim3((unsigned)(f1 - f0)), dim3(lanes), split_lds_bytes(lanes),
+                     (hipStream_t)stream, store_device(st), (long)f0);
+  COCLR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int coclr_jpeg_decode_store(const coclr_jpeg_store* st, const int64_t* sel, const int64_t* sel_host, int F,
+                                       const int64_t* geom, const int64_t* geom_host, const int64_t* prefix,
+                                       const int64_t* prefix_host, int stages, int16_t* coefs, uint8_t* planes,
+                                       int64_t coef_blocks, uint8_t* out, int64_t out_bytes, int32_t* status,
+                                       void* stream) {
+  if (!store_ok(st) || !sel || !sel_host || !geom || !geom_host || !prefix || !prefix_host || !coefs || !planes ||
+      !out || !status)
+    return COCLR_EINVAL;
+  if (F < 1 || stages < 1 || stages > 7 || coef_blocks < 1 || out_bytes < 1) return COCLR_EINVAL;
+  if (((uintptr_t)coefs & 15) || ((uintptr_t)planes & 15) || ((uintptr_t)out & 15) || ((uintptr_t)sel & 7) ||
+      ((uintptr_t)geom & 7) || ((uintptr_t)prefix & 7))
+    return COCLR_EINVAL;
+  const int64_t* pblocks = prefix_host;
+  const int64_t* prows = prefix_host + F + 1;
+  const int64_t* pchunks = prefix_host + 2 * (F + 1);
+  if (pblocks[0] != 0 || prows[0] != 0 || pchunks[0] != 0) return COCLR_EINVAL;
+  long cend = 0, oend = 0;
+  for (int f = 0; f < F; ++f) {
+    const int64_t* t = geom_host + (long)f * JR_FIELDS;
+    if (sel_host[f] < 0 || sel_host[f] >= st->nframes) return COCLR_EINVAL;
+    jc_store_frame fr;
+    jc_geom g;
+    if (!store_frame_ok(st, sel_host[f], false, fr, g)) return COCLR_EINVAL;
+    if (t[JR_H] != fr.H || t[JR_W] != fr.W || t[JR_NCOMP] != fr.ncomp || t[JR_HS] != fr.hs || t[JR_VS] != fr.vs)
+      return COCLR_EINVAL;
+    // storage: in frame order, no overlap, inside the buffers; an output frame starts 16-byte aligned
+    const long cb = t[JR_CBLOCK], ob = t[JR_OBYTE];
+    if (cb < cend || cb > coef_blocks - g.nblocks) return COCLR_EINVAL;
+    if (ob < oend || (ob & 15) || ob > out_bytes - (long)g.H * g.W * 3) return COCLR_EINVAL;
+    cend = cb + g.nblocks;
+    oend = ob + (long)g.H * g.W * 3;
+    if (pblocks[f + 1] - pblocks[f] != g.nblocks || prows[f + 1] - prows[f] != jc_row_groups(g)) return COCLR_EINVAL;
+    if (pchunks[f + 1] - pchunks[f] != jc_store_lanes(fr.len, fr.nseg, st->chunk_bytes)) return COCLR_EINVAL;
+  }
+  const long lanes1 = pchunks[F], lanes2 = pblocks[F], lanes3 = prows[F];
+  const long limit = 0x7fffffffL;        // workgroups of one launch
+  if (lanes1 / 256 >= limit || lanes2 / 256 >= limit || lanes3 / 256 >= limit) return COCLR_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const ragged_geom gs = {geom, prefix, prefix + F + 1, F, coef_blocks, out_bytes};
+  if (stages & 1) {
+    const long first = geom_host[JR_CBLOCK];
+    COCLR_RETURN_IF(hipMemsetAsync(coefs + first * 64, 0, (size_t)(cend - first) * 128, s));
+    COCLR_RETURN_IF(hipMemsetAsync(status, 0, (size_t)F * 4, s));
+    hipLaunchKernelGGL(jpeg_entropy_store_kernel, dim3(cdiv(lanes1, 256)), dim3(256), 0, s, store_device(st), sel,
+                       prefix + 2 * (F + 1), lanes1, gs, coefs, status);
+    COCLR_LAUNCH_CHECK();
   }
   if (stages & 2) {
     hipLaunchKernelGGL(jpeg_idct_kernel<ragged_geom>, dim3(cdiv(lanes2, 256)), dim3(256), 0, s, coefs, lanes2, gs,

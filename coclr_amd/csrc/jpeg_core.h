@@ -589,3 +589,117 @@ JC_HD bool jc_ragged_frame(const int64_t* tab, long f, long coef_blocks, long ou
 }
 
 JC_HD long jc_row_groups(const jc_geom& g) { return (long)g.H * ((g.W + 15) / 16); }   // colour lanes of a frame
+
+// ---- a device-resident store of frames, decoded by index (coclr_jpeg_store_index, coclr_jpeg_decode_store) ----------
+// Per frame JS_FIELDS int64 words.  The JM_QUANT .. JM_SEG words of a descriptor are kept once per distinct table set:
+// set i lies at tables[JS_TABLE_PAD + i * JS_TABLE_WORDS], so tables + i * JS_TABLE_WORDS serves as `meta` for every
+// function above that reads only JM_QUANT / JM_HUFF.  Segment offsets of frames with restart markers lie in one flat
+// int32 array.  A restart-less frame (JS_NSEG == 1) has one row of JS_ROW_WORDS words per chunk of chunk_bytes raw
+// bytes: the serial decoder's state at the chunk's first symbol, which jc_chunk_write decodes the chunk from.
+// All of it is device data to a kernel: jc_store_frame_get clamps whatever a record holds to the buffers.
+enum {
+  JS_BASE = 0,             // first entropy-coded byte of the frame in the store's bytes, 64 bits
+  JS_LEN,                  // entropy-coded bytes, < 2^31
+  JS_RI,                   // restart interval in MCUs, 0 = none
+  JS_NSEG,                 // restart segments (1: decoded by chunk from its rows)
+  JS_TSET,                 // table set
+  JS_SEG,                  // first of its JS_NSEG words in the segment array (JS_NSEG > 1)
+  JS_ROW,                  // first of its chunk rows (JS_NSEG == 1)
+  JS_GEOM,                 // jc_geom_pack
+  JS_FIELDS = 8,
+  JS_TABLE_WORDS = JM_SEG - JM_QUANT,
+  JS_TABLE_PAD = JM_QUANT,
+  JS_ROW_WORDS = 4,
+};
+
+JC_HD int64_t jc_geom_pack(long H, long W, long ncomp, long hs, long vs) {
+  return (int64_t)(H | W << 16 | ncomp << 32 | hs << 36 | vs << 40);
+}
+
+struct jc_store_frame {
+  const uint8_t* bytes;    // the frame's first byte: positions below are relative to it
+  int len, nseg;
+  long ri, seg, row;
+  const int32_t* meta;     // displaced: meta[JM_QUANT ..] and meta[JM_HUFF ..] are the frame's table set
+  long H, W, ncomp, hs, vs;    // as recorded; not checked (jc_geometry_ok)
+};
+
+JC_HD void jc_store_frame_get(const int64_t* rec, const uint8_t* data, int64_t data_bytes, const int32_t* tables,
+                              long table_sets, jc_store_frame& o) {
+  int64_t base = rec[JS_BASE], len = rec[JS_LEN], ts = rec[JS_TSET], nseg = rec[JS_NSEG];
+  base = base < 0 ? 0 : base > data_bytes ? data_bytes : base;
+  len = len < 0 ? 0 : len > data_bytes - base ? data_bytes - base : len;
+  len = len > 0x7fffffff ? 0x7fffffff : len;
+  ts = ts < 0 || ts >= table_sets ? 0 : ts;
+  o.bytes = data + base;
+  o.len = (int)len;
+  o.nseg = nseg < 1 ? 1 : nseg > 0x7fffffff ? 0x7fffffff : (int)nseg;
+  o.ri = rec[JS_RI];
+  o.seg = rec[JS_SEG];
+  o.row = rec[JS_ROW];
+  o.meta = tables + ts * JS_TABLE_WORDS;
+  const int64_t p = rec[JS_GEOM];
+  o.H = p & 0xFFFF; o.W = p >> 16 & 0xFFFF; o.ncomp = p >> 32 & 15; o.hs = p >> 36 & 15; o.vs = p >> 40 & 15;
+}
+
+// jc_segment_range for a frame of the store: segment `seg` of its f.nseg, offsets from the flat array `segs` of nsegs
+// words; bytes [s0, s1) relative to f.bytes, MCUs [m0, m1).  False: no such segment, or its words leave the array.
+JC_HD bool jc_store_segment(const jc_store_frame& f, const int32_t* segs, long nsegs, long seg, const jc_geom& g, int* s0,
+                            int* s1, int* m0, int* m1) {
+  if (seg < 0 || seg >= f.nseg || f.seg < 0 || f.seg > nsegs - f.nseg) return false;
+  const long hi = f.len;
+  long a = segs[f.seg + seg];
+  long b = seg + 1 < f.nseg ? segs[f.seg + seg + 1] : hi;
+  a = a < 0 ? 0 : a > hi ? hi : a;
+  b = b < a ? a : b > hi ? hi : b;
+  const long total = (long)g.mcux * g.mcuy;
+  long ri = f.ri;
+  if (ri < 1 || ri > total) ri = total;
+  long first = seg > total ? total : seg * ri;
+  first = first > total ? total : first;
+  long last = first + ri;
+  last = last > total ? total : last;
+  *s0 = (int)a; *s1 = (int)b; *m0 = (int)first; *m1 = (int)last;
+  return true;
+}
+
+// A chunk's row: word 0 = jc_state_word (14 bits) | (pos - first byte of the chunk) << 14 (17 bits) | past << 31,
+// word 1 = blocks of the frame completed before the chunk, word 2 = DC predictor 0 | predictor 1 << 16, word 3 =
+// predictor 2; a past state is word 0 = 1 << 31 and zeros.  A true entry lies within a symbol's length (8 raw bytes at most, FF 00 pairs included) of its chunk.
+JC_HD void jc_row_pack(uint32_t* row, const jc_state& s, long chunk_start, uint32_t blocks, const uint32_t* dc) {
+  if (s.pos == JC_PAST) {                                  // one form: such a chunk writes nothing
+    row[0] = 1u << 31;
+    row[1] = row[2] = row[3] = 0;
+    return;
+  } else {
+    long rel = (long)s.pos - chunk_start;
+    rel = rel < 0 ? 0 : rel > 0x1FFFF ? 0x1FFFF : rel;
+    row[0] = ((uint32_t)jc_state_word(s) & 0x3FFFu) | (uint32_t)rel << 14;
+  }
+  row[1] = blocks;
+  row[2] = (dc[0] & 0xFFFFu) | dc[1] << 16;
+  row[3] = dc[2] & 0xFFFFu;
+}
+
+// The state a row holds for the chunk that starts at chunk_start of a frame of `len` bytes.  Whatever the words are,
+// the position lies in [chunk_start, len] and block and k are ones jc_chunk_write takes.
+JC_HD jc_state jc_row_unpack(const uint32_t* row, long chunk_start, int len, const jc_geom& g, long* blocks, int* dc) {
+  *blocks = (long)row[1];
+  dc[0] = (int16_t)(row[2] & 0xFFFFu);
+  dc[1] = (int16_t)(row[2] >> 16);
+  dc[2] = (int16_t)(row[3] & 0xFFFFu);
+  if (row[0] >> 31) return jc_state_past();
+  long pos = chunk_start + (long)(row[0] >> 14 & 0x1FFFFu);
+  pos = pos > len ? len : pos;
+  return jc_state_unpack((int32_t)pos, (int32_t)(row[0] & 0x3FFFu), g);
+}
+
+JC_HD long jc_chunk_start(int len, int chunk_bytes, long i) {
+  const long c = i * chunk_bytes;
+  return c > len ? len : c;
+}
+
+// the entropy lanes of a store frame: its chunks, or its restart segments
+JC_HD long jc_store_lanes(int len, int nseg, int chunk_bytes) {
+  return nseg == 1 ? jc_chunk_count(0, len, chunk_bytes) : nseg;
+}

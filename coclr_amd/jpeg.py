@@ -9,6 +9,8 @@
 A batch whose videos differ in frame size (kinetics400-256 keeps every video's aspect ratio) goes through
 `cat_ragged` and `decode_ragged` instead, to a staging.RaggedFrames that stage_train_clips_ragged and
 stage_classifier_clips_ragged take; `pack`, per video, is the same.
+A dataset that fits into the device's memory can stay there compressed: `Store.add(pack)` per video, once, then
+`Store.decode(ids)` per step by frame index, to the same RaggedFrames, with nothing but the ids travelling (class Store).
 
 Scope: baseline / extended sequential Huffman (SOF0, SOF1), 8-bit, one interleaved scan, one component or YCbCr with
 luma sampled 1x1, 2x1 or 2x2, optional restart intervals -- what ffmpeg, cv2.imwrite and PIL write by default.
@@ -32,6 +34,7 @@ META_QUANT, META_HUFF, HUFF_WORDS = 16, 208, 96
 META_SEG = META_HUFF + 6 * HUFF_WORDS           # csrc/jpeg_core.h: JM_*
 MAX_SIDE = 8192
 DEFAULT_SPLIT = 64                               # chunk size when COCLR_JPEG_SPLIT is unset
+DEFAULT_STORE_CHUNK = 64                         # a Store's chunk size (PROVISIONAL)
 
 _SOF_NAMES = {0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)", 0xC5: "differential sequential (SOF5)",
               0xC6: "differential progressive (SOF6)", 0xC7: "differential lossless (SOF7)",
@@ -507,6 +510,204 @@ def decode_ragged(data, meta, device=None, max_stage_bytes=256 << 20, return_sta
 
 
 decode_ragged.last_status = None
+
+
+def _store_policy(chunk_bytes):
+    """A store's chunk size: `chunk_bytes` if given, else DEFAULT_STORE_CHUNK; 8..65536 (a store has no serial path)."""
+    chunk_bytes = split_policy(DEFAULT_STORE_CHUNK if chunk_bytes is None else chunk_bytes)
+    if chunk_bytes == 0:
+        raise ValueError("coclr_amd: a store's chunk_bytes must be in 8..65536, got 0")
+    return chunk_bytes
+
+
+class Store:
+    """A dataset's JPEG frames kept compressed on the device, parsed and validated once, decoded by frame index.
+
+        store = jpeg.Store(capacity_bytes, capacity_frames)      # once, before the epochs
+        first = store.add(jpeg.pack(raws))                       # per video; its frames are first .. first + len - 1
+        frames = store.decode(ids)                               # per step: a staging.RaggedFrames, as decode_ragged's
+
+    `add` takes what `pack` returns for one video (any geometry, gray or YCbCr, any sampling, with or without restart
+    markers), refuses what `check_meta` refuses, uploads the bytes and records, for every chunk of `chunk_bytes` raw
+    bytes of a frame without restart markers, the serial Huffman decoder's state at the chunk's start
+    (coclr_jpeg_store_index: the rounds of the split decoder, run once).  `decode` then decodes every chunk in one
+    pass from its recorded state; frames with restart markers keep a lane per segment.  Frames, `status` and
+    `decode.last_status` are bit for bit `decode_ragged`'s on the same bytes, whatever `chunk_bytes` is.
+
+    The buffers are allocated once and never grow: `capacity_bytes` of compressed bytes (may exceed 2 GiB; one frame
+    may not), `capacity_frames` records of 64 bytes (device and host), 16 bytes of row per `chunk_bytes` of capacity,
+    `capacity_table_sets` sets of quantisers and Huffman tables (3 KiB each, stored once per distinct set: cv2 and PIL
+    write the same tables into every frame of a dataset) and `capacity_segments` restart-segment offsets (default
+    64 per frame).  `chunk_bytes=None` is DEFAULT_STORE_CHUNK.
+    Not in scope: saving a built store, sharding one across ranks, datasets larger than the device's memory (those
+    stay with pack / cat / decode) and splitting inside the restart segments of frames with restart markers."""
+
+    def __init__(self, capacity_bytes, capacity_frames, chunk_bytes=None, device=None, capacity_table_sets=64,
+                 capacity_segments=None):
+        self.chunk_bytes = _store_policy(chunk_bytes)
+        capacity_bytes, capacity_frames = int(capacity_bytes), int(capacity_frames)
+        capacity_segments = 64 * capacity_frames if capacity_segments is None else int(capacity_segments)
+        if capacity_bytes < 1 or capacity_frames < 1 or capacity_table_sets < 1 or capacity_segments < 0:
+            raise ValueError("coclr_amd: a store's capacities are positive")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.capacity_bytes, self.capacity_frames, self.capacity_segments = capacity_bytes, capacity_frames, \
+            capacity_segments
+        words = ops.JS_TABLE_PAD + int(capacity_table_sets) * ops.JS_TABLE_WORDS
+        rows = capacity_bytes // self.chunk_bytes + capacity_frames              # a frame has len // chunk + 1 at most
+        self._host = (torch.zeros(capacity_frames, ops.JS_FIELDS, dtype=torch.int64),
+                      torch.zeros(words, dtype=torch.int32), torch.zeros(max(1, capacity_segments), dtype=torch.int32))
+        self._data = torch.empty(capacity_bytes, dtype=torch.uint8, device=self.device)
+        self._dev = tuple(torch.zeros_like(t, device=self.device) for t in self._host)
+        self._rows = torch.empty(rows, ops.JS_ROW_WORDS, dtype=torch.int32, device=self.device)
+        self._sets = {}                                        # the 768 words' bytes -> table set
+        self._geo = torch.zeros(capacity_frames, 5, dtype=torch.int64)    # host: H, W, components, hs, vs
+        self._lanes = torch.zeros(capacity_frames, dtype=torch.int64)     # host: chunks, or restart segments
+        self._frames = self._bytes = self._segs = self.chunk_rows = 0
+
+    def __len__(self):
+        return self._frames
+
+    @property
+    def nbytes(self):
+        """Compressed bytes held (the write cursor)."""
+        return self._bytes
+
+    @property
+    def table_sets(self):
+        """Distinct sets of quantisers and Huffman tables held."""
+        return len(self._sets)
+
+    def frame_size(self, id):
+        """(W, H) of frame `id`: what TrainTransform.draw takes."""
+        id = int(id)
+        if not 0 <= id < self._frames:
+            raise ValueError("coclr_amd: frame %d of a store of %d" % (id, self._frames))
+        return int(self._geo[id, 1]), int(self._geo[id, 0])
+
+    def _advance_cursor(self, nbytes):
+        """TEST ONLY: moves the write cursor by `nbytes` without writing, so that a test reaches byte offsets past
+        2^31 without uploading that much."""
+        if nbytes < 0 or self._bytes + nbytes > self.capacity_bytes:
+            raise ValueError("coclr_amd: the cursor leaves the store")
+        self._bytes += int(nbytes)
+
+    def _buffers(self):
+        """The arguments of ops.jpeg_store_desc."""
+        frames, tables, segs = self._dev
+        return (self._data, frames, self._host[0], self._frames, tables, self._host[1], len(self._sets), segs,
+                self._host[2], self._segs, self._rows, self.chunk_bytes)
+
+    def add(self, pack):
+        """One video's (data, meta) of `pack` -> the id of its first frame; ids are consecutive in insertion order.
+        ValueError, before anything is written: what check_meta refuses; more bytes, frames, table sets or
+        restart segments than the store was made for."""
+        data, meta = pack
+        H, W, ncomp, hs, vs = check_meta(data, meta)
+        F, n = meta.shape[0], data.numel()
+        m = meta[:, 8:].to(torch.int64)
+        ln, nseg = m[:, 1], m[:, 3]
+        lanes = torch.where(nseg == 1, (-(-ln // self.chunk_bytes)).clamp(min=1), nseg)
+        keys = [meta[f, 8 + META_QUANT:8 + META_SEG].numpy().tobytes() for f in range(F)]
+        fresh = list(dict.fromkeys(k for k in keys if k not in self._sets))
+        nsegs = int(nseg[nseg > 1].sum())
+        host_frames, host_tables, host_segs = self._host
+        for have, more, room, what in ((self._bytes, n, self.capacity_bytes, "bytes"),
+                                       (self._frames, F, self.capacity_frames, "frames"),
+                                       (len(self._sets), len(fresh), (host_tables.numel() - ops.JS_TABLE_PAD) //
+                                        ops.JS_TABLE_WORDS, "table sets"),
+                                       (self._segs, nsegs, self.capacity_segments, "restart segments")):
+            if have + more > room:
+                raise ValueError("coclr_amd: the store holds %d of %d %s and the pack brings %d" %
+                                 (have, room, what, more))
+        f0, s0 = self._frames, len(self._sets)
+        for k in fresh:
+            at = ops.JS_TABLE_PAD + len(self._sets) * ops.JS_TABLE_WORDS
+            host_tables[at:at + ops.JS_TABLE_WORDS] = torch.frombuffer(bytearray(k), dtype=torch.int32)
+            self._sets[k] = len(self._sets)
+        rec = torch.zeros(F, ops.JS_FIELDS, dtype=torch.int64)
+        rec[:, 0] = self._bytes + m[:, 0]
+        rec[:, 1], rec[:, 2], rec[:, 3] = ln, m[:, 2], nseg
+        rec[:, 4] = torch.tensor([self._sets[k] for k in keys], dtype=torch.int64)
+        multi = nseg > 1
+        rec[:, 5] = self._segs + torch.cumsum(torch.where(multi, nseg, 0), 0) - torch.where(multi, nseg, 0)
+        rec[:, 6] = self.chunk_rows + torch.cumsum(torch.where(multi, 0, lanes), 0) - torch.where(multi, 0, lanes)
+        rec[:, 7] = H | W << 16 | ncomp << 32 | hs << 36 | vs << 40
+        host_frames[f0:f0 + F] = rec
+        if nsegs:
+            live = torch.arange(m.shape[1] - META_SEG)[None, :] < torch.where(multi, nseg, 0)[:, None]
+            host_segs[self._segs:self._segs + nsegs] = m[:, META_SEG:][live].to(torch.int32)
+        self._geo[f0:f0 + F] = torch.tensor([H, W, ncomp, hs, vs], dtype=torch.int64)
+        self._lanes[f0:f0 + F] = lanes
+        frames, tables, segs = self._dev
+        self._data[self._bytes:self._bytes + n].copy_(data)
+        frames[f0:f0 + F].copy_(rec)
+        if fresh:
+            a = ops.JS_TABLE_PAD + s0 * ops.JS_TABLE_WORDS
+            tables[a:a + len(fresh) * ops.JS_TABLE_WORDS].copy_(host_tables[a:a + len(fresh) * ops.JS_TABLE_WORDS])
+        if nsegs:
+            segs[self._segs:self._segs + nsegs].copy_(host_segs[self._segs:self._segs + nsegs])
+        was = self._frames, self._bytes, self._segs, self.chunk_rows
+        self._frames, self._bytes, self._segs = f0 + F, self._bytes + n, self._segs + nsegs
+        self.chunk_rows += int(lanes[~multi].sum())
+        try:
+            ops.jpeg_store_index(self._buffers(), f0, f0 + F)
+        except Exception:                                      # refused by the entry point: the frames are not kept
+            self._frames, self._bytes, self._segs, self.chunk_rows = was
+            for k in fresh:
+                del self._sets[k]
+            raise
+        return f0
+
+    def plan(self, ids, max_stage_bytes=256 << 20):
+        """The host tables of `decode` for the selection `ids` -> (sel int64 (n,), geo int64 (n, 5), offset, total
+        bytes, stages, blocks): ragged_plan's tables for those frames in that order, every stage's prefix with a
+        third row, the entropy lanes (chunks, or restart segments) of all frames before each one."""
+        sel = torch.as_tensor(ids).reshape(-1)
+        if sel.numel() < 1 or sel.is_floating_point() or sel.is_complex() or sel.dtype == torch.bool:
+            raise ValueError("coclr_amd: ids must be integers, one at least")
+        sel = sel.to("cpu", torch.int64).contiguous()
+        if bool(((sel < 0) | (sel >= self._frames)).any()):
+            raise ValueError("coclr_amd: ids must lie in [0, %d)" % self._frames)
+        geo = self._geo[sel]
+        offset, total, stages, blocks = ragged_plan(geo, max_stage_bytes)
+        lanes = self._lanes[sel]
+        out = []
+        for k, e, geom, prefix in stages:
+            p = torch.zeros(3, e - k + 1, dtype=torch.int64)
+            p[:2] = prefix
+            p[2, 1:] = lanes[k:e].cumsum(0)
+            out.append((k, e, geom, p))
+        return sel, geo, offset, total, out, blocks
+
+    def decode(self, ids, return_status=False, max_stage_bytes=256 << 20):
+        """Frames `ids` (an integer tensor or sequence, in batch order, repeats allowed) -> staging.RaggedFrames, as
+        decode_ragged returns for the same frames in that order.  Ids outside [0, len(store)) are a ValueError before
+        any launch.  Whole frames are decoded `max_stage_bytes` of intermediate storage at a time; the result does
+        not depend on it.  The per-frame status is returned with return_status=True and kept in `decode.last_status`."""
+        from . import staging
+        sel, geo, offset, total, stages, blocks = self.plan(ids, max_stage_bytes)
+        F, device = sel.numel(), self.device
+        tables = torch.cat([sel] + [t.reshape(-1) for _, _, geom, prefix in stages for t in (geom, prefix)])
+        d_tables = tables.to(device)                                         # the selection and every stage's tables
+        d_sel = d_tables[:F]
+        pixels = torch.empty((total + 15) & ~15, dtype=torch.uint8, device=device)
+        coefs = torch.empty(blocks * 64, dtype=torch.int16, device=device)
+        planes = torch.empty(blocks * 64, dtype=torch.uint8, device=device)
+        status = torch.empty(F, dtype=torch.int32, device=device)
+        store, at = self._buffers(), F
+        for k, e, geom, prefix in stages:
+            d_geom = d_tables[at:at + geom.numel()].view(geom.shape)
+            at += geom.numel()
+            d_prefix = d_tables[at:at + prefix.numel()].view(prefix.shape)
+            at += prefix.numel()
+            ops.jpeg_decode_store(store, d_sel[k:e], sel[k:e], d_geom, geom, d_prefix, prefix, coefs, planes, pixels,
+                                  status[k:e])
+        Store.decode.last_status = status
+        frames = staging.RaggedFrames(pixels, offset, geo[:, 0].to(torch.int32), geo[:, 1].to(torch.int32))
+        return (frames, status) if return_status else frames
+
+
+Store.decode.last_status = None
 
 
 def decode_frames(raws, out=None, device=None, max_stage_bytes=256 << 20, chunk_bytes=None):

@@ -1214,6 +1214,59 @@ def jpeg_decode_ragged(data, meta, meta_host, geom, geom_host, prefix, prefix_ho
         _p(status, torch.int32), chunk_bytes, _stream()), "jpeg_decode_ragged")
 
 
+JS_FIELDS, JS_TABLE_WORDS, JS_TABLE_PAD, JS_ROW_WORDS = 8, 768, 16, 4     # csrc/jpeg_core.h: JS_*
+
+
+def jpeg_store_desc(data, frames, frames_host, nframes, tables, tables_host, table_sets, segs, segs_host, nsegs, rows,
+                    chunk_bytes):
+    """The `coclr_jpeg_store` of a store's buffers (include/coclr_hip.h), each on the device with its host copy: data
+    uint8 flat, frames int64 (capacity, 8), tables int32 (16 + sets * 768,), segs int32 flat, rows int32 (capacity, 4).
+    nframes, table_sets and nsegs say how much of each is filled."""
+    for dev, host, ty in ((frames, frames_host, torch.int64), (tables, tables_host, torch.int32),
+                          (segs, segs_host, torch.int32)):
+        if dev.dtype != ty or host.dtype != ty or host.is_cuda or dev.shape != host.shape or \
+                not dev.is_contiguous() or not host.is_contiguous():
+            raise ValueError("coclr_amd: a store's tables are contiguous, device and host alike")
+    if data.dtype != torch.uint8 or data.dim() != 1 or rows.dtype != torch.int32 or not rows.is_contiguous() or \
+            frames.shape[0] < nframes or tables.numel() < JS_TABLE_PAD + table_sets * JS_TABLE_WORDS or \
+            segs.numel() < nsegs:
+        raise ValueError("coclr_amd: a store's buffers do not hold what it says is filled")
+    return _lib.JpegStore(_p(data, torch.uint8), data.numel(), _p(frames, torch.int64), frames_host.data_ptr(),
+                          int(nframes), _p(tables, torch.int32), tables_host.data_ptr(), int(table_sets),
+                          _p(segs, torch.int32) if nsegs else None, segs_host.data_ptr() if nsegs else None, int(nsegs),
+                          _p(rows, torch.int32), rows.numel() // JS_ROW_WORDS, int(chunk_bytes))
+
+
+def jpeg_store_index(store, f0, f1):
+    """Writes the chunk rows of the restart-less frames among store frames [f0, f1) (include/coclr_hip.h:
+    coclr_jpeg_store_index); `store`: the arguments of jpeg_store_desc."""
+    desc = jpeg_store_desc(*store)
+    _lib.check(_L().coclr_jpeg_store_index(C.byref(desc), int(f0), int(f1), _stream()), "jpeg_store_index")
+
+
+def jpeg_decode_store(store, sel, sel_host, geom, geom_host, prefix, prefix_host, coefs, planes, out, status, stages=7):
+    """jpeg_decode_ragged for the store frames `sel` names (include/coclr_hip.h: coclr_jpeg_decode_store): sel int64
+    (F,), geom int64 (F, 8) and prefix int64 (3, F + 1) -- blocks, row groups, entropy lanes -- on the device and the
+    same three on the host; `store`: the arguments of jpeg_store_desc; workspaces and output as jpeg_decode_ragged."""
+    desc = jpeg_store_desc(*store)
+    F = sel_host.numel()
+    for dev, host, want, what in ((sel, sel_host, (F,), "selection"), (geom, geom_host, (F, JR_FIELDS), "geometry table"),
+                                  (prefix, prefix_host, (3, F + 1), "prefix arrays")):
+        if tuple(dev.shape) != want or tuple(host.shape) != want or host.is_cuda or host.dtype != torch.int64 or \
+                dev.dtype != torch.int64 or not dev.is_contiguous() or not host.is_contiguous():
+            raise ValueError("coclr_amd: the %s must be contiguous int64 %s, device and host" % (what, want))
+    blocks = min(coefs.numel() // 64, planes.numel() // 64)
+    if out.dim() != 1 or not out.is_contiguous() or not coefs.is_contiguous() or not planes.is_contiguous() or \
+            blocks < 1:
+        raise ValueError("coclr_amd: jpeg_decode_store needs flat workspaces and a flat output")
+    _check_status(status, F)
+    hp = lambda t: C.cast(t.data_ptr(), C.POINTER(C.c_int64))                # noqa: E731
+    _lib.check(_L().coclr_jpeg_decode_store(
+        C.byref(desc), _p(sel, torch.int64), hp(sel_host), F, _p(geom, torch.int64), hp(geom_host),
+        _p(prefix, torch.int64), hp(prefix_host), int(stages), _p(coefs, torch.int16), _p(planes, torch.uint8), blocks,
+        _p(out, torch.uint8), out.numel(), _p(status, torch.int32), _stream()), "jpeg_decode_store")
+
+
 def resize_boxes_ragged_u8(pixels, desc, desc_host, xtab, ytab, T, S, out):
     """resize_boxes_u8 over a flat byte buffer of frames that differ in size from clip to clip: desc int32
     (n_clips, 14), the ten words of resize_boxes_u8 then {offset low, offset high, W, H} of the clip's frames

@@ -784,6 +784,78 @@ int coclr_jpeg_decode_ragged(const uint8_t* data, int64_t data_len, const int32_
                              int64_t coef_blocks, uint8_t* out, int64_t out_bytes, int32_t* status, int chunk_bytes,
                              void* stream);
 
+/* A dataset's compressed frames kept on the device, parsed and validated once, and decoded by frame index
+ * (coclr_amd/jpeg.py: class Store).  What a frame's Huffman decoder needs to start in the middle of its bytes is a
+ * property of the file, so it is found once (coclr_jpeg_store_index) and every later decode of a restart-less frame
+ * is ONE pass, a lane per chunk, with no rounds (coclr_jpeg_decode_store).
+ * data: every frame's entropy-coded bytes, data_bytes of them, DEVICE; data_bytes may exceed 2^31, one frame's count
+ *   may not.
+ * frames: int64 [nframes][8], DEVICE, and frames_host, the same on the HOST (csrc/jpeg_core.h: JS_*): {first byte
+ *   (64 bits), byte count, restart interval, restart segments, table set, first word in segs, first row in rows,
+ *   H | W << 16 | components << 32 | hs << 36 | vs << 40}.
+ * tables: int32 [16 + table_sets * 768], DEVICE, and tables_host: set i holds words 16 .. 783 of coclr_jpeg_decode's
+ *   descriptor (quantisers, Huffman tables) at word 16 + i * 768, once per distinct set.
+ * segs: int32 [nsegs], DEVICE, and segs_host: for every frame of more than one restart segment the first byte of each,
+ *   relative to the frame's first byte.  May be null when nsegs is 0.
+ * rows: uint32 [nrows][4], DEVICE: for every frame of ONE restart segment a row per chunk of chunk_bytes raw bytes
+ *   (at least one), the serial decoder at the first symbol that starts in the chunk (csrc/jpeg_core.h: jc_row_pack):
+ *   bit, block of the MCU and zigzag index (14 bits), position relative to the chunk (17), "only zero bits are left"
+ *   (1); the frame's blocks completed before it (32); the three DC predictors (3 x 16).  16 bytes per chunk_bytes
+ *   compressed bytes.
+ * chunk_bytes: 8..65536, fixed for the life of the store. */
+typedef struct {
+  const uint8_t* data;
+  int64_t data_bytes;
+  const int64_t* frames;
+  const int64_t* frames_host;
+  int64_t nframes;
+  const int32_t* tables;
+  const int32_t* tables_host;
+  int64_t table_sets;
+  const int32_t* segs;
+  const int32_t* segs_host;
+  int64_t nsegs;
+  uint32_t* rows;
+  int64_t nrows;
+  int32_t chunk_bytes;
+} coclr_jpeg_store;
+
+/* Writes the rows of the restart-less frames among frames [f0, f1) of `st`, whose bytes, records, tables and segment
+ * words are in place: one workgroup per frame runs the scan rounds of coclr_jpeg_decode_split to their fixed point
+ * (in windows of up to 1024 chunks) and stores per chunk the entry state, block count and predictors that its write
+ * pass would start from.  No coefficients are written.  Frames with restart markers get no rows: their segment
+ * offsets are their index.  The kernel reads the device copies and stays inside data, tables and rows whatever they
+ * hold.
+ * COCLR_EINVAL before any launch: a null pointer; chunk_bytes outside 8..65536; f0 < 0, f1 <= f0 or f1 > nframes; a
+ * frame of [f0, f1) whose bytes leave data or number 2^31 or more, whose geometry is not one coclr_jpeg_decode takes,
+ * whose table set does not exist or holds what coclr_jpeg_decode refuses, whose segment count is not ceil(MCUs /
+ * interval), whose segment words leave segs, decrease or leave its bytes, or whose rows leave `rows`.
+ * Additive: the ABI number stays 25 -- no existing signature or behaviour changed. */
+int coclr_jpeg_store_index(const coclr_jpeg_store* st, int64_t f0, int64_t f1, void* stream);
+
+/* coclr_jpeg_decode_ragged for F frames of a store named by a selection: frame i of the call is store frame sel[i];
+ * repeats are allowed.  Bytes, tables, segment words and rows are reached through the selection, bytes with 64-bit
+ * addresses.
+ * sel: int64 [F], DEVICE, and sel_host.
+ * geom, geom_host, coefs, planes, coef_blocks, out, out_bytes, stages, status: as coclr_jpeg_decode_ragged.
+ * prefix: int64 [3][F + 1], DEVICE, and prefix_host: blocks and row groups as there, then the entropy lanes of all
+ *   frames before each one: a frame of one restart segment has a lane per chunk, any other a lane per segment.
+ * Entropy stage: one launch, one pass.  A lane finds its frame by binary search in the third prefix; a chunk's lane
+ * loads its row and decodes the chunk from it (jc_chunk_write), a segment's lane decodes its segment.  Status bits of
+ * a frame's lanes are OR-ed.  A row is the serial decoder's state for those bytes, so coefs, out and status are bit
+ * for bit those of coclr_jpeg_decode on the same bytes, whatever chunk_bytes the store was built with.
+ * The kernels stay in bounds whatever the device copies hold, rows included: a selection outside the store names
+ * frame 0, a record is clamped to the buffers, and a row of any words decodes to garbage inside the frame's own
+ * coefficient blocks (the guarantee jc_chunk_write gives for guessed states).
+ * COCLR_EINVAL before any launch: what coclr_jpeg_decode_ragged refuses of geom, prefix, the workspaces and out; a
+ * selection outside [0, nframes); a selected frame whose recorded geometry is not its row of geom, whose bytes leave
+ * data, whose rows or segment words leave their arrays, or whose third prefix step is not its lane count.
+ * Additive: the ABI number stays 25 -- no existing signature or behaviour changed. */
+int coclr_jpeg_decode_store(const coclr_jpeg_store* st, const int64_t* sel, const int64_t* sel_host, int F,
+                            const int64_t* geom, const int64_t* geom_host, const int64_t* prefix,
+                            const int64_t* prefix_host, int stages, int16_t* coefs, uint8_t* planes,
+                            int64_t coef_blocks, uint8_t* out, int64_t out_bytes, int32_t* status, void* stream);
+
 /* coclr_resize_boxes_u8 for frames that differ in size from clip to clip: `frames` is ONE flat byte buffer of nbytes
  * bytes, 16-byte aligned, and a descriptor is int32 [14]: the ten words of coclr_resize_boxes_u8 ({first frame} is
  * not read) followed by {byte offset of the clip's first frame, low word; high word; W; H} of the clip's T frames,
