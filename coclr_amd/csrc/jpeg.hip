@@ -28,9 +28,16 @@ constexpr int JPEG_MAX_SIDE = 8192;
 // block():  lane id of the inverse DCT -> its frame's first block, and the block within the frame
 // group():  lane id of the colour stage -> first block, the frame's first output byte, row and row group
 // geom():   the geometry these found
+// box, x0(), y0(), width():  what group() found besides: the colour stage's pixel origin in the frame and its output
+//           row's width and pitch: 0, 0 and g.W, except for window_geom, whose rows and groups are those of a BOX of
+//           the frame.  The box is an object of its own so that it lives in registers: `store` is indexed by component
+// window_geom: ragged_geom plus a box per frame (coclr_jpeg_decode_store_window; jpeg_core.h: JW_*).  block() maps a
+// lane to a block of the box's MCU rectangle and returns its FULL-frame index, group() to a row and group of the box:
+// the workspaces keep the full-frame layout, so the kernels address and compute as for a whole frame, on fewer lanes.
 struct one_geom {
   static constexpr bool ragged = false;
   struct store {};
+  struct box {};
   jc_geom g;
   __device__ const jc_geom& geom(const store&) const { return g; }
   __device__ bool frame(long f, store&, long* cb, long* ob) const {
@@ -44,7 +51,7 @@ struct one_geom {
     *cb = f * (long)g.nblocks;
     return true;
   }
-  __device__ bool group(long id, int groups, store&, long* cb, long* ob, int* y, int* xg) const {
+  __device__ bool group(long id, int groups, store&, box&, long* cb, long* ob, int* y, int* xg) const {
     *xg = (int)(id % groups);
     const long row = id / groups;
     *y = (int)(row % g.H);
@@ -53,12 +60,16 @@ struct one_geom {
     *ob = f * (long)g.H * g.W * 3;
     return true;
   }
-  __device__ bool vec_ok(const jc_geom&, long) const { return true; }
+  __device__ bool vec_ok(int, long) const { return true; }
+  __device__ int x0(const box&) const { return 0; }
+  __device__ int y0(const box&) const { return 0; }
+  __device__ int width(const store&, const box&) const { return g.W; }
 };
 
 struct ragged_geom {
-  static constexpr bool ragged = true;
+  static constexpr bool ragged = true, windowed = false;
   typedef jc_geom store;
+  struct box {};
   const int64_t* tab;        // [F][JR_FIELDS]
   const int64_t* blocks;     // [F + 1] prefix of blocks
   const int64_t* rows;       // [F + 1] prefix of row groups
@@ -76,7 +87,7 @@ struct ragged_geom {
     *blk = (int)local;
     return true;
   }
-  __device__ bool group(long id, int, store& o, long* cb, long* ob, int* y, int* xg) const {
+  __device__ bool group(long id, int, store& o, box&, long* cb, long* ob, int* y, int* xg) const {
     const long f = jc_find_frame(rows, F, id);
     if (!frame(f, o, cb, ob)) return false;
     const long local = id - rows[f];
@@ -86,7 +97,49 @@ struct ragged_geom {
     *y = (int)(local / groups);
     return true;
   }
-  __device__ bool vec_ok(const jc_geom& g, long ob) const { return g.W % 16 == 0 && (ob & 15) == 0; }
+  __device__ bool vec_ok(int width, long ob) const { return width % 16 == 0 && (ob & 15) == 0; }
+  __device__ int x0(const box&) const { return 0; }
+  __device__ int y0(const box&) const { return 0; }
+  __device__ int width(const store& o, const box&) const { return o.W; }
+};
+
+struct window_geom {
+  static constexpr bool ragged = true, windowed = true;
+  typedef jc_geom store;
+  typedef jc_window box;
+  const int64_t* tab;        // [F][JR_FIELDS]; JR_OBYTE is the first byte of the frame's 3 * w * h output bytes
+  const int64_t* win;        // [F][JW_FIELDS]
+  const int64_t* blocks;     // [F + 1] prefix of the windows' blocks
+  const int64_t* rows;       // [F + 1] prefix of the boxes' row groups
+  long F, coef_blocks, out_bytes;
+  __device__ const jc_geom& geom(const store& o) const { return o; }
+  __device__ bool frame(long f, store& o, box& w, long* cb, long* ob) const {
+    return jc_window_frame(tab, win, f, coef_blocks, out_bytes, JPEG_MAX_SIDE, o, w, cb, ob);
+  }
+  __device__ bool block(long id, store& o, long* cb, int* blk) const {
+    const long f = jc_find_frame(blocks, F, id);
+    box w;
+    long ob;
+    if (!frame(f, o, w, cb, &ob)) return false;
+    const long local = id - blocks[f];
+    if (local < 0 || local >= jc_window_blocks(o, w)) return false;
+    *blk = jc_window_block(o, w, local);
+    return true;
+  }
+  __device__ bool group(long id, int, store& o, box& w, long* cb, long* ob, int* y, int* xg) const {
+    const long f = jc_find_frame(rows, F, id);
+    if (!frame(f, o, w, cb, ob)) return false;
+    const long local = id - rows[f];
+    if (local < 0 || local >= jc_window_row_groups(w)) return false;
+    const int groups = (w.w + 15) / 16;
+    *xg = (int)(local % groups);
+    *y = (int)(local / groups);
+    return true;
+  }
+  __device__ bool vec_ok(int width, long ob) const { return width % 16 == 0 && (ob & 15) == 0; }
+  __device__ int x0(const box& w) const { return w.x0; }
+  __device__ int y0(const box& w) const { return w.y0; }
+  __device__ int width(const store&, const box& w) const { return w.w; }
 };
 
 // one wave per workgroup: with one lane per frame, 64 frames are all a CU gets, so the waves spread over the CUs
@@ -289,24 +342,27 @@ __global__ __launch_bounds__(256) void jpeg_colour_kernel(const uint8_t* __restr
   const long id = (long)blockIdx.x * 256 + threadIdx.x;
   if (id >= n) return;
   typename GS::store gst;
+  typename GS::box box;
   long cb, ob;
   int y, xg;
-  if (!gs.group(id, groups, gst, &cb, &ob, &y, &xg)) return;
+  if (!gs.group(id, groups, gst, box, &cb, &ob, &y, &xg)) return;
   const jc_geom& g = gs.geom(gst);
   const uint8_t* p = planes + cb * 64;
-  uint8_t* o = out + ob + ((long)y * g.W + (long)xg * 16) * 3;
+  const int width = gs.width(gst, box);                                    // of an output row: g.W, or the box's
+  uint8_t* o = out + ob + ((long)y * width + (long)xg * 16) * 3;
   const int x0 = xg * 16;
-  if (aligned && gs.vec_ok(g, ob)) {
+  const int fx = gs.x0(box) + x0, fy = gs.y0(box) + y;                     // the group's first pixel in the frame
+  if (aligned && gs.vec_ok(width, ob)) {
     __attribute__((aligned(16))) uint8_t px[48];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) jc_pixel(p, g, x0 + i, y, px + 3 * i);
+    for (int i = 0; i < 16; ++i) jc_pixel(p, g, fx + i, fy, px + 3 * i);
 #pragma unroll
     for (int i = 0; i < 3; ++i) reinterpret_cast<uint4*>(o)[i] = reinterpret_cast<const uint4*>(px)[i];
   } else {
-    const int nx = g.W - x0 < 16 ? g.W - x0 : 16;
+    const int nx = width - x0 < 16 ? width - x0 : 16;
     for (int i = 0; i < nx; ++i) {
       uint8_t px[3];
-      jc_pixel(p, g, x0 + i, y, px);
+      jc_pixel(p, g, fx + i, fy, px);
       o[3 * i] = px[0];
       o[3 * i + 1] = px[1];
       o[3 * i + 2] = px[2];
@@ -607,17 +663,29 @@ __global__ __launch_bounds__(1024) void jpeg_store_index_kernel(store_view sv, l
 // The entropy stage of coclr_jpeg_decode_store, one pass: lane id is chunk or restart segment `local` of call frame f
 // (binary search in the lane prefix), which is store frame sel[f].  The geometry and the coefficient blocks are the
 // call's (gs, checked against coef_blocks); bytes, tables and rows are the store's, clamped.
+// GS = window_geom (coclr_jpeg_decode_store_window): only MCUs [first, last) of the frame, the linear range of the
+// window's MCU rectangle, are wanted.  A chunk's lane also loads the NEXT row's block count (a past row, or none: the
+// frame's), returns when the blocks it touches miss the range (jc_window_skips_blocks), and else decodes up to `last`;
+// a segment's lane returns when its MCUs miss the range.  No lane depends on another, so the lanes that run write what
+// they write in a full decode.
+template <class GS>
 __global__ __launch_bounds__(256) void jpeg_entropy_store_kernel(store_view sv, const int64_t* __restrict__ sel,
-                                                                 const int64_t* __restrict__ lanes, long n,
-                                                                 ragged_geom gs, int16_t* __restrict__ coef,
+                                                                 const int64_t* __restrict__ lanes, long n, GS gs,
+                                                                 int16_t* __restrict__ coef,
                                                                  int32_t* __restrict__ status) {
   const long id = (long)blockIdx.x * 256 + threadIdx.x;
   if (id >= n) return;
   const long f = jc_find_frame(lanes, gs.F, id);
   const long local = id - lanes[f];
   jc_geom g;
+  typename GS::box box;
   long cb, ob;
-  if (local < 0 || !gs.frame(f, g, &cb, &ob)) return;
+  if (local < 0) return;
+  if constexpr (GS::windowed) {
+    if (!gs.frame(f, g, box, &cb, &ob)) return;
+  } else {
+    if (!gs.frame(f, g, &cb, &ob)) return;
+  }
   long sf = sel[f];
   sf = sf < 0 || sf >= sv.nframes ? 0 : sf;
   jc_store_frame fr;
@@ -632,11 +700,23 @@ __global__ __launch_bounds__(256) void jpeg_entropy_store_kernel(store_view sv, 
     long block;
     int dc[3];
     const jc_state in = jc_row_unpack(row, jc_chunk_start(fr.len, sv.chunk_bytes, local), fr.len, g, &block, dc);
+    int last = g.mcux * g.mcuy;
+    if constexpr (GS::windowed) {
+      long next = (long)last * g.mcu_blocks;
+      if (local + 1 < jc_chunk_count(0, fr.len, sv.chunk_bytes) && at + 1 < sv.nrows) {
+        const uint2 nw = *reinterpret_cast<const uint2*>(sv.rows + (at + 1) * JS_ROW_WORDS);
+        if (!(nw.x >> 31)) next = (long)nw.y;
+      }
+      if (jc_window_skips_blocks(g, box, block, next)) return;
+      last = (int)jc_window_last(g, box);
+    }
     st = jc_chunk_write(fr.bytes, fr.len, jc_chunk_end(0, fr.len, sv.chunk_bytes, local), sv.chunk_bytes, fr.meta, g,
-                        in, block, dc, 0, g.mcux * g.mcuy, dst);
+                        in, block, dc, 0, last, dst);
   } else {
     int s0, s1, m0, m1;
     if (!jc_store_segment(fr, sv.segs, sv.nsegs, local, g, &s0, &s1, &m0, &m1)) return;
+    if constexpr (GS::windowed)
+      if (jc_window_skips_mcus(g, box, m0, m1)) return;
     st = jc_decode_segment(fr.bytes, s0, s1, fr.meta, g, m0, m1, dst);
   }
   if (st) atomicOr(&status[f], st);
@@ -712,17 +792,46 @@ extern "C" int coclr_jpeg_store_index(const coclr_jpeg_store* st, int64_t f0, in
   return 0;
 }
 
-extern "C" int coclr_jpeg_decode_store(const coclr_jpeg_store* st, const int64_t* sel, const int64_t* sel_host, int F,
-                                       const int64_t* geom, const int64_t* geom_host, const int64_t* prefix,
-                                       const int64_t* prefix_host, int stages, int16_t* coefs, uint8_t* planes,
-                                       int64_t coef_blocks, uint8_t* out, int64_t out_bytes, int32_t* status,
-                                       void* stream) {
+namespace {
+
+// The stages of a store decode over the geometry source GS: ragged_geom (whole frames) or window_geom (a box of each).
+template <class GS>
+int store_stages(const coclr_jpeg_store* st, const int64_t* sel, const int64_t* lanes, const GS& gs, long lanes1,
+                 long lanes2, long lanes3, long first, long cend, int F, int stages, int16_t* coefs, uint8_t* planes,
+                 uint8_t* out, int32_t* status, hipStream_t s) {
+  if (stages & 1) {
+    COCLR_RETURN_IF(hipMemsetAsync(coefs + first * 64, 0, (size_t)(cend - first) * 128, s));
+    COCLR_RETURN_IF(hipMemsetAsync(status, 0, (size_t)F * 4, s));
+    hipLaunchKernelGGL(jpeg_entropy_store_kernel<GS>, dim3(cdiv(lanes1, 256)), dim3(256), 0, s, store_device(st), sel,
+                       lanes, lanes1, gs, coefs, status);
+    COCLR_LAUNCH_CHECK();
+  }
+  if (stages & 2) {
+    hipLaunchKernelGGL(jpeg_idct_kernel<GS>, dim3(cdiv(lanes2, 256)), dim3(256), 0, s, coefs, lanes2, gs, planes);
+    COCLR_LAUNCH_CHECK();
+  }
+  if (stages & 4) {
+    hipLaunchKernelGGL(jpeg_colour_kernel<GS>, dim3(cdiv(lanes3, 256)), dim3(256), 0, s, planes, lanes3, 0, gs, 1, out);
+    COCLR_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// coclr_jpeg_decode_store (window == nullptr) and coclr_jpeg_decode_store_window: everything is checked on the host
+// copies first.  With a window table the output frame is the box (3 * w * h bytes) and the block and row-group
+// prefixes count the box's MCU rectangle and rows; the MCU rectangle is derived here, from the box and the store's
+// host record, never taken from the caller.
+int jpeg_decode_store_impl(const coclr_jpeg_store* st, const int64_t* sel, const int64_t* sel_host, int F,
+                           const int64_t* geom, const int64_t* geom_host, const int64_t* window,
+                           const int64_t* window_host, const int64_t* prefix, const int64_t* prefix_host, int stages,
+                           int16_t* coefs, uint8_t* planes, int64_t coef_blocks, uint8_t* out, int64_t out_bytes,
+                           int32_t* status, void* stream) {
   if (!store_ok(st) || !sel || !sel_host || !geom || !geom_host || !prefix || !prefix_host || !coefs || !planes ||
       !out || !status)
     return COCLR_EINVAL;
   if (F < 1 || stages < 1 || stages > 7 || coef_blocks < 1 || out_bytes < 1) return COCLR_EINVAL;
   if (((uintptr_t)coefs & 15) || ((uintptr_t)planes & 15) || ((uintptr_t)out & 15) || ((uintptr_t)sel & 7) ||
-      ((uintptr_t)geom & 7) || ((uintptr_t)prefix & 7))
+      ((uintptr_t)geom & 7) || ((uintptr_t)prefix & 7) || ((uintptr_t)window & 7))
     return COCLR_EINVAL;
   const int64_t* pblocks = prefix_host;
   const int64_t* prows = prefix_host + F + 1;
@@ -737,37 +846,57 @@ extern "C" int coclr_jpeg_decode_store(const coclr_jpeg_store* st, const int64_t
     if (!store_frame_ok(st, sel_host[f], false, fr, g)) return COCLR_EINVAL;
     if (t[JR_H] != fr.H || t[JR_W] != fr.W || t[JR_NCOMP] != fr.ncomp || t[JR_HS] != fr.hs || t[JR_VS] != fr.vs)
       return COCLR_EINVAL;
+    long obytes = (long)g.H * g.W * 3, nblocks = g.nblocks, ngroups = jc_row_groups(g);
+    if (window_host) {
+      const int64_t* b = window_host + (long)f * JW_FIELDS;
+      jc_window w;
+      if (!jc_window_init(g, b[JW_X0], b[JW_Y0], b[JW_W], b[JW_H], w)) return COCLR_EINVAL;
+      obytes = (long)w.w * w.h * 3;
+      nblocks = jc_window_blocks(g, w);
+      ngroups = jc_window_row_groups(w);
+    }
     // storage: in frame order, no overlap, inside the buffers; an output frame starts 16-byte aligned
     const long cb = t[JR_CBLOCK], ob = t[JR_OBYTE];
     if (cb < cend || cb > coef_blocks - g.nblocks) return COCLR_EINVAL;
-    if (ob < oend || (ob & 15) || ob > out_bytes - (long)g.H * g.W * 3) return COCLR_EINVAL;
+    if (ob < oend || (ob & 15) || ob > out_bytes - obytes) return COCLR_EINVAL;
     cend = cb + g.nblocks;
-    oend = ob + (long)g.H * g.W * 3;
-    if (pblocks[f + 1] - pblocks[f] != g.nblocks || prows[f + 1] - prows[f] != jc_row_groups(g)) return COCLR_EINVAL;
+    oend = ob + obytes;
+    if (pblocks[f + 1] - pblocks[f] != nblocks || prows[f + 1] - prows[f] != ngroups) return COCLR_EINVAL;
     if (pchunks[f + 1] - pchunks[f] != jc_store_lanes(fr.len, fr.nseg, st->chunk_bytes)) return COCLR_EINVAL;
   }
   const long lanes1 = pchunks[F], lanes2 = pblocks[F], lanes3 = prows[F];
   const long limit = 0x7fffffffL;        // workgroups of one launch
   if (lanes1 / 256 >= limit || lanes2 / 256 >= limit || lanes3 / 256 >= limit) return COCLR_EINVAL;
   hipStream_t s = (hipStream_t)stream;
+  const long first = geom_host[JR_CBLOCK];
+  if (window_host) {
+    const window_geom gs = {geom, window, prefix, prefix + F + 1, F, coef_blocks, out_bytes};
+    return store_stages(st, sel, prefix + 2 * (F + 1), gs, lanes1, lanes2, lanes3, first, cend, F, stages, coefs,
+                        planes, out, status, s);
+  }
   const ragged_geom gs = {geom, prefix, prefix + F + 1, F, coef_blocks, out_bytes};
-  if (stages & 1) {
-    const long first = geom_host[JR_CBLOCK];
-    COCLR_RETURN_IF(hipMemsetAsync(coefs + first * 64, 0, (size_t)(cend - first) * 128, s));
-    COCLR_RETURN_IF(hipMemsetAsync(status, 0, (size_t)F * 4, s));
-    hipLaunchKernelGGL(jpeg_entropy_store_kernel, dim3(cdiv(lanes1, 256)), dim3(256), 0, s, store_device(st), sel,
-                       prefix + 2 * (F + 1), lanes1, gs, coefs, status);
-    COCLR_LAUNCH_CHECK();
-  }
-  if (stages & 2) {
-    hipLaunchKernelGGL(jpeg_idct_kernel<ragged_geom>, dim3(cdiv(lanes2, 256)), dim3(256), 0, s, coefs, lanes2, gs,
-                       planes);
-    COCLR_LAUNCH_CHECK();
-  }
-  if (stages & 4) {
-    hipLaunchKernelGGL(jpeg_colour_kernel<ragged_geom>, dim3(cdiv(lanes3, 256)), dim3(256), 0, s, planes, lanes3, 0, gs,
-                       1, out);
-    COCLR_LAUNCH_CHECK();
-  }
-  return 0;
+  return store_stages(st, sel, prefix + 2 * (F + 1), gs, lanes1, lanes2, lanes3, first, cend, F, stages, coefs, planes,
+                      out, status, s);
+}
+
+}  // namespace
+
+extern "C" int coclr_jpeg_decode_store(const coclr_jpeg_store* st, const int64_t* sel, const int64_t* sel_host, int F,
+                                       const int64_t* geom, const int64_t* geom_host, const int64_t* prefix,
+                                       const int64_t* prefix_host, int stages, int16_t* coefs, uint8_t* planes,
+                                       int64_t coef_blocks, uint8_t* out, int64_t out_bytes, int32_t* status,
+                                       void* stream) {
+  return jpeg_decode_store_impl(st, sel, sel_host, F, geom, geom_host, nullptr, nullptr, prefix, prefix_host, stages,
+                                coefs, planes, coef_blocks, out, out_bytes, status, stream);
+}
+
+extern "C" int coclr_jpeg_decode_store_window(const coclr_jpeg_store* st, const int64_t* sel, const int64_t* sel_host,
+                                              int F, const int64_t* geom, const int64_t* geom_host,
+                                              const int64_t* window, const int64_t* window_host, const int64_t* prefix,
+                                              const int64_t* prefix_host, int stages, int16_t* coefs, uint8_t* planes,
+                                              int64_t coef_blocks, uint8_t* out, int64_t out_bytes, int32_t* status,
+                                              void* stream) {
+  if (!window || !window_host) return COCLR_EINVAL;
+  return jpeg_decode_store_impl(st, sel, sel_host, F, geom, geom_host, window, window_host, prefix, prefix_host, stages,
+                                coefs, planes, coef_blocks, out, out_bytes, status, stream);
 }

@@ -703,3 +703,94 @@ JC_HD long jc_chunk_start(int len, int chunk_bytes, long i) {
 JC_HD long jc_store_lanes(int len, int nseg, int chunk_bytes) {
   return nseg == 1 ? jc_chunk_count(0, len, chunk_bytes) : nseg;
 }
+
+// ---- a pixel box of a store frame, decoded alone (coclr_jpeg_decode_store_window) ------------------------------------
+// Per frame JW_FIELDS int64 words: the box x0, y0, w, h inside the frame.  Coefficients and sample planes keep the
+// full-frame layout of jc_geom, so every function above addresses and computes as it does for a whole frame; fewer
+// lanes run.  What must be decoded is the MCU rectangle [mx0, mx1) x [my0, my1) that holds every sample jc_pixel
+// reads for the box's pixels: the luma samples of the box, and on an axis subsampled by 2 the chroma columns or rows
+// (p >> 1) - 1 .. (p >> 1) + 1 that jc_chroma touches, clamped to the plane's real size dw / dh as jc_chroma clamps.
+enum { JW_X0 = 0, JW_Y0, JW_W, JW_H, JW_FIELDS = 4 };
+
+struct jc_window {
+  int x0, y0, w, h;            // the box, inside the frame
+  int mx0, my0, mx1, my1;      // its MCU rectangle
+};
+
+// False: the box is empty or leaves the frame (nothing of `o` is then to be used).
+JC_HD bool jc_window_init(const jc_geom& g, long x0, long y0, long w, long h, jc_window& o) {
+  if (x0 < 0 || y0 < 0 || w < 1 || h < 1 || x0 > g.W - w || y0 > g.H - h) return false;
+  o.x0 = (int)x0; o.y0 = (int)y0; o.w = (int)w; o.h = (int)h;
+  const int xl = (int)(x0 + w - 1), yl = (int)(y0 + h - 1);
+  o.mx0 = o.x0 / (8 * g.hs);
+  o.mx1 = xl / (8 * g.hs);
+  o.my0 = o.y0 / (8 * g.vs);
+  o.my1 = yl / (8 * g.vs);
+  if (g.ncomp == 3 && g.hs == 2) {
+    int lo = (o.x0 >> 1) - 1, hi = (xl >> 1) + 1;
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > g.dw - 1 ? g.dw - 1 : hi;
+    o.mx0 = lo / 8 < o.mx0 ? lo / 8 : o.mx0;
+    o.mx1 = hi / 8 > o.mx1 ? hi / 8 : o.mx1;
+  }
+  if (g.ncomp == 3 && g.vs == 2) {
+    int lo = (o.y0 >> 1) - 1, hi = (yl >> 1) + 1;
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > g.dh - 1 ? g.dh - 1 : hi;
+    o.my0 = lo / 8 < o.my0 ? lo / 8 : o.my0;
+    o.my1 = hi / 8 > o.my1 ? hi / 8 : o.my1;
+  }
+  ++o.mx1;
+  ++o.my1;
+  return true;
+}
+
+JC_HD long jc_window_blocks(const jc_geom& g, const jc_window& o) {         // inverse-DCT lanes of a window
+  return (long)(o.mx1 - o.mx0) * (o.my1 - o.my0) * g.mcu_blocks;
+}
+
+JC_HD long jc_window_row_groups(const jc_window& o) { return (long)o.h * ((o.w + 15) / 16); }   // colour lanes
+
+JC_HD long jc_window_first(const jc_geom& g, const jc_window& o) { return (long)o.my0 * g.mcux + o.mx0; }
+JC_HD long jc_window_last(const jc_geom& g, const jc_window& o) { return (long)(o.my1 - 1) * g.mcux + o.mx1; }
+
+// Block `local` (0 <= local < jc_window_blocks) of the window -> its index in the FULL frame's coefficient order: the
+// window's luma blocks row by row, then its Cb blocks, then its Cr blocks.
+JC_HD int jc_window_block(const jc_geom& g, const jc_window& o, long local) {
+  const long mcus = (long)(o.mx1 - o.mx0) * (o.my1 - o.my0);
+  const long luma = g.ncomp == 1 ? mcus : mcus * g.hs * g.vs;
+  const int c = local < luma ? 0 : local < luma + mcus ? 1 : 2;
+  const long i = c == 0 ? local : local - luma - (c - 1) * mcus;
+  const int sx = c == 0 ? g.hs : 1, sy = c == 0 ? g.vs : 1;
+  const int wb = (o.mx1 - o.mx0) * sx;
+  const int by = o.my0 * sy + (int)(i / wb), bx = o.mx0 * sx + (int)(i % wb);
+  return g.boff[c] + by * g.bw[c] + bx;
+}
+
+// An entropy lane that touches blocks b0 .. b1 of the frame (a chunk: the blocks completed before it through those
+// completed before the next chunk -- the block in progress at the boundary has symbols in both) decodes nothing the
+// window needs when the range lies wholly before the window's first MCU or starts at or after the end of its last.
+JC_HD bool jc_window_skips_blocks(const jc_geom& g, const jc_window& o, long b0, long b1) {
+  return b1 < jc_window_first(g, o) * g.mcu_blocks || b0 >= jc_window_last(g, o) * g.mcu_blocks;
+}
+
+JC_HD bool jc_window_skips_mcus(const jc_geom& g, const jc_window& o, long m0, long m1) {     // a restart segment
+  return m1 <= jc_window_first(g, o) || m0 >= jc_window_last(g, o);
+}
+
+// jc_ragged_frame for a window: frame f's geometry and first block as there, its box from `win`, and its first output
+// byte checked for the 3 * w * h bytes the box takes.  False (the frame is skipped) unless all of it holds.
+JC_HD bool jc_window_frame(const int64_t* tab, const int64_t* win, long f, long coef_blocks, long out_bytes,
+                           long max_side, jc_geom& g, jc_window& o, long* cblock, long* obyte) {
+  const int64_t* t = tab + f * JR_FIELDS;
+  const int64_t* b = win + f * JW_FIELDS;
+  if (!jc_geometry_ok(t[JR_H], t[JR_W], t[JR_NCOMP], t[JR_HS], t[JR_VS], max_side)) return false;
+  jc_geom_init(g, (int)t[JR_H], (int)t[JR_W], (int)t[JR_NCOMP], (int)t[JR_HS], (int)t[JR_VS]);
+  if (!jc_window_init(g, b[JW_X0], b[JW_Y0], b[JW_W], b[JW_H], o)) return false;
+  const long cb = t[JR_CBLOCK], ob = t[JR_OBYTE];
+  if (cb < 0 || cb > coef_blocks - g.nblocks) return false;
+  if (ob < 0 || ob > out_bytes - (long)o.w * o.h * 3) return false;
+  *cblock = cb;
+  *obyte = ob;
+  return true;
+}

@@ -10,7 +10,8 @@ A batch whose videos differ in frame size (kinetics400-256 keeps every video's a
 `cat_ragged` and `decode_ragged` instead, to a staging.RaggedFrames that stage_train_clips_ragged and
 stage_classifier_clips_ragged take; `pack`, per video, is the same.
 A dataset that fits into the device's memory can stay there compressed: `Store.add(pack)` per video, once, then
-`Store.decode(ids)` per step by frame index, to the same RaggedFrames, with nothing but the ids travelling (class Store).
+`Store.decode(ids)` per step by frame index, to the same RaggedFrames, with nothing but the ids travelling (class Store);
+`Store.decode(ids, boxes)` decodes one pixel box of every frame alone, what staging.stage_train_clips_cropped takes.
 
 Scope: baseline / extended sequential Huffman (SOF0, SOF1), 8-bit, one interleaved scan, one component or YCbCr with
 luma sampled 1x1, 2x1 or 2x2, optional restart intervals -- what ffmpeg, cv2.imwrite and PIL write by default.
@@ -512,6 +513,49 @@ def decode_ragged(data, meta, device=None, max_stage_bytes=256 << 20, return_sta
 decode_ragged.last_status = None
 
 
+def _window_mcus(geo, boxes):
+    """window_mcus for int64 tables: geo (n, 5) H, W, components, hs, vs; boxes (n, 4) -> int64 (n, 4)."""
+    H, W, ncomp, hs, vs = geo.unbind(1)
+    x0, y0, w, h = boxes.unbind(1)
+
+    def axis(p0, n, size, s):
+        last = p0 + n - 1
+        lo, hi = p0 // (8 * s), last // (8 * s)
+        sub = (ncomp == 3) & (s == 2)
+        clo = ((p0 >> 1) - 1).clamp(min=0) // 8
+        chi = torch.minimum((size + 1) // 2 - 1, (last >> 1) + 1) // 8
+        return torch.where(sub, torch.minimum(lo, clo), lo), torch.where(sub, torch.maximum(hi, chi), hi) + 1
+
+    (mx0, mx1), (my0, my1) = axis(x0, w, W, hs), axis(y0, h, H, vs)
+    return torch.stack([mx0, my0, mx1, my1], 1)
+
+
+def window_mcus(H, W, ncomp, hs, vs, x0, y0, w, h):
+    """The MCU rectangle (mx0, my0, mx1, my1), ends exclusive, that holds every sample the decoder reads for the pixel
+    box (x0, y0, w, h) of a frame (csrc/jpeg_core.h: jc_window_init, which the entry point runs itself): the box's luma
+    samples and, on an axis subsampled by 2, chroma columns or rows (p >> 1) - 1 .. (p >> 1) + 1 clamped to the plane."""
+    return tuple(_window_mcus(torch.tensor([[H, W, ncomp, hs, vs]]), torch.tensor([[x0, y0, w, h]]))[0].tolist())
+
+
+def _check_boxes(boxes, geo):
+    """`boxes` of Store.decode / Store.plan against the selected frames' geometry -> int64 (n, 4) on the host."""
+    n = geo.shape[0]
+    try:
+        boxes = torch.as_tensor(boxes)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError("coclr_amd: boxes must be an integer (n, 4) tensor or sequence: x0, y0, w, h per frame")
+    if boxes.is_floating_point() or boxes.is_complex() or boxes.dtype == torch.bool or tuple(boxes.shape) != (n, 4):
+        raise ValueError("coclr_amd: boxes must be integers of shape (%d, 4): x0, y0, w, h per selected frame, got %s %s"
+                         % (n, boxes.dtype, tuple(boxes.shape)))
+    boxes = boxes.to("cpu", torch.int64).contiguous()
+    x0, y0, w, h = boxes.unbind(1)
+    if bool(((w < 1) | (h < 1)).any()):
+        raise ValueError("coclr_amd: a box is at least 1 x 1")
+    if bool(((x0 < 0) | (y0 < 0) | (x0 > geo[:, 1] - w) | (y0 > geo[:, 0] - h)).any()):
+        raise ValueError("coclr_amd: a box leaves its frame")
+    return boxes
+
+
 def _store_policy(chunk_bytes):
     """A store's chunk size: `chunk_bytes` if given, else DEFAULT_STORE_CHUNK; 8..65536 (a store has no serial path)."""
     chunk_bytes = split_policy(DEFAULT_STORE_CHUNK if chunk_bytes is None else chunk_bytes)
@@ -658,10 +702,14 @@ class Store:
             raise
         return f0
 
-    def plan(self, ids, max_stage_bytes=256 << 20):
+    def plan(self, ids, max_stage_bytes=256 << 20, boxes=None):
         """The host tables of `decode` for the selection `ids` -> (sel int64 (n,), geo int64 (n, 5), offset, total
         bytes, stages, blocks): ragged_plan's tables for those frames in that order, every stage's prefix with a
-        third row, the entropy lanes (chunks, or restart segments) of all frames before each one."""
+        third row, the entropy lanes (chunks, or restart segments) of all frames before each one.
+        With `boxes` (x0, y0, w, h per selected frame) the tables are those of coclr_jpeg_decode_store_window, and the
+        tuple has a seventh member, the window table int64 (n, 4): offset and total lay out the h x w boxes, a stage's
+        geom names those offsets and its first two prefix rows count the box's MCU rectangle and row groups.  The
+        stages themselves, the coefficient blocks and `blocks` are unchanged: the workspace stays full-frame."""
         sel = torch.as_tensor(ids).reshape(-1)
         if sel.numel() < 1 or sel.is_floating_point() or sel.is_complex() or sel.dtype == torch.bool:
             raise ValueError("coclr_amd: ids must be integers, one at least")
@@ -677,19 +725,46 @@ class Store:
             p[:2] = prefix
             p[2, 1:] = lanes[k:e].cumsum(0)
             out.append((k, e, geom, p))
-        return sel, geo, offset, total, out, blocks
+        if boxes is None:
+            return sel, geo, offset, total, out, blocks
+        boxes = _check_boxes(boxes, geo)
+        size = 3 * boxes[:, 2] * boxes[:, 3]
+        step = (size + 15) & ~15
+        offset = step.cumsum(0) - step
+        total = int(offset[-1] + size[-1])
+        rect = _window_mcus(geo, boxes)
+        per_mcu = torch.where(geo[:, 2] == 1, 1, geo[:, 3] * geo[:, 4] + 2)
+        nblocks = (rect[:, 2] - rect[:, 0]) * (rect[:, 3] - rect[:, 1]) * per_mcu
+        rows = boxes[:, 3] * ((boxes[:, 2] + 15) // 16)
+        for k, e, geom, p in out:
+            geom[:, 6] = offset[k:e]
+            p[0, 1:] = nblocks[k:e].cumsum(0)
+            p[1, 1:] = rows[k:e].cumsum(0)
+        return sel, geo, offset, total, out, blocks, boxes
 
-    def decode(self, ids, return_status=False, max_stage_bytes=256 << 20):
+    def decode(self, ids, boxes=None, return_status=False, max_stage_bytes=256 << 20):
         """Frames `ids` (an integer tensor or sequence, in batch order, repeats allowed) -> staging.RaggedFrames, as
         decode_ragged returns for the same frames in that order.  Ids outside [0, len(store)) are a ValueError before
         any launch.  Whole frames are decoded `max_stage_bytes` of intermediate storage at a time; the result does
-        not depend on it.  The per-frame status is returned with return_status=True and kept in `decode.last_status`."""
+        not depend on it.  The per-frame status is returned with return_status=True and kept in `decode.last_status`.
+        `boxes`: an integer (n, 4) tensor or sequence, x0, y0, w, h per selected frame; frame i of the result is then
+        that h x w region alone, bit for bit `decode(ids).frame(i)[y0:y0 + h, x0:x0 + w]`, and only the chunks, restart
+        segments, blocks and pixels it needs are decoded (coclr_jpeg_decode_store_window; staging.clip_frames makes
+        ids and boxes from a batch's plans).  A box of a wrong shape or type, smaller than 1 x 1 or leaving its frame
+        is a ValueError before any launch.  The status then reports damage met in what WAS decoded only; clean files
+        give 0 either way.  The workspace, and so `max_stage_bytes`, still counts full frames."""
         from . import staging
-        sel, geo, offset, total, stages, blocks = self.plan(ids, max_stage_bytes)
+        window = None
+        if boxes is None:
+            sel, geo, offset, total, stages, blocks = self.plan(ids, max_stage_bytes)
+        else:
+            sel, geo, offset, total, stages, blocks, window = self.plan(ids, max_stage_bytes, boxes)
         F, device = sel.numel(), self.device
-        tables = torch.cat([sel] + [t.reshape(-1) for _, _, geom, prefix in stages for t in (geom, prefix)])
+        tables = torch.cat([sel] + [t.reshape(-1) for _, _, geom, prefix in stages for t in (geom, prefix)] +
+                           ([] if window is None else [window.reshape(-1)]))
         d_tables = tables.to(device)                                         # the selection and every stage's tables
         d_sel = d_tables[:F]
+        d_window = None if window is None else d_tables[tables.numel() - window.numel():].view(window.shape)
         pixels = torch.empty((total + 15) & ~15, dtype=torch.uint8, device=device)
         coefs = torch.empty(blocks * 64, dtype=torch.int16, device=device)
         planes = torch.empty(blocks * 64, dtype=torch.uint8, device=device)
@@ -700,10 +775,17 @@ class Store:
             at += geom.numel()
             d_prefix = d_tables[at:at + prefix.numel()].view(prefix.shape)
             at += prefix.numel()
-            ops.jpeg_decode_store(store, d_sel[k:e], sel[k:e], d_geom, geom, d_prefix, prefix, coefs, planes, pixels,
-                                  status[k:e])
+            if window is None:
+                ops.jpeg_decode_store(store, d_sel[k:e], sel[k:e], d_geom, geom, d_prefix, prefix, coefs, planes,
+                                      pixels, status[k:e])
+            else:
+                ops.jpeg_decode_store_window(store, d_sel[k:e], sel[k:e], d_geom, geom, d_window[k:e], window[k:e],
+                                             d_prefix, prefix, coefs, planes, pixels, status[k:e])
         Store.decode.last_status = status
-        frames = staging.RaggedFrames(pixels, offset, geo[:, 0].to(torch.int32), geo[:, 1].to(torch.int32))
+        if window is None:
+            frames = staging.RaggedFrames(pixels, offset, geo[:, 0].to(torch.int32), geo[:, 1].to(torch.int32))
+        else:
+            frames = staging.RaggedFrames(pixels, offset, window[:, 3].to(torch.int32), window[:, 2].to(torch.int32))
         return (frames, status) if return_status else frames
 
 

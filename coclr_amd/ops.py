@@ -1244,27 +1244,54 @@ def jpeg_store_index(store, f0, f1):
     _lib.check(_L().coclr_jpeg_store_index(C.byref(desc), int(f0), int(f1), _stream()), "jpeg_store_index")
 
 
-def jpeg_decode_store(store, sel, sel_host, geom, geom_host, prefix, prefix_host, coefs, planes, out, status, stages=7):
-    """jpeg_decode_ragged for the store frames `sel` names (include/coclr_hip.h: coclr_jpeg_decode_store): sel int64
-    (F,), geom int64 (F, 8) and prefix int64 (3, F + 1) -- blocks, row groups, entropy lanes -- on the device and the
-    same three on the host; `store`: the arguments of jpeg_store_desc; workspaces and output as jpeg_decode_ragged."""
+JW_FIELDS = 4        # csrc/jpeg_core.h: per frame the box x0, y0, w, h
+
+
+def _jpeg_decode_store(who, store, sel, sel_host, geom, geom_host, window, prefix, prefix_host, coefs, planes, out,
+                       status, stages):
+    """The body of jpeg_decode_store (`window` None) and jpeg_decode_store_window (`window`: the table, device and
+    host)."""
     desc = jpeg_store_desc(*store)
     F = sel_host.numel()
-    for dev, host, want, what in ((sel, sel_host, (F,), "selection"), (geom, geom_host, (F, JR_FIELDS), "geometry table"),
-                                  (prefix, prefix_host, (3, F + 1), "prefix arrays")):
+    tables = [(sel, sel_host, (F,), "selection"), (geom, geom_host, (F, JR_FIELDS), "geometry table"),
+              (prefix, prefix_host, (3, F + 1), "prefix arrays")]
+    if window is not None:
+        tables.append(window + ((F, JW_FIELDS), "window table"))
+    for dev, host, want, what in tables:
         if tuple(dev.shape) != want or tuple(host.shape) != want or host.is_cuda or host.dtype != torch.int64 or \
                 dev.dtype != torch.int64 or not dev.is_contiguous() or not host.is_contiguous():
             raise ValueError("coclr_amd: the %s must be contiguous int64 %s, device and host" % (what, want))
     blocks = min(coefs.numel() // 64, planes.numel() // 64)
     if out.dim() != 1 or not out.is_contiguous() or not coefs.is_contiguous() or not planes.is_contiguous() or \
             blocks < 1:
-        raise ValueError("coclr_amd: jpeg_decode_store needs flat workspaces and a flat output")
+        raise ValueError("coclr_amd: %s needs flat workspaces and a flat output" % who)
     _check_status(status, F)
     hp = lambda t: C.cast(t.data_ptr(), C.POINTER(C.c_int64))                # noqa: E731
-    _lib.check(_L().coclr_jpeg_decode_store(
-        C.byref(desc), _p(sel, torch.int64), hp(sel_host), F, _p(geom, torch.int64), hp(geom_host),
-        _p(prefix, torch.int64), hp(prefix_host), int(stages), _p(coefs, torch.int16), _p(planes, torch.uint8), blocks,
-        _p(out, torch.uint8), out.numel(), _p(status, torch.int32), _stream()), "jpeg_decode_store")
+    head = (C.byref(desc), _p(sel, torch.int64), hp(sel_host), F, _p(geom, torch.int64), hp(geom_host))
+    tail = (_p(prefix, torch.int64), hp(prefix_host), int(stages), _p(coefs, torch.int16), _p(planes, torch.uint8),
+            blocks, _p(out, torch.uint8), out.numel(), _p(status, torch.int32), _stream())
+    if window is None:
+        _lib.check(_L().coclr_jpeg_decode_store(*head, *tail), who)
+    else:
+        _lib.check(_L().coclr_jpeg_decode_store_window(*head, _p(window[0], torch.int64), hp(window[1]), *tail), who)
+
+
+def jpeg_decode_store(store, sel, sel_host, geom, geom_host, prefix, prefix_host, coefs, planes, out, status, stages=7):
+    """jpeg_decode_ragged for the store frames `sel` names (include/coclr_hip.h: coclr_jpeg_decode_store): sel int64
+    (F,), geom int64 (F, 8) and prefix int64 (3, F + 1) -- blocks, row groups, entropy lanes -- on the device and the
+    same three on the host; `store`: the arguments of jpeg_store_desc; workspaces and output as jpeg_decode_ragged."""
+    _jpeg_decode_store("jpeg_decode_store", store, sel, sel_host, geom, geom_host, None, prefix, prefix_host, coefs,
+                       planes, out, status, stages)
+
+
+def jpeg_decode_store_window(store, sel, sel_host, geom, geom_host, window, window_host, prefix, prefix_host, coefs,
+                             planes, out, status, stages=7):
+    """jpeg_decode_store for one pixel box of every frame (include/coclr_hip.h: coclr_jpeg_decode_store_window):
+    window int64 (F, 4) -- x0, y0, w, h -- on the device and the host; frame i of `out` is its h x w box at geom[i, 6];
+    the first two rows of `prefix` count the box's MCU rectangle and row groups; the workspaces keep the full-frame
+    layout."""
+    _jpeg_decode_store("jpeg_decode_store_window", store, sel, sel_host, geom, geom_host, (window, window_host), prefix,
+                       prefix_host, coefs, planes, out, status, stages)
 
 
 def resize_boxes_ragged_u8(pixels, desc, desc_host, xtab, ytab, T, S, out):

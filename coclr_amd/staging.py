@@ -1214,3 +1214,84 @@ def stage_classifier_clips_ragged(frames, plans, img_dim, flip=False, first=None
     samples = _ragged_samples(frames, B, T, first)
     tables = classifier_tables_ragged(plans, samples, T, S, size, flip)
     return _stage_classifier(True, frames.pixels, frames.pixels.device, tables, B, T, S, size, mean, std, out)
+
+
+# ---- training clips whose frames were decoded as their crop boxes alone (jpeg.Store.decode(ids, boxes)) ---------------
+
+def clip_frames(ids, plans, T):
+    """What a batch's clips read, for jpeg.Store.decode(sel, boxes): ids (B, 2T) store ids, sample b's 2 T frames;
+    plans: B plans of TrainTransform.draw, or their pack_plan tensors stacked.  Returns (sel int64 (2 B T,), boxes
+    int64 (2 B T, 4)): for clip c of sample b the T ids of half[c] of the sample's frames, each with box[c] -- the
+    layout stage_train_clips_cropped takes.  A half that no clip reads (OneClipTransform) is not selected, so it is
+    not decoded; a half both clips read is selected twice, once per box."""
+    T = int(T)
+    ids = torch.as_tensor(ids)
+    if ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool or ids.dim() != 2 or T < 1 or \
+            ids.shape[1] != 2 * T or ids.shape[0] < 1:
+        raise ValueError("coclr_amd: ids must be integers of shape (B, 2 T), got %s %s for T = %d" %
+                         (ids.dtype, tuple(ids.shape), T))
+    ids = ids.to("cpu", torch.int64)
+    plans = _plan_list([plans] if isinstance(plans, dict) else plans, unpack_plan, 2)
+    if len(plans) != ids.shape[0]:
+        raise ValueError("coclr_amd: %d plans for %d samples" % (len(plans), ids.shape[0]))
+    sel, boxes = [], []
+    for b, plan in enumerate(plans):
+        if len(plan["half"]) != 2 or len(plan["box"]) != 2:
+            raise ValueError("coclr_amd: a plan names two clips")
+        for c in range(2):
+            half, box = plan["half"][c], plan["box"][c]
+            if half not in (0, 1) or isinstance(half, bool):
+                raise ValueError("coclr_amd: a clip reads half 0 or 1 of the frames, got %r" % (half,))
+            if len(box) != 4 or any(int(v) != v for v in box):
+                raise ValueError("coclr_amd: a box is four integers, got %r" % (box,))
+            sel.append(ids[b, int(half) * T:(int(half) + 1) * T])
+            boxes.extend([[int(v) for v in box]] * T)
+    return torch.cat(sel), torch.tensor(boxes, dtype=torch.int64)
+
+
+def train_tables_cropped(plans, clips, T, S):
+    """train_tables_ragged for clips whose frames ARE their boxes: `clips` [(byte offset of the clip's first frame, w,
+    h)], two per plan; clip c of a plan must have its box[c]'s size.  The descriptors read the whole of every frame,
+    (0, T, 0, 0, w, h), so the axis tables, the programs and the group size are train_tables_ragged's for the same
+    plans.  Returns (desc int32 (2B, 14), xtab, ytab, kinds, params, group_size), all on the host."""
+    plans = _plan_list(plans, unpack_plan, 2)
+    if 2 * len(plans) != len(clips):
+        raise ValueError("coclr_amd: %d plans for %d clips" % (len(plans), len(clips)))
+    rows, programs, rag = [], [], []
+    for b, plan in enumerate(plans):
+        W = max(int(box[0] + box[2]) for box in plan["box"])              # the frame is gone: each box against itself
+        H = max(int(box[1] + box[3]) for box in plan["box"])
+        r, p = check_train_plans([plan], 1, T, W, H)
+        for c, row in enumerate(r):
+            offset, w, h = clips[2 * b + c]
+            if (w, h) != (row[4], row[5]):
+                raise ValueError("coclr_amd: clip %d of sample %d holds %d x %d frames and its box is %d x %d" %
+                                 (c, b, w, h, row[4], row[5]))
+            rows.append((0, T, 0, 0, w, h))
+            rag.append(_rag_words(offset, w, h))
+        programs.extend(p)
+    return _train_tables(rows, programs, rag, T, S)
+
+
+def stage_train_clips_cropped(frames, plans, out_size, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
+    """stage_train_clips_ragged for frames decoded as their crop boxes alone, the same TWO launches
+    (coclr_resize_boxes_ragged_u8 reading every frame whole, then coclr_augment_clips):
+        frames = store.decode(*clip_frames(ids, plans, T))
+    frames: RaggedFrames of 2 B T frames; clip (b, c) is frames (2 b + c) T .. + T - 1, all of the size of box[c] of
+    plan b, following each other at 3 w h bytes rounded up to 16 (checked here, on the host).  plans: the B plans
+    clip_frames was given.  Returns (B, 2, 3, T, S, S) fp32 on the device, bit for bit stage_train_clips_ragged's
+    result on the whole frames."""
+    plans = _plan_list([plans] if isinstance(plans, dict) else plans, unpack_plan, 2)
+    B, S = len(plans), int(out_size)
+    if B < 1:
+        raise ValueError("coclr_amd: stage_train_clips_cropped needs at least one plan")
+    T = len(plans[0]["programs"][0])
+    if T < 1:
+        raise ValueError("coclr_amd: a plan has one program per frame")
+    if S < 1 or S * S > JITTER_MAX_PIXELS:
+        raise ValueError("coclr_amd: stage_train_clips_cropped takes an output size of 1..224, got %d" % S)
+    if isinstance(frames, RaggedFrames) and len(frames) != 2 * B * T:
+        raise ValueError("coclr_amd: %d frames for %d clips of %d" % (len(frames), 2 * B, T))
+    clips = _ragged_samples(frames, 2 * B, T, None)                          # a clip's frames: one size, one stride
+    tables = train_tables_cropped(plans, [(o, W, H) for o, W, H in clips], T, S)
+    return _stage_train(ops.resize_boxes_ragged_u8, frames.pixels, frames.pixels.device, tables, B, T, S, mean, std, out)

@@ -856,6 +856,37 @@ int coclr_jpeg_decode_store(const coclr_jpeg_store* st, const int64_t* sel, cons
                             const int64_t* prefix_host, int stages, int16_t* coefs, uint8_t* planes,
                             int64_t coef_blocks, uint8_t* out, int64_t out_bytes, int32_t* status, void* stream);
 
+/* coclr_jpeg_decode_store for ONE pixel box of every selected frame (what nvJPEG calls a ROI decode): the training
+ * transform crops before it resizes, so no pixel outside a clip's RandomSizedCrop box reaches the model.
+ * window: int64 [F][4], DEVICE, and window_host: {x0, y0, w, h} of frame i's box inside the frame (csrc/jpeg_core.h:
+ *   JW_*).
+ * out: frame i is its box alone, h x w x 3 bytes at geom[i][6], rows w * 3 bytes apart; offsets in frame order,
+ *   16-byte aligned, the frames neither overlapping nor leaving out_bytes.
+ * prefix: int64 [3][F + 1] as coclr_jpeg_decode_store, with the first two rows counted for the window: the blocks of the
+ *   box's MCU rectangle, and the box's row groups h * ceil(w / 16).  The third row is unchanged: every chunk and
+ *   segment keeps its lane, and a lane that has nothing to do returns.
+ * coefs, planes, coef_blocks, geom[i][5]: the FULL-frame layout of coclr_jpeg_decode_store, so every block and sample
+ *   lies where a whole decode puts it and the arithmetic is the same at the same addresses, on fewer lanes.  The entry
+ *   derives the MCU rectangle [mx0, mx1) x [my0, my1) itself, from the box and the store's host record: the MCUs of
+ *   the box's luma samples and of the chroma samples the fancy upsampling reads for them (on an axis subsampled by 2,
+ *   columns or rows (p >> 1) - 1 .. (p >> 1) + 1 clamped to the plane's real size).  With first = my0 * mcux + mx0 and
+ *   last = (my1 - 1) * mcux + mx1:
+ *   entropy   a chunk's lane reads its row and the next row's block count and returns when the blocks it touches lie
+ *             wholly before MCU `first` or start at or after MCU `last`; else it decodes its chunk, up to `last`.  A
+ *             segment's lane returns when its MCUs miss [first, last).  Blocks of MCUs at or after `last` stay zero.
+ *   idct      a lane per block of the MCU rectangle.     colour   a lane per 16 pixels of a row of the box.
+ * The bytes of `out` are bit for bit the box cut from coclr_jpeg_decode_store's frame.  status holds the bits met in
+ * the chunks and segments that WERE decoded: damage outside them goes unreported; a clean file gives 0 either way.
+ * Sample planes outside the MCU rectangle are not written and not read.  The bounds of coclr_jpeg_decode_store hold.
+ * COCLR_EINVAL before any launch: what coclr_jpeg_decode_store refuses (output frames and the first two prefix rows
+ * measured for the window); a null window table; w < 1, h < 1, or a box that leaves its frame.
+ * Additive: the ABI number stays 25 -- no existing signature or behaviour changed. */
+int coclr_jpeg_decode_store_window(const coclr_jpeg_store* st, const int64_t* sel, const int64_t* sel_host, int F,
+                                   const int64_t* geom, const int64_t* geom_host, const int64_t* window,
+                                   const int64_t* window_host, const int64_t* prefix, const int64_t* prefix_host,
+                                   int stages, int16_t* coefs, uint8_t* planes, int64_t coef_blocks, uint8_t* out,
+                                   int64_t out_bytes, int32_t* status, void* stream);
+
 /* coclr_resize_boxes_u8 for frames that differ in size from clip to clip: `frames` is ONE flat byte buffer of nbytes
  * bytes, 16-byte aligned, and a descriptor is int32 [14]: the ten words of coclr_resize_boxes_u8 ({first frame} is
  * not read) followed by {byte offset of the clip's first frame, low word; high word; W; H} of the clip's T frames,
