@@ -10,7 +10,11 @@
 // entry is its predecessor's exit (jpeg_core.h), which is the serial decoder's result for any bytes.
 // A store (coclr_jpeg_store_index, coclr_jpeg_decode_store, at the end) finds those states once per frame and keeps
 // them: jpeg_store_index_kernel is the split kernel without its write pass, jpeg_entropy_store_kernel the write pass
-// alone, a lane per chunk of any frame of the call.
+// alone, a lane per chunk of any frame of the call.  The two kernels that find the states share one window loop
+// (split_windows) and differ in what a lane does with its true entry.
+// On the host every entry point is its own validation of its arguments and its choice of a geometry source; what they
+// check alike (tables_ok, offsets_ok, frame_storage_ok), how frames are dealt to the two entropy kernels (plan_split,
+// split_lanes, launch_entropy) and the stages themselves (run_stages) exist once.
 #include "../../include/coclr_hip.h"
 #include "common.h"
 #include "jpeg_core.h"
@@ -22,16 +26,17 @@ constexpr int JPEG_MAX_SIDE = 8192;
 // Where a kernel gets a frame's geometry and storage from.  one_geom: the call's single geometry, by value, frame f
 // at f times the per-frame sizes (coclr_jpeg_decode, coclr_jpeg_decode_split); the kernels read it where it lies, in
 // the kernel arguments (a copy would cost LDS or scratch: it is indexed by component), and `store` is empty.
-// ragged_geom: per frame from the device table of coclr_jpeg_decode_ragged, built into the caller's `store`; a lane
-// finds its frame by binary search over the prefix of lane counts.  False: skip.
-// frame():  frame f -> its first block and first output byte
+// table_geom<false>: per frame from the device table of coclr_jpeg_decode_ragged or coclr_jpeg_decode_store, built into
+// the caller's `store`; a lane finds its frame by binary search over the prefix of lane counts.  False: skip.
+// frame():  frame f -> its first block and first output byte (and, given a box to fill, its box)
 // block():  lane id of the inverse DCT -> its frame's first block, and the block within the frame
 // group():  lane id of the colour stage -> first block, the frame's first output byte, row and row group
 // geom():   the geometry these found
 // box, x0(), y0(), width():  what group() found besides: the colour stage's pixel origin in the frame and its output
-//           row's width and pitch: 0, 0 and g.W, except for window_geom, whose rows and groups are those of a BOX of
-//           the frame.  The box is an object of its own so that it lives in registers: `store` is indexed by component
-// window_geom: ragged_geom plus a box per frame (coclr_jpeg_decode_store_window; jpeg_core.h: JW_*).  block() maps a
+//           row's width and pitch: 0, 0 and g.W, except for table_geom<true>, whose rows and groups are those of a BOX
+//           of the frame.  The box is an object of its own so that it lives in registers: `store` is indexed by
+//           component
+// table_geom<true>: the same plus a box per frame (coclr_jpeg_decode_store_window; jpeg_core.h: JW_*).  block() maps a
 // lane to a block of the box's MCU rectangle and returns its FULL-frame index, group() to a row and group of the box:
 // the workspaces keep the full-frame layout, so the kernels address and compute as for a whole frame, on fewer lanes.
 struct one_geom {
@@ -66,55 +71,25 @@ struct one_geom {
   __device__ int width(const store&, const box&) const { return g.W; }
 };
 
-struct ragged_geom {
-  static constexpr bool ragged = true, windowed = false;
+template <bool WINDOWED>
+struct table_geom {
+  static constexpr bool ragged = true, windowed = WINDOWED;
   typedef jc_geom store;
-  struct box {};
-  const int64_t* tab;        // [F][JR_FIELDS]
-  const int64_t* blocks;     // [F + 1] prefix of blocks
-  const int64_t* rows;       // [F + 1] prefix of row groups
-  long F, coef_blocks, out_bytes;
-  __device__ const jc_geom& geom(const store& o) const { return o; }
-  __device__ bool frame(long f, store& o, long* cb, long* ob) const {
-    return jc_ragged_frame(tab, f, coef_blocks, out_bytes, JPEG_MAX_SIDE, o, cb, ob);
-  }
-  __device__ bool block(long id, store& o, long* cb, int* blk) const {
-    const long f = jc_find_frame(blocks, F, id);
-    long ob;
-    if (!frame(f, o, cb, &ob)) return false;
-    const long local = id - blocks[f];
-    if (local < 0 || local >= o.nblocks) return false;
-    *blk = (int)local;
-    return true;
-  }
-  __device__ bool group(long id, int, store& o, box&, long* cb, long* ob, int* y, int* xg) const {
-    const long f = jc_find_frame(rows, F, id);
-    if (!frame(f, o, cb, ob)) return false;
-    const long local = id - rows[f];
-    if (local < 0 || local >= jc_row_groups(o)) return false;
-    const int groups = (o.W + 15) / 16;
-    *xg = (int)(local % groups);
-    *y = (int)(local / groups);
-    return true;
-  }
-  __device__ bool vec_ok(int width, long ob) const { return width % 16 == 0 && (ob & 15) == 0; }
-  __device__ int x0(const box&) const { return 0; }
-  __device__ int y0(const box&) const { return 0; }
-  __device__ int width(const store& o, const box&) const { return o.W; }
-};
-
-struct window_geom {
-  static constexpr bool ragged = true, windowed = true;
-  typedef jc_geom store;
-  typedef jc_window box;
-  const int64_t* tab;        // [F][JR_FIELDS]; JR_OBYTE is the first byte of the frame's 3 * w * h output bytes
-  const int64_t* win;        // [F][JW_FIELDS]
-  const int64_t* blocks;     // [F + 1] prefix of the windows' blocks
-  const int64_t* rows;       // [F + 1] prefix of the boxes' row groups
+  struct whole { static constexpr int x0 = 0, y0 = 0; };
+  typedef std::conditional_t<WINDOWED, jc_window, whole> box;
+  const int64_t* tab;        // [F][JR_FIELDS]; windowed: JR_OBYTE is the first of the box's 3 * w * h output bytes
+  const int64_t* win;        // [F][JW_FIELDS]; unused unless windowed
+  const int64_t* blocks;     // [F + 1] prefix of the frames' blocks, or of the blocks of the boxes' MCU rectangles
+  const int64_t* rows;       // [F + 1] prefix of the frames' row groups, or the boxes'
   long F, coef_blocks, out_bytes;
   __device__ const jc_geom& geom(const store& o) const { return o; }
   __device__ bool frame(long f, store& o, box& w, long* cb, long* ob) const {
-    return jc_window_frame(tab, win, f, coef_blocks, out_bytes, JPEG_MAX_SIDE, o, w, cb, ob);
+    if constexpr (WINDOWED) return jc_window_frame(tab, win, f, coef_blocks, out_bytes, JPEG_MAX_SIDE, o, w, cb, ob);
+    else return jc_ragged_frame(tab, f, coef_blocks, out_bytes, JPEG_MAX_SIDE, o, cb, ob);
+  }
+  __device__ bool frame(long f, store& o, long* cb, long* ob) const {
+    box w;
+    return frame(f, o, w, cb, ob);
   }
   __device__ bool block(long id, store& o, long* cb, int* blk) const {
     const long f = jc_find_frame(blocks, F, id);
@@ -122,16 +97,24 @@ struct window_geom {
     long ob;
     if (!frame(f, o, w, cb, &ob)) return false;
     const long local = id - blocks[f];
-    if (local < 0 || local >= jc_window_blocks(o, w)) return false;
-    *blk = jc_window_block(o, w, local);
+    if constexpr (WINDOWED) {
+      if (local < 0 || local >= jc_window_blocks(o, w)) return false;
+      *blk = jc_window_block(o, w, local);
+    } else {
+      if (local < 0 || local >= o.nblocks) return false;
+      *blk = (int)local;
+    }
     return true;
   }
   __device__ bool group(long id, int, store& o, box& w, long* cb, long* ob, int* y, int* xg) const {
     const long f = jc_find_frame(rows, F, id);
     if (!frame(f, o, w, cb, ob)) return false;
     const long local = id - rows[f];
-    if (local < 0 || local >= jc_window_row_groups(w)) return false;
-    const int groups = (w.w + 15) / 16;
+    long n;
+    if constexpr (WINDOWED) n = jc_window_row_groups(w);
+    else n = jc_row_groups(o);
+    if (local < 0 || local >= n) return false;
+    const int groups = (width(o, w) + 15) / 16;
     *xg = (int)(local % groups);
     *y = (int)(local / groups);
     return true;
@@ -139,8 +122,13 @@ struct window_geom {
   __device__ bool vec_ok(int width, long ob) const { return width % 16 == 0 && (ob & 15) == 0; }
   __device__ int x0(const box& w) const { return w.x0; }
   __device__ int y0(const box& w) const { return w.y0; }
-  __device__ int width(const store&, const box& w) const { return w.w; }
+  __device__ int width(const store& o, const box& w) const {
+    if constexpr (WINDOWED) return w.w;
+    else return o.W;
+  }
 };
+typedef table_geom<false> ragged_geom;
+typedef table_geom<true> window_geom;
 
 // one wave per workgroup: with one lane per frame, 64 frames are all a CU gets, so the waves spread over the CUs
 template <class GS>
@@ -164,12 +152,12 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
   if (st) atomicOr(&status[f], st);
 }
 
-// One window of blockDim.x chunks, from chunk w0, of a segment [s0, s1) whose tables are in LDS (`tab`), on the lanes of
-// its workgroup; `first` is the true state at the window's start.  Relaxation, then the scan (see
-// jpeg_entropy_split_kernel, which decodes from the result, and jpeg_store_index_kernel, which stores it).  Afterwards
-// `in` is the lane's TRUE entry and `out` its exit, `v` the inclusive and `e` the exclusive prefix over the window's
-// lanes of {blocks completed (saturating at total), three DC sums}.  ex: [L][2], ps: [L][4] words of LDS.  Every
-// barrier is on a workgroup-uniform path: all lanes call this together.
+// One window of blockDim.x chunks, from chunk w0, of a segment [s0, s1) whose tables are in LDS (`tab`), on the lanes
+// of its workgroup; `first` is the true state at the window's start.  Relaxation, then the scan (see split_windows,
+// which calls this window after window).  Afterwards `in` is the lane's TRUE entry and `out` its exit, `v` the
+// inclusive and `e` the exclusive prefix over the window's lanes of {blocks completed (saturating at total), three DC
+// sums}.  ex: [L][2], ps: [L][4] words of LDS.  Every barrier is on a workgroup-uniform path: all lanes call this
+// together.
 struct split_lane {
   bool live;
   int cend;
@@ -233,16 +221,54 @@ __device__ __forceinline__ void split_window(const uint8_t* __restrict__ data, i
   }
 }
 
-// One workgroup per frame of ONE segment (the others return at once), one lane per chunk of chunk_bytes raw bytes; a
-// frame with more chunks than lanes is done in windows of blockDim.x chunks, in order, each starting from the
+// A segment [s0, s1) of `total` blocks on the lanes of one workgroup, one lane per chunk of chunk_bytes raw bytes; a
+// segment with more chunks than lanes is done in windows of blockDim.x chunks, in order, each starting from the
 // converged exit of the one before.  Per window:
 //   relaxation  every lane scans its chunk from a guessed state (lane 0 from the true one); then rounds: read the
 //               left neighbour's exit, and scan again if it is not the entry this lane used.  A round in which no
 //               lane changed has reached the serial decoder's states; blockDim.x rounds always suffice.
 //   scan        exclusive prefix of blocks completed and DC sums over the lanes (Hillis-Steele in LDS)
-//   write       every lane decodes its chunk once more from its true state, to jc_decode_segment's addresses
-// Dynamic LDS: the descriptor's tables (JM_SEG words), per lane an exit state (2 words) and a scan element (4),
-// and the window's carry (8): split_lds_bytes().  Every barrier is on a workgroup-uniform path.
+//   emit        every lane with a chunk: emit(chunk, its end, its TRUE entry, blocks of the segment done before it,
+//               the three DC sums there) -- jpeg_entropy_split_kernel decodes the chunk once more from that state,
+//               jpeg_store_index_kernel stores the state
+// Returns the first chunk no window reached: fewer than the segment has once only zero bits are left.
+// LDS: `tab`, the segment's tables (JM_SEG words; the caller loads what it uses), per lane an exit state (ex, 2 words)
+// and a scan element (ps, 4), and the carry from window to window (8: state (2), blocks, DC predictors (3)), which the
+// caller sets to {s0, 0, ...} in front of the barrier that precedes the call: split_lds_bytes().  All lanes of the
+// workgroup call this together, so every barrier is on a workgroup-uniform path.
+template <class Emit>
+__device__ __forceinline__ long split_windows(const uint8_t* __restrict__ data, int s0, int s1, int chunk_bytes,
+                                              const int32_t* tab, const jc_geom& g, uint32_t total, int32_t* ex,
+                                              uint32_t* ps, int32_t* carry, Emit emit) {
+  const int t = threadIdx.x, L = blockDim.x;
+  const long nchunks = jc_chunk_count(s0, s1, chunk_bytes);
+  long w0 = 0;
+  for (; w0 < nchunks; w0 += L) {
+    const jc_state first = jc_state_unpack(carry[0], carry[1], g);
+    if (first.pos == JC_PAST) break;                                       // uniform: nothing but zero bits is left
+    const uint32_t block0 = (uint32_t)carry[2];
+    const uint32_t dc0[3] = {(uint32_t)carry[3], (uint32_t)carry[4], (uint32_t)carry[5]};
+    split_lane w;
+    split_window(data, s0, s1, chunk_bytes, tab, g, w0, nchunks, first, total, ex, ps, w);
+    if (w.live) {
+      const uint32_t dc[3] = {dc0[0] + w.e[1], dc0[1] + w.e[2], dc0[2] + w.e[3]};
+      emit(w0 + t, w.cend, w.in, jc_blocks_add(block0, w.e[0], total), dc);
+    }
+    __syncthreads();                                                       // the carry and the scan have been read
+    if (t == L - 1) {
+      carry[0] = w.out.pos;
+      carry[1] = jc_state_word(w.out);
+      carry[2] = (int32_t)jc_blocks_add(block0, w.v[0], total);
+      for (int i = 0; i < 3; ++i) carry[3 + i] = (int32_t)(dc0[i] + w.v[1 + i]);
+    }
+    __syncthreads();
+  }
+  return w0;
+}
+
+// One workgroup per frame of ONE segment (the others return at once): split_windows, every chunk written from its
+// true state to jc_decode_segment's addresses.  Dynamic LDS: split_lds_bytes().  Every barrier is on a
+// workgroup-uniform path.
 template <class GS>
 __global__ __launch_bounds__(1024) void jpeg_entropy_split_kernel(const uint8_t* __restrict__ data, int data_len,
                                                                   const int32_t* __restrict__ meta, int width,
@@ -284,31 +310,14 @@ __global__ __launch_bounds__(1024) void jpeg_entropy_split_kernel(const uint8_t*
     carry[1] = carry[2] = carry[3] = carry[4] = carry[5] = 0;
   }
   __syncthreads();
-  const long nchunks = jc_chunk_count(s0, s1, chunk_bytes);
   const uint32_t total = (uint32_t)((long)(m1 - m0) * g.mcu_blocks);
   int16_t* dst = coef + cb * 64;
   int st = 0;
-  for (long w0 = 0; w0 < nchunks; w0 += L) {
-    const jc_state first = jc_state_unpack(carry[0], carry[1], g);
-    if (first.pos == JC_PAST) break;                                       // uniform: nothing but zero bits is left
-    const uint32_t block0 = (uint32_t)carry[2];
-    const uint32_t dc0[3] = {(uint32_t)carry[3], (uint32_t)carry[4], (uint32_t)carry[5]};
-    split_lane w;
-    split_window(data, s0, s1, chunk_bytes, tab, g, w0, nchunks, first, total, ex, ps, w);
-    if (w.live) {
-      const int dc[3] = {(int16_t)(dc0[0] + w.e[1]), (int16_t)(dc0[1] + w.e[2]), (int16_t)(dc0[2] + w.e[3])};
-      st |= jc_chunk_write(data, s1, w.cend, chunk_bytes, tab, g, w.in, (long)jc_blocks_add(block0, w.e[0], total), dc,
-                           m0, m1, dst);
-    }
-    __syncthreads();                                                       // the carry and the scan have been read
-    if (t == L - 1) {
-      carry[0] = w.out.pos;
-      carry[1] = jc_state_word(w.out);
-      carry[2] = (int32_t)jc_blocks_add(block0, w.v[0], total);
-      for (int i = 0; i < 3; ++i) carry[3 + i] = (int32_t)(dc0[i] + w.v[1 + i]);
-    }
-    __syncthreads();
-  }
+  split_windows(data, s0, s1, chunk_bytes, tab, g, total, ex, ps, carry,
+                [&](long, int cend, const jc_state& in, uint32_t block, const uint32_t* sums) {
+                  const int dc[3] = {(int16_t)sums[0], (int16_t)sums[1], (int16_t)sums[2]};
+                  st |= jc_chunk_write(data, s1, cend, chunk_bytes, tab, g, in, (long)block, dc, m0, m1, dst);
+                });
   if (st) atomicOr(&status[f], st);
 }
 
@@ -374,6 +383,32 @@ bool geometry_ok(int H, int W, int ncomp, int hs, int vs) {
   return jc_geometry_ok(H, W, ncomp, hs, vs, JPEG_MAX_SIDE);
 }
 
+// ---- the host side: what every entry point checks and launches alike ------------------------------------------------
+
+// The quantisers and Huffman tables of a descriptor (words JM_QUANT .. JM_SEG of m) are in the kernels' ranges.  Run per
+// frame of every call; a function of its own on a cache line's start, since where these loops fall in the library
+// otherwise moves a call's host time by a third (0.16 against 0.11 ms at 776 frames, the same object code).
+__attribute__((noinline, aligned(64))) bool tables_ok(const int32_t* m, int ncomp) {
+  for (int i = 0; i < 64 * ncomp; ++i)
+    if (m[JM_QUANT + i] < 0 || m[JM_QUANT + i] > 255) return false;
+  for (int t = 0; t < 6; ++t) {
+    const int32_t* h = m + JM_HUFF + t * JM_HUFF_WORDS;
+    for (int l = 0; l < 16; ++l)
+      if (h[l] < 0 || h[l] > 65536 || (l && h[l] < h[l - 1]) || h[16 + l] < -65536 || h[16 + l] > 255) return false;
+  }
+  return true;
+}
+
+// the first bytes of a frame's restart segments do not go back and stay inside its `len` bytes
+bool offsets_ok(const int32_t* seg, long nseg, long len) {
+  long last = 0;
+  for (long s = 0; s < nseg; ++s) {
+    if (seg[s] < last || seg[s] > len) return false;
+    last = seg[s];
+  }
+  return true;
+}
+
 // what the kernels rely on, checked on the host copy of the descriptors
 bool meta_ok(const int32_t* meta, int F, int width, int64_t data_len, const jc_geom& g, int* maxseg) {
   const long total = (long)g.mcux * g.mcuy;
@@ -384,23 +419,139 @@ bool meta_ok(const int32_t* meta, int F, int width, int64_t data_len, const jc_g
     if (off < 0 || len < 0 || off + len > data_len) return false;
     if (ri < 0 || nseg < 1 || nseg > width - JM_SEG) return false;
     if (nseg != (ri == 0 ? 1 : (total + ri - 1) / ri)) return false;
-    long last = 0;
-    for (int s = 0; s < nseg; ++s) {
-      const long at = m[JM_SEG + s];
-      if (at < last || at > len) return false;
-      last = at;
-    }
-    for (int i = 0; i < 64 * g.ncomp; ++i)
-      if (m[JM_QUANT + i] < 0 || m[JM_QUANT + i] > 255) return false;
-    for (int t = 0; t < 6; ++t) {
-      const int32_t* h = m + JM_HUFF + t * JM_HUFF_WORDS;
-      for (int l = 0; l < 16; ++l)
-        if (h[l] < 0 || h[l] > 65536 || (l && h[l] < h[l - 1]) || h[16 + l] < -65536 || h[16 + l] > 255) return false;
-    }
+    if (!offsets_ok(m + JM_SEG, nseg, len) || !tables_ok(m, g.ncomp)) return false;
     if (nseg > most) most = (int)nseg;
   }
   *maxseg = most;
   return true;
+}
+
+// Frame f of a table-driven call (t: its row of the geometry table, g: its geometry, obytes: its output): the storage
+// is in frame order, no overlap, inside the buffers, an output frame 16-byte aligned, cend / oend the end of the frames
+// so far; and the prefixes of blocks and of row groups (prefix_host, F + 1 words each) grow by `blocks` and `groups`.
+bool frame_storage_ok(const int64_t* t, const jc_geom& g, long obytes, long blocks, long groups,
+                      const int64_t* prefix_host, int F, int f, long coef_blocks, long out_bytes, long& cend,
+                      long& oend) {
+  const int64_t* pblocks = prefix_host + f;
+  const int64_t* prows = prefix_host + F + 1 + f;
+  const long cb = t[JR_CBLOCK], ob = t[JR_OBYTE];
+  if (cb < cend || cb > coef_blocks - g.nblocks) return false;
+  if (ob < oend || (ob & 15) || ob > out_bytes - obytes) return false;
+  cend = cb + g.nblocks;
+  oend = ob + obytes;
+  return pblocks[1] - pblocks[0] == blocks && prows[1] - prows[0] == groups;
+}
+
+// Who decodes what.  chunks(f): the chunks of frame f if it is ONE segment, which a workgroup of the relaxation
+// kernels takes, else 0.  -> how many such frames, and the chunks of the longest.
+struct split_plan { long single = 0, most_chunks = 1; };
+
+template <class Chunks>
+split_plan plan_split(long f0, long f1, Chunks chunks) {
+  split_plan p;
+  for (long f = f0; f < f1; ++f) {
+    const long n = chunks(f);
+    if (n < 1) continue;
+    ++p.single;
+    if (n > p.most_chunks) p.most_chunks = n;
+  }
+  return p;
+}
+
+// a relaxation workgroup has a lane per chunk of the call's longest frame, in whole waves, up to 1024
+int split_lanes(long most_chunks) { return most_chunks > 1024 ? 1024 : (int)((most_chunks + 63) / 64 * 64); }
+
+// no launch of a call may need more workgroups than a grid has
+bool grid_ok(long lanes1, int per1, long lanes2, long lanes3) {
+  const long limit = 0x7fffffffL;
+  return lanes1 / per1 < limit && lanes2 / 256 < limit && lanes3 / 256 < limit;
+}
+
+// What the stages of one call work on: the frames' coefficient blocks are [first, cend) of coefs, lanes2 / lanes3 the
+// lanes of the inverse DCT and of the colour stage, groups / aligned what jpeg_colour_kernel takes.
+struct stage_args {
+  int F, stages;
+  int16_t* coefs;
+  uint8_t* planes;
+  uint8_t* out;
+  int32_t* status;
+  long first, cend, lanes2, lanes3;
+  int groups, aligned;
+  hipStream_t s;
+};
+
+// The stages over the geometry source GS; entropy() launches the call's own entropy kernels onto zeroed coefficients
+// and status words and returns 0 or an error.
+template <class GS, class Entropy>
+int run_stages(const GS& gs, const stage_args& a, Entropy entropy) {
+  if (a.stages & 1) {
+    COCLR_RETURN_IF(hipMemsetAsync(a.coefs + a.first * 64, 0, (size_t)(a.cend - a.first) * 128, a.s));
+    COCLR_RETURN_IF(hipMemsetAsync(a.status, 0, (size_t)a.F * 4, a.s));
+    const int e = entropy();
+    if (e) return e;
+  }
+  if (a.stages & 2) {
+    hipLaunchKernelGGL(jpeg_idct_kernel<GS>, dim3(cdiv(a.lanes2, 256)), dim3(256), 0, a.s, a.coefs, a.lanes2, gs,
+                       a.planes);
+    COCLR_LAUNCH_CHECK();
+  }
+  if (a.stages & 4) {
+    hipLaunchKernelGGL(jpeg_colour_kernel<GS>, dim3(cdiv(a.lanes3, 256)), dim3(256), 0, a.s, a.planes, a.lanes3,
+                       a.groups, gs, a.aligned, a.out);
+    COCLR_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// The entropy stage of a call on descriptors: frames of one segment go to the split kernel when chunk_bytes asked for
+// it (plan), all others to a lane per restart segment.
+template <class GS>
+int launch_entropy(const GS& gs, const uint8_t* data, int64_t data_len, const int32_t* meta, int width, int F,
+                   int maxseg, const split_plan& plan, int chunk_bytes, int16_t* coefs, int32_t* status,
+                   hipStream_t s) {
+  if (plan.single < F) {
+    hipLaunchKernelGGL(jpeg_entropy_kernel<GS>, dim3(cdiv((long)F * maxseg, 64)), dim3(64), 0, s, data, (int)data_len,
+                       meta, width, F, maxseg, plan.single > 0 ? 1 : 0, gs, coefs, status);
+    COCLR_LAUNCH_CHECK();
+  }
+  if (plan.single > 0) {
+    const int lanes = split_lanes(plan.most_chunks);
+    hipLaunchKernelGGL(jpeg_entropy_split_kernel<GS>, dim3(F), dim3(lanes), split_lds_bytes(lanes), s, data,
+                       (int)data_len, meta, width, maxseg, chunk_bytes, gs, coefs, status);
+    COCLR_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// The tail of both calls on descriptors: who decodes what (geom_of(f): frame f's geometry, on the host; maxseg is the
+// call's, as the kernels clamp with it), then the stages.
+template <class GS, class GeomOf>
+int decode_descriptors(const GS& gs, const stage_args& a, const uint8_t* data, int64_t data_len, const int32_t* meta,
+                       const int32_t* meta_host, int width, int maxseg, int chunk_bytes, GeomOf geom_of) {
+  if (!grid_ok((long)a.F * maxseg, 64, a.lanes2, a.lanes3)) return COCLR_EINVAL;
+  split_plan plan;
+  if (chunk_bytes)
+    plan = plan_split(0, a.F, [&](long f) -> long {
+      const int32_t* m = meta_host + f * width;
+      int s0, s1, m0, m1;
+      if (jc_segment_count(m, width, maxseg) != 1 ||
+          !jc_segment_range(m, width, maxseg, (int)data_len, 0, geom_of(f), &s0, &s1, &m0, &m1))
+        return 0;
+      return jc_chunk_count(s0, s1, chunk_bytes);
+    });
+  return run_stages(gs, a, [&] {
+    return launch_entropy(gs, data, data_len, meta, width, a.F, maxseg, plan, chunk_bytes, a.coefs, a.status, a.s);
+  });
+}
+
+// what the two calls on descriptors ask of their common arguments
+bool descriptor_args_ok(const uint8_t* data, int64_t data_len, const int32_t* meta, const int32_t* meta_host, int F,
+                        int width, int stages, const int16_t* coefs, const uint8_t* planes, const uint8_t* out,
+                        const int32_t* status, int chunk_bytes) {
+  if (!data || !meta || !meta_host || !coefs || !planes || !out || !status) return false;
+  if (F < 1 || width <= JM_SEG || data_len < 0 || data_len > 0x7fffffff || stages < 1 || stages > 7) return false;
+  if (((uintptr_t)coefs & 15) || ((uintptr_t)meta & 3)) return false;
+  return chunk_bytes == 0 || (chunk_bytes >= 8 && chunk_bytes <= 65536);
 }
 
 }  // namespace
@@ -417,64 +568,23 @@ extern "C" int coclr_jpeg_workspace(int H, int W, int ncomp, int hs, int vs, int
 
 namespace {
 
+// coclr_jpeg_decode and coclr_jpeg_decode_split: one geometry, frame f at f times the per-frame sizes.  `planes` and
+// `out` may lie anywhere; whether the colour stage stores 16 bytes at a time is decided here, for the call.
 int jpeg_decode_impl(const uint8_t* data, int64_t data_len, const int32_t* meta, const int32_t* meta_host, int F,
                      int width, int H, int W, int ncomp, int hs, int vs, int stages, int16_t* coefs, uint8_t* planes,
                      uint8_t* out, int32_t* status, int chunk_bytes, void* stream) {
-  if (!data || !meta || !meta_host || !coefs || !planes || !out || !status) return COCLR_EINVAL;
-  if (F < 1 || width <= JM_SEG || data_len < 0 || data_len > 0x7fffffff || stages < 1 || stages > 7)
+  if (!descriptor_args_ok(data, data_len, meta, meta_host, F, width, stages, coefs, planes, out, status, chunk_bytes))
     return COCLR_EINVAL;
-  if (!geometry_ok(H, W, ncomp, hs, vs) || ((uintptr_t)coefs & 15) || ((uintptr_t)meta & 3)) return COCLR_EINVAL;
+  if (!geometry_ok(H, W, ncomp, hs, vs)) return COCLR_EINVAL;
   jc_geom g;
   jc_geom_init(g, H, W, ncomp, hs, vs);
   int maxseg = 1;
   if (!meta_ok(meta_host, F, width, data_len, g, &maxseg)) return COCLR_EINVAL;
-  if (chunk_bytes != 0 && (chunk_bytes < 8 || chunk_bytes > 65536)) return COCLR_EINVAL;
   const int groups = (W + 15) / 16;
-  const long lanes1 = (long)F * maxseg, lanes2 = (long)F * g.nblocks, lanes3 = (long)F * H * groups;
-  const long limit = 0x7fffffffL;        // workgroups of one launch
-  if (lanes1 / 64 >= limit || lanes2 / 256 >= limit || lanes3 / 256 >= limit) return COCLR_EINVAL;
-  // who decodes what: frames of one segment go to the split kernel when chunk_bytes asks for it; its workgroup has
-  // a lane per chunk of the call's longest such frame, up to 1024
-  long single = 0, most_chunks = 1;
-  if (chunk_bytes)
-    for (int f = 0; f < F; ++f) {
-      const int32_t* m = meta_host + (long)f * width;
-      int s0, s1, m0, m1;
-      if (jc_segment_count(m, width, maxseg) != 1 ||
-          !jc_segment_range(m, width, maxseg, (int)data_len, 0, g, &s0, &s1, &m0, &m1))
-        continue;
-      ++single;
-      const long n = jc_chunk_count(s0, s1, chunk_bytes);
-      if (n > most_chunks) most_chunks = n;
-    }
-  hipStream_t s = (hipStream_t)stream;
-  const one_geom gs = {g};
-  if (stages & 1) {
-    COCLR_RETURN_IF(hipMemsetAsync(coefs, 0, (size_t)F * g.nblocks * 128, s));
-    COCLR_RETURN_IF(hipMemsetAsync(status, 0, (size_t)F * 4, s));
-    if (single < F) {
-      hipLaunchKernelGGL(jpeg_entropy_kernel<one_geom>, dim3(cdiv(lanes1, 64)), dim3(64), 0, s, data, (int)data_len,
-                         meta, width, F, maxseg, single > 0 ? 1 : 0, gs, coefs, status);
-      COCLR_LAUNCH_CHECK();
-    }
-    if (single > 0) {
-      const int lanes = most_chunks > 1024 ? 1024 : (int)((most_chunks + 63) / 64 * 64);
-      hipLaunchKernelGGL(jpeg_entropy_split_kernel<one_geom>, dim3(F), dim3(lanes), split_lds_bytes(lanes), s, data,
-                         (int)data_len, meta, width, maxseg, chunk_bytes, gs, coefs, status);
-      COCLR_LAUNCH_CHECK();
-    }
-  }
-  if (stages & 2) {
-    hipLaunchKernelGGL(jpeg_idct_kernel<one_geom>, dim3(cdiv(lanes2, 256)), dim3(256), 0, s, coefs, lanes2, gs, planes);
-    COCLR_LAUNCH_CHECK();
-  }
-  if (stages & 4) {
-    const int vec = W % 16 == 0 && ((uintptr_t)out & 15) == 0;
-    hipLaunchKernelGGL(jpeg_colour_kernel<one_geom>, dim3(cdiv(lanes3, 256)), dim3(256), 0, s, planes, lanes3, groups,
-                       gs, vec, out);
-    COCLR_LAUNCH_CHECK();
-  }
-  return 0;
+  const stage_args a = {F, stages, coefs, planes, out, status, 0, (long)F * g.nblocks, (long)F * g.nblocks,
+                        (long)F * H * groups, groups, W % 16 == 0 && ((uintptr_t)out & 15) == 0, (hipStream_t)stream};
+  return decode_descriptors(one_geom{g}, a, data, data_len, meta, meta_host, width, maxseg, chunk_bytes,
+                            [&](long) -> const jc_geom& { return g; });
 }
 
 }  // namespace
@@ -494,95 +604,46 @@ extern "C" int coclr_jpeg_decode_split(const uint8_t* data, int64_t data_len, co
                           status, chunk_bytes, stream);
 }
 
-// Frames of differing geometry in one call: the stages of jpeg_decode_impl with the geometry, the first coefficient
-// block and the first output byte per frame (jpeg_core.h: JR_*).  Everything is checked on the host copies first.
+// Frames of differing geometry in one call: jpeg_decode_impl with the geometry, the first coefficient block and the
+// first output byte per frame (jpeg_core.h: JR_*), from tables that are checked on their host copies first; the
+// buffers must be 16-byte aligned.
 extern "C" int coclr_jpeg_decode_ragged(const uint8_t* data, int64_t data_len, const int32_t* meta,
                                         const int32_t* meta_host, int F, int width, const int64_t* geom,
                                         const int64_t* geom_host, const int64_t* prefix, const int64_t* prefix_host,
                                         int stages, int16_t* coefs, uint8_t* planes, int64_t coef_blocks, uint8_t* out,
                                         int64_t out_bytes, int32_t* status, int chunk_bytes, void* stream) {
-  if (!data || !meta || !meta_host || !geom || !geom_host || !prefix || !prefix_host || !coefs || !planes || !out ||
-      !status)
+  if (!descriptor_args_ok(data, data_len, meta, meta_host, F, width, stages, coefs, planes, out, status, chunk_bytes))
     return COCLR_EINVAL;
-  if (F < 1 || width <= JM_SEG || data_len < 0 || data_len > 0x7fffffff || stages < 1 || stages > 7)
+  if (!geom || !geom_host || !prefix || !prefix_host || coef_blocks < 1 || out_bytes < 1) return COCLR_EINVAL;
+  if (((uintptr_t)planes & 15) || ((uintptr_t)out & 15) || ((uintptr_t)geom & 7) || ((uintptr_t)prefix & 7))
     return COCLR_EINVAL;
-  if (((uintptr_t)coefs & 15) || ((uintptr_t)planes & 15) || ((uintptr_t)out & 15) || ((uintptr_t)meta & 3) ||
-      ((uintptr_t)geom & 7) || ((uintptr_t)prefix & 7))
-    return COCLR_EINVAL;
-  if (coef_blocks < 1 || out_bytes < 1) return COCLR_EINVAL;
-  if (chunk_bytes != 0 && (chunk_bytes < 8 || chunk_bytes > 65536)) return COCLR_EINVAL;
-  const int64_t* pblocks = prefix_host;
-  const int64_t* prows = prefix_host + F + 1;
-  if (pblocks[0] != 0 || prows[0] != 0) return COCLR_EINVAL;
+  if (prefix_host[0] != 0 || prefix_host[F + 1] != 0) return COCLR_EINVAL;
+  const auto geom_of = [&](long f) {
+    const int64_t* t = geom_host + f * JR_FIELDS;
+    jc_geom g;
+    jc_geom_init(g, (int)t[JR_H], (int)t[JR_W], (int)t[JR_NCOMP], (int)t[JR_HS], (int)t[JR_VS]);
+    return g;
+  };
   int maxseg = 1;
-  long single = 0, most_chunks = 1, cend = 0, oend = 0;
+  long cend = 0, oend = 0;
   for (int f = 0; f < F; ++f) {
     const int64_t* t = geom_host + (long)f * JR_FIELDS;
     if (!jc_geometry_ok(t[JR_H], t[JR_W], t[JR_NCOMP], t[JR_HS], t[JR_VS], JPEG_MAX_SIDE)) return COCLR_EINVAL;
-    jc_geom g;
-    jc_geom_init(g, (int)t[JR_H], (int)t[JR_W], (int)t[JR_NCOMP], (int)t[JR_HS], (int)t[JR_VS]);
-    // storage: in frame order, no overlap, inside the buffers; an output frame starts 16-byte aligned
-    const long cb = t[JR_CBLOCK], ob = t[JR_OBYTE];
-    if (cb < cend || cb > coef_blocks - g.nblocks) return COCLR_EINVAL;
-    if (ob < oend || (ob & 15) || ob > out_bytes - (long)g.H * g.W * 3) return COCLR_EINVAL;
-    cend = cb + g.nblocks;
-    oend = ob + (long)g.H * g.W * 3;
-    if (pblocks[f + 1] - pblocks[f] != g.nblocks || prows[f + 1] - prows[f] != jc_row_groups(g)) return COCLR_EINVAL;
-    const int32_t* m = meta_host + (long)f * width;
+    const jc_geom g = geom_of(f);
+    if (!frame_storage_ok(t, g, (long)g.H * g.W * 3, g.nblocks, jc_row_groups(g), prefix_host, F, f, coef_blocks,
+                          out_bytes, cend, oend))
+      return COCLR_EINVAL;
     int segs = 1;
-    if (!meta_ok(m, 1, width, data_len, g, &segs)) return COCLR_EINVAL;
+    if (!meta_ok(meta_host + (long)f * width, 1, width, data_len, g, &segs)) return COCLR_EINVAL;
     if (segs > maxseg) maxseg = segs;
   }
-  // who decodes what, as in jpeg_decode_impl; maxseg is the call's, as the kernels clamp with it
-  if (chunk_bytes)
-    for (int f = 0; f < F; ++f) {
-      const int64_t* t = geom_host + (long)f * JR_FIELDS;
-      jc_geom g;
-      jc_geom_init(g, (int)t[JR_H], (int)t[JR_W], (int)t[JR_NCOMP], (int)t[JR_HS], (int)t[JR_VS]);
-      const int32_t* m = meta_host + (long)f * width;
-      int s0, s1, m0, m1;
-      if (jc_segment_count(m, width, maxseg) != 1 ||
-          !jc_segment_range(m, width, maxseg, (int)data_len, 0, g, &s0, &s1, &m0, &m1))
-        continue;
-      ++single;
-      const long n = jc_chunk_count(s0, s1, chunk_bytes);
-      if (n > most_chunks) most_chunks = n;
-    }
-  const long lanes1 = (long)F * maxseg, lanes2 = pblocks[F], lanes3 = prows[F];
-  const long limit = 0x7fffffffL;        // workgroups of one launch
-  if (lanes1 / 64 >= limit || lanes2 / 256 >= limit || lanes3 / 256 >= limit) return COCLR_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const ragged_geom gs = {geom, prefix, prefix + F + 1, F, coef_blocks, out_bytes};
-  if (stages & 1) {
-    const long first = geom_host[JR_CBLOCK];
-    COCLR_RETURN_IF(hipMemsetAsync(coefs + first * 64, 0, (size_t)(cend - first) * 128, s));
-    COCLR_RETURN_IF(hipMemsetAsync(status, 0, (size_t)F * 4, s));
-    if (single < F) {
-      hipLaunchKernelGGL(jpeg_entropy_kernel<ragged_geom>, dim3(cdiv(lanes1, 64)), dim3(64), 0, s, data, (int)data_len,
-                         meta, width, F, maxseg, single > 0 ? 1 : 0, gs, coefs, status);
-      COCLR_LAUNCH_CHECK();
-    }
-    if (single > 0) {
-      const int lanes = most_chunks > 1024 ? 1024 : (int)((most_chunks + 63) / 64 * 64);
-      hipLaunchKernelGGL(jpeg_entropy_split_kernel<ragged_geom>, dim3(F), dim3(lanes), split_lds_bytes(lanes), s, data,
-                         (int)data_len, meta, width, maxseg, chunk_bytes, gs, coefs, status);
-      COCLR_LAUNCH_CHECK();
-    }
-  }
-  if (stages & 2) {
-    hipLaunchKernelGGL(jpeg_idct_kernel<ragged_geom>, dim3(cdiv(lanes2, 256)), dim3(256), 0, s, coefs, lanes2, gs,
-                       planes);
-    COCLR_LAUNCH_CHECK();
-  }
-  if (stages & 4) {
-    hipLaunchKernelGGL(jpeg_colour_kernel<ragged_geom>, dim3(cdiv(lanes3, 256)), dim3(256), 0, s, planes, lanes3, 0, gs,
-                       1, out);
-    COCLR_LAUNCH_CHECK();
-  }
-  return 0;
+  const stage_args a = {F, stages, coefs, planes, out, status, (long)geom_host[JR_CBLOCK], cend, (long)prefix_host[F],
+                        (long)prefix_host[2 * F + 1], 0, 1, (hipStream_t)stream};
+  return decode_descriptors(ragged_geom{geom, nullptr, prefix, prefix + F + 1, F, coef_blocks, out_bytes}, a, data,
+                            data_len, meta, meta_host, width, maxseg, chunk_bytes, geom_of);
 }
 
-// ---- frames of a device-resident store, decoded by index ---------------------------------------------------------------
+// ---- frames of a device-resident store, decoded by index ------------------------------------------------------------
 namespace {
 
 struct store_view {          // the device side of a coclr_jpeg_store
@@ -599,10 +660,10 @@ struct store_view {          // the device side of a coclr_jpeg_store
   int chunk_bytes;
 };
 
-// One workgroup per frame f0 + blockIdx.x of ONE segment (the others return at once): the relaxation and the scan of
-// jpeg_entropy_split_kernel, window by window, and where that kernel decodes every chunk once more from its true
-// state, this one stores the state (jc_row_pack).  Once only zero bits are left every later chunk's row says so.
-// Dynamic LDS as there (split_lds_bytes); every barrier is on a workgroup-uniform path.
+// One workgroup per frame f0 + blockIdx.x of ONE segment (the others return at once): split_windows, every chunk's
+// true state stored (jc_row_pack) where jpeg_entropy_split_kernel decodes from it.  Once only zero bits are left
+// every later chunk's row says so.  Dynamic LDS as there (split_lds_bytes); every barrier is on a workgroup-uniform
+// path.
 __global__ __launch_bounds__(1024) void jpeg_store_index_kernel(store_view sv, long f0) {
   extern __shared__ int32_t index_lds[];
   __shared__ jc_geom g;
@@ -626,38 +687,19 @@ __global__ __launch_bounds__(1024) void jpeg_store_index_kernel(store_view sv, l
     carry[0] = carry[1] = carry[2] = carry[3] = carry[4] = carry[5] = 0;
   }
   __syncthreads();
-  const uint8_t* data = fr.bytes;
   const uint32_t total = (uint32_t)((long)g.mcux * g.mcuy * g.mcu_blocks);
   uint32_t* rows = sv.rows + fr.row * JS_ROW_WORDS;
-  long w0 = 0;
-  for (; w0 < nchunks; w0 += L) {
-    const jc_state first = jc_state_unpack(carry[0], carry[1], g);
-    if (first.pos == JC_PAST) break;                                       // uniform: nothing but zero bits is left
-    const uint32_t block0 = (uint32_t)carry[2];
-    const uint32_t dc0[3] = {(uint32_t)carry[3], (uint32_t)carry[4], (uint32_t)carry[5]};
-    split_lane w;
-    split_window(data, 0, s1, chunk_bytes, tab, g, w0, nchunks, first, total, ex, ps, w);
-    if (w.live) {
-      const uint32_t dc[3] = {dc0[0] + w.e[1], dc0[1] + w.e[2], dc0[2] + w.e[3]};
-      uint32_t row[JS_ROW_WORDS];
-      jc_row_pack(row, w.in, jc_chunk_start(s1, chunk_bytes, w0 + t), jc_blocks_add(block0, w.e[0], total), dc);
-      *reinterpret_cast<uint4*>(rows + (w0 + t) * JS_ROW_WORDS) = make_uint4(row[0], row[1], row[2], row[3]);
-    }
-    __syncthreads();                                                       // the carry and the scan have been read
-    if (t == L - 1) {
-      carry[0] = w.out.pos;
-      carry[1] = jc_state_word(w.out);
-      carry[2] = (int32_t)jc_blocks_add(block0, w.v[0], total);
-      for (int i = 0; i < 3; ++i) carry[3 + i] = (int32_t)(dc0[i] + w.v[1 + i]);
-    }
-    __syncthreads();
-  }
-  const uint32_t none[3] = {0, 0, 0};
-  for (long i = w0 + t; i < nchunks; i += L) {                             // behind the end of the real bits
+  const auto store_row = [&](long chunk, const jc_state& in, long start, uint32_t block, const uint32_t* dc) {
     uint32_t row[JS_ROW_WORDS];
-    jc_row_pack(row, jc_state_past(), 0, total, none);
-    *reinterpret_cast<uint4*>(rows + i * JS_ROW_WORDS) = make_uint4(row[0], row[1], row[2], row[3]);
-  }
+    jc_row_pack(row, in, start, block, dc);
+    *reinterpret_cast<uint4*>(rows + chunk * JS_ROW_WORDS) = make_uint4(row[0], row[1], row[2], row[3]);
+  };
+  const long reached = split_windows(fr.bytes, 0, s1, chunk_bytes, tab, g, total, ex, ps, carry,
+                                     [&](long chunk, int, const jc_state& in, uint32_t block, const uint32_t* dc) {
+                                       store_row(chunk, in, jc_chunk_start(s1, chunk_bytes, chunk), block, dc);
+                                     });
+  const uint32_t none[3] = {0, 0, 0};
+  for (long i = reached + t; i < nchunks; i += L) store_row(i, jc_state_past(), 0, total, none);   // past the real bits
 }
 
 // The entropy stage of coclr_jpeg_decode_store, one pass: lane id is chunk or restart segment `local` of call frame f
@@ -681,11 +723,7 @@ __global__ __launch_bounds__(256) void jpeg_entropy_store_kernel(store_view sv, 
   typename GS::box box;
   long cb, ob;
   if (local < 0) return;
-  if constexpr (GS::windowed) {
-    if (!gs.frame(f, g, box, &cb, &ob)) return;
-  } else {
-    if (!gs.frame(f, g, &cb, &ob)) return;
-  }
+  if (!gs.frame(f, g, box, &cb, &ob)) return;
   long sf = sel[f];
   sf = sf < 0 || sf >= sv.nframes ? 0 : sf;
   jc_store_frame fr;
@@ -754,38 +792,23 @@ bool store_frame_ok(const coclr_jpeg_store* st, long f, bool deep, jc_store_fram
     return false;
   }
   if (!deep) return true;
-  long last = 0;
-  for (long s = 0; nseg > 1 && s < nseg; ++s) {
-    const long at = st->segs_host[fr.seg + s];
-    if (at < last || at > len) return false;
-    last = at;
-  }
-  for (int i = 0; i < 64 * g.ncomp; ++i)
-    if (fr.meta[JM_QUANT + i] < 0 || fr.meta[JM_QUANT + i] > 255) return false;
-  for (int t = 0; t < 6; ++t) {
-    const int32_t* h = fr.meta + JM_HUFF + t * JM_HUFF_WORDS;
-    for (int l = 0; l < 16; ++l)
-      if (h[l] < 0 || h[l] > 65536 || (l && h[l] < h[l - 1]) || h[16 + l] < -65536 || h[16 + l] > 255) return false;
-  }
-  return true;
+  return (nseg == 1 || offsets_ok(st->segs_host + fr.seg, nseg, len)) && tables_ok(fr.meta, g.ncomp);
 }
 
 }  // namespace
 
 extern "C" int coclr_jpeg_store_index(const coclr_jpeg_store* st, int64_t f0, int64_t f1, void* stream) {
   if (!store_ok(st) || f0 < 0 || f1 <= f0 || f1 > st->nframes || f1 - f0 >= 0x7fffffffL) return COCLR_EINVAL;
-  long single = 0, most_chunks = 1;
-  for (long f = f0; f < f1; ++f) {
+  bool ok = true;
+  const split_plan plan = plan_split(f0, f1, [&](long f) -> long {
     jc_store_frame fr;
     jc_geom g;
-    if (!store_frame_ok(st, f, true, fr, g)) return COCLR_EINVAL;
-    if (fr.nseg != 1) continue;
-    ++single;
-    const long n = jc_chunk_count(0, fr.len, st->chunk_bytes);
-    if (n > most_chunks) most_chunks = n;
-  }
-  if (!single) return 0;
-  const int lanes = most_chunks > 1024 ? 1024 : (int)((most_chunks + 63) / 64 * 64);
+    ok = ok && store_frame_ok(st, f, true, fr, g);
+    return ok && fr.nseg == 1 ? jc_chunk_count(0, fr.len, st->chunk_bytes) : 0;
+  });
+  if (!ok) return COCLR_EINVAL;
+  if (!plan.single) return 0;
+  const int lanes = split_lanes(plan.most_chunks);
   hipLaunchKernelGGL(jpeg_store_index_kernel, dim3((unsigned)(f1 - f0)), dim3(lanes), split_lds_bytes(lanes),
                      (hipStream_t)stream, store_device(st), (long)f0);
   COCLR_LAUNCH_CHECK();
@@ -793,29 +816,6 @@ extern "C" int coclr_jpeg_store_index(const coclr_jpeg_store* st, int64_t f0, in
 }
 
 namespace {
-
-// The stages of a store decode over the geometry source GS: ragged_geom (whole frames) or window_geom (a box of each).
-template <class GS>
-int store_stages(const coclr_jpeg_store* st, const int64_t* sel, const int64_t* lanes, const GS& gs, long lanes1,
-                 long lanes2, long lanes3, long first, long cend, int F, int stages, int16_t* coefs, uint8_t* planes,
-                 uint8_t* out, int32_t* status, hipStream_t s) {
-  if (stages & 1) {
-    COCLR_RETURN_IF(hipMemsetAsync(coefs + first * 64, 0, (size_t)(cend - first) * 128, s));
-    COCLR_RETURN_IF(hipMemsetAsync(status, 0, (size_t)F * 4, s));
-    hipLaunchKernelGGL(jpeg_entropy_store_kernel<GS>, dim3(cdiv(lanes1, 256)), dim3(256), 0, s, store_device(st), sel,
-                       lanes, lanes1, gs, coefs, status);
-    COCLR_LAUNCH_CHECK();
-  }
-  if (stages & 2) {
-    hipLaunchKernelGGL(jpeg_idct_kernel<GS>, dim3(cdiv(lanes2, 256)), dim3(256), 0, s, coefs, lanes2, gs, planes);
-    COCLR_LAUNCH_CHECK();
-  }
-  if (stages & 4) {
-    hipLaunchKernelGGL(jpeg_colour_kernel<GS>, dim3(cdiv(lanes3, 256)), dim3(256), 0, s, planes, lanes3, 0, gs, 1, out);
-    COCLR_LAUNCH_CHECK();
-  }
-  return 0;
-}
 
 // coclr_jpeg_decode_store (window == nullptr) and coclr_jpeg_decode_store_window: everything is checked on the host
 // copies first.  With a window table the output frame is the box (3 * w * h bytes) and the block and row-group
@@ -833,10 +833,8 @@ int jpeg_decode_store_impl(const coclr_jpeg_store* st, const int64_t* sel, const
   if (((uintptr_t)coefs & 15) || ((uintptr_t)planes & 15) || ((uintptr_t)out & 15) || ((uintptr_t)sel & 7) ||
       ((uintptr_t)geom & 7) || ((uintptr_t)prefix & 7) || ((uintptr_t)window & 7))
     return COCLR_EINVAL;
-  const int64_t* pblocks = prefix_host;
-  const int64_t* prows = prefix_host + F + 1;
   const int64_t* pchunks = prefix_host + 2 * (F + 1);
-  if (pblocks[0] != 0 || prows[0] != 0 || pchunks[0] != 0) return COCLR_EINVAL;
+  if (prefix_host[0] != 0 || prefix_host[F + 1] != 0 || pchunks[0] != 0) return COCLR_EINVAL;
   long cend = 0, oend = 0;
   for (int f = 0; f < F; ++f) {
     const int64_t* t = geom_host + (long)f * JR_FIELDS;
@@ -855,28 +853,26 @@ int jpeg_decode_store_impl(const coclr_jpeg_store* st, const int64_t* sel, const
       nblocks = jc_window_blocks(g, w);
       ngroups = jc_window_row_groups(w);
     }
-    // storage: in frame order, no overlap, inside the buffers; an output frame starts 16-byte aligned
-    const long cb = t[JR_CBLOCK], ob = t[JR_OBYTE];
-    if (cb < cend || cb > coef_blocks - g.nblocks) return COCLR_EINVAL;
-    if (ob < oend || (ob & 15) || ob > out_bytes - obytes) return COCLR_EINVAL;
-    cend = cb + g.nblocks;
-    oend = ob + obytes;
-    if (pblocks[f + 1] - pblocks[f] != nblocks || prows[f + 1] - prows[f] != ngroups) return COCLR_EINVAL;
+    if (!frame_storage_ok(t, g, obytes, nblocks, ngroups, prefix_host, F, f, coef_blocks, out_bytes, cend, oend))
+      return COCLR_EINVAL;
     if (pchunks[f + 1] - pchunks[f] != jc_store_lanes(fr.len, fr.nseg, st->chunk_bytes)) return COCLR_EINVAL;
   }
-  const long lanes1 = pchunks[F], lanes2 = pblocks[F], lanes3 = prows[F];
-  const long limit = 0x7fffffffL;        // workgroups of one launch
-  if (lanes1 / 256 >= limit || lanes2 / 256 >= limit || lanes3 / 256 >= limit) return COCLR_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const long first = geom_host[JR_CBLOCK];
-  if (window_host) {
-    const window_geom gs = {geom, window, prefix, prefix + F + 1, F, coef_blocks, out_bytes};
-    return store_stages(st, sel, prefix + 2 * (F + 1), gs, lanes1, lanes2, lanes3, first, cend, F, stages, coefs,
-                        planes, out, status, s);
-  }
-  const ragged_geom gs = {geom, prefix, prefix + F + 1, F, coef_blocks, out_bytes};
-  return store_stages(st, sel, prefix + 2 * (F + 1), gs, lanes1, lanes2, lanes3, first, cend, F, stages, coefs, planes,
-                      out, status, s);
+  const stage_args a = {F, stages, coefs, planes, out, status, (long)geom_host[JR_CBLOCK], cend, (long)prefix_host[F],
+                        (long)prefix_host[2 * F + 1], 0, 1, (hipStream_t)stream};
+  const long lanes1 = pchunks[F];
+  if (!grid_ok(lanes1, 256, a.lanes2, a.lanes3)) return COCLR_EINVAL;
+  // one pass: a lane per chunk or restart segment of any frame of the call, from the store's rows
+  const auto stages_over = [&](const auto& gs) {
+    typedef std::decay_t<decltype(gs)> GS;
+    return run_stages(gs, a, [&] {
+      hipLaunchKernelGGL(jpeg_entropy_store_kernel<GS>, dim3(cdiv(lanes1, 256)), dim3(256), 0, a.s, store_device(st),
+                         sel, prefix + 2 * (F + 1), lanes1, gs, coefs, status);
+      COCLR_LAUNCH_CHECK();
+      return 0;
+    });
+  };
+  if (window_host) return stages_over(window_geom{geom, window, prefix, prefix + F + 1, F, coef_blocks, out_bytes});
+  return stages_over(ragged_geom{geom, nullptr, prefix, prefix + F + 1, F, coef_blocks, out_bytes});
 }
 
 }  // namespace

@@ -127,6 +127,22 @@ def test_stage_budget(stores, ragged, chunk_bytes):
         _check(frames, status, ragged, picks)
 
 
+def test_rows_are_the_recorded_rows():
+    """tests/golden/jpeg_store_rows.json (tools/make_jpeg_store_rows_golden.py): what coclr_jpeg_store_index stored for
+    the 54 fixtures added in index order, at chunk sizes 8 and 64, as a count and a digest of the rows' bytes."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location(
+        "make_jpeg_store_rows_golden", os.path.join(J.ROOT, "tools", "make_jpeg_store_rows_golden.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    with open(tool.OUT) as f:
+        want = json.load(f)
+    assert sorted(want) == ["64", "8"]
+    assert want["8"]["chunk_rows"] > 1024 * 2                                          # several windows of the indexer
+    assert tool.digests() == want
+
+
 def test_bytes_behind_two_gib():
     """64-bit addressing: the write cursor is moved past 2^31 before the first add (Store._advance_cursor, for this
     test only); the allocation is untouched memory."""

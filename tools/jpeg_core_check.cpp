@@ -3,30 +3,15 @@
 //
 //   jpeg_core_check <cases file>
 //
-// The cases file is little-endian int32 words and bytes, written by the test from coclr_amd.jpeg.pack:
-//   magic 0x4A504731, case count, then per case
-//   H, W, components, hs, vs, descriptor width, byte count, corrupt (0 / 1),
-//   descriptor[width] int32, the entropy-coded bytes, the expected H * W * 3 RGB bytes.
+// The cases file is written by the test from coclr_amd.jpeg.pack; tools/jpeg_check.h has its format and its reader.
 // Every case must decode to exactly its expected bytes with status 0.  Cases marked `corrupt` are then decoded again
 // damaged -- cut at five points, 32 seeded single-byte overwrites, and once with sixteen one bits at the start of
 // the stream, which is no code of any JPEG Huffman table -- in buffers of exactly the sizes the kernels get, so that
 // a read or store out of bounds, a signed overflow or a shift out of range ends the program.  The sixteen one bits
 // must raise the status flag.  Exit 0 = all held.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include "../coclr_amd/csrc/jpeg_core.h"
+#include "jpeg_check.h"
 
 namespace {
-
-struct Case {
-  int H, W, ncomp, hs, vs, width, len, corrupt;
-  std::vector<int32_t> meta;
-  std::vector<uint8_t> data, want;
-};
 
 // the three stages as the kernels run them, every buffer exactly as large as the entry point asks for
 int decode(const Case& c, const std::vector<int32_t>& meta, const uint8_t* data, int len, std::vector<uint8_t>& out) {
@@ -55,13 +40,6 @@ int decode(const Case& c, const std::vector<int32_t>& meta, const uint8_t* data,
   return status;
 }
 
-uint32_t lcg(uint32_t& s) {
-  s = s * 1664525u + 1013904223u;
-  return s >> 8;
-}
-
-bool read_exact(FILE* f, void* p, size_t n) { return n == 0 || fread(p, 1, n, f) == n; }
-
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -69,30 +47,18 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: %s <cases file>\n", argv[0]);
     return 2;
   }
-  FILE* f = fopen(argv[1], "rb");
-  int32_t head[2];
-  if (!f || !read_exact(f, head, sizeof head) || head[0] != 0x4A504731 || head[1] < 1) {
+  std::vector<Case> cases;
+  if (!read_cases(argv[1], true, cases)) {
     fprintf(stderr, "cannot read %s\n", argv[1]);
     return 2;
   }
   int failed = 0, damaged = 0, flagged = 0;
-  for (int i = 0; i < head[1]; ++i) {
-    Case c;
-    int32_t h[8];
-    if (!read_exact(f, h, sizeof h)) return 2;
-    c.H = h[0]; c.W = h[1]; c.ncomp = h[2]; c.hs = h[3]; c.vs = h[4]; c.width = h[5]; c.len = h[6]; c.corrupt = h[7];
-    if (c.H < 1 || c.W < 1 || c.H > 8192 || c.W > 8192 || c.width <= JM_SEG || c.width > (1 << 20) || c.len < 0) return 2;
-    c.meta.resize(c.width);
-    c.data.resize(c.len);
-    c.want.resize((size_t)c.H * c.W * 3);
-    if (!read_exact(f, c.meta.data(), (size_t)c.width * 4) || !read_exact(f, c.data.data(), c.len) ||
-        !read_exact(f, c.want.data(), c.want.size()))
-      return 2;
+  for (int i = 0; i < (int)cases.size(); ++i) {
+    const Case& c = cases[i];
     std::vector<uint8_t> out;
-    c.meta[JM_OFF] = 0;                    // the case's bytes stand alone
     const int status = decode(c, c.meta, c.data.data(), c.len, out);
     size_t wrong = 0;
-    for (size_t k = 0; k < out.size(); ++k) wrong += out[k] != c.want[k];
+    for (size_t k = 0; k < out.size(); ++k) wrong += out[k] != c.rgb[k];
     if (status != 0 || wrong) {
       printf("case %d (%d x %d, %d components, %dx%d): status %d, %zu bytes differ\n", i, c.W, c.H, c.ncomp, c.hs,
              c.vs, status, wrong);
@@ -124,8 +90,7 @@ int main(int argc, char** argv) {
       }
     }
   }
-  fclose(f);
-  printf("%d cases, %d failed; %d damaged streams decoded in bounds, %d of them flagged\n", head[1], failed, damaged,
-         flagged);
+  printf("%d cases, %d failed; %d damaged streams decoded in bounds, %d of them flagged\n", (int)cases.size(), failed,
+         damaged, flagged);
   return failed ? 1 : 0;
 }

@@ -14,25 +14,11 @@
 //           finding its frame by the search.  Every frame must equal its expected bytes and every byte between and
 //           behind the frames must still be 0x5a.  All buffers are exact heap blocks, so a store outside is reported.
 // Exit 0 = all held.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include "../coclr_amd/csrc/jpeg_core.h"
+#include "jpeg_check.h"
 
 namespace {
 
 constexpr long kMaxSide = 8192;
-
-struct Case {
-  int H, W, ncomp, hs, vs, width, len;
-  std::vector<int32_t> meta;
-  std::vector<uint8_t> data, want;
-};
-
-bool read_exact(FILE* f, void* p, size_t n) { return n == 0 || fread(p, 1, n, f) == n; }
 
 int check_prefix(const std::vector<int64_t>& count, const char* what) {
   const long F = (long)count.size();
@@ -65,28 +51,11 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: %s <cases file>\n", argv[0]);
     return 2;
   }
-  FILE* f = fopen(argv[1], "rb");
-  int32_t head[2];
-  if (!f || !read_exact(f, head, sizeof head) || head[0] != 0x4A504731 || head[1] < 1) {
+  std::vector<Case> cases;
+  if (!read_cases(argv[1], true, cases)) {
     fprintf(stderr, "cannot read %s\n", argv[1]);
     return 2;
   }
-  std::vector<Case> cases(head[1]);
-  for (Case& c : cases) {
-    int32_t h[8];
-    if (!read_exact(f, h, sizeof h)) return 2;
-    c.H = h[0]; c.W = h[1]; c.ncomp = h[2]; c.hs = h[3]; c.vs = h[4]; c.width = h[5]; c.len = h[6];
-    if (c.H < 1 || c.W < 1 || c.H > kMaxSide || c.W > kMaxSide || c.width <= JM_SEG || c.width > (1 << 20) || c.len < 0)
-      return 2;
-    c.meta.resize(c.width);
-    c.data.resize(c.len);
-    c.want.resize((size_t)c.H * c.W * 3);
-    if (!read_exact(f, c.meta.data(), (size_t)c.width * 4) || !read_exact(f, c.data.data(), c.len) ||
-        !read_exact(f, c.want.data(), c.want.size()))
-      return 2;
-    c.meta[JM_OFF] = 0;                    // every case's bytes stand alone here
-  }
-  fclose(f);
 
   // ---- search -------------------------------------------------------------------------------------------------------
   int searched = 0, wrong = 0;
@@ -94,8 +63,8 @@ int main(int argc, char** argv) {
     std::vector<int64_t> ones(300, 1), equal(1000, 1800), single(1, 7), mixed;
     uint32_t s = 99u;
     for (int i = 0; i < 257; ++i) {
-      s = s * 1664525u + 1013904223u;
-      mixed.push_back(i % 5 == 0 ? 1 : 1 + (s >> 8) % 5000);
+      const uint32_t v = lcg(s);
+      mixed.push_back(i % 5 == 0 ? 1 : 1 + v % 5000);
     }
     wrong += check_prefix(ones, "frames of one lane");
     wrong += check_prefix(equal, "many equal frames");
@@ -170,12 +139,12 @@ int main(int argc, char** argv) {
     const long ob = tab[i * JR_FIELDS + JR_OBYTE];
     for (; at < ob; ++at) { ++gap_bytes; gap_wrong += out[at] != 0x5a; }
     size_t differ = 0;
-    for (size_t k = 0; k < c.want.size(); ++k) differ += out[ob + k] != c.want[k];
+    for (size_t k = 0; k < c.rgb.size(); ++k) differ += out[ob + k] != c.rgb[k];
     if (differ) {
       printf("frame %ld (%d x %d, %d components, %dx%d): %zu bytes differ\n", i, c.W, c.H, c.ncomp, c.hs, c.vs, differ);
       ++failed;
     }
-    at = ob + (long)c.want.size();
+    at = ob + (long)c.rgb.size();
   }
   for (; at < out_bytes; ++at) { ++gap_bytes; gap_wrong += out[at] != 0x5a; }
   // a table the kernels must turn away: a frame whose storage leaves the buffers, and a geometry they do not take

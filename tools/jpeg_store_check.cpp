@@ -7,9 +7,9 @@
 // The cases file is the one tools/jpeg_core_check.cpp reads (tests/_jpeg_cases.py: write_core_check_cases).  Every case
 // becomes a store of one frame whose bytes lie behind 4 GiB of nothing (the base is a 64-bit number; only the frame's
 // own bytes are allocated, exactly), at chunk sizes 8, 16, 64, 128 and 65536.  For a frame of one restart segment:
-//   rows     the kernel's order -- windows of 1024 chunks, cold scans, rounds to the fixed point, prefix sums -- packed
-//            by jc_row_pack, must equal, word for word, the rows of ONE serial walk over the bytes that notes its state
-//            at the first symbol of every chunk;
+//   rows     the kernel's order (tools/jpeg_check.h: relax_windows -- windows of 1024 chunks, cold scans, rounds to the
+//            fixed point, prefix sums) packed by jc_row_pack, must equal, word for word, the rows of ONE serial walk
+//            over the bytes that notes its state at the first symbol of every chunk (serial_rows, there);
 //   decode   every chunk decoded once from its unpacked row, last chunk first, must give jc_decode_segment's
 //            coefficients and status;
 //   garbage  the rows overwritten with seeded random words, decoded into an exact heap block: every store in bounds.
@@ -17,115 +17,30 @@
 // decode alike.  The cases marked `corrupt` are damaged with a seed -- 24 flipped bytes, 5 cuts (the record still
 // names the full length: the clamp of jc_store_frame_get), 16 inserted bytes -- and held to the same checks.
 // Exit 0 = all held.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include "../coclr_amd/csrc/jpeg_core.h"
+#include "jpeg_check.h"
 
 namespace {
 
-constexpr int LANES = 1024;            // the kernel's largest workgroup: chunks per window
 constexpr int64_t FAR = 1LL << 32;     // where the frame's bytes lie in the imagined store
-
-struct Case {
-  int H, W, ncomp, hs, vs, width, len, corrupt;
-  std::vector<int32_t> meta;
-  std::vector<uint8_t> data;
-};
 
 struct Tally {
   long frames = 0, rows = 0, segments = 0, garbage = 0, failed = 0;
 };
 
-bool same(const jc_state& a, const jc_state& b) { return a.pos == b.pos && jc_state_word(a) == jc_state_word(b); }
-
-uint32_t lcg(uint32_t& s) {
-  s = s * 1664525u + 1013904223u;
-  return s >> 8;
-}
-
-// the rows of one frame as jpeg_store_index_kernel finds them
+// the rows of one frame as jpeg_store_index_kernel finds them: every chunk's true state packed, and behind the end of
+// the real bits, where no window goes, rows that say so
 void index_rows(const uint8_t* data, int len, const int32_t* meta, const jc_geom& g, int cb, std::vector<uint32_t>& rows) {
   const long nchunks = jc_chunk_count(0, len, cb);
   const uint32_t total = (uint32_t)((long)g.mcux * g.mcuy * g.mcu_blocks);
   rows.assign((size_t)nchunks * JS_ROW_WORDS, 0xDEADBEEFu);
-  jc_state first = jc_state_make(0, 0, 0, 0);
-  uint32_t block0 = 0, dc0[3] = {0, 0, 0};
-  std::vector<jc_state> in(LANES), out(LANES), prev(LANES);
-  std::vector<int> blocks(LANES);
-  std::vector<uint32_t> dcs((size_t)LANES * 3);
-  long w0 = 0;
-  for (; w0 < nchunks; w0 += LANES) {
-    if (first.pos == JC_PAST) break;
-    const int n = (int)(nchunks - w0 < LANES ? nchunks - w0 : LANES);
-    auto scan = [&](int t) {
-      jc_chunk_scan(data, len, jc_chunk_end(0, len, cb, w0 + t), cb, meta, g, in[t], &out[t], &blocks[t],
-                    &dcs[(size_t)t * 3]);
-    };
-    for (int t = 0; t < n; ++t) {
-      in[t] = t == 0 ? first : jc_chunk_cold(data, 0, len, cb, w0 + t);
-      scan(t);
-    }
-    for (int r = 0; r < LANES; ++r) {
-      prev = out;                                  // every chunk reads the previous round's exits
-      bool any = false;
-      for (int t = 1; t < n; ++t)
-        if (!same(prev[t - 1], in[t])) {
-          in[t] = prev[t - 1];
-          scan(t);
-          any = true;
-        }
-      if (!any) break;
-    }
-    uint32_t block = block0, dc[3] = {dc0[0], dc0[1], dc0[2]};
-    for (int t = 0; t < n; ++t) {
-      jc_row_pack(&rows[(size_t)(w0 + t) * JS_ROW_WORDS], in[t], jc_chunk_start(len, cb, w0 + t), block, dc);
-      block = jc_blocks_add(block, (uint32_t)blocks[t] > total ? total : (uint32_t)blocks[t], total);
-      for (int c = 0; c < 3; ++c) dc[c] += dcs[(size_t)t * 3 + c];
-    }
-    first = out[n - 1];
-    block0 = block;
-    for (int c = 0; c < 3; ++c) dc0[c] = dc[c];
-  }
+  const Relaxed r = relax_windows(
+      data, 0, len, meta, g, total, cb,
+      [&](long chunk, const jc_state& in, const jc_state&, uint32_t block, const uint32_t* dc) {
+        jc_row_pack(&rows[(size_t)chunk * JS_ROW_WORDS], in, jc_chunk_start(len, cb, chunk), block, dc);
+      });
   const uint32_t none[3] = {0, 0, 0};
-  for (long i = w0; i < nchunks; ++i) jc_row_pack(&rows[(size_t)i * JS_ROW_WORDS], jc_state_past(), 0, total, none);
-}
-
-// the same rows from one serial walk: the decoder's state whenever a symbol is the first to start in a later chunk
-void serial_rows(const uint8_t* data, int len, const int32_t* meta, const jc_geom& g, int cb, std::vector<uint32_t>& rows) {
-  const long nchunks = jc_chunk_count(0, len, cb);
-  const uint64_t total = (uint64_t)((long)g.mcux * g.mcuy * g.mcu_blocks);
-  rows.assign((size_t)nchunks * JS_ROW_WORDS, 0xDEADBEEFu);
-  uint32_t dc[3] = {0, 0, 0};
-  uint64_t blocks = 0;
-  jc_row_pack(&rows[0], jc_state_make(0, 0, 0, 0), 0, 0, dc);      // chunk 0 starts where the frame does
-  long next = 1;
-  jc_cbits b;
-  jc_cbits_init(b, data, jc_state_make(0, 0, 0, 0), len);
-  int blk = 0, k = 0, ignored = 0;
-  for (;;) {
-    jc_cfill(b);
-    int bit;
-    const int pos = jc_cbits_pos(b, &bit);
-    if (pos == JC_PAST) break;
-    for (; next < nchunks && pos >= jc_chunk_start(len, cb, next); ++next)
-      jc_row_pack(&rows[(size_t)next * JS_ROW_WORDS], jc_state_make(pos, bit, blk, k), jc_chunk_start(len, cb, next),
-                  (uint32_t)(blocks > total ? total : blocks), dc);
-    const int comp = jc_block_comp(g, blk);
-    int at, val;
-    const int nk = jc_symbol(meta, b, comp, k, &at, &val, &ignored);
-    if (k == 0) dc[comp] += (uint32_t)val;
-    k = nk;
-    if (k == 64) {
-      k = 0;
-      ++blocks;
-      if (++blk >= g.mcu_blocks) blk = 0;
-    }
-  }
-  for (; next < nchunks; ++next) jc_row_pack(&rows[(size_t)next * JS_ROW_WORDS], jc_state_past(), 0, 0, dc);
+  for (long i = r.reached; i < nchunks; ++i)
+    jc_row_pack(&rows[(size_t)i * JS_ROW_WORDS], jc_state_past(), 0, total, none);
 }
 
 // what a lane of jpeg_entropy_store_kernel does for chunk i of a frame of one segment
@@ -201,8 +116,6 @@ void check(const Case& c, const uint8_t* bytes, int have, int len, int cb, uint3
   free(store);
 }
 
-bool read_exact(FILE* f, void* p, size_t n) { return n == 0 || fread(p, 1, n, f) == n; }
-
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -210,27 +123,11 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: %s <cases file>\n", argv[0]);
     return 2;
   }
-  FILE* f = fopen(argv[1], "rb");
-  int32_t head[2];
-  if (!f || !read_exact(f, head, sizeof head) || head[0] != 0x4A504731 || head[1] < 1) {
+  std::vector<Case> cases;
+  if (!read_cases(argv[1], false, cases)) {
     fprintf(stderr, "cannot read %s\n", argv[1]);
     return 2;
   }
-  std::vector<Case> cases(head[1]);
-  for (Case& c : cases) {
-    int32_t h[8];
-    if (!read_exact(f, h, sizeof h)) return 2;
-    c.H = h[0]; c.W = h[1]; c.ncomp = h[2]; c.hs = h[3]; c.vs = h[4]; c.width = h[5]; c.len = h[6]; c.corrupt = h[7];
-    if (c.H < 1 || c.W < 1 || c.H > 8192 || c.W > 8192 || c.width <= JM_SEG || c.width > (1 << 20) || c.len < 0)
-      return 2;
-    c.meta.resize(c.width);
-    c.data.resize(c.len);
-    if (!read_exact(f, c.meta.data(), (size_t)c.width * 4) || !read_exact(f, c.data.data(), c.len) ||
-        fseek(f, (long)c.H * c.W * 3, SEEK_CUR) != 0)
-      return 2;
-    if (c.meta[JM_NSEG] < 1 || c.meta[JM_NSEG] > c.width - JM_SEG) return 2;
-  }
-  fclose(f);
 
   const int sizes[] = {8, 16, 64, 128, 65536};
   Tally clean, damaged;

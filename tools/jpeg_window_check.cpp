@@ -8,8 +8,9 @@
 // The cases file is the one tools/jpeg_core_check.cpp reads (tests/_jpeg_cases.py: write_core_check_cases); the boxes
 // file lists per case its pixel boxes (tests/_jpeg_window_cases.py: write_boxes).  For every case, at chunk sizes 8 and
 // 64, and every box:
-//   rows     one serial walk over the bytes notes the decoder's state at the first symbol of every chunk (once per
-//            case and chunk size; the store's rows, tools/jpeg_store_check.cpp ties the kernel's order to this walk);
+//   rows     one serial walk over the bytes notes the decoder's state at the first symbol of every chunk (serial_rows of
+//            tools/jpeg_check.h, once per case and chunk size; the store's rows, tools/jpeg_store_check.cpp ties the
+//            kernel's order to this walk);
 //   entropy  what a lane of the window kernel does, per chunk, last chunk first: its own row and the next row's block
 //            count, the skip predicate, jc_chunk_write with m1 = the window's last MCU -- or per restart segment the
 //            segment predicate and jc_decode_segment -- into zero-filled coefficients in an exact heap block;
@@ -21,60 +22,13 @@
 //   reads    every sample jc_pixel reads for a pixel of the box -- the luma sample, and the chroma columns and rows
 //            jc_chroma addresses, listed here from its definition -- lies in a block of the MCU rectangle.
 // Exit 0 = all held.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include "../coclr_amd/csrc/jpeg_core.h"
+#include "jpeg_check.h"
 
 namespace {
-
-struct Case {
-  int H, W, ncomp, hs, vs, width, len;
-  std::vector<int32_t> meta;
-  std::vector<uint8_t> data, rgb;
-  std::vector<int32_t> boxes;          // [n][4]
-};
 
 struct Tally {
   long windows = 0, lanes = 0, skipped = 0, blocks = 0, pixels = 0, reads = 0, failed = 0;
 };
-
-// the rows of a frame of one restart segment from one serial walk (tools/jpeg_store_check.cpp: serial_rows)
-void serial_rows(const uint8_t* data, int len, const int32_t* meta, const jc_geom& g, int cb, std::vector<uint32_t>& rows) {
-  const long nchunks = jc_chunk_count(0, len, cb);
-  const uint64_t total = (uint64_t)((long)g.mcux * g.mcuy * g.mcu_blocks);
-  rows.assign((size_t)nchunks * JS_ROW_WORDS, 0xDEADBEEFu);
-  uint32_t dc[3] = {0, 0, 0};
-  uint64_t blocks = 0;
-  jc_row_pack(&rows[0], jc_state_make(0, 0, 0, 0), 0, 0, dc);
-  long next = 1;
-  jc_cbits b;
-  jc_cbits_init(b, data, jc_state_make(0, 0, 0, 0), len);
-  int blk = 0, k = 0, ignored = 0;
-  for (;;) {
-    jc_cfill(b);
-    int bit;
-    const int pos = jc_cbits_pos(b, &bit);
-    if (pos == JC_PAST) break;
-    for (; next < nchunks && pos >= jc_chunk_start(len, cb, next); ++next)
-      jc_row_pack(&rows[(size_t)next * JS_ROW_WORDS], jc_state_make(pos, bit, blk, k), jc_chunk_start(len, cb, next),
-                  (uint32_t)(blocks > total ? total : blocks), dc);
-    const int comp = jc_block_comp(g, blk);
-    int at, val;
-    const int nk = jc_symbol(meta, b, comp, k, &at, &val, &ignored);
-    if (k == 0) dc[comp] += (uint32_t)val;
-    k = nk;
-    if (k == 64) {
-      k = 0;
-      ++blocks;
-      if (++blk >= g.mcu_blocks) blk = 0;
-    }
-  }
-  for (; next < nchunks; ++next) jc_row_pack(&rows[(size_t)next * JS_ROW_WORDS], jc_state_past(), 0, 0, dc);
-}
 
 // the MCU a block of the frame (coefficient order) belongs to
 long block_mcu(const jc_geom& g, int blk) {
@@ -234,8 +188,6 @@ void check(const Case& c, size_t id, int cb, Tally& tally) {
   }
 }
 
-bool read_exact(FILE* f, void* p, size_t n) { return n == 0 || fread(p, 1, n, f) == n; }
-
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -243,33 +195,20 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: %s <cases file> <boxes file>\n", argv[0]);
     return 2;
   }
-  FILE* f = fopen(argv[1], "rb");
+  std::vector<Case> cases;
   FILE* fb = fopen(argv[2], "rb");
-  int32_t head[2], bhead[2];
-  if (!f || !fb || !read_exact(f, head, sizeof head) || head[0] != 0x4A504731 || head[1] < 1 ||
-      !read_exact(fb, bhead, sizeof bhead) || bhead[0] != 0x4A505742 || bhead[1] != head[1]) {
+  int32_t bhead[2];
+  if (!read_cases(argv[1], true, cases) || !fb || !read_exact(fb, bhead, sizeof bhead) || bhead[0] != 0x4A505742 ||
+      bhead[1] != (int32_t)cases.size()) {
     fprintf(stderr, "cannot read %s and %s\n", argv[1], argv[2]);
     return 2;
   }
-  std::vector<Case> cases(head[1]);
   for (Case& c : cases) {
-    int32_t h[8], n;
-    if (!read_exact(f, h, sizeof h)) return 2;
-    c.H = h[0]; c.W = h[1]; c.ncomp = h[2]; c.hs = h[3]; c.vs = h[4]; c.width = h[5]; c.len = h[6];
-    if (!jc_geometry_ok(c.H, c.W, c.ncomp, c.hs, c.vs, 8192) || c.width <= JM_SEG || c.width > (1 << 20) || c.len < 0)
-      return 2;
-    c.meta.resize(c.width);
-    c.data.resize(c.len);
-    c.rgb.resize((size_t)c.H * c.W * 3);
-    if (!read_exact(f, c.meta.data(), (size_t)c.width * 4) || !read_exact(f, c.data.data(), c.len) ||
-        !read_exact(f, c.rgb.data(), c.rgb.size()))
-      return 2;
-    if (c.meta[JM_NSEG] < 1 || c.meta[JM_NSEG] > c.width - JM_SEG) return 2;
+    int32_t n;
     if (!read_exact(fb, &n, 4) || n < 1 || n > 4096) return 2;
     c.boxes.resize((size_t)n * 4);
     if (!read_exact(fb, c.boxes.data(), c.boxes.size() * 4)) return 2;
   }
-  fclose(f);
   fclose(fb);
 
   const int sizes[] = {8, 64};
