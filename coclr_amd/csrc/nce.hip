@@ -900,7 +900,7 @@ __global__ void sigmoid_bwd_kernel(const float* __restrict__ dw, const float* __
     ds[e] = dw[e] * w[e] * (1.f - w[e]);
 }
 
-// out[n][c][:] (+)= a[n][c][:] * g[n*C+c] + b[n*C+c]   (one wave per plane, 16 B lanes)
+// out[n][c][:] (+)= a[n][c][:] * g[n*C+c] + b[n*C+c]   (one wave per plane, one float per lane and pass)
 __global__ void __launch_bounds__(256)
 plane_scale_kernel(const float* __restrict__ a, const float* __restrict__ g,
                    const float* __restrict__ b, float* out, int planes, int C, int S,

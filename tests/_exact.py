@@ -1,5 +1,7 @@
 """Shared pieces of the exact pooling / BatchNorm GPU tests (tests/test_gpu_pool_exact.py,
-tests/test_gpu_bn_exact.py) and of the contrastive head (tests/test_gpu_head_exact.py, tests/test_gpu_loss_exact.py): operand placement with guards, exact comparison, and the BatchNorm backward reference
+tests/test_gpu_bn_exact.py), of the contrastive head (tests/test_gpu_head_exact.py, tests/test_gpu_loss_exact.py) and of
+the optimiser, global average pool and self-gating kernels (tests/test_gpu_small_exact.py, with its references in
+tests/_small_cases.py): operand placement with guards, exact comparison, and the BatchNorm backward reference
 in float64 with fp32 roundings at the points the kernels determine."""
 import pytest
 import torch

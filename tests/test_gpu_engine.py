@@ -156,6 +156,62 @@ def test_sep_inception_block(gating):
     check_module(m, lambda sd, xx: orc.sep_inception(sd, "m", xx, True, gating), x, per_tensor=True)
 
 
+@pytest.mark.parametrize("sliced", [False, True], ids=["fresh-output", "slice-of-a-block-and-a-second-consumer"])
+def test_self_gating_unit(sliced):
+    """engine.self_gating alone: out = x * sigmoid(fc(mean_{T,H,W} x)) (backbone/s3dg.py:68-78) into a fresh tensor, and
+    into a channel slice of a wider block output while x also feeds a second consumer whose backward runs first, so
+    that the gating's own data gradient accumulates.  Output, dX, dW and db against float64 autograd at
+    test_sep_inception_block's bar: forward 1e-3; every gradient within max(3 x the fp32 CPU evaluation's own error,
+    5e-3) and no tensor beyond 2e-2."""
+    from coclr_amd import engine
+    torch.manual_seed(3)
+    N, C, dims = 2, 12, (2, 5, 7)
+    x, dout, extra = (torch.randn(N, C, *dims) for _ in range(3))
+    fc = torch.nn.Linear(C, C)
+
+    def oracle(dtype):
+        xr = x.detach().clone().to(dtype).requires_grad_(True)
+        W, b = (t.detach().to(dtype).requires_grad_(True) for t in (fc.weight, fc.bias))
+        w = torch.sigmoid(torch.nn.functional.linear(xr.mean((2, 3, 4)), W, b))
+        out = xr * w[:, :, None, None, None]
+        out.backward(dout.to(dtype))
+        return out.detach(), xr.grad + (extra.to(dtype) if sliced else 0), W.grad, b.grad
+
+    ref32, ref64 = oracle(torch.float32), oracle(torch.float64)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    fcg = torch.nn.Linear(C, C)
+    fcg.load_state_dict(fc.state_dict())
+    fcg = fcg.cuda()
+    engine.new_pass(dev)
+    run = engine.Run(dev, save=True, need_input_grad=True)
+    xin = engine.Val(x.cuda())
+    if sliced:
+        block = torch.full((N, C + 5, *dims), -12345.0, device="cuda")
+        engine.self_gating(run, xin, fcg, out=engine.Val(block, 2, C))
+        other = engine.subsample(run, xin, 1)           # emitted later: its backward writes dX first
+        assert torch.equal(other.view(), xin.view())
+        run.out = engine.Val(block)
+        dblock = torch.zeros_like(block)
+        dblock[:, 2:2 + C] = dout.cuda()
+        run.grads[id(other.base)] = extra.cuda()
+        run.backward(dblock)
+        assert run.grad_writes[id(xin.base)] == 2, "the gating's data gradient must have accumulated"
+        out = block[:, 2:2 + C]
+        assert bool((block[:, :2] == -12345.0).all()) and bool((block[:, 2 + C:] == -12345.0).all())
+    else:
+        res = engine.self_gating(run, xin, fcg)
+        run.out = res
+        run.backward(dout.cuda())
+        out = res.view()
+    torch.cuda.synchronize()
+    got = (out, run.grads[id(xin.base)], run.param_grads[id(fcg.weight)], run.param_grads[id(fcg.bias)])
+    assert rel(got[0], ref32[0]) <= 1e-3, "forward rel err %.3e" % rel(got[0], ref32[0])
+    for name, g, r32, r64 in zip(("out", "dX", "dW", "db"), got, ref32, ref64):
+        e_got, e_ref = rel(g, r64), rel(r32, r64)
+        print("self_gating %s: err vs fp64 %.3e (fp32 CPU: %.3e)" % (name, e_got, e_ref))
+        assert g.shape == r64.shape and e_got <= 2e-2 and e_got <= max(3.0 * e_ref, 5e-3), (name, e_got, e_ref)
+
+
 def test_s3d_stages_per_tensor_gradients():
     """Stages 2 and 3 of S3D at their real widths (Conv_2b/2c; MaxPool_3a + Mixed_3b + Mixed_3c,
     backbone/s3dg.py:151-164) with >= 2048 values per BatchNorm channel: every one of their 54

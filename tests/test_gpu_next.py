@@ -360,6 +360,42 @@ def test_adam_leaves_and_reenters_the_native_path():
     assert float(opt.state[ps[0]]["step"]) == 3.0
 
 
+def test_adam_matches_torch_skipped_gradient_and_lr_change():
+    """Per-tensor groups with alternating lr, sizes of 1, 5, _CHUNK and _CHUNK+3 elements and a matrix, a parameter that
+    has no gradient in steps 0 and 3 (its step counter must not advance), an lr change at step 4: every step against
+    torch's own Adam on the same GPU, and every parameter's step counter equal to torch's after every step."""
+    from coclr_amd import optim as O
+    gen = torch.Generator().manual_seed(0)
+    host = [torch.randn(s, generator=gen) for s in [(1,), (5,), (O._CHUNK,), (O._CHUNK + 3,), (7, 3)]]
+    ps = [h.cuda().requires_grad_(True) for h in host]
+    ref_ps = [h.cuda().requires_grad_(True) for h in host]
+    lrs = [1e-4 if i % 2 else 1e-3 for i in range(len(ps))]
+    opt = O.Adam([{"params": p, "lr": lr} for p, lr in zip(ps, lrs)], lr=1e-3, weight_decay=1e-5)
+    ref = O._TorchAdam([{"params": p, "lr": lr} for p, lr in zip(ref_ps, lrs)], lr=1e-3, weight_decay=1e-5)
+    gen = torch.Generator().manual_seed(1)
+    for step in range(6):
+        skip = (1,) if step in (0, 3) else ()      # (5,) gets no gradient in steps 0 and 3
+        if step == 4:
+            for g in list(opt.param_groups) + list(ref.param_groups):
+                g["lr"] = g["lr"] * 0.1
+        for i, (p, rp) in enumerate(zip(ps, ref_ps)):
+            if i in skip:
+                p.grad = rp.grad = None
+                continue
+            gr = (torch.randn(rp.shape, generator=gen) * 0.1).cuda()
+            p.grad, rp.grad = gr, gr.clone()
+        opt.step()
+        ref.step()
+        assert opt._plan is not None, "the HIP path must be the one that ran"
+        for i, (p, rp) in enumerate(zip(ps, ref_ps)):
+            check_close(p, rp, 1e-6, "step %d parameter %d" % (step, i))
+            a, b = opt.state.get(p, {}), ref.state.get(rp, {})
+            assert ("step" in a) == ("step" in b), (step, i)
+            if "step" in b:
+                assert float(a["step"]) == float(b["step"]), (step, i, float(a["step"]), float(b["step"]))
+    assert float(opt.state[ps[1]]["step"]) == 4.0 and float(opt.state[ps[0]]["step"]) == 6.0
+
+
 # ---- DDP glue: gradients produced inside the buckets -------------------------------------------
 
 def test_gradients_in_ddp_buckets_bit_identical_and_deterministic(monkeypatch):

@@ -86,6 +86,34 @@ def test_sgd_matches_torch(opts):
         assert len(opt.state) == 0 and opt.state_dict()["state"] == {}
 
 
+@pytest.mark.parametrize("opts", [dict(momentum=0.9, weight_decay=1e-3), dict(momentum=0.9, nesterov=True)],
+                         ids=lambda o: "-".join("%s=%s" % kv for kv in o.items()))
+def test_sgd_gradients_as_bucket_views(opts):
+    """The gradients are views 4 bytes into one flat buffer each, as DDP's bucket views are: no row of the launch has its
+    three pointers on a 16-byte boundary, every chunk takes the scalar loop, and the step stays bit-identical."""
+    O = _O()
+    ps, ref_ps = _pair([(5,), (32768 + 3,)])
+    opt = O.SGD([{"params": p} for p in ps], lr=0.1, **opts)
+    ref = O._TorchSGD([{"params": p} for p in ref_ps], lr=0.1, **opts)
+    bucket = torch.zeros(1 + sum(p.numel() for p in ps) + 8, device="cuda")
+    assert bucket.data_ptr() % 16 == 0
+    gen = torch.Generator().manual_seed(6)
+    for step in range(4):
+        off = 1
+        for p, rp in zip(ps, ref_ps):
+            gr = (torch.randn(rp.shape, generator=gen) * 0.1).cuda()
+            p.grad = bucket[off:off + p.numel()].view_as(p)
+            p.grad.copy_(gr)
+            rp.grad = gr
+            assert p.grad.data_ptr() % 16 != 0 and p.grad.is_contiguous()
+            off += p.numel() + 3                    # 1, 9: both one float past a 16-byte boundary
+        opt.step()
+        ref.step()
+        assert opt._plan is not None, "the HIP path must be the one that ran"
+        _same(ps, ref_ps, "step %d" % step)
+        _state_same(opt, ref, ps, ref_ps)
+
+
 def test_one_launch_per_step_and_no_foreach(monkeypatch):
     O = _O()
     from coclr_amd import ops
