@@ -161,6 +161,8 @@ _SIGNATURES = {
     "coclr_resize_boxes_ragged_u8": [vp, i64, vp, _P(i32), i32, i32, i32, vp, i64, vp, i64, vp, vp],
     "coclr_resize2_boxes_ragged": [vp, i64, vp, _P(i32), i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, i32, _P(f32),
                                    _P(f32), vp, vp, vp],
+    "coclr_stage_crops_ragged": [vp, i64, vp, _P(i32), i32, i32, vp, _P(i64), i32, i32, i32, vp, vp, i32, vp, vp, i32,
+                                 _P(f32), _P(f32), vp, vp, vp],
     "coclr_colstats_workspace": [i32, i32, _P(i64)],
     "coclr_bn1d_stats": [vp, vp, vp, i32, i32, vp],
     "coclr_center_rows": [vp, vp, vp, i32, i32, vp],

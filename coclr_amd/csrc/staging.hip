@@ -96,7 +96,45 @@ struct CropArgs {
   int crop[16][3];                           // x0, y0, flip
   float mean[3], std[3];
   int F, H, W, T, n_clips, cw, ch, S, Sp, xtaps, ytaps, R, cap_rows;
+  // the ragged form (coclr_stage_crops_ragged): one descriptor per output clip, one byte offset per slot
+  const int32_t* desc; const int64_t* slot_off;
+  long nbytes;                               // bytes of `frames`
 };
+
+// The RAGGED form of the crop kernel: the clips of MANY videos, of differing frame sizes, in one launch.  An output
+// clip is one (video, crop, clip) triple with its own descriptor {x0, y0, flip, W, H} (device data, int32 x
+// CROP_FIELDS); `frames` is one flat byte buffer and slot_off[clip*T + t] the byte offset of the frame that slot
+// reads (64 bits; test clips are strided, padded and overlapping, so there is no step from one slot to the next).
+// The crop SIZE and the tables stay those of the launch.  W, H and the box are clamped to the clip's OWN frame, and a
+// slot whose frame would not lie inside the buffer of `nbytes`, or is smaller than the crop, is skipped, so nothing
+// is read outside it whatever the device copies hold (the entry point validates the host copies before the launch).
+enum { CROP_X0 = 0, CROP_Y0, CROP_FLIP, CROP_W, CROP_H, CROP_FIELDS };
+constexpr int kRagMaxSide = 32768;
+
+struct CropRows { const uint8_t* fr; int x0, flip, W; };     // fr: row y0 + ylo of the frame, column 0
+
+template <bool RAGGED>
+__device__ __forceinline__ bool crop_rows(const CropArgs& a, int slot, int crop, int ylo, CropRows& o) {
+  if (RAGGED) {
+    const int32_t* d = a.desc + (long)(slot / a.T) * CROP_FIELDS;
+    const int W = min(max(d[CROP_W], 1), kRagMaxSide), H = min(max(d[CROP_H], 1), kRagMaxSide);
+    const long off = a.slot_off[slot];
+    if (W < a.cw || H < a.ch || off < 0 || off > a.nbytes - (long)W * H * 3) return false;
+    const int y0 = min(max(d[CROP_Y0], 0), H - a.ch);
+    o.x0 = min(max(d[CROP_X0], 0), W - a.cw);
+    o.flip = d[CROP_FLIP] != 0;
+    o.W = W;
+    o.fr = a.frames + off + (long)(y0 + ylo) * W * 3;
+  } else {
+    const int y0 = a.crop[crop][1];
+    const int f = min(max(a.slot_frame[slot], 0), a.F - 1);
+    o.x0 = a.crop[crop][0];
+    o.flip = a.crop[crop][2];
+    o.W = a.W;
+    o.fr = a.frames + ((long)f * a.H + (y0 + ylo)) * (long)a.W * 3;
+  }
+  return true;
+}
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
@@ -105,27 +143,28 @@ __device__ __forceinline__ unsigned fix8(int acc) {       // PIL's clip8 of a 22
   return min((unsigned)t >> 22, 255u);
 }
 
-template <bool U8OUT>
+template <bool U8OUT, bool RAGGED>
 __global__ void __launch_bounds__(256)
 stage_crops_kernel(const CropArgs a) {
   extern __shared__ __align__(16) uint8_t hrows[];      // [rows][3][Sp]
   const int tid = threadIdx.x;
-  const int band = blockIdx.x, slot = blockIdx.y, crop = blockIdx.z;
+  const int band = blockIdx.x, slot = blockIdx.y, crop = RAGGED ? 0 : blockIdx.z;
   const int r0 = band * a.R, r1 = min(r0 + a.R, a.S);                  // output rows [r0, r1)
-  const int x0 = a.crop[crop][0], y0 = a.crop[crop][1], flip = a.crop[crop][2];
-  const int f = clampi(a.slot_frame[slot], 0, a.F - 1);
   const int ylo = clampi(a.ymin[r0], 0, a.ch - 1);
   const int rows = min(clampi(a.ymin[r1 - 1] + a.ytaps, ylo + 1, a.ch) - ylo, a.cap_rows);
   const int Sp = a.Sp, nxg = Sp >> 2;
+  CropRows g;
+  if (!crop_rows<RAGGED>(a, slot, crop, ylo, g)) return;              // uniform
+  const int x0 = g.x0, flip = g.flip, W = g.W;
   // byte offset of crop column j, channel 0, within a frame row: xb + xs*j
-  const int xb = flip ? (a.W - 1 - x0) * 3 : x0 * 3, xs = flip ? -3 : 3;
-  const uint8_t* fr = a.frames + ((long)f * a.H + (y0 + ylo)) * (long)a.W * 3;
+  const int xb = flip ? (W - 1 - x0) * 3 : x0 * 3, xs = flip ? -3 : 3;
+  const uint8_t* fr = g.fr;
 
   // horizontal pass: item = (row, c, xg), xg fastest
   for (int it = tid; it < rows * 3 * nxg; it += 256) {
     const int xg = it % nxg, rc = it / nxg;
     const int c = rc % 3, row = rc / 3;
-    const uint8_t* src = fr + (long)row * a.W * 3 + xb + c;
+    const uint8_t* src = fr + (long)row * W * 3 + xb + c;
     const int4 xm = reinterpret_cast<const int4*>(a.xmin)[xg];
     int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
     for (int i = 0; i < a.xtaps; ++i) {
@@ -197,7 +236,6 @@ enum { BOX_FIRST = 0, BOX_FRAMES, BOX_X0, BOX_Y0, BOX_W, BOX_H, BOX_XOFF, BOX_YO
 // which follow each other at W * H * 3 bytes rounded up to 16 (every frame starts aligned); `first` is not read.  The box is clamped to the clip's OWN frame, and a
 // clip whose T frames do not lie inside the buffer of `nbytes` is skipped, so nothing is read outside it.
 enum { RAG_OFF_LO = 0, RAG_OFF_HI, RAG_W, RAG_H, RAG_FIELDS };
-constexpr int kRagMaxSide = 32768;
 
 struct RagFrame { const uint8_t* base; int W, H; };
 
@@ -752,6 +790,24 @@ color_jitter_kernel(const JitterArgs a) {
 
 }  // namespace
 
+// Band height of the crop kernel: the most output rows whose source rows fit the LDS budget.  ymin is non-decreasing
+// and advances by at most ch/S (+1 from truncation) per output row, so a band of R rows spans at most
+// floor((R-1)*ch/S) + ytaps + 1 source rows; the kernel clamps to cap_rows whatever the tables say.
+// False: one output row's taps do not fit 64 KiB of LDS.
+static bool crop_band(int ch, int S, int Sp, int ytaps, int* R_out, int* cap_out) {
+  int R = 32, cap = 0;
+  for (;; R >>= 1) {
+    cap = (int)(((long)(R - 1) * ch) / S) + ytaps + 2;
+    if (cap > ch) cap = ch;
+    const long bytes = (long)cap * 3 * Sp;
+    if (bytes <= (R > 1 ? 32768 : 65536)) break;
+    if (R == 1) return false;
+  }
+  *R_out = R;
+  *cap_out = cap;
+  return true;
+}
+
 // The launch both crop entry points share: `out` (fp32, with mean / std) or `out8` (the resized bytes).
 static int launch_crops(const uint8_t* frames, int F, int H, int W, const int32_t* slot_frame, int n_clips, int T,
                         const int32_t* crops, int n_crops, int cw, int ch, int S, const int32_t* xmin,
@@ -775,27 +831,19 @@ static int launch_crops(const uint8_t* frames, int F, int H, int W, const int32_
     a.mean[c] = out ? mean[c] : 0.f; a.std[c] = out ? std[c] : 1.f;      // host arrays, read at call time
     if (a.std[c] == 0.f) return COCLR_EINVAL;
   }
-  // band height: the most output rows whose source rows fit the LDS budget.  ymin is non-decreasing and
-  // advances by at most ch/S (+1 from truncation) per output row, so a band of R rows spans at most
-  // floor((R-1)*ch/S) + ytaps + 1 source rows; the kernel clamps to cap_rows whatever the tables say.
   const int Sp = (S + 3) & ~3;
-  int R = 32, cap = 0;
-  for (;; R >>= 1) {
-    cap = (int)(((long)(R - 1) * ch) / S) + ytaps + 2;
-    if (cap > ch) cap = ch;
-    const long bytes = (long)cap * 3 * Sp;
-    if (bytes <= (R > 1 ? 32768 : 65536)) break;
-    if (R == 1) return COCLR_EINVAL;                   // one output row's taps do not fit 64 KiB of LDS
-  }
+  int R = 0, cap = 0;
+  if (!crop_band(ch, S, Sp, ytaps, &R, &cap)) return COCLR_EINVAL;
   const long bands = (S + R - 1) / R;
   if (bands * n_clips * T * n_crops * 256 >= (1L << 32)) return COCLR_EINVAL;
   a.frames = frames; a.slot_frame = slot_frame; a.xmin = xmin; a.xk = xk; a.ymin = ymin; a.yk = yk;
   a.out = out; a.out8 = out8;
   a.F = F; a.H = H; a.W = W; a.T = T; a.n_clips = n_clips; a.cw = cw; a.ch = ch; a.S = S; a.Sp = Sp;
   a.xtaps = xtaps; a.ytaps = ytaps; a.R = R; a.cap_rows = cap;
+  a.desc = nullptr; a.slot_off = nullptr; a.nbytes = 0;
   dim3 grid((unsigned)bands, (unsigned)(n_clips * T), (unsigned)n_crops);
-  if (out) hipLaunchKernelGGL(stage_crops_kernel<false>, grid, dim3(256), (size_t)cap * 3 * Sp, stream, a);
-  else hipLaunchKernelGGL(stage_crops_kernel<true>, grid, dim3(256), (size_t)cap * 3 * Sp, stream, a);
+  if (out) hipLaunchKernelGGL((stage_crops_kernel<false, false>), grid, dim3(256), (size_t)cap * 3 * Sp, stream, a);
+  else hipLaunchKernelGGL((stage_crops_kernel<true, false>), grid, dim3(256), (size_t)cap * 3 * Sp, stream, a);
   COCLR_LAUNCH_CHECK();
   return 0;
 }
@@ -817,6 +865,58 @@ extern "C" int coclr_resize_crops_u8(const uint8_t* frames, int F, int H, int W,
   if (!out) return COCLR_EINVAL;
   return launch_crops(frames, F, H, W, slot_frame, n_clips, T, crops, n_crops, cw, ch, S, xmin, xk, xtaps, ymin,
                       yk, ytaps, nullptr, nullptr, nullptr, out, (hipStream_t)stream_);
+}
+
+extern "C" int coclr_stage_crops_ragged(const uint8_t* frames, int64_t nbytes, const int32_t* desc,
+                                        const int32_t* desc_host, int n_clips, int T, const int64_t* slot_off,
+                                        const int64_t* slot_off_host, int cw, int ch, int S, const int32_t* xmin,
+                                        const int32_t* xk, int xtaps, const int32_t* ymin, const int32_t* yk, int ytaps,
+                                        const float* mean, const float* std, uint8_t* out8, float* out, void* stream_) {
+  if (!frames || !desc || !desc_host || !slot_off || !slot_off_host || !xmin || !xk || !ymin || !yk)
+    return COCLR_EINVAL;
+  if ((out8 == nullptr) == (out == nullptr) || (out && (!mean || !std))) return COCLR_EINVAL;     // one of the two forms
+  if ((((uintptr_t)frames) & 15) || (((uintptr_t)desc) & 3) || (((uintptr_t)slot_off) & 7) ||
+      (((uintptr_t)xmin) & 15) || (((uintptr_t)xk) & 15) || (((uintptr_t)ymin) & 3) || (((uintptr_t)yk) & 3) ||
+      (((uintptr_t)out) & 3))
+    return COCLR_EINVAL;                                                  // 16-byte x-table loads
+  if (nbytes < 1 || n_clips < 1 || T < 1 || S < 1 || S > 512 || cw < 1 || ch < 1) return COCLR_EINVAL;
+  if (xtaps < 1 || xtaps > 64 || ytaps < 1 || ytaps > 64) return COCLR_EINVAL;
+  if ((long)n_clips * T > 65535) return COCLR_EINVAL;
+  CropArgs a;
+  for (int c = 0; c < 3; ++c) {
+    a.mean[c] = out ? mean[c] : 0.f; a.std[c] = out ? std[c] : 1.f;      // host arrays, read at call time
+    if (a.std[c] == 0.f) return COCLR_EINVAL;
+  }
+  for (int k = 0; k < n_clips; ++k) {
+    const int32_t* d = desc_host + (long)k * CROP_FIELDS;
+    const int W = d[CROP_W], H = d[CROP_H];
+    if (W < 1 || H < 1 || W > kRagMaxSide || H > kRagMaxSide) return COCLR_EINVAL;
+    if (d[CROP_X0] < 0 || d[CROP_Y0] < 0 || (long)d[CROP_X0] + cw > W || (long)d[CROP_Y0] + ch > H)
+      return COCLR_EINVAL;                                                // the box is held to the clip's own frame
+    if (d[CROP_FLIP] != 0 && d[CROP_FLIP] != 1) return COCLR_EINVAL;
+    const long fb = (long)W * H * 3;
+    for (int t = 0; t < T; ++t) {                                         // slots may repeat and share frames
+      const long off = (long)slot_off_host[(long)k * T + t];
+      if (off < 0 || (off & 15) || off > (long)nbytes - fb) return COCLR_EINVAL;
+    }
+  }
+  const int Sp = (S + 3) & ~3;
+  int R = 0, cap = 0;
+  if (!crop_band(ch, S, Sp, ytaps, &R, &cap)) return COCLR_EINVAL;
+  const long bands = (S + R - 1) / R;
+  if (bands * n_clips * T * 256 >= (1L << 32)) return COCLR_EINVAL;
+  a.frames = frames; a.slot_frame = nullptr; a.xmin = xmin; a.xk = xk; a.ymin = ymin; a.yk = yk;
+  a.out = out; a.out8 = out8;
+  a.F = 0; a.H = 0; a.W = 0; a.T = T; a.n_clips = n_clips; a.cw = cw; a.ch = ch; a.S = S; a.Sp = Sp;
+  a.xtaps = xtaps; a.ytaps = ytaps; a.R = R; a.cap_rows = cap;
+  a.desc = desc; a.slot_off = slot_off; a.nbytes = (long)nbytes;
+  for (int k = 0; k < 16; ++k) a.crop[k][0] = a.crop[k][1] = a.crop[k][2] = 0;
+  const dim3 grid((unsigned)bands, (unsigned)(n_clips * T));
+  const hipStream_t stream = (hipStream_t)stream_;
+  if (out) hipLaunchKernelGGL((stage_crops_kernel<false, true>), grid, dim3(256), (size_t)cap * 3 * Sp, stream, a);
+  else hipLaunchKernelGGL((stage_crops_kernel<true, true>), grid, dim3(256), (size_t)cap * 3 * Sp, stream, a);
+  COCLR_LAUNCH_CHECK();
+  return 0;
 }
 
 // The launch both program entry points share; `aug` admits kinds 6 (blur) and 7 (flip) and runs the augment form.

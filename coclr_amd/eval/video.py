@@ -11,6 +11,8 @@ batch -- weight 1/n per crop of n clips -- to its row of the probability and fea
 (ops.segment_softmax_accum / ops.segment_accum).  A video that spans two batches contributes two segments.
 Nothing is read back and nothing synchronises before `finish()`, whose results are device tensors (clips handed
 over as HOST tensors are copied before `add()` returns, so the caller may reuse its staging buffer).
+`add()` takes staged clips, `add_frames` one video's decoded frames, `add_videos` / `add_stored` many videos of any
+mix of frame sizes from a staging.RaggedFrames / a jpeg.Store, staged straight into the batch once per model pass.
 """
 import collections
 import random
@@ -137,6 +139,150 @@ class VideoEvaluator:
                 # (add() copies the crop into the batch on this stream before the next chunk overwrites `buf`)
                 video = self.add(clips, label=label if video is None else None, video=video)
         return video
+
+    def add_videos(self, frames, videos, crops="ten", crop_size=224, out_size=128, jitter=None, rng=random):
+        """MANY videos, of differing frame sizes, from their decoded frames in one staging.RaggedFrames (jpeg.Store.decode,
+        jpeg.decode_ragged, staging.ragged_from_frames): `videos` [(first, count, frame_index, label)] -- the video's
+        frame 0 is frame `first` of `frames`, it has `count` frames there, all of one size, and `frame_index`
+        (n_clips, T) names the frame of every clip position RELATIVE to the video (staging.test_frame_index, or one row
+        of a train-mode sampler).  The clips go video by video, crop by crop in the order of `crops`, clip by clip,
+        STRAIGHT into the free rows of the batch: one coclr_stage_crops_ragged launch (two with `jitter`) per stretch
+        of rows up to the next model pass, whatever number of videos it holds.  Segments, weights and results are those
+        of add_frames called per video; `jitter` is drawn from `rng` once per crop, video by video, in staging order,
+        before anything is staged.  Returns the videos' indices."""
+        if not isinstance(frames, staging.RaggedFrames):
+            raise ValueError("coclr_amd: add_videos takes a staging.RaggedFrames; add_frames takes one video's tensor")
+        if frames.pixels.device != self.device:
+            raise ValueError("coclr_amd: the frames are on %s, the evaluator on %s" % (frames.pixels.device, self.device))
+        crop_size, S = int(crop_size), int(out_size)
+        Hs, Ws = frames.height.tolist(), frames.width.tolist()
+
+        def size_of(first, count, idx):
+            if first + count > len(frames):
+                raise IndexError("coclr_amd: a video of frames %d..%d, but there are %d frames" %
+                                 (first, first + count - 1, len(frames)))
+            H, W = Hs[first], Ws[first]
+            if any(Hs[f] != H or Ws[f] != W for f in range(first, first + count)):
+                raise ValueError("coclr_amd: the frames %d..%d of one video differ in size" % (first, first + count - 1))
+            return W, H
+
+        # first everything that can be refused, for every video; only then the draws and the evaluator's state
+        checked, T = self._check_videos(videos, size_of, crops, crop_size, S, jitter)
+        clips, programs, runs = [], [], []                # runs: (label, [clips of every crop])
+        for first, idx, todo, label in checked:
+            drawn = None if jitter is None else [jitter.draw(rng, 1)[0] for _ in todo]
+            for k, (x0, y0, fl) in enumerate(todo):
+                clips.extend((row, (x0, y0), fl) for row in idx + first)
+                if drawn is not None:
+                    programs.extend([drawn[k]] * idx.shape[0])
+            runs.append((label, [idx.shape[0]] * len(todo)))
+        desc, slot_off = staging.crops_tables_ragged(frames, clips, crop_size)
+        if jitter is not None:
+            staging.program_tables(programs)              # refuse a bad program before anything is launched
+        desc_dev, off_dev = desc.to(self.device), slot_off.to(self.device)
+        if self._buf is None:
+            self._buf = torch.zeros(self.batch_clips, 3, T, S, S, dtype=torch.float32, device=self.device)
+        # the crops still to be registered, as add() registers them: (video, clips of the crop, clips still to go)
+        out, pending = [], collections.deque()
+        for label, per_crop in runs:
+            out.append(len(self._crops))
+            self._labels.append(label)
+            self._crops.append(len(per_crop))
+            pending.extend([out[-1], n, n] for n in per_crop)
+        at, total = 0, desc.shape[0]
+        while at < total:
+            k = min(total - at, self.batch_clips - self._fill)
+            staging.launch_crops_ragged(frames.pixels, desc[at:at + k], slot_off[at:at + k], desc_dev[at:at + k],
+                                        off_dev[at:at + k], crop_size, crop_size, S, staging.IMAGENET_MEAN,
+                                        staging.IMAGENET_STD, self._buf[self._fill:self._fill + k],
+                                        None if jitter is None else programs[at:at + k])
+            left = k
+            while left:
+                crop = pending[0]
+                m = min(left, crop[2])
+                self._segs.append((self._fill, m, crop[0]))
+                self._weights.append(1.0 / crop[1])
+                self._fill += m
+                left -= m
+                crop[2] -= m
+                if not crop[2]:
+                    pending.popleft()
+            at += k
+            if self._fill == self.batch_clips:
+                self._flush()
+        return out
+
+    def add_stored(self, store, videos, crops="ten", crop_size=224, out_size=128, jitter=None, rng=random,
+                   max_stage_bytes=256 << 20):
+        """add_videos from a jpeg.Store: `videos` [(first, count, frame_index, label)] with `first` the STORE id of the
+        video's frame 0.  As many videos share one `store.decode` call as `max_stage_bytes` of decoded pixels allows
+        (one at least), and only the distinct frames their `frame_index` rows name are decoded: a video with one clip
+        of T frames decodes T frames, not the whole video.  Returns the videos' indices."""
+        max_stage_bytes, crop_size, S = int(max_stage_bytes), int(crop_size), int(out_size)
+
+        def size_of(first, count, idx):
+            if first + count > len(store):
+                raise IndexError("coclr_amd: a video of frames %d..%d, but the store holds %d" %
+                                 (first, first + count - 1, len(store)))
+            hw = store._geo[torch.from_numpy(idx).reshape(-1) + first, :2]      # H, W of the frames the clips read
+            if bool((hw != hw[0]).any()):
+                raise ValueError("coclr_amd: the frames %d..%d of one video differ in size" % (first, first + count - 1))
+            return int(hw[0, 1]), int(hw[0, 0])
+
+        # every video is checked before the first decode: a refused call leaves the evaluator and `rng` as they were
+        checked, _ = self._check_videos(videos, size_of, crops, crop_size, S, jitter)
+        out, group, ids, held, nbytes = [], [], [], 0, 0
+
+        def run():
+            frames = store.decode(torch.cat(ids))
+            out.extend(self.add_videos(frames, group, crops, crop_size, S, jitter, rng))
+
+        for first, idx, _, label in checked:
+            distinct, local = torch.unique(torch.from_numpy(idx), return_inverse=True)      # sorted: the frames keep their order
+            W, H = store.frame_size(first + int(distinct[0]))
+            need = distinct.numel() * ((3 * W * H + staging.RAGGED_ALIGN - 1) & ~(staging.RAGGED_ALIGN - 1))
+            if group and nbytes + need > max_stage_bytes:
+                run()
+                group, ids, held, nbytes = [], [], 0, 0
+            group.append((held, distinct.numel(), local, label))
+            ids.append(first + distinct)
+            held += distinct.numel()
+            nbytes += need
+        run()
+        return out
+
+    def _check_videos(self, videos, size_of, crops, crop_size, S, jitter):
+        """What add_videos and add_stored refuse, for ALL `videos` [(first, count, frame_index, label)] and before
+        anything is drawn, decoded, staged or registered.  `size_of(first, count, idx)` -> (W, H) of the video's frames,
+        refusing frames that do not exist or differ in size.  Returns ([(first, idx int64 (n_clips, T) relative to the
+        video, crops [(x0, y0, flip)], label)], T)."""
+        if crops not in CROP_MODES:
+            raise ValueError("coclr_amd: crops must be one of %s, got %r" % (sorted(CROP_MODES), crops))
+        videos = list(videos)
+        if not videos:
+            raise ValueError("coclr_amd: at least one video is needed")
+        if jitter is not None and S * S > staging.JITTER_MAX_PIXELS:
+            raise ValueError("coclr_amd: color_jitter takes frames of up to 224 x 224 pixels, got %d x %d" % (S, S))
+        where, flip_list = CROP_MODES[crops]
+        out, T = [], None
+        for first, count, frame_index, label in videos:
+            first, count = int(first), int(count)
+            if count < 1 or first < 0:
+                raise IndexError("coclr_amd: a video of %d frames from frame %d" % (count, first))
+            idx = staging.check_frame_index(frame_index, count).numpy().astype("int64")
+            W, H = size_of(first, count, idx)
+            boxes = staging.five_crop_boxes(W, H, crop_size, where)
+            todo = staging.check_crops(boxes * len(flip_list), [f for f in flip_list for _ in boxes],
+                                       crop_size, crop_size, W, H)
+            T = idx.shape[1] if T is None else T
+            want = (3, T, S, S) if self._buf is None else tuple(self._buf.shape[1:])
+            if (3, idx.shape[1], S, S) != want:
+                raise ValueError("coclr_amd: clip size %s differs from the evaluator's %s" % ((3, idx.shape[1], S, S), want))
+            if T > staging.CROPS_MAX_SLOTS:
+                raise ValueError("coclr_amd: a clip of %d frames exceeds the %d slots of a launch" %
+                                 (T, staging.CROPS_MAX_SLOTS))
+            out.append((first, idx, todo, None if label is None else int(label)))
+        return out, T
 
     def _flush(self):
         """Run the batch (rows past `_fill` are padding: they belong to no segment) and accumulate."""

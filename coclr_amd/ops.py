@@ -1308,6 +1308,42 @@ def resize2_boxes_ragged(pixels, desc, desc_host, xtab, ytab, tab2, T, size, S, 
     _resize2_boxes("resize2_boxes_ragged", True, pixels, desc, desc_host, xtab, ytab, tab2, T, size, S, out, mean, std)
 
 
+def stage_crops_ragged(pixels, desc, desc_host, slot_off, slot_off_host, cw, ch, S, xmin, xk, ymin, yk, out, mean=None,
+                       std=None):
+    """stage_crops / resize_crops_u8 for the clips of many videos in one launch (include/coclr_hip.h:
+    coclr_stage_crops_ragged): pixels the flat byte buffer; desc int32 (n_clips, 5) = {x0, y0, flip, W, H} and slot_off
+    int64 (n_clips, T), the byte offset of every slot's frame, each on the device and on the host; the tables as
+    stage_crops takes them.  `out` fp32 (n_clips, 3, T, S, S) takes the clips normalised with `mean` / `std`; `out`
+    uint8 (n_clips*T, S, S, 3) takes the resized bytes."""
+    _clip_source(pixels, desc, desc_host, 5, True)
+    n_clips, S = desc.shape[0], int(S)
+    if slot_off.dim() != 2 or slot_off.shape[0] != n_clips or slot_off.shape != slot_off_host.shape or \
+            slot_off_host.is_cuda or slot_off_host.dtype != torch.int64 or not slot_off.is_contiguous() or \
+            not slot_off_host.is_contiguous():
+        raise ValueError("coclr_amd: slot offsets must be contiguous int64 (n_clips, T), device and host")
+    T = slot_off.shape[1]
+    Sp = (S + 3) & ~3
+    if tuple(xmin.shape) != (Sp,) or xk.dim() != 2 or xk.shape[1] != Sp or \
+            tuple(ymin.shape) != (Sp,) or yk.dim() != 2 or yk.shape[1] != Sp:
+        raise ValueError("coclr_amd: resampling tables must be (Sp,) and (taps, Sp) with Sp = %d" % Sp)
+    for t in (xmin, xk, ymin, yk):
+        if not t.is_contiguous():
+            raise ValueError("coclr_amd: stage_crops_ragged needs contiguous table tensors")
+    u8 = out.dtype == torch.uint8
+    if not u8 and (mean is None or std is None):
+        raise ValueError("coclr_amd: the fp32 form of stage_crops_ragged needs mean and std")
+    want = (n_clips * T, S, S, 3) if u8 else (n_clips, 3, T, S, S)
+    if tuple(out.shape) != want or not out.is_contiguous():
+        raise ValueError("coclr_amd: out must be contiguous %s, got %s" % (want, tuple(out.shape)))
+    m, s = (None, None) if u8 else [(C.c_float * 3)(*[float(v) for v in t]) for t in (mean, std)]
+    i32 = torch.int32
+    _lib.check(_L().coclr_stage_crops_ragged(
+        _p(pixels, torch.uint8), pixels.numel(), _p(desc, i32), C.cast(desc_host.data_ptr(), C.POINTER(C.c_int32)),
+        n_clips, T, _p(slot_off, torch.int64), C.cast(slot_off_host.data_ptr(), C.POINTER(C.c_int64)), int(cw), int(ch),
+        S, _p(xmin, i32), _p(xk, i32), xk.shape[0], _p(ymin, i32), _p(yk, i32), yk.shape[0], m, s,
+        _p(out, torch.uint8) if u8 else None, None if u8 else _p(out), _stream()), "stage_crops_ragged")
+
+
 def _program_call(name, frames, kinds, params, group_size, T, mean, std, out, host_tables):
     if frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
         raise ValueError("coclr_amd: frames must be contiguous (N, H, W, 3), got %s" % (tuple(frames.shape),))

@@ -1295,3 +1295,103 @@ def stage_train_clips_cropped(frames, plans, out_size, mean=IMAGENET_MEAN, std=I
     clips = _ragged_samples(frames, 2 * B, T, None)                          # a clip's frames: one size, one stride
     tables = train_tables_cropped(plans, [(o, W, H) for o, W, H in clips], T, S)
     return _stage_train(ops.resize_boxes_ragged_u8, frames.pixels, frames.pixels.device, tables, B, T, S, mean, std, out)
+
+
+# ---- test clips of many videos in one launch (eval/main_classifier.py:425-521,548-684) ---------------------------------
+
+CROPS_MAX_SLOTS = 65535                 # (clip, t) slots per coclr_stage_crops_ragged launch: the grid's y limit
+
+
+def crops_tables_ragged(frames, clips, crop_size):
+    """The host tables of coclr_stage_crops_ragged.  frames: a RaggedFrames, or anything with its three host tables
+    `offset`, `height`, `width` (the pixels are not touched).  clips: [(frame ids (T,) into `frames`, (x0, y0), flip)],
+    one per output clip, in output order; the box is the crop_size box at (x0, y0) of the FLIPPED frame, as stage_crops
+    takes it.  Every clip is checked against its OWN frames, which must share one size.  Returns (desc int32 (n, 5) =
+    {x0, y0, flip, W, H}, slot_off int64 (n, T): the byte offset of every slot's frame)."""
+    cw, ch = _crop_wh(crop_size)
+    clips = list(clips)
+    if not clips:
+        raise ValueError("coclr_amd: crops_tables_ragged needs at least one clip")
+    off = np.asarray(torch.as_tensor(frames.offset).cpu(), dtype=np.int64)
+    Hs = np.asarray(torch.as_tensor(frames.height).cpu(), dtype=np.int64)
+    Ws = np.asarray(torch.as_tensor(frames.width).cpu(), dtype=np.int64)
+    F = off.shape[0]
+    rows = []
+    for ids, _, _ in clips:
+        ids = np.asarray(ids.cpu() if torch.is_tensor(ids) else ids)
+        if ids.ndim != 1 or ids.size == 0 or ids.dtype.kind not in "iu":
+            raise ValueError("coclr_amd: a clip's frame ids must be integers of shape (T,), got %s %s" %
+                             (ids.dtype, ids.shape))
+        rows.append(ids.astype(np.int64))
+    T = rows[0].size
+    if any(r.size != T for r in rows):
+        raise ValueError("coclr_amd: the clips of one call share one length T")
+    ids = np.stack(rows)
+    lo, hi = int(ids.min()), int(ids.max())
+    if lo < 0 or hi >= F:
+        raise IndexError("coclr_amd: frame ids span %d..%d but there are %d frames" % (lo, hi, F))
+    W, H = Ws[ids], Hs[ids]
+    mixed = np.nonzero((W != W[:, :1]).any(1) | (H != H[:, :1]).any(1))[0]
+    if mixed.size:
+        raise ValueError("coclr_amd: the frames of clip %d differ in size; one clip is one video" % int(mixed[0]))
+    desc = np.zeros((len(clips), 5), dtype=np.int32)
+    for k, (_, box, flip) in enumerate(clips):
+        (x0, y0, fl), = check_crops([box], [flip], cw, ch, int(W[k, 0]), int(H[k, 0]))
+        desc[k] = (x0, y0, fl, W[k, 0], H[k, 0])
+    return torch.from_numpy(desc), torch.from_numpy(np.ascontiguousarray(off[ids]))
+
+
+def stage_crops_ragged(frames, clips, crop_size, out_size, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None, jitter=None):
+    """stage_crops for the clips of MANY videos, of differing frame sizes, in ONE launch (coclr_stage_crops_ragged):
+    frames: RaggedFrames (jpeg.Store.decode, jpeg.decode_ragged, ragged_from_frames).  clips: [(frame ids (T,) into
+    `frames`, (x0, y0), flip)], one per output clip: flip the frame -> crop the crop_size box at (x0, y0) of the FLIPPED
+    frame -> Image.resize((S, S), BICUBIC) -> ColorJitter -> ToTensor -> Normalize.  The frames of a clip share one size;
+    ids may repeat (a strided or left-padded test clip) and clips may share frames.  Returns (n, 3, T, S, S) fp32 on the
+    device, every clip bit-identical to stage_crops on its video alone.  `out`: any contiguous 16-byte-aligned fp32
+    destination of that shape, e.g. free rows of a model's input batch.  `jitter`: one program per clip
+    (ColorJitter.draw); the call is then two launches, resize to bytes and coclr_color_jitter_clips.  More than 65535
+    slots are cut into launches."""
+    if not isinstance(frames, RaggedFrames):
+        raise ValueError("coclr_amd: the ragged staging takes a RaggedFrames (jpeg.Store.decode, ragged_from_frames)")
+    cw, ch = _crop_wh(crop_size)
+    S = int(out_size)
+    desc, slot_off = crops_tables_ragged(frames, clips, (cw, ch))
+    n, T = slot_off.shape
+    device = frames.pixels.device
+    _check_out(out, (n, 3, T, S, S), fp32=True)
+    if out is not None and (out.device != device or out.data_ptr() % 16):
+        raise ValueError("coclr_amd: out must be 16-byte aligned and on the frames' device %s" % device)
+    if jitter is not None:
+        jitter = list(jitter)
+        if len(jitter) != n:
+            raise ValueError("coclr_amd: need one jitter program per clip, got %d programs and %d clips" %
+                             (len(jitter), n))
+        if S * S > JITTER_MAX_PIXELS:
+            raise ValueError("coclr_amd: color_jitter takes frames of up to 224 x 224 pixels, got %d x %d" % (S, S))
+        program_tables(jitter)                            # refuse a bad program before anything is launched
+    if out is None:
+        out = torch.empty(n, 3, T, S, S, dtype=torch.float32, device=device)
+    return launch_crops_ragged(frames.pixels, desc, slot_off, desc.to(device), slot_off.to(device), cw, ch, S, mean, std,
+                               out, jitter)
+
+
+def launch_crops_ragged(pixels, desc, slot_off, desc_dev, off_dev, cw, ch, S, mean, std, out, jitter=None):
+    """The launches alone: the tables of crops_tables_ragged on the host and on the device, already checked, for any
+    run of their rows; `out` (n, 3, T, S, S) fp32 on the device; `jitter` one checked program per clip."""
+    n, T = slot_off.shape
+    if T > CROPS_MAX_SLOTS:
+        raise ValueError("coclr_amd: a clip of %d frames exceeds the %d slots of a launch" % (T, CROPS_MAX_SLOTS))
+    device = pixels.device
+    xmin, xk, ymin, yk = _device_tables(cw, ch, S, device)
+    per = CROPS_MAX_SLOTS // T
+    u8 = None if jitter is None else torch.empty(min(n, per) * T, S, S, 3, dtype=torch.uint8, device=device)
+    for k in range(0, n, per):
+        e = min(k + per, n)
+        if jitter is None:
+            ops.stage_crops_ragged(pixels, desc_dev[k:e], desc[k:e], off_dev[k:e], slot_off[k:e], cw, ch, S, xmin, xk,
+                                   ymin, yk, out[k:e], mean, std)
+        else:
+            ops.stage_crops_ragged(pixels, desc_dev[k:e], desc[k:e], off_dev[k:e], slot_off[k:e], cw, ch, S, xmin, xk,
+                                   ymin, yk, u8[:(e - k) * T])
+            color_jitter(u8[:(e - k) * T], jitter[k:e], T, T, mean, std, out=out[k:e], device=device)
+    return out

@@ -911,6 +911,35 @@ int coclr_resize2_boxes_ragged(const uint8_t* frames, int64_t nbytes, const int3
                                const int32_t* ytab, int64_t ylen, const int32_t* tab2, int64_t len2, int taps2,
                                const float* mean, const float* std, uint8_t* out8, float* out, void* stream);
 
+/* Five/ten-crop test clips of MANY videos, of differing frame sizes, in one launch (eval/main_classifier.py:425-521,
+ * 548-684: the test modes and the retrieval feature extraction): the chain of coclr_stage_crops /
+ * coclr_resize_crops_u8 -- flip the frame -> crop the cw x ch box at (x0, y0) OF THE FLIPPED FRAME -> PIL's
+ * Image.resize((S, S), BICUBIC) on 8-bit pixels -> bytes, or / 255 -> (x - mean[c]) / std[c] -- with the geometry per
+ * output clip.  It is the same kernel body, the geometry read from a descriptor instead of the arguments.
+ * frames: ONE flat byte buffer of nbytes bytes, 16-byte aligned (a staging.RaggedFrames).  An output clip is one
+ * (video, crop, clip) triple, one row of the model's batch.  desc: int32 [n_clips][5] = {x0, y0, flip, W, H}, W x H
+ * the size of the clip's frames, on the device, and desc_host, the same on the host.  slot_off: int64 [n_clips*T],
+ * the byte offset of the frame every (clip, t) reads, device and host: per slot, because test clips are strided
+ * (ds > 1), left-padded with frame 0 when the video is shorter than a clip, and overlap; slots may repeat and clips
+ * may share frames.  cw, ch, S and the four tables are those of coclr_stage_crops, one set for the launch.
+ * Exactly one output: out fp32 [n_clips][3][T][S][S], normalised (mean / std HOST arrays read at call time), or out8
+ * uint8 [n_clips*T][S][S][3], the input of coclr_color_jitter_clips with group_size = T (one program per clip).
+ * The descriptors and offsets are device data: the kernel clamps W, H and the box into range and skips a slot whose
+ * frame would not lie inside [0, nbytes) or is smaller than the crop, so nothing is read or written out of bounds
+ * whatever the device copies hold.
+ * COCLR_EINVAL before any launch: a null pointer; frames, xmin or xk not 16-byte aligned, slot_off not 8-byte, desc,
+ * ymin, yk or out not 4-byte; both outputs or neither; out without mean / std; std == 0; nbytes, n_clips, T, S, cw,
+ * ch < 1; S > 512; taps outside 1..64; W or H outside 1..32768; a box that leaves its OWN W x H frame (whether or not
+ * it would fit a larger frame of the batch); flip not 0/1; a slot offset that is negative, not a multiple of 16 or
+ * whose 3 * W * H bytes leave the buffer; n_clips*T > 65535 or a grid over the launch limits; an output row whose
+ * ytaps source rows (3*Sp bytes each) exceed 64 KiB.
+ * Additive: the ABI number stays 25 -- no existing signature or behaviour changed. */
+int coclr_stage_crops_ragged(const uint8_t* frames, int64_t nbytes, const int32_t* desc, const int32_t* desc_host,
+                             int n_clips, int T, const int64_t* slot_off, const int64_t* slot_off_host, int cw, int ch,
+                             int S, const int32_t* xmin, const int32_t* xk, int xtaps, const int32_t* ymin,
+                             const int32_t* yk, int ytaps, const float* mean, const float* std, uint8_t* out8,
+                             float* out, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* Evaluation consumers (model/classifier.py:47-61; eval/main_classifier.py) */
 /* ------------------------------------------------------------------------ */
