@@ -289,6 +289,7 @@ class Run:
         self.grads = {}        # id(base tensor) -> grad tensor
         self.param_grads = {}  # id(param) -> grad tensor
         self._slots_out = set()   # parameters whose bucket view has been handed out in this run
+        self.handout = None    # id(parameter / input) -> memory set aside for its gradient (_record_backward)
         self.no_grad_bases = set()
         self.out = None
         self.plan = None       # PackPlan of the module being run
@@ -323,10 +324,17 @@ class Run:
         self.grad_writes[id(val.base)] = self.grad_writes.get(id(val.base), 0) + 1
         g = self.grads.get(id(val.base))
         if g is None:
-            g = torch.empty_like(val.base)
+            g = self.grad_mem(val.base)
             self.grads[id(val.base)] = g
             return g, False
         return g, True
+
+    def grad_mem(self, t):
+        """New memory for d(t).  While a launch plan's backward is recorded, the gradients that are handed to
+        autograd (parameters, the input) take the memory the entry has set aside for them, outside the pool that
+        the forward log writes to."""
+        g = self.handout.pop(id(t), None) if self.handout else None
+        return torch.empty_like(t) if g is None else g
 
     def grad_of(self, val):
         g = self.grads.get(id(val.base))
@@ -345,7 +353,7 @@ class Run:
             if v.device == p.device and v.shape == p.shape and v.dtype == p.dtype:
                 self._slots_out.add(id(p))
                 return v.view_as(v)          # new tensor object: autograd adopts it without a copy
-        return torch.empty_like(p)
+        return self.grad_mem(p)
 
     def add_param_grad(self, p, g):
         old = self.param_grads.get(id(p))
@@ -1137,9 +1145,9 @@ def self_gating(run, x, fc, out=None):
             ds = run.empty(N, C_)
             ops.sigmoid_bwd(dwgt, wgt, ds)
             if fc.weight.requires_grad:
-                dW = torch.empty_like(W_)          # dW[o][i] = sum_n ds[n][o] a[n][i]
+                dW = run.grad_mem(W_)              # dW[o][i] = sum_n ds[n][o] a[n][i]
                 ops.gemm(ds, 1, C_, a, C_, 1, dW, C_, None, C_, C_, N)
-                db = run.empty(C_)
+                db = run.grad_mem(fc.bias)
                 ops.colsum(ds, db)
                 run.add_param_grad(fc.weight, dW)
                 run.add_param_grad(fc.bias, db)
@@ -1160,7 +1168,8 @@ class EngineFn(torch.autograd.Function):
     """backbone(x, *params) as ONE autograd node."""
 
     @staticmethod
-    def forward(ctx, module, kwargs, x, *params):
+    def forward(ctx, module, kwargs, warming, x, *params):
+        """warming: the launch-plan entry this pass is a warm-up pass of, if any (_plan_entry)."""
         need_dx = x.requires_grad
         new_pass(x.device)
         run = Run(x.device, save=True, need_input_grad=need_dx)
@@ -1173,6 +1182,7 @@ class EngineFn(torch.autograd.Function):
         ctx.xin = xin
         ctx.params = params
         ctx.need_dx = need_dx
+        ctx.warming = warming
         ctx.module_defer = getattr(module, "__dict__", {}).get("_coclr_defer_join", False)
         out = run.out.view()
         # A FRESH tensor object: autograd stamps what we return with grad_fn, and grad_fn -> ctx
@@ -1188,6 +1198,9 @@ class EngineFn(torch.autograd.Function):
         if run is None:
             raise RuntimeError("coclr_amd: backbone backward called twice (graph not retained)")
         ctx.run = None
+        if ctx.warming is not None:
+            ctx.warming.trained = True       # passes of this signature are differentiated: worth recording
+            ctx.warming = None
         run.backward(dout, defer_join=DEFER_JOIN and bool(ctx.module_defer))
         dx = run.grads.pop(id(ctx.xin.base), None) if ctx.need_dx else None
         # Hand the gradients over WITHOUT keeping a reference: AccumulateGrad takes a freshly
@@ -1197,7 +1210,7 @@ class EngineFn(torch.autograd.Function):
                       for p in ctx.params)
         run.param_grads.clear()
         run.grads.clear()
-        return (None, None, dx) + grads
+        return (None, None, None, dx) + grads
 
 
 # ---------------------------------------------------------------------------------
@@ -1205,9 +1218,11 @@ class EngineFn(torch.autograd.Function):
 # ---------------------------------------------------------------------------------
 # The launch sequence of a node is static per signature: its recorded C-ABI calls are re-issued as ordinary
 # launches on the ordinary streams, without the host work of the interpreted pass in between.
-# After _PLAN_WARMUP interpreted passes with an unchanged signature the node's forward is run once more with
-# its allocations in a private torch.cuda.MemPool while every call it makes is logged; its tape is kept (the
-# tensors it references now have addresses nobody else is given) and logged the same way at the first backward.
+# After _PLAN_WARMUP interpreted passes with an unchanged signature, one of which at least has reached backward,
+# the node's forward is run once more with its allocations in a private torch.cuda.MemPool while every call it
+# makes is logged; its tape is kept (the tensors it references now have addresses nobody else is given) and
+# logged the same way at the first backward (the gradients that backward hands to autograd live in a second
+# pool, which the forward log never writes to).
 # From then on a step of the node is: patch the two places that hold the input's address if the caller's
 # tensor moved, re-issue the forward log; copy dout into its recorded place, re-issue the backward log, hand
 # autograd fresh aliases of the recorded gradient tensors (DDP bucket views where DDP has them).
@@ -1225,11 +1240,12 @@ _STATIC_PTRS = set()
 class _PlanEntry:
     __slots__ = ("sig", "seen", "pool", "fwd", "bwd", "run", "xin", "x_ptr", "x_span", "x_refs", "x_fixed",
                  "out", "dout", "grads", "dx", "params", "need_dx", "version", "disabled", "static_dout", "defer",
-                 "stream")
+                 "stream", "trained", "grad_pool")
 
     def __init__(self, sig):
         self.sig, self.seen = sig, 0
-        self.pool = self.fwd = self.bwd = self.run = self.xin = None
+        self.trained = False     # an interpreted pass of this entry has reached backward (EngineFn.backward)
+        self.pool = self.grad_pool = self.fwd = self.bwd = self.run = self.xin = None
         self.x_ptr = self.x_span = 0
         self.x_refs, self.x_fixed = None, False
         self.out = self.dout = self.grads = self.dx = None
@@ -1261,10 +1277,12 @@ def _plan_drop(ent):
 
 
 def _plan_entry(module, x, params, kwargs):
-    """The node's plan entry when this call can go through it (recording or replaying), else None."""
+    """(entry, go).  go: this call goes through the node's plan entry (recording or replaying).  An entry with
+    go False is still warming up: the call runs interpreted, and its backward tells the entry that passes of
+    this signature are being differentiated.  (None, False): the call has nothing to do with a plan."""
     if kwargs or not x.is_cuda or x.dim() != 5 or not _dense5(x) or DECISION_PROBE is not None or \
             torch.cuda.is_current_stream_capturing():
-        return None
+        return None, False
     store = module.__dict__.get("_coclr_plan_entries")
     if store is None:
         store = module.__dict__["_coclr_plan_entries"] = {}
@@ -1272,26 +1290,42 @@ def _plan_entry(module, x, params, kwargs):
     key = (tuple(x.shape), bool(x.requires_grad))
     ent = store.get(key)
     if ent is None and len(store) >= _PLAN_MAX_SHAPES:
-        return None                              # every entry keeps a memory pool: odd shapes run interpreted
+        return None, False                       # every entry keeps a memory pool: odd shapes run interpreted
     if ent is None or ent.sig != sig:
         if ent is not None:
             _plan_drop(ent)
         ent = store[key] = _PlanEntry(sig)       # new shape / moved storage / switches changed: start over
     if ent.disabled:
-        return None
+        return None, False
     ent.seen += 1
     if ent.seen <= _PLAN_WARMUP:
-        return None
+        return ent, False
+    if ent.fwd is None and not ent.trained:
+        # No pass of this entry has reached backward yet (main_coclr.py:403 skips loss.backward() until the queue
+        # is full).  A forward recorded now would keep its whole tape in the pool, and the logs could not follow
+        # the input to another address until a backward had consumed that tape: the recording waits.
+        return ent, False
     stream = torch.cuda.current_stream(x.device).cuda_stream
     if ent.fwd is not None:
         if stream != ent.stream:
-            return None                          # recorded on another stream: this call runs interpreted
+            return None, False                   # recorded on another stream: this call runs interpreted
         if x.data_ptr() != ent.x_ptr and (ent.x_fixed or ent.run is not None):
             # the input moved and the logs cannot follow it: an address inside a multi-problem table, or a tape
             # that has not been logged yet (forward recorded, no backward since) and reads the input through
             # its own tensor objects.  This call runs interpreted.
-            return None
-    return ent
+            return None, False
+    return ent, True
+
+
+def _plan_abandon(ent, why):
+    """A recording raised partway (out of memory, an error of the library).  The entry gives up everything it
+    holds -- above all a tape that is half consumed must never be differentiated again -- and every later pass of
+    its signature runs interpreted."""
+    _plan_drop(ent)
+    ent.disabled = True
+    ent.pool = ent.grad_pool = ent.fwd = ent.bwd = ent.run = ent.xin = None
+    ent.out = ent.dout = ent.grads = ent.dx = ent.x_refs = None
+    PLAN_STATS["disabled"].append(why)
 
 
 def _record_forward(ent, module, x, defer):
@@ -1300,17 +1334,21 @@ def _record_forward(ent, module, x, defer):
     ent.pool = torch.cuda.MemPool()
     ent.stream = torch.cuda.current_stream(dev).cuda_stream
     rec = _plan.Recorder(ent.stream)
-    with torch.cuda.use_mem_pool(ent.pool, device=dev), rec:
-        run = Run(dev, save=True, need_input_grad=need_dx)
-        xin = Val(x.detach())
-        if not need_dx:
-            run.no_grad_bases.add(id(xin.base))
-        run.begin(module)
-        run.out = module._emit(run, xin)
-        out = run.out.view()
-        if not out.is_contiguous():
-            rec.taint("the node's output is a channel slice")
-            out = out.contiguous()
+    try:
+        with torch.cuda.use_mem_pool(ent.pool, device=dev), rec:
+            run = Run(dev, save=True, need_input_grad=need_dx)
+            xin = Val(x.detach())
+            if not need_dx:
+                run.no_grad_bases.add(id(xin.base))
+            run.begin(module)
+            run.out = module._emit(run, xin)
+            out = run.out.view()
+            if not out.is_contiguous():
+                rec.taint("the node's output is a channel slice")
+                out = out.contiguous()
+    except BaseException as e:
+        _plan_abandon(ent, "recording the forward raised %s" % type(e).__name__)
+        raise
     n, c, t, h, w = x.shape
     ent.x_ptr = x.data_ptr()
     ent.x_span = ((n - 1) * x.stride(0) + c * t * h * w) * x.element_size()
@@ -1333,16 +1371,30 @@ def _record_backward(ent, dout, params):
         static_dout, ent.static_dout = None, None
     run = ent.run
     rec = _plan.Recorder(torch.cuda.current_stream(dev).cuda_stream)
-    with torch.cuda.use_mem_pool(ent.pool, device=dev):
-        if static_dout is None:
-            static_dout = torch.empty(ent.out.shape, dtype=dout.dtype, device=dev)
-            static_dout.copy_(dout)
-        with rec:
-            run.backward(static_dout, defer_join=DEFER_JOIN and ent.defer)
-            dx = run.grads.pop(id(ent.xin.base), None) if ent.need_dx else None
-            grads = tuple(run.param_grads.pop(id(p), None) if p.requires_grad else None for p in params)
-            run.param_grads.clear()
-            run.grads.clear()
+    try:
+        # What autograd is handed -- the parameters' gradients, the input's -- is `.grad` until the caller drops
+        # it, which may be after the next forward (zero_grad() in front of backward; gradient accumulation).  In
+        # ent.pool it would take blocks that temporaries of the forward have given back, and the forward log
+        # would write over it at the next replay: it gets a pool of its own that only the backward log writes to.
+        ent.grad_pool = torch.cuda.MemPool()
+        with torch.cuda.use_mem_pool(ent.grad_pool, device=dev):
+            run.handout = {id(p): torch.empty_like(p) for p in params if p.requires_grad}
+            if ent.need_dx:
+                run.handout[id(ent.xin.base)] = torch.empty_like(ent.xin.base)
+        with torch.cuda.use_mem_pool(ent.pool, device=dev):
+            if static_dout is None:
+                static_dout = torch.empty(ent.out.shape, dtype=dout.dtype, device=dev)
+                static_dout.copy_(dout)
+            with rec:
+                run.backward(static_dout, defer_join=DEFER_JOIN and ent.defer)
+                dx = run.grads.pop(id(ent.xin.base), None) if ent.need_dx else None
+                grads = tuple(run.param_grads.pop(id(p), None) if p.requires_grad else None for p in params)
+                run.param_grads.clear()
+                run.grads.clear()
+        run.handout = None
+    except BaseException as e:
+        _plan_abandon(ent, "recording the backward raised %s" % type(e).__name__)
+        raise
     if rec.plan.stream != ent.stream:
         rec.taint("backward ran on another stream than the forward")
     ent.bwd, ent.dout, ent.grads, ent.dx = rec.plan, static_dout, grads, dx
@@ -1544,11 +1596,12 @@ def run_module(module, x, **kwargs):
     if params is None:
         params = module.__dict__["_coclr_params"] = list(module.parameters())
     if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+        ent = None
         if PLAN:
-            ent = _plan_entry(module, x, params, kwargs)
-            if ent is not None:
+            ent, go = _plan_entry(module, x, params, kwargs)
+            if go:
                 return PlanFn.apply(ent, module, x, *params)
-        return EngineFn.apply(module, kwargs, x, *params)
+        return EngineFn.apply(module, kwargs, ent, x, *params)
     if not _dense5(x):
         x = x.contiguous()
     if PLAN_INFER and not kwargs and _INFER_STORE in module.__dict__:
