@@ -87,27 +87,6 @@ struct ConvArgs {
   int in_relu;
 };
 
-// Which kernel instantiation a planned forward / data-gradient launch runs, and with what launch geometry: the
-// ONE place that decides it (conv3d_fwd_impl launches what this says, coclr_conv3d_fwd_plan reports it).
-enum { FF_IGEMM = 0, FF_WINO_T = 1, FF_WINO_TF = 2, FF_WINO_HW = 3, FF_WINO_HW8 = 4, FF_STEM = 5 };
-struct FwdQuery {
-  bool x16;        // x is 16-byte aligned
-  bool y8;         // y is 8-byte aligned
-  bool n_index, in_affine, slot, bwd_sums;
-};
-struct FwdSel {
-  int family;      // FF_*
-  int form;        // FF_WINO_TF: matrices of the form (6: F(4,3), 5: F(2,4), 9: polyphase stem); 0 otherwise
-  int KT, KH, KW, CC, BM, BN, PCH, OCC;   // template numbers (0: the kernel has none)
-  bool XV4, XG, X16, INAFF, lattice, pairable;
-  // what the launcher derives: the window as the kernel sees it (16-byte-granule forms widen it), tiles, LDS, grid
-  int WW, plane, planeS, mtiles, nchunks, threads;
-  long lds, grid;
-};
-
-// a launcher's own tile / LDS / grid arithmetic against the selection it was called for, BEFORE it launches
-inline bool sel_agrees(const FwdSel* s, const ConvArgs& a, size_t lds, long grid, int threads);
-
 // sum over each 16-lane row (result in every lane of the row)
 __device__ __forceinline__ float row16_sum(float v) {
   v += __builtin_amdgcn_update_dpp(0.f, v, 0xB1, 0xf, 0xf, true);    // quad_perm [1,0,3,2]
@@ -1851,41 +1830,6 @@ conv_wino_hw_kernel(const ConvArgs a, const int total_tiles) {
   flush(std::integral_constant<int, 8>{});
 }
 
-template <int CC, int PCH, bool X16 = false, int ABL = 0>
-int launch_wino_hw(ConvArgs& a, ConvPlan& p, hipStream_t stream, const FwdSel* sel = nullptr) {
-  if (p.WW > 255 || p.WH > 255 || p.WT > 255 || p.lTN > 7) return COCLR_EINVAL;
-  a.mtiles = cdiv(a.Cout, 64);
-  if (X16) {
-    // rows widened to whole 16-byte granules: [2*ow0 - 4, 2*ow0 + 2*TW + 4)
-    const int wwp = 2 * (1 << p.lTW) + 8;
-    a.WW = wwp;
-    a.plane1 = p.WT * p.WH * wwp;
-    a.plane = (a.plane1 << p.lTN) / 4;                 // granules
-    if (a.plane > PCH * 64) return COCLR_EINVAL;
-    a.planeS = cdiv(a.plane, 64) * 256;
-    a.inv_plane1 = 1.0f / (float)(a.plane1 / 4);
-    a.inv_hw = 1.0f / (float)(p.WH * (wwp / 4));
-    a.inv_ww = 1.0f / (float)(wwp / 4);
-  } else {
-    if (p.plane > PCH * 64) return COCLR_EINVAL;
-    a.planeS = cdiv(p.plane, 64) * 64;
-  }
-  a.nchunks = cdiv(a.Cin, CC);
-  const size_t stage = ((size_t)16 * CC * 64 + (size_t)CC * a.planeS) * sizeof(float);
-  // two stages + statistics partials + window coordinate table
-  const size_t lds = 2 * stage + (size_t)2 * 64 * 64 * sizeof(float) + (size_t)PCH * 256 * sizeof(unsigned);
-  if (lds > 160 * 1024) return COCLR_EINVAL;
-  auto kern = conv_wino_hw_kernel<CC, PCH, X16, ABL>;
-  static std::atomic<uint64_t> attr_done{0};
-  COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
-  const long total = (long)a.mtiles * a.ntiles;
-  const int grid = total < kWinoGrid ? (int)total : kWinoGrid;
-  if (!sel_agrees(sel, a, lds, grid, 256)) return (int)hipErrorUnknown;   // launcher and select_forward disagree
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, stream, a, (int)total);
-  COCLR_LAUNCH_CHECK();
-  return 0;
-}
-
 // ------------------------------------------------------------------------------------
 // The same F(2x2,3x3) convolution with TWO waves per SIMD (round 4).
 //
@@ -2312,47 +2256,6 @@ conv_wino_hw8_kernel(const ConvArgs a, const int total_tiles) {
   else run_tiles(std::false_type{});
 }
 
-template <int CC, int PCH>
-int launch_wino_hw8(ConvArgs& a, ConvPlan& p, hipStream_t stream, const FwdSel* sel = nullptr) {
-  if (p.WW > 255 || p.WH > 255 || p.WT > 255 || p.lTN > 7 || a.Cin % CC) return COCLR_EINVAL;
-  a.mtiles = cdiv(a.Cout, 64);
-  const int wwp = 2 * (1 << p.lTW) + 8;
-  a.WW = wwp;
-  a.plane1 = p.WT * p.WH * wwp;
-  a.plane = (a.plane1 << p.lTN) / 4;                 // granules
-  if (a.plane > PCH * 64) return COCLR_EINVAL;
-  // + 32 floats: the four channel planes a patch read touches sit half the banks apart
-  a.planeS = cdiv(a.plane, 64) * 256 + 32;
-  a.inv_plane1 = 1.0f / (float)(a.plane1 / 4);
-  a.inv_hw = 1.0f / (float)(p.WH * (wwp / 4));
-  a.inv_ww = 1.0f / (float)(wwp / 4);
-  a.nchunks = a.Cin / CC;
-  const size_t stage = ((size_t)16 * CC * 64 + (size_t)CC * a.planeS) * sizeof(float);
-  const size_t lds = 2 * stage + (size_t)2 * 64 * 64 * sizeof(float) + (size_t)PCH * 64 * sizeof(unsigned);
-  if (lds > 160 * 1024) return COCLR_EINVAL;
-  auto kern = conv_wino_hw8_kernel<CC, PCH>;
-#ifdef COCLR_WINO_ABLATE
-  {
-    static const int abl = getenv("COCLR_W8_ABL") ? atoi(getenv("COCLR_W8_ABL")) : 0;
-    if (abl == 1) kern = conv_wino_hw8_kernel<CC, PCH, 1>;
-    if (abl == 2) kern = conv_wino_hw8_kernel<CC, PCH, 2>;
-    if (abl == 3) kern = conv_wino_hw8_kernel<CC, PCH, 3>;
-    if (abl == 4) kern = conv_wino_hw8_kernel<CC, PCH, 4>;
-    if (abl == 7) kern = conv_wino_hw8_kernel<CC, PCH, 7>;
-    if (abl) hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 160 * 1024);
-  }
-#endif
-  static std::atomic<uint64_t> attr_done{0};
-  COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
-  const long total = (long)a.mtiles * a.ntiles;
-  const int grid = total < kWinoGrid ? (int)total : kWinoGrid;
-  if (!sel_agrees(sel, a, lds, grid, 512)) return (int)hipErrorUnknown;   // launcher and select_forward disagree
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, stream, a, (int)total);
-  COCLR_LAUNCH_CHECK();
-  return 0;
-}
-
 // ------------------------------------------------------------------------------------
 // Stem kernel: spatial (1,KH,KW) stencil over a handful of input channels (Cin = 3:
 // backbone/s3dg.py:145 Conv_1a.conv1, and the five slices of resnet_2d3d.py:138).
@@ -2671,27 +2574,6 @@ conv_stem_kernel(const ConvArgs a, const int nboxes) {
 
 constexpr int kStemGrid = 512;   // persistent workgroups of the stem kernel (2 per CU)
 
-template <int KH, int KW, int CIN, int PCH>
-int launch_stem(ConvArgs& a, ConvPlan& p, hipStream_t stream, const FwdSel* sel = nullptr) {
-  constexpr int KROWS = CIN * KH * ((KW + 1) & ~1);
-  constexpr int W_FLOATS = ((KROWS * 64 + 255) / 256) * 256;
-  if (p.plane > PCH * 64 || a.Cin != CIN) return COCLR_EINVAL;
-  if (p.WT > 255 || p.WH > 255 || p.WW > 255 || (1 << p.lTN) > 255) return COCLR_EINVAL;
-  a.mtiles = cdiv(a.Cout, 64);
-  a.planeS = cdiv(p.plane, 64) * 64;
-  a.nchunks = 1;
-  const size_t lds = ((size_t)W_FLOATS + 2 * (size_t)CIN * a.planeS) * sizeof(float);
-  if (lds > 160 * 1024) return COCLR_EINVAL;
-  auto kern = conv_stem_kernel<KH, KW, CIN, PCH>;
-  static std::atomic<uint64_t> attr_done{0};
-  COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
-  if (!sel_agrees(sel, a, lds, (long)a.ntiles * a.mtiles, 256)) return (int)hipErrorUnknown;   // launcher and select_forward disagree
-  hipLaunchKernelGGL(kern, dim3((unsigned)a.ntiles, (unsigned)a.mtiles), dim3(256), lds, stream, a,
-                     p.nboxes);
-  COCLR_LAUNCH_CHECK();
-  return 0;
-}
-
 // Weight re-layout:  dst[tap][r][c]  (r < RP rows = reduction channels,
 // c < CP = produced channels), zero padded.
 //   forward : r = cin,  c = cout, src tap = tap_base + tap*tap_step
@@ -2854,26 +2736,18 @@ inline int granule_count(const ConvPlan& p) {
   return ((p.WT * p.WH * ((1 << p.lTW) + 8)) << p.lTN) / 4;
 }
 
-// A launch that coclr_conv3d_fwd_multi may fuse with its neighbour: the launcher fills the slot instead of
-// launching; two slots with the same `single` function are the same kernel variant.
+// ---- launching ------------------------------------------------------------------------------------------------
+// A launcher takes the ConvArgs, grid and LDS bytes the selection worked out (select_forward, apply) and does three
+// things: raise the kernel's dynamic-LDS limit once, launch, check.
 typedef int (*SingleFn)(const ConvArgs&, long, size_t, hipStream_t);
 typedef int (*PairFn)(const ConvArgs&, const ConvArgs&, long, long, size_t, hipStream_t);
-struct PairSlot {
-  ConvArgs args;
-  long blocks;
-  size_t lds;
-  SingleFn single;
-  PairFn pair;
-  bool pending;
-};
 
-// Raise the dynamic-LDS limit of kernel `Kern` once, launch it on 256-thread blocks, check.  One instantiation,
-// hence one `attr_done` flag, per kernel.
-template <auto Kern, typename... Args>
-int launch_dyn_lds(long blocks, size_t lds, hipStream_t stream, const Args&... args) {
+// One instantiation, hence one `attr_done` flag, per kernel.
+template <auto Kern, int THREADS, typename... Args>
+int launch_dyn_lds(dim3 grid, size_t lds, hipStream_t stream, const Args&... args) {
   static std::atomic<uint64_t> attr_done{0};
   COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(Kern), 160 * 1024, attr_done));
-  hipLaunchKernelGGL(Kern, dim3((unsigned)blocks), dim3(256), lds, stream, args...);
+  hipLaunchKernelGGL(Kern, grid, dim3(THREADS), lds, stream, args...);
   COCLR_LAUNCH_CHECK();
   return 0;
 }
@@ -2881,12 +2755,25 @@ int launch_dyn_lds(long blocks, size_t lds, hipStream_t stream, const Args&... a
 // the SingleFn / PairFn of a kernel: one function per kernel, so comparing pointers compares kernel variants
 template <auto Kern>
 int launch_single(const ConvArgs& a, long blocks, size_t lds, hipStream_t stream) {
-  return launch_dyn_lds<Kern>(blocks, lds, stream, a);
+  return launch_dyn_lds<Kern, 256>(dim3((unsigned)blocks), lds, stream, a);
 }
 
 template <auto Kern>
 int launch_pair(const ConvArgs& a0, const ConvArgs& a1, long b0, long b1, size_t lds, hipStream_t stream) {
-  return launch_dyn_lds<Kern>(b0 + b1, lds, stream, a0, a1, (int)b0);
+  return launch_dyn_lds<Kern, 256>(dim3((unsigned)(b0 + b1)), lds, stream, a0, a1, (int)b0);
+}
+
+// the persistent F(2x2,3x3) kernels walk all (cout tile, box) pairs from a grid of at most kWinoGrid workgroups
+template <auto Kern, int THREADS>
+int launch_persistent(const ConvArgs& a, long grid, size_t lds, hipStream_t stream) {
+  return launch_dyn_lds<Kern, THREADS>(dim3((unsigned)grid), lds, stream, a, (int)((long)a.mtiles * a.ntiles));
+}
+
+// the stem kernel: a.ntiles persistent workgroups per cout tile walk the boxes
+template <auto Kern>
+int launch_stem(const ConvArgs& a, long, size_t lds, hipStream_t stream) {
+  return launch_dyn_lds<Kern, 256>(dim3((unsigned)a.ntiles, (unsigned)a.mtiles), lds, stream, a,
+                                   a.nbw * a.nbh * a.nbt * a.nbn);
 }
 
 // Two DIFFERENT variants of the (1,3,3) small-map kernel in one launch: on the first 8x8x8 blocks the wide
@@ -2901,104 +2788,188 @@ conv_igemm_133_mixed_kernel(const ConvArgs a0, const ConvArgs a1, const int nb0)
     conv_igemm_body<1, 3, 3, 8, 64, BNB, 3, false, true>(a1, (int)blockIdx.x - nb0, (int)gridDim.x - nb0);
 }
 
+// ---- the kernel table -----------------------------------------------------------------------------------------
+// A row is one kernel instantiation: the numbers coclr_conv3d_fwd_plan reports about it and the functions that
+// launch it.  Rows are only ever built by the *_row<...>() templates below, from the SAME template arguments for
+// both, so what is reported is what runs.
+enum { FF_IGEMM = 0, FF_WINO_T = 1, FF_WINO_TF = 2, FF_WINO_HW = 3, FF_WINO_HW8 = 4, FF_STEM = 5 };
+struct KernelRow {
+  int family;      // FF_*
+  int form;        // FF_WINO_TF: matrices of the form (6: F(4,3), 5: F(2,4), 9: polyphase stem); 0 otherwise
+  int KT, KH, KW, CC, BM, BN, PCH, OCC;   // template numbers (0: the kernel has none)
+  bool XV4, XG, X16, INAFF;
+  int threads;
+  SingleFn single;
+  PairFn pair;     // nullptr: the kernel has no pair form
+};
+
+// pair kernels exist for the stencils sibling units of an inception block share: (1,3,3) of the two
+// separable branches, 16-byte-staged (1,1,1) of the fused heads and the pool branch
+template <int KT, int KH, int KW, int CC, int BM, int BN, int PCH, bool XV4 = false, bool XG = false>
+constexpr KernelRow igemm_row() {
+  PairFn pair = nullptr;
+  if constexpr (KT == 1 && ((KH == 3 && KW == 3) || (KH == 1 && KW == 1 && XV4)))
+    pair = &launch_pair<conv_igemm_pair_kernel<KT, KH, KW, CC, BM, BN, PCH, XV4, XG>>;
+  return {FF_IGEMM, 0, KT, KH, KW, CC, BM, BN, PCH, 0, XV4, XG, false, false, 256,
+          &launch_single<conv_igemm_kernel<KT, KH, KW, CC, BM, BN, PCH, XV4, XG>>, pair};
+}
+
+// (the pair kernels of the 4-byte forms of F(2,3) and F(4,3) are built with their rows but never selected:
+// select_forward pairs these families only under 16-byte staging)
+template <int CC, int BM, int BNP, int PCH, bool XV4, int OCC = 1>
+constexpr KernelRow wino_t_row() {
+  return {FF_WINO_T, 0, 3, 1, 1, CC, BM, BNP, PCH, OCC, XV4, false, false, false, 256,
+          &launch_single<conv_wino_t_kernel<CC, BM, BNP, PCH, XV4, OCC>>,
+          &launch_pair<conv_wino_t_pair_kernel<CC, BM, BNP, PCH, XV4, OCC>>};
+}
+
+// the temporal Winograd family (conv_wino_tf_body) on a KT-tap stencil: Form::TAPS weight matrices per stage
+template <typename Form, int KT, int CC, int BM, int BNQ, int PCH, bool XV4, int OCC, bool INAFF = false>
+constexpr KernelRow wino_tf_row() {
+  PairFn pair = nullptr;
+  if constexpr (Form::PAIR && !INAFF)
+    pair = &launch_pair<conv_wino_tf_pair_kernel<Form, CC, BM, BNQ, PCH, XV4, OCC>>;
+  return {FF_WINO_TF, Form::TAPS, KT, 1, 1, CC, BM, BNQ, PCH, OCC, XV4, false, false, INAFF, 256,
+          &launch_single<conv_wino_tf_kernel<Form, CC, BM, BNQ, PCH, XV4, OCC, INAFF>>, pair};
+}
+
+template <int CC, int PCH, bool X16 = false>
+constexpr KernelRow wino_hw_row() {
+  return {FF_WINO_HW, 0, 1, 3, 3, CC, 64, 64, PCH, 0, false, false, X16, false, 256,
+          &launch_persistent<conv_wino_hw_kernel<CC, PCH, X16>, 256>, nullptr};
+}
+
+template <int CC, int PCH>
+constexpr KernelRow wino_hw8_row() {
+  return {FF_WINO_HW8, 0, 1, 3, 3, CC, 64, 64, PCH, 0, false, false, true, false, 512,
+          &launch_persistent<conv_wino_hw8_kernel<CC, PCH>, 512>, nullptr};
+}
+
+template <int KH, int KW, int CIN, int PCH>
+constexpr KernelRow stem_row() {
+  return {FF_STEM, 0, 1, KH, KW, CIN, 64, 128, PCH, 0, false, false, false, false, 256,
+          &launch_stem<conv_stem_kernel<KH, KW, CIN, PCH>>, nullptr};
+}
+
+// What plan_forward picks from the geometry alone; coclr_conv3d_fwd_plan reports these numbers.
+enum FwdVariant {
+  V_PW_128x128 = 0, V_PW_64x128 = 1, V_PW_64x64 = 2,   // (1,1,1), stride 1, undilated (choose_tile)
+  V_PW_STRIDED = 3,                                    // (1,1,1), strided or dilated
+  V_S_128x128 = 10, V_S_64x128 = 11, V_S_64x64 = 12,   // (1,3,3) (choose_tile)
+  V_S_64x64_WIDE = 13,                                 // (1,3,3), 64x64 tile whose window exceeds 256 floats
+  V_T3_128x128 = 20, V_T3_64x128 = 21, V_T3_64x64 = 22,// (3,1,1) (choose_tile)
+  V_T4 = 25,                                           // (4,1,1)
+  V_S7 = 30,                                           // (1,7,7), chunked
+  V_STEM = 31,                                         // (1,7,7) of 3 channels: the persistent stem kernel
+  V_T7 = 40,                                           // (7,1,1)
+  V_POLY7 = 41,                                        // (7,1,1) stride 2, polyphase Winograd form
+  V_F23 = 50, V_F43 = 51, V_F24 = 52,                  // temporal Winograd F(2,3), F(4,3), F(2,4)
+  V_F2X2 = 60,                                         // Winograd F(2x2,3x3)
+};
+
+// which row of a variant: its 4-byte-staged kernel, its 16-byte-staged one (XV4 / XG / X16), and what only one
+// variant has
+enum { ALT_4B = 0, ALT_16B = 1,
+       ALT_INAFF = 2,                                  // V_POLY7: + ALT_4B / ALT_16B
+       ALT_HW_PCH10 = 2, ALT_HW8 = 3 };                // V_F2X2: ALT_4B is the 6-piece window, ALT_16B one wave
+
+// THE table: every forward / data-gradient kernel of the library, the rows of a variant adjacent and in ALT order.
+//
+// 16-byte-staged kernels run with HALF the channel chunk of their 4-byte forms: the chunk is what
+// sizes the LDS stages, and two or three workgroups per CU became five or six.  Measured at B=32
+// (same box, alternating): Conv_2b 0.082 -> 0.070 ms forward / 0.070 -> 0.059 data gradient, the
+// fused heads of Mixed_3c 0.223 -> 0.20 / 0.19 -> 0.195, of Mixed_4b 0.058 -> 0.054 / 0.060 ->
+// 0.051, Conv_1a.conv2 1.36 -> 1.31; the (1,3,3) small-map kernel did not move and keeps 8.
+//
+// F(2,3) under 16-byte staging: 8-channel chunks and a four-workgroups-per-CU register budget (accumulators in
+// arch VGPRs, 99 registers; 27 KB of LDS): four waves per SIMD instead of three.  Measured at B=32 against
+// the 16-channel / three-wave form: Conv_2c.conv2 1.02-1.06 -> 0.99 ms forward, 0.907 -> 0.874
+// data gradient; Mixed_3c.b1.conv2 0.212 -> 0.204 / 0.205 -> 0.200; the 8x8x8 layers unchanged.
+struct FwdTableRow { int variant, alt; KernelRow k; };
+constexpr FwdTableRow kFwdTable[] = {
+    {V_PW_128x128, ALT_4B, igemm_row<1, 1, 1, 32, 128, 128, 2>()},
+    {V_PW_128x128, ALT_16B, igemm_row<1, 1, 1, 32, 128, 128, 2, true>()},
+    {V_PW_64x128, ALT_4B, igemm_row<1, 1, 1, 32, 64, 128, 2>()},
+    {V_PW_64x128, ALT_16B, igemm_row<1, 1, 1, 16, 64, 128, 2, true>()},
+    {V_PW_64x64, ALT_4B, igemm_row<1, 1, 1, 32, 64, 64, 1>()},
+    {V_PW_64x64, ALT_16B, igemm_row<1, 1, 1, 16, 64, 64, 1, true>()},
+    {V_PW_STRIDED, ALT_4B, igemm_row<1, 1, 1, 16, 64, 64, 4>()},
+    {V_S_128x128, ALT_4B, igemm_row<1, 3, 3, 4, 128, 128, 4>()},
+    {V_S_128x128, ALT_16B, igemm_row<1, 3, 3, 4, 128, 128, 3, false, true>()},
+    {V_S_64x128, ALT_4B, igemm_row<1, 3, 3, 8, 64, 128, 4>()},
+    {V_S_64x128, ALT_16B, igemm_row<1, 3, 3, 8, 64, 128, 3, false, true>()},
+    {V_S_64x64, ALT_4B, igemm_row<1, 3, 3, 8, 64, 64, 4>()},
+    {V_S_64x64, ALT_16B, igemm_row<1, 3, 3, 8, 64, 64, 3, false, true>()},
+    {V_S_64x64_WIDE, ALT_4B, igemm_row<1, 3, 3, 8, 64, 64, 8>()},
+    {V_S_64x64_WIDE, ALT_16B, igemm_row<1, 3, 3, 8, 64, 64, 3, false, true>()},
+    {V_T3_128x128, ALT_4B, igemm_row<3, 1, 1, 4, 128, 128, 4>()},
+    {V_T3_128x128, ALT_16B, igemm_row<3, 1, 1, 4, 128, 128, 4, true>()},
+    {V_T3_64x128, ALT_4B, igemm_row<3, 1, 1, 8, 64, 128, 4>()},
+    {V_T3_64x128, ALT_16B, igemm_row<3, 1, 1, 8, 64, 128, 4, true>()},
+    {V_T3_64x64, ALT_4B, igemm_row<3, 1, 1, 8, 64, 64, 4>()},
+    {V_T3_64x64, ALT_16B, igemm_row<3, 1, 1, 8, 64, 64, 4, true>()},
+    {V_T4, ALT_4B, igemm_row<4, 1, 1, 8, 64, 128, 4>()},
+    {V_T4, ALT_16B, igemm_row<4, 1, 1, 8, 64, 128, 4, true>()},
+    {V_S7, ALT_4B, igemm_row<1, 7, 7, 4, 64, 128, 20>()},
+    {V_STEM, ALT_4B, stem_row<7, 7, 3, 20>()},
+    {V_T7, ALT_4B, igemm_row<7, 1, 1, 8, 64, 128, 8>()},
+    {V_T7, ALT_16B, igemm_row<7, 1, 1, 4, 64, 128, 8, true>()},
+    {V_POLY7, ALT_4B, wino_tf_row<StemPoly7, 7, 8, 64, 64, 6, false, 2>()},
+    {V_POLY7, ALT_16B, wino_tf_row<StemPoly7, 7, 8, 64, 64, 6, true, 2>()},
+    {V_POLY7, ALT_INAFF + ALT_4B, wino_tf_row<StemPoly7, 7, 8, 64, 64, 6, false, 2, true>()},
+    {V_POLY7, ALT_INAFF + ALT_16B, wino_tf_row<StemPoly7, 7, 8, 64, 64, 6, true, 2, true>()},
+    {V_F23, ALT_4B, wino_t_row<16, 64, 64, 4, false>()},
+    {V_F23, ALT_16B, wino_t_row<8, 64, 64, 4, true, 4>()},
+    {V_F43, ALT_4B, wino_tf_row<WinoF43, 3, 8, 64, 64, 6, false, 3>()},
+    {V_F43, ALT_16B, wino_tf_row<WinoF43, 3, 8, 64, 64, 6, true, 3>()},
+    {V_F24, ALT_4B, wino_tf_row<WinoF24, 4, 8, 64, 64, 4, false, 3>()},
+    {V_F24, ALT_16B, wino_tf_row<WinoF24, 4, 8, 64, 64, 4, true, 3>()},
+    {V_F2X2, ALT_4B, wino_hw_row<8, 6>()},
+    {V_F2X2, ALT_16B, wino_hw_row<8, 3, true>()},
+    {V_F2X2, ALT_HW_PCH10, wino_hw_row<8, 10>()},
+    {V_F2X2, ALT_HW8, wino_hw8_row<8, 3>()},
+};
+constexpr int kFwdRows = sizeof(kFwdTable) / sizeof(kFwdTable[0]);
+
+// variant -> index of its first row, worked out once by the compiler: a lookup indexes, it never searches
+struct FwdIndex { signed char first[64]; bool ordered; };
+constexpr FwdIndex index_fwd_table() {
+  FwdIndex ix{};
+  ix.ordered = true;
+  for (int i = 0; i < kFwdRows; ++i) {
+    const bool opens = i == 0 || kFwdTable[i].variant != kFwdTable[i - 1].variant;
+    if (opens) ix.first[kFwdTable[i].variant] = (signed char)i;
+    if (kFwdTable[i].alt != i - ix.first[kFwdTable[i].variant]) ix.ordered = false;
+  }
+  return ix;
+}
+constexpr FwdIndex kFwdIndex = index_fwd_table();
+static_assert(kFwdIndex.ordered, "kFwdTable: the rows of a variant are adjacent, their alt counts from 0");
+
+inline const KernelRow* fwd_row(int variant, int alt) {
+  const int i = kFwdIndex.first[variant] + alt;
+  return i < kFwdRows && kFwdTable[i].variant == variant ? &kFwdTable[i].k : nullptr;
+}
+
+// Two DIFFERENT rows of the (1,3,3) small-map kernel in one launch (conv_igemm_133_mixed_kernel)
 inline PairFn mixed_pair(SingleFn f0, SingleFn f1) {
-  const SingleFn wide = &launch_single<conv_igemm_kernel<1, 3, 3, 8, 64, 128, 3, false, true>>;
-  const SingleFn narrow = &launch_single<conv_igemm_kernel<1, 3, 3, 8, 64, 64, 3, false, true>>;
+  constexpr SingleFn wide = igemm_row<1, 3, 3, 8, 64, 128, 3, false, true>().single;
+  constexpr SingleFn narrow = igemm_row<1, 3, 3, 8, 64, 64, 3, false, true>().single;
   if (f0 == wide && f1 == narrow) return &launch_pair<conv_igemm_133_mixed_kernel<128, 64>>;
   if (f0 == narrow && f1 == wide) return &launch_pair<conv_igemm_133_mixed_kernel<64, 128>>;
   return nullptr;
 }
 
-template <int KT, int KH, int KW, int CC, int BM, int BN, int PCH, bool XV4 = false, bool XG = false>
-int launch_variant(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot = nullptr,
-                   const FwdSel* sel = nullptr) {
-  constexpr int TAPS = KT * KH * KW;
-  a.mtiles = cdiv(a.Cout, BM);
-  if (XG) {
-    const int wwp = (1 << p.lTW) + 8;
-    a.WW = wwp;
-    a.plane1 = p.WT * p.WH * wwp;
-    a.plane = (a.plane1 << p.lTN) / 4;
-    if (a.plane > PCH * 64) return COCLR_EINVAL;
-    a.planeS = cdiv(a.plane, 64) * 256;
-    a.inv_plane1 = 1.0f / (float)(a.plane1 / 4);
-    a.inv_hw = 1.0f / (float)(p.WH * (wwp / 4));
-    a.inv_ww = 1.0f / (float)(wwp / 4);
-  } else {
-    if (p.plane > PCH * 64) return COCLR_EINVAL;
-    a.planeS = XV4 ? p.plane : cdiv(p.plane, 64) * 64;    // 16-byte staging packs rows back to back
-  }
-  a.nchunks = cdiv(a.Cin, CC);
-  const size_t stage = ((size_t)TAPS * CC * BM + (size_t)CC * a.planeS) * sizeof(float);
-  const size_t lds_main = stage * (a.nchunks > 1 ? 2 : 1);
-  const size_t lds_red = (size_t)4 * BM * 2 * sizeof(float);
-  const size_t lds = lds_main > lds_red ? lds_main : lds_red;
-  if (lds > 160 * 1024) return COCLR_EINVAL;
-  const long blocks = (long)a.mtiles * a.ntiles;
-  if (!sel_agrees(sel, a, lds, blocks, 256)) return (int)hipErrorUnknown;   // launcher and select_forward disagree
-  // pair kernels exist for the stencils sibling units of an inception block share: (1,3,3) of the two
-  // separable branches, 16-byte-staged (1,1,1) of the fused heads and the pool branch
-  constexpr bool PAIRABLE = KT == 1 && ((KH == 3 && KW == 3) || (KH == 1 && KW == 1 && XV4));
-  if (slot && PAIRABLE) {
-    slot->args = a; slot->blocks = blocks; slot->lds = lds; slot->pending = true;
-    slot->single = &launch_single<conv_igemm_kernel<KT, KH, KW, CC, BM, BN, PCH, XV4, XG>>;
-    if constexpr (PAIRABLE) slot->pair = &launch_pair<conv_igemm_pair_kernel<KT, KH, KW, CC, BM, BN, PCH, XV4, XG>>;
-    return 0;
-  }
-  return launch_single<conv_igemm_kernel<KT, KH, KW, CC, BM, BN, PCH, XV4, XG>>(a, blocks, lds, stream);
-}
-
-template <int CC, int BM, int BNP, int PCH, bool XV4, int OCC = 1>
-int launch_wino_t(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot = nullptr,
-                  const FwdSel* sel = nullptr) {
-  if (p.plane > PCH * 64) return COCLR_EINVAL;
-  a.mtiles = cdiv(a.Cout, BM);
-  // 16-byte staging packs the channel rows back to back
-  a.planeS = XV4 ? p.plane : cdiv(p.plane, 64) * 64;
-  a.nchunks = cdiv(a.Cin, CC);
-  const size_t stage = ((size_t)4 * CC * BM + (size_t)CC * a.planeS) * sizeof(float);
-  const size_t lds_main = stage * (a.nchunks > 1 ? 2 : 1);
-  const size_t lds_red = (size_t)4 * BM * 2 * sizeof(float);
-  const size_t lds = lds_main > lds_red ? lds_main : lds_red;
-  if (lds > 160 * 1024) return COCLR_EINVAL;
-  const long blocks = (long)a.mtiles * a.ntiles;
-  if (!sel_agrees(sel, a, lds, blocks, 256)) return (int)hipErrorUnknown;   // launcher and select_forward disagree
-  if (slot) {
-    slot->args = a; slot->blocks = blocks; slot->lds = lds; slot->pending = true;
-    slot->single = &launch_single<conv_wino_t_kernel<CC, BM, BNP, PCH, XV4, OCC>>;
-    slot->pair = &launch_pair<conv_wino_t_pair_kernel<CC, BM, BNP, PCH, XV4, OCC>>;
-    return 0;
-  }
-  return launch_single<conv_wino_t_kernel<CC, BM, BNP, PCH, XV4, OCC>>(a, blocks, lds, stream);
-}
-
-// the temporal Winograd family (conv_wino_tf_body): Form::TAPS weight matrices per stage, the affine table of
-// INAFF behind the stages; a slot is filled only where the form has a pair kernel
-template <typename Form, int CC, int BM, int BNQ, int PCH, bool XV4, int OCC, bool INAFF = false>
-int launch_wino_tf(ConvArgs& a, ConvPlan& p, hipStream_t stream, PairSlot* slot = nullptr,
-                   const FwdSel* sel = nullptr) {
-  if (p.plane > PCH * 64) return COCLR_EINVAL;
-  a.mtiles = cdiv(a.Cout, BM);
-  a.planeS = XV4 ? p.plane : cdiv(p.plane, 64) * 64;
-  a.nchunks = cdiv(a.Cin, CC);
-  const size_t stage = ((size_t)Form::TAPS * CC * BM + (size_t)CC * a.planeS) * sizeof(float);
-  const size_t lds_main = stage * (a.nchunks > 1 ? 2 : 1) + (INAFF ? (size_t)2 * a.CinP * sizeof(float) : 0);
-  const size_t lds_red = (size_t)4 * BM * 2 * sizeof(float);
-  const size_t lds = lds_main > lds_red ? lds_main : lds_red;
-  if (lds > 160 * 1024) return COCLR_EINVAL;
-  const long blocks = (long)a.mtiles * a.ntiles;
-  if (!sel_agrees(sel, a, lds, blocks, 256)) return (int)hipErrorUnknown;   // launcher and select_forward disagree
-  constexpr SingleFn single = &launch_single<conv_wino_tf_kernel<Form, CC, BM, BNQ, PCH, XV4, OCC, INAFF>>;
-  if constexpr (Form::PAIR && !INAFF) {
-    if (slot) {
-      slot->args = a; slot->blocks = blocks; slot->lds = lds; slot->pending = true;
-      slot->single = single;
-      slot->pair = &launch_pair<conv_wino_tf_pair_kernel<Form, CC, BM, BNQ, PCH, XV4, OCC>>;
-      return 0;
-    }
-  }
-  return single(a, blocks, lds, stream);
-}
+// A launch that coclr_conv3d_fwd_multi may fuse with its neighbour: conv3d_fwd_impl fills the slot instead of
+// launching; two slots with the same `single` function are the same kernel.
+struct PairSlot {
+  ConvArgs args;
+  long blocks;
+  size_t lds;
+  SingleFn single;
+  PairFn pair;
+  bool pending;
+};
 
 // efficiency of covering Cout with tiles of BM rows
 inline double cover(int cout, int bm) { return (double)cout / ((double)cdiv(cout, bm) * bm); }
@@ -3142,11 +3113,11 @@ int plan_forward(const coclr_conv_desc* d, ConvPlan* p, int* variant) {
     if (plain) {
       c = choose_tile(*p, 1, 1, 1, true, true, 128, 64);
       conv_pick_box(p, c.lbn, 1, 1, 1);
-      *variant = c.lbn == 6 ? 2 : (c.bm == 128 ? 0 : 1);
+      *variant = c.lbn == 6 ? V_PW_64x64 : (c.bm == 128 ? V_PW_128x128 : V_PW_64x128);
     } else {
       conv_pick_box(p, 6, 1, 1, 1);
       if (p->plane > 256) return COCLR_EINVAL;
-      *variant = 3;
+      *variant = V_PW_STRIDED;
     }
   } else if (kt == 1 && kh == 3 && kw == 3 && d->algo == 1) {
     // Winograd F(2x2,3x3): plan over 2x2 output blocks as a (1,4,4) stencil with stride (1,2,2)
@@ -3158,12 +3129,12 @@ int plan_forward(const coclr_conv_desc* d, ConvPlan* p, int* variant) {
     p->sh = p->sw = 2;
     conv_pick_box(p, 6, 1, 4, 4);
     if (p->plane > 640) return COCLR_EINVAL;
-    *variant = 60;
+    *variant = V_F2X2;
   } else if (kt == 1 && kh == 3 && kw == 3) {
     c = choose_tile(*p, 1, 3, 3, true, true, 256, 512);
     conv_pick_box(p, c.lbn, 1, 3, 3);
-    if (c.lbn == 6) *variant = p->plane <= 256 ? 12 : 13;
-    else *variant = c.bm == 128 ? 10 : 11;
+    if (c.lbn == 6) *variant = p->plane <= 256 ? V_S_64x64 : V_S_64x64_WIDE;
+    else *variant = c.bm == 128 ? V_S_128x128 : V_S_64x128;
   } else if (kt == 3 && kh == 1 && kw == 1 && d->algo == 2) {
     // temporal Winograd F(4,3): plan over frame QUADS as a (6,1,1) stencil with stride 4
     if (!(p->st == 1 && p->sh == 1 && p->sw == 1 && p->pt == 1 && p->dt == 1 && p->dh == 1 &&
@@ -3174,7 +3145,7 @@ int plan_forward(const coclr_conv_desc* d, ConvPlan* p, int* variant) {
     p->st = 4;
     conv_pick_box(p, 6, 6, 1, 1);
     if (p->plane > 384) return COCLR_EINVAL;
-    *variant = 51;
+    *variant = V_F43;
   } else if (kt == 3 && kh == 1 && kw == 1 && d->algo == 1) {
     // temporal Winograd F(2,3): plan over frame PAIRS as a (4,1,1) stencil with stride 2
     if (!(p->st == 1 && p->sh == 1 && p->sw == 1 && p->pt == 1 && p->dt == 1 && p->dh == 1 &&
@@ -3184,11 +3155,11 @@ int plan_forward(const coclr_conv_desc* d, ConvPlan* p, int* variant) {
     p->st = 2;
     conv_pick_box(p, 6, 4, 1, 1);
     if (p->plane > 256) return COCLR_EINVAL;
-    *variant = 50;
+    *variant = V_F23;
   } else if (kt == 3 && kh == 1 && kw == 1) {
     c = choose_tile(*p, 3, 1, 1, true, true, 256, 256);
     conv_pick_box(p, c.lbn, 3, 1, 1);
-    *variant = c.lbn == 6 ? 22 : (c.bm == 128 ? 20 : 21);
+    *variant = c.lbn == 6 ? V_T3_64x64 : (c.bm == 128 ? V_T3_128x128 : V_T3_64x128);
   } else if (kt == 4 && kh == 1 && kw == 1 && d->algo == 2) {
     // 4-tap temporal stencil through F(2,4): plan over frame PAIRS as a (5,1,1) stencil with stride 2
     if (!(p->st == 1 && p->sh == 1 && p->sw == 1 && p->pt == 1 && p->dt == 1 && p->dh == 1 &&
@@ -3199,16 +3170,16 @@ int plan_forward(const coclr_conv_desc* d, ConvPlan* p, int* variant) {
     p->st = 2;
     conv_pick_box(p, 6, 5, 1, 1);
     if (p->plane > 256) return COCLR_EINVAL;
-    *variant = 52;
+    *variant = V_F24;
   } else if (kt == 4 && kh == 1 && kw == 1) {
     conv_pick_box(p, 7, 4, 1, 1);
-    *variant = 25;
+    *variant = V_T4;
   } else if (kt == 1 && kh == 7 && kw == 7) {
     conv_pick_box(p, 7, 1, 7, 7);
-    *variant = 30;
+    *variant = V_S7;
     if (p->Cin == 3 && p->dt == 1 && p->dh == 1 && p->dw == 1 && p->plane <= 20 * 64 &&
         p->WT <= 255 && p->WH <= 255 && p->WW <= 255) {
-      *variant = 31;     // persistent stem kernel: one statistics partial per workgroup
+      *variant = V_STEM;     // persistent stem kernel: one statistics partial per workgroup
       if (p->ntiles > kStemGrid) p->ntiles = kStemGrid;
     }
   } else if (kt == 7 && kh == 1 && kw == 1 && d->algo == 1) {
@@ -3221,14 +3192,19 @@ int plan_forward(const coclr_conv_desc* d, ConvPlan* p, int* variant) {
     p->st = 4;
     conv_pick_box(p, 6, 9, 1, 1);
     if (p->plane > 384) return COCLR_EINVAL;
-    *variant = 41;
+    *variant = V_POLY7;
   } else if (kt == 7 && kh == 1 && kw == 1) {
     conv_pick_box(p, 7, 7, 1, 1);
-    *variant = 40;
+    *variant = V_T7;
   } else {
     return COCLR_EINVAL;
   }
   return 0;
+}
+
+// the variants whose epilogue forms the backward sums of a BatchNorm unit
+inline bool bwd_sums_variant(int variant) {
+  return variant != V_F2X2 && variant != V_STEM && variant != V_F43 && variant != V_F24 && variant != V_POLY7;
 }
 
 }  // namespace
@@ -3247,104 +3223,133 @@ extern "C" int coclr_conv3d_bwd_sums_ok(const coclr_conv_desc* d, int* ok) {
   int v;
   int rc = plan_forward(d, &p, &v);
   if (rc) return rc;
-  *ok = (v != 60 && v != 31 && v != 51 && v != 52 && v != 41) ? 1 : 0;
+  *ok = bwd_sums_variant(v) ? 1 : 0;
   return 0;
 }
 
 namespace {
 
-inline bool bwd_sums_variant(int variant) {
-  return variant != 60 && variant != 31 && variant != 51 && variant != 52 && variant != 41;
-}
-
-inline bool sel_agrees(const FwdSel* s, const ConvArgs& a, size_t lds, long grid, int threads) {
-  return !s || (a.mtiles == s->mtiles && a.nchunks == s->nchunks && a.planeS == s->planeS && a.WW == s->WW &&
-                a.plane == s->plane && (long)lds == s->lds && grid == s->grid && threads == s->threads);
-}
+// Which kernel a planned forward / data-gradient launch runs, and with what launch geometry: the ONE place that
+// decides it (conv3d_fwd_impl applies and launches what this says, coclr_conv3d_fwd_plan reports it).
+struct FwdQuery {
+  bool x16;        // x is 16-byte aligned
+  bool y8;         // y is 8-byte aligned
+  bool n_index, in_affine, slot, bwd_sums;
+};
+struct FwdSel {
+  KernelRow k;
+  bool lattice, pairable;
+  // the window as the kernel sees it (16-byte-granule forms widen it), tiles, LDS, grid
+  int WW, plane, planeS, mtiles, nchunks;
+  long lds, grid;
+};
 
 // stages of the chunked kernels (direct, F(2,3), the temporal Winograd family): `taps` weight matrices and a
 // window per chunk, double buffered when there is more than one chunk, `extra` bytes behind them
 inline int sel_staged(FwdSel& s, const ConvPlan& p, int taps, size_t extra) {
-  s.mtiles = cdiv(p.Cout, s.BM);
-  if (s.XG) {
+  const KernelRow& k = s.k;
+  s.mtiles = cdiv(p.Cout, k.BM);
+  if (k.XG) {
     const int wwp = (1 << p.lTW) + 8;
     s.WW = wwp;
     s.plane = ((p.WT * p.WH * wwp) << p.lTN) / 4;
-    if (s.plane > s.PCH * 64) return COCLR_EINVAL;
+    if (s.plane > k.PCH * 64) return COCLR_EINVAL;
     s.planeS = cdiv(s.plane, 64) * 256;
   } else {
-    if (p.plane > s.PCH * 64) return COCLR_EINVAL;
-    s.planeS = s.XV4 ? p.plane : cdiv(p.plane, 64) * 64;
+    if (p.plane > k.PCH * 64) return COCLR_EINVAL;
+    s.planeS = k.XV4 ? p.plane : cdiv(p.plane, 64) * 64;    // 16-byte staging packs rows back to back
   }
-  s.nchunks = cdiv(p.Cin, s.CC);
-  const size_t stage = ((size_t)taps * s.CC * s.BM + (size_t)s.CC * s.planeS) * sizeof(float);
+  s.nchunks = cdiv(p.Cin, k.CC);
+  const size_t stage = ((size_t)taps * k.CC * k.BM + (size_t)k.CC * s.planeS) * sizeof(float);
   const size_t lds_main = stage * (s.nchunks > 1 ? 2 : 1) + extra;
-  const size_t lds_red = (size_t)4 * s.BM * 2 * sizeof(float);
+  const size_t lds_red = (size_t)4 * k.BM * 2 * sizeof(float);
   s.lds = (long)(lds_main > lds_red ? lds_main : lds_red);
   if (s.lds > 160 * 1024) return COCLR_EINVAL;
   s.grid = (long)s.mtiles * p.ntiles;
-  s.threads = 256;
   return 0;
 }
 
 // the persistent F(2x2,3x3) kernels: one wave per SIMD (hw, 4- or 16-byte window staging) or two (hw8)
-inline int sel_wino_hw(FwdSel& s, const ConvPlan& p, bool hw8) {
+inline int sel_wino_hw(FwdSel& s, const ConvPlan& p) {
+  const KernelRow& k = s.k;
+  const bool hw8 = k.family == FF_WINO_HW8;
   if (p.WW > 255 || p.WH > 255 || p.WT > 255 || p.lTN > 7) return COCLR_EINVAL;
-  if (hw8 && p.Cin % s.CC) return COCLR_EINVAL;
+  if (hw8 && p.Cin % k.CC) return COCLR_EINVAL;
   s.mtiles = cdiv(p.Cout, 64);
-  if (s.X16) {
+  if (k.X16) {
+    // rows widened to whole 16-byte granules: [2*ow0 - 4, 2*ow0 + 2*TW + 4)
     const int wwp = 2 * (1 << p.lTW) + 8;
     s.WW = wwp;
-    s.plane = ((p.WT * p.WH * wwp) << p.lTN) / 4;
-    if (s.plane > s.PCH * 64) return COCLR_EINVAL;
+    s.plane = ((p.WT * p.WH * wwp) << p.lTN) / 4;      // granules
+    if (s.plane > k.PCH * 64) return COCLR_EINVAL;
+    // hw8, + 32 floats: the four channel planes a patch read touches sit half the banks apart
     s.planeS = cdiv(s.plane, 64) * 256 + (hw8 ? 32 : 0);
   } else {
-    if (p.plane > s.PCH * 64) return COCLR_EINVAL;
+    if (p.plane > k.PCH * 64) return COCLR_EINVAL;
     s.planeS = cdiv(p.plane, 64) * 64;
   }
-  s.nchunks = hw8 ? p.Cin / s.CC : cdiv(p.Cin, s.CC);
-  const size_t stage = ((size_t)16 * s.CC * 64 + (size_t)s.CC * s.planeS) * sizeof(float);
+  s.nchunks = hw8 ? p.Cin / k.CC : cdiv(p.Cin, k.CC);
+  const size_t stage = ((size_t)16 * k.CC * 64 + (size_t)k.CC * s.planeS) * sizeof(float);
+  // two stages + statistics partials + window coordinate table
   s.lds = (long)(2 * stage + (size_t)2 * 64 * 64 * sizeof(float) +
-                 (size_t)s.PCH * (hw8 ? 64 : 256) * sizeof(unsigned));
+                 (size_t)k.PCH * (hw8 ? 64 : 256) * sizeof(unsigned));
   if (s.lds > 160 * 1024) return COCLR_EINVAL;
   const long total = (long)s.mtiles * p.ntiles;
   s.grid = total < kWinoGrid ? total : kWinoGrid;
-  s.threads = hw8 ? 512 : 256;
   return 0;
 }
 
 inline int sel_stem(FwdSel& s, const ConvPlan& p) {
-  const int krows = s.CC * s.KH * ((s.KW + 1) & ~1);
+  const KernelRow& k = s.k;
+  const int krows = k.CC * k.KH * ((k.KW + 1) & ~1);
   const int w_floats = ((krows * 64 + 255) / 256) * 256;
-  if (p.plane > s.PCH * 64 || p.Cin != s.CC) return COCLR_EINVAL;
+  if (p.plane > k.PCH * 64 || p.Cin != k.CC) return COCLR_EINVAL;
   if (p.WT > 255 || p.WH > 255 || p.WW > 255 || (1 << p.lTN) > 255) return COCLR_EINVAL;
   s.mtiles = cdiv(p.Cout, 64);
   s.planeS = cdiv(p.plane, 64) * 64;
   s.nchunks = 1;
-  s.lds = (long)(((size_t)w_floats + 2 * (size_t)s.CC * s.planeS) * sizeof(float));
+  s.lds = (long)(((size_t)w_floats + 2 * (size_t)k.CC * s.planeS) * sizeof(float));
   if (s.lds > 160 * 1024) return COCLR_EINVAL;
   s.grid = (long)p.ntiles * s.mtiles;
-  s.threads = 256;
   return 0;
 }
 
-inline void sel_kernel(FwdSel& s, int family, int KT, int KH, int KW, int CC, int BM, int BN, int PCH, int OCC) {
-  s.family = family;
-  s.KT = KT; s.KH = KH; s.KW = KW; s.CC = CC; s.BM = BM; s.BN = BN; s.PCH = PCH; s.OCC = OCC;
+#ifdef COCLR_WINO_ABLATE
+// timing ablations of the F(2x2,3x3) kernels (wrong results by design; build with -DCOCLR_WINO_ABLATE,
+// tools/wino_ablate.sh): the row keeps its numbers and launches the ablated kernel.  One-wave 16-byte kernel,
+// COCLR_WINO_ABL: 1 no window DMA, 2 no weight DMA, 8 no statistics, 16 no patch reads + input transform,
+// 32 no weight reads.  Measured at B=32 on Conv_2c.conv1 forward (0.797 ms): 1 -> 0.737,
+// 2 -> 0.782, 3 -> 0.673, 8 -> 0.785, 16 -> 0.682, 32 -> 0.755, 48 -> 0.555.  Two-wave kernel: COCLR_W8_ABL.
+template <int ABL> constexpr SingleFn kHwAbl = &launch_persistent<conv_wino_hw_kernel<8, 3, true, ABL>, 256>;
+template <int ABL> constexpr SingleFn kHw8Abl = &launch_persistent<conv_wino_hw8_kernel<8, 3, ABL>, 512>;
+inline void ablate(KernelRow& k) {
+  if (k.family == FF_WINO_HW8) {
+    static const int abl = getenv("COCLR_W8_ABL") ? atoi(getenv("COCLR_W8_ABL")) : 0;
+    k.single = abl == 1 ? kHw8Abl<1> : abl == 2 ? kHw8Abl<2> : abl == 3 ? kHw8Abl<3> : abl == 4 ? kHw8Abl<4>
+             : abl == 7 ? kHw8Abl<7> : k.single;
+  } else if (k.X16) {
+    static const int abl = getenv("COCLR_WINO_ABL") ? atoi(getenv("COCLR_WINO_ABL")) : 0;
+    k.single = abl == 1 ? kHwAbl<1> : abl == 2 ? kHwAbl<2> : abl == 3 ? kHwAbl<3> : abl == 8 ? kHwAbl<8>
+             : abl == 16 ? kHwAbl<16> : abl == 32 ? kHwAbl<32> : abl == 48 ? kHwAbl<48> : k.single;
+  }
 }
+#endif
 
-// Everything conv3d_fwd_impl decides between plan_forward and the launch: the refusals, the 16-byte staging
-// predicates, the two-wave F(2x2,3x3) kernel and its fall-through, the launchers' tile / LDS arithmetic and
-// their refusals.  Returns what the launch returns before it launches.
+// Everything between plan_forward and the launch: the variant-dependent refusals, the 16-byte staging predicates
+// that pick the row of the variant, the two-wave F(2x2,3x3) kernel and its fall-through, the tile / LDS / grid
+// arithmetic of the row's family and its refusals.  Returns what the launch returns before it launches.
 int select_forward(const coclr_conv_desc* d, const ConvPlan& p, int variant, const FwdQuery& q, FwdSel* out) {
   FwdSel s;
   memset(&s, 0, sizeof(s));
-  s.WW = p.WW; s.plane = p.plane;
   s.lattice = d->ys_t > 0;
-  // backward sums: only in the kernels whose epilogue forms them
+  // backward sums: only in the kernels whose epilogue forms them, never with a gather
   if (q.bwd_sums && (!bwd_sums_variant(variant) || q.n_index)) return COCLR_EINVAL;
   // consumer-side BatchNorm apply: only the kernel that has the operand path for it, never with a gather
-  if (q.in_affine && (variant != 41 || q.n_index)) return COCLR_EINVAL;
+  if (q.in_affine && (variant != V_POLY7 || q.n_index)) return COCLR_EINVAL;
+  // the Winograd bodies have no gather path (they would read sample n where n_index[n] is meant)
+  const bool wino = variant == V_POLY7 || variant == V_F23 || variant == V_F43 || variant == V_F24 ||
+                    variant == V_F2X2;
+  if (q.n_index && wino) return COCLR_EINVAL;
   const int x_cstride = p.Ti * p.Hi * p.Wi;
   const int y_cstride = s.lattice ? d->yT * d->yH * d->yW : p.To * p.Ho * p.Wo;
   const int CinP = pad_to(p.Cin, 32), CoutP = pad_to(p.Cout, 128);
@@ -3367,59 +3372,48 @@ int select_forward(const coclr_conv_desc* d, const ConvPlan& p, int variant, con
                   xalign && granule_count(p) <= 192;
   // the temporal Winograd kernels: the same staging, their planners have checked stride and dilation
   const bool xv4t = p.Hi == 1 && p.WH == 1 && p.lTW >= 2 && (p.plane % 4) == 0 && xalign;
+
+  // row `alt` of the variant, then the launch geometry of its family
+  auto take = [&](int alt) -> int {
+    const KernelRow* k = fwd_row(variant, alt);
+    if (!k) return COCLR_EINVAL;
+    s.k = *k;
+    s.WW = p.WW; s.plane = p.plane;
+    switch (k->family) {
+      case FF_IGEMM:
+        s.pairable = k->pair != nullptr;
+        return sel_staged(s, p, k->KT * k->KH * k->KW, 0);
+      case FF_WINO_T:
+        s.pairable = k->XV4;
+        return sel_staged(s, p, 4, 0);
+      case FF_WINO_TF:
+        s.pairable = k->pair != nullptr && k->XV4 && !s.lattice;
+        // the affine table of INAFF sits behind the stages
+        return sel_staged(s, p, k->form, k->INAFF ? (size_t)2 * CinP * sizeof(float) : 0);
+      case FF_STEM: return sel_stem(s, p);
+      default: return sel_wino_hw(s, p);
+    }
+  };
   int rc = COCLR_EINVAL;
   switch (variant) {
-    // 16-byte-staged kernels run with HALF the channel chunk of their 4-byte forms: the chunk is what
-    // sizes the LDS stages, and two or three workgroups per CU became five or six.  Measured at B=32
-    // (same box, alternating): Conv_2b 0.082 -> 0.070 ms forward / 0.070 -> 0.059 data gradient, the
-    // fused heads of Mixed_3c 0.223 -> 0.20 / 0.19 -> 0.195, of Mixed_4b 0.058 -> 0.054 / 0.060 ->
-    // 0.051, Conv_1a.conv2 1.36 -> 1.31; the (1,3,3) small-map kernel did not move and keeps 8.
-    case 0: s.XV4 = xv4; sel_kernel(s, FF_IGEMM, 1, 1, 1, 32, 128, 128, 2, 0); break;
-    case 1: s.XV4 = xv4; sel_kernel(s, FF_IGEMM, 1, 1, 1, xv4 ? 16 : 32, 64, 128, 2, 0); break;
-    case 2: s.XV4 = xv4; sel_kernel(s, FF_IGEMM, 1, 1, 1, xv4 ? 16 : 32, 64, 64, 1, 0); break;
-    case 3: sel_kernel(s, FF_IGEMM, 1, 1, 1, 16, 64, 64, 4, 0); break;
-    case 10: s.XG = xg; sel_kernel(s, FF_IGEMM, 1, 3, 3, 4, 128, 128, xg ? 3 : 4, 0); break;
-    case 11: s.XG = xg; sel_kernel(s, FF_IGEMM, 1, 3, 3, 8, 64, 128, xg ? 3 : 4, 0); break;
-    case 12: s.XG = xg; sel_kernel(s, FF_IGEMM, 1, 3, 3, 8, 64, 64, xg ? 3 : 4, 0); break;
-    case 13: s.XG = xg; sel_kernel(s, FF_IGEMM, 1, 3, 3, 8, 64, 64, xg ? 3 : 8, 0); break;
-    case 20: s.XV4 = xv4; sel_kernel(s, FF_IGEMM, 3, 1, 1, 4, 128, 128, 4, 0); break;
-    case 21: s.XV4 = xv4; sel_kernel(s, FF_IGEMM, 3, 1, 1, 8, 64, 128, 4, 0); break;
-    case 22: s.XV4 = xv4; sel_kernel(s, FF_IGEMM, 3, 1, 1, 8, 64, 64, 4, 0); break;
-    case 25: s.XV4 = xv4; sel_kernel(s, FF_IGEMM, 4, 1, 1, 8, 64, 128, 4, 0); break;
-    case 30: sel_kernel(s, FF_IGEMM, 1, 7, 7, 4, 64, 128, 20, 0); break;
-    case 40: s.XV4 = xv4; sel_kernel(s, FF_IGEMM, 7, 1, 1, xv4 ? 4 : 8, 64, 128, 8, 0); break;
-    case 31: sel_kernel(s, FF_STEM, 1, 7, 7, 3, 64, 128, 20, 0); rc = sel_stem(s, p); break;
-    case 50:
-      // conv_wino_t_body has no gather path (it would read sample n where n_index[n] is meant): refuse, like the
-      // other Winograd forms
-      if (q.n_index) return COCLR_EINVAL;
-      // 8-channel chunks and a four-workgroups-per-CU register budget (accumulators in arch VGPRs,
-      // 99 registers; 27 KB of LDS): four waves per SIMD instead of three.  Measured at B=32 against
-      // the 16-channel / three-wave form: Conv_2c.conv2 1.02-1.06 -> 0.99 ms forward, 0.907 -> 0.874
-      // data gradient; Mixed_3c.b1.conv2 0.212 -> 0.204 / 0.205 -> 0.200; the 8x8x8 layers unchanged.
-      s.XV4 = xv4t;
-      sel_kernel(s, FF_WINO_T, 3, 1, 1, xv4t ? 8 : 16, 64, 64, 4, xv4t ? 4 : 1);
-      rc = sel_staged(s, p, 4, 0);
-      s.pairable = xv4t;
+    case V_PW_128x128: case V_PW_64x128: case V_PW_64x64:
+    case V_T3_128x128: case V_T3_64x128: case V_T3_64x64: case V_T4: case V_T7:
+      rc = take(xv4 ? ALT_16B : ALT_4B);
       break;
-    case 51:
-    case 52:
-      if (q.n_index) return COCLR_EINVAL;
-      s.XV4 = xv4t;
-      s.form = variant == 52 ? 5 : 6;
-      sel_kernel(s, FF_WINO_TF, variant == 52 ? 4 : 3, 1, 1, 8, 64, 64, variant == 52 ? 4 : 6, 3);
-      rc = sel_staged(s, p, s.form, 0);
-      s.pairable = variant == 51 && xv4t && !s.lattice;
+    case V_S_128x128: case V_S_64x128: case V_S_64x64: case V_S_64x64_WIDE:
+      rc = take(xg ? ALT_16B : ALT_4B);
       break;
-    case 41:
-      if (q.n_index) return COCLR_EINVAL;
-      s.XV4 = xv4t; s.INAFF = q.in_affine;
-      s.form = 9;
-      sel_kernel(s, FF_WINO_TF, 7, 1, 1, 8, 64, 64, 6, 2);
-      rc = sel_staged(s, p, 9, q.in_affine ? (size_t)2 * CinP * sizeof(float) : 0);
+    case V_PW_STRIDED: case V_S7: case V_STEM:
+      rc = take(ALT_4B);
       break;
-    case 60: {
-      if (q.n_index || !q.y8 || (d->y_nstride % 2) != 0) return COCLR_EINVAL;
+    case V_F23: case V_F43: case V_F24:
+      rc = take(xv4t ? ALT_16B : ALT_4B);
+      break;
+    case V_POLY7:
+      rc = take((q.in_affine ? ALT_INAFF : 0) + (xv4t ? ALT_16B : ALT_4B));
+      break;
+    case V_F2X2: {
+      if (!q.y8 || (d->y_nstride % 2) != 0) return COCLR_EINVAL;
       // the destination keeps its full row pitch
       const double ycs = (double)d->To * d->Ho * d->Wo;
       if (((double)(1 << p.lTN) * (double)d->y_nstride + (double)(p.Cout + 128) * ycs) * 4.0 >= lim)
@@ -3431,35 +3425,72 @@ int select_forward(const coclr_conv_desc* d, const ConvPlan& p, int variant, con
       const int gran = ((p.WT * p.WH * (2 * (1 << p.lTW) + 8)) << p.lTN) / 4;
       const bool x16 = !x16_off && p.lTW >= 1 && xalign && gran <= 192;
       // two waves per SIMD (conv_wino_hw8_kernel) wherever it applies; COCLR_WINO_W8=0 (read per call:
-      // an A/B and test switch) keeps the one-wave kernel
+      // an A/B and test switch) keeps the one-wave kernel, as do Cin % 8 != 0 and a window that does not fit
       const char* w8env = getenv("COCLR_WINO_W8");
       const bool w8 = !(w8env && w8env[0] == '0');
-      s.X16 = x16;
-      if (x16 && w8) {
-        sel_kernel(s, FF_WINO_HW8, 1, 3, 3, 8, 64, 64, 3, 0);
-        rc = sel_wino_hw(s, p, true);
-      }
-      if (rc == COCLR_EINVAL) {
-        s.WW = p.WW; s.plane = p.plane;
-        sel_kernel(s, FF_WINO_HW, 1, 3, 3, 8, 64, 64, x16 ? 3 : (p.plane <= 384 ? 6 : 10), 0);
-        rc = sel_wino_hw(s, p, false);
-      }
+      if (x16 && w8) rc = take(ALT_HW8);
+      if (rc == COCLR_EINVAL) rc = take(x16 ? ALT_16B : (p.plane <= 384 ? ALT_4B : ALT_HW_PCH10));
+#ifdef COCLR_WINO_ABLATE
+      ablate(s.k);
+#endif
       break;
     }
     default: return COCLR_EINVAL;
-  }
-  if (s.family == FF_IGEMM) {
-    rc = sel_staged(s, p, s.KT * s.KH * s.KW, 0);
-    // pair kernels exist for the stencils sibling units of an inception block share: (1,3,3) of the two
-    // separable branches, 16-byte-staged (1,1,1) of the fused heads and the pool branch
-    s.pairable = s.KT == 1 && ((s.KH == 3 && s.KW == 3) || (s.KH == 1 && s.KW == 1 && s.XV4));
   }
   if (rc) return rc;
   *out = s;
   return 0;
 }
 
-// The launch behind coclr_conv3d_fwd.  With `slot`, variants that have a pair kernel fill it instead of
+// Copy a selection into the ConvArgs of its launch: the tiles, chunks and window select_forward derived, and what
+// the kernels of the row's family read in fields the planner filled for the GROUPED problem.
+void apply(const FwdSel& s, const coclr_conv_desc* d, const ConvPlan& p, ConvArgs& a) {
+  a.mtiles = s.mtiles; a.nchunks = s.nchunks; a.planeS = s.planeS;
+  if (s.k.XG || s.k.X16) {
+    // 16-byte-granule window: WW / plane1 are the padded row / sample extents in floats, plane the number of
+    // granules, the reciprocals in granules
+    a.WW = s.WW;
+    a.plane1 = p.WT * p.WH * s.WW;
+    a.plane = s.plane;
+    a.inv_plane1 = 1.0f / (float)(a.plane1 / 4);
+    a.inv_hw = 1.0f / (float)(p.WH * (s.WW / 4));
+    a.inv_ww = 1.0f / (float)(s.WW / 4);
+  }
+  switch (s.k.family) {
+    case FF_WINO_T:
+      // a.To = frame pairs; the kernel finds the frame count in yst and the plane pitch in yHf/yWf
+      a.yst = d->To; a.yHf = p.Ho; a.yWf = p.Wo;
+      a.y_cstride = d->To * p.Ho * p.Wo;
+      a.st = 1;
+      break;
+    case FF_WINO_TF:
+      if (s.k.form == StemPoly7::TAPS) {
+        // a.To = output pairs; the kernel finds the frame count in yst and the plane pitch in yHf/yWf
+        a.yst = d->To; a.yHf = p.Ho; a.yWf = p.Wo;
+        a.y_cstride = d->To * p.Ho * p.Wo;
+        a.st = 1; a.pt = 3;
+        break;
+      }
+      // a.To = frame quads (F(4,3)) / pairs (F(2,4)); the kernel finds the frame count in To_full and, when the
+      // destination is dense, the plane pitch in yHf/yWf (a lattice along T keeps what the caller set)
+      a.To_full = d->To;
+      if (!s.lattice) {
+        a.yst = 1; a.yot = 0; a.yHf = p.Ho; a.yWf = p.Wo;
+        a.y_cstride = d->To * p.Ho * p.Wo;
+      }
+      a.st = 1;
+      break;
+    case FF_WINO_HW:
+    case FF_WINO_HW8:
+      // a.Ho/Wo = 2x2 blocks; the destination keeps its full row pitch
+      a.yHf = d->Ho; a.yWf = d->Wo;
+      a.y_cstride = d->To * d->Ho * d->Wo;
+      break;
+    default: break;
+  }
+}
+
+// The launch behind coclr_conv3d_fwd.  With `slot`, a selection that has a pair kernel fills it instead of
 // launching (see PairSlot).
 int conv3d_fwd_impl(const coclr_conv_desc* d, const float* x, const float* w_packed, float* y,
                     float* stats, const float* bias, const float* ep_scale, const float* ep_shift,
@@ -3472,10 +3503,9 @@ int conv3d_fwd_impl(const coclr_conv_desc* d, const float* x, const float* w_pac
   ConvArgs a;
   a.bwd_y = nullptr; a.bwd_scale = a.bwd_shift = a.bwd_mean = a.bwd_invstd = nullptr; a.bwd_relu = 0;
   if (bw && bw->bwd_y) {
-    // backward sums of the BatchNorm unit whose dz this data gradient writes: only in the kernels whose
-    // epilogue forms them (not the spatial Winograd / stem kernels), into the statistics slots, and never
-    // together with an epilogue of the forward kind
-    if (!bwd_sums_variant(variant) || !stats || accumulate || bias || ep_scale || relu || n_index ||
+    // backward sums of the BatchNorm unit whose dz this data gradient writes: into the statistics slots, and never
+    // together with an epilogue of the forward kind (which kernels form them: select_forward)
+    if (!stats || accumulate || bias || ep_scale || relu ||
         !bw->bwd_scale || !bw->bwd_shift || !bw->bwd_mean || !bw->bwd_invstd)
       return COCLR_EINVAL;
     a.bwd_y = bw->bwd_y; a.bwd_scale = bw->bwd_scale; a.bwd_shift = bw->bwd_shift;
@@ -3491,8 +3521,7 @@ int conv3d_fwd_impl(const coclr_conv_desc* d, const float* x, const float* w_pac
   a.st = p.st; a.sh = p.sh; a.sw = p.sw; a.pt = p.pt; a.ph = p.ph; a.pw = p.pw;
   a.dt = p.dt; a.dh = p.dh; a.dw = p.dw;
   // destination lattice: o*step + offset inside a (yT, yH, yW) tensor; ys_t == 0 means dense
-  const bool lattice = d->ys_t > 0;
-  if (lattice) {
+  if (d->ys_t > 0) {
     a.yst = d->ys_t; a.ysh = d->ys_h; a.ysw = d->ys_w;
     a.yot = d->yo_t; a.yoh = d->yo_h; a.yow = d->yo_w;
     a.yHf = d->yH; a.yWf = d->yW;
@@ -3508,13 +3537,13 @@ int conv3d_fwd_impl(const coclr_conv_desc* d, const float* x, const float* w_pac
   a.inv_plane1 = 1.0f / (float)p.plane1;
   a.inv_hw = 1.0f / (float)(p.WH * p.WW);
   a.inv_ww = 1.0f / (float)p.WW;
-  a.ntiles = p.ntiles; a.mtiles = 0; a.planeS = 0; a.nchunks = 0;
+  a.ntiles = p.ntiles;
   a.relu = relu; a.accumulate = accumulate;
   a.To_full = 0;
   a.in_scale = a.in_shift = nullptr; a.in_relu = 0;
   if (bw && bw->in_scale) {
-    // consumer-side BatchNorm apply: only the kernel that has the operand path for it, never with a gather
-    if (variant != 41 || !bw->in_shift || n_index) return COCLR_EINVAL;
+    // consumer-side BatchNorm apply (which kernel has the operand path for it: select_forward)
+    if (!bw->in_shift) return COCLR_EINVAL;
     a.in_scale = bw->in_scale; a.in_shift = bw->in_shift; a.in_relu = bw->in_relu;
   }
   {
@@ -3529,121 +3558,13 @@ int conv3d_fwd_impl(const coclr_conv_desc* d, const float* x, const float* w_pac
   FwdSel s;
   rc = select_forward(d, p, variant, q, &s);
   if (rc) return rc;
-  const bool xv4 = s.XV4, xg = s.XG;
-  PairSlot* const pslot = s.pairable ? slot : nullptr;
-  rc = COCLR_EINVAL;
-  switch (variant) {
-    case 0:  rc = xv4 ? launch_variant<1, 1, 1, 32, 128, 128, 2, true>(a, p, stream, pslot, &s)
-                      : launch_variant<1, 1, 1, 32, 128, 128, 2>(a, p, stream, nullptr, &s);
-             break;
-    case 1:  rc = xv4 ? launch_variant<1, 1, 1, 16, 64, 128, 2, true>(a, p, stream, pslot, &s)
-                      : launch_variant<1, 1, 1, 32, 64, 128, 2>(a, p, stream, nullptr, &s);
-             break;
-    case 2:  rc = xv4 ? launch_variant<1, 1, 1, 16, 64, 64, 1, true>(a, p, stream, pslot, &s)
-                      : launch_variant<1, 1, 1, 32, 64, 64, 1>(a, p, stream, nullptr, &s);
-             break;
-    case 3:  rc = launch_variant<1, 1, 1, 16, 64, 64, 4>(a, p, stream, nullptr, &s); break;
-    case 10: rc = xg ? launch_variant<1, 3, 3, 4, 128, 128, 3, false, true>(a, p, stream, pslot, &s)
-                     : launch_variant<1, 3, 3, 4, 128, 128, 4>(a, p, stream, pslot, &s);
-             break;
-    case 11: rc = xg ? launch_variant<1, 3, 3, 8, 64, 128, 3, false, true>(a, p, stream, pslot, &s)
-                     : launch_variant<1, 3, 3, 8, 64, 128, 4>(a, p, stream, pslot, &s);
-             break;
-    case 12: rc = xg ? launch_variant<1, 3, 3, 8, 64, 64, 3, false, true>(a, p, stream, pslot, &s)
-                     : launch_variant<1, 3, 3, 8, 64, 64, 4>(a, p, stream, pslot, &s);
-             break;
-    case 13: rc = xg ? launch_variant<1, 3, 3, 8, 64, 64, 3, false, true>(a, p, stream, pslot, &s)
-                     : launch_variant<1, 3, 3, 8, 64, 64, 8>(a, p, stream, pslot, &s);
-             break;
-    case 20: rc = xv4 ? launch_variant<3, 1, 1, 4, 128, 128, 4, true>(a, p, stream, nullptr, &s)
-                      : launch_variant<3, 1, 1, 4, 128, 128, 4>(a, p, stream, nullptr, &s);
-             break;
-    case 21: rc = xv4 ? launch_variant<3, 1, 1, 8, 64, 128, 4, true>(a, p, stream, nullptr, &s)
-                      : launch_variant<3, 1, 1, 8, 64, 128, 4>(a, p, stream, nullptr, &s);
-             break;
-    case 22: rc = xv4 ? launch_variant<3, 1, 1, 8, 64, 64, 4, true>(a, p, stream, nullptr, &s)
-                      : launch_variant<3, 1, 1, 8, 64, 64, 4>(a, p, stream, nullptr, &s);
-             break;
-    case 25: rc = xv4 ? launch_variant<4, 1, 1, 8, 64, 128, 4, true>(a, p, stream, nullptr, &s)
-                      : launch_variant<4, 1, 1, 8, 64, 128, 4>(a, p, stream, nullptr, &s);
-             break;
-    case 50: {
-      // a.To = frame pairs; the kernel finds the frame count in yst and the plane pitch in yHf/yWf
-      a.yst = d->To; a.yHf = p.Ho; a.yWf = p.Wo;
-      a.y_cstride = d->To * p.Ho * p.Wo;
-      a.st = 1;
-      rc = xv4 ? launch_wino_t<8, 64, 64, 4, true, 4>(a, p, stream, pslot, &s)
-               : launch_wino_t<16, 64, 64, 4, false>(a, p, stream, nullptr, &s);
-      break;
-    }
-    case 51:
-    case 52: {
-      // a.To = frame quads (F(4,3)) / pairs (F(2,4)); the kernel finds the frame count in To_full and, when the
-      // destination is dense, the plane pitch in yHf/yWf (a lattice along T keeps what was set above)
-      a.To_full = d->To;
-      if (!lattice) {
-        a.yst = 1; a.yot = 0; a.yHf = p.Ho; a.yWf = p.Wo;
-        a.y_cstride = d->To * p.Ho * p.Wo;
-      }
-      a.st = 1;
-      if (variant == 52)
-        rc = xv4 ? launch_wino_tf<WinoF24, 8, 64, 64, 4, true, 3>(a, p, stream, nullptr, &s)
-                 : launch_wino_tf<WinoF24, 8, 64, 64, 4, false, 3>(a, p, stream, nullptr, &s);
-      else
-        rc = xv4 ? launch_wino_tf<WinoF43, 8, 64, 64, 6, true, 3>(a, p, stream, pslot, &s)
-                 : launch_wino_tf<WinoF43, 8, 64, 64, 6, false, 3>(a, p, stream, nullptr, &s);
-      break;
-    }
-    case 60: {
-      // a.Ho/Wo = 2x2 blocks; the destination keeps its full row pitch
-      a.yHf = d->Ho; a.yWf = d->Wo;
-      a.y_cstride = d->To * d->Ho * d->Wo;
-      if (s.family == FF_WINO_HW8) { rc = launch_wino_hw8<8, 3>(a, p, stream, &s); break; }
-      if (s.X16) {
-#ifdef COCLR_WINO_ABLATE
-        // timing ablations (wrong results by design; build with -DCOCLR_WINO_ABLATE, tools/wino_ablate.sh):
-        // 1 no window DMA, 2 no weight DMA, 8 no statistics, 16 no patch reads + input transform,
-        // 32 no weight reads.  Measured at B=32 on Conv_2c.conv1 forward (0.797 ms): 1 -> 0.737,
-        // 2 -> 0.782, 3 -> 0.673, 8 -> 0.785, 16 -> 0.682, 32 -> 0.755, 48 -> 0.555.
-        static const int abl = getenv("COCLR_WINO_ABL") ? atoi(getenv("COCLR_WINO_ABL")) : 0;
-        switch (abl) {
-          case 1: return launch_wino_hw<8, 3, true, 1>(a, p, stream, &s);
-          case 2: return launch_wino_hw<8, 3, true, 2>(a, p, stream, &s);
-          case 3: return launch_wino_hw<8, 3, true, 3>(a, p, stream, &s);
-          case 8: return launch_wino_hw<8, 3, true, 8>(a, p, stream, &s);
-          case 16: return launch_wino_hw<8, 3, true, 16>(a, p, stream, &s);
-          case 32: return launch_wino_hw<8, 3, true, 32>(a, p, stream, &s);
-          case 48: return launch_wino_hw<8, 3, true, 48>(a, p, stream, &s);
-          default: break;
-        }
-#endif
-        rc = launch_wino_hw<8, 3, true>(a, p, stream, &s);
-        break;
-      }
-      rc = s.PCH == 6 ? launch_wino_hw<8, 6>(a, p, stream, &s) : launch_wino_hw<8, 10>(a, p, stream, &s);
-      break;
-    }
-    case 30: rc = launch_variant<1, 7, 7, 4, 64, 128, 20>(a, p, stream, nullptr, &s); break;
-    case 31: rc = launch_stem<7, 7, 3, 20>(a, p, stream, &s); break;
-    case 41: {
-      // a.To = output pairs; the kernel finds the frame count in yst and the plane pitch in yHf/yWf
-      a.yst = d->To; a.yHf = p.Ho; a.yWf = p.Wo;
-      a.y_cstride = d->To * p.Ho * p.Wo;
-      a.st = 1; a.pt = 3;
-      if (s.INAFF)
-        rc = xv4 ? launch_wino_tf<StemPoly7, 8, 64, 64, 6, true, 2, true>(a, p, stream, nullptr, &s)
-                 : launch_wino_tf<StemPoly7, 8, 64, 64, 6, false, 2, true>(a, p, stream, nullptr, &s);
-      else
-        rc = xv4 ? launch_wino_tf<StemPoly7, 8, 64, 64, 6, true, 2>(a, p, stream, nullptr, &s)
-                 : launch_wino_tf<StemPoly7, 8, 64, 64, 6, false, 2>(a, p, stream, nullptr, &s);
-      break;
-    }
-    case 40: rc = xv4 ? launch_variant<7, 1, 1, 4, 64, 128, 8, true>(a, p, stream, nullptr, &s)
-                      : launch_variant<7, 1, 1, 8, 64, 128, 8>(a, p, stream, nullptr, &s);
-             break;
+  apply(s, d, p, a);
+  if (slot && s.pairable) {
+    slot->args = a; slot->blocks = s.grid; slot->lds = (size_t)s.lds; slot->pending = true;
+    slot->single = s.k.single; slot->pair = s.k.pair;
+    return 0;
   }
-  if (rc) return rc;
-  return 0;
+  return s.k.single(a, s.grid, (size_t)s.lds, stream);
 }
 
 }  // namespace
@@ -3660,10 +3581,11 @@ extern "C" int coclr_conv3d_fwd_plan(const coclr_conv_desc* d, int flags, int32_
   FwdSel s;
   rc = select_forward(d, p, variant, q, &s);
   if (rc) return rc;
-  const int32_t v[40] = {variant, s.family, s.form, s.KT, s.KH, s.KW, s.CC, s.BM, s.BN, s.PCH,
-                         s.OCC, s.XV4, s.XG, s.X16, s.INAFF, s.lattice, s.pairable, p.lTW, p.lTH, p.lTT,
+  const KernelRow& k = s.k;
+  const int32_t v[40] = {variant, k.family, k.form, k.KT, k.KH, k.KW, k.CC, k.BM, k.BN, k.PCH,
+                         k.OCC, k.XV4, k.XG, k.X16, k.INAFF, s.lattice, s.pairable, p.lTW, p.lTH, p.lTT,
                          p.lTN, p.WT, p.WH, s.WW, s.plane, p.ntiles, s.mtiles, s.nchunks, s.planeS, (int32_t)s.lds,
-                         (int32_t)s.grid, s.threads, s.pairable && q.slot, p.nboxes, p.nbw, p.nbh, p.nbt, p.nbn,
+                         (int32_t)s.grid, k.threads, s.pairable && q.slot, p.nboxes, p.nbw, p.nbh, p.nbt, p.nbn,
                          bwd_sums_variant(variant), 0};
   for (int i = 0; i < 40; ++i) out[i] = v[i];
   return 0;

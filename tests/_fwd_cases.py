@@ -202,7 +202,8 @@ def _i(variant, family, form, k, cc, bm, bn, pch, occ=0, xv4=False, xg=False, x1
     return (variant, family, form) + tuple(k) + (cc, bm, bn, pch, occ, xv4, xg, x16, inaff, lat)
 
 
-# every <variant, family, form, KT KH KW CC BM BN PCH OCC, XV4 XG X16 INAFF lattice> conv3d_fwd_impl's switch can name.
+# every <variant, family, form, KT KH KW CC BM BN PCH OCC, XV4 XG X16 INAFF lattice> the kernel table of
+# conv_igemm.hip (kFwdTable: one row per variant and staging form) holds.
 # A lattice does not change the kernel of the direct forms (it is a run-time destination mapping there), so it is
 # listed only for variants 51 / 52, whose kernels read the frame count and pitch from other fields under it.
 INSTANTIATIONS = (

@@ -2,8 +2,8 @@
 planner and select_forward(), nothing launched) says what every row of tests/_fwd_cases.py reaches, and this
 module asserts that the table covers
 
-  * every kernel instantiation conv3d_fwd_impl's switch can name, except those listed as UNREACHABLE with the
-    planner condition that excludes them (and none of those is reached);
+  * every kernel instantiation the launcher's kernel table (kFwdTable, the rows select_forward picks from) holds,
+    except those listed as UNREACHABLE with the planner condition that excludes them (and none of those is reached);
   * every pair route of coclr_conv3d_fwd_multi (PAIRS);
   * every dispatch edge, per kernel family, by a NAMED row (HOLDERS): deleting one of those rows fails here;
   * the conditions the exact comparison of tests/test_gpu_fwd_exact.py rests on, per row;
