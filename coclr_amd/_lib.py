@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COCLR_LIB_PATH") or os.path.join(_HERE, "libcoclr_hip.so")
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 i32, i64, f32, f64, vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
 
@@ -163,6 +163,17 @@ _SIGNATURES = {
                                    _P(f32), vp, vp, vp],
     "coclr_stage_crops_ragged": [vp, i64, vp, _P(i32), i32, i32, vp, _P(i64), i32, i32, i32, vp, vp, i32, vp, vp, i32,
                                  _P(f32), _P(f32), vp, vp, vp],
+    # host-only plan queries of the staging launchers: the launcher's arguments without the stream, then the plan
+    "coclr_stage_crops_plan": [vp, i32, i32, i32, vp, i32, i32, _P(i32), i32, i32, i32, i32, vp, vp, i32, vp, vp, i32,
+                               _P(f32), _P(f32), vp, vp, _P(i32)],
+    "coclr_stage_crops_ragged_plan": [vp, i64, vp, _P(i32), i32, i32, vp, _P(i64), i32, i32, i32, vp, vp, i32, vp, vp,
+                                      i32, _P(f32), _P(f32), vp, vp, _P(i32)],
+    "coclr_resize_boxes_plan": [i32, vp, i64, i32, i32, i32, vp, _P(i32), i32, i32, i32, vp, i64, vp, i64, vp, _P(i32)],
+    "coclr_resize2_boxes_plan": [i32, vp, i64, i32, i32, i32, vp, _P(i32), i32, i32, i32, i32, vp, i64, vp, i64, vp,
+                                 i64, i32, _P(f32), _P(f32), vp, vp, _P(i32)],
+    "coclr_stage_clips_plan": [vp, i32, vp, i32, i32, i32, i64, _P(f32), _P(f32), _P(i32)],
+    "coclr_jitter_plan": [i32, vp, i32, i32, i32, i32, vp, vp, _P(i32), _P(f32), i32, i32, i32, _P(f32), _P(f32), vp,
+                          _P(i32)],
     "coclr_colstats_workspace": [i32, i32, _P(i64)],
     "coclr_bn1d_stats": [vp, vp, vp, i32, i32, vp],
     "coclr_center_rows": [vp, vp, vp, i32, i32, vp],

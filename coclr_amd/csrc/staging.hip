@@ -22,6 +22,7 @@ struct StageArgs {
   int C, S;
   long THW;        // elements of one (b, c, s) run: seq_len*H*W, contiguous on both sides
   int from_u8;
+  int vec;         // StagePlan::vec: 16-byte loads and stores, every run of `in` AND of `out` starts 16-byte aligned
 };
 
 __device__ __forceinline__ float norm1(float x, float mean, float std) {
@@ -39,7 +40,7 @@ stage_clips_kernel(const StageArgs a) {
   float* dst = a.out + (((long)b * a.S + s) * a.C + c) * a.THW;
   if (U8) {
     const uint8_t* src = static_cast<const uint8_t*>(a.in) + (long)run * a.THW;
-    if ((a.THW & 15) == 0 && (((uintptr_t)src) & 15) == 0) {
+    if (a.vec) {
       const long n16 = a.THW >> 4;
       for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n16; i += (long)gridDim.x * 256) {
         const uint4 q = reinterpret_cast<const uint4*>(src)[i];
@@ -60,7 +61,7 @@ stage_clips_kernel(const StageArgs a) {
     }
   } else {
     const float* src = static_cast<const float*>(a.in) + (long)run * a.THW;
-    if ((a.THW & 3) == 0 && (((uintptr_t)src) & 15) == 0) {
+    if (a.vec) {
       const long n4 = a.THW >> 2;
       for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         const float4 q = reinterpret_cast<const float4*>(src)[i];
@@ -790,29 +791,48 @@ color_jitter_kernel(const JitterArgs a) {
 
 }  // namespace
 
-// Band height of the crop kernel: the most output rows whose source rows fit the LDS budget.  ymin is non-decreasing
-// and advances by at most ch/S (+1 from truncation) per output row, so a band of R rows spans at most
+// Host-only plan queries (coclr_*_plan below): every launcher of this file computes one of these structs and launches
+// from it, and the query reports the same struct without launching.
+
+// Band height of the crop and box kernels: the most output rows whose source rows fit the LDS budget.  ymin is
+// non-decreasing and advances by at most ch/S (+1 from truncation) per output row, so a band of R rows spans at most
 // floor((R-1)*ch/S) + ytaps + 1 source rows; the kernel clamps to cap_rows whatever the tables say.
 // False: one output row's taps do not fit 64 KiB of LDS.
-static bool crop_band(int ch, int S, int Sp, int ytaps, int* R_out, int* cap_out) {
-  int R = 32, cap = 0;
+struct BandPlan {
+  int R, bands, cap_rows, clipped;           // clipped: cap_rows is the box height, not the bound
+  long lds;                                  // dynamic LDS bytes: cap_rows * 3 * Sp
+  int u8out, ragged, vec;                    // the instantiation; vec: 16-byte stores of the fp32 forms
+};
+
+static bool crop_band(int ch, int S, int Sp, int ytaps, BandPlan* p) {
+  int R = 32, cap = 0, clipped = 0;
   for (;; R >>= 1) {
     cap = (int)(((long)(R - 1) * ch) / S) + ytaps + 2;
-    if (cap > ch) cap = ch;
+    clipped = cap > ch;
+    if (clipped) cap = ch;
     const long bytes = (long)cap * 3 * Sp;
     if (bytes <= (R > 1 ? 32768 : 65536)) break;
     if (R == 1) return false;
   }
-  *R_out = R;
-  *cap_out = cap;
+  p->R = R;
+  p->bands = (S + R - 1) / R;
+  p->cap_rows = cap;
+  p->clipped = clipped;
+  p->lds = (long)cap * 3 * Sp;
   return true;
 }
 
-// The launch both crop entry points share: `out` (fp32, with mean / std) or `out8` (the resized bytes).
-static int launch_crops(const uint8_t* frames, int F, int H, int W, const int32_t* slot_frame, int n_clips, int T,
-                        const int32_t* crops, int n_crops, int cw, int ch, int S, const int32_t* xmin,
-                        const int32_t* xk, int xtaps, const int32_t* ymin, const int32_t* yk, int ytaps,
-                        const float* mean, const float* std, float* out, uint8_t* out8, hipStream_t stream) {
+static void report_band(const BandPlan& p, int32_t* out) {
+  out[0] = p.R; out[1] = p.bands; out[2] = p.cap_rows; out[3] = (int32_t)p.lds; out[4] = p.clipped;
+  out[5] = p.u8out; out[6] = p.ragged; out[7] = p.vec;
+}
+
+// What both crop entry points check and plan: `out` (fp32, with mean / std) or `out8` (the resized bytes).  Fills the
+// kernel's arguments and the plan; no device pointer is read.
+static int plan_crops(const uint8_t* frames, int F, int H, int W, const int32_t* slot_frame, int n_clips, int T,
+                      const int32_t* crops, int n_crops, int cw, int ch, int S, const int32_t* xmin,
+                      const int32_t* xk, int xtaps, const int32_t* ymin, const int32_t* yk, int ytaps,
+                      const float* mean, const float* std, float* out, uint8_t* out8, CropArgs& a, BandPlan& p) {
   if (!frames || !slot_frame || !crops || !xmin || !xk || !ymin || !yk || (!out && !out8) || (out && (!mean || !std)))
     return COCLR_EINVAL;
   if (F < 1 || H < 1 || W < 1 || T < 1 || n_clips < 1 || S < 1 || S > 512 || cw < 1 || ch < 1)
@@ -820,7 +840,6 @@ static int launch_crops(const uint8_t* frames, int F, int H, int W, const int32_
   if (n_crops < 1 || n_crops > 16 || xtaps < 1 || xtaps > 64 || ytaps < 1 || ytaps > 64)
     return COCLR_EINVAL;
   if ((long)W * 3 * H > 0x7fffffffL || (long)n_clips * T > 65535) return COCLR_EINVAL;
-  CropArgs a;
   for (int k = 0; k < n_crops; ++k) {
     const int x0 = crops[3 * k], y0 = crops[3 * k + 1], flip = crops[3 * k + 2];
     if (x0 < 0 || y0 < 0 || (long)x0 + cw > W || (long)y0 + ch > H || (flip != 0 && flip != 1))
@@ -832,19 +851,46 @@ static int launch_crops(const uint8_t* frames, int F, int H, int W, const int32_
     if (a.std[c] == 0.f) return COCLR_EINVAL;
   }
   const int Sp = (S + 3) & ~3;
-  int R = 0, cap = 0;
-  if (!crop_band(ch, S, Sp, ytaps, &R, &cap)) return COCLR_EINVAL;
-  const long bands = (S + R - 1) / R;
-  if (bands * n_clips * T * n_crops * 256 >= (1L << 32)) return COCLR_EINVAL;
+  if (!crop_band(ch, S, Sp, ytaps, &p)) return COCLR_EINVAL;
+  if ((long)p.bands * n_clips * T * n_crops * 256 >= (1L << 32)) return COCLR_EINVAL;
+  p.u8out = out ? 0 : 1; p.ragged = 0;
+  p.vec = out && (S & 3) == 0 && (((uintptr_t)out) & 15) == 0;           // reported only: the kernel tests this itself
   a.frames = frames; a.slot_frame = slot_frame; a.xmin = xmin; a.xk = xk; a.ymin = ymin; a.yk = yk;
   a.out = out; a.out8 = out8;
   a.F = F; a.H = H; a.W = W; a.T = T; a.n_clips = n_clips; a.cw = cw; a.ch = ch; a.S = S; a.Sp = Sp;
-  a.xtaps = xtaps; a.ytaps = ytaps; a.R = R; a.cap_rows = cap;
+  a.xtaps = xtaps; a.ytaps = ytaps; a.R = p.R; a.cap_rows = p.cap_rows;
   a.desc = nullptr; a.slot_off = nullptr; a.nbytes = 0;
-  dim3 grid((unsigned)bands, (unsigned)(n_clips * T), (unsigned)n_crops);
-  if (out) hipLaunchKernelGGL((stage_crops_kernel<false, false>), grid, dim3(256), (size_t)cap * 3 * Sp, stream, a);
-  else hipLaunchKernelGGL((stage_crops_kernel<true, false>), grid, dim3(256), (size_t)cap * 3 * Sp, stream, a);
+  return 0;
+}
+
+static int launch_crops(const uint8_t* frames, int F, int H, int W, const int32_t* slot_frame, int n_clips, int T,
+                        const int32_t* crops, int n_crops, int cw, int ch, int S, const int32_t* xmin,
+                        const int32_t* xk, int xtaps, const int32_t* ymin, const int32_t* yk, int ytaps,
+                        const float* mean, const float* std, float* out, uint8_t* out8, hipStream_t stream) {
+  CropArgs a;
+  BandPlan p;
+  if (const int rc = plan_crops(frames, F, H, W, slot_frame, n_clips, T, crops, n_crops, cw, ch, S, xmin, xk, xtaps,
+                                ymin, yk, ytaps, mean, std, out, out8, a, p))
+    return rc;
+  dim3 grid((unsigned)p.bands, (unsigned)(n_clips * T), (unsigned)n_crops);
+  if (out) hipLaunchKernelGGL((stage_crops_kernel<false, false>), grid, dim3(256), (size_t)p.lds, stream, a);
+  else hipLaunchKernelGGL((stage_crops_kernel<true, false>), grid, dim3(256), (size_t)p.lds, stream, a);
   COCLR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int coclr_stage_crops_plan(const uint8_t* frames, int F, int H, int W, const int32_t* slot_frame,
+                                      int n_clips, int T, const int32_t* crops, int n_crops, int cw, int ch, int S,
+                                      const int32_t* xmin, const int32_t* xk, int xtaps, const int32_t* ymin,
+                                      const int32_t* yk, int ytaps, const float* mean, const float* std,
+                                      uint8_t* out8, float* out, int32_t* plan) {
+  if (!plan || (out8 == nullptr) == (out == nullptr)) return COCLR_EINVAL;
+  CropArgs a;
+  BandPlan p;
+  if (const int rc = plan_crops(frames, F, H, W, slot_frame, n_clips, T, crops, n_crops, cw, ch, S, xmin, xk, xtaps,
+                                ymin, yk, ytaps, mean, std, out, out8, a, p))
+    return rc;
+  report_band(p, plan);
   return 0;
 }
 
@@ -867,11 +913,12 @@ extern "C" int coclr_resize_crops_u8(const uint8_t* frames, int F, int H, int W,
                       yk, ytaps, nullptr, nullptr, nullptr, out, (hipStream_t)stream_);
 }
 
-extern "C" int coclr_stage_crops_ragged(const uint8_t* frames, int64_t nbytes, const int32_t* desc,
-                                        const int32_t* desc_host, int n_clips, int T, const int64_t* slot_off,
-                                        const int64_t* slot_off_host, int cw, int ch, int S, const int32_t* xmin,
-                                        const int32_t* xk, int xtaps, const int32_t* ymin, const int32_t* yk, int ytaps,
-                                        const float* mean, const float* std, uint8_t* out8, float* out, void* stream_) {
+// What coclr_stage_crops_ragged checks and plans; as plan_crops.
+static int plan_crops_ragged(const uint8_t* frames, int64_t nbytes, const int32_t* desc, const int32_t* desc_host,
+                             int n_clips, int T, const int64_t* slot_off, const int64_t* slot_off_host, int cw, int ch,
+                             int S, const int32_t* xmin, const int32_t* xk, int xtaps, const int32_t* ymin,
+                             const int32_t* yk, int ytaps, const float* mean, const float* std, uint8_t* out8,
+                             float* out, CropArgs& a, BandPlan& p) {
   if (!frames || !desc || !desc_host || !slot_off || !slot_off_host || !xmin || !xk || !ymin || !yk)
     return COCLR_EINVAL;
   if ((out8 == nullptr) == (out == nullptr) || (out && (!mean || !std))) return COCLR_EINVAL;     // one of the two forms
@@ -882,7 +929,6 @@ extern "C" int coclr_stage_crops_ragged(const uint8_t* frames, int64_t nbytes, c
   if (nbytes < 1 || n_clips < 1 || T < 1 || S < 1 || S > 512 || cw < 1 || ch < 1) return COCLR_EINVAL;
   if (xtaps < 1 || xtaps > 64 || ytaps < 1 || ytaps > 64) return COCLR_EINVAL;
   if ((long)n_clips * T > 65535) return COCLR_EINVAL;
-  CropArgs a;
   for (int c = 0; c < 3; ++c) {
     a.mean[c] = out ? mean[c] : 0.f; a.std[c] = out ? std[c] : 1.f;      // host arrays, read at call time
     if (a.std[c] == 0.f) return COCLR_EINVAL;
@@ -901,33 +947,66 @@ extern "C" int coclr_stage_crops_ragged(const uint8_t* frames, int64_t nbytes, c
     }
   }
   const int Sp = (S + 3) & ~3;
-  int R = 0, cap = 0;
-  if (!crop_band(ch, S, Sp, ytaps, &R, &cap)) return COCLR_EINVAL;
-  const long bands = (S + R - 1) / R;
-  if (bands * n_clips * T * 256 >= (1L << 32)) return COCLR_EINVAL;
+  if (!crop_band(ch, S, Sp, ytaps, &p)) return COCLR_EINVAL;
+  if ((long)p.bands * n_clips * T * 256 >= (1L << 32)) return COCLR_EINVAL;
+  p.u8out = out ? 0 : 1; p.ragged = 1;
+  p.vec = out && (S & 3) == 0 && (((uintptr_t)out) & 15) == 0;           // reported only: the kernel tests this itself
   a.frames = frames; a.slot_frame = nullptr; a.xmin = xmin; a.xk = xk; a.ymin = ymin; a.yk = yk;
   a.out = out; a.out8 = out8;
   a.F = 0; a.H = 0; a.W = 0; a.T = T; a.n_clips = n_clips; a.cw = cw; a.ch = ch; a.S = S; a.Sp = Sp;
-  a.xtaps = xtaps; a.ytaps = ytaps; a.R = R; a.cap_rows = cap;
+  a.xtaps = xtaps; a.ytaps = ytaps; a.R = p.R; a.cap_rows = p.cap_rows;
   a.desc = desc; a.slot_off = slot_off; a.nbytes = (long)nbytes;
   for (int k = 0; k < 16; ++k) a.crop[k][0] = a.crop[k][1] = a.crop[k][2] = 0;
-  const dim3 grid((unsigned)bands, (unsigned)(n_clips * T));
+  return 0;
+}
+
+extern "C" int coclr_stage_crops_ragged(const uint8_t* frames, int64_t nbytes, const int32_t* desc,
+                                        const int32_t* desc_host, int n_clips, int T, const int64_t* slot_off,
+                                        const int64_t* slot_off_host, int cw, int ch, int S, const int32_t* xmin,
+                                        const int32_t* xk, int xtaps, const int32_t* ymin, const int32_t* yk, int ytaps,
+                                        const float* mean, const float* std, uint8_t* out8, float* out, void* stream_) {
+  CropArgs a;
+  BandPlan p;
+  if (const int rc = plan_crops_ragged(frames, nbytes, desc, desc_host, n_clips, T, slot_off, slot_off_host, cw, ch, S,
+                                       xmin, xk, xtaps, ymin, yk, ytaps, mean, std, out8, out, a, p))
+    return rc;
+  const dim3 grid((unsigned)p.bands, (unsigned)(n_clips * T));
   const hipStream_t stream = (hipStream_t)stream_;
-  if (out) hipLaunchKernelGGL((stage_crops_kernel<false, true>), grid, dim3(256), (size_t)cap * 3 * Sp, stream, a);
-  else hipLaunchKernelGGL((stage_crops_kernel<true, true>), grid, dim3(256), (size_t)cap * 3 * Sp, stream, a);
+  if (out) hipLaunchKernelGGL((stage_crops_kernel<false, true>), grid, dim3(256), (size_t)p.lds, stream, a);
+  else hipLaunchKernelGGL((stage_crops_kernel<true, true>), grid, dim3(256), (size_t)p.lds, stream, a);
   COCLR_LAUNCH_CHECK();
   return 0;
 }
 
-// The launch both program entry points share; `aug` admits kinds 6 (blur) and 7 (flip) and runs the augment form.
-static int launch_jitter(bool aug, const uint8_t* frames, int N, int H, int W, int T, const int32_t* kinds,
-                         const float* params, const int32_t* kinds_host, const float* params_host, int G, int P,
-                         int group_size, const float* mean, const float* std, float* out, hipStream_t stream) {
+extern "C" int coclr_stage_crops_ragged_plan(const uint8_t* frames, int64_t nbytes, const int32_t* desc,
+                                             const int32_t* desc_host, int n_clips, int T, const int64_t* slot_off,
+                                             const int64_t* slot_off_host, int cw, int ch, int S, const int32_t* xmin,
+                                             const int32_t* xk, int xtaps, const int32_t* ymin, const int32_t* yk,
+                                             int ytaps, const float* mean, const float* std, uint8_t* out8, float* out,
+                                             int32_t* plan) {
+  if (!plan) return COCLR_EINVAL;
+  CropArgs a;
+  BandPlan p;
+  if (const int rc = plan_crops_ragged(frames, nbytes, desc, desc_host, n_clips, T, slot_off, slot_off_host, cw, ch, S,
+                                       xmin, xk, xtaps, ymin, yk, ytaps, mean, std, out8, out, a, p))
+    return rc;
+  report_band(p, plan);
+  return 0;
+}
+
+// What a program launch does.  cuts: contrast and blur ops of the longest program (a pass ends at each).
+struct JitterPlan { int aug, use_lds, items, per_lane, vec, cuts; long lds; };
+
+// What both program entry points check and plan; `aug` admits kinds 6 (blur) and 7 (flip) and runs the augment form.
+static int plan_jitter(bool aug, const uint8_t* frames, int N, int H, int W, int T, const int32_t* kinds,
+                       const float* params, const int32_t* kinds_host, const float* params_host, int G, int P,
+                       int group_size, const float* mean, const float* std, float* out, JitterArgs& a, JitterPlan& p) {
   if (!frames || !kinds || !params || !kinds_host || !params_host || !mean || !std || !out) return COCLR_EINVAL;
   if (N < 1 || H < 1 || W < 1 || T < 1 || G < 1 || P < 1 || P > 8 || group_size < 1) return COCLR_EINVAL;
   if (N % T != 0 || (long)G * group_size < N) return COCLR_EINVAL;
   if ((long)H * W > kJitMaxPixels) return COCLR_EINVAL;     // the frame's bytes must fit one workgroup's LDS
   bool whole = false;                                       // an op that needs the whole frame: contrast, blur
+  int cuts = 0, run = 0;
   for (long i = 0; i < (long)G * P; ++i) {
     const int kind = kinds_host[i];
     const float v = params_host[i];
@@ -937,8 +1016,10 @@ static int launch_jitter(bool aug, const uint8_t* frames, int N, int H, int W, i
     if (kind == JIT_GRAY && !(v == 0.f || v == 1.f || v == 2.f)) return COCLR_EINVAL;
     if (kind == JIT_BLUR && !(v >= 0.f && v <= kBlurMaxRadius)) return COCLR_EINVAL;                // NaN too
     whole = whole || kind == JIT_CONTRAST || kind == JIT_BLUR;
+    if (i % P == 0) run = 0;
+    run += kind == JIT_CONTRAST || kind == JIT_BLUR;
+    cuts = run > cuts ? run : cuts;
   }
-  JitterArgs a;
   for (int c = 0; c < 3; ++c) {
     a.mean[c] = mean[c]; a.std[c] = std[c];             // host arrays, read at call time
     if (a.std[c] == 0.f) return COCLR_EINVAL;
@@ -948,8 +1029,22 @@ static int launch_jitter(bool aug, const uint8_t* frames, int N, int H, int W, i
   a.items = (a.HW + 3) / 4;
   a.vec = (W & 3) == 0 && (((uintptr_t)out) & 15) == 0;
   a.use_lds = whole ? 1 : 0;
-  const size_t lds = whole ? (size_t)a.items * 12 : 0;
-  if (whole) {                                           // 224 x 224 x 3 = 147 KiB of the CU's 160
+  const int nt = aug ? kAugThreads : kJitThreads;
+  p.aug = aug; p.use_lds = a.use_lds; p.items = a.items; p.per_lane = (a.items + nt - 1) / nt; p.vec = a.vec;
+  p.cuts = cuts; p.lds = whole ? (long)a.items * 12 : 0;
+  return 0;
+}
+
+static int launch_jitter(bool aug, const uint8_t* frames, int N, int H, int W, int T, const int32_t* kinds,
+                         const float* params, const int32_t* kinds_host, const float* params_host, int G, int P,
+                         int group_size, const float* mean, const float* std, float* out, hipStream_t stream) {
+  JitterArgs a;
+  JitterPlan p;
+  if (const int rc = plan_jitter(aug, frames, N, H, W, T, kinds, params, kinds_host, params_host, G, P, group_size,
+                                 mean, std, out, a, p))
+    return rc;
+  const size_t lds = (size_t)p.lds;
+  if (p.use_lds) {                                       // 224 x 224 x 3 = 147 KiB of the CU's 160
     static std::atomic<uint64_t> attr_done{0}, attr_done_aug{0};
     if (aug)
       COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(color_jitter_kernel<true>), kJitMaxPixels * 3,
@@ -961,6 +1056,21 @@ static int launch_jitter(bool aug, const uint8_t* frames, int N, int H, int W, i
   if (aug) hipLaunchKernelGGL(color_jitter_kernel<true>, dim3((unsigned)N), dim3(kAugThreads), lds, stream, a);
   else hipLaunchKernelGGL(color_jitter_kernel<false>, dim3((unsigned)N), dim3(kJitThreads), lds, stream, a);
   COCLR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int coclr_jitter_plan(int aug, const uint8_t* frames, int N, int H, int W, int T, const int32_t* kinds,
+                                 const float* params, const int32_t* kinds_host, const float* params_host, int G,
+                                 int P, int group_size, const float* mean, const float* std, float* out,
+                                 int32_t* plan) {
+  if (!plan) return COCLR_EINVAL;
+  JitterArgs a;
+  JitterPlan p;
+  if (const int rc = plan_jitter(aug != 0, frames, N, H, W, T, kinds, params, kinds_host, params_host, G, P,
+                                 group_size, mean, std, out, a, p))
+    return rc;
+  plan[0] = p.aug; plan[1] = p.use_lds; plan[2] = (int32_t)p.lds; plan[3] = p.items; plan[4] = p.per_lane;
+  plan[5] = p.vec; plan[6] = p.cuts;
   return 0;
 }
 
@@ -993,10 +1103,10 @@ static bool rag_ok(const int32_t* rag, int T, int64_t nbytes, int* W, int* H) {
   return true;
 }
 
-// The launch both box entry points share.  ragged: `desc` rows carry RAG_FIELDS more words, F / H / W are not used.
-static int launch_boxes(bool ragged, const uint8_t* frames, int64_t nbytes, int F, int H, int W, const int32_t* desc,
-                        const int32_t* desc_host, int n_clips, int T, int S, const int32_t* xtab, int64_t xlen,
-                        const int32_t* ytab, int64_t ylen, uint8_t* out, void* stream_) {
+// What both box entry points check and plan.  ragged: `desc` rows carry RAG_FIELDS more words, F / H / W are not used.
+static int plan_boxes(bool ragged, const uint8_t* frames, int64_t nbytes, int F, int H, int W, const int32_t* desc,
+                      const int32_t* desc_host, int n_clips, int T, int S, const int32_t* xtab, int64_t xlen,
+                      const int32_t* ytab, int64_t ylen, uint8_t* out, BoxArgs& a, BandPlan& p) {
   if (!frames || !desc || !desc_host || !xtab || !ytab || !out) return COCLR_EINVAL;
   if (T < 1 || n_clips < 1 || S < 1 || S > 512) return COCLR_EINVAL;
   if (ragged) {
@@ -1029,28 +1139,45 @@ static int launch_boxes(bool ragged, const uint8_t* frames, int64_t nbytes, int 
     hmax = d[BOX_H] > hmax ? d[BOX_H] : hmax;
     ytmax = d[BOX_YTAPS] > ytmax ? d[BOX_YTAPS] : ytmax;
   }
-  // band height as in launch_crops, for the tallest box and the most taps of the launch: a band of any box then
+  // band height as in plan_crops, for the tallest box and the most taps of the launch: a band of any box then
   // spans no more source rows than that; the kernel clamps to cap_rows whatever the tables say
-  int R = 32, cap = 0;
-  for (;; R >>= 1) {
-    cap = (int)(((long)(R - 1) * hmax) / S) + ytmax + 2;
-    if (cap > hmax) cap = hmax;
-    const long bytes = (long)cap * 3 * Sp;
-    if (bytes <= (R > 1 ? 32768 : 65536)) break;
-    if (R == 1) return COCLR_EINVAL;                   // one output row's taps do not fit 64 KiB of LDS
-  }
-  const long bands = (S + R - 1) / R;
-  if (bands * n_clips * T * 256 >= (1L << 32)) return COCLR_EINVAL;
-  BoxArgs a;
+  if (!crop_band(hmax, S, Sp, ytmax, &p)) return COCLR_EINVAL;       // one output row's taps do not fit 64 KiB of LDS
+  if ((long)p.bands * n_clips * T * 256 >= (1L << 32)) return COCLR_EINVAL;
+  p.u8out = 1; p.ragged = ragged; p.vec = 0;
   a.frames = frames; a.desc = desc; a.xtab = xtab; a.ytab = ytab; a.out8 = out;
-  a.F = F; a.H = H; a.W = W; a.T = T; a.S = S; a.Sp = Sp; a.R = R; a.cap_rows = cap;
+  a.F = F; a.H = H; a.W = W; a.T = T; a.S = S; a.Sp = Sp; a.R = p.R; a.cap_rows = p.cap_rows;
   a.xlen = (int)xlen; a.ylen = (int)ylen; a.nbytes = (long)nbytes;
-  const dim3 grid((unsigned)bands, (unsigned)(n_clips * T));
+  return 0;
+}
+
+static int launch_boxes(bool ragged, const uint8_t* frames, int64_t nbytes, int F, int H, int W, const int32_t* desc,
+                        const int32_t* desc_host, int n_clips, int T, int S, const int32_t* xtab, int64_t xlen,
+                        const int32_t* ytab, int64_t ylen, uint8_t* out, void* stream_) {
+  BoxArgs a;
+  BandPlan p;
+  if (const int rc = plan_boxes(ragged, frames, nbytes, F, H, W, desc, desc_host, n_clips, T, S, xtab, xlen, ytab, ylen,
+                                out, a, p))
+    return rc;
+  const dim3 grid((unsigned)p.bands, (unsigned)(n_clips * T));
   if (ragged)
-    hipLaunchKernelGGL(resize_boxes_kernel<true>, grid, dim3(256), (size_t)cap * 3 * Sp, (hipStream_t)stream_, a);
+    hipLaunchKernelGGL(resize_boxes_kernel<true>, grid, dim3(256), (size_t)p.lds, (hipStream_t)stream_, a);
   else
-    hipLaunchKernelGGL(resize_boxes_kernel<false>, grid, dim3(256), (size_t)cap * 3 * Sp, (hipStream_t)stream_, a);
+    hipLaunchKernelGGL(resize_boxes_kernel<false>, grid, dim3(256), (size_t)p.lds, (hipStream_t)stream_, a);
   COCLR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int coclr_resize_boxes_plan(int ragged, const uint8_t* frames, int64_t nbytes, int F, int H, int W,
+                                       const int32_t* desc, const int32_t* desc_host, int n_clips, int T, int S,
+                                       const int32_t* xtab, int64_t xlen, const int32_t* ytab, int64_t ylen,
+                                       uint8_t* out, int32_t* plan) {
+  if (!plan) return COCLR_EINVAL;
+  BoxArgs a;
+  BandPlan p;
+  if (const int rc = plan_boxes(ragged != 0, frames, nbytes, F, H, W, desc, desc_host, n_clips, T, S, xtab, xlen, ytab,
+                                ylen, out, a, p))
+    return rc;
+  report_band(p, plan);
   return 0;
 }
 
@@ -1068,11 +1195,16 @@ extern "C" int coclr_resize_boxes_ragged_u8(const uint8_t* frames, int64_t nbyte
                       stream_);
 }
 
-// The launch both classifier entry points share.  ragged: as launch_boxes.
-static int launch_resize2(bool ragged, const uint8_t* frames, int64_t nbytes, int F, int H, int W, const int32_t* desc,
-                          const int32_t* desc_host, int n_clips, int T, int size, int S, const int32_t* xtab,
-                          int64_t xlen, const int32_t* ytab, int64_t ylen, const int32_t* tab2, int64_t len2,
-                          int taps2, const float* mean, const float* std, uint8_t* out8, float* out, void* stream_) {
+// What a launch of the two-stage kernel does.  one_h1: H1's rows (cap1 * 3 * P), not H2's (capA * 3 * Sp), sized `one`;
+// optin: the launch needs more than 64 KiB and raises the instantiation's dynamic-LDS limit.
+struct Resize2Plan { int R, bands, cap1, capA, one_h1, optin, u8out, ragged, vec; long lds; };
+
+// What both classifier entry points check and plan.  ragged: as plan_boxes.
+static int plan_resize2(bool ragged, const uint8_t* frames, int64_t nbytes, int F, int H, int W, const int32_t* desc,
+                        const int32_t* desc_host, int n_clips, int T, int size, int S, const int32_t* xtab,
+                        int64_t xlen, const int32_t* ytab, int64_t ylen, const int32_t* tab2, int64_t len2,
+                        int taps2, const float* mean, const float* std, uint8_t* out8, float* out, Resize2Args& a,
+                        Resize2Plan& p) {
   if (!frames || !desc || !desc_host || !xtab || !ytab || !tab2) return COCLR_EINVAL;
   if ((out8 == nullptr) == (out == nullptr) || (out && (!mean || !std))) return COCLR_EINVAL;     // one of the two forms
   if (T < 1 || n_clips < 1 || S < 1 || size < 1) return COCLR_EINVAL;
@@ -1088,7 +1220,6 @@ static int launch_resize2(bool ragged, const uint8_t* frames, int64_t nbytes, in
   const int P = (size + 3) & ~3, Sp = (S + 3) & ~3;
   if (xlen < 2 * P || ylen < 2 * P || xlen > 0x7fffffffL || ylen > 0x7fffffffL) return COCLR_EINVAL;
   if (taps2 < 1 || taps2 > 64 || len2 < (int64_t)Sp * (1 + taps2)) return COCLR_EINVAL;
-  Resize2Args a;
   for (int c = 0; c < 3; ++c) {
     a.mean[c] = out ? mean[c] : 0.f; a.std[c] = out ? std[c] : 1.f;      // host arrays, read at call time
     if (a.std[c] == 0.f) return COCLR_EINVAL;
@@ -1118,7 +1249,7 @@ static int launch_resize2(bool ragged, const uint8_t* frames, int64_t nbytes, in
   // taps2 + 2 rows of the size x size image, and capA of those at most floor((capA-1) h / oh) + ytaps + 2 source rows
   // of a clip; the kernel clamps to both caps whatever the tables say.  Up to 80 KiB two workgroups share a CU; a
   // single output row may take the whole 160 KiB.
-  int R = 32, cap1 = 0, capA = 0;
+  int R = 32, cap1 = 0, capA = 0, one_h1 = 0;
   long bytes = 0;
   for (;; R >>= 1) {
     capA = (int)(((long)(R - 1) * size) / S) + taps2 + 2;
@@ -1130,30 +1261,63 @@ static int launch_resize2(bool ragged, const uint8_t* frames, int64_t nbytes, in
       if (c1 > d[CLS_H]) c1 = d[CLS_H];
       if (c1 > cap1) cap1 = (int)c1;
     }
-    const long one = (long)cap1 * 3 * P > (long)capA * 3 * Sp ? (long)cap1 * 3 * P : (long)capA * 3 * Sp;
+    one_h1 = (long)cap1 * 3 * P > (long)capA * 3 * Sp;
+    const long one = one_h1 ? (long)cap1 * 3 * P : (long)capA * 3 * Sp;
     bytes = one + (long)capA * 3 * P;
     if (bytes <= (R > 1 ? kClsLdsTwo : kClsLdsMax)) break;
     if (R == 1) return COCLR_EINVAL;                   // one output row's halo does not fit the CU's LDS
   }
   const long bands = (S + R - 1) / R;
   if (bands * n_clips * T * kClsThreads >= (1L << 32)) return COCLR_EINVAL;
+  p.R = R; p.bands = (int)bands; p.cap1 = cap1; p.capA = capA; p.one_h1 = one_h1; p.optin = bytes > 65536;
+  p.u8out = out8 ? 1 : 0; p.ragged = ragged; p.lds = bytes;
+  p.vec = out && (S & 3) == 0 && (((uintptr_t)out) & 15) == 0;           // reported only: the kernel tests this itself
   a.frames = frames; a.desc = desc; a.xtab = xtab; a.ytab = ytab; a.tab2 = tab2; a.out8 = out8; a.out = out;
   a.F = F; a.H = H; a.W = W; a.T = T; a.size = size; a.P = P; a.S = S; a.Sp = Sp; a.taps2 = taps2; a.R = R;
   a.cap1 = cap1; a.capA = capA; a.xlen = (int)xlen; a.ylen = (int)ylen; a.nbytes = (long)nbytes;
+  return 0;
+}
+
+static int launch_resize2(bool ragged, const uint8_t* frames, int64_t nbytes, int F, int H, int W, const int32_t* desc,
+                          const int32_t* desc_host, int n_clips, int T, int size, int S, const int32_t* xtab,
+                          int64_t xlen, const int32_t* ytab, int64_t ylen, const int32_t* tab2, int64_t len2,
+                          int taps2, const float* mean, const float* std, uint8_t* out8, float* out, void* stream_) {
+  Resize2Args a;
+  Resize2Plan p;
+  if (const int rc = plan_resize2(ragged, frames, nbytes, F, H, W, desc, desc_host, n_clips, T, size, S, xtab, xlen,
+                                  ytab, ylen, tab2, len2, taps2, mean, std, out8, out, a, p))
+    return rc;
   static std::atomic<uint64_t> attr_u8{0}, attr_f32{0}, attr_rag_u8{0}, attr_rag_f32{0};
-  const dim3 grid((unsigned)bands, (unsigned)(n_clips * T));
+  const dim3 grid((unsigned)p.bands, (unsigned)(n_clips * T));
   const void* fn = ragged ? (out8 ? reinterpret_cast<const void*>(resize2_boxes_kernel<true, true>)
                                   : reinterpret_cast<const void*>(resize2_boxes_kernel<false, true>))
                           : (out8 ? reinterpret_cast<const void*>(resize2_boxes_kernel<true, false>)
                                   : reinterpret_cast<const void*>(resize2_boxes_kernel<false, false>));
   std::atomic<uint64_t>& done = ragged ? (out8 ? attr_rag_u8 : attr_rag_f32) : (out8 ? attr_u8 : attr_f32);
-  if (bytes > 65536) COCLR_RETURN_IF(ensure_dyn_lds(fn, kClsLdsMax, done));
+  if (p.optin) COCLR_RETURN_IF(ensure_dyn_lds(fn, kClsLdsMax, done));
   const hipStream_t st = (hipStream_t)stream_;
-  if (ragged && out8) hipLaunchKernelGGL((resize2_boxes_kernel<true, true>), grid, dim3(kClsThreads), (size_t)bytes, st, a);
-  else if (ragged) hipLaunchKernelGGL((resize2_boxes_kernel<false, true>), grid, dim3(kClsThreads), (size_t)bytes, st, a);
-  else if (out8) hipLaunchKernelGGL((resize2_boxes_kernel<true, false>), grid, dim3(kClsThreads), (size_t)bytes, st, a);
-  else hipLaunchKernelGGL((resize2_boxes_kernel<false, false>), grid, dim3(kClsThreads), (size_t)bytes, st, a);
+  const size_t bytes = (size_t)p.lds;
+  if (ragged && out8) hipLaunchKernelGGL((resize2_boxes_kernel<true, true>), grid, dim3(kClsThreads), bytes, st, a);
+  else if (ragged) hipLaunchKernelGGL((resize2_boxes_kernel<false, true>), grid, dim3(kClsThreads), bytes, st, a);
+  else if (out8) hipLaunchKernelGGL((resize2_boxes_kernel<true, false>), grid, dim3(kClsThreads), bytes, st, a);
+  else hipLaunchKernelGGL((resize2_boxes_kernel<false, false>), grid, dim3(kClsThreads), bytes, st, a);
   COCLR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int coclr_resize2_boxes_plan(int ragged, const uint8_t* frames, int64_t nbytes, int F, int H, int W,
+                                        const int32_t* desc, const int32_t* desc_host, int n_clips, int T, int size,
+                                        int S, const int32_t* xtab, int64_t xlen, const int32_t* ytab, int64_t ylen,
+                                        const int32_t* tab2, int64_t len2, int taps2, const float* mean,
+                                        const float* std, uint8_t* out8, float* out, int32_t* plan) {
+  if (!plan) return COCLR_EINVAL;
+  Resize2Args a;
+  Resize2Plan p;
+  if (const int rc = plan_resize2(ragged != 0, frames, nbytes, F, H, W, desc, desc_host, n_clips, T, size, S, xtab,
+                                  xlen, ytab, ylen, tab2, len2, taps2, mean, std, out8, out, a, p))
+    return rc;
+  plan[0] = p.R; plan[1] = p.bands; plan[2] = p.cap1; plan[3] = p.capA; plan[4] = (int32_t)p.lds; plan[5] = p.one_h1;
+  plan[6] = p.optin; plan[7] = p.u8out; plan[8] = p.ragged; plan[9] = p.vec;
   return 0;
 }
 
@@ -1175,13 +1339,15 @@ extern "C" int coclr_resize2_boxes_ragged(const uint8_t* frames, int64_t nbytes,
                         tab2, len2, taps2, mean, std, out8, out, stream_);
 }
 
-extern "C" int coclr_stage_clips(const void* frames, int from_u8, float* out, int B, int C, int S,
-                                 int64_t THW, const float* mean, const float* std, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+// What coclr_stage_clips checks and plans.  vec: THW is a multiple of the 16-byte access (so every run of either side
+// starts where its buffer does, mod 16) and BOTH buffers start 16-byte aligned: the kernel loads and stores 16 bytes.
+struct StagePlan { int u8, vec, gx; };
+
+static int plan_stage(const void* frames, int from_u8, float* out, int B, int C, int S, int64_t THW, const float* mean,
+                      const float* std, StageArgs& a, StagePlan& p) {
   if (B <= 0 || C <= 0 || C > 4 || S <= 0 || THW <= 0 || !frames || !out || !mean || !std)
     return COCLR_EINVAL;
   if ((long)B * C * S > 65535) return COCLR_EINVAL;
-  StageArgs a;
   a.in = frames; a.out = out; a.C = C; a.S = S; a.THW = (long)THW; a.from_u8 = from_u8;
   for (int c = 0; c < 4; ++c) {
     a.mean[c] = c < C ? mean[c] : 0.f;     // host arrays: three floats, read at call time
@@ -1192,9 +1358,30 @@ extern "C" int coclr_stage_clips(const void* frames, int from_u8, float* out, in
   long gx = (THW / per_thread + 255) / 256;
   if (gx < 1) gx = 1;
   if (gx > 64) gx = 64;
-  dim3 grid((unsigned)gx, (unsigned)(B * C * S));
+  a.vec = THW % per_thread == 0 && (((uintptr_t)frames) & 15) == 0 && (((uintptr_t)out) & 15) == 0;
+  p.u8 = from_u8 != 0; p.vec = a.vec; p.gx = (int)gx;
+  return 0;
+}
+
+extern "C" int coclr_stage_clips(const void* frames, int from_u8, float* out, int B, int C, int S,
+                                 int64_t THW, const float* mean, const float* std, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  StageArgs a;
+  StagePlan p;
+  if (const int rc = plan_stage(frames, from_u8, out, B, C, S, THW, mean, std, a, p)) return rc;
+  dim3 grid((unsigned)p.gx, (unsigned)(B * C * S));
   if (from_u8) hipLaunchKernelGGL(stage_clips_kernel<true>, grid, dim3(256), 0, stream, a);
   else hipLaunchKernelGGL(stage_clips_kernel<false>, grid, dim3(256), 0, stream, a);
   COCLR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int coclr_stage_clips_plan(const void* frames, int from_u8, float* out, int B, int C, int S, int64_t THW,
+                                      const float* mean, const float* std, int32_t* plan) {
+  if (!plan) return COCLR_EINVAL;
+  StageArgs a;
+  StagePlan p;
+  if (const int rc = plan_stage(frames, from_u8, out, B, C, S, THW, mean, std, a, p)) return rc;
+  plan[0] = p.u8; plan[1] = p.vec; plan[2] = p.gx;
   return 0;
 }

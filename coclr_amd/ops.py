@@ -1431,3 +1431,112 @@ def segment_softmax_accum(logits, segs, weight, out):
 def segment_accum(x, segs, weight, out):
     """segment_softmax_accum without the softmax (per-video feature sums)."""
     _segment_call("segment_accum", x, segs, weight, out)
+
+
+# ---- host-only plan queries of the staging launchers (ABI 26) ---------------------------------------------------
+# Each runs its launcher's own validation and planning function and launches nothing; no device is needed.  Device
+# pointers are not read, only tested for null and alignment, so the queries take ADDRESSES: PLAN_ADDR (aligned) unless
+# the caller names the tensors it will launch with (`t.data_ptr()`).  A refusal raises as the launcher's would.
+
+PLAN_ADDR = 1 << 20
+
+
+def _f3(v):
+    return (C.c_float * 3)(*[float(x) for x in v])
+
+
+def _band_dict(out):
+    return dict(R=out[0], bands=out[1], cap_rows=out[2], lds=out[3], clipped=bool(out[4]), u8out=bool(out[5]),
+                ragged=bool(out[6]), vec=bool(out[7]))
+
+
+def _host_i32(t, fields):
+    t = torch.as_tensor(t, dtype=torch.int32).contiguous()
+    if t.dim() != 2 or t.shape[1] != fields or t.is_cuda:
+        raise ValueError("coclr_amd: host descriptors must be int32 (n_clips, %d)" % fields)
+    return t
+
+
+def stage_crops_plan(F, H, W, n_clips, T, crops, cw, ch, S, xtaps, ytaps, u8=False, out_addr=PLAN_ADDR,
+                     mean=(0., 0., 0.), std=(1., 1., 1.)):
+    """What stage_crops (u8=False) / resize_crops_u8 (u8=True) would launch: R, bands, cap_rows, lds, clipped, u8out,
+    ragged, vec (include/coclr_hip.h: coclr_stage_crops_plan)."""
+    flat = [int(v) for c in crops for v in c]
+    box = (C.c_int32 * max(len(flat), 1))(*flat)
+    out = (C.c_int32 * 8)()
+    a = PLAN_ADDR
+    _lib.check(_L().coclr_stage_crops_plan(a, F, H, W, a, n_clips, T, box, len(flat) // 3, cw, ch, S, a, a, xtaps, a, a,
+                                           ytaps, _f3(mean), _f3(std), out_addr if u8 else None,
+                                           None if u8 else out_addr, out), "stage_crops_plan")
+    return _band_dict(out)
+
+
+def stage_crops_ragged_plan(nbytes, desc_host, slot_off_host, cw, ch, S, xtaps, ytaps, u8=False, out_addr=PLAN_ADDR,
+                            mean=(0., 0., 0.), std=(1., 1., 1.)):
+    """What stage_crops_ragged would launch; desc_host int32 (n_clips, 5), slot_off_host int64 (n_clips, T)."""
+    d = _host_i32(desc_host, 5)
+    so = torch.as_tensor(slot_off_host, dtype=torch.int64).contiguous()
+    out = (C.c_int32 * 8)()
+    a = PLAN_ADDR
+    _lib.check(_L().coclr_stage_crops_ragged_plan(
+        a, int(nbytes), a, C.cast(d.data_ptr(), C.POINTER(C.c_int32)), d.shape[0], so.shape[1], a,
+        C.cast(so.data_ptr(), C.POINTER(C.c_int64)), cw, ch, S, a, a, xtaps, a, a, ytaps, _f3(mean), _f3(std),
+        out_addr if u8 else None, None if u8 else out_addr, out), "stage_crops_ragged_plan")
+    return _band_dict(out)
+
+
+def resize_boxes_plan(desc_host, T, S, xlen, ylen, shape=None, nbytes=None):
+    """What resize_boxes_u8 (shape = (F, H, W)) / resize_boxes_ragged_u8 (nbytes) would launch."""
+    ragged = nbytes is not None
+    d = _host_i32(desc_host, 14 if ragged else 10)
+    F, H, W = (0, 0, 0) if ragged else shape
+    out = (C.c_int32 * 8)()
+    a = PLAN_ADDR
+    _lib.check(_L().coclr_resize_boxes_plan(int(ragged), a, int(nbytes or 0), F, H, W, a,
+                                            C.cast(d.data_ptr(), C.POINTER(C.c_int32)), d.shape[0], T, S, a, xlen, a,
+                                            ylen, a, out), "resize_boxes_plan")
+    return _band_dict(out)
+
+
+def resize2_boxes_plan(desc_host, T, size, S, xlen, ylen, taps2, u8=False, shape=None, nbytes=None,
+                       out_addr=PLAN_ADDR, mean=(0., 0., 0.), std=(1., 1., 1.)):
+    """What resize2_boxes (shape = (F, H, W)) / resize2_boxes_ragged (nbytes) would launch: R, bands, cap1, capA, lds,
+    one ("h1" | "h2": which rows sized the shared buffer), optin, u8out, ragged, vec."""
+    ragged = nbytes is not None
+    d = _host_i32(desc_host, 18 if ragged else 14)
+    F, H, W = (0, 0, 0) if ragged else shape
+    Sp = (S + 3) & ~3
+    out = (C.c_int32 * 10)()
+    a = PLAN_ADDR
+    _lib.check(_L().coclr_resize2_boxes_plan(
+        int(ragged), a, int(nbytes or 0), F, H, W, a, C.cast(d.data_ptr(), C.POINTER(C.c_int32)), d.shape[0], T, size,
+        S, a, xlen, a, ylen, a, Sp * (1 + taps2), taps2, _f3(mean), _f3(std), out_addr if u8 else None,
+        None if u8 else out_addr, out), "resize2_boxes_plan")
+    return dict(R=out[0], bands=out[1], cap1=out[2], capA=out[3], lds=out[4], one="h1" if out[5] else "h2",
+                optin=bool(out[6]), u8out=bool(out[7]), ragged=bool(out[8]), vec=bool(out[9]))
+
+
+def stage_clips_plan(B, Cc, S, thw, u8, src_addr=PLAN_ADDR, out_addr=PLAN_ADDR):
+    """What stage_clips would launch: u8, vec (16-byte loads and stores), gx."""
+    m = (C.c_float * Cc)(*([0.] * Cc)) if 0 < Cc <= 4 else _f3((0, 0, 0))
+    s = (C.c_float * Cc)(*([1.] * Cc)) if 0 < Cc <= 4 else _f3((1, 1, 1))
+    out = (C.c_int32 * 3)()
+    _lib.check(_L().coclr_stage_clips_plan(src_addr, int(bool(u8)), out_addr, B, Cc, S, thw, m, s, out),
+               "stage_clips_plan")
+    return dict(u8=bool(out[0]), vec=bool(out[1]), gx=out[2])
+
+
+def jitter_plan(aug, N, H, W, T, kinds_host, params_host, group_size, out_addr=PLAN_ADDR):
+    """What color_jitter_clips (aug=False) / augment_clips (aug=True) would launch: aug, use_lds, lds, items,
+    per_lane, vec, cuts (contrast and blur ops of the longest program)."""
+    hk = torch.as_tensor(kinds_host, dtype=torch.int32).contiguous()
+    hp = torch.as_tensor(params_host, dtype=torch.float32).contiguous()
+    if hk.dim() != 2 or hk.shape != hp.shape:
+        raise ValueError("coclr_amd: kinds and params must be (G, P) tables")
+    out = (C.c_int32 * 7)()
+    a = PLAN_ADDR
+    _lib.check(_L().coclr_jitter_plan(int(bool(aug)), a, N, H, W, T, a, a, C.cast(hk.data_ptr(), C.POINTER(C.c_int32)),
+                                      C.cast(hp.data_ptr(), C.POINTER(C.c_float)), hk.shape[0], hk.shape[1],
+                                      int(group_size), _f3((0, 0, 0)), _f3((1, 1, 1)), out_addr, out), "jitter_plan")
+    return dict(aug=bool(out[0]), use_lds=bool(out[1]), lds=out[2], items=out[3], per_lane=out[4], vec=bool(out[5]),
+                cuts=out[6])

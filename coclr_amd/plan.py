@@ -31,7 +31,9 @@ _QUERIES = frozenset((
     "coclr_abi_version", "coclr_conv_packed_size", "coclr_conv_pack_describe", "coclr_conv3d_ntiles",
     "coclr_conv3d_bwd_sums_ok", "coclr_conv3d_wgrad_bn_ok", "coclr_conv3d_wgrad_workspace", "coclr_conv3d_wgrad_plan",
     "coclr_pool_plan", "coclr_bn_plan", "coclr_bn_multi_plan", "coclr_bn_backward_workspace",
-    "coclr_bn_act_backward_pooled_fits", "coclr_gemm_workspace", "coclr_colstats_workspace"))
+    "coclr_bn_act_backward_pooled_fits", "coclr_gemm_workspace", "coclr_colstats_workspace",
+    "coclr_stage_crops_plan", "coclr_stage_crops_ragged_plan", "coclr_resize_boxes_plan", "coclr_resize2_boxes_plan",
+    "coclr_stage_clips_plan", "coclr_jitter_plan"))
 
 _CARG = type(C.byref(C.c_int()))
 

@@ -940,6 +940,60 @@ int coclr_stage_crops_ragged(const uint8_t* frames, int64_t nbytes, const int32_
                              const int32_t* yk, int ytaps, const float* mean, const float* std, uint8_t* out8,
                              float* out, void* stream);
 
+/* What the staging launchers above would do (ABI 26): each query takes the arguments of its launcher without the
+ * stream, runs the launcher's own validation and planning function -- the launcher launches from the struct this
+ * reports -- and launches nothing.  No device is needed and no DEVICE pointer is read: of those only whether they
+ * are null and how they are aligned matters, so any address with the alignment in question will do.  HOST arrays
+ * (crops, desc_host, slot_off_host, kinds_host, params_host, mean, std) are read as the launcher reads them.
+ * Each returns what its launcher would return before launching: COCLR_EINVAL for everything the launcher refuses,
+ * and for a null `plan`.
+ *
+ * Crop form (coclr_stage_crops with `out`, coclr_resize_crops_u8 with `out8`; exactly one of the two),
+ * coclr_stage_crops_ragged, and the box form (ragged = 0 coclr_resize_boxes_u8, 1 coclr_resize_boxes_ragged_u8):
+ *  plan[0] R, output rows per band      plan[1] bands (grid x)     plan[2] cap_rows, source rows a band may stage
+ *  plan[3] dynamic LDS bytes            plan[4] cap_rows is the box height, not the bound (clipped)
+ *  plan[5] U8OUT instantiation          plan[6] RAGGED instantiation
+ *  plan[7] 16-byte stores (fp32 forms: S % 4 == 0 and `out` 16-byte aligned).  Unlike the other fields this one is a
+ *          RESTATEMENT: the crop kernels evaluate the same predicate themselves from S and `out` and are not handed
+ *          the flag (their bodies are as they were before ABI 26); tests/test_gpu_stage_exact.py holds the rows on
+ *          either side of it to the exact result.  The same holds for plan[9] of the two-stage form below.
+ *          coclr_stage_clips_plan's plan[1] and coclr_jitter_plan's plan[5] ARE the values their kernels branch on. */
+int coclr_stage_crops_plan(const uint8_t* frames, int F, int H, int W, const int32_t* slot_frame, int n_clips,
+                           int T, const int32_t* crops, int n_crops, int cw, int ch, int S, const int32_t* xmin,
+                           const int32_t* xk, int xtaps, const int32_t* ymin, const int32_t* yk, int ytaps,
+                           const float* mean, const float* std, uint8_t* out8, float* out, int32_t plan[8]);
+int coclr_stage_crops_ragged_plan(const uint8_t* frames, int64_t nbytes, const int32_t* desc,
+                                  const int32_t* desc_host, int n_clips, int T, const int64_t* slot_off,
+                                  const int64_t* slot_off_host, int cw, int ch, int S, const int32_t* xmin,
+                                  const int32_t* xk, int xtaps, const int32_t* ymin, const int32_t* yk, int ytaps,
+                                  const float* mean, const float* std, uint8_t* out8, float* out, int32_t plan[8]);
+int coclr_resize_boxes_plan(int ragged, const uint8_t* frames, int64_t nbytes, int F, int H, int W,
+                            const int32_t* desc, const int32_t* desc_host, int n_clips, int T, int S,
+                            const int32_t* xtab, int64_t xlen, const int32_t* ytab, int64_t ylen, uint8_t* out,
+                            int32_t plan[8]);
+/* Two-stage form (ragged = 0 coclr_resize2_boxes, 1 coclr_resize2_boxes_ragged):
+ *  plan[0] R    plan[1] bands    plan[2] cap1, source rows    plan[3] capA, rows of the size x size image
+ *  plan[4] dynamic LDS bytes     plan[5] `one` is sized by H1's rows (cap1 * 3 * P), not H2's (capA * 3 * Sp)
+ *  plan[6] more than 64 KiB: the instantiation's dynamic-LDS limit is raised
+ *  plan[7] U8OUT    plan[8] RAGGED    plan[9] 16-byte stores (as above: a restatement of the kernel's own test) */
+int coclr_resize2_boxes_plan(int ragged, const uint8_t* frames, int64_t nbytes, int F, int H, int W,
+                             const int32_t* desc, const int32_t* desc_host, int n_clips, int T, int size, int S,
+                             const int32_t* xtab, int64_t xlen, const int32_t* ytab, int64_t ylen,
+                             const int32_t* tab2, int64_t len2, int taps2, const float* mean, const float* std,
+                             uint8_t* out8, float* out, int32_t plan[10]);
+/* coclr_stage_clips:  plan[0] uint8 source instantiation    plan[1] 16-byte loads and stores: THW a multiple of 16
+ * (uint8) / 4 (fp32) elements and BOTH `frames` and `out` 16-byte aligned; the kernel branches on this value and
+ * nothing else    plan[2] grid x */
+int coclr_stage_clips_plan(const void* frames, int from_u8, float* out, int B, int C, int S, int64_t THW,
+                           const float* mean, const float* std, int32_t plan[3]);
+/* Program form (aug = 0 coclr_color_jitter_clips, 1 coclr_augment_clips):
+ *  plan[0] AUG instantiation    plan[1] use_lds (a program has a contrast or a blur)    plan[2] dynamic LDS bytes
+ *  plan[3] items (four pixels each)    plan[4] items per lane    plan[5] 16-byte stores (W % 4 == 0, `out` aligned)
+ *  plan[6] contrast and blur ops of the longest program: the passes it is cut into, less one */
+int coclr_jitter_plan(int aug, const uint8_t* frames, int N, int H, int W, int T, const int32_t* kinds,
+                      const float* params, const int32_t* kinds_host, const float* params_host, int G, int P,
+                      int group_size, const float* mean, const float* std, float* out, int32_t plan[7]);
+
 /* ------------------------------------------------------------------------ */
 /* Evaluation consumers (model/classifier.py:47-61; eval/main_classifier.py) */
 /* ------------------------------------------------------------------------ */

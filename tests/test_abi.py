@@ -92,6 +92,12 @@ def test_planning_entry_points():
     bp = ops.bn_plan(32, 64, 16 * 64 * 64)
     assert not bp["fwd"]["one_wg"] and bp["bwd"]["groups"] == 32 and bp["bwd"]["vec"]
     assert ops.bn_plan(32, 832, 64)["bwd"]["one_wg"]
+    # the staging launchers (ABI 26): ten-crop test clips at 128, and a training batch's stage_clips
+    sp = ops.stage_crops_plan(32, 256, 340, 10, 32, [(0, 0, 0)], 224, 224, 128, 9, 9)
+    assert sp["R"] == 32 and sp["bands"] == 4 and sp["vec"] and not sp["u8out"] and not sp["ragged"]
+    cp = ops.stage_clips_plan(32, 3, 2, 32 * 128 * 128, True)
+    assert cp["vec"] and cp["gx"] == 64 and not ops.stage_clips_plan(32, 3, 2, 32 * 128 * 128, True,
+                                                                     out_addr=ops.PLAN_ADDR + 4)["vec"]
 
 
 def test_rejected_arguments():

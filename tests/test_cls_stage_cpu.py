@@ -330,9 +330,9 @@ def test_stage_classifier_clips_refusals(monkeypatch, gold, plans):
 def test_entry_point_refusals():
     """coclr_resize2_boxes validates on the host before anything is launched: no GPU is needed to be refused.  The
     addition is additive: the ABI number stays."""
-    assert _lib.ABI_VERSION == 25 and "coclr_resize2_boxes" in _lib.EXPORTED_SYMBOLS
+    assert _lib.ABI_VERSION == 26 and "coclr_resize2_boxes" in _lib.EXPORTED_SYMBOLS
     lib = _lib.load()
-    assert lib.coclr_abi_version() == 25
+    assert lib.coclr_abi_version() == 26
     p = C.c_void_p(4096)
     P, Sp = 24, 16
     #           first T  x0 y0 w   h   ow  oh  cx   cy xoff yoff xt yt

@@ -240,9 +240,9 @@ def test_abi_of_stage_crops():
     src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "coclr_hip.h")).read(), flags=re.S)
     assert re.search(r"\bint\s+coclr_stage_crops\s*\(", src)
     assert "coclr_stage_crops" in _lib.EXPORTED_SYMBOLS
-    assert _lib.ABI_VERSION == 25
+    assert _lib.ABI_VERSION == 26
     lib = _lib.load()
-    assert lib.coclr_abi_version() == 25
+    assert lib.coclr_abi_version() == 26
     # everything is validated on the host before anything is launched: no GPU is needed to be refused
     p = C.c_void_p(4096)
     ok = dict(frames=p, F=6, H=40, W=52, slot_frame=p, n_clips=3, T=4, crops=[0, 0, 0, 24, 12, 1], cw=28, ch=28, S=16,

@@ -43,7 +43,7 @@ def test_abi_is_additive_and_exported():
     assert NAME in declared and NAME in exported and NAME in _lib.EXPORTED_SYMBOLS
     assert declared == exported == set(_lib.EXPORTED_SYMBOLS)
     assert hasattr(ops, "stage_crops_ragged")
-    assert lib.coclr_abi_version() == _lib.ABI_VERSION == 25
+    assert lib.coclr_abi_version() == _lib.ABI_VERSION == 26
     # the signature the header states, word for word in the binding: pointers, 64-bit sizes, 32-bit counts
     i32, i64, vp, P = C.c_int32, C.c_int64, C.c_void_p, C.POINTER
     assert _lib._SIGNATURES[NAME] == [vp, i64, vp, P(i32), i32, i32, vp, P(i64), i32, i32, i32, vp, vp, i32, vp, vp,

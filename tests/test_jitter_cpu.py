@@ -208,8 +208,8 @@ def test_color_jitter_host_logic_and_refusals(monkeypatch):
 
 def test_entry_point_refusals():
     """coclr_color_jitter_clips and coclr_resize_crops_u8 validate on the host before anything is launched: no GPU
-    is needed to be refused.  The ABI number moves only with the library (coclr_pool_plan, coclr_bn_plan: 25)."""
-    assert _lib.ABI_VERSION == 25
+    is needed to be refused.  The ABI number moves only with the library (coclr_pool_plan, coclr_bn_plan: 25; the staging plan queries: 26)."""
+    assert _lib.ABI_VERSION == 26
     for name in ("coclr_color_jitter_clips", "coclr_resize_crops_u8"):
         assert name in _lib.EXPORTED_SYMBOLS
     lib = _lib.load()

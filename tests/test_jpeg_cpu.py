@@ -139,7 +139,7 @@ def test_abi_is_additive_and_exported():
     for name in ("coclr_jpeg_workspace", "coclr_jpeg_decode"):
         assert name in declared and name in exported and name in _lib.EXPORTED_SYMBOLS
     assert declared == exported == set(_lib.EXPORTED_SYMBOLS)
-    assert lib.coclr_abi_version() == _lib.ABI_VERSION == 25
+    assert lib.coclr_abi_version() == _lib.ABI_VERSION == 26
 
 
 def test_workspace_without_a_device():

@@ -28,7 +28,7 @@ def test_split_entry_point_is_declared_exported_and_bound():
     assert name in declared and name in exported and name in _lib.EXPORTED_SYMBOLS
     assert declared == exported == set(_lib.EXPORTED_SYMBOLS)
     assert len(getattr(lib, name).argtypes) == len(lib.coclr_jpeg_decode.argtypes) + 1
-    assert lib.coclr_abi_version() == _lib.ABI_VERSION == 25
+    assert lib.coclr_abi_version() == _lib.ABI_VERSION == 26
 
 
 def test_split_entry_point_rejects_before_any_launch():

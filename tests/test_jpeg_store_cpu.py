@@ -198,7 +198,7 @@ def test_entry_points_are_declared_exported_and_bound():
     for name in ("coclr_jpeg_store_index", "coclr_jpeg_decode_store"):
         assert name in declared and name in exported and name in _lib.EXPORTED_SYMBOLS
     assert declared == exported == set(_lib.EXPORTED_SYMBOLS)
-    assert lib.coclr_abi_version() == _lib.ABI_VERSION == 25
+    assert lib.coclr_abi_version() == _lib.ABI_VERSION == 26
     fields = re.search(r"typedef struct \{([^}]*)\} coclr_jpeg_store;", header).group(1)
     assert re.findall(r"(\w+);", fields) == [n for n, _ in _lib.JpegStore._fields_]
 

@@ -138,7 +138,7 @@ def test_entry_point_is_declared_exported_and_bound():
     name = "coclr_jpeg_decode_store_window"
     assert name in declared and name in exported and name in _lib.EXPORTED_SYMBOLS
     assert declared == exported == set(_lib.EXPORTED_SYMBOLS)
-    assert lib.coclr_abi_version() == _lib.ABI_VERSION == 25
+    assert lib.coclr_abi_version() == _lib.ABI_VERSION == 26
     assert callable(ops.jpeg_decode_store_window) and ops.JW_FIELDS == 4
     # the window entry is the store entry with the window table, device and host, in front of the prefix
     sig, base = _lib._SIGNATURES[name], _lib._SIGNATURES["coclr_jpeg_decode_store"]

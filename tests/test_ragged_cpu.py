@@ -329,7 +329,7 @@ def test_abi_is_additive_and_exported():
     for name in NAMES:
         assert name in declared and name in exported and name in _lib.EXPORTED_SYMBOLS, name
         assert hasattr(ops, name[len("coclr_"):])
-    assert lib.coclr_abi_version() == _lib.ABI_VERSION == 25
+    assert lib.coclr_abi_version() == _lib.ABI_VERSION == 26
     assert text.count("Additive: the ABI number stays 25") >= 3 + 3
 
 

@@ -239,11 +239,11 @@ def test_stage_train_clips_refusals(monkeypatch, gold, plans):
 def test_entry_point_refusals():
     """coclr_augment_clips and coclr_resize_boxes_u8 validate on the host before anything is launched: no GPU is
     needed to be refused.  The additions are additive: the ABI number and the old entry points' limits stay."""
-    assert _lib.ABI_VERSION == 25
+    assert _lib.ABI_VERSION == 26
     for name in ("coclr_augment_clips", "coclr_resize_boxes_u8"):
         assert name in _lib.EXPORTED_SYMBOLS
     lib = _lib.load()
-    assert lib.coclr_abi_version() == 25
+    assert lib.coclr_abi_version() == 26
     p = C.c_void_p(4096)
     ok = dict(frames=p, N=6, H=20, W=24, T=3, kinds=p, params=p, hk=[1, 6, 7, 5], hp=[1.2, 1.375, 0, 2], G=2, P=2,
               gs=3, mean=[0.5, 0.5, 0.5], std=[0.2, 0.2, 0.2], out=p)

@@ -124,10 +124,10 @@ def test_abi_declares_the_segment_entries():
     for name in ("coclr_segment_softmax_accum", "coclr_segment_accum"):
         assert re.search(r"\bint\s+%s\s*\(" % name, src), name
         assert name in _lib.EXPORTED_SYMBOLS
-    assert _lib.ABI_VERSION == 25
-    assert re.search(r"return\s+25\s*;", open(os.path.join(ROOT, "coclr_amd", "csrc", "version.hip")).read())
+    assert _lib.ABI_VERSION == 26
+    assert re.search(r"return\s+26\s*;", open(os.path.join(ROOT, "coclr_amd", "csrc", "version.hip")).read())
     lib = _lib.load()
-    assert lib.coclr_abi_version() == 25
+    assert lib.coclr_abi_version() == 26
     # the segments are validated on the host, before anything is launched: no GPU is needed to be refused
     x = C.c_void_p(4096)
     w = (C.c_float * 2)(1.0, 1.0)
