@@ -896,3 +896,103 @@ extern "C" int coclr_jpeg_decode_store_window(const coclr_jpeg_store* st, const 
   return jpeg_decode_store_impl(st, sel, sel_host, F, geom, geom_host, window, window_host, prefix, prefix_host, stages,
                                 coefs, planes, coef_blocks, out, out_bytes, status, stream);
 }
+
+// ---- a selection of store frames copied to a device arena -----------------------------------------------------------
+namespace {
+
+// A lane per 16-byte word: the words of every distinct frame's hull, then its rows (jpeg_core.h: jc_gather_lane).  The
+// source may be pinned host memory: one 16-byte load and one 16-byte store per lane, no byte path.  The plan is the
+// device copy; the four sizes are the host's, and no word outside them is touched whatever the plan holds.
+__global__ __launch_bounds__(256) void jpeg_store_gather_kernel(const uint4* __restrict__ src_data, long src_words,
+                                                                const uint4* __restrict__ src_rows, long src_nrows,
+                                                                const int64_t* __restrict__ plan, long m, long lanes,
+                                                                uint4* __restrict__ arena, long arena_words,
+                                                                uint4* __restrict__ arena_rows, long arena_nrows) {
+  const long id = (long)blockIdx.x * 256 + threadIdx.x;
+  if (id >= lanes) return;
+  bool rows;
+  int64_t src, dst;
+  if (!jc_gather_lane(plan, m, id, src_words, src_nrows, arena_words, arena_nrows, &rows, &src, &dst)) return;
+  if (rows) arena_rows[dst] = src_rows[src];
+  else arena[dst] = src_data[src];
+}
+
+// The address a kernel reads `bytes` bytes at `p` through: device memory, or host memory that is registered with the
+// runtime (pinned) -- first and last byte alike.  Null for everything else (pageable or managed memory, no device),
+// with the runtime's last error cleared: a kernel must never be launched on such a pointer.
+const void* gather_source(const void* p, int64_t bytes) {
+  const void* dev = nullptr;
+  for (int end = 0; end < 2; ++end) {
+    hipPointerAttribute_t at;
+    const void* q = (const uint8_t*)p + (end ? bytes - 1 : 0);
+    if (hipPointerGetAttributes(&at, q) != hipSuccess) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+    if (at.isManaged || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeHost) || !at.devicePointer)
+      return nullptr;
+    if (at.type == hipMemoryTypeHost && !at.hostPointer) return nullptr;
+    if (end) continue;
+    // a host pointer's device address, by its distance from the host address the runtime answers with
+    dev = at.type == hipMemoryTypeDevice
+              ? p
+              : (const uint8_t*)at.devicePointer + ((const uint8_t*)q - (const uint8_t*)at.hostPointer);
+  }
+  return dev;
+}
+
+}  // namespace
+
+extern "C" int coclr_jpeg_store_gather(const coclr_jpeg_store* st, const int64_t* plan, const int64_t* plan_host,
+                                       int64_t m, const int64_t* slot_host, const int64_t* frames_host, int64_t n,
+                                       uint8_t* arena, int64_t arena_bytes, uint32_t* arena_rows, int64_t arena_nrows,
+                                       void* stream) {
+  if (!store_ok(st) || !plan || !plan_host || !slot_host || !frames_host || !arena || !arena_rows) return COCLR_EINVAL;
+  if (m < 1 || n < m || n > 0x7fffffffL || arena_bytes < 1 || arena_nrows < 1 || st->data_bytes < 1) return COCLR_EINVAL;
+  if (((uintptr_t)st->data & 15) || ((uintptr_t)arena & 15) || ((uintptr_t)arena_rows & 15) || ((uintptr_t)plan & 7))
+    return COCLR_EINVAL;
+  int64_t end = 0, rows = 0, lanes = 0;
+  for (int64_t j = 0; j < m; ++j) {
+    const int64_t* p = plan_host + j * JG_FIELDS;
+    const int64_t f = p[JG_FRAME];
+    if (f < 0 || f >= st->nframes) return COCLR_EINVAL;
+    jc_store_frame fr;
+    jc_geom g;
+    int64_t brings;
+    const int64_t* rec = st->frames_host + f * JS_FIELDS;
+    if (!store_frame_ok(st, f, false, fr, g) ||
+        !jc_gather_frame_ok(rec, st->data_bytes, st->nrows, st->chunk_bytes, &brings))
+      return COCLR_EINVAL;
+    if (p[JG_SRC] != rec[JS_BASE] || p[JG_LEN] != rec[JS_LEN] || p[JG_SRCROW] != rec[JS_ROW] ||
+        p[JG_NROWS] != brings || p[JG_LANE] != lanes)
+      return COCLR_EINVAL;
+    jc_span s;
+    if (!jc_gather_span(p[JG_SRC], p[JG_LEN], p[JG_DST], s)) return COCLR_EINVAL;            // the congruence
+    if (s.dst << 4 < end || s.dst << 4 > end + 15 || jc_gather_end(s) > arena_bytes)         // its neighbour; the
+      return COCLR_EINVAL;                                                                   // arena: whole words
+    if (p[JG_DSTROW] != rows || rows > arena_nrows - brings) return COCLR_EINVAL;
+    end = jc_gather_end(s);
+    rows += brings;
+    lanes += s.words + brings;
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t j = slot_host[i];
+    if (j < 0 || j >= m) return COCLR_EINVAL;
+    const int64_t* p = plan_host + j * JG_FIELDS;
+    int64_t want[JS_FIELDS];
+    jc_gather_rebase(st->frames_host + p[JG_FRAME] * JS_FIELDS, p[JG_DST], p[JG_DSTROW], want);
+    for (int k = 0; k < JS_FIELDS; ++k)
+      if (frames_host[i * JS_FIELDS + k] != want[k]) return COCLR_EINVAL;
+  }
+  if (lanes < 1) return 0;
+  if (!grid_ok(lanes, 256, 0, 0)) return COCLR_EINVAL;
+  const void* data = gather_source(st->data, st->data_bytes);
+  const void* srows = gather_source(st->rows, st->nrows * JS_ROW_WORDS * 4);
+  if (!data || !srows || ((uintptr_t)data & 15) || ((uintptr_t)srows & 15)) return COCLR_EINVAL;
+  hipLaunchKernelGGL(jpeg_store_gather_kernel, dim3(cdiv(lanes, 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const uint4*)data, (long)((st->data_bytes + 15) >> 4), (const uint4*)srows, (long)st->nrows, plan,
+                     (long)m, (long)lanes, (uint4*)arena, (long)(arena_bytes >> 4), (uint4*)arena_rows,
+                     (long)arena_nrows);
+  COCLR_LAUNCH_CHECK();
+  return 0;
+}

@@ -794,3 +794,96 @@ JC_HD bool jc_window_frame(const int64_t* tab, const int64_t* win, long f, long 
   *obyte = ob;
   return true;
 }
+
+// ---- a selection of store frames copied to a device arena (coclr_jpeg_store_gather) ---------------------------------
+// The store's bytes and rows may lie in pinned host memory; a call's distinct frames are copied to a device arena, 16
+// bytes per lane, and decoded there through records rebased to the arena.  Frame j's first arena byte is congruent to
+// its first store byte mod 16, so the copy is one of whole aligned 16-byte words: the frame's HULL, words
+// [base >> 4, (base + len + 15) >> 4).  Every word of a hull holds a byte of the frame, so a hull never leaves the
+// 16-byte words its buffer's bytes touch.  An empty frame has no hull.  Hulls follow each other in the arena without a
+// gap and never share a word; what a hull holds outside its frame is copied and never read.  Rows are 16 bytes each.
+// Per distinct frame JG_FIELDS int64 words; a lane finds its frame by binary search over the JG_LANE column.  The plan
+// is device data to the kernel: every word address derived from it is held against the buffers' sizes, which are
+// kernel arguments.
+enum {
+  JG_FRAME = 0,            // the store frame
+  JG_SRC,                  // its first byte in the store (JS_BASE)
+  JG_LEN,                  // its bytes (JS_LEN)
+  JG_DST,                  // its first byte in the arena, congruent to JG_SRC mod 16
+  JG_SRCROW,               // its first row in the store (JS_ROW)
+  JG_NROWS,                // its rows: jc_chunk_count for a frame of one restart segment, else 0
+  JG_DSTROW,               // its first row in the arena
+  JG_LANE,                 // lanes (hull words, then rows) of all frames before it
+  JG_FIELDS = 8,
+};
+
+struct jc_span {
+  int64_t src, dst, words;     // first 16-byte word in the store and in the arena, and how many
+};
+
+// The hull of `len` bytes at store byte `src`, to be copied to arena byte `dst`.  False: a negative or overflowing
+// range, a frame of 2^31 bytes or more, or a `dst` that is not congruent to `src` mod 16.
+JC_HD bool jc_gather_span(int64_t src, int64_t len, int64_t dst, jc_span& o) {
+  const int64_t top = (int64_t)1 << 62;
+  if (src < 0 || dst < 0 || len < 0 || len > 0x7fffffff || src > top || dst > top || ((src ^ dst) & 15)) return false;
+  o.src = src >> 4;
+  o.dst = dst >> 4;
+  o.words = len == 0 ? 0 : ((src + len + 15) >> 4) - (src >> 4);
+  return true;
+}
+
+// where a frame whose store byte is `src` goes when the hulls before it end at arena byte `end` (a multiple of 16),
+// and where its own hull ends
+JC_HD int64_t jc_gather_place(int64_t end, int64_t src) { return end + (src & 15); }
+JC_HD int64_t jc_gather_end(const jc_span& s) { return (s.dst + s.words) << 4; }
+
+// The rows a store frame brings: false when the record's bytes leave the store's `data_bytes` or its rows the store's
+// `nrows` (the refusal of coclr_jpeg_store_gather; frames with restart markers bring none).
+JC_HD bool jc_gather_frame_ok(const int64_t* rec, int64_t data_bytes, int64_t nrows, int chunk_bytes, int64_t* brings) {
+  const int64_t base = rec[JS_BASE], len = rec[JS_LEN], nseg = rec[JS_NSEG], row = rec[JS_ROW];
+  if (base < 0 || len < 0 || len > 0x7fffffff || data_bytes < len || base > data_bytes - len || nseg < 1) return false;
+  *brings = nseg == 1 ? jc_chunk_count(0, (int)len, chunk_bytes) : 0;
+  return *brings == 0 || (row >= 0 && nrows >= *brings && row <= nrows - *brings);
+}
+
+// the record of a frame in the arena: its own, with the first byte and the first row replaced
+JC_HD void jc_gather_rebase(const int64_t* rec, int64_t dst, int64_t dstrow, int64_t* out) {
+  for (int i = 0; i < JS_FIELDS; ++i) out[i] = rec[i];
+  out[JS_BASE] = dst;
+  out[JS_ROW] = dstrow;
+}
+
+// jc_find_frame over the JG_LANE column of a plan of m frames
+JC_HD long jc_gather_find(const int64_t* plan, long m, int64_t id) {
+  long lo = 0, hi = m - 1;
+  while (lo < hi) {
+    const long mid = lo + (hi - lo + 1) / 2;
+    if (plan[mid * JG_FIELDS + JG_LANE] <= id) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// Lane `id` of a gather: which 16-byte word it copies.  `rows` says whether the word is a row (then src / dst count
+// rows) or a word of the bytes.  False: the lane has nothing to copy, or its words leave a buffer (sizes in words).
+JC_HD bool jc_gather_lane(const int64_t* plan, long m, int64_t id, int64_t src_words, int64_t src_rows,
+                          int64_t dst_words, int64_t dst_rows, bool* rows, int64_t* src, int64_t* dst) {
+  const int64_t* p = plan + jc_gather_find(plan, m, id) * JG_FIELDS;
+  int64_t local = id - p[JG_LANE];
+  jc_span s;
+  if (local < 0 || !jc_gather_span(p[JG_SRC], p[JG_LEN], p[JG_DST], s)) return false;
+  if (local < s.words) {
+    *rows = false;
+    *src = s.src + local;
+    *dst = s.dst + local;
+    return *src < src_words && *dst < dst_words;
+  }
+  local -= s.words;
+  const int64_t top = (int64_t)1 << 62;
+  if (local >= p[JG_NROWS] || p[JG_SRCROW] < 0 || p[JG_DSTROW] < 0 || p[JG_SRCROW] > top || p[JG_DSTROW] > top)
+    return false;
+  *rows = true;
+  *src = p[JG_SRCROW] + local;
+  *dst = p[JG_DSTROW] + local;
+  return *src < src_rows && *dst < dst_rows;
+}

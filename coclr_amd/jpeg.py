@@ -12,6 +12,8 @@ stage_classifier_clips_ragged take; `pack`, per video, is the same.
 A dataset that fits into the device's memory can stay there compressed: `Store.add(pack)` per video, once, then
 `Store.decode(ids)` per step by frame index, to the same RaggedFrames, with nothing but the ids travelling (class Store);
 `Store.decode(ids, boxes)` decodes one pixel box of every frame alone, what staging.stage_train_clips_cropped takes.
+A dataset larger than the device's memory keeps its bytes in pinned host memory, `Store(..., bytes_on="host")`, and a
+built store of either kind is written and read back as data with `Store.save` / `Store.load`.
 
 Scope: baseline / extended sequential Huffman (SOF0, SOF1), 8-bit, one interleaved scan, one component or YCbCr with
 luma sampled 1x1, 2x1 or 2x2, optional restart intervals -- what ffmpeg, cv2.imwrite and PIL write by default.
@@ -583,11 +585,28 @@ class Store:
     `capacity_table_sets` sets of quantisers and Huffman tables (3 KiB each, stored once per distinct set: cv2 and PIL
     write the same tables into every frame of a dataset) and `capacity_segments` restart-segment offsets (default
     64 per frame).  `chunk_bytes=None` is DEFAULT_STORE_CHUNK.
-    Not in scope: saving a built store, sharding one across ranks, datasets larger than the device's memory (those
-    stay with pack / cat / decode) and splitting inside the restart segments of frames with restart markers."""
+
+    A dataset larger than the device's memory: `bytes_on="host"` keeps the compressed bytes and the chunk rows in
+    pinned host memory (the records, table sets and segment words, 64 bytes per frame, stay on the device).  `add`
+    then indexes through a device scratch the size of the largest pack, and `decode` first copies the selection's
+    DISTINCT frames to a device arena in one launch (coclr_jpeg_store_gather: a frame selected several times crosses
+    the bus once) and decodes them there with the same kernels; the arena is kept and grows to the largest call.
+    Ids, results, status and refusals are those of a device store holding the same packs.
+
+    `save(path)` writes a built store as data (a JSON header and .npy arrays); `Store.load(path, ...)` reads one back
+    as either kind, without parsing or indexing anything, and `add` carries on from there.
+    Not in scope: one host arena shared between ranks, sharding a store across ranks, gathering only the chunks a
+    pixel box needs (whole frames cross the bus), decode kernels that read host memory themselves, and splitting
+    inside the restart segments of frames with restart markers."""
+
+    FORMAT_VERSION = 1
+    _FILES = ("data", "frames", "tables", "segs", "rows", "geo", "lanes")
 
     def __init__(self, capacity_bytes, capacity_frames, chunk_bytes=None, device=None, capacity_table_sets=64,
-                 capacity_segments=None):
+                 capacity_segments=None, bytes_on="device"):
+        if bytes_on not in ("device", "host"):
+            raise ValueError("coclr_amd: bytes_on must be 'device' or 'host', got %r" % (bytes_on,))
+        self.bytes_on = bytes_on
         self.chunk_bytes = _store_policy(chunk_bytes)
         capacity_bytes, capacity_frames = int(capacity_bytes), int(capacity_frames)
         capacity_segments = 64 * capacity_frames if capacity_segments is None else int(capacity_segments)
@@ -600,9 +619,15 @@ class Store:
         rows = capacity_bytes // self.chunk_bytes + capacity_frames              # a frame has len // chunk + 1 at most
         self._host = (torch.zeros(capacity_frames, ops.JS_FIELDS, dtype=torch.int64),
                       torch.zeros(words, dtype=torch.int32), torch.zeros(max(1, capacity_segments), dtype=torch.int32))
-        self._data = torch.empty(capacity_bytes, dtype=torch.uint8, device=self.device)
+        if bytes_on == "device":
+            where = dict(device=self.device)
+        else:                                                  # pinned, unless this is the CPU double of the tests
+            where = dict(device="cpu", pin_memory=self.device.type == "cuda")
+        # 16 bytes of room behind the bytes: coclr_jpeg_store_gather reads whole 16-byte words
+        self._data = torch.empty(capacity_bytes + 16, dtype=torch.uint8, **where)[:capacity_bytes]
         self._dev = tuple(torch.zeros_like(t, device=self.device) for t in self._host)
-        self._rows = torch.empty(rows, ops.JS_ROW_WORDS, dtype=torch.int32, device=self.device)
+        self._rows = torch.empty(rows, ops.JS_ROW_WORDS, dtype=torch.int32, **where)
+        self._scratch = self._scratch_rows = self._arena = self._arena_rows = None     # a host store's, grown on demand
         self._sets = {}                                        # the 768 words' bytes -> table set
         self._geo = torch.zeros(capacity_frames, 5, dtype=torch.int64)    # host: H, W, components, hs, vs
         self._lanes = torch.zeros(capacity_frames, dtype=torch.int64)     # host: chunks, or restart segments
@@ -694,13 +719,79 @@ class Store:
         self._frames, self._bytes, self._segs = f0 + F, self._bytes + n, self._segs + nsegs
         self.chunk_rows += int(lanes[~multi].sum())
         try:
-            ops.jpeg_store_index(self._buffers(), f0, f0 + F)
+            if self.bytes_on == "host":
+                self._index_through_scratch(data, rec, was)
+            else:
+                ops.jpeg_store_index(self._buffers(), f0, f0 + F)
         except Exception:                                      # refused by the entry point: the frames are not kept
             self._frames, self._bytes, self._segs, self.chunk_rows = was
             for k in fresh:
                 del self._sets[k]
             raise
         return f0
+
+    @staticmethod
+    def _grown(buf, shape, **where):
+        """`buf` if it holds `shape` (its first dimension counts), else a new buffer half as large again."""
+        if buf is not None and buf.shape[0] >= shape[0]:
+            return buf
+        return torch.empty((shape[0] + shape[0] // 2 + 16,) + tuple(shape[1:]), **where)
+
+    def _index_through_scratch(self, data, rec, was):
+        """A host store's indexing: the new pack's bytes go to a device scratch, coclr_jpeg_store_index runs on a store
+        view of the pack alone -- its records rebased to the scratch, the tables and segment words the store's own --
+        and the rows come back into the host rows.  A row is relative to its chunk, so these are the device store's."""
+        _, bytes0, _, rows0 = was
+        n, F, nrows = data.numel(), rec.shape[0], self.chunk_rows - rows0
+        self._scratch = self._grown(self._scratch, (n + 16,), dtype=torch.uint8, device=self.device)
+        self._scratch_rows = self._grown(self._scratch_rows, (max(1, nrows), ops.JS_ROW_WORDS), dtype=torch.int32,
+                                         device=self.device)
+        local = rec.clone()
+        local[:, 0] -= bytes0
+        local[:, 6] -= rows0
+        self._scratch[:n].copy_(data)
+        _, tables, segs = self._dev
+        ops.jpeg_store_index((self._scratch[:max(1, n)], local.to(self.device), local, F, tables, self._host[1],
+                              len(self._sets), segs, self._host[2], self._segs, self._scratch_rows, self.chunk_bytes),
+                             0, F)
+        if nrows:
+            self._rows[rows0:rows0 + nrows].copy_(self._scratch_rows[:nrows])
+
+    def gather_plan(self, sel):
+        """The host tables of coclr_jpeg_store_gather for the selection `sel` (int64 (n,), inside the store) -> (plan
+        int64 (m, 8), slot int64 (n,), records int64 (n, 8), arena bytes, arena rows): the m DISTINCT frames in store
+        order with their places in the arena (csrc/jpeg_core.h: JG_*), the plan entry of every selected frame, and the
+        selected frames' records rebased to the arena.  Frame j's first arena byte is congruent to its first store
+        byte mod 16 and its hull of whole 16-byte words starts where the one before ends; rows are consecutive."""
+        frames, slot = torch.unique(sel, return_inverse=True)
+        rec = self._host[0][frames]
+        src, ln = rec[:, 0], rec[:, 1]
+        words = torch.where(ln > 0, ((src + ln + 15) >> 4) - (src >> 4), torch.zeros_like(ln))
+        dst = ((words.cumsum(0) - words) << 4) + (src & 15)
+        nrows = torch.where(rec[:, 3] == 1, self._lanes[frames], torch.zeros_like(ln))
+        dstrow = nrows.cumsum(0) - nrows
+        lanes = words + nrows
+        plan = torch.stack([frames, src, ln, dst, rec[:, 6], nrows, dstrow, lanes.cumsum(0) - lanes], 1).contiguous()
+        records = self._host[0][sel]                           # (advanced indexing: a copy)
+        records[:, 0], records[:, 6] = dst[slot], dstrow[slot]
+        return plan, slot.contiguous(), records, int(words.sum()) << 4, int(nrows.sum())
+
+    def _gather(self, gather, d_tables):
+        """Copies the planned frames to the device arena, one launch -> the arguments of ops.jpeg_store_desc for the
+        arena as a store: data and rows the arena's, frames the rebased records, tables and segment words this
+        store's own.  `d_tables`: the plan and the records on the device, one after the other."""
+        plan, slot, records, nbytes, nrows = gather
+        # 16 bytes of room, as every store's bytes have; coclr_jpeg_store takes no store without a byte or a row
+        self._arena = self._grown(self._arena, (max(16, nbytes) + 16,), dtype=torch.uint8, device=self.device)
+        self._arena_rows = self._grown(self._arena_rows, (max(1, nrows), ops.JS_ROW_WORDS), dtype=torch.int32,
+                                       device=self.device)
+        arena, arena_rows = self._arena[:max(16, nbytes)], self._arena_rows[:max(1, nrows)]
+        d_plan = d_tables[:plan.numel()].view(plan.shape)
+        d_records = d_tables[plan.numel():].view(records.shape)
+        ops.jpeg_store_gather(self._buffers(), d_plan, plan, slot, records, arena, arena_rows)
+        _, tables, segs = self._dev
+        return (arena, d_records, records, records.shape[0], tables, self._host[1], len(self._sets), segs, self._host[2],
+                self._segs, arena_rows, self.chunk_bytes)
 
     def plan(self, ids, max_stage_bytes=256 << 20, boxes=None):
         """The host tables of `decode` for the selection `ids` -> (sel int64 (n,), geo int64 (n, 5), offset, total
@@ -760,7 +851,12 @@ class Store:
         else:
             sel, geo, offset, total, stages, blocks, window = self.plan(ids, max_stage_bytes, boxes)
         F, device = sel.numel(), self.device
+        gather = None
+        if self.bytes_on == "host":                            # the kernels see the arena's frames 0 .. F-1
+            gather = self.gather_plan(sel)
+            sel = torch.arange(F, dtype=torch.int64)
         tables = torch.cat([sel] + [t.reshape(-1) for _, _, geom, prefix in stages for t in (geom, prefix)] +
+                           ([] if gather is None else [gather[0].reshape(-1), gather[2].reshape(-1)]) +
                            ([] if window is None else [window.reshape(-1)]))
         d_tables = tables.to(device)                                         # the selection and every stage's tables
         d_sel = d_tables[:F]
@@ -770,6 +866,9 @@ class Store:
         planes = torch.empty(blocks * 64, dtype=torch.uint8, device=device)
         status = torch.empty(F, dtype=torch.int32, device=device)
         store, at = self._buffers(), F
+        if gather is not None:
+            tail = tables.numel() - (0 if window is None else window.numel())
+            store = self._gather(gather, d_tables[tail - gather[0].numel() - gather[2].numel():tail])
         for k, e, geom, prefix in stages:
             d_geom = d_tables[at:at + geom.numel()].view(geom.shape)
             at += geom.numel()
@@ -787,6 +886,105 @@ class Store:
         else:
             frames = staging.RaggedFrames(pixels, offset, window[:, 3].to(torch.int32), window[:, 2].to(torch.int32))
         return (frames, status) if return_status else frames
+
+    _SLICE = 64 << 20        # bytes moved at a time by save and load
+
+    def _filled(self, table_sets=None):
+        """name -> (buffer, filled length along its first dimension) of everything `save` writes."""
+        sets = ops.JS_TABLE_PAD + (len(self._sets) if table_sets is None else table_sets) * ops.JS_TABLE_WORDS
+        return {"data": (self._data, self._bytes), "frames": (self._host[0], self._frames),
+                "tables": (self._host[1], sets), "segs": (self._host[2], self._segs),
+                "rows": (self._rows, self.chunk_rows), "geo": (self._geo, self._frames),
+                "lanes": (self._lanes, self._frames)}
+
+    @staticmethod
+    def _constants():
+        return {"JS_FIELDS": ops.JS_FIELDS, "JS_TABLE_WORDS": ops.JS_TABLE_WORDS, "JS_TABLE_PAD": ops.JS_TABLE_PAD,
+                "JS_ROW_WORDS": ops.JS_ROW_WORDS}
+
+    def save(self, path):
+        """Writes the store to the directory `path` (made if missing): header.json -- format version, chunk_bytes, the
+        JS_* constants, the counts -- and the filled part of every buffer as <name>.npy.  Data only.  The bytes and
+        rows are written in slices, from the host buffers of a host store and downloaded from a device store's."""
+        import json
+        os.makedirs(path, exist_ok=True)
+        filled = self._filled()
+        for name, (buf, n) in filled.items():
+            out = np.lib.format.open_memmap(os.path.join(path, name + ".npy"), mode="w+",
+                                            dtype=np.dtype(str(buf.dtype).split(".")[1]), shape=(n,) + tuple(buf.shape[1:]))
+            step = max(1, self._SLICE // max(1, buf[0:1].numel() * buf.element_size()))
+            for a in range(0, n, step):
+                out[a:a + step] = buf[a:min(n, a + step)].cpu().numpy()
+            out.flush()
+            del out
+        header = {"format": "coclr_amd.jpeg.Store", "version": self.FORMAT_VERSION, "chunk_bytes": self.chunk_bytes,
+                  "constants": self._constants(), "frames": self._frames, "bytes": self._bytes, "segments": self._segs,
+                  "rows": self.chunk_rows, "table_sets": len(self._sets)}
+        with open(os.path.join(path, "header.json"), "w") as f:
+            json.dump(header, f, indent=1)
+
+    @classmethod
+    def load(cls, path, device=None, bytes_on="device", capacity_bytes=None, capacity_frames=None,
+             capacity_table_sets=None, capacity_segments=None):
+        """A store `save` wrote -> a Store of either kind, whichever kind wrote it: nothing is parsed and nothing is
+        indexed.  Capacities default to what the file holds (the segment capacity to the constructor's 64 per frame
+        where that is more); larger ones let `add` carry on, ids continuing.  The arrays are read memory-mapped, a slice
+        at a time.  ValueError, before any buffer is made: a header of another format version, JS_* constants that are
+        not this library's, counts that disagree with the arrays' shapes, a truncated array, capacities below what
+        the file holds.  What the arrays HOLD is not trusted: the entry points validate every record per call."""
+        import json
+        try:
+            with open(os.path.join(path, "header.json")) as f:
+                head = json.load(f)
+        except (OSError, ValueError) as e:
+            raise ValueError("coclr_amd: no readable store header in %s: %s" % (path, e))
+        if not isinstance(head, dict) or head.get("format") != "coclr_amd.jpeg.Store" or \
+                head.get("version") != cls.FORMAT_VERSION:
+            raise ValueError("coclr_amd: %s is not a store of format version %d" % (path, cls.FORMAT_VERSION))
+        if head.get("constants") != cls._constants():
+            raise ValueError("coclr_amd: the store was written with other JS_* constants: %r" % (head.get("constants"),))
+        try:
+            counts = {k: head[k] for k in ("frames", "bytes", "segments", "rows", "table_sets")}
+            chunk_bytes = _store_policy(head["chunk_bytes"])
+        except KeyError as e:
+            raise ValueError("coclr_amd: the store header lacks %s" % e)
+        if any(isinstance(v, bool) or not isinstance(v, int) or v < 0 for v in counts.values()):
+            raise ValueError("coclr_amd: the store header's counts must be non-negative integers: %r" % (counts,))
+        nf, nb, ns, nr, nt = (counts[k] for k in ("frames", "bytes", "segments", "rows", "table_sets"))
+        want = {"data": ((nb,), np.uint8), "frames": ((nf, ops.JS_FIELDS), np.int64),
+                "tables": ((ops.JS_TABLE_PAD + nt * ops.JS_TABLE_WORDS,), np.int32), "segs": ((ns,), np.int32),
+                "rows": ((nr, ops.JS_ROW_WORDS), np.int32), "geo": ((nf, 5), np.int64), "lanes": ((nf,), np.int64)}
+        arrays = {}
+        for name, (shape, dtype) in want.items():
+            try:
+                arrays[name] = np.load(os.path.join(path, name + ".npy"), mmap_mode="r", allow_pickle=False)
+            except Exception as e:                             # missing, cut short, or no array at all
+                raise ValueError("coclr_amd: %s.npy of the store cannot be read: %s" % (name, e))
+            if arrays[name].shape != shape or arrays[name].dtype != dtype:
+                raise ValueError("coclr_amd: %s.npy holds %s %s where the header's counts ask for %s %s" %
+                                 (name, arrays[name].dtype, arrays[name].shape, np.dtype(dtype), shape))
+        caps = {"capacity_bytes": max(1, nb) if capacity_bytes is None else int(capacity_bytes),
+                "capacity_frames": max(1, nf) if capacity_frames is None else int(capacity_frames),
+                "capacity_table_sets": max(1, nt) if capacity_table_sets is None else int(capacity_table_sets)}
+        caps["capacity_segments"] = max(ns, 64 * caps["capacity_frames"]) if capacity_segments is None else \
+            int(capacity_segments)
+        for (what, cap), have in zip(caps.items(), (nb, nf, nt, ns)):
+            if cap < have:
+                raise ValueError("coclr_amd: %s=%d is below the %d the file holds" % (what, cap, have))
+        if caps["capacity_bytes"] // chunk_bytes + caps["capacity_frames"] < nr:
+            raise ValueError("coclr_amd: the file holds %d rows, more than its bytes and frames can have" % nr)
+        store = cls(chunk_bytes=chunk_bytes, device=device, bytes_on=bytes_on, **caps)
+        store._frames, store._bytes, store._segs, store.chunk_rows = nf, nb, ns, nr
+        for name, (buf, n) in store._filled(nt).items():
+            step = max(1, cls._SLICE // max(1, buf[0:1].numel() * buf.element_size()))
+            for a in range(0, n, step):
+                buf[a:min(n, a + step)].copy_(torch.from_numpy(np.array(arrays[name][a:a + step])))
+        sets = store._host[1][ops.JS_TABLE_PAD:ops.JS_TABLE_PAD + nt * ops.JS_TABLE_WORDS]
+        store._sets = {sets[i * ops.JS_TABLE_WORDS:(i + 1) * ops.JS_TABLE_WORDS].numpy().tobytes(): i
+                       for i in range(nt)}
+        for dev, host in zip(store._dev, store._host):
+            dev.copy_(host)
+        return store
 
 
 Store.decode.last_status = None

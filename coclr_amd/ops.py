@@ -1218,10 +1218,11 @@ JS_FIELDS, JS_TABLE_WORDS, JS_TABLE_PAD, JS_ROW_WORDS = 8, 768, 16, 4     # csrc
 
 
 def jpeg_store_desc(data, frames, frames_host, nframes, tables, tables_host, table_sets, segs, segs_host, nsegs, rows,
-                    chunk_bytes):
+                    chunk_bytes, host_bytes=False):
     """The `coclr_jpeg_store` of a store's buffers (include/coclr_hip.h), each on the device with its host copy: data
     uint8 flat, frames int64 (capacity, 8), tables int32 (16 + sets * 768,), segs int32 flat, rows int32 (capacity, 4).
-    nframes, table_sets and nsegs say how much of each is filled."""
+    nframes, table_sets and nsegs say how much of each is filled.  `host_bytes`: data and rows may be host tensors,
+    what coclr_jpeg_store_gather alone takes (and only pinned: it asks the runtime)."""
     for dev, host, ty in ((frames, frames_host, torch.int64), (tables, tables_host, torch.int32),
                           (segs, segs_host, torch.int32)):
         if dev.dtype != ty or host.dtype != ty or host.is_cuda or dev.shape != host.shape or \
@@ -1231,10 +1232,11 @@ def jpeg_store_desc(data, frames, frames_host, nframes, tables, tables_host, tab
             frames.shape[0] < nframes or tables.numel() < JS_TABLE_PAD + table_sets * JS_TABLE_WORDS or \
             segs.numel() < nsegs:
         raise ValueError("coclr_amd: a store's buffers do not hold what it says is filled")
-    return _lib.JpegStore(_p(data, torch.uint8), data.numel(), _p(frames, torch.int64), frames_host.data_ptr(),
+    bytes_of = (lambda t, ty: t.data_ptr()) if host_bytes else _p
+    return _lib.JpegStore(bytes_of(data, torch.uint8), data.numel(), _p(frames, torch.int64), frames_host.data_ptr(),
                           int(nframes), _p(tables, torch.int32), tables_host.data_ptr(), int(table_sets),
                           _p(segs, torch.int32) if nsegs else None, segs_host.data_ptr() if nsegs else None, int(nsegs),
-                          _p(rows, torch.int32), rows.numel() // JS_ROW_WORDS, int(chunk_bytes))
+                          bytes_of(rows, torch.int32), rows.numel() // JS_ROW_WORDS, int(chunk_bytes))
 
 
 def jpeg_store_index(store, f0, f1):
@@ -1292,6 +1294,32 @@ def jpeg_decode_store_window(store, sel, sel_host, geom, geom_host, window, wind
     layout."""
     _jpeg_decode_store("jpeg_decode_store_window", store, sel, sel_host, geom, geom_host, (window, window_host), prefix,
                        prefix_host, coefs, planes, out, status, stages)
+
+
+JG_FIELDS = 8        # csrc/jpeg_core.h: per distinct frame of a gather, JG_*
+
+
+def jpeg_store_gather(store, plan, plan_host, slot_host, frames_host, arena, arena_rows):
+    """Copies the hulls and rows of the distinct frames `plan` names from a store whose bytes and rows may be pinned host
+    memory to the device arenas (include/coclr_hip.h: coclr_jpeg_store_gather): plan int64 (m, 8) on the device and
+    plan_host; slot_host int64 (n,) and frames_host int64 (n, 8), the plan entry and the rebased record of each frame
+    of the decode call; arena uint8 flat and arena_rows int32 (rows, 4) on the device.  `store`: the arguments of
+    jpeg_store_desc."""
+    desc = jpeg_store_desc(*store, host_bytes=True)
+    m, n = plan_host.shape[0], slot_host.numel()
+    for t, want, what in ((plan, (m, JG_FIELDS), "plan"), (plan_host, (m, JG_FIELDS), "plan"),
+                          (slot_host, (n,), "slots"), (frames_host, (n, JS_FIELDS), "rebased records")):
+        if tuple(t.shape) != want or t.dtype != torch.int64 or not t.is_contiguous() or \
+                (t is not plan and t.is_cuda):
+            raise ValueError("coclr_amd: the %s of a gather must be contiguous int64 %s" % (what, want))
+    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous() or \
+            arena_rows.dtype != torch.int32 or not arena_rows.is_contiguous():
+        raise ValueError("coclr_amd: jpeg_store_gather needs a flat uint8 arena and int32 rows")
+    hp = lambda t: C.cast(t.data_ptr(), C.POINTER(C.c_int64))                # noqa: E731
+    rc = _L().coclr_jpeg_store_gather(C.byref(desc), _p(plan, torch.int64), hp(plan_host), m, hp(slot_host),
+                                      hp(frames_host), n, _p(arena, torch.uint8), arena.numel(),
+                                      _p(arena_rows, torch.int32), arena_rows.numel() // JS_ROW_WORDS, _stream())
+    _lib.check(rc, "jpeg_store_gather")
 
 
 def resize_boxes_ragged_u8(pixels, desc, desc_host, xtab, ytab, T, S, out):

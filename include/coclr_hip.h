@@ -887,6 +887,38 @@ int coclr_jpeg_decode_store_window(const coclr_jpeg_store* st, const int64_t* se
                                    int stages, int16_t* coefs, uint8_t* planes, int64_t coef_blocks, uint8_t* out,
                                    int64_t out_bytes, int32_t* status, void* stream);
 
+/* Copies the bytes and rows of m distinct frames of a store to a device arena, one launch, so that a store whose
+ * `data` and `rows` lie in PINNED HOST memory (a dataset larger than the device's memory) is decoded by
+ * coclr_jpeg_decode_store / _window from the arena: a coclr_jpeg_store whose data / rows are the arena's, whose frames
+ * are the rebased records and whose tables / segs are the source store's own, with the selection 0 .. n-1.  `st` with
+ * device data and rows is taken alike (compaction).
+ * st: the source.  data and rows: device memory, or host memory registered with the runtime (hipHostMalloc,
+ *   hipHostRegister), 16-byte aligned, allocated with 16 bytes of room behind data_bytes.  Only frames_host is read of
+ *   its tables.
+ * plan: int64 [m][8], DEVICE, and plan_host (csrc/jpeg_core.h: JG_*): per distinct frame {store frame, first byte and
+ *   byte count in the store, first byte in the arena, first row and row count in the store, first row in the arena,
+ *   lanes of all frames before it}.  A frame's lanes are the 16-byte words of its hull [base & ~15, (base + len + 15)
+ *   & ~15) -- none for an empty frame -- and then its rows.  Its first arena byte is congruent to its first store byte
+ *   mod 16; hulls follow each other in the arena from byte 0 without a gap, rows likewise from row 0.  What a hull
+ *   holds outside its frame is copied too and is never read.
+ * slot_host: int64 [n], HOST: the plan entry of each of the n frames of the decode call (repeats share one).
+ * frames_host: int64 [n][8], HOST: the rebased records the decode call will be given: the store's own with the first
+ *   byte and the first row replaced by the arena's (jc_gather_rebase).
+ * arena: arena_bytes bytes, arena_rows: uint32 [arena_nrows][4], both DEVICE and 16-byte aligned.
+ * The kernel reads the device plan and holds every word it touches against the four buffer sizes, which it is given
+ * by value: whatever the plan holds, nothing outside the 16-byte words of data, rows, arena and arena_rows is touched.
+ * COCLR_EINVAL before any launch: a null or misaligned pointer; m < 1 or n < m; a plan frame outside [0, nframes),
+ * whose record is not one coclr_jpeg_decode_store takes, whose bytes or rows leave the source arrays or are not what
+ * the plan says; an arena byte that breaks the congruence or a hull that does not start where the one before it ends;
+ * a hull or rows that leave the arena; a lane prefix that is not the frames' lane counts; a slot outside [0, m); a
+ * rebased record that is not the store's record moved to the plan's place; and a source data or rows pointer whose
+ * first or last byte hipPointerGetAttributes does not report as device memory or registered host memory (pageable and
+ * managed memory are refused, and the runtime's last-error state is left clean).
+ * Additive: the ABI number stays 26 -- no existing signature or behaviour changed. */
+int coclr_jpeg_store_gather(const coclr_jpeg_store* st, const int64_t* plan, const int64_t* plan_host, int64_t m,
+                            const int64_t* slot_host, const int64_t* frames_host, int64_t n, uint8_t* arena,
+                            int64_t arena_bytes, uint32_t* arena_rows, int64_t arena_nrows, void* stream);
+
 /* coclr_resize_boxes_u8 for frames that differ in size from clip to clip: `frames` is ONE flat byte buffer of nbytes
  * bytes, 16-byte aligned, and a descriptor is int32 [14]: the ten words of coclr_resize_boxes_u8 ({first frame} is
  * not read) followed by {byte offset of the clip's first frame, low word; high word; W; H} of the clip's T frames,
