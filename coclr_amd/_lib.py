@@ -159,6 +159,8 @@ _SIGNATURES = {
     "coclr_jpeg_decode_store_window": [_P(JpegStore), vp, _P(i64), i32, vp, _P(i64), vp, _P(i64), vp, _P(i64), i32, vp,
                                        vp, i64, vp, i64, vp, vp],
     "coclr_jpeg_store_gather": [_P(JpegStore), vp, _P(i64), i64, _P(i64), _P(i64), i64, vp, i64, vp, i64, vp],
+    "coclr_jpeg_store_gather_shards": [_P(_P(JpegStore)), i32, vp, _P(i64), vp, _P(i64), i64, _P(i64), _P(i64), i64, vp,
+                                       i64, vp, i64, vp],
     "coclr_resize_boxes_ragged_u8": [vp, i64, vp, _P(i32), i32, i32, i32, vp, i64, vp, i64, vp, vp],
     "coclr_resize2_boxes_ragged": [vp, i64, vp, _P(i32), i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, i32, _P(f32),
                                    _P(f32), vp, vp, vp],

@@ -900,21 +900,56 @@ extern "C" int coclr_jpeg_decode_store_window(const coclr_jpeg_store* st, const 
 // ---- a selection of store frames copied to a device arena -----------------------------------------------------------
 namespace {
 
-// A lane per 16-byte word: the words of every distinct frame's hull, then its rows (jpeg_core.h: jc_gather_lane).  The
-// source may be pinned host memory: one 16-byte load and one 16-byte store per lane, no byte path.  The plan is the
-// device copy; the four sizes are the host's, and no word outside them is touched whatever the plan holds.
-__global__ __launch_bounds__(256) void jpeg_store_gather_kernel(const uint4* __restrict__ src_data, long src_words,
-                                                                const uint4* __restrict__ src_rows, long src_nrows,
-                                                                const int64_t* __restrict__ plan, long m, long lanes,
-                                                                uint4* __restrict__ arena, long arena_words,
-                                                                uint4* __restrict__ arena_rows, long arena_nrows) {
+// Where a gather's lanes read from.  one_source: the call's single source, in the arguments (coclr_jpeg_store_gather).
+// shard_sources: a by-value table of up to JG_MAX_SHARDS sources and the device column that names each plan row's
+// (coclr_jpeg_store_gather_shards); a row whose shard lies outside the table copies nothing.
+// find(): jpeg_core.h's lane arithmetic held against the lane's own source and the arena -> that source, or null.
+struct jg_source {
+  const uint4* data;
+  long words;                  // the 16-byte words its bytes touch
+  const uint4* rows;
+  long nrows;
+};
+
+struct one_source {
+  jg_source s;
+  __device__ const jg_source* find(const int64_t* plan, long m, long id, long arena_words, long arena_nrows,
+                                   bool* rows, int64_t* src, int64_t* dst) const {
+    return jc_gather_lane(plan, m, id, s.words, s.nrows, arena_words, arena_nrows, rows, src, dst) ? &s : nullptr;
+  }
+};
+
+struct shard_sources {
+  jg_source s[JG_MAX_SHARDS];
+  const int64_t* shard;        // int64 [m], DEVICE
+  long n;
+  __device__ const jg_source* find(const int64_t* plan, long m, long id, long arena_words, long arena_nrows,
+                                   bool* rows, int64_t* src, int64_t* dst) const {
+    int64_t which;
+    if (!jc_gather_lane_from(plan, shard, m, id, s, n, arena_words, arena_nrows, &which, rows, src, dst))
+      return nullptr;
+    return &s[which];
+  }
+};
+
+// A lane per 16-byte word: the words of every distinct frame's hull, then its rows (jpeg_core.h: jc_gather_lane_from).
+// A source may be pinned host memory or a peer's memory: one 16-byte load and one 16-byte store per lane, no byte
+// path.  The plan (and the shard column) is the device copy; the sizes are the host's, by value, and no word outside
+// them is touched whatever the device data holds.
+template <class SRC, class... ARGS>    // ARGS: what SRC is made of, as the kernel's leading arguments
+__global__ __launch_bounds__(256) void jpeg_store_gather_kernel(ARGS... source, const int64_t* __restrict__ plan,
+                                                                long m, long lanes, uint4* __restrict__ arena,
+                                                                long arena_words, uint4* __restrict__ arena_rows,
+                                                                long arena_nrows) {
   const long id = (long)blockIdx.x * 256 + threadIdx.x;
   if (id >= lanes) return;
+  const SRC at{source...};
   bool rows;
   int64_t src, dst;
-  if (!jc_gather_lane(plan, m, id, src_words, src_nrows, arena_words, arena_nrows, &rows, &src, &dst)) return;
-  if (rows) arena_rows[dst] = src_rows[src];
-  else arena[dst] = src_data[src];
+  const jg_source* s = at.find(plan, m, id, arena_words, arena_nrows, &rows, &src, &dst);
+  if (!s) return;
+  if (rows) arena_rows[dst] = s->rows[src];
+  else arena[dst] = s->data[src];
 }
 
 // The address a kernel reads `bytes` bytes at `p` through: device memory, or host memory that is registered with the
@@ -943,17 +978,32 @@ const void* gather_source(const void* p, int64_t bytes) {
 
 }  // namespace
 
-extern "C" int coclr_jpeg_store_gather(const coclr_jpeg_store* st, const int64_t* plan, const int64_t* plan_host,
-                                       int64_t m, const int64_t* slot_host, const int64_t* frames_host, int64_t n,
-                                       uint8_t* arena, int64_t arena_bytes, uint32_t* arena_rows, int64_t arena_nrows,
-                                       void* stream) {
-  if (!store_ok(st) || !plan || !plan_host || !slot_host || !frames_host || !arena || !arena_rows) return COCLR_EINVAL;
-  if (m < 1 || n < m || n > 0x7fffffffL || arena_bytes < 1 || arena_nrows < 1 || st->data_bytes < 1) return COCLR_EINVAL;
-  if (((uintptr_t)st->data & 15) || ((uintptr_t)arena & 15) || ((uintptr_t)arena_rows & 15) || ((uintptr_t)plan & 7))
+namespace {
+
+// a shard of coclr_jpeg_store_gather_shards: store_ok for what a gather reads -- the bytes, the rows and the host
+// tables -- and a shard may be EMPTY
+bool gather_shard_ok(const coclr_jpeg_store* st) {
+  if (!st || !st->data || !st->rows || !st->tables_host) return false;
+  if (st->data_bytes < 1 || st->nframes < 0 || st->table_sets < 0 || st->nsegs < 0 || st->nrows < 1) return false;
+  if ((st->nframes > 0 && !st->frames_host) || (st->nsegs > 0 && !st->segs_host)) return false;
+  if (st->chunk_bytes < 8 || st->chunk_bytes > 65536) return false;
+  return !(((uintptr_t)st->data & 15) || ((uintptr_t)st->rows & 15));
+}
+
+// The body of both gather entries.  `shard_host` null: the one source of coclr_jpeg_store_gather, every row's shard 0.
+int gather_impl(const coclr_jpeg_store* const* shards, int nshards, const int64_t* plan, const int64_t* plan_host,
+                const int64_t* shard, const int64_t* shard_host, int64_t m, const int64_t* slot_host,
+                const int64_t* frames_host, int64_t n, uint8_t* arena, int64_t arena_bytes, uint32_t* arena_rows,
+                int64_t arena_nrows, void* stream) {
+  if (!plan || !plan_host || !slot_host || !frames_host || !arena || !arena_rows) return COCLR_EINVAL;
+  if (m < 1 || n < m || n > 0x7fffffffL || arena_bytes < 1 || arena_nrows < 1) return COCLR_EINVAL;
+  if (((uintptr_t)arena & 15) || ((uintptr_t)arena_rows & 15) || ((uintptr_t)plan & 7) || ((uintptr_t)shard & 7))
     return COCLR_EINVAL;
   int64_t end = 0, rows = 0, lanes = 0;
   for (int64_t j = 0; j < m; ++j) {
     const int64_t* p = plan_host + j * JG_FIELDS;
+    if (shard_host && !jc_gather_order_ok(plan_host, shard_host, j, nshards)) return COCLR_EINVAL;
+    const coclr_jpeg_store* st = shards[shard_host ? shard_host[j] : 0];
     const int64_t f = p[JG_FRAME];
     if (f < 0 || f >= st->nframes) return COCLR_EINVAL;
     jc_store_frame fr;
@@ -979,6 +1029,7 @@ extern "C" int coclr_jpeg_store_gather(const coclr_jpeg_store* st, const int64_t
     const int64_t j = slot_host[i];
     if (j < 0 || j >= m) return COCLR_EINVAL;
     const int64_t* p = plan_host + j * JG_FIELDS;
+    const coclr_jpeg_store* st = shards[shard_host ? shard_host[j] : 0];
     int64_t want[JS_FIELDS];
     jc_gather_rebase(st->frames_host + p[JG_FRAME] * JS_FIELDS, p[JG_DST], p[JG_DSTROW], want);
     for (int k = 0; k < JS_FIELDS; ++k)
@@ -986,13 +1037,52 @@ extern "C" int coclr_jpeg_store_gather(const coclr_jpeg_store* st, const int64_t
   }
   if (lanes < 1) return 0;
   if (!grid_ok(lanes, 256, 0, 0)) return COCLR_EINVAL;
-  const void* data = gather_source(st->data, st->data_bytes);
-  const void* srows = gather_source(st->rows, st->nrows * JS_ROW_WORDS * 4);
-  if (!data || !srows || ((uintptr_t)data & 15) || ((uintptr_t)srows & 15)) return COCLR_EINVAL;
-  hipLaunchKernelGGL(jpeg_store_gather_kernel, dim3(cdiv(lanes, 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const uint4*)data, (long)((st->data_bytes + 15) >> 4), (const uint4*)srows, (long)st->nrows, plan,
-                     (long)m, (long)lanes, (uint4*)arena, (long)(arena_bytes >> 4), (uint4*)arena_rows,
-                     (long)arena_nrows);
+  shard_sources from = {};
+  for (int k = 0; k < nshards; ++k) {                       // every source, whether or not a row reads it
+    const coclr_jpeg_store* st = shards[k];
+    const void* data = gather_source(st->data, st->data_bytes);
+    const void* srows = gather_source(st->rows, st->nrows * JS_ROW_WORDS * 4);
+    if (!data || !srows || ((uintptr_t)data & 15) || ((uintptr_t)srows & 15)) return COCLR_EINVAL;
+    from.s[k] = {(const uint4*)data, (long)((st->data_bytes + 15) >> 4), (const uint4*)srows, (long)st->nrows};
+  }
+  const dim3 grid(cdiv(lanes, 256)), block(256);
+  if (!shard_host) {
+    const jg_source& one = from.s[0];
+    hipLaunchKernelGGL((jpeg_store_gather_kernel<one_source, const uint4* __restrict__, long, const uint4* __restrict__,
+                                                 long>),
+                       grid, block, 0, (hipStream_t)stream, one.data, one.words, one.rows, one.nrows, plan, (long)m,
+                       (long)lanes, (uint4*)arena, (long)(arena_bytes >> 4), (uint4*)arena_rows, (long)arena_nrows);
+  } else {
+    from.shard = shard;
+    from.n = nshards;
+    hipLaunchKernelGGL((jpeg_store_gather_kernel<shard_sources, shard_sources>), grid, block, 0, (hipStream_t)stream,
+                       from, plan, (long)m, (long)lanes, (uint4*)arena, (long)(arena_bytes >> 4), (uint4*)arena_rows,
+                       (long)arena_nrows);
+  }
   COCLR_LAUNCH_CHECK();
   return 0;
+}
+
+}  // namespace
+
+extern "C" int coclr_jpeg_store_gather(const coclr_jpeg_store* st, const int64_t* plan, const int64_t* plan_host,
+                                       int64_t m, const int64_t* slot_host, const int64_t* frames_host, int64_t n,
+                                       uint8_t* arena, int64_t arena_bytes, uint32_t* arena_rows, int64_t arena_nrows,
+                                       void* stream) {
+  if (!store_ok(st) || st->data_bytes < 1 || ((uintptr_t)st->data & 15)) return COCLR_EINVAL;
+  return gather_impl(&st, 1, plan, plan_host, nullptr, nullptr, m, slot_host, frames_host, n, arena, arena_bytes,
+                     arena_rows, arena_nrows, stream);
+}
+
+extern "C" int coclr_jpeg_store_gather_shards(const coclr_jpeg_store* const* shards, int nshards, const int64_t* plan,
+                                              const int64_t* plan_host, const int64_t* shard,
+                                              const int64_t* shard_host, int64_t m, const int64_t* slot_host,
+                                              const int64_t* frames_host, int64_t n, uint8_t* arena,
+                                              int64_t arena_bytes, uint32_t* arena_rows, int64_t arena_nrows,
+                                              void* stream) {
+  if (!shards || nshards < 1 || nshards > JG_MAX_SHARDS || !shard || !shard_host) return COCLR_EINVAL;
+  for (int k = 0; k < nshards; ++k)
+    if (!gather_shard_ok(shards[k]) || shards[k]->chunk_bytes != shards[0]->chunk_bytes) return COCLR_EINVAL;
+  return gather_impl(shards, nshards, plan, plan_host, shard, shard_host, m, slot_host, frames_host, n, arena,
+                     arena_bytes, arena_rows, arena_nrows, stream);
 }

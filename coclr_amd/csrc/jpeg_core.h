@@ -864,11 +864,31 @@ JC_HD long jc_gather_find(const int64_t* plan, long m, int64_t id) {
   return lo;
 }
 
-// Lane `id` of a gather: which 16-byte word it copies.  `rows` says whether the word is a row (then src / dst count
-// rows) or a word of the bytes.  False: the lane has nothing to copy, or its words leave a buffer (sizes in words).
-JC_HD bool jc_gather_lane(const int64_t* plan, long m, int64_t id, int64_t src_words, int64_t src_rows,
-                          int64_t dst_words, int64_t dst_rows, bool* rows, int64_t* src, int64_t* dst) {
-  const int64_t* p = plan + jc_gather_find(plan, m, id) * JG_FIELDS;
+// A sharded gather is the same gather with a SOURCE per plan row: the shards of a store lie in different buffers (the
+// memory of this rank, or a peer's mapped through hipIpc), at most JG_MAX_SHARDS of them, one per GPU of a node.  The
+// int64 column shard[m] names row j's source; JG_FRAME, JG_SRC and JG_SRCROW then count inside THAT shard.  The rules
+// of placement are unchanged -- the congruence is to the frame's first shard byte -- and the rows of a plan are ordered
+// by (shard, frame).
+enum { JG_MAX_SHARDS = 8 };
+
+struct jc_gather_size {
+  int64_t words, nrows;        // one source: the 16-byte words its bytes touch, and its rows
+};
+
+// Lane `id` of a gather over `nshards` sources: which 16-byte word it copies, and from which source.  `Src` is any
+// struct with the members of jc_gather_size (the kernel's table entry carries the two pointers as well); `shard`
+// null: every row reads source 0.  `rows` says whether the word is a row (then src / dst count rows) or a word of the
+// bytes.  False: the lane has nothing to copy, its row names a source outside [0, nshards), or its words leave THAT
+// source or the arena (sizes in words).  Plan and shard column are device data: nothing read from them is trusted.
+template <class Src>
+JC_HD bool jc_gather_lane_from(const int64_t* plan, const int64_t* shard, long m, int64_t id, const Src* srcs,
+                               int64_t nshards, int64_t dst_words, int64_t dst_rows, int64_t* which, bool* rows,
+                               int64_t* src, int64_t* dst) {
+  const long j = jc_gather_find(plan, m, id);
+  const int64_t* p = plan + j * JG_FIELDS;
+  const int64_t w = shard ? shard[j] : 0;
+  if (w < 0 || w >= nshards) return false;
+  *which = w;
   int64_t local = id - p[JG_LANE];
   jc_span s;
   if (local < 0 || !jc_gather_span(p[JG_SRC], p[JG_LEN], p[JG_DST], s)) return false;
@@ -876,7 +896,7 @@ JC_HD bool jc_gather_lane(const int64_t* plan, long m, int64_t id, int64_t src_w
     *rows = false;
     *src = s.src + local;
     *dst = s.dst + local;
-    return *src < src_words && *dst < dst_words;
+    return *src < srcs[w].words && *dst < dst_words;
   }
   local -= s.words;
   const int64_t top = (int64_t)1 << 62;
@@ -885,5 +905,24 @@ JC_HD bool jc_gather_lane(const int64_t* plan, long m, int64_t id, int64_t src_w
   *rows = true;
   *src = p[JG_SRCROW] + local;
   *dst = p[JG_DSTROW] + local;
-  return *src < src_rows && *dst < dst_rows;
+  return *src < srcs[w].nrows && *dst < dst_rows;
+}
+
+// the gather of ONE source (coclr_jpeg_store_gather): the one-shard case of the above
+JC_HD bool jc_gather_lane(const int64_t* plan, long m, int64_t id, int64_t src_words, int64_t src_rows,
+                          int64_t dst_words, int64_t dst_rows, bool* rows, int64_t* src, int64_t* dst) {
+  const jc_gather_size one = {src_words, src_rows};
+  int64_t which;
+  return jc_gather_lane_from(plan, (const int64_t*)nullptr, m, id, &one, 1, dst_words, dst_rows, &which, rows, src,
+                             dst);
+}
+
+// Row j of a sharded plan against the row before it: its source exists and the rows are ordered by (shard, frame),
+// strictly -- a plan holds DISTINCT frames (the refusal of coclr_jpeg_store_gather_shards).
+JC_HD bool jc_gather_order_ok(const int64_t* plan, const int64_t* shard, long j, int64_t nshards) {
+  const int64_t w = shard[j], f = plan[j * JG_FIELDS + JG_FRAME];
+  if (w < 0 || w >= nshards || f < 0) return false;
+  if (j == 0) return true;
+  const int64_t pw = shard[j - 1], pf = plan[(j - 1) * JG_FIELDS + JG_FRAME];
+  return pw < w || (pw == w && pf < f);
 }

@@ -14,6 +14,8 @@ A dataset that fits into the device's memory can stay there compressed: `Store.a
 `Store.decode(ids, boxes)` decodes one pixel box of every frame alone, what staging.stage_train_clips_cropped takes.
 A dataset larger than the device's memory keeps its bytes in pinned host memory, `Store(..., bytes_on="host")`, and a
 built store of either kind is written and read back as data with `Store.save` / `Store.load`.
+A dataset that fits the GPUs of a node but not one of them is sharded: each rank's device Store becomes one shard of a
+`ShardedStore` (`ShardedStore.join`), mapped into its peers through hipIpc, and `decode` takes global ids.
 
 Scope: baseline / extended sequential Huffman (SOF0, SOF1), 8-bit, one interleaved scan, one component or YCbCr with
 luma sampled 1x1, 2x1 or 2x2, optional restart intervals -- what ffmpeg, cv2.imwrite and PIL write by default.
@@ -566,6 +568,80 @@ def _store_policy(chunk_bytes):
     return chunk_bytes
 
 
+def _gather_tables(frames, slot, rec, lanes, records):
+    """The placement of a gather (csrc/jpeg_core.h: JG_*): `frames` the m distinct frames as the plan names them (inside
+    their store, or inside their shard), `rec` their records and `lanes` their entropy lanes, in the order they take in
+    the arena; `slot` the plan entry of each of the n selected frames and `records` their records (a copy, rebased
+    here) -> (plan, slot, records, arena bytes, arena rows)."""
+    src, ln = rec[:, 0], rec[:, 1]
+    words = torch.where(ln > 0, ((src + ln + 15) >> 4) - (src >> 4), torch.zeros_like(ln))
+    dst = ((words.cumsum(0) - words) << 4) + (src & 15)
+    nrows = torch.where(rec[:, 3] == 1, lanes, torch.zeros_like(ln))
+    dstrow = nrows.cumsum(0) - nrows
+    lanes = words + nrows
+    plan = torch.stack([frames, src, ln, dst, rec[:, 6], nrows, dstrow, lanes.cumsum(0) - lanes], 1).contiguous()
+    records[:, 0], records[:, 6] = dst[slot], dstrow[slot]
+    return plan, slot.contiguous(), records, int(words.sum()) << 4, int(nrows.sum())
+
+
+def _arena_views(self, nbytes, nrows):
+    """The kept device arena of `self` (a Store or a ShardedStore), grown to hold `nbytes` and `nrows` -> its views."""
+    # 16 bytes of room, as every store's bytes have; coclr_jpeg_store takes no store without a byte or a row
+    self._arena = Store._grown(self._arena, (max(16, nbytes) + 16,), dtype=torch.uint8, device=self.device)
+    self._arena_rows = Store._grown(self._arena_rows, (max(1, nrows), ops.JS_ROW_WORDS), dtype=torch.int32,
+                                    device=self.device)
+    return self._arena[:max(16, nbytes)], self._arena_rows[:max(1, nrows)]
+
+
+def _decode_store(self, gathers, ids, boxes, max_stage_bytes):
+    """The body of Store.decode and ShardedStore.decode -> (frames, status).  `gathers`: the selection's distinct
+    frames are first copied to the device arena (self.gather_plan, self._gather) and decoded there as frames
+    0 .. F-1; else the kernels read self._buffers() through the selection."""
+    from . import staging
+    window = None
+    if boxes is None:
+        sel, geo, offset, total, stages, blocks = self.plan(ids, max_stage_bytes)
+    else:
+        sel, geo, offset, total, stages, blocks, window = self.plan(ids, max_stage_bytes, boxes)
+    F, device = sel.numel(), self.device
+    gather, moved = None, []
+    if gathers:                                                # the kernels see the arena's frames 0 .. F-1
+        gather = self.gather_plan(sel)
+        sel = torch.arange(F, dtype=torch.int64)
+        moved = [gather[0].reshape(-1), gather[2].reshape(-1)] + [t.reshape(-1) for t in gather[5:]]
+    tables = torch.cat([sel] + [t.reshape(-1) for _, _, geom, prefix in stages for t in (geom, prefix)] + moved +
+                       ([] if window is None else [window.reshape(-1)]))
+    d_tables = tables.to(device)                                             # the selection and every stage's tables
+    d_sel = d_tables[:F]
+    d_window = None if window is None else d_tables[tables.numel() - window.numel():].view(window.shape)
+    pixels = torch.empty((total + 15) & ~15, dtype=torch.uint8, device=device)
+    coefs = torch.empty(blocks * 64, dtype=torch.int16, device=device)
+    planes = torch.empty(blocks * 64, dtype=torch.uint8, device=device)
+    status = torch.empty(F, dtype=torch.int32, device=device)
+    at = F
+    if gather is None:
+        store = self._buffers()
+    else:
+        tail = tables.numel() - (0 if window is None else window.numel())
+        store = self._gather(gather, d_tables[tail - sum(t.numel() for t in moved):tail])
+    for k, e, geom, prefix in stages:
+        d_geom = d_tables[at:at + geom.numel()].view(geom.shape)
+        at += geom.numel()
+        d_prefix = d_tables[at:at + prefix.numel()].view(prefix.shape)
+        at += prefix.numel()
+        if window is None:
+            ops.jpeg_decode_store(store, d_sel[k:e], sel[k:e], d_geom, geom, d_prefix, prefix, coefs, planes,
+                                  pixels, status[k:e])
+        else:
+            ops.jpeg_decode_store_window(store, d_sel[k:e], sel[k:e], d_geom, geom, d_window[k:e], window[k:e],
+                                         d_prefix, prefix, coefs, planes, pixels, status[k:e])
+    if window is None:
+        frames = staging.RaggedFrames(pixels, offset, geo[:, 0].to(torch.int32), geo[:, 1].to(torch.int32))
+    else:
+        frames = staging.RaggedFrames(pixels, offset, window[:, 3].to(torch.int32), window[:, 2].to(torch.int32))
+    return frames, status
+
+
 class Store:
     """A dataset's JPEG frames kept compressed on the device, parsed and validated once, decoded by frame index.
 
@@ -595,9 +671,11 @@ class Store:
 
     `save(path)` writes a built store as data (a JSON header and .npy arrays); `Store.load(path, ...)` reads one back
     as either kind, without parsing or indexing anything, and `add` carries on from there.
-    Not in scope: one host arena shared between ranks, sharding a store across ranks, gathering only the chunks a
-    pixel box needs (whole frames cross the bus), decode kernels that read host memory themselves, and splitting
-    inside the restart segments of frames with restart markers."""
+    A dataset that fits the devices of a NODE but not one of them is sharded: class ShardedStore.
+    Not in scope: one host arena shared between ranks, shards on other nodes, re-balancing shards, a gather that
+    skips the arena for local frames, gathering only the chunks a pixel box needs (whole frames cross the bus), decode
+    kernels that read host memory themselves, and splitting inside the restart segments of frames with restart
+    markers."""
 
     FORMAT_VERSION = 1
     _FILES = ("data", "frames", "tables", "segs", "rows", "geo", "lanes")
@@ -764,28 +842,14 @@ class Store:
         selected frames' records rebased to the arena.  Frame j's first arena byte is congruent to its first store
         byte mod 16 and its hull of whole 16-byte words starts where the one before ends; rows are consecutive."""
         frames, slot = torch.unique(sel, return_inverse=True)
-        rec = self._host[0][frames]
-        src, ln = rec[:, 0], rec[:, 1]
-        words = torch.where(ln > 0, ((src + ln + 15) >> 4) - (src >> 4), torch.zeros_like(ln))
-        dst = ((words.cumsum(0) - words) << 4) + (src & 15)
-        nrows = torch.where(rec[:, 3] == 1, self._lanes[frames], torch.zeros_like(ln))
-        dstrow = nrows.cumsum(0) - nrows
-        lanes = words + nrows
-        plan = torch.stack([frames, src, ln, dst, rec[:, 6], nrows, dstrow, lanes.cumsum(0) - lanes], 1).contiguous()
-        records = self._host[0][sel]                           # (advanced indexing: a copy)
-        records[:, 0], records[:, 6] = dst[slot], dstrow[slot]
-        return plan, slot.contiguous(), records, int(words.sum()) << 4, int(nrows.sum())
+        return _gather_tables(frames, slot, self._host[0][frames], self._lanes[frames], self._host[0][sel])
 
     def _gather(self, gather, d_tables):
         """Copies the planned frames to the device arena, one launch -> the arguments of ops.jpeg_store_desc for the
         arena as a store: data and rows the arena's, frames the rebased records, tables and segment words this
         store's own.  `d_tables`: the plan and the records on the device, one after the other."""
         plan, slot, records, nbytes, nrows = gather
-        # 16 bytes of room, as every store's bytes have; coclr_jpeg_store takes no store without a byte or a row
-        self._arena = self._grown(self._arena, (max(16, nbytes) + 16,), dtype=torch.uint8, device=self.device)
-        self._arena_rows = self._grown(self._arena_rows, (max(1, nrows), ops.JS_ROW_WORDS), dtype=torch.int32,
-                                       device=self.device)
-        arena, arena_rows = self._arena[:max(16, nbytes)], self._arena_rows[:max(1, nrows)]
+        arena, arena_rows = _arena_views(self, nbytes, nrows)
         d_plan = d_tables[:plan.numel()].view(plan.shape)
         d_records = d_tables[plan.numel():].view(records.shape)
         ops.jpeg_store_gather(self._buffers(), d_plan, plan, slot, records, arena, arena_rows)
@@ -844,47 +908,8 @@ class Store:
         ids and boxes from a batch's plans).  A box of a wrong shape or type, smaller than 1 x 1 or leaving its frame
         is a ValueError before any launch.  The status then reports damage met in what WAS decoded only; clean files
         give 0 either way.  The workspace, and so `max_stage_bytes`, still counts full frames."""
-        from . import staging
-        window = None
-        if boxes is None:
-            sel, geo, offset, total, stages, blocks = self.plan(ids, max_stage_bytes)
-        else:
-            sel, geo, offset, total, stages, blocks, window = self.plan(ids, max_stage_bytes, boxes)
-        F, device = sel.numel(), self.device
-        gather = None
-        if self.bytes_on == "host":                            # the kernels see the arena's frames 0 .. F-1
-            gather = self.gather_plan(sel)
-            sel = torch.arange(F, dtype=torch.int64)
-        tables = torch.cat([sel] + [t.reshape(-1) for _, _, geom, prefix in stages for t in (geom, prefix)] +
-                           ([] if gather is None else [gather[0].reshape(-1), gather[2].reshape(-1)]) +
-                           ([] if window is None else [window.reshape(-1)]))
-        d_tables = tables.to(device)                                         # the selection and every stage's tables
-        d_sel = d_tables[:F]
-        d_window = None if window is None else d_tables[tables.numel() - window.numel():].view(window.shape)
-        pixels = torch.empty((total + 15) & ~15, dtype=torch.uint8, device=device)
-        coefs = torch.empty(blocks * 64, dtype=torch.int16, device=device)
-        planes = torch.empty(blocks * 64, dtype=torch.uint8, device=device)
-        status = torch.empty(F, dtype=torch.int32, device=device)
-        store, at = self._buffers(), F
-        if gather is not None:
-            tail = tables.numel() - (0 if window is None else window.numel())
-            store = self._gather(gather, d_tables[tail - gather[0].numel() - gather[2].numel():tail])
-        for k, e, geom, prefix in stages:
-            d_geom = d_tables[at:at + geom.numel()].view(geom.shape)
-            at += geom.numel()
-            d_prefix = d_tables[at:at + prefix.numel()].view(prefix.shape)
-            at += prefix.numel()
-            if window is None:
-                ops.jpeg_decode_store(store, d_sel[k:e], sel[k:e], d_geom, geom, d_prefix, prefix, coefs, planes,
-                                      pixels, status[k:e])
-            else:
-                ops.jpeg_decode_store_window(store, d_sel[k:e], sel[k:e], d_geom, geom, d_window[k:e], window[k:e],
-                                             d_prefix, prefix, coefs, planes, pixels, status[k:e])
+        frames, status = _decode_store(self, self.bytes_on == "host", ids, boxes, max_stage_bytes)
         Store.decode.last_status = status
-        if window is None:
-            frames = staging.RaggedFrames(pixels, offset, geo[:, 0].to(torch.int32), geo[:, 1].to(torch.int32))
-        else:
-            frames = staging.RaggedFrames(pixels, offset, window[:, 3].to(torch.int32), window[:, 2].to(torch.int32))
         return (frames, status) if return_status else frames
 
     _SLICE = 64 << 20        # bytes moved at a time by save and load
@@ -988,6 +1013,279 @@ class Store:
 
 
 Store.decode.last_status = None
+
+
+class _Shard:
+    """What a ShardedStore keeps of one shard: `data` and `rows`, the buffers a gather reads (a Store's own, device or
+    pinned host, or a peer's device buffers mapped through hipIpc), and host copies of its books as they were when the
+    shard was sealed: n frames, nbytes, records (n, 8), table words (sets * 768), segment words, geo (n, 5), lanes (n)."""
+
+    def __init__(self, data, rows, nbytes, rec, tables, segs, geo, lanes):
+        self.data, self.rows, self.nbytes, self.rec, self.tables, self.segs, self.geo, self.lanes = \
+            data, rows, int(nbytes), rec, tables, segs, geo, lanes
+        self.n = rec.shape[0]
+
+    @classmethod
+    def of(cls, store):
+        n, sets = len(store), store.table_sets
+        rec, tables, segs = store._host
+        return cls(store._data, store._rows, store.nbytes, rec[:n].clone(),
+                   tables[ops.JS_TABLE_PAD:ops.JS_TABLE_PAD + sets * ops.JS_TABLE_WORDS].clone(),
+                   segs[:store._segs].clone(), store._geo[:n].clone(), store._lanes[:n].clone())
+
+    def blobs(self):
+        """The books as two flat tensors, int64 and int32, and what `from_blobs` needs to cut them."""
+        return (torch.cat([self.rec.reshape(-1), self.geo.reshape(-1), self.lanes]),
+                torch.cat([self.tables, self.segs]))
+
+    @classmethod
+    def from_blobs(cls, data, rows, nbytes, n, sets, nsegs, i64, i32):
+        w = sets * ops.JS_TABLE_WORDS
+        return cls(data, rows, nbytes, i64[:8 * n].view(n, ops.JS_FIELDS), i32[:w], i32[w:w + nsegs],
+                   i64[8 * n:13 * n].view(n, 5), i64[13 * n:14 * n])
+
+
+_NODE_GROUP = None
+
+
+def _node_group():
+    """The gloo side channel of ShardedStore.join: the world group if that is gloo, else a gloo group of all ranks
+    (built once, as model.pretrain's host group is)."""
+    global _NODE_GROUP
+    import torch.distributed as dist
+    if _NODE_GROUP is None:
+        if os.environ.get("MASTER_ADDR", "") in ("127.0.0.1", "localhost", "::1"):
+            os.environ.setdefault("GLOO_SOCKET_IFNAME", "lo")     # a container need not resolve its own host name
+        _NODE_GROUP = dist.new_group(backend="gloo") if dist.get_backend() != "gloo" else dist.group.WORLD
+    return _NODE_GROUP
+
+
+class ShardedStore:
+    """One dataset's JPEG store in up to 8 shards, one per GPU of a node, decoded by GLOBAL frame index.
+
+        sh = jpeg.ShardedStore([a, b, c])            # the shards are Stores of this process, device or host kind
+        sh = jpeg.ShardedStore.join(store, group)    # collective: this rank's device Store becomes shard `rank`
+        frames = sh.decode(ids)                      # Store.decode's contract, bit for bit
+
+    Every rank of a data-parallel job draws from the whole dataset, so without sharding every rank holds every frame.
+    Here each rank holds 1/W of the compressed bytes in its HBM and maps its peers' buffers through hipIpc; `decode`
+    copies the selection's DISTINCT frames -- local ones included: one path, and a local copy runs at HBM speed -- from
+    whichever shard holds them into a device arena in ONE launch (coclr_jpeg_store_gather_shards, 16 bytes per lane)
+    and decodes them there with Store's kernels.  Frames, status, `decode.last_status`, refusals, boxes and
+    `max_stage_bytes` staging are those of one Store that was given the same packs in global order.
+
+    Ids: a global id is bases[s] + the frame's id inside shard s, `bases` the exclusive running sum of the shards'
+    lengths in shard order; a one-shard ShardedStore has its Store's ids.  A shard may be empty.
+
+    Sealing: the shards' books are copied when the ShardedStore is made and are immutable from then on -- `add` is a
+    ValueError here; a Store passed in is not modified and stays usable on its own, but what is added to it later is
+    not seen here.  The union of the shards' table sets, de-duplicated by their 768 words, is one device array; the
+    shards' restart-segment words, concatenated, another; every record's set index and first segment word are remapped
+    on the sealed host copy.  Shards that differ in chunk_bytes or device, and more than 8, are refused.
+    Replicated on EVERY rank: 112 bytes of host memory per frame of the WHOLE dataset (record 64, geo 40, lanes 8), and
+    on the device 4 bytes per restart segment and 3 KiB per distinct table set.  The compressed bytes and the chunk
+    rows are not replicated.
+
+    Lifetime, the one rule of `join`: a rank must not free its store, or leave, while a peer can still launch a gather
+    on its buffers.  `close()` is the collective that ends that: every rank waits for its own device, drops its
+    mappings and meets the others at a barrier; after it the Store is the rank's own again.
+    The cross-GPU path has run as two processes on ONE device only (unmeasured: no multi-GPU node).
+    Not in scope: shards on other nodes, re-balancing shards, a gather that skips the arena for local frames, one host
+    arena shared between ranks."""
+
+    MAX_SHARDS = ops.JG_MAX_SHARDS
+
+    def __init__(self, shards):
+        shards = list(shards)
+        if not 1 <= len(shards) <= self.MAX_SHARDS or not all(isinstance(s, Store) for s in shards):
+            raise ValueError("coclr_amd: a ShardedStore takes 1..%d Stores, got %d" % (self.MAX_SHARDS, len(shards)))
+        if len({s.chunk_bytes for s in shards}) != 1 or len({s.device for s in shards}) != 1:
+            raise ValueError("coclr_amd: the shards of a store share one chunk_bytes and one device, got %s on %s" %
+                             ([s.chunk_bytes for s in shards], [str(s.device) for s in shards]))
+        self._group = None
+        self._seal([_Shard.of(s) for s in shards], shards[0].chunk_bytes, shards[0].device)
+
+    def _seal(self, parts, chunk_bytes, device):
+        self.chunk_bytes, self.device, self._parts = int(chunk_bytes), device, parts
+        W, T = ops.JS_TABLE_WORDS, ops.JS_TABLE_PAD
+        counts = torch.tensor([p.n for p in parts], dtype=torch.int64)
+        self._ends = counts.cumsum(0)
+        self._bases = self._ends - counts
+        self._frames, self._bytes = int(counts.sum()), sum(p.nbytes for p in parts)
+        self._sets, words, seg0 = {}, [], 0
+        rec = torch.cat([p.rec for p in parts]).clone()
+        for s, p in enumerate(parts):
+            lo, hi = int(self._bases[s]), int(self._ends[s])
+            remap = torch.zeros(max(1, p.tables.numel() // W), dtype=torch.int64)
+            for i in range(p.tables.numel() // W):
+                key = p.tables[i * W:(i + 1) * W].numpy().tobytes()
+                if key not in self._sets:
+                    self._sets[key] = len(self._sets)
+                    words.append(p.tables[i * W:(i + 1) * W])
+                remap[i] = self._sets[key]
+            if bool(((p.rec[:, 4] < 0) | (p.rec[:, 4] >= p.tables.numel() // W)).any()):
+                raise ValueError("coclr_amd: a record of shard %d names a table set the shard does not hold" % s)
+            rec[lo:hi, 4] = remap[p.rec[:, 4]]
+            rec[lo:hi, 5] += seg0
+            seg0 += p.segs.numel()
+        self._segs = seg0
+        tables = torch.cat([torch.zeros(T, dtype=torch.int32)] + words)
+        segs = torch.cat([p.segs for p in parts] + [torch.zeros(0 if seg0 else 1, dtype=torch.int32)])
+        self._host = (rec, tables, segs)                                     # sealed: records, table words, segment words
+        self._dev_tables, self._dev_segs = tables.to(device), segs.to(device)
+        self._geo = torch.cat([p.geo for p in parts])
+        self._lanes = torch.cat([p.lanes for p in parts])
+        self._arena = self._arena_rows = None
+        self._sources = [(p.data, p.rows, rec[int(self._bases[s]):int(self._ends[s])], p.n, tables, len(self._sets),
+                          segs, seg0, self.chunk_bytes) for s, p in enumerate(parts)]
+
+    @classmethod
+    def join(cls, store, group=None):
+        """COLLECTIVE over `group`, a gloo group of the ranks of ONE node (default: the world as a gloo group): this
+        rank's device Store becomes shard `rank` of the store every rank gets back.  Every rank synchronises its
+        device and exports its bytes and rows through hipIpc (torch's IPC tensor sharing carries the handles over the
+        host channel); sizes travel first, then each rank's books as two flat tensors -- no per-frame pickling.  The
+        outcome is the same on every rank: if any rank could not export or map, every rank raises the same
+        RuntimeError and none is sharded.  ValueError: a `bytes_on="host"` store (pinned memory is not exported; that
+        kind is legal in the in-process form), more than 8 ranks, ranks that differ in chunk_bytes."""
+        import torch.distributed as dist
+        from torch.multiprocessing.reductions import reduce_tensor
+        if not isinstance(store, Store) or store.bytes_on != "device":
+            raise ValueError("coclr_amd: ShardedStore.join takes this rank's device Store; a bytes_on='host' store "
+                             "cannot be shared between processes")
+        group = _node_group() if group is None else group
+        world, rank = dist.get_world_size(group), dist.get_rank(group)
+        if store.device.type == "cuda":
+            torch.cuda.synchronize(store.device)
+        mine, handles, err = _Shard.of(store), None, None
+        try:
+            handles = [reduce_tensor(store._data), reduce_tensor(store._rows)]
+        except Exception as e:                                 # hipIpcGetMemHandle refused: still take part
+            err = e
+        i64, i32 = mine.blobs()
+        head = torch.tensor([err is None, mine.n, mine.nbytes, mine.tables.numel() // ops.JS_TABLE_WORDS,
+                             mine.segs.numel(), store.chunk_bytes, store._data.numel(), store._rows.shape[0]],
+                            dtype=torch.int64)
+        heads = [torch.zeros_like(head) for _ in range(world)]
+        dist.all_gather(heads, head, group=group)                            # sizes first
+        heads = torch.stack(heads)
+        if world > cls.MAX_SHARDS or len(set(heads[:, 5].tolist())) != 1:
+            raise ValueError("coclr_amd: ShardedStore.join takes 1..%d ranks of one chunk_bytes, got %d ranks with %s" %
+                             (cls.MAX_SHARDS, world, heads[:, 5].tolist()))
+        objs, parts, mapped = [None] * world, [], []
+        dist.all_gather_object(objs, handles, group=group)
+        for r in range(world):                                               # the books, rank by rank
+            _, n, nbytes, sets, nsegs = heads[r, :5].tolist()
+            a = i64 if r == rank else torch.empty(14 * n, dtype=torch.int64)
+            b = i32 if r == rank else torch.empty(sets * ops.JS_TABLE_WORDS + nsegs, dtype=torch.int32)
+            for t in (a, b):
+                if t.numel():
+                    dist.broadcast(t, src=dist.get_global_rank(group, r), group=group)
+            parts.append((nbytes, n, sets, nsegs, a, b))
+        try:
+            if err is None and (not bool(heads[:, 0].all()) or any(o is None for o in objs)):
+                raise RuntimeError("a peer could not export its buffers")
+            for r in range(world if err is None else 0):
+                if r == rank:
+                    data, rows = store._data, store._rows
+                else:
+                    data, rows = [fn(*args) for fn, args in objs[r]]
+                    mapped.extend([data, rows])
+                    if data.dtype != torch.uint8 or data.numel() != int(heads[r, 6]) or rows.dtype != torch.int32 or \
+                            tuple(rows.shape) != (int(heads[r, 7]), ops.JS_ROW_WORDS):
+                        raise RuntimeError("rank %d's mapped buffers are not what it announced" % r)
+                    for t in (data, rows):
+                        if t.device != store.device:
+                            t.reshape(-1)[:1].to(store.device)               # makes torch enable peer access to it
+                parts[r] = _Shard.from_blobs(data, rows, *parts[r])
+        except Exception as e:                                 # hipIpc across devices / processes refused here
+            err = e
+        ok = torch.tensor([0 if err is not None else 1], dtype=torch.int32)
+        dist.all_reduce(ok, op=dist.ReduceOp.MIN, group=group)               # agree, as pretrain._peer_stage does
+        if int(ok) == 0:
+            del mapped, parts
+            raise RuntimeError("coclr_amd: ShardedStore.join: a rank could not export or map a shard's buffers "
+                               "through hipIpc; no rank is sharded") from err
+        self = cls.__new__(cls)
+        self._group, self._mapped, self._own = group, mapped, store          # the mapped tensors are kept alive
+        self._seal(parts, store.chunk_bytes, store.device)
+        return self
+
+    def close(self):
+        """Drops the peers' mappings; after it `decode` is a ValueError.  For a joined store a COLLECTIVE: every rank
+        waits for its own device (its gathers on its peers' buffers are done), drops its mappings, and leaves through
+        a barrier -- so that no rank frees its store, or exits, while a peer can still launch a gather on it."""
+        if self._parts is None:
+            return
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        self._parts = self._sources = self._arena = self._arena_rows = None
+        if self._group is not None:
+            import torch.distributed as dist
+            self._mapped = self._own = None
+            dist.barrier(group=self._group)
+
+    def __len__(self):
+        return self._frames
+
+    @property
+    def nbytes(self):
+        """Compressed bytes held by all shards."""
+        return self._bytes
+
+    @property
+    def table_sets(self):
+        """Distinct sets of quantisers and Huffman tables in the union."""
+        return len(self._sets)
+
+    @property
+    def bases(self):
+        """int64 (shards,): the global id of every shard's frame 0."""
+        return self._bases.clone()
+
+    def shard_of(self, ids):
+        """The shard of every global id (int64, the shape of `ids`); ids outside [0, len) are a ValueError."""
+        ids = torch.as_tensor(ids).to("cpu", torch.int64)
+        if bool(((ids < 0) | (ids >= self._frames)).any()):
+            raise ValueError("coclr_amd: ids must lie in [0, %d)" % self._frames)
+        return torch.searchsorted(self._ends, ids.contiguous(), right=True)
+
+    frame_size = Store.frame_size
+    plan = Store.plan                                      # on the global geo and lanes
+
+    def add(self, pack):
+        raise ValueError("coclr_amd: a ShardedStore is sealed; add to a Store before it becomes a shard")
+
+    def gather_plan(self, sel):
+        """Store.gather_plan for global ids -> its tuple and, sixth, the shard column int64 (m,): the m distinct frames
+        ordered by (shard, frame) -- which is the order of their global ids -- with plan[:, 0] the frame's id INSIDE its
+        shard, bytes and rows counted there, and the congruence held to the frame's first shard byte."""
+        frames, slot = torch.unique(sel, return_inverse=True)
+        shard = self.shard_of(frames)
+        rec = self._host[0]
+        return _gather_tables(frames - self._bases[shard], slot, rec[frames], self._lanes[frames], rec[sel]) + \
+            (shard.contiguous(),)
+
+    def _gather(self, gather, d_tables):
+        """Store._gather over the shards; `d_tables`: plan, records and shard column on the device, in that order."""
+        plan, slot, records, nbytes, nrows, shard = gather
+        arena, arena_rows = _arena_views(self, nbytes, nrows)
+        a, b = plan.numel(), plan.numel() + records.numel()
+        d_plan, d_records = d_tables[:a].view(plan.shape), d_tables[a:b].view(records.shape)
+        ops.jpeg_store_gather_shards(self._sources, d_plan, plan, d_tables[b:], shard, slot, records, arena, arena_rows)
+        return (arena, d_records, records, records.shape[0], self._dev_tables, self._host[1], len(self._sets),
+                self._dev_segs, self._host[2], self._segs, arena_rows, self.chunk_bytes)
+
+    def decode(self, ids, boxes=None, return_status=False, max_stage_bytes=256 << 20):
+        """Store.decode for global ids: the same plan, the shard gather, the same kernels on the arena."""
+        if self._parts is None:
+            raise ValueError("coclr_amd: the ShardedStore was closed")
+        frames, status = _decode_store(self, True, ids, boxes, max_stage_bytes)
+        ShardedStore.decode.last_status = Store.decode.last_status = status
+        return (frames, status) if return_status else frames
+
+
+ShardedStore.decode.last_status = None
 
 
 def decode_frames(raws, out=None, device=None, max_stage_bytes=256 << 20, chunk_bytes=None):

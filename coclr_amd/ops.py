@@ -1322,6 +1322,55 @@ def jpeg_store_gather(store, plan, plan_host, slot_host, frames_host, arena, are
     _lib.check(rc, "jpeg_store_gather")
 
 
+JG_MAX_SHARDS = 8    # csrc/jpeg_core.h: the sources of one sharded gather, one per GPU of a node
+
+
+def jpeg_shard_desc(data, rows, frames_host, nframes, tables_host, table_sets, segs_host, nsegs, chunk_bytes):
+    """The `coclr_jpeg_store` of ONE SOURCE of jpeg_store_gather_shards: data uint8 flat and rows int32 (capacity, 4),
+    on the device (this process's memory or a peer's mapped buffer) or pinned on the host; the host tables the shard's
+    records are read against: frames_host int64 (>= nframes, 8), tables_host int32, segs_host int32.  The device
+    tables of a store are not part of a source; a shard may hold no frame."""
+    if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous() or rows.dtype != torch.int32 or \
+            not rows.is_contiguous() or rows.numel() % JS_ROW_WORDS:
+        raise ValueError("coclr_amd: a shard's bytes are flat uint8 and its rows contiguous int32 (n, 4)")
+    for host, ty in ((frames_host, torch.int64), (tables_host, torch.int32), (segs_host, torch.int32)):
+        if host.dtype != ty or host.is_cuda or not host.is_contiguous():
+            raise ValueError("coclr_amd: a shard's tables are contiguous host tensors")
+    if frames_host.numel() < nframes * JS_FIELDS or tables_host.numel() < JS_TABLE_PAD + table_sets * JS_TABLE_WORDS or \
+            segs_host.numel() < nsegs:
+        raise ValueError("coclr_amd: a shard's tables do not hold what it says is filled")
+    return _lib.JpegStore(data.data_ptr(), data.numel(), None, frames_host.data_ptr() if nframes else None,
+                          int(nframes), None, tables_host.data_ptr(), int(table_sets), None,
+                          segs_host.data_ptr() if nsegs else None, int(nsegs), rows.data_ptr(),
+                          rows.numel() // JS_ROW_WORDS, int(chunk_bytes))
+
+
+def jpeg_store_gather_shards(shards, plan, plan_host, shard, shard_host, slot_host, frames_host, arena, arena_rows):
+    """jpeg_store_gather over several sources (include/coclr_hip.h: coclr_jpeg_store_gather_shards): `shards` the
+    arguments of jpeg_shard_desc per source, 1..8 of them; plan int64 (m, 8) and shard int64 (m,) on the device with
+    plan_host and shard_host; the rest as jpeg_store_gather."""
+    if not 1 <= len(shards) <= JG_MAX_SHARDS:
+        raise ValueError("coclr_amd: a sharded gather has 1..%d sources, got %d" % (JG_MAX_SHARDS, len(shards)))
+    descs = [jpeg_shard_desc(*s) for s in shards]
+    m, n = plan_host.shape[0], slot_host.numel()
+    for t, want, what in ((plan, (m, JG_FIELDS), "plan"), (plan_host, (m, JG_FIELDS), "plan"),
+                          (shard, (m,), "shard column"), (shard_host, (m,), "shard column"),
+                          (slot_host, (n,), "slots"), (frames_host, (n, JS_FIELDS), "rebased records")):
+        if tuple(t.shape) != want or t.dtype != torch.int64 or not t.is_contiguous() or \
+                (t is not plan and t is not shard and t.is_cuda):
+            raise ValueError("coclr_amd: the %s of a gather must be contiguous int64 %s" % (what, want))
+    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous() or \
+            arena_rows.dtype != torch.int32 or not arena_rows.is_contiguous():
+        raise ValueError("coclr_amd: jpeg_store_gather_shards needs a flat uint8 arena and int32 rows")
+    hp = lambda t: C.cast(t.data_ptr(), C.POINTER(C.c_int64))                # noqa: E731
+    table = (C.POINTER(_lib.JpegStore) * len(descs))(*[C.pointer(d) for d in descs])
+    rc = _L().coclr_jpeg_store_gather_shards(table, len(descs), _p(plan, torch.int64), hp(plan_host),
+                                             _p(shard, torch.int64), hp(shard_host), m, hp(slot_host), hp(frames_host),
+                                             n, _p(arena, torch.uint8), arena.numel(), _p(arena_rows, torch.int32),
+                                             arena_rows.numel() // JS_ROW_WORDS, _stream())
+    _lib.check(rc, "jpeg_store_gather_shards")
+
+
 def resize_boxes_ragged_u8(pixels, desc, desc_host, xtab, ytab, T, S, out):
     """resize_boxes_u8 over a flat byte buffer of frames that differ in size from clip to clip: desc int32
     (n_clips, 14), the ten words of resize_boxes_u8 then {offset low, offset high, W, H} of the clip's frames

@@ -919,6 +919,35 @@ int coclr_jpeg_store_gather(const coclr_jpeg_store* st, const int64_t* plan, con
                             const int64_t* slot_host, const int64_t* frames_host, int64_t n, uint8_t* arena,
                             int64_t arena_bytes, uint32_t* arena_rows, int64_t arena_nrows, void* stream);
 
+/* coclr_jpeg_store_gather with a SOURCE per plan row: the shards of one dataset lie in different buffers -- stores of
+ * this process, device or pinned host, or the device memory of another rank of the node mapped through hipIpc
+ * (coclr_amd/jpeg.py: class ShardedStore) -- and one launch copies the selection's distinct frames from whichever
+ * shard holds them into the arena, which is then decoded exactly as there.
+ * shards: nshards (1..8, JG_MAX_SHARDS: one per GPU of a node) sources.  Of each only data, data_bytes, rows, nrows,
+ *   chunk_bytes and the HOST tables are read: frames_host (its own nframes records, bytes and rows counted inside the
+ *   shard; may be null when nframes is 0: a shard may be empty), tables_host / table_sets and segs_host / nsegs as the
+ *   records name them.  frames, tables and segs (DEVICE) may be null.  data and rows as coclr_jpeg_store_gather's.
+ * plan, plan_host: as coclr_jpeg_store_gather, with {frame, first byte, first row} counted inside the row's own shard
+ *   and the congruence held to the frame's first SHARD byte.
+ * shard: int64 [m], DEVICE, and shard_host: the source of every plan row.  Rows are ordered by (shard, frame), strictly.
+ * slot_host, frames_host, arena, arena_rows: as coclr_jpeg_store_gather; a rebased record is its shard's record moved.
+ * The kernel is coclr_jpeg_store_gather's with a by-value table {data, words, rows, nrows} per source: a lane reads its
+ * row's shard from the device column, returns when that lies outside [0, nshards), and holds its word against THAT
+ * source's sizes and the arena's.  Whatever the device plan and shard column hold, nothing outside the buffers is
+ * touched.
+ * COCLR_EINVAL before any launch: what coclr_jpeg_store_gather refuses, per row against the row's own shard; nshards
+ * outside 1..8; a null shard (or one without data, rows or host tables); shards that differ in chunk_bytes; a shard
+ * index outside [0, nshards); rows not ordered by (shard, frame); and ANY shard's data or rows pointer -- read by a
+ * row or not -- whose first or last byte hipPointerGetAttributes does not report as device memory or registered host
+ * memory (the runtime's last-error state is left clean).  A buffer opened from a hipIpc handle has to pass that same
+ * query: no launch on an address the runtime has not vouched for.
+ * Additive: the ABI number stays 26 -- no existing signature or behaviour changed. */
+int coclr_jpeg_store_gather_shards(const coclr_jpeg_store* const* shards, int nshards, const int64_t* plan,
+                                   const int64_t* plan_host, const int64_t* shard, const int64_t* shard_host,
+                                   int64_t m, const int64_t* slot_host, const int64_t* frames_host, int64_t n,
+                                   uint8_t* arena, int64_t arena_bytes, uint32_t* arena_rows, int64_t arena_nrows,
+                                   void* stream);
+
 /* coclr_resize_boxes_u8 for frames that differ in size from clip to clip: `frames` is ONE flat byte buffer of nbytes
  * bytes, 16-byte aligned, and a descriptor is int32 [14]: the ten words of coclr_resize_boxes_u8 ({first frame} is
  * not read) followed by {byte offset of the clip's first frame, low word; high word; W; H} of the clip's T frames,
