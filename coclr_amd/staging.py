@@ -26,6 +26,9 @@ reference's draws on the host, then every clip's RandomSizedCrop box and its Col
 The classifier's transform (eval/main_classifier.py:729-744) is `ClassifierTransform` + `stage_classifier_clips`: the
 draws of RandomSizedCrop(consistent=True) with its ten attempts and its Scale + CenterCrop fallback, then both bicubic
 resizes (to 224, then to img_dim) in ONE launch, the clip's ColorJitter and the loop's batch flip in a second.
+CoCLR's two-stream samples (main_coclr.py:447-473; dataset/lmdb_dataset.py:498-509), 4 T frames of RGB and flow under
+the chain at seq_len = 2 T, are `stage_two_stream_clips` and its ragged and cropped forms: the same kernels on another
+decomposition of a sample into clips, landing in the tensors CoCLR.forward reads (`TwoStreamClips`).
 """
 import math
 import numbers
@@ -497,9 +500,11 @@ def augment(frames_u8, programs, group_size, T, mean=IMAGENET_MEAN, std=IMAGENET
 
 
 class TrainTransform:
-    """The reference's training transform (main_nce.py:366-390, the same chain in main_coclr.py) as a source of
-    PLANS: `draw` consumes `random` and `np.random` exactly as `transform(seq)` does on 2 * seq_len frames and says
-    what it would do; stage_train_clips does it on the GPU.  A plan is a dict
+    """The reference's training transform (main_nce.py:366-390) as a source of PLANS: `draw` consumes `random` and
+    `np.random` exactly as `transform(seq)` does on 2 * seq_len frames and says what it would do; stage_train_clips
+    does it on the GPU.  main_coclr.py:447-473 is the same chain at `seq_len = args.seq_len * 2` on 4 T frames, RGB and
+    flow: TrainTransform(img_dim, 2 * T) draws its plans and stage_two_stream_clips stages them (the two-stream
+    section below; tests/golden/two_stream_transform.pt).  A plan is a dict
         half      (a, b): which half of the 2T frames clip 0 / clip 1 reads (0 or 1)
         box       ((x0, y0, w, h), (x0, y0, w, h)): RandomSizedCrop's box per clip (the whole frame when its draw
                   does not fit)
@@ -669,16 +674,21 @@ def _axis_tables(keys, make):
     return torch.from_numpy(np.concatenate(bufs[0])), torch.from_numpy(np.concatenate(bufs[1])), words
 
 
-def check_train_plans(plans, B, T, W, H):
+def check_train_plans(plans, B, T, W, H, slots=None):
     """`plans` (a list of B plans, or the stacked packed tensor) -> (descriptor rows without table fields, per-frame
-    programs of all B * 2 clips), refused here, on the host, when a plan is not one the kernels take."""
+    programs of all B * 2 clips), refused here, on the host, when a plan is not one the kernels take.
+    `slots`: two_stream_slots(reverse) for two-stream samples of 4 T frames.  A plan clip then has 2 T programs and
+    becomes one clip of T frames per slot (clip c, stream s) that names it: quarter 2 half[c] + s of the sample's
+    frames, box[c], programs s T .. s T + T - 1.  The rows are slot-major -- len(slots) * B clips -- as the outputs are."""
     plans = _plan_list(plans, unpack_plan, 2)
     if len(plans) != B:
         raise ValueError("coclr_amd: %d plans for %d samples" % (len(plans), B))
-    rows, programs = [], []
-    for b, plan in enumerate(plans):
+    per_clip = T if slots is None else 2 * T
+    checked = []
+    for plan in plans:
         if len(plan["half"]) != 2 or len(plan["box"]) != 2 or len(plan["programs"]) != 2:
             raise ValueError("coclr_amd: a plan names two clips")
+        checked.append([])
         for c in range(2):
             half = plan["half"][c]
             x0, y0, w, h = plan["box"][c]
@@ -687,11 +697,23 @@ def check_train_plans(plans, B, T, W, H):
             if any(int(v) != v for v in (x0, y0, w, h)) or x0 < 0 or y0 < 0 or w < 1 or h < 1 or x0 + w > W or y0 + h > H:
                 raise ValueError("coclr_amd: box (%r, %r, %r, %r) leaves the %d x %d frame" % (x0, y0, w, h, W, H))
             progs = [list(p) for p in plan["programs"][c]]
-            if len(progs) != T:
-                raise ValueError("coclr_amd: a plan has one program per frame, got %d for T = %d" % (len(progs), T))
-            rows.append((b * 2 * T + int(half) * T, T, int(x0), int(y0), int(w), int(h)))
-            programs.append(progs)
-    distinct = {tuple(tuple(op) for op in p) for progs in programs for p in progs}
+            if len(progs) != per_clip:
+                raise ValueError("coclr_amd: a plan has one program per frame%s, got %d for T = %d" %
+                                 ("" if slots is None else " of both streams, 2 T", len(progs), T))
+            checked[-1].append((int(half), (int(x0), int(y0), int(w), int(h)), progs))
+    rows, programs = [], []
+    if slots is None:
+        for b, clips in enumerate(checked):
+            for half, box, progs in clips:
+                rows.append((b * 2 * T + half * T, T) + box)
+                programs.append(progs)
+    else:
+        for c, s in slots:
+            for b, clips in enumerate(checked):
+                half, box, progs = clips[c]
+                rows.append((b * 4 * T + (2 * half + s) * T, T) + box)
+                programs.append(progs[s * T:(s + 1) * T])
+    distinct = {tuple(tuple(op) for op in p) for clips in checked for _, _, progs in clips for p in progs}
     augment_tables([list(p) for p in distinct])                    # refuses a bad op
     return rows, programs
 
@@ -708,29 +730,63 @@ def _train_tables(rows, programs, rag, T, S):
     return desc, xtab, ytab, kinds, params, T if per_clip else 1
 
 
-def train_tables(plans, B, T, W, H, S):
+def train_tables(plans, B, T, W, H, S, slots=None):
     """The host side of stage_train_clips for B samples of 2 T frames of W x H staged to S x S: checks the plans and
     returns (desc int32 (2B, 10), xtab, ytab int32, kinds int32 (G, P), params fp32 (G, P), group_size) as the
-    two entry points take them, all on the host.  May be computed ahead (stage_train_clips(tables=))."""
-    rows, programs = check_train_plans(plans, B, T, W, H)
+    two entry points take them, all on the host.  May be computed ahead (stage_train_clips(tables=)).
+    `slots`: as check_train_plans takes it, for samples of 4 T frames; desc is then (len(slots) B, 10)."""
+    rows, programs = check_train_plans(plans, B, T, W, H, slots)
     return _train_tables(rows, programs, [[]] * len(rows), T, S)
 
 
-def _stage_train(resize, frames, device, tables, B, T, S, mean, std, out):
-    """The tail of stage_train_clips and stage_train_clips_ragged: `out` checked, the frames uploaded, the two
-    launches.  `frames`: (B, 2T, H, W, 3), or the flat bytes of a RaggedFrames; `resize`: the form of
-    ops.resize_boxes_u8 that takes them."""
+def _stage_train(resize, frames, device, tables, lead, T, S, mean, std, out):
+    """The tail of every stage_train_clips_* and stage_two_stream_clips_*: `out` checked, the frames uploaded, the
+    two launches.  `frames`: (B, n, H, W, 3), or the flat bytes of a RaggedFrames; `resize`: the form of
+    ops.resize_boxes_u8 that takes them; `lead`: the leading dimensions of the result, lead + (3, T, S, S), whose
+    product is the number of clips in `tables` -- clip k of the descriptors is clip k of the result."""
     desc, xtab, ytab, kinds, params, group_size = tables
-    _check_out(out, (B, 2, 3, T, S, S))
+    shape, n_clips = tuple(lead) + (3, T, S, S), desc.shape[0]
+    assert math.prod(lead) == n_clips
+    _check_out(out, shape)
     frames = _upload(frames, device)
     device = frames.device
-    u8 = torch.empty(B * 2 * T, S, S, 3, dtype=torch.uint8, device=device)
+    u8 = torch.empty(n_clips * T, S, S, 3, dtype=torch.uint8, device=device)
     if out is None:
-        out = torch.empty(B, 2, 3, T, S, S, dtype=torch.float32, device=device)
+        out = torch.empty(shape, dtype=torch.float32, device=device)
     resize(frames, desc.to(device), desc, xtab.to(device), ytab.to(device), T, S, u8)
     ops.augment_clips(u8, kinds.to(device), params.to(device), group_size, T, mean, std,
-                      out.view(B * 2, 3, T, S, S), host_tables=(kinds, params))
+                      out.view(n_clips, 3, T, S, S), host_tables=(kinds, params))
     return out
+
+
+def _result_lead(slots, B):
+    """The leading dimensions of a staged batch: (B, 2), or two streams' (2, 2, B) / (3, B) (TwoStreamClips)."""
+    return (B, 2) if slots is None else (2, 2, B) if len(slots) == 4 else (len(slots), B)
+
+
+def _train_clips(who, slots, frames_u8, plans, out_size, mean, std, out, device, tables=None):
+    """The body of stage_train_clips (slots None: a sample is 2 T frames) and stage_two_stream_clips (slots of
+    two_stream_slots: 4 T frames)."""
+    parts = 2 if slots is None else 4
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() not in (4, 5) or frames_u8.shape[-1] != 3:
+        raise ValueError("coclr_amd: frames must be uint8 (B, %dT, H, W, 3) or (%dT, H, W, 3), got %s %s" %
+                         (parts, parts, frames_u8.dtype, tuple(frames_u8.shape)))
+    if frames_u8.dim() == 4:
+        frames_u8 = frames_u8[None]
+        if isinstance(plans, dict):
+            plans = [plans]
+    B, n, H, W = frames_u8.shape[:4]
+    if B < 1 or n < parts or n % parts != 0 or H < 1 or W < 1:
+        raise ValueError("coclr_amd: a sample is %d T frames, got %s" % (parts, tuple(frames_u8.shape)))
+    T, S = n // parts, int(out_size)
+    if S < 1 or S * S > JITTER_MAX_PIXELS:
+        raise ValueError("coclr_amd: %s takes an output size of 1..224, got %d" % (who, S))
+    if tables is None:
+        tables = train_tables(plans, B, T, W, H, S, slots)
+    lead = _result_lead(slots, B)
+    if tuple(tables[0].shape) != (math.prod(lead), 10):
+        raise ValueError("coclr_amd: tables for %d clips, frames for %d" % (tables[0].shape[0], math.prod(lead)))
+    return _stage_train(ops.resize_boxes_u8, frames_u8, device, tables, lead, T, S, mean, std, out)
 
 
 def stage_train_clips(frames_u8, plans, out_size, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None, device=None,
@@ -743,24 +799,7 @@ def stage_train_clips(frames_u8, plans, out_size, mean=IMAGENET_MEAN, std=IMAGEN
     Returns (B, 2, 3, T, S, S) fp32 on the device: what `model(...)` takes after the script's `tr()`.
     A bad plan is refused here before anything is launched.  S up to 224 (the augment kernel's frame limit).
     `tables`: train_tables(plans, ...) computed ahead; `plans` is then not read."""
-    if frames_u8.dtype != torch.uint8 or frames_u8.dim() not in (4, 5) or frames_u8.shape[-1] != 3:
-        raise ValueError("coclr_amd: frames must be uint8 (B, 2T, H, W, 3) or (2T, H, W, 3), got %s %s" %
-                         (frames_u8.dtype, tuple(frames_u8.shape)))
-    if frames_u8.dim() == 4:
-        frames_u8 = frames_u8[None]
-        if isinstance(plans, dict):
-            plans = [plans]
-    B, T2, H, W = frames_u8.shape[:4]
-    if B < 1 or T2 < 2 or T2 % 2 != 0 or H < 1 or W < 1:
-        raise ValueError("coclr_amd: a sample is 2 T frames, got %s" % (tuple(frames_u8.shape),))
-    T, S = T2 // 2, int(out_size)
-    if S < 1 or S * S > JITTER_MAX_PIXELS:
-        raise ValueError("coclr_amd: stage_train_clips takes an output size of 1..224, got %d" % S)
-    if tables is None:
-        tables = train_tables(plans, B, T, W, H, S)
-    if tuple(tables[0].shape) != (2 * B, 10):
-        raise ValueError("coclr_amd: tables for %d clips, frames for %d" % (tables[0].shape[0], 2 * B))
-    return _stage_train(ops.resize_boxes_u8, frames_u8, device, tables, B, T, S, mean, std, out)
+    return _train_clips("stage_train_clips", None, frames_u8, plans, out_size, mean, std, out, device, tables)
 
 
 # ---- the classifier's transform (eval/main_classifier.py:729-744,216-220; utils/augmentation.py:21-58,90-146) --------
@@ -1138,22 +1177,85 @@ def _rag_words(offset, W, H):
     return [lo - (1 << 32) if lo >= 1 << 31 else lo, offset >> 32, W, H]
 
 
-def train_tables_ragged(plans, samples, T, S):
+def _slot_major(per_sample, slots):
+    """Per sample its clips, in check_train_plans' order for one plan -> the clips of the batch in the order of the
+    result: sample by sample, or (two streams) slot by slot."""
+    return [clip for group in (per_sample if slots is None else zip(*per_sample)) for clip in group]
+
+
+def train_tables_ragged(plans, samples, T, S, slots=None):
     """train_tables for samples of differing frame sizes: `samples` [(byte offset of the sample's first frame, W, H)];
     every plan is checked against its own sample's (W, H).  Returns (desc int32 (2B, 14), xtab, ytab, kinds, params,
-    group_size) as coclr_resize_boxes_ragged_u8 and coclr_augment_clips take them, all on the host."""
+    group_size) as coclr_resize_boxes_ragged_u8 and coclr_augment_clips take them, all on the host.
+    `slots`: as check_train_plans takes it; a sample's offset is then FOUR, one per quarter of its 4 T frames (None: not
+    decoded, refused when a slot reads it), and desc is (len(slots) B, 14), slot-major."""
     plans = _plan_list(plans, unpack_plan, 2)
     if len(plans) != len(samples):
         raise ValueError("coclr_amd: %d plans for %d samples" % (len(plans), len(samples)))
-    rows, programs, rag = [], [], []
-    for plan, (offset, W, H) in zip(plans, samples):
-        r, p = check_train_plans([plan], 1, T, W, H)
+    per_sample = []
+    for b, (plan, (offset, W, H)) in enumerate(zip(plans, samples)):
+        r, p = check_train_plans([plan], 1, T, W, H, slots)
         stride = (3 * H * W + RAGGED_ALIGN - 1) & ~(RAGGED_ALIGN - 1)
-        for row in r:                                            # row[0]: the clip's first frame within its sample
-            rows.append((0,) + row[1:])
-            rag.append(_rag_words(offset + row[0] * stride, W, H))
-        programs.extend(p)
+        clips = []
+        for row, progs in zip(r, p):                             # row[0]: the clip's first frame within its sample
+            at = offset + row[0] * stride if slots is None else offset[row[0] // T]
+            if at is None:
+                raise ValueError("coclr_amd: a staged clip of sample %d reads quarter %d of its frames, which is marked "
+                                 "as not decoded" % (b, row[0] // T))
+            clips.append(((0,) + row[1:], _rag_words(at, W, H), progs))
+        per_sample.append(clips)
+    rows, rag, programs = zip(*_slot_major(per_sample, slots))
     return _train_tables(rows, programs, rag, T, S)
+
+
+def _train_head(who, slots, plans, out_size):
+    """The head of the ragged and the cropped forms, where T comes from the plans: (plans as a list, B, T, S)."""
+    plans = _plan_list([plans] if isinstance(plans, dict) else plans, unpack_plan, 2)
+    B, S = len(plans), int(out_size)
+    if B < 1:
+        raise ValueError("coclr_amd: %s needs at least one plan" % who)
+    n = len(plans[0]["programs"][0])
+    if n < 1 or (slots is not None and n % 2 != 0):
+        raise ValueError("coclr_amd: a plan has one program per frame%s, got %d" %
+                         ("" if slots is None else " of both streams, 2 T (TrainTransform(img_dim, 2 * T))", n))
+    if S < 1 or S * S > JITTER_MAX_PIXELS:
+        raise ValueError("coclr_amd: %s takes an output size of 1..224, got %d" % (who, S))
+    return plans, B, n if slots is None else n // 2, S
+
+
+def _ragged_quarters(frames, B, T, first):
+    """_ragged_samples for two-stream samples, whose four quarters of T frames need not follow each other: `first`
+    (B, 4), the first frame of each quarter (default 4 T b + T q), -1 where a quarter was not decoded.  Each quarter is
+    checked as _ragged_samples checks a sample, and the quarters of a sample must share one size.  Returns per sample
+    ((byte offset per quarter, None for a missing one), W, H)."""
+    if first is None:
+        first = [[4 * T * b + T * q for q in range(4)] for b in range(B)]
+    else:
+        first = torch.as_tensor(first)
+        if first.is_floating_point() or first.is_complex() or first.dtype == torch.bool or tuple(first.shape) != (B, 4):
+            raise ValueError("coclr_amd: first must be integers of shape (%d, 4), the first frame of each quarter, got %s "
+                             "%s" % (B, first.dtype, tuple(first.shape)))
+        first = first.tolist()
+    there = [(b, q) for b in range(B) for q in range(4) if first[b][q] != -1]
+    got = dict(zip(there, _ragged_samples(frames, len(there), T, [first[b][q] for b, q in there]))) if there else {}
+    out = []
+    for b in range(B):
+        sizes = {got[b, q][1:] for q in range(4) if (b, q) in got}
+        if len(sizes) != 1:
+            raise ValueError("coclr_amd: the quarters of sample %d hold frames of %d sizes; the RGB and the flow frames "
+                             "of one sample share one size" % (b, len(sizes)))
+        (W, H), = sizes
+        out.append(([got[b, q][0] if (b, q) in got else None for q in range(4)], W, H))
+    return out
+
+
+def _train_clips_ragged(who, slots, frames, plans, out_size, first, mean, std, out):
+    """The body of stage_train_clips_ragged (slots None) and stage_two_stream_clips_ragged."""
+    plans, B, T, S = _train_head(who, slots, plans, out_size)
+    samples = _ragged_samples(frames, B, 2 * T, first) if slots is None else _ragged_quarters(frames, B, T, first)
+    tables = train_tables_ragged(plans, samples, T, S, slots)
+    return _stage_train(ops.resize_boxes_ragged_u8, frames.pixels, frames.pixels.device, tables, _result_lead(slots, B),
+                        T, S, mean, std, out)
 
 
 def stage_train_clips_ragged(frames, plans, out_size, first=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
@@ -1162,18 +1264,7 @@ def stage_train_clips_ragged(frames, plans, out_size, first=None, mean=IMAGENET_
     frames: RaggedFrames.  Sample b is frames first[b] .. first[b] + 2T - 1 (default first[b] = 2 T b), which share
     one size; T comes from the plans.  plans: B plans of TrainTransform.draw(W_b, H_b), or their pack_plan tensors
     stacked.  Returns (B, 2, 3, T, S, S) fp32 on the device, each sample bit-identical to stage_train_clips on it."""
-    plans = _plan_list([plans] if isinstance(plans, dict) else plans, unpack_plan, 2)
-    B, S = len(plans), int(out_size)
-    if B < 1:
-        raise ValueError("coclr_amd: stage_train_clips_ragged needs at least one plan")
-    T = len(plans[0]["programs"][0])
-    if T < 1:
-        raise ValueError("coclr_amd: a plan has one program per frame")
-    if S < 1 or S * S > JITTER_MAX_PIXELS:
-        raise ValueError("coclr_amd: stage_train_clips_ragged takes an output size of 1..224, got %d" % S)
-    samples = _ragged_samples(frames, B, 2 * T, first)
-    tables = train_tables_ragged(plans, samples, T, S)
-    return _stage_train(ops.resize_boxes_ragged_u8, frames.pixels, frames.pixels.device, tables, B, T, S, mean, std, out)
+    return _train_clips_ragged("stage_train_clips_ragged", None, frames, plans, out_size, first, mean, std, out)
 
 
 def classifier_tables_ragged(plans, samples, T, img_dim, size=224, flip=False):
@@ -1224,52 +1315,74 @@ def clip_frames(ids, plans, T):
     int64 (2 B T, 4)): for clip c of sample b the T ids of half[c] of the sample's frames, each with box[c] -- the
     layout stage_train_clips_cropped takes.  A half that no clip reads (OneClipTransform) is not selected, so it is
     not decoded; a half both clips read is selected twice, once per box."""
+    ids, clips = _selection_args(ids, plans, T)
+    T = int(T)
+    sel, boxes = [], []
+    for b, pair in enumerate(clips):
+        for half, box in pair:
+            sel.append(ids[b, half * T:(half + 1) * T])
+            boxes.extend([box] * T)
+    return torch.cat(sel), torch.tensor(boxes, dtype=torch.int64)
+
+
+def _check_ids(ids, T):
+    """`ids` as int64 (B, 2T) on the host, refused when it is not that."""
     T = int(T)
     ids = torch.as_tensor(ids)
     if ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool or ids.dim() != 2 or T < 1 or \
             ids.shape[1] != 2 * T or ids.shape[0] < 1:
         raise ValueError("coclr_amd: ids must be integers of shape (B, 2 T), got %s %s for T = %d" %
                          (ids.dtype, tuple(ids.shape), T))
-    ids = ids.to("cpu", torch.int64)
+    return ids.to("cpu", torch.int64)
+
+
+def _selection_args(ids, plans, T):
+    """The checks of clip_frames and two_stream_frames: (ids int64 (B, 2T) on the host, per plan its two clips'
+    (half, box as a list of ints))."""
+    ids = _check_ids(ids, T)
     plans = _plan_list([plans] if isinstance(plans, dict) else plans, unpack_plan, 2)
     if len(plans) != ids.shape[0]:
         raise ValueError("coclr_amd: %d plans for %d samples" % (len(plans), ids.shape[0]))
-    sel, boxes = [], []
-    for b, plan in enumerate(plans):
+    clips = []
+    for plan in plans:
         if len(plan["half"]) != 2 or len(plan["box"]) != 2:
             raise ValueError("coclr_amd: a plan names two clips")
+        clips.append([])
         for c in range(2):
             half, box = plan["half"][c], plan["box"][c]
             if half not in (0, 1) or isinstance(half, bool):
                 raise ValueError("coclr_amd: a clip reads half 0 or 1 of the frames, got %r" % (half,))
             if len(box) != 4 or any(int(v) != v for v in box):
                 raise ValueError("coclr_amd: a box is four integers, got %r" % (box,))
-            sel.append(ids[b, int(half) * T:(int(half) + 1) * T])
-            boxes.extend([[int(v) for v in box]] * T)
-    return torch.cat(sel), torch.tensor(boxes, dtype=torch.int64)
+            clips[-1].append((int(half), [int(v) for v in box]))
+    return ids, clips
 
 
-def train_tables_cropped(plans, clips, T, S):
+def train_tables_cropped(plans, clips, T, S, slots=None):
     """train_tables_ragged for clips whose frames ARE their boxes: `clips` [(byte offset of the clip's first frame, w,
     h)], two per plan; clip c of a plan must have its box[c]'s size.  The descriptors read the whole of every frame,
     (0, T, 0, 0, w, h), so the axis tables, the programs and the group size are train_tables_ragged's for the same
-    plans.  Returns (desc int32 (2B, 14), xtab, ytab, kinds, params, group_size), all on the host."""
+    plans.  Returns (desc int32 (2B, 14), xtab, ytab, kinds, params, group_size), all on the host.
+    `slots`: as check_train_plans takes it; `clips` are then len(slots) per plan, slot-major, as two_stream_frames
+    selects them, and so is desc."""
     plans = _plan_list(plans, unpack_plan, 2)
-    if 2 * len(plans) != len(clips):
-        raise ValueError("coclr_amd: %d plans for %d clips" % (len(plans), len(clips)))
-    rows, programs, rag = [], [], []
+    B, per = len(plans), 2 if slots is None else len(slots)
+    if per * B != len(clips):
+        raise ValueError("coclr_amd: %d plans for %d clips" % (B, len(clips)))
+    per_sample = []
     for b, plan in enumerate(plans):
         W = max(int(box[0] + box[2]) for box in plan["box"])              # the frame is gone: each box against itself
         H = max(int(box[1] + box[3]) for box in plan["box"])
-        r, p = check_train_plans([plan], 1, T, W, H)
-        for c, row in enumerate(r):
-            offset, w, h = clips[2 * b + c]
+        r, p = check_train_plans([plan], 1, T, W, H, slots)
+        staged = []
+        for c, (row, progs) in enumerate(zip(r, p)):
+            offset, w, h = clips[2 * b + c if slots is None else c * B + b]
             if (w, h) != (row[4], row[5]):
                 raise ValueError("coclr_amd: clip %d of sample %d holds %d x %d frames and its box is %d x %d" %
                                  (c, b, w, h, row[4], row[5]))
-            rows.append((0, T, 0, 0, w, h))
-            rag.append(_rag_words(offset, w, h))
-        programs.extend(p)
+            staged.append(((0, T, 0, 0, w, h), _rag_words(offset, w, h), progs))
+        per_sample.append(staged)
+    rows, rag, programs = zip(*_slot_major(per_sample, slots))
     return _train_tables(rows, programs, rag, T, S)
 
 
@@ -1281,20 +1394,171 @@ def stage_train_clips_cropped(frames, plans, out_size, mean=IMAGENET_MEAN, std=I
     plan b, following each other at 3 w h bytes rounded up to 16 (checked here, on the host).  plans: the B plans
     clip_frames was given.  Returns (B, 2, 3, T, S, S) fp32 on the device, bit for bit stage_train_clips_ragged's
     result on the whole frames."""
-    plans = _plan_list([plans] if isinstance(plans, dict) else plans, unpack_plan, 2)
-    B, S = len(plans), int(out_size)
-    if B < 1:
-        raise ValueError("coclr_amd: stage_train_clips_cropped needs at least one plan")
-    T = len(plans[0]["programs"][0])
-    if T < 1:
-        raise ValueError("coclr_amd: a plan has one program per frame")
-    if S < 1 or S * S > JITTER_MAX_PIXELS:
-        raise ValueError("coclr_amd: stage_train_clips_cropped takes an output size of 1..224, got %d" % S)
-    if isinstance(frames, RaggedFrames) and len(frames) != 2 * B * T:
-        raise ValueError("coclr_amd: %d frames for %d clips of %d" % (len(frames), 2 * B, T))
-    clips = _ragged_samples(frames, 2 * B, T, None)                          # a clip's frames: one size, one stride
-    tables = train_tables_cropped(plans, [(o, W, H) for o, W, H in clips], T, S)
-    return _stage_train(ops.resize_boxes_ragged_u8, frames.pixels, frames.pixels.device, tables, B, T, S, mean, std, out)
+    return _train_clips_cropped("stage_train_clips_cropped", None, frames, plans, out_size, mean, std, out)
+
+
+def _train_clips_cropped(who, slots, frames, plans, out_size, mean, std, out):
+    """The body of stage_train_clips_cropped (slots None) and stage_two_stream_clips_cropped."""
+    plans, B, T, S = _train_head(who, slots, plans, out_size)
+    n_clips = math.prod(_result_lead(slots, B))
+    if isinstance(frames, RaggedFrames) and len(frames) != n_clips * T:
+        raise ValueError("coclr_amd: %d frames for %d clips of %d" % (len(frames), n_clips, T))
+    clips = _ragged_samples(frames, n_clips, T, None)                        # a clip's frames: one size, one stride
+    tables = train_tables_cropped(plans, [(o, W, H) for o, W, H in clips], T, S, slots)
+    return _stage_train(ops.resize_boxes_ragged_u8, frames.pixels, frames.pixels.device, tables, _result_lead(slots, B),
+                        T, S, mean, std, out)
+
+
+# ---- CoCLR's two-stream batches: RGB + flow (main_coclr.py:365-376,447-473; dataset/lmdb_dataset.py:498-509) ---------
+#
+# A sample is 4 T frames in the dataset's order, four QUARTERS: rgb(clip 1), flow(clip 1), rgb(clip 2), flow(clip 2).
+# The reference transforms them with the chain of main_nce.py at seq_len = 2 T, so the plans are
+# TrainTransform(img_dim, 2 * T).draw(W, H) and pack_plan(plan, 2 * T) unchanged: a plan clip has 2 T programs, program
+# j < T for RGB frame j and program j >= T for flow frame j - T (one box, one jitter draw, one blur sigma and one flip
+# for both streams; a gray clip's channel is drawn per frame across all 2 T), and half[c] selects quarters 2 half[c]
+# (RGB) and 2 half[c] + 1 (flow).  Nothing new runs on the GPU: every (output tensor, sample) pair is ONE clip of T
+# frames for the kernels stage_train_clips launches -- a first frame, a box and T programs -- and the result lands
+# where the model reads it.
+
+_TWO_STREAM_SLOTS = ((None, ((0, 0), (0, 1), (1, 0), (1, 1))),         # x1, f1, x2, f2
+                     (False, ((0, 0), (1, 0), (1, 1))),                # x1, x2, f2: what CoCLR.forward reads
+                     (True, ((1, 0), (1, 1), (0, 1))))                 # x2, f2, f1: what it reads with reverse=True
+
+
+def two_stream_slots(reverse):
+    """The tensors a two-stream batch is staged into, in the order they lie in TwoStreamClips.out, as (clip, stream)
+    pairs, stream 0 RGB and 1 flow.  `reverse`: None for all four, or CoCLR's `reverse` (a bool) for the three its
+    forward reads."""
+    for key, slots in _TWO_STREAM_SLOTS:
+        if reverse is key:
+            return slots
+    raise ValueError("coclr_amd: reverse is None (stage all four clips), False or True (the three clips CoCLR reads "
+                     "with that `reverse`), got %r" % (reverse,))
+
+
+class TwoStreamClips:
+    """A staged two-stream batch.
+      x1, f1, x2, f2  fp32 (B, 3, T, S, S), each contiguous: RGB and flow of clip 1 and of clip 2; None where the clip
+                      was not staged
+      out             the ONE allocation behind them:
+                        reverse=None   (2, 2, B, 3, T, S, S), [clip][stream]
+                        reverse=False  (3, B, 3, T, S, S), [x1, x2, f2]
+                        reverse=True   (3, B, 3, T, S, S), [x2, f2, f1]
+      blocks()        (block1, block2), (B, 2, 3, T, S, S) views of `out` for `model(block1, block2, vname)`: block[:, 0]
+                      and block[:, 1], which is all CoCLR.forward takes of a block, ARE the staged tensors -- no copy.
+    ALIASING in the three-clip forms: two neighbouring slots of `out` make a block, so the stream of block1 that
+    CoCLR.forward never reads is not staged but aliases a tensor of block2 -- block1[:, 1] is x2 (not f1) with
+    reverse=False, block1[:, 0] is f2 (not x1) with reverse=True.  Such blocks are right for a CoCLR of that `reverse`
+    and wrong for any other reader of block1, which is why reverse=None, all four clips, is the default."""
+
+    def __init__(self, out, reverse=None):
+        slots = two_stream_slots(reverse)
+        if out.dim() != (7 if reverse is None else 6) or tuple(out.shape[:-4]) != _result_lead(slots, out.shape[-5]) or \
+                out.shape[-4] != 3 or not out.is_contiguous():
+            raise ValueError("coclr_amd: a two-stream result with reverse=%r is contiguous %s, got %s" %
+                             (reverse, "(2, 2, B, 3, T, S, S)" if reverse is None else "(3, B, 3, T, S, S)",
+                              tuple(out.shape)))
+        self.out, self.reverse = out, reverse
+        self.x1 = self.f1 = self.x2 = self.f2 = None
+        flat = out.view((len(slots),) + tuple(out.shape[-5:]))
+        for k, (c, s) in enumerate(slots):
+            setattr(self, "xf"[s] + "12"[c], flat[k])
+
+    def blocks(self):
+        if self.reverse is None:
+            return self.out[0].transpose(0, 1), self.out[1].transpose(0, 1)
+        first, second = self.out[0:2].transpose(0, 1), self.out[1:3].transpose(0, 1)
+        return (second, first) if self.reverse else (first, second)
+
+
+def stage_two_stream_clips(frames_u8, plans, out_size, reverse=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None,
+                           device=None):
+    """stage_train_clips for CoCLR's two-stream samples, the same TWO launches, bit-identical to the reference's
+    transform of main_coclr.py on the 4 T frames.
+    frames_u8: (B, 4T, H, W, 3) or (4T, H, W, 3) uint8 in the dataset's order -- rgb(clip 1), flow(clip 1), rgb(clip 2),
+    flow(clip 2) -- on the host (uploaded once, as bytes) or the device.
+    plans: B plans of TrainTransform(img_dim, 2 * T).draw, or their pack_plan(plan, 2 * T) tensors stacked.
+    reverse: None stages all four clips; False / True stage only the three that CoCLR(reverse=...).forward reads
+    (TwoStreamClips, which see for the aliasing this implies).  out: TwoStreamClips.out to fill.
+    Returns a TwoStreamClips; `model(*clips.blocks(), vname)`.  Refusals come before anything is launched."""
+    slots = two_stream_slots(reverse)
+    return TwoStreamClips(_train_clips("stage_two_stream_clips", slots, frames_u8, plans, out_size, mean, std, out,
+                                       device), reverse)
+
+
+def stage_two_stream_clips_ragged(frames, plans, out_size, first=None, reverse=None, mean=IMAGENET_MEAN,
+                                  std=IMAGENET_STD, out=None):
+    """stage_two_stream_clips for a batch whose samples differ in frame size (stage_train_clips_ragged's launches).
+    frames: RaggedFrames.  first: integer (B, 4), the first frame of each quarter of each sample (default
+    4 T b + T q: every sample's 4 T frames in the dataset's order, one sample after the other); -1 marks a quarter that
+    was not decoded, refused if a staged clip reads it (two_stream_frames(boxes=False) makes `first` for a selection
+    without the quarters nothing reads).  A quarter's T frames share one size and follow each other at 3 H W bytes
+    rounded up to 16; the quarters of one sample share one size -- RGB and flow frames of different sizes are refused
+    (two_stream_frames).  T comes from the plans.  Returns a TwoStreamClips, each sample bit-identical to
+    stage_two_stream_clips on it."""
+    slots = two_stream_slots(reverse)
+    return TwoStreamClips(_train_clips_ragged("stage_two_stream_clips_ragged", slots, frames, plans, out_size, first,
+                                              mean, std, out), reverse)
+
+
+def stage_two_stream_clips_cropped(frames, plans, out_size, reverse=None, mean=IMAGENET_MEAN, std=IMAGENET_STD,
+                                   out=None):
+    """stage_two_stream_clips_ragged for frames decoded as their crop boxes alone (stage_train_clips_cropped's launches):
+        frames = store.decode(*two_stream_frames(ids_rgb, ids_flow, plans, T, reverse))
+    frames: RaggedFrames of len(two_stream_slots(reverse)) B T frames in two_stream_frames' order -- slot, then sample,
+    then T frames, all of the size of the clip's box.  plans, reverse: what two_stream_frames was given.  Returns a
+    TwoStreamClips, bit for bit stage_two_stream_clips_ragged's on the whole frames."""
+    slots = two_stream_slots(reverse)
+    return TwoStreamClips(_train_clips_cropped("stage_two_stream_clips_cropped", slots, frames, plans, out_size, mean,
+                                               std, out), reverse)
+
+
+def two_stream_frames(ids_rgb, ids_flow, plans, T, reverse=None, boxes=True, frame_size=None):
+    """What a two-stream batch's staged clips read from ONE jpeg.Store or ShardedStore that holds the RGB and the flow
+    videos under different ids: the two-stream clip_frames.
+    ids_rgb, ids_flow: integer (B, 2T), the store ids of sample b's two clips of T frames (the SAME frame indices
+    of the RGB and of the flow video: dataset/lmdb_dataset.py:498-500).  plans, reverse: as the staging takes them.
+      boxes=True   -> (sel int64 (n B T,), boxes int64 (n B T, 4)) for store.decode(sel, boxes) and
+                      stage_two_stream_clips_cropped, n = len(two_stream_slots(reverse)): slot by slot, sample by sample,
+                      the T ids of the quarter the clip reads, each with the clip's box.
+      boxes=False  -> (sel int64, first int64 (B, 4)) for a full-frame store.decode(sel) and
+                      stage_two_stream_clips_ragged(first=first): sample by sample the quarters some staged clip reads,
+                      each once; first[b, q] is quarter q's place in `sel`, or -1.
+    A quarter no staged clip reads is absent from `sel` either way: the clip CoCLR.forward does not read (reverse False
+    or True) and the half OneClipTransform abandons.
+    The RGB and the flow frames of a sample must have ONE size.  The reference would crop a flow frame with the box
+    drawn for the RGB frame's size and let PIL pad with black what the box leaves; UCF101, HMDB51 and kinetics400-256
+    never do this (flow is computed on the RGB frames), so it is refused with ValueError instead: here when
+    `frame_size` is given (store.frame_size: the first RGB and the first flow frame of every sample are compared; a
+    video's frames share one size), and in any case by stage_two_stream_clips_ragged, which sees every frame.  The
+    cropped route without `frame_size` refuses only a box that leaves the flow frame (store.decode)."""
+    slots = two_stream_slots(reverse)
+    T = int(T)
+    rgb, clips = _selection_args(ids_rgb, plans, T)
+    flow = _check_ids(ids_flow, T)
+    if flow.shape != rgb.shape:
+        raise ValueError("coclr_amd: ids_rgb is %s and ids_flow %s" % (tuple(rgb.shape), tuple(flow.shape)))
+    ids, B = (rgb, flow), rgb.shape[0]
+    if frame_size is not None:
+        for b in range(B):
+            a, f = tuple(frame_size(int(rgb[b, 0]))), tuple(frame_size(int(flow[b, 0])))
+            if a != f:
+                raise ValueError("coclr_amd: sample %d has RGB frames of %d x %d and flow frames of %d x %d; the two "
+                                 "streams of a sample share one size" % ((b,) + a + f))
+    if boxes:
+        sel, rows = [], []
+        for c, s in slots:
+            for b in range(B):
+                half, box = clips[b][c]
+                sel.append(ids[s][b, half * T:(half + 1) * T])
+                rows.extend([box] * T)
+        return torch.cat(sel), torch.tensor(rows, dtype=torch.int64)
+    sel, first = [], torch.full((B, 4), -1, dtype=torch.int64)
+    for b in range(B):
+        for q in sorted({2 * clips[b][c][0] + s for c, s in slots}):
+            first[b, q] = T * len(sel)
+            sel.append(ids[q % 2][b, (q // 2) * T:(q // 2 + 1) * T])
+    return torch.cat(sel), first
 
 
 # ---- test clips of many videos in one launch (eval/main_classifier.py:425-521,548-684) ---------------------------------

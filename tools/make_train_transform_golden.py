@@ -53,21 +53,22 @@ class RandomApply:
         return img
 
 
-def chain(A):
-    """get_transform('train', args) of main_nce.py with args.img_dim, args.seq_len = IMG_DIM, SEQ_LEN."""
+def chain(A, seq_len=SEQ_LEN):
+    """get_transform('train', args) of main_nce.py with args.img_dim, args.seq_len = IMG_DIM, SEQ_LEN; main_coclr.py:447-473
+    is the same text with `seq_len = args.seq_len * 2` (tools/make_two_stream_golden.py)."""
     null = G.Compose([
-        A.RandomSizedCrop(size=IMG_DIM, consistent=False, seq_len=SEQ_LEN, bottom_area=0.2),
-        A.RandomHorizontalFlip(consistent=False, seq_len=SEQ_LEN),
+        A.RandomSizedCrop(size=IMG_DIM, consistent=False, seq_len=seq_len, bottom_area=0.2),
+        A.RandomHorizontalFlip(consistent=False, seq_len=seq_len),
         A.ToTensor()])
     base = G.Compose([
-        A.RandomSizedCrop(size=IMG_DIM, consistent=False, seq_len=SEQ_LEN, bottom_area=0.2),
-        RandomApply([A.ColorJitter(0.4, 0.4, 0.4, 0.1, p=1.0, consistent=False, seq_len=SEQ_LEN)], p=0.8),
-        A.RandomGray(p=0.2, seq_len=SEQ_LEN),
-        RandomApply([A.GaussianBlur([.1, 2.], seq_len=SEQ_LEN)], p=0.5),
-        A.RandomHorizontalFlip(consistent=False, seq_len=SEQ_LEN),
+        A.RandomSizedCrop(size=IMG_DIM, consistent=False, seq_len=seq_len, bottom_area=0.2),
+        RandomApply([A.ColorJitter(0.4, 0.4, 0.4, 0.1, p=1.0, consistent=False, seq_len=seq_len)], p=0.8),
+        A.RandomGray(p=0.2, seq_len=seq_len),
+        RandomApply([A.GaussianBlur([.1, 2.], seq_len=seq_len)], p=0.5),
+        A.RandomHorizontalFlip(consistent=False, seq_len=seq_len),
         A.ToTensor()])
-    return A.TransformController([A.TwoClipTransform(base, null, seq_len=SEQ_LEN, p=0.3),
-                                  A.OneClipTransform(base, null, seq_len=SEQ_LEN)], weights=[0.5, 0.5])
+    return A.TransformController([A.TwoClipTransform(base, null, seq_len=seq_len, p=0.3),
+                                  A.OneClipTransform(base, null, seq_len=seq_len)], weights=[0.5, 0.5])
 
 
 class Draws:
