@@ -63,6 +63,54 @@ __device__ __forceinline__ float pool_in(const PoolGeom& g, float v, int c) {
   return v;
 }
 
+// floor(n / d) for n >= 0 and a divisor that is the same in every lane: the tiled kernels turn a flat work-item
+// number into (volume, t, h, w) and a plane number into (sample, channel) with run-time extents, and hipcc's
+// 32-bit division is ~30 vector instructions each time -- more than the window scan it feeds.  Below 2^20 the
+// quotient is a float multiply by the reciprocal (formed once per divisor) and one correction step: n is exact in
+// fp32, and with 1 / d up to 2 ulp off and the product rounded once the product is within n / d * 2^-21 <= 1/2 of
+// n / d, so its truncation is within one of the quotient.  Same value as n / d for every n.
+struct PoolDiv { int d; float r; };
+__device__ __forceinline__ PoolDiv pool_div(int d) {
+  PoolDiv p;
+  p.d = d;
+  p.r = 1.f / (float)d;
+  return p;
+}
+// n < 2^20 is the caller's: element and work-item numbers inside one workgroup's <= kTileFloats tile
+__device__ __forceinline__ int pool_quot_small(int n, const PoolDiv& p) {
+  int q = (int)((float)n * p.r);
+  const int rem = n - q * p.d;
+  q += (rem >= p.d ? 1 : 0) - (rem < 0 ? 1 : 0);
+  return q;
+}
+// plane numbers: any n >= 0
+__device__ __forceinline__ int pool_quot(int n, const PoolDiv& p) {
+  if (n >= (1 << 20)) return n / p.d;
+  return pool_quot_small(n, p);
+}
+
+// Volumes smaller than one pass of the workgroup (Si < 1024: fewer than 256 float4 slots) are staged and stored as
+// ONE run of float4 slots over the group's tile, [gcount][S4], four slots per thread at a time -- every thread busy
+// and its loads in flight together -- instead of volume by volume with part of the workgroup idle.  Slot e: i = the
+// slot inside its volume, (n, c) = sample and plane of that volume.  Larger volumes keep the per-volume loop, whose
+// plane arithmetic is scalar: the kernels are bound by vector instruction issue, and the ~45 per slot of this form
+// cost more there than the round trips they overlap (MaxPool_3a forward 173 -> 187 us with it, MaxPool_5a 23 -> 18).
+constexpr int kSlotRunBelow = 256;
+struct PoolSlots { int S4, C, pl0; PoolDiv dS4, dC; };
+__device__ __forceinline__ PoolSlots pool_slots(int S4, int C, int pl0) {
+  PoolSlots s;
+  s.S4 = S4; s.C = C; s.pl0 = pl0;
+  s.dS4 = pool_div(S4); s.dC = pool_div(C);
+  return s;
+}
+__device__ __forceinline__ void pool_slot(const PoolSlots& s, int e, int& i, int& n, int& c) {
+  const int gi = pool_quot_small(e, s.dS4);
+  i = e - gi * s.S4;
+  const int pl = s.pl0 + gi;
+  n = pool_quot(pl, s.dC);
+  c = pl - n * s.C;
+}
+
 __global__ void __launch_bounds__(256)
 maxpool3d_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int* __restrict__ idx,
                      const PoolGeom g) {
@@ -148,35 +196,73 @@ maxpool3d_tiled_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
   const int Si = g.Ti * g.Hi * g.Wi, So = g.To * g.Ho * g.Wo;
   const int pl0 = blockIdx.x * G;
   const int gcount = min(G, planes - pl0);
+  const PoolDiv dC = pool_div(g.C), dfold = pool_div(tfold);
   // ---- load: G volumes are contiguous per sample only if they share n; handle generally
-  for (int gi = 0; gi < gcount; ++gi) {
-    const int pl = pl0 + gi;
-    const int n = pl / g.C, c = pl - n * g.C;
-    const float* xp = x + (long)n * g.x_nstride + (long)c * Si;
-    float* tp = tile + gi * Si;
-    const int ch = c / g.tfold;          // channel of the un-folded tensor
-    if (vec) {      // PoolFwdPlan::vec: Si % 4 == 0 and x_nstride % 4 == 0
-      for (int i = threadIdx.x; i < (Si >> 2); i += 256) {
-        float4 v = pool_ld4(xp, i, g.nt != 0);
-        v.x = pool_in(g, v.x, ch); v.y = pool_in(g, v.y, ch);
-        v.z = pool_in(g, v.z, ch); v.w = pool_in(g, v.w, ch);
-        reinterpret_cast<float4*>(tp)[i] = v;
+  const int S4 = Si >> 2;
+  if (vec && S4 < kSlotRunBelow) {      // PoolFwdPlan::vec: Si % 4 == 0 and x_nstride % 4 == 0
+    const int total4 = gcount * S4;
+    const PoolSlots slots = pool_slots(S4, g.C, pl0);
+    for (int e0 = threadIdx.x; e0 < total4; e0 += 4 * 256) {
+      float4 r[4];
+      float sc[4], sf[4];             // the slot's channel coefficients, requested with its data
+      bool live[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int e = e0 + k * 256;
+        live[k] = e < total4;
+        sc[k] = sf[k] = 0.f;
+        if (live[k]) {
+          int i, n, c;
+          pool_slot(slots, e, i, n, c);
+          r[k] = pool_ld4(x + (long)n * g.x_nstride + (long)c * Si, i, g.nt != 0);
+          if (g.in_scale) {
+            const int ch = pool_quot(c, dfold);   // channel of the un-folded tensor (g.tfold == tfold)
+            sc[k] = g.in_scale[ch];
+            sf[k] = g.in_shift[ch];
+          }
+        }
       }
-    } else {
-      for (int i = threadIdx.x; i < Si; i += 256) tp[i] = pool_in(g, xp[i], ch);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!live[k]) continue;
+        float4 v = r[k];
+        if (g.in_scale) {             // pool_in, with the coefficients already here
+          v.x = fmaf(v.x, sc[k], sf[k]); v.y = fmaf(v.y, sc[k], sf[k]);
+          v.z = fmaf(v.z, sc[k], sf[k]); v.w = fmaf(v.w, sc[k], sf[k]);
+          if (g.in_relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+        }
+        reinterpret_cast<float4*>(tile)[e0 + k * 256] = v;
+      }
+    }
+  } else {
+    for (int gi = 0; gi < gcount; ++gi) {
+      const int pl = pl0 + gi;
+      const int n = pool_quot(pl, dC), c = pl - n * g.C;
+      const float* xp = x + (long)n * g.x_nstride + (long)c * Si;
+      float* tp = tile + gi * Si;
+      const int ch = pool_quot(c, dfold);  // channel of the un-folded tensor (g.tfold == tfold)
+      if (vec) {
+        for (int i = threadIdx.x; i < S4; i += 256) {
+          float4 v = pool_ld4(xp, i, g.nt != 0);
+          v.x = pool_in(g, v.x, ch); v.y = pool_in(g, v.y, ch);
+          v.z = pool_in(g, v.z, ch); v.w = pool_in(g, v.w, ch);
+          reinterpret_cast<float4*>(tp)[i] = v;
+        }
+      } else {
+        for (int i = threadIdx.x; i < Si; i += 256) tp[i] = pool_in(g, xp[i], ch);
+      }
     }
   }
   __syncthreads();
   constexpr int NR = (WPT - 1) * SW + KW;    // input columns feeding WPT outputs
   const int OWC = (g.Wo + WPT - 1) / WPT;
   const int rows = g.To * g.Ho;
-  const int items = gcount * rows * OWC;
+  const int items = gcount * rows * OWC;       // <= kTileFloats
+  const PoolDiv dOWC = pool_div(OWC), dHo = pool_div(g.Ho), dTo = pool_div(g.To);
   for (int it = threadIdx.x; it < items; it += 256) {
-    const int owc = it % OWC;
-    int r = it / OWC;
-    const int oh = r % g.Ho; r /= g.Ho;
-    const int ot = r % g.To;
-    const int gi = r / g.To;
+    const int r0 = pool_quot_small(it, dOWC), owc = it - r0 * OWC;
+    const int r1 = pool_quot_small(r0, dHo), oh = r0 - r1 * g.Ho;
+    const int gi = pool_quot_small(r1, dTo), ot = r1 - gi * g.To;
     const int ow0 = owc * WPT;
     const float* tp = tile + gi * Si;
     float best[WPT];
@@ -189,20 +275,40 @@ maxpool3d_tiled_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
       const int tt = max(t0, 0), hh = max(h0, 0), ww = max(w0 + j * SW, 0);
       bi[j] = (tt * g.Hi + hh) * g.Wi + ww;
     }
+    // No branch around a row or a column outside the volume: every read goes to a clamped (valid) address and
+    // the value is replaced by -inf, which the scan below never takes -- as skipping the element did.  All reads of
+    // an item are then independent LDS loads with nothing but selects between them and the compares (the branchy
+    // form waited for each read under its own exec mask).
+    // (-inf through a register the optimiser cannot see into: knowing the constant, it turns every select back into a
+    // branch around the read and the compares that -inf cannot win)
+    float ninf = -INFINITY;
+    asm volatile("" : "+v"(ninf));
+    int wc[NR];
+    bool wok[NR];
 #pragma unroll
+    for (int q = 0; q < NR; ++q) {
+      const int w = w0 + q;
+      wok[q] = w >= 0 && w < g.Wi;
+      wc[q] = min(max(w, 0), g.Wi - 1);
+    }
+    // at most 16 reads in flight: the three frames of a 3x3x3 window stay a loop (unrolled, their 45 to 54 reads
+    // are all hoisted to the top and their registers halve the waves per SIMD)
+#pragma unroll(KT * KH * NR <= 16 ? KT : 1)
     for (int kt = 0; kt < KT; ++kt) {
       const int t = t0 + kt;
-      if (t < 0 || t >= g.Ti) continue;
+      const bool tok = t >= 0 && t < g.Ti;
+      const int tcl = min(max(t, 0), g.Ti - 1);
 #pragma unroll
       for (int kh = 0; kh < KH; ++kh) {
         const int h = h0 + kh;
-        if (h < 0 || h >= g.Hi) continue;
-        const int rowoff = (t * g.Hi + h) * g.Wi;
+        const bool rok = tok && h >= 0 && h < g.Hi;
+        const int rowoff = (t * g.Hi + h) * g.Wi;            // used only by elements that exist
+        const float* rp = tp + (tcl * g.Hi + min(max(h, 0), g.Hi - 1)) * g.Wi;
         float v[NR];
 #pragma unroll
         for (int q = 0; q < NR; ++q) {
-          const int w = w0 + q;
-          v[q] = (w >= 0 && w < g.Wi) ? tp[rowoff + w] : -INFINITY;
+          const float e = rp[wc[q]];
+          v[q] = (rok && wok[q]) ? e : ninf;
         }
 #pragma unroll
         for (int j = 0; j < WPT; ++j) {
@@ -215,15 +321,16 @@ maxpool3d_tiled_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
       }
     }
     const int pl = pl0 + gi;
-    const int n = pl / g.C, c = pl - n * g.C;
+    const int n = pool_quot(pl, dC), c = pl - n * g.C;
     const long obase = ((long)ot * g.Ho + oh) * g.Wo + ow0;
     float* yp = y + (long)n * g.y_nstride + (long)c * So + obase;
+    // indices are relative to the un-folded (n, c) volume
+    const int fold_off = WITH_IDX ? (pl - pool_quot(pl, dfold) * tfold) * Si : 0;
 #pragma unroll
     for (int j = 0; j < WPT; ++j) {
       if (ow0 + j < g.Wo) {
         yp[j] = best[j];
-        // indices are relative to the un-folded (n, c) volume
-        if (WITH_IDX) idx[(long)pl * So + obase + j] = bi[j] + (pl % tfold) * Si;
+        if (WITH_IDX) idx[(long)pl * So + obase + j] = bi[j] + fold_off;
       }
     }
   }
@@ -242,46 +349,59 @@ maxpool3d_tiled_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
 template <int PT, int PH, int PW, int KQ>
 struct ClassLoads {
   int i[PT * PH * PW][KQ];      // the arg-max index AS LOADED (-1: no element), added to b only when applied:
-  int b[PT * PH * PW][KQ];      // arithmetic on the loaded value next to the load would make every class wait
-  float v[PT * PH * PW][KQ];    // for its own round trip before the next class's loads are even issued
+  float v[PT * PH * PW][KQ];    // arithmetic on the loaded value next to the load would make every class wait
+  int b[KQ];                    // for its own round trip before the next class's loads are even issued
 };
 
+// Thread slot q = threadIdx.x + k * 256 owns ONE block of PT x PH x PW neighbouring outputs of one volume, the
+// output (a * PT + ct, b * PH + ch, cc * PW + cw) of every class (ct, ch, cw): the slot is taken apart into
+// (volume, a, b, cc) once, and a class only adds its constant offset and tests that its output exists.  (Taking q
+// apart per class, by that class's own extents, cost five 32-bit divisions per class and slot: 4063 vector
+// instructions per thread in the 27-class form.)  Which lane holds which output of a class is free -- the windows
+// of one class are disjoint -- so every input element still receives its addends in class order.
+// class_shape's kq is the slot count per thread: G * ceil(To / PT) * ceil(Ho / PH) * ceil(Wo / PW) <= KQ * 256.
 template <int PT, int PH, int PW, int KQ>
 __device__ __forceinline__ void class_load(ClassLoads<PT, PH, PW, KQ>& L, const float* __restrict__ dy,
                                            const int* __restrict__ idx, const PoolGeom& g,
                                            long dy_nstride, int pl0, int gcount, int tfold, int Si,
                                            int So) {
+  const int mt = (g.To + PT - 1) / PT, mh = (g.Ho + PH - 1) / PH, mw = (g.Wo + PW - 1) / PW;
+  const int msize = mt * mh * mw;              // gcount * msize <= KQ * 256
+  const PoolDiv dsize = pool_div(msize), dhw = pool_div(mh * mw), dw = pool_div(mw);
+  const PoolDiv dC = pool_div(g.C), dfold = pool_div(tfold);
 #pragma unroll
-  for (int ct = 0; ct < PT; ++ct)
+  for (int k = 0; k < KQ; ++k) {
+    const int q = threadIdx.x + k * 256;
+    const bool live = q < gcount * msize;
+    const int gi = live ? pool_quot_small(q, dsize) : 0;
+    int m = live ? q - gi * msize : 0;
+    const int a = pool_quot_small(m, dhw);
+    m -= a * mh * mw;
+    const int b = pool_quot_small(m, dw), cc = m - b * mw;
+    const int t0 = a * PT, h0 = b * PH, w0 = cc * PW;
+    const int o0 = (t0 * g.Ho + h0) * g.Wo + w0;
+    const int pl = pl0 + gi;
+    const int n = pool_quot(pl, dC), c = pl - n * g.C;
+    const int* ip = idx + (long)pl * So + o0;
+    const float* dp = dy + (long)n * dy_nstride + (long)c * So + o0;
+    L.b[k] = gi * Si - (pl - pool_quot(pl, dfold) * tfold) * Si;
 #pragma unroll
-    for (int ch = 0; ch < PH; ++ch)
+    for (int ct = 0; ct < PT; ++ct)
 #pragma unroll
-      for (int cw = 0; cw < PW; ++cw) {
-        const int cls = (ct * PH + ch) * PW + cw;
-        const int nt = (g.To - ct + PT - 1) / PT, nh = (g.Ho - ch + PH - 1) / PH,
-                  nw = (g.Wo - cw + PW - 1) / PW;
-        const int csize = (nt > 0 && nh > 0 && nw > 0) ? nt * nh * nw : 0;
+      for (int ch = 0; ch < PH; ++ch)
 #pragma unroll
-        for (int k = 0; k < KQ; ++k) {
-          const int q = threadIdx.x + k * 256;
+        for (int cw = 0; cw < PW; ++cw) {
+          const int cls = (ct * PH + ch) * PW + cw;
+          const int off = (ct * g.Ho + ch) * g.Wo + cw;
+          const bool has = live && t0 + ct < g.To && h0 + ch < g.Ho && w0 + cw < g.Wo;
           L.i[cls][k] = -1;
-          L.b[cls][k] = 0;
           L.v[cls][k] = 0.f;
-          if (q < gcount * csize) {
-            const int gi = q / csize;
-            int m = q - gi * csize;
-            const int a = m / (nh * nw);
-            m -= a * nh * nw;
-            const int b = m / nw, cc = m - b * nw;
-            const int o = ((a * PT + ct) * g.Ho + (b * PH + ch)) * g.Wo + (cc * PW + cw);
-            const int pl = pl0 + gi;
-            const int n = pl / g.C, c = pl - n * g.C;
-            L.b[cls][k] = gi * Si - (pl % tfold) * Si;
-            L.i[cls][k] = idx[(long)pl * So + o];
-            L.v[cls][k] = dy[(long)n * dy_nstride + (long)c * So + o];
+          if (has) {
+            L.i[cls][k] = ip[off];
+            L.v[cls][k] = dp[off];
           }
         }
-      }
+  }
 }
 
 // the tile's zero fill (or anything else written to LDS before) must be followed by no barrier of
@@ -293,7 +413,7 @@ __device__ __forceinline__ void class_apply(const ClassLoads<PT, PH, PW, KQ>& L,
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS only: the loads stay in flight
 #pragma unroll
     for (int k = 0; k < KQ; ++k)
-      if (L.i[cls][k] >= 0) tile[L.b[cls][k] + L.i[cls][k]] += L.v[cls][k];
+      if (L.i[cls][k] >= 0) tile[L.b[k] + L.i[cls][k]] += L.v[cls][k];
   }
 }
 
@@ -345,13 +465,42 @@ maxpool3d_tiled_bwd_kernel(const float* __restrict__ dy, const int* __restrict__
     class_scatter_generic(tile, dy, idx, g, dy_nstride, pl0, gcount, tfold, Si, So);
   }
   __syncthreads();
+  const PoolDiv dC = pool_div(g.C);
+  const int S4 = Si >> 2;
+  if (vec && S4 < kSlotRunBelow) {      // PoolBwdPlan::vec: Si % 4 == 0 and dx_nstride % 4 == 0
+    const int total4 = gcount * S4;
+    const PoolSlots slots = pool_slots(S4, g.C, pl0);
+    for (int e0 = threadIdx.x; e0 < total4; e0 += 4 * 256) {
+      float4 o[4];
+      float* dp[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int e = e0 + k * 256;
+        dp[k] = nullptr;
+        if (e < total4) {
+          int i, n, c;
+          pool_slot(slots, e, i, n, c);
+          dp[k] = dx + (long)n * dx_nstride + (long)c * Si + 4 * i;
+          if (accumulate) o[k] = *reinterpret_cast<const float4*>(dp[k]);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (!dp[k]) continue;
+        float4 v = reinterpret_cast<const float4*>(tile)[e0 + k * 256];
+        if (accumulate) { v.x += o[k].x; v.y += o[k].y; v.z += o[k].z; v.w += o[k].w; }
+        *reinterpret_cast<float4*>(dp[k]) = v;
+      }
+    }
+    return;
+  }
   for (int gi = 0; gi < gcount; ++gi) {
     const int pl = pl0 + gi;
-    const int n = pl / g.C, c = pl - n * g.C;
+    const int n = pool_quot(pl, dC), c = pl - n * g.C;
     float* dxp = dx + (long)n * dx_nstride + (long)c * Si;
     const float* tp = tile + gi * Si;
-    if (vec) {      // PoolBwdPlan::vec: Si % 4 == 0 and dx_nstride % 4 == 0
-      for (int i = threadIdx.x; i < (Si >> 2); i += 256) {
+    if (vec) {
+      for (int i = threadIdx.x; i < S4; i += 256) {
         float4 v = reinterpret_cast<const float4*>(tp)[i];
         if (accumulate) {
           const float4 o = reinterpret_cast<const float4*>(dxp)[i];
@@ -606,10 +755,11 @@ bn_pool_bwd_apply_kernel(const float* __restrict__ pdy, const int* __restrict__ 
   if constexpr (PT > 0) class_apply<PT, PH, PW, KQ>(L, tile);
   else class_scatter_generic(tile, pdy, pidx, g, pdy_nstride, pl0, gcount, tfold, Si, So);
   __syncthreads();
+  const PoolDiv dC = pool_div(g.C), dfold = pool_div(tfold);
   for (int gi = 0; gi < gcount; ++gi) {
     const int pl = pl0 + gi;
-    const int n = pl / g.C, c = pl - n * g.C;       // c: folded plane index inside the sample
-    const int ch = c / tfold;
+    const int n = pool_quot(pl, dC), c = pl - n * g.C;       // c: folded plane index inside the sample
+    const int ch = pool_quot(c, dfold);
     const float A = coef[gi][0], B = coef[gi][1], D = coef[gi][2];
     const float sc = scale[ch], sf = shift[ch];
     const float* yp = y + (long)n * y_nstride + (long)c * Si;
