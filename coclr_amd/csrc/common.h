@@ -35,6 +35,17 @@ static inline hipError_t ensure_dyn_lds(const void* kern, int bytes, std::atomic
   return e;
 }
 
+// Launch a kernel that takes more dynamic LDS than the default limit: raise the limit (once per device), launch,
+// check.  One instantiation, hence one `attr_done` flag, per kernel.
+template <auto Kern, int THREADS, typename... Args>
+int launch_dyn_lds(dim3 grid, size_t lds, hipStream_t stream, const Args&... args) {
+  static std::atomic<uint64_t> attr_done{0};
+  COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(Kern), 160 * 1024, attr_done));
+  hipLaunchKernelGGL(Kern, grid, dim3(THREADS), lds, stream, args...);
+  COCLR_LAUNCH_CHECK();
+  return 0;
+}
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;

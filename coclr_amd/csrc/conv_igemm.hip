@@ -2738,19 +2738,9 @@ inline int granule_count(const ConvPlan& p) {
 
 // ---- launching ------------------------------------------------------------------------------------------------
 // A launcher takes the ConvArgs, grid and LDS bytes the selection worked out (select_forward, apply) and does three
-// things: raise the kernel's dynamic-LDS limit once, launch, check.
+// things: raise the kernel's dynamic-LDS limit once, launch, check (launch_dyn_lds, common.h).
 typedef int (*SingleFn)(const ConvArgs&, long, size_t, hipStream_t);
 typedef int (*PairFn)(const ConvArgs&, const ConvArgs&, long, long, size_t, hipStream_t);
-
-// One instantiation, hence one `attr_done` flag, per kernel.
-template <auto Kern, int THREADS, typename... Args>
-int launch_dyn_lds(dim3 grid, size_t lds, hipStream_t stream, const Args&... args) {
-  static std::atomic<uint64_t> attr_done{0};
-  COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(Kern), 160 * 1024, attr_done));
-  hipLaunchKernelGGL(Kern, grid, dim3(THREADS), lds, stream, args...);
-  COCLR_LAUNCH_CHECK();
-  return 0;
-}
 
 // the SingleFn / PairFn of a kernel: one function per kernel, so comparing pointers compares kernel variants
 template <auto Kern>

@@ -8,12 +8,23 @@
 // backbone/s3dg.py:11-13,39-42 and backbone/resnet_2d3d.py:53-59,138.
 //
 // GEMM view: M = Cout, N = J = Cin*taps, K = all output positions of the batch.
-// One workgroup owns a (64 x BJ) tile of dW and a strided subset of the
-// position boxes (split-K); per box it stages dY[64][128] (+1 pad, conflict
-// free column reads) and the X stencil window of the channels its j-range
-// touches, then runs v_mfma_f32_32x32x2_f32 with k = position.  Partial tiles
-// go to [split][Cout][J]; a second kernel folds the splits (no atomics, so the
+// A workgroup owns a tile of dW and a strided subset of the position boxes
+// (split-K); per box it stages dY and the X stencil window in LDS, then runs
+// v_mfma_f32_32x32x2_f32 with k = position.  Partial tiles go to
+// [split][Cout][J]; a second kernel folds the splits (no atomics, so the
 // result is run-to-run deterministic).
+//
+// Five kernels, each described where it stands:
+//   conv_wgrad_kernel<BJ, PCH>       first generation: lanes are (ci, tap) columns of a 64 x BJ tile; the
+//                                    fallback for narrow layers, strided stencils and wide windows
+//   conv_wgrad2_kernel<...>          loader / matrix wave specialisation, lanes are input channels: (1,3,3),
+//                                    (3,1,1), (7,1,1), (1,1,1), and the Winograd-domain forms F(2,3) along T
+//                                    (WINO) and F(2x2,3x3) (WHW)
+//   conv_wgrad_pw_kernel<MB, NB>     pointwise layers as a plain GEMM fed by 16-byte LDS-DMA
+//   conv_wgrad_stem_kernel<..., BNA> (1,7,7) over 3 channels; BNA applies BatchNorm's backward as it loads
+//   wgrad_reduce_kernel              folds the split slices into up to four destinations
+// Behind them the host side: plan_wgrad picks box, grid and split from the geometry, select_wgrad names the
+// row of kWgradTable (one row per instantiation, 21 of them) and its LDS bytes, wgrad_run launches that row.
 #include <cstdlib>
 
 #include "common.h"
@@ -1064,22 +1075,186 @@ wgrad_reduce_kernel(const float* __restrict__ part, WgradDst dst, long CJ, int S
 
 struct WPlan {
   ConvPlan p;
-  int variant, BJ, S, jtiles, mtiles, planeP, pch, nci_max;
-  // second-generation kernel
-  int v2;            // 0: not applicable, else variant id (6: temporal Winograd form of id 2)
+  int id;            // WgradId
+  int S;             // split count; the launch grid is (S, jtiles, mtiles)
+  int jtiles;        // ci tiles (WID_GEN1: tiles of BJ columns j = (ci, tap))
+  int mtiles;        // co tiles
+  int planeP;        // LDS pitch of one channel's window
+  int bj, nci_max;   // WID_GEN1: j extent of a tile and the most channels its columns touch
   int pw;            // pointwise: 16-byte-DMA GEMM kernel applicable
-  int rebox;         // id 7: the 32 x 2 box was re-cut to 16 x 4
-  ConvPlan p2;
-  int S2, planeP2, mt2, ct2;
-  size_t lds2;
+  int rebox;         // WID_WINO_HW: the 32 x 2 box was re-cut to 16 x 4
 };
 
+// What plan_wgrad picks from the geometry alone; coclr_conv3d_wgrad_plan reports these numbers as out[1].
+enum WgradId {
+  WID_GEN1 = 0,      // first-generation (ci,tap)-lane kernel: narrow layers, strided stencils, whatever is left
+  WID_S133 = 1,      // wave-specialised kernel, (1,3,3)
+  WID_T311 = 2,      // wave-specialised kernel, (3,1,1)
+  WID_T711 = 3,      // wave-specialised kernel, (7,1,1)
+  WID_PW128 = 4,     // pointwise stride 1, 128 co x 128 ci tile (wave-specialised or 16-byte-DMA GEMM kernel)
+  WID_PW64 = 5,      // pointwise stride 1, 64 co x 64 ci tile (likewise)
+  WID_WINO_T = 6,    // (3,1,1) in the temporal Winograd F(2,3) domain: the (4,1,1) / stride-2 view over frame pairs
+  WID_WINO_HW = 7,   // (1,3,3) in the Winograd F(2x2,3x3) domain
+  WID_STEM = 9,      // (1,7,7) over 3 channels: the stem kernel
+};
+
+// ---- the kernel table -------------------------------------------------------------------------------------------
+// A row is one kernel instantiation: the numbers coclr_conv3d_wgrad_plan reports about it and the function that
+// launches it.  Rows are only ever built by the *_row<...>() templates below, from the SAME template arguments for
+// both, so what is reported is what runs.
+enum { WF_GEN1 = 0, WF_WAVE = 1, WF_STEM = 2, WF_PWDMA = 3 };
+
+// the kernels take one of two argument blocks; a row's launch function knows which (`Member`)
+union WgradKernArgs { WgradArgs gen1; Wgrad2Args wave; };
+typedef int (*WgradLaunchFn)(const WgradKernArgs&, dim3, size_t, hipStream_t);
+
+template <auto Kern, int THREADS, auto Member>
+int launch_row(const WgradKernArgs& a, dim3 grid, size_t lds, hipStream_t stream) {
+  return launch_dyn_lds<Kern, THREADS>(grid, lds, stream, a.*Member);
+}
+
+struct WgradRow {
+  int family, id;    // WF_*, WgradId
+  int PCH;           // template PCH: 64-element chunks of one channel's window the kernel can hold (0: it has none)
+  int BJ;            // WF_GEN1: template BJ (0 otherwise)
+  int slices;        // workspace slices one split writes
+  int KT, KH, KW, MB, NB, NL;   // the other template numbers (0: the kernel has none)
+  bool WINO, WHW, BNA;
+  int threads;
+  WgradLaunchFn launch;
+};
+
+template <int BJ, int PCH>
+constexpr WgradRow gen1_row() {
+  return {WF_GEN1, WID_GEN1, PCH, BJ, 1, 0, 0, 0, 0, 0, 0, false, false, false, 256,
+          &launch_row<conv_wgrad_kernel<BJ, PCH>, 256, &WgradKernArgs::gen1>};
+}
+
+// the F(2x2,3x3) form writes two slices per split (one per xi half)
+template <int KT, int KH, int KW, int MB, int NB, int PCH, bool WINO = false, int NL = 4, bool WHW = false>
+constexpr WgradRow wave_row() {
+  constexpr int id = WHW ? WID_WINO_HW : WINO ? WID_WINO_T : KH == 3 ? WID_S133 : KT == 3 ? WID_T311 :
+                     KT == 7 ? WID_T711 : MB == 2 ? WID_PW128 : WID_PW64;
+  constexpr int threads = 256 + 64 * NL;
+  return {WF_WAVE, id, PCH, 0, WHW ? 2 : 1, KT, KH, KW, MB, NB, NL, WINO, WHW, false, threads,
+          &launch_row<conv_wgrad2_kernel<KT, KH, KW, MB, NB, PCH, WINO, NL, WHW>, threads, &WgradKernArgs::wave>};
+}
+
+template <int MB, int NB>
+constexpr WgradRow pw_row() {
+  return {WF_PWDMA, MB == 2 ? WID_PW128 : WID_PW64, 0, 0, 1, 0, 0, 0, MB, NB, 0, false, false, false, 512,
+          &launch_row<conv_wgrad_pw_kernel<MB, NB>, 512, &WgradKernArgs::wave>};
+}
+
+// the stem kernel writes four slices per split (one per matrix wave)
+template <bool BNA>
+constexpr WgradRow stem_row() {
+  return {WF_STEM, WID_STEM, 20, 0, 4, 1, 7, 7, 0, 0, 0, false, false, BNA, 512,
+          &launch_row<conv_wgrad_stem_kernel<7, 7, 3, 20, BNA>, 512, &WgradKernArgs::wave>};
+}
+
+// THE table: every weight-gradient kernel of the library (tests/_wgrad_cases.py: INSTANTIATIONS).  gen1 <128, 2>
+// is never selected: a stencil's window is always wider than its 128-position box (UNREACHABLE there).
+//
+// NL: the temporal forms are loader-bound with four loader waves (3 or 4 MFMAs per four LDS-DMA pieces), so they
+// run EIGHT loader waves beside the four matrix waves (768 threads; 48-64 accumulator registers leave room for
+// three waves per SIMD): direct 1.20 -> 1.05 ms, Winograd 1.07 -> 0.90 ms on Conv_2c.conv2.  (7,1,1) (112
+// accumulators) and (1,3,3) (144) keep four.
+constexpr WgradRow kWgradTable[] = {
+    gen1_row<64, 2>(), gen1_row<64, 4>(), gen1_row<64, 8>(), gen1_row<64, 20>(),
+    gen1_row<128, 2>(), gen1_row<128, 4>(), gen1_row<128, 8>(), gen1_row<128, 20>(),
+    wave_row<1, 3, 3, 1, 1, 2>(), wave_row<1, 3, 3, 1, 1, 3>(),
+    wave_row<3, 1, 1, 1, 1, 2, false, 8>(),                                                   // NL = 8
+    wave_row<7, 1, 1, 1, 1, 4>(),
+    wave_row<1, 1, 1, 2, 2, 2>(), wave_row<1, 1, 1, 1, 1, 2>(),
+    wave_row<4, 1, 1, 1, 1, 2, true, 8>(),                                                    // F(2,3), NL = 8
+    wave_row<1, 3, 3, 1, 1, 2, false, 4, true>(), wave_row<1, 3, 3, 1, 1, 3, false, 4, true>(),   // F(2x2,3x3)
+    pw_row<2, 2>(), pw_row<1, 1>(),
+    stem_row<false>(), stem_row<true>(),
+};
+constexpr int kWgradRows = sizeof(kWgradTable) / sizeof(kWgradTable[0]);
+constexpr int kWgradMaxPch = 20;
+
+// (family, id, BJ == 128, BNA, window chunks) -> the row with the smallest PCH that holds them, worked out once by
+// the compiler: a lookup indexes, it never searches.  Entries are row number + 1; 0: no such kernel.
+struct WgradIndex { signed char at[4][10][2][2][kWgradMaxPch + 1]; bool unique; };
+constexpr WgradIndex index_wgrad_table() {
+  WgradIndex ix{};
+  ix.unique = true;
+  for (int i = 0; i < kWgradRows; ++i) {
+    const WgradRow& r = kWgradTable[i];
+    signed char(&slot)[kWgradMaxPch + 1] = ix.at[r.family][r.id][r.BJ == 128][r.BNA];
+    const int top = r.PCH ? r.PCH : kWgradMaxPch;      // a kernel without PCH takes any window
+    if (slot[top] && kWgradTable[slot[top] - 1].PCH == r.PCH) ix.unique = false;
+    for (int pch = 0; pch <= top; ++pch)
+      if (!slot[pch] || kWgradTable[slot[pch] - 1].PCH > r.PCH) slot[pch] = (signed char)(i + 1);
+  }
+  return ix;
+}
+constexpr WgradIndex kWgradIndex = index_wgrad_table();
+inline constexpr const WgradRow* wgrad_row(int family, int id, int bj, bool bna, int pch) {
+  if (pch < 0 || pch > kWgradMaxPch) return nullptr;
+  const int i = kWgradIndex.at[family][id][bj == 128][bna][pch];
+  return i ? &kWgradTable[i - 1] : nullptr;
+}
+static_assert(kWgradRows == 21 && kWgradIndex.unique, "kWgradTable: one row per (family, id, PCH, BJ, BNA)");
+// every row the planner can name exists, up to the widest window it accepts for that id
+static_assert(wgrad_row(WF_GEN1, WID_GEN1, 64, false, 20) && wgrad_row(WF_GEN1, WID_GEN1, 128, false, 20) &&
+              wgrad_row(WF_WAVE, WID_S133, 0, false, 3) && wgrad_row(WF_WAVE, WID_T311, 0, false, 2) &&
+              wgrad_row(WF_WAVE, WID_T711, 0, false, 4) && wgrad_row(WF_WAVE, WID_PW128, 0, false, 2) &&
+              wgrad_row(WF_WAVE, WID_PW64, 0, false, 2) && wgrad_row(WF_WAVE, WID_WINO_T, 0, false, 2) &&
+              wgrad_row(WF_WAVE, WID_WINO_HW, 0, false, 3) && wgrad_row(WF_PWDMA, WID_PW128, 0, false, 2) &&
+              wgrad_row(WF_PWDMA, WID_PW64, 0, false, 2) && wgrad_row(WF_STEM, WID_STEM, 0, false, 20) &&
+              wgrad_row(WF_STEM, WID_STEM, 0, true, 20), "kWgradTable: a kernel the planner names is missing");
+
+// ---- the selection ----------------------------------------------------------------------------------------------
+constexpr size_t kLdsMax = 160 * 1024;
+
+// LDS bytes of a row for a plan: the ONE place they are written
+inline size_t wgrad_lds(const WgradRow& r, const WPlan& w) {
+  size_t floats;
+  if (r.family == WF_GEN1)          // dY[64][128 + 1], the offset table, the windows of nci_max channels
+    floats = (size_t)64 * 129 + 128 + (size_t)w.nci_max * w.planeP;
+  else if (r.family == WF_PWDMA)    // two stages of unpadded [co rows + ci rows][64 positions]
+    floats = (size_t)2 * 128 * r.MB * 64;
+  else if (r.family == WF_STEM)     // two stages of dY[64][128 + 1] and three windows; BNA: y rows and flags beside dz
+    floats = 2 * ((size_t)(r.BNA ? 2 : 1) * 64 * 129 + (r.BNA ? 128 : 0) + (size_t)3 * w.planeP);
+  else                              // two stages of dY[co rows][64 + 1] and 64 NB windows
+    floats = 2 * ((size_t)(r.WHW ? 32 : 64 * r.MB) * 65 + (size_t)64 * r.NB * w.planeP);
+  return floats * sizeof(float);
+}
+
+// Which kernel instantiation a planned launch runs, and its LDS bytes: the ONE place that decides it (wgrad_run
+// launches what this says, coclr_conv3d_wgrad_plan reports it, coclr_conv3d_wgrad_workspace sizes the slices by it,
+// the planner accepts a box only if this finds a row whose LDS fits).  `bn`: the form that applies BatchNorm's
+// backward while it loads; row == nullptr: no kernel holds the plan's window (or, with `bn`, has that form).
+struct WSel { const WgradRow* row; size_t lds; };
+inline WSel select_wgrad(const WPlan& w, bool aligned16, bool bn = false) {
+  const int family = w.id == WID_GEN1 ? WF_GEN1 : w.id == WID_STEM ? WF_STEM : (w.pw && aligned16) ? WF_PWDMA : WF_WAVE;
+  const WgradRow* r = wgrad_row(family, w.id, w.bj, bn, cdiv(w.p.plane, 64));
+  return {r, r ? wgrad_lds(*r, w) : 0};
+}
+inline bool sel_ok(const WSel& s) { return s.row && s.lds <= kLdsMax; }
+
+// the stem kernel that applies BatchNorm's backward while it loads exists for this plan (see _bn_ok)
+inline bool stem_bn_ok(const WPlan& w) { return sel_ok(select_wgrad(w, false, true)); }
+
+// ---- planning ---------------------------------------------------------------------------------------------------
 // Split count as a multiple of 8: the grid is (split, ci tile, co tile) with the split fastest, and the
 // hardware deals consecutive workgroup ids round-robin over the 8 XCDs -- with S % 8 == 0 the workgroups
 // that stream the SAME boxes (same split, other tiles) sit on one XCD and share its L2.
 inline int xcd_round(int S) {
   static const bool off = getenv("COCLR_XCD_MAP") && atoi(getenv("COCLR_XCD_MAP")) == 0;
   return (!off && S >= 16) ? (S & ~7) : S;
+}
+
+// Split-K: `budget` workgroups over the output tiles, but at least `min_boxes` boxes per workgroup so the
+// partial-sum traffic stays small next to the streamed operands
+inline int split_count(int budget, int tiles, int ntiles, int min_boxes, bool round) {
+  int S = budget / tiles;
+  if (S > ntiles / min_boxes) S = ntiles / min_boxes;
+  if (S < 1) S = 1;
+  return round ? xcd_round(S) : S;
 }
 
 // Order of the (split, ci tile, co tile) workgroups of the second-generation / pointwise kernels, see
@@ -1089,153 +1264,6 @@ inline int wgrad_order_env() {
   const char* e = getenv("COCLR_WGRAD_ORDER");
   if (!e) return -1;
   return e[0] == 't' ? 1 : (e[0] == 's' ? 0 : -1);
-}
-
-// tile of the v2 kernel for a stencil: returns variant id or 0
-// stem: (1,7,7) over 3 channels -> conv_wgrad_stem_kernel; fills the v2 plan fields
-int pick_stem(const coclr_conv_desc* d, WPlan* w) {
-  w->pw = 0;
-  w->rebox = 0;
-  if (!(d->kt == 1 && d->kh == 7 && d->kw == 7 && d->Cin == 3)) return 0;
-  ConvPlan& p = w->p2;
-  conv_normalise(d, &p);
-  conv_pick_box(&p, 7, 1, 7, 7);
-  if (p.lTW < 1) return 0;
-  // LDS row pitch of the window == 7 (mod 32): the (kh,kw) offsets of 32 consecutive columns
-  // then hit distinct banks (the extra columns are loaded like any other, never read)
-  while ((p.WW & 31) != 7) ++p.WW;
-  p.plane1 = p.WT * p.WH * p.WW;
-  p.plane = p.plane1 << p.lTN;
-  if (cdiv(p.plane, 64) > 20) return 0;
-  w->planeP2 = p.plane | 1;
-  const size_t stage = ((size_t)64 * 129 + (size_t)3 * w->planeP2) * sizeof(float);
-  w->lds2 = 2 * stage;
-  if (w->lds2 > 160 * 1024) return 0;
-  const double lim = 2147483648.0;
-  if (((double)(1 << p.lTN) * d->x_nstride + (double)p.Cin * p.Ti * p.Hi * p.Wi) * 4.0 >= lim) return 0;
-  if (((double)(1 << p.lTN) * d->y_nstride + (double)p.Cout * p.To * p.Ho * p.Wo) * 4.0 >= lim) return 0;
-  w->mt2 = cdiv(p.Cout, 64);
-  w->ct2 = 1;
-  int S = 256 / w->mt2;                 // one 512-thread workgroup per CU
-  if (S > p.ntiles / 2) S = p.ntiles / 2;
-  if (S < 1) S = 1;
-  w->S2 = S;
-  return 9;
-}
-
-int pick_v2(const coclr_conv_desc* d, WPlan* w) {
-  const int kt = d->kt, kh = d->kh, kw = d->kw;
-  int MB = 1, NB = 1, id = 0;
-  w->pw = 0;
-  w->rebox = 0;
-  if (kt == 1 && kh == 3 && kw == 3) id = 1;
-  else if (kt == 3 && kh == 1 && kw == 1) id = 2;
-  else if (kt == 7 && kh == 1 && kw == 1) id = 3;
-  else if (kt == 1 && kh == 1 && kw == 1) {
-    if (d->st != 1 || d->sh != 1 || d->sw != 1) return 0;
-    if (d->Cin > 64 && d->Cout > 64) { id = 4; MB = NB = 2; } else id = 5;
-  } else return 0;
-  // narrow layers: a 64co x 64ci workgroup tile would be mostly padding; the (ci,tap)-lane
-  // kernel packs them better
-  if (id <= 3 && (d->Cin < 48 || d->Cout < 48)) return 0;
-  if (d->Cin < 8) return 0;
-  ConvPlan& p = w->p2;
-  conv_normalise(d, &p);
-  if (id == 2 && d->algo >= 1 && d->st == 1 && d->pt == 1 && d->Ti == d->To && d->Cin >= 48 &&
-      d->Cout >= 48) {
-    // Winograd F(2,3) along T (the layer's forward / data gradient use it: desc.algo = 1): plan the
-    // (4,1,1) / stride-2 view over frame PAIRS, 32 pairs per box
-    ConvPlan q = p;
-    q.To = (p.To + 1) / 2;
-    q.st = 2;
-    conv_pick_box(&q, 5, 4, 1, 1);
-    const int planeP = q.plane | 1;
-    const size_t stage = ((size_t)64 * 65 + (size_t)64 * planeP) * sizeof(float);
-    const double lim = 2147483648.0;
-    if (q.lTW >= 1 && cdiv(q.plane, 64) <= 2 && 2 * stage <= 160 * 1024 &&
-        ((double)(1 << q.lTN) * d->x_nstride + (double)q.Cin * q.Ti * q.Hi * q.Wi) * 4.0 < lim &&
-        ((double)(1 << q.lTN) * d->y_nstride + (double)q.Cout * p.To * q.Ho * q.Wo) * 4.0 < lim) {
-      p = q;
-      w->planeP2 = planeP;
-      w->lds2 = 2 * stage;
-      w->mt2 = cdiv(p.Cout, 64);
-      w->ct2 = cdiv(p.Cin, 64);
-      int S = 512 / (w->mt2 * w->ct2);
-      if (S > p.ntiles / 4) S = p.ntiles / 4;
-      if (S < 1) S = 1;
-      w->S2 = xcd_round(S);
-      return 6;
-    }
-  }
-  // COCLR_WGRAD_WINO2: 0 never, 1 (default) the layers whose forward is Winograd (desc.algo = 1: maps of 16x16
-  // and up), 2 every wide (1,3,3) stride-1 'same' layer on an even map
-  static const int wino2_mode = getenv("COCLR_WGRAD_WINO2") ? atoi(getenv("COCLR_WGRAD_WINO2")) : 1;
-  if (id == 1 && (d->algo == 1 || wino2_mode >= 2) && d->st == 1 && d->sh == 1 && d->sw == 1 && d->ph == 1 &&
-      d->pw == 1 && d->pt == 0 && (d->Ho % 2) == 0 && (d->Wo % 2) == 0 && d->Hi == d->Ho && d->Wi == d->Wo) {
-    // F(2x2,3x3) domain: 32 co x 64 ci per workgroup, boxes of 64 positions = 16 blocks whose pairs are
-    // neighbours along w
-    const bool off = wino2_mode <= 0;
-    ConvPlan q = p;
-    conv_pick_box(&q, 6, 1, 3, 3);
-    if (q.lTW == 5 && q.lTH == 1 && q.lTT == 0 && q.lTN == 0 && q.Ho >= 4) {
-      // 32 x 2 boxes stage a 34 x 4 window (three LDS-DMA pieces per channel); 16 x 4 boxes an 18 x 6 one
-      // (two pieces): with 16 MFMAs per block pair instead of 36 the loader waves are what paces this
-      // kernel, and a third fewer window pieces is a third less of their work
-      q.lTW = 4; q.lTH = 2;
-      q.nbw = cdiv(q.Wo, 16); q.nbh = cdiv(q.Ho, 4);
-      q.ntiles = q.nbw * q.nbh * q.nbt * q.nbn;
-      q.nboxes = q.ntiles;
-      q.WH = 3 + 3; q.WW = 15 + 3;
-      q.plane1 = q.WT * q.WH * q.WW;
-      q.plane = q.plane1;
-      w->rebox = 1;
-    }
-    const int planeP = q.plane | 1;
-    const size_t stage = ((size_t)32 * 65 + (size_t)64 * planeP) * sizeof(float);
-    const double lim = 2147483648.0;
-    if (!off && q.lTW >= 2 && q.lTH >= 1 && cdiv(q.plane, 64) <= 3 && 2 * stage <= 160 * 1024 &&
-        ((double)(1 << q.lTN) * d->x_nstride + (double)q.Cin * q.Ti * q.Hi * q.Wi) * 4.0 < lim &&
-        ((double)(1 << q.lTN) * d->y_nstride + (double)q.Cout * q.To * q.Ho * q.Wo) * 4.0 < lim) {
-      p = q;
-      w->planeP2 = planeP;
-      w->lds2 = 2 * stage;
-      w->mt2 = cdiv(p.Cout, 32);
-      w->ct2 = cdiv(p.Cin, 64);
-      int S = 512 / (w->mt2 * w->ct2);
-      if (S > p.ntiles / 4) S = p.ntiles / 4;
-      if (S < 1) S = 1;
-      w->S2 = xcd_round(S);
-      return 7;
-    }
-    w->rebox = 0;
-  }
-  conv_pick_box(&p, 6, kt, kh, kw);
-  if ((id == 4 || id == 5) && p.Ti == 1 && p.Hi == 1 && p.lTW == 6 && p.lTN == 0 &&
-      (p.Wi % 64) == 0 && (d->x_nstride % 4) == 0 && (d->y_nstride % 4) == 0) {
-    // contiguous 64-position boxes, everything 16-byte aligned: the 16-byte-DMA GEMM kernel
-    // (pointer alignment is checked at launch)
-    w->pw = 1;
-  }
-  if (p.lTW < 1) return 0;
-  const int pch = cdiv(p.plane, 64);
-  const int maxpch = id == 1 ? 3 : (id == 3 ? 4 : 2);
-  if (pch > maxpch) return 0;
-  w->planeP2 = p.plane | 1;
-  const size_t stage = ((size_t)64 * MB * 65 + (size_t)64 * NB * w->planeP2) * sizeof(float);
-  w->lds2 = 2 * stage;
-  if (w->lds2 > 160 * 1024) return 0;
-  // every byte offset formed inside a box stays below the 2 GiB descriptor range
-  const double lim = 2147483648.0;
-  if (((double)(1 << p.lTN) * d->x_nstride + (double)p.Cin * p.Ti * p.Hi * p.Wi) * 4.0 >= lim) return 0;
-  if (((double)(1 << p.lTN) * d->y_nstride + (double)p.Cout * p.To * p.Ho * p.Wo) * 4.0 >= lim) return 0;
-  w->mt2 = cdiv(p.Cout, 64 * MB);
-  w->ct2 = cdiv(p.Cin, 64 * NB);
-  // one 512-thread workgroup per CU; two rounds of workgroups, >= 4 boxes each
-  int S = 512 / (w->mt2 * w->ct2);
-  if (S > p.ntiles / 4) S = p.ntiles / 4;
-  if (S < 1) S = 1;
-  w->S2 = xcd_round(S);
-  return id;
 }
 
 // Policy (measured per launch on one MI355X, tools/wgrad_order_ab.py, profiles/r04_wgrad_order.txt; traffic
@@ -1253,103 +1281,224 @@ inline int wgrad_tile_fastest(const coclr_conv_desc* d) {
   return forced >= 0 ? forced : wgrad_tile_default(d);
 }
 
+// What the stem and every wave-specialised candidate (box, planeP and id set) must pass: a kernel holds the window's
+// chunks, its two LDS stages fit, and every byte offset formed inside a box stays below the 2 GiB descriptor range.
+// `frames`: output frames of one dY channel.
+inline bool wgrad_fits(const coclr_conv_desc* d, const WPlan& w, int frames) {
+  const ConvPlan& p = w.p;
+  const double lim = 2147483648.0;
+  return sel_ok(select_wgrad(w, false)) &&
+         ((double)(1 << p.lTN) * d->x_nstride + (double)p.Cin * p.Ti * p.Hi * p.Wi) * 4.0 < lim &&
+         ((double)(1 << p.lTN) * d->y_nstride + (double)p.Cout * frames * p.Ho * p.Wo) * 4.0 < lim;
+}
+
+// stem: (1,7,7) over 3 channels -> conv_wgrad_stem_kernel
+bool pick_stem(const coclr_conv_desc* d, WPlan* w) {
+  if (!(d->kt == 1 && d->kh == 7 && d->kw == 7 && d->Cin == 3)) return false;
+  WPlan c = {};
+  c.id = WID_STEM;
+  ConvPlan& p = c.p;
+  conv_normalise(d, &p);
+  conv_pick_box(&p, 7, 1, 7, 7);
+  if (p.lTW < 1) return false;
+  // LDS row pitch of the window == 7 (mod 32): the (kh,kw) offsets of 32 consecutive columns
+  // then hit distinct banks (the extra columns are loaded like any other, never read)
+  while ((p.WW & 31) != 7) ++p.WW;
+  p.plane1 = p.WT * p.WH * p.WW;
+  p.plane = p.plane1 << p.lTN;
+  c.planeP = p.plane | 1;
+  if (!wgrad_fits(d, c, p.To)) return false;
+  c.mtiles = cdiv(p.Cout, 64);
+  c.jtiles = 1;
+  c.S = split_count(256, c.mtiles, p.ntiles, 2, false);   // one 512-thread workgroup per CU
+  *w = c;
+  return true;
+}
+
+// a wave-specialised candidate that fits becomes the plan; its tiles and split: one 512-thread workgroup per CU,
+// two rounds of workgroups, >= 4 boxes each
+inline bool wave_accept(WPlan* w, WPlan c) {
+  const WgradRow& r = *select_wgrad(c, false).row;
+  c.mtiles = cdiv(c.p.Cout, r.WHW ? 32 : 64 * r.MB);
+  c.jtiles = cdiv(c.p.Cin, 64 * r.NB);
+  c.S = split_count(512, c.mtiles * c.jtiles, c.p.ntiles, 4, true);
+  *w = c;
+  return true;
+}
+
+// the wave-specialised kernel (and, for pointwise layers, the 16-byte-DMA GEMM kernel beside it)
+bool pick_v2(const coclr_conv_desc* d, WPlan* w) {
+  const int kt = d->kt, kh = d->kh, kw = d->kw;
+  int id;
+  if (kt == 1 && kh == 3 && kw == 3) id = WID_S133;
+  else if (kt == 3 && kh == 1 && kw == 1) id = WID_T311;
+  else if (kt == 7 && kh == 1 && kw == 1) id = WID_T711;
+  else if (kt == 1 && kh == 1 && kw == 1) {
+    if (d->st != 1 || d->sh != 1 || d->sw != 1) return false;
+    id = (d->Cin > 64 && d->Cout > 64) ? WID_PW128 : WID_PW64;
+  } else return false;
+  // narrow layers: a 64co x 64ci workgroup tile would be mostly padding; the (ci,tap)-lane
+  // kernel packs them better
+  if (id <= WID_T711 && (d->Cin < 48 || d->Cout < 48)) return false;
+  if (d->Cin < 8) return false;
+  WPlan c = {};
+  conv_normalise(d, &c.p);
+  if (id == WID_T311 && d->algo >= 1 && d->st == 1 && d->pt == 1 && d->Ti == d->To && d->Cin >= 48 &&
+      d->Cout >= 48) {
+    // Winograd F(2,3) along T (the layer's forward / data gradient use it: desc.algo = 1): plan the
+    // (4,1,1) / stride-2 view over frame PAIRS, 32 pairs per box
+    WPlan q = c;
+    q.id = WID_WINO_T;
+    q.p.To = (c.p.To + 1) / 2;
+    q.p.st = 2;
+    conv_pick_box(&q.p, 5, 4, 1, 1);
+    q.planeP = q.p.plane | 1;
+    if (q.p.lTW >= 1 && wgrad_fits(d, q, c.p.To)) return wave_accept(w, q);
+  }
+  // COCLR_WGRAD_WINO2: 0 never, 1 (default) the layers whose forward is Winograd (desc.algo = 1: maps of 16x16
+  // and up), 2 every wide (1,3,3) stride-1 'same' layer on an even map
+  static const int wino2_mode = getenv("COCLR_WGRAD_WINO2") ? atoi(getenv("COCLR_WGRAD_WINO2")) : 1;
+  if (id == WID_S133 && (d->algo == 1 || wino2_mode >= 2) && d->st == 1 && d->sh == 1 && d->sw == 1 && d->ph == 1 &&
+      d->pw == 1 && d->pt == 0 && (d->Ho % 2) == 0 && (d->Wo % 2) == 0 && d->Hi == d->Ho && d->Wi == d->Wo) {
+    // F(2x2,3x3) domain: 32 co x 64 ci per workgroup, boxes of 64 positions = 16 blocks whose pairs are
+    // neighbours along w
+    WPlan q = c;
+    q.id = WID_WINO_HW;
+    ConvPlan& b = q.p;
+    conv_pick_box(&b, 6, 1, 3, 3);
+    if (b.lTW == 5 && b.lTH == 1 && b.lTT == 0 && b.lTN == 0 && b.Ho >= 4) {
+      // 32 x 2 boxes stage a 34 x 4 window (three LDS-DMA pieces per channel); 16 x 4 boxes an 18 x 6 one
+      // (two pieces): with 16 MFMAs per block pair instead of 36 the loader waves are what paces this
+      // kernel, and a third fewer window pieces is a third less of their work
+      b.lTW = 4; b.lTH = 2;
+      b.nbw = cdiv(b.Wo, 16); b.nbh = cdiv(b.Ho, 4);
+      b.ntiles = b.nbw * b.nbh * b.nbt * b.nbn;
+      b.nboxes = b.ntiles;
+      b.WH = 3 + 3; b.WW = 15 + 3;
+      b.plane1 = b.WT * b.WH * b.WW;
+      b.plane = b.plane1;
+      q.rebox = 1;
+    }
+    q.planeP = b.plane | 1;
+    if (wino2_mode > 0 && b.lTW >= 2 && b.lTH >= 1 && wgrad_fits(d, q, b.To)) return wave_accept(w, q);
+  }
+  c.id = id;
+  ConvPlan& p = c.p;
+  conv_pick_box(&p, 6, kt, kh, kw);
+  // contiguous 64-position boxes, everything 16-byte aligned: the 16-byte-DMA GEMM kernel
+  // (pointer alignment is checked at launch)
+  c.pw = (id == WID_PW128 || id == WID_PW64) && p.Ti == 1 && p.Hi == 1 && p.lTW == 6 && p.lTN == 0 &&
+         (p.Wi % 64) == 0 && (d->x_nstride % 4) == 0 && (d->y_nstride % 4) == 0;
+  if (p.lTW < 1) return false;
+  c.planeP = p.plane | 1;
+  return wgrad_fits(d, c, p.To) && wave_accept(w, c);
+}
+
+// stem, then the wave-specialised kernel, then the first-generation kernel for whatever those two turned down
 int plan_wgrad(const coclr_conv_desc* d, WPlan* w) {
   if (!d || d->N <= 0 || d->Cin <= 0 || d->Cout <= 0) return COCLR_EINVAL;
   if (d->dt != 1 || d->dh != 1 || d->dw != 1) return COCLR_EINVAL;
-  w->v2 = pick_stem(d, w);
-  if (w->v2) return 0;
-  w->v2 = pick_v2(d, w);
-  if (w->v2) return 0;
-  ConvPlan& p = w->p;
+  if (pick_stem(d, w) || pick_v2(d, w)) return 0;
+  WPlan c = {};
+  c.id = WID_GEN1;
+  ConvPlan& p = c.p;
   conv_normalise(d, &p);
   const int taps = d->kt * d->kh * d->kw;
   conv_pick_box(&p, 7, d->kt, d->kh, d->kw);
-  const int J = p.Cin * taps;
   if (p.WT > 255 || p.WH > 255 || p.WW > 255 || (1 << p.lTN) > 255) return COCLR_EINVAL;
-  w->pch = cdiv(p.plane, 64);
-  w->planeP = w->pch * 64 + 1;
-  w->BJ = taps == 1 ? 64 : 128;
-  w->nci_max = taps == 1 ? 64 : (w->BJ - 1) / taps + 2;
-  if (w->nci_max > p.Cin) w->nci_max = p.Cin;
-  // variant = PCH bucket
-  if (w->pch <= 2) w->variant = 0;
-  else if (w->pch <= 4) w->variant = 1;
-  else if (w->pch <= 8) w->variant = 2;
-  else if (w->pch <= 20) w->variant = 3;
-  else return COCLR_EINVAL;
-  const size_t lds = ((size_t)64 * 129 + 128 + (size_t)w->nci_max * w->planeP) * sizeof(float);
-  if (lds > 160 * 1024) return COCLR_EINVAL;
-  w->jtiles = cdiv(J, w->BJ);
-  w->mtiles = cdiv(p.Cout, 64);
-  // split-K: enough workgroups to fill 256 CUs x ~3, but at least 4 boxes per workgroup so
-  // the partial-sum traffic stays small next to the streamed operands
-  int S = 768 / (w->jtiles * w->mtiles);
-  if (S > p.ntiles / 4) S = p.ntiles / 4;
-  if (S < 1) S = 1;
-  w->S = xcd_round(S);
+  c.planeP = cdiv(p.plane, 64) * 64 + 1;
+  c.bj = taps == 1 ? 64 : 128;
+  c.nci_max = taps == 1 ? 64 : (c.bj - 1) / taps + 2;
+  if (c.nci_max > p.Cin) c.nci_max = p.Cin;
+  if (!sel_ok(select_wgrad(c, false))) return COCLR_EINVAL;   // more than 20 window chunks, or LDS
+  c.jtiles = cdiv(p.Cin * taps, c.bj);
+  c.mtiles = cdiv(p.Cout, 64);
+  // enough workgroups to fill 256 CUs x ~3
+  c.S = split_count(768, c.jtiles * c.mtiles, p.ntiles, 4, true);
+  *w = c;
   return 0;
 }
 
-// LDS of the stem kernel's two stages in the BNA form
-inline size_t stem_bna_lds(const WPlan& w) {
-  return 2 * ((size_t)2 * 64 * 129 + 128 + (size_t)3 * w.planeP2) * sizeof(float);
+// ---- kernel arguments -------------------------------------------------------------------------------------------
+// the fields both argument blocks have
+template <typename Args>
+void fill_geometry(Args& a, const coclr_conv_desc* d, const WPlan& w, const float* x, const float* dy,
+                   float* workspace) {
+  const ConvPlan& p = w.p;
+  a.x = x; a.dy = dy; a.part = workspace;
+  a.x_nstride = d->x_nstride; a.dy_nstride = d->y_nstride;
+  a.x_cstride = p.Ti * p.Hi * p.Wi; a.dy_cstride = p.To * p.Ho * p.Wo;
+  a.N = p.N; a.Cin = p.Cin; a.Cout = p.Cout; a.J = p.Cin * d->kt * d->kh * d->kw;
+  a.Ti = p.Ti; a.Hi = p.Hi; a.Wi = p.Wi; a.To = p.To; a.Ho = p.Ho; a.Wo = p.Wo;
+  a.st = p.st; a.sh = p.sh; a.sw = p.sw; a.pt = p.pt; a.ph = p.ph; a.pw = p.pw;
+  a.lTW = p.lTW; a.lTH = p.lTH; a.lTT = p.lTT; a.lTN = p.lTN;
+  a.nbw = p.nbw; a.nbh = p.nbh; a.nbt = p.nbt; a.nbn = p.nbn;
+  a.WT = p.WT; a.WH = p.WH; a.WW = p.WW; a.plane1 = p.plane1; a.plane = p.plane;
+  a.planeP = w.planeP;
+  a.ntiles = p.ntiles; a.S = w.S;
 }
-// the stem kernel that applies BatchNorm's backward while it loads exists for this plan (see _bn_ok)
-inline bool stem_bn_ok(const WPlan& w) { return w.v2 == 9 && stem_bna_lds(w) <= (size_t)160 * 1024; }
 
-// Which kernel instantiation a planned launch runs: the ONE place that decides it (wgrad_run launches what
-// this says, coclr_conv3d_wgrad_plan reports it, coclr_conv3d_wgrad_workspace sizes the slices by it).
-enum { WF_GEN1 = 0, WF_WAVE = 1, WF_STEM = 2, WF_PWDMA = 3 };
-struct WSel {
-  int family;   // WF_*
-  int id;       // WF_WAVE: 1-7; WF_PWDMA: 4 (128 x 128 tile) or 5 (64 x 64); WF_STEM: 9; WF_GEN1: 0
-  int pch;      // template PCH (0: the kernel has none)
-  int bj;       // WF_GEN1: template BJ
-  int slices;   // workspace slices one split writes
+// BatchNorm backward apply pass folded into the weight gradient (stem kernel, BNA form)
+struct WgradBn {
+  const float* y;
+  const float* coef;
+  long y_nstride;
+  int relu;
 };
-inline WSel select_wgrad(const WPlan& w, bool aligned16) {
-  WSel s = {WF_GEN1, 0, 0, 0, 1};
-  if (!w.v2) {
-    static const int pch_of[4] = {2, 4, 8, 20};
-    s.pch = pch_of[w.variant];
-    s.bj = w.BJ;
-    return s;
+
+void fill_args(WgradKernArgs* ka, const WgradRow& row, const coclr_conv_desc* d, const WPlan& w, const float* x,
+               const float* dy, float* workspace, const WgradBn* bn) {
+  const ConvPlan& p = w.p;
+  if (row.family == WF_GEN1) {
+    WgradArgs& a = ka->gen1;
+    fill_geometry(a, d, w, x, dy, workspace);
+    a.taps = d->kt * d->kh * d->kw; a.KH = d->kh; a.KW = d->kw;
+    a.pch = cdiv(p.plane, 64);
+    a.jtiles = w.jtiles; a.mtiles = w.mtiles;
+    return;
   }
-  const int pch = cdiv(w.p2.plane, 64);
-  s.id = w.v2;
-  if (w.v2 == 9) {
-    s.family = WF_STEM; s.pch = 20; s.slices = 4;
-  } else if (w.pw && aligned16) {
-    s.family = WF_PWDMA;
-  } else {
-    s.family = WF_WAVE;
-    switch (w.v2) {
-      case 1: case 7: s.pch = pch <= 2 ? 2 : 3; break;
-      case 3: s.pch = 4; break;
-      default: s.pch = 2;
-    }
-    if (w.v2 == 7) s.slices = 2;
-  }
-  return s;
+  Wgrad2Args& a = ka->wave;
+  fill_geometry(a, d, w, x, dy, workspace);
+  a.inv_plane1 = 1.0f / (float)p.plane1;
+  a.inv_hw = 1.0f / (float)(p.WH * p.WW);
+  a.inv_ww = 1.0f / (float)p.WW;
+  a.To_full = d->To;
+  a.xcd = wgrad_tile_fastest(d);
+  a.bn_y = bn ? bn->y : nullptr; a.bn_coef = bn ? bn->coef : nullptr;
+  a.bn_y_nstride = bn ? bn->y_nstride : 0; a.bn_relu = bn ? bn->relu : 0;
+  if (w.id == WID_WINO_T) a.dy_cstride = d->To * p.Ho * p.Wo;     // p.To counts pairs there
 }
 
-template <int BJ, int PCH>
-int launch_wgrad(WgradArgs& a, const WPlan& w, hipStream_t stream) {
-  const size_t lds = ((size_t)64 * 129 + 128 + (size_t)w.nci_max * a.planeP) * sizeof(float);
-  auto kern = conv_wgrad_kernel<BJ, PCH>;
-  static std::atomic<uint64_t> attr_done{0};
-  COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
-  hipLaunchKernelGGL(kern, dim3(a.S, a.jtiles, a.mtiles), dim3(256), lds, stream, a);
-  COCLR_LAUNCH_CHECK();
-  return 0;
-}
-
-template <int KT, int KH, int KW, int MB, int NB, int PCH, bool WINO = false, int NL = 4, bool WHW = false>
-int launch_wgrad2(const Wgrad2Args& a, const WPlan& w, hipStream_t stream) {
-  auto kern = conv_wgrad2_kernel<KT, KH, KW, MB, NB, PCH, WINO, NL, WHW>;
-  static std::atomic<uint64_t> attr_done{0};
-  COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
-  hipLaunchKernelGGL(kern, dim3(w.S2, w.ct2, w.mt2), dim3(256 + 64 * NL), w.lds2, stream, a);
+// validate, plan, select, fill, launch, fold
+int wgrad_run(const coclr_conv_desc* d, const float* x, const float* dy, const WgradBn* bn,
+              float* const* dw_list, const int32_t* row_end, int nseg, float* workspace,
+              int64_t w_co_stride, int64_t w_ci_stride, int tap_base, int accumulate, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!d || !dw_list || !row_end || nseg < 1 || nseg > 4) return COCLR_EINVAL;
+  WgradDst dst;
+  dst.n = nseg;
+  for (int i = 0; i < 4; ++i) {
+    dst.p[i] = i < nseg ? dw_list[i] : nullptr;
+    dst.end[i] = i < nseg ? row_end[i] : 0;
+    if (i < nseg && (!dw_list[i] || row_end[i] <= (i ? row_end[i - 1] : 0))) return COCLR_EINVAL;
+  }
+  if (row_end[nseg - 1] != d->Cout) return COCLR_EINVAL;
+  WPlan w;
+  int rc = plan_wgrad(d, &w);
+  if (rc) return rc;
+  const WSel sel = select_wgrad(w, ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0, bn != nullptr);
+  if (!sel_ok(sel)) return COCLR_EINVAL;   // only with `bn`: see _bn_ok
+  WgradKernArgs ka;
+  fill_args(&ka, *sel.row, d, w, x, dy, workspace, bn);
+  rc = sel.row->launch(ka, dim3(w.S, w.jtiles, w.mtiles), sel.lds, stream);
+  if (rc) return rc;
+  const int taps = d->kt * d->kh * d->kw;
+  const int J = d->Cin * taps;
+  const long CJ = (long)d->Cout * J;
+  int blocks = cdiv(CJ, 64);
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, stream, workspace, dst, CJ,
+                     w.S * sel.row->slices, J, taps, (long)w_co_stride, (long)w_ci_stride, tap_base, accumulate);
   COCLR_LAUNCH_CHECK();
   return 0;
 }
@@ -1361,8 +1510,7 @@ extern "C" int coclr_conv3d_wgrad_workspace(const coclr_conv_desc* d, int64_t* e
   int rc = plan_wgrad(d, &w);
   if (rc) return rc;
   // split slices: the stem kernel writes four per split (one per matrix wave), the F(2x2,3x3) form two
-  *elems = (int64_t)(w.v2 ? w.S2 : w.S) * select_wgrad(w, true).slices * d->Cout * d->Cin * d->kt * d->kh *
-           d->kw;
+  *elems = (int64_t)w.S * select_wgrad(w, true).row->slices * d->Cout * d->Cin * d->kt * d->kh * d->kw;
   return 0;
 }
 
@@ -1371,34 +1519,18 @@ extern "C" int coclr_conv3d_wgrad_plan(const coclr_conv_desc* d, int operands_16
   WPlan w;
   int rc = plan_wgrad(d, &w);
   if (rc) return rc;
-  const WSel s = select_wgrad(w, operands_16B_aligned != 0);
-  const ConvPlan& p = w.v2 ? w.p2 : w.p;
-  out[0] = s.family; out[1] = s.id; out[2] = s.pch; out[3] = s.bj;
-  out[4] = w.v2 ? w.S2 : w.S;
-  out[5] = s.slices;
-  out[6] = w.v2 ? w.ct2 : w.jtiles;
-  out[7] = w.v2 ? w.mt2 : w.mtiles;
+  const WgradRow& r = *select_wgrad(w, operands_16B_aligned != 0).row;
+  const ConvPlan& p = w.p;
+  out[0] = r.family; out[1] = r.id; out[2] = r.PCH; out[3] = r.BJ;
+  out[4] = w.S; out[5] = r.slices; out[6] = w.jtiles; out[7] = w.mtiles;
   out[8] = p.lTW; out[9] = p.lTH; out[10] = p.lTT; out[11] = p.lTN;
   out[12] = p.ntiles;
   // only the wave-specialised and pointwise-DMA kernels consult the order (wgrad_tile)
-  out[13] = (s.family == WF_WAVE || s.family == WF_PWDMA) ? wgrad_tile_default(d) : 0;
+  out[13] = (r.family == WF_WAVE || r.family == WF_PWDMA) ? wgrad_tile_default(d) : 0;
   out[14] = stem_bn_ok(w) ? 1 : 0;
   out[15] = w.rebox;
   return 0;
 }
-
-namespace {
-// BatchNorm backward apply pass folded into the weight gradient (stem kernel, BNA form)
-struct WgradBn {
-  const float* y;
-  const float* coef;
-  long y_nstride;
-  int relu;
-};
-int wgrad_run(const coclr_conv_desc* d, const float* x, const float* dy, const WgradBn* bn,
-              float* const* dw_list, const int32_t* row_end, int nseg, float* workspace,
-              int64_t w_co_stride, int64_t w_ci_stride, int tap_base, int accumulate, void* stream_);
-}  // namespace
 
 extern "C" int coclr_conv3d_wgrad(const coclr_conv_desc* d, const float* x, const float* dy,
                                   float* dw, float* workspace, int64_t w_co_stride,
@@ -1440,136 +1572,3 @@ extern "C" int coclr_conv3d_wgrad_bn(const coclr_conv_desc* d, const float* x, c
                    stream_);
 }
 
-namespace {
-int wgrad_run(const coclr_conv_desc* d, const float* x, const float* dy, const WgradBn* bn,
-              float* const* dw_list, const int32_t* row_end, int nseg, float* workspace,
-              int64_t w_co_stride, int64_t w_ci_stride, int tap_base, int accumulate, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (!d || !dw_list || !row_end || nseg < 1 || nseg > 4) return COCLR_EINVAL;
-  WgradDst dst;
-  dst.n = nseg;
-  for (int i = 0; i < 4; ++i) {
-    dst.p[i] = i < nseg ? dw_list[i] : nullptr;
-    dst.end[i] = i < nseg ? row_end[i] : 0;
-    if (i < nseg && (!dw_list[i] || row_end[i] <= (i ? row_end[i - 1] : 0))) return COCLR_EINVAL;
-  }
-  if (row_end[nseg - 1] != d->Cout) return COCLR_EINVAL;
-  WPlan w;
-  int rc = plan_wgrad(d, &w);
-  if (rc) return rc;
-  if (bn && !stem_bn_ok(w)) return COCLR_EINVAL;   // see _bn_ok
-  const int taps = d->kt * d->kh * d->kw;
-  int S_used;
-  if (w.v2) {
-    const ConvPlan& p = w.p2;
-    Wgrad2Args a;
-    a.x = x; a.dy = dy; a.part = workspace;
-    a.x_nstride = d->x_nstride; a.dy_nstride = d->y_nstride;
-    a.x_cstride = p.Ti * p.Hi * p.Wi; a.dy_cstride = p.To * p.Ho * p.Wo;
-    a.N = p.N; a.Cin = p.Cin; a.Cout = p.Cout; a.J = p.Cin * taps;
-    a.Ti = p.Ti; a.Hi = p.Hi; a.Wi = p.Wi; a.To = p.To; a.Ho = p.Ho; a.Wo = p.Wo;
-    a.st = p.st; a.sh = p.sh; a.sw = p.sw; a.pt = p.pt; a.ph = p.ph; a.pw = p.pw;
-    a.lTW = p.lTW; a.lTH = p.lTH; a.lTT = p.lTT; a.lTN = p.lTN;
-    a.nbw = p.nbw; a.nbh = p.nbh; a.nbt = p.nbt; a.nbn = p.nbn;
-    a.WT = p.WT; a.WH = p.WH; a.WW = p.WW; a.plane1 = p.plane1; a.plane = p.plane;
-    a.planeP = w.planeP2;
-    a.inv_plane1 = 1.0f / (float)p.plane1;
-    a.inv_hw = 1.0f / (float)(p.WH * p.WW);
-    a.inv_ww = 1.0f / (float)p.WW;
-    a.ntiles = p.ntiles; a.S = w.S2;
-    a.To_full = d->To;
-    a.xcd = wgrad_tile_fastest(d);
-    a.bn_y = bn ? bn->y : nullptr; a.bn_coef = bn ? bn->coef : nullptr;
-    a.bn_y_nstride = bn ? bn->y_nstride : 0; a.bn_relu = bn ? bn->relu : 0;
-    if (w.v2 == 6) a.dy_cstride = d->To * p.Ho * p.Wo;     // p.To counts pairs there
-    const WSel sel = select_wgrad(w, ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0);
-    if (sel.family == WF_PWDMA) {
-      const bool big = sel.id == 4;
-      const size_t lds = (size_t)2 * (big ? 256 : 128) * 64 * sizeof(float);
-      if (big) {
-        auto kern = conv_wgrad_pw_kernel<2, 2>;
-        static std::atomic<uint64_t> attr_done{0};
-        COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
-        hipLaunchKernelGGL(kern, dim3(w.S2, w.ct2, w.mt2), dim3(512), lds, stream, a);
-      } else {
-        auto kern = conv_wgrad_pw_kernel<1, 1>;
-        static std::atomic<uint64_t> attr_done{0};
-        COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
-        hipLaunchKernelGGL(kern, dim3(w.S2, w.ct2, w.mt2), dim3(512), lds, stream, a);
-      }
-      COCLR_LAUNCH_CHECK();
-      rc = 0;
-    } else if (sel.family == WF_STEM) {
-      if (bn) {
-        auto kern = conv_wgrad_stem_kernel<7, 7, 3, 20, true>;
-        static std::atomic<uint64_t> attr_done{0};
-        COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
-        hipLaunchKernelGGL(kern, dim3(w.S2, 1, w.mt2), dim3(512), stem_bna_lds(w), stream, a);
-      } else {
-        auto kern = conv_wgrad_stem_kernel<7, 7, 3, 20>;
-        static std::atomic<uint64_t> attr_done{0};
-        COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done));
-        hipLaunchKernelGGL(kern, dim3(w.S2, 1, w.mt2), dim3(512), w.lds2, stream, a);
-      }
-      COCLR_LAUNCH_CHECK();
-      rc = 0;
-    } else
-    switch (sel.id * 8 + sel.pch) {
-      case 1 * 8 + 2: rc = launch_wgrad2<1, 3, 3, 1, 1, 2>(a, w, stream); break;
-      case 1 * 8 + 3: rc = launch_wgrad2<1, 3, 3, 1, 1, 3>(a, w, stream); break;
-      // the temporal forms are loader-bound with four loader waves (3 or 4 MFMAs per four LDS-DMA
-      // pieces): EIGHT loader waves beside the four matrix waves (768 threads; 48-64 accumulator
-      // registers leave room for three waves per SIMD): direct 1.20 -> 1.05 ms, Winograd 1.07 ->
-      // 0.90 ms on Conv_2c.conv2.  (7,1,1) (112 accumulators) and (1,3,3) (144) keep four.
-      case 2 * 8 + 2: rc = launch_wgrad2<3, 1, 1, 1, 1, 2, false, 8>(a, w, stream); break;
-      case 3 * 8 + 4: rc = launch_wgrad2<7, 1, 1, 1, 1, 4>(a, w, stream); break;
-      case 4 * 8 + 2: rc = launch_wgrad2<1, 1, 1, 2, 2, 2>(a, w, stream); break;
-      case 5 * 8 + 2: rc = launch_wgrad2<1, 1, 1, 1, 1, 2>(a, w, stream); break;
-      case 6 * 8 + 2: rc = launch_wgrad2<4, 1, 1, 1, 1, 2, true, 8>(a, w, stream); break;
-      case 7 * 8 + 2: rc = launch_wgrad2<1, 3, 3, 1, 1, 2, false, 4, true>(a, w, stream); break;
-      case 7 * 8 + 3: rc = launch_wgrad2<1, 3, 3, 1, 1, 3, false, 4, true>(a, w, stream); break;
-      default: rc = COCLR_EINVAL;
-    }
-    if (rc) return rc;
-    S_used = w.S2 * sel.slices;
-  } else {
-    const ConvPlan& p = w.p;
-    WgradArgs a;
-    a.x = x; a.dy = dy; a.part = workspace;
-    a.x_nstride = d->x_nstride; a.dy_nstride = d->y_nstride;
-    a.x_cstride = p.Ti * p.Hi * p.Wi; a.dy_cstride = p.To * p.Ho * p.Wo;
-    a.N = p.N; a.Cin = p.Cin; a.Cout = p.Cout;
-    a.taps = taps; a.KH = d->kh; a.KW = d->kw;
-    a.J = p.Cin * a.taps;
-    a.Ti = p.Ti; a.Hi = p.Hi; a.Wi = p.Wi; a.To = p.To; a.Ho = p.Ho; a.Wo = p.Wo;
-    a.st = p.st; a.sh = p.sh; a.sw = p.sw; a.pt = p.pt; a.ph = p.ph; a.pw = p.pw;
-    a.lTW = p.lTW; a.lTH = p.lTH; a.lTT = p.lTT; a.lTN = p.lTN;
-    a.nbw = p.nbw; a.nbh = p.nbh; a.nbt = p.nbt; a.nbn = p.nbn;
-    a.WT = p.WT; a.WH = p.WH; a.WW = p.WW; a.plane1 = p.plane1; a.plane = p.plane;
-    a.planeP = w.planeP; a.pch = w.pch;
-    a.ntiles = p.ntiles; a.S = w.S; a.jtiles = w.jtiles; a.mtiles = w.mtiles;
-    const WSel sel = select_wgrad(w, false);
-    switch (sel.bj * 32 + sel.pch) {
-      case 64 * 32 + 2: rc = launch_wgrad<64, 2>(a, w, stream); break;
-      case 64 * 32 + 4: rc = launch_wgrad<64, 4>(a, w, stream); break;
-      case 64 * 32 + 8: rc = launch_wgrad<64, 8>(a, w, stream); break;
-      case 64 * 32 + 20: rc = launch_wgrad<64, 20>(a, w, stream); break;
-      case 128 * 32 + 2: rc = launch_wgrad<128, 2>(a, w, stream); break;
-      case 128 * 32 + 4: rc = launch_wgrad<128, 4>(a, w, stream); break;
-      case 128 * 32 + 8: rc = launch_wgrad<128, 8>(a, w, stream); break;
-      case 128 * 32 + 20: rc = launch_wgrad<128, 20>(a, w, stream); break;
-      default: rc = COCLR_EINVAL;
-    }
-    if (rc) return rc;
-    S_used = w.S;
-  }
-  const int J = d->Cin * taps;
-  const long CJ = (long)d->Cout * J;
-  int blocks = cdiv(CJ, 64);
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, stream, workspace, dst, CJ,
-                     S_used, J, taps, (long)w_co_stride, (long)w_ci_stride, tap_base, accumulate);
-  COCLR_LAUNCH_CHECK();
-  return 0;
-}
-}  // namespace
