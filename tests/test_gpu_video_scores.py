@@ -1,6 +1,9 @@
 """Video-level scores on the GPU: the two segmented-accumulate kernels (csrc/retrieval.hip) against float64
 torch on the CPU, and coclr_amd.eval.video.VideoEvaluator end to end on S3D against the CPU oracle restating
-eval/main_classifier.py:482-494,533 (multi-crop probabilities) and :624-640 (retrieval features).
+eval/main_classifier.py:482-494,533 (multi-crop probabilities) and :624-640 (retrieval features).  The kernels' exact
+suite is tests/test_gpu_segment_exact.py; the last tests here run the evaluator's own bookkeeping on a table model: its
+tables growing past 64 videos, passes of more than 64 segments, a crop cut into several batches, batches of one clip,
+and a second use after finish().
 
 Bars: 1e-6 relative for the kernels -- elementwise fp32 formulas, the bar of the loss epilogue
 (tests/test_gpu_next.py) -- and the project's standing 1e-3 for anything that went through the backbone."""
@@ -8,7 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from _cases import check_close
+from _cases import check_close, rel_err
 from oracle import coclr_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -249,3 +252,141 @@ def test_video_evaluator_end_to_end_on_s3d():
     acc, _, _ = nn_retrieval(res.features[ntr:], rl[ntr:].cuda(), res.features[:ntr], rl[:ntr].cuda(), ks=(1, 5))
     want_acc, _ = orc.nn_retrieval(ref_feat[ntr:].float(), rl[ntr:], ref_feat[:ntr].float(), rl[:ntr], ks=(1, 5))
     assert [round(float(a), 5) for a in acc] == [round(a, 5) for a in want_acc]
+
+
+# ---- the evaluator's tables and batching on the table model (a model pass costs nothing) ----------------------------------
+
+def _table_run(lengths, crops, batch_clips, order="crop-major", C_=51, width=24, seed=0, ev=None):
+    """`lengths[v]` clips per crop of video v through a VideoEvaluator on a _TableModel; `order`: every video's first crop,
+    then every video's second ("crop-major"), or all crops of a video before the next video ("video-major").
+    Returns (VideoScores, float64 probabilities, float64 features, labels, the evaluator): the references are the
+    per-video loops of eval/main_classifier.py:482-494,533 and :624-640."""
+    from coclr_amd.eval.video import VideoEvaluator
+    g = torch.Generator().manual_seed(seed)
+    n_rows = sum(lengths)
+    logits = torch.randn(crops, n_rows, C_, generator=g) * 3
+    feats = torch.randn(crops, n_rows, width, generator=g)
+    labels = [int(v) for v in torch.randint(0, C_, (len(lengths),), generator=g)]
+    want_p, want_f, pos = [], [], 0
+    for n in lengths:
+        want_p.append(F.softmax(logits[:, pos:pos + n].double(), -1).mean(1).mean(0))
+        want_f.append(feats[:, pos:pos + n].double().mean(1).mean(0))
+        pos += n
+    if ev is None:
+        model = _TableModel(logits.reshape(crops * n_rows, C_), feats.reshape(crops * n_rows, width)).cuda().eval()
+        ev = VideoEvaluator(model, batch_clips=batch_clips)
+    else:
+        assert ev.model.logits.shape == (crops * n_rows, C_)
+        ev.model.logits.copy_(logits.reshape(crops * n_rows, C_))
+        ev.model.feats.copy_(feats.reshape(crops * n_rows, width))
+    starts = [sum(lengths[:v]) for v in range(len(lengths))]
+
+    def add(v, c):
+        clips = torch.zeros(lengths[v], 3, 1, 1, 1)
+        first = c * n_rows + starts[v]
+        clips[:, 0, 0, 0, 0] = torch.arange(first, first + lengths[v], dtype=torch.float32)
+        got = ev.add(clips.cuda(), label=labels[v], video=None if c == 0 else v)
+        assert got == v
+    if order == "crop-major":
+        for c in range(crops):
+            for v in range(len(lengths)):
+                add(v, c)
+    else:
+        for v in range(len(lengths)):
+            for c in range(crops):
+                add(v, c)
+    res = ev.finish()
+    torch.cuda.synchronize()
+    return res, torch.stack(want_p), torch.stack(want_f), labels, ev
+
+
+def _held_to_the_bar(res, want_p, want_f, labels, what):
+    """1e-6 of the largest reference element, probabilities and features; equal labels.  Printed besides: the worst
+    video's error against its OWN largest probability (a dropped or doubled segment is wrong by the order of that)."""
+    ep = (res.probs.cpu().double() - want_p).abs().max(1).values / want_p.abs().max(1).values
+    print("%s: probabilities %.2e and features %.2e of the largest reference element; worst video %d, %.2e of its own "
+          "largest probability" % (what, rel_err(res.probs, want_p), rel_err(res.features, want_f), int(ep.argmax()),
+                                   float(ep.max())))
+    check_close(res.probs, want_p, 1e-6, what + ": probabilities")
+    check_close(res.features, want_f, 1e-6, what + ": features")
+    assert res.labels.cpu().tolist() == labels
+
+
+@pytest.mark.parametrize("order", ["crop-major", "video-major"])
+def test_tables_grow_while_sums_are_live(monkeypatch, order):
+    """150 videos: the tables start at 64 rows and are copied to 130 or more when the 65th video has been added, with
+    the sums of the videos before it in them (video-major, a second time past 130 videos)."""
+    from coclr_amd import ops
+    g = torch.Generator().manual_seed(5)
+    lengths = [int(n) for n in torch.randint(1, 4, (150,), generator=g)]
+    assert set(lengths) == {1, 2, 3}
+    caps = []
+    inner = ops.segment_softmax_accum
+
+    def watched(x, segs, w, out):
+        caps.append((out.shape[0], max(o for _, _, o in segs)))
+        inner(x, segs, w, out)
+    monkeypatch.setattr(ops, "segment_softmax_accum", watched)
+    res, want_p, want_f, labels, ev = _table_run(lengths, 2, 32, order)
+    assert ev.passes == -(-2 * sum(lengths) // 32) == len(caps)
+    sizes = [c for c, _ in caps]
+    assert sizes[0] == 64 and sizes == sorted(sizes) and len(set(sizes)) >= 2
+    grown = sorted(set(sizes))[1]
+    assert grown >= 130 and sizes.index(grown) >= 2          # passes before the copy left sums in the 64-row tables
+    assert all(top < cap for cap, top in caps)
+    assert res.probs.shape == (150, 51) and res.features.shape == (150, 24)
+    _held_to_the_bar(res, want_p, want_f, labels, "150 videos, %s" % order)
+    check_close(res.probs[:64], want_p[:64], 1e-6, "the first 64 videos")
+
+
+def test_more_segments_than_one_launch_takes(monkeypatch):
+    from coclr_amd import ops
+    seen = []
+    inner = ops.segment_softmax_accum
+    monkeypatch.setattr(ops, "segment_softmax_accum",
+                        lambda x, segs, w, out: (seen.append(len(segs)), inner(x, segs, w, out))[1])
+    res, want_p, want_f, labels, ev = _table_run([1] * 100, 2, 80)
+    assert seen == [80, 80, 40] and max(seen) > 64          # 80 segments: a launch of 64 and one of 16
+    _held_to_the_bar(res, want_p, want_f, labels, "80 one-clip videos per pass")
+    # video-major, both crops of a video lie next to each other in one pass: the same output row twice, 40 times, in a
+    # pass of more than 64 segments
+    seen.clear()
+    res, want_p, want_f, labels, ev = _table_run([1] * 100, 2, 80, "video-major", seed=1)
+    assert seen == [80, 80, 40]
+    _held_to_the_bar(res, want_p, want_f, labels, "80 one-clip crops per pass, both crops of a video adjacent")
+
+
+def test_a_crop_cut_into_three_batches(monkeypatch):
+    from coclr_amd import ops
+    seen = []
+    inner = ops.segment_accum
+    monkeypatch.setattr(ops, "segment_accum",
+                        lambda x, segs, w, out: (seen.append((list(segs), list(w))), inner(x, segs, w, out))[1])
+    lengths = [2, 3, 20, 1, 2]
+    res, want_p, want_f, labels, ev = _table_run(lengths, 2, 8)
+    pieces = [n for segs, _ in seen for _, n, v in segs if v == 2]
+    assert pieces[:4] == [3, 8, 8, 1] and sum(pieces) == 40          # the first crop: four pieces, two of them whole batches
+    assert all(w == 1.0 / lengths[v] for segs, ws in seen for (_, _, v), w in zip(segs, ws))
+    _held_to_the_bar(res, want_p, want_f, labels, "a crop of 20 clips in batches of 8")
+
+
+def test_batches_of_one_clip():
+    res, want_p, want_f, labels, ev = _table_run([1, 3, 2, 5], 2, 1)
+    assert ev.passes == 22
+    _held_to_the_bar(res, want_p, want_f, labels, "batch_clips = 1")
+
+
+def test_an_evaluator_is_reusable_after_finish():
+    first = [3, 1, 7, 2, 9, 1]
+    second = [2, 11, 1, 4, 5]                           # another number of videos, the same number of clips
+    assert sum(first) == sum(second) and len(first) != len(second)
+    res1, want_p, want_f, labels, ev = _table_run(first, 2, 8, seed=2)
+    _held_to_the_bar(res1, want_p, want_f, labels, "first use")
+    assert len(ev) == 0
+    res2, want_p, want_f, labels, ev = _table_run(second, 2, 8, seed=3, ev=ev)
+    _held_to_the_bar(res2, want_p, want_f, labels, "second use")
+    fresh, _, _, _, _ = _table_run(second, 2, 8, seed=3)
+    assert torch.equal(res2.probs, fresh.probs) and torch.equal(res2.features, fresh.features)
+    assert torch.equal(res2.labels, fresh.labels)
+    assert float(res2.top1) == float(fresh.top1) and float(res2.top5) == float(fresh.top5)
+    assert res2.probs.shape[0] == len(second) != res1.probs.shape[0]
