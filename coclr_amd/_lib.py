@@ -181,6 +181,7 @@ _SIGNATURES = {
     "coclr_bn1d_stats": [vp, vp, vp, i32, i32, vp],
     "coclr_center_rows": [vp, vp, vp, i32, i32, vp],
     "coclr_retrieval_hits": [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, vp],
+    "coclr_fuse_scores": [vp, vp, vp, vp, vp, vp, i32, i32, vp],
     "coclr_segment_softmax_accum": [vp, _P(i32), _P(f32), vp, i32, i32, i32, i32, vp],
     "coclr_segment_accum": [vp, _P(i32), _P(f32), vp, i32, i32, i32, i32, vp],
 }

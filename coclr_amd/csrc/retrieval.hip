@@ -9,6 +9,8 @@
 //   * video-level scores of the test modes (eval/main_classifier.py:488,533,637,673): clips of one video are
 //     rows of a fixed-size batch; per video, out += weight * sum over its rows of softmax(row) (or of the row
 //     itself, for features) -- a segmented accumulate, because a batch cuts across video boundaries
+//   * two-stream test fusion (eval/merge_2stream_prob.py:80-98): the float64 mean of two probability rows and
+//     the first maximum of either row and of the mean, one wave per video
 #include "common.h"
 #include "../../include/coclr_hip.h"
 #include <math.h>
@@ -117,6 +119,56 @@ retrieval_hits_kernel(const float* __restrict__ sim, const int64_t* __restrict__
       while (next_k < nk && ks[next_k] == t + 1) { hits[(long)b * nk + next_k] = found ? 1.f : 0.f; ++next_k; }
     }
     __syncthreads();
+  }
+}
+
+// ---- two-stream score fusion ----------------------------------------------------------------------------
+// (value descending, column ascending): the order of retrieval_hits_kernel, on doubles.  A slot that has seen
+// no column carries FUSE_NONE and loses to any column.
+#define FUSE_NONE 0x7fffffff
+__device__ __forceinline__ void fuse_take(double& best, int& bi, double v, int c) {
+  if (c != FUSE_NONE && (bi == FUSE_NONE || v > best || (v == best && c < bi))) { best = v; bi = c; }
+}
+
+// One wave per video, four videos per workgroup; lanes stride over the C columns.  fused[v][c] = (p1 + p2) * 0.5
+// in double (what numpy forms from the two fp32 rows, merge_2stream_prob.py:95), and the first maximum of p1, p2
+// and the mean (np.argmax, :96-98) as argmax[v][0..2]; hits[v][i] = argmax[v][i] == label[v].
+__global__ void __launch_bounds__(256)
+fuse_scores_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+                   const int64_t* __restrict__ label, double* __restrict__ fused,
+                   int32_t* __restrict__ argmax, float* __restrict__ hits, int V, int C) {
+  const int lane = threadIdx.x & 63;
+  const long v = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (v >= V) return;                           // whole waves leave: the shuffles below see 64 lanes
+  const float* a = p1 + v * C;
+  const float* b = p2 + v * C;
+  double* o = fused + v * C;
+  double best[3] = {0.0, 0.0, 0.0};
+  int bi[3] = {FUSE_NONE, FUSE_NONE, FUSE_NONE};
+  for (int c = lane; c < C; c += 64) {
+    const double x = (double)a[c], y = (double)b[c];
+    const double f = (x + y) * 0.5;
+    o[c] = f;
+    fuse_take(best[0], bi[0], x, c);
+    fuse_take(best[1], bi[1], y, c);
+    fuse_take(best[2], bi[2], f, c);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double ob = __shfl_xor(best[j], off);
+      const int oi = __shfl_xor(bi[j], off);
+      fuse_take(best[j], bi[j], ob, oi);
+    }
+  }
+  if (lane == 0) {                              // lane 0 owns column 0: bi is a column of the row
+    const int64_t want = label[v];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      argmax[v * 3 + j] = bi[j];
+      hits[v * 3 + j] = (int64_t)bi[j] == want ? 1.f : 0.f;
+    }
   }
 }
 
@@ -264,6 +316,17 @@ extern "C" int coclr_retrieval_hits(const float* sim, const int64_t* train_label
   COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), 150 * 1024, attr_done));
   hipLaunchKernelGGL(kern, dim3(B), dim3(256), use_lds ? lds_row : 0, stream, sim, train_label,
                      test_label, ks, nk, kmax, hits, topidx, N, use_lds);
+  COCLR_LAUNCH_CHECK();
+  return 0;
+}
+
+// (p1 + p2) / 2 and the three arg-maxima of eval/merge_2stream_prob.py:80-98
+extern "C" int coclr_fuse_scores(const float* p1, const float* p2, const int64_t* label, double* fused,
+                                 int32_t* argmax, float* hits, int V, int C, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (V <= 0 || C <= 0 || !p1 || !p2 || !label || !fused || !argmax || !hits) return COCLR_EINVAL;
+  hipLaunchKernelGGL(fuse_scores_kernel, dim3(cdiv(V, 4)), dim3(256), 0, stream, p1, p2, label, fused,
+                     argmax, hits, V, C);
   COCLR_LAUNCH_CHECK();
   return 0;
 }

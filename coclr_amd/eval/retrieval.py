@@ -12,6 +12,19 @@ import torch
 from .. import ops
 
 
+def center_normalize(f):
+    """F.normalize(f - f.mean(0), p=2, dim=1) of an (n, C) fp32 device matrix (ref :690-695)."""
+    f = f.contiguous()
+    n, C_ = f.shape
+    ws = torch.empty(ops.colstats_workspace(n, C_), dtype=torch.float32, device=f.device)
+    c = torch.empty_like(f)
+    ops.center_rows(f, c, ws)                        # f - f.mean(0)          (ref :690-691)
+    out = torch.empty_like(f)
+    inv = torch.empty(n, dtype=torch.float32, device=f.device)
+    ops.l2norm_fwd(c, out, inv)                      # F.normalize(p=2, dim=1) (ref :694-695)
+    return out
+
+
 def nn_retrieval(test_feature, test_label, train_feature, train_label, ks=(1, 5, 10, 20, 50)):
     """Returns (accuracies: fp32 device tensor (len(ks),), sim: (n_test, n_train) fp32,
     topidx: int32 (n_test, max(ks)) nearest training clips in order).  Labels are int64 vectors;
@@ -24,19 +37,7 @@ def nn_retrieval(test_feature, test_label, train_feature, train_label, ks=(1, 5,
     if train_feature.shape[1] != C_ or ks[-1] > ntr:
         raise ValueError("coclr_amd: feature widths differ or k exceeds the training set")
     dev = test_feature.device
-
-    def prep(f):
-        f = f.contiguous()
-        n = f.shape[0]
-        ws = torch.empty(ops.colstats_workspace(n, C_), dtype=torch.float32, device=dev)
-        c = torch.empty_like(f)
-        ops.center_rows(f, c, ws)                        # f - f.mean(0)          (ref :690-691)
-        out = torch.empty_like(f)
-        inv = torch.empty(n, dtype=torch.float32, device=dev)
-        ops.l2norm_fwd(c, out, inv)                      # F.normalize(p=2, dim=1) (ref :694-695)
-        return out
-
-    te, tr = prep(test_feature), prep(train_feature)
+    te, tr = center_normalize(test_feature), center_normalize(train_feature)
     sim = torch.empty(nt, ntr, dtype=torch.float32, device=dev)
     # sim[m][n] = sum_c te[m][c] * tr[n][c]                                     (ref :698)
     ops.gemm(te, C_, 1, tr, 1, C_, sim, ntr, None, nt, ntr, C_)

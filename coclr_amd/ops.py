@@ -1478,6 +1478,21 @@ def retrieval_hits(sim, train_label, test_label, ks, hits, topidx=None):
         "retrieval_hits")
 
 
+def fuse_scores(p1, p2, labels, fused, argmax, hits):
+    """fused (V, C) float64 = (p1 + p2) / 2 in double; argmax int32 (V, 3) = first maximum of p1, p2 and the mean;
+    hits fp32 (V, 3) = argmax == labels (eval/merge_2stream_prob.py:80-98).  Everything dense."""
+    if p1.dim() != 2 or p2.shape != p1.shape or p1.numel() == 0:
+        raise ValueError("coclr_amd: fuse_scores takes two (V, C) probability matrices of one shape")
+    V, C_ = p1.shape
+    if tuple(labels.shape) != (V,) or tuple(fused.shape) != (V, C_) or tuple(argmax.shape) != (V, 3) or \
+            tuple(hits.shape) != (V, 3):
+        raise ValueError("coclr_amd: fuse_scores takes labels (V,), fused (V, C), argmax (V, 3) and hits (V, 3)")
+    if not all(t.is_contiguous() for t in (p1, p2, labels, fused, argmax, hits)):
+        raise ValueError("coclr_amd: fuse_scores takes contiguous tensors")
+    _lib.check(_L().coclr_fuse_scores(_p(p1), _p(p2), _p(labels, torch.int64), _p(fused, torch.float64),
+                                      _p(argmax, torch.int32), _p(hits), V, C_, _stream()), "fuse_scores")
+
+
 SEGMENT_MAX_C = 4096      # widest row the segmented accumulate takes (COCLR_SEG_MAX_C)
 
 

@@ -1077,6 +1077,14 @@ int coclr_retrieval_hits(const float* sim, const int64_t* train_label, const int
                          const int32_t* ks, int nk, float* hits, int32_t* topidx, int B, int N,
                          int kmax, void* stream);
 
+/* Two-stream score fusion (eval/merge_2stream_prob.py:80-98): for every video v of p1[V][C] and p2[V][C]
+ * (dense fp32 rows), fused[v][c] = ((double)p1 + (double)p2) * 0.5 as float64, and argmax[v][0..2] = the
+ * first maximum (value descending, column ascending: np.argmax) of p1[v], of p2[v] and of fused[v];
+ * hits[v][i] = 1.0 if argmax[v][i] == label[v] else 0.0 (fp32, so coclr_colsum gives the three
+ * accuracies).  C has no upper limit.  A NaN leaves the arg-maxima in [0, C) and deterministic, no more. */
+int coclr_fuse_scores(const float* p1, const float* p2, const int64_t* label, double* fused,
+                      int32_t* argmax, float* hits, int V, int C, void* stream);
+
 /* Video-level scores of the test modes (eval/main_classifier.py:488,533): for every segment s = {first row,
  * rows, out row} of logits[R][C],  out[out row][:] += weight[s] * sum over its rows of softmax(row), rows
  * added in ascending order in fp32 (no atomics: results are run-to-run identical).  `segs` (S x 3 int32) and
