@@ -68,32 +68,7 @@ __global__ void bn_eval_affine_kernel(const float* __restrict__ gamma, const flo
 // z = act(y*scale[c] + shift[c] (+ res)),  act = ReLU or identity.
 // y is contiguous [N][C][S]; z/res may live inside wider tensors (channel
 // slices of a concat buffer) -> explicit sample strides.
-typedef float nt_f32x4 __attribute__((ext_vector_type(4)));
-
-inline long bn_nt_bytes() {
-  const char* e = getenv("COCLR_BN_NT_MB");
-  const long mb = e ? atol(e) : 0;
-  return mb < 0 ? -1 : (mb << 20);
-}
-
-// 16-byte load / store, optionally NON-TEMPORAL: the streaming passes over tensors far larger than the 256 MB
-// infinity cache would otherwise evict what the MFMA-bound kernels of the other streams keep re-reading there
-__device__ __forceinline__ float4 ld4(const float* p, int i, bool nt) {
-  if (nt) {
-    const nt_f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const nt_f32x4*>(p) + i);
-    return make_float4(t.x, t.y, t.z, t.w);
-  }
-  return reinterpret_cast<const float4*>(p)[i];
-}
-__device__ __forceinline__ void st4(float* p, int i, const float4& w, bool nt) {
-  if (nt) {
-    nt_f32x4 t; t.x = w.x; t.y = w.y; t.z = w.z; t.w = w.w;
-    __builtin_nontemporal_store(t, reinterpret_cast<nt_f32x4*>(p) + i);
-  } else {
-    reinterpret_cast<float4*>(p)[i] = w;
-  }
-}
-
+// Streaming passes over big tensors use the non-temporal 16-byte accesses of common.h (ld4 / st4, nt_f32x4).
 template <bool VEC, bool NT = false>
 __global__ void __launch_bounds__(256)
 bn_act_apply_kernel(const float* __restrict__ y, const float* __restrict__ scale,
@@ -715,8 +690,8 @@ inline int reduce_groups(int N, int S) {
   return g < 1 ? 1 : g;
 }
 
-// Route of one BatchNorm pass.  The launchers below switch on this struct and coclr_bn_plan reports it without
-// launching, so there is one copy of the rules.
+// Route of one BatchNorm pass.  bn_fwd_route / bn_bwd_route work it out from the shape, the strides and which
+// operands there are; the launchers below and coclr_bn_plan both call them, so there is one copy of the rules.
 struct BnRoute {
   int one_wg;        // one workgroup per channel, one launch (small layers)
   int vec;           // 16-byte accesses
@@ -729,59 +704,212 @@ inline bool bn_vec(long S, long a, long b, long c = 0, long d = 0, long e = 0) {
   return S % 4 == 0 && a % 4 == 0 && b % 4 == 0 && c % 4 == 0 && d % 4 == 0 && e % 4 == 0;
 }
 
-// small_ok: the caller has a one-workgroup form for this pass (no residual / z / dres, not from partials)
+// small_ok: the pass has a one-workgroup form for these operands
 inline BnRoute bn_route(int N, int C, long S, bool vec, bool small_ok, bool reduce) {
   BnRoute r;
   r.one_wg = small_ok && (long)N * S <= kSmallChannel;
   r.vec = vec;
   r.nt = 0; r.groups = 0; r.gx = r.gy = 0;
   if (r.one_wg) return r;
-  static const long nt_bytes = bn_nt_bytes();
-  r.nt = vec && nt_bytes >= 0 && (long)N * C * S * 4 >= nt_bytes;
+  static const long nt_from = nt_bytes();
+  r.nt = vec && nt_from >= 0 && (long)N * C * S * 4 >= nt_from;
   if (reduce) r.groups = reduce_groups(N, (int)S);
   const dim3 grid = plane_grid(N, C, (int)S);
   r.gx = (int)grid.x; r.gy = (int)grid.y;
   return r;
 }
 
+// Forward: statistics + apply (coclr_bn_finalize_apply).
+inline BnRoute bn_fwd_route(int N, int C, long S, long y_nstride, long z_nstride) {
+  return bn_route(N, C, S, bn_vec(S, y_nstride, z_nstride), true, false);
+}
+
+// The apply pass alone (coclr_bn_act_apply), optionally with a residual: no one-workgroup form.
+inline BnRoute bn_apply_route(int N, int C, long S, long y_nstride, long z_nstride, bool has_res, long res_nstride) {
+  return bn_route(N, C, S, bn_vec(S, y_nstride, z_nstride, has_res ? res_nstride : 0), false, false);
+}
+
+// Backward.  The one-workgroup form exists without z / dres only; from_partials: the sums come from the data
+// gradient, so there is no reduce pass, no one-workgroup form, and the apply pass streams with temporal accesses.
+inline BnRoute bn_bwd_route(int N, int C, long S, long dz_nstride, long y_nstride, long dy_nstride, bool has_z,
+                            long z_nstride, bool has_dres, long dres_nstride, bool from_partials) {
+  const bool vec = bn_vec(S, dz_nstride, y_nstride, dy_nstride, has_z ? z_nstride : 0, has_dres ? dres_nstride : 0);
+  BnRoute r = bn_route(N, C, S, vec, !has_z && !has_dres && !from_partials, !from_partials);
+  if (from_partials) r.nt = 0;
+  return r;
+}
+
+// Reduce pass + coefficients (coclr_bn_act_backward_coeffs): no dy, no one-workgroup form.
+inline BnRoute bn_coeffs_route(int N, int C, long S, long dz_nstride, long y_nstride) {
+  return bn_route(N, C, S, bn_vec(S, dz_nstride, y_nstride), false, true);
+}
+
+// Launch the instantiation of a kernel template a route picked -- form 0: scalar, 1: 16-byte accesses, 2: 16-byte
+// non-temporal (the streaming apply pass only) -- with ONE argument list.
+template <auto Scalar, auto Vec, auto VecNt = Vec, typename... Args>
+int launch_form(int form, dim3 grid, hipStream_t stream, const Args&... args) {
+  if (form == 2) hipLaunchKernelGGL(VecNt, grid, dim3(256), 0, stream, args...);
+  else if (form == 1) hipLaunchKernelGGL(Vec, grid, dim3(256), 0, stream, args...);
+  else hipLaunchKernelGGL(Scalar, grid, dim3(256), 0, stream, args...);
+  COCLR_LAUNCH_CHECK();
+  return 0;
+}
+
+// Non-temporal loads / stores in the streaming BatchNorm passes: they move tensors of up to 2 GB through a chip
+// whose other streams run MFMA-bound kernels that live on what they keep re-reading from L2 / the 256 MB
+// infinity cache (weights, stencil windows, split-K partials).  Measured inside the step, same box, alternating
+// x4 (profiles/r06_bn_nontemporal_ab.txt): +1.3 % with every such pass non-temporal, +0.9 % with only the
+// tensors above 200 MB.  COCLR_BN_NT_MB=<MB> sets the size from which a pass is non-temporal, -1 switches it off.
+int launch_apply(const BnRoute& rt, const float* y, const float* scale, const float* shift, const float* residual,
+                 float* z, int N, int C, long S, long y_nstride, long z_nstride, long res_nstride, int relu,
+                 hipStream_t stream) {
+  return launch_form<bn_act_apply_kernel<false>, bn_act_apply_kernel<true>, bn_act_apply_kernel<true, true>>(
+      rt.vec + rt.nt, dim3(rt.gx, rt.gy), stream, y, scale, shift, residual, z, N, C, (int)S, y_nstride, z_nstride,
+      res_nstride, relu);
+}
+
+// The operands of coclr_bn_act_backward that a coclr_bn_bwd_call does not carry
+struct BnBwdExtra { const float* z; float* dres; long z_nstride, dres_nstride; int dres_accumulate; };
+
+// the `relu` the two-pass backward kernels read: bit 0 ReLU mask, bit 1 non-temporal passes
+inline int relu_nt(const coclr_bn_bwd_call& c, const BnRoute& rt) { return (c.relu ? 1 : 0) | (rt.nt ? 2 : 0); }
+
+// backward pass 1: per (channel, sample group) partial sums of g and g*xhat
+int launch_bwd_reduce(const coclr_bn_bwd_call& c, const BnBwdExtra& x, const BnRoute& rt, hipStream_t stream) {
+  return launch_form<bn_act_bwd_reduce_kernel<false>, bn_act_bwd_reduce_kernel<true>>(
+      rt.vec, dim3(c.C, rt.groups), stream, c.dz, c.y, x.z, c.scale, c.shift, c.mean, c.invstd, c.sums_ws, c.N, c.C,
+      (int)c.S, c.dz_nstride, c.y_nstride, x.z_nstride, relu_nt(c, rt));
+}
+
+// backward pass 2: fold the `groups` partials per channel, coefficients, dy (+ dres), dgamma / dbeta
+int launch_bwd_apply(const coclr_bn_bwd_call& c, const BnBwdExtra& x, const BnRoute& rt, int groups,
+                     hipStream_t stream) {
+  const double count = (double)c.N * (double)c.S;
+  return launch_form<bn_act_bwd_apply_kernel<false>, bn_act_bwd_apply_kernel<true>>(
+      rt.vec, dim3(rt.gx, rt.gy), stream, c.dz, c.y, x.z, c.scale, c.shift, c.mean, c.invstd, c.sums_ws, groups,
+      count, c.training, c.dgamma, c.dbeta, c.dy, x.dres, c.N, c.C, (int)c.S, c.dz_nstride, c.y_nstride,
+      c.dy_nstride, x.z_nstride, x.dres_nstride, relu_nt(c, rt), x.dres_accumulate);
+}
+
+// ---- one unit from its call struct: the body behind the single-unit entry points and the multi ones ------------
+inline bool bn_unit_ok(const coclr_bn_fwd_call& c) {
+  return c.C > 0 && c.ntiles > 0 && c.N > 0 && c.S > 0 && c.y && c.z;
+}
+inline bool bn_unit_ok(const coclr_bn_bwd_call& c) { return c.N > 0 && c.C > 0 && c.S > 0 && c.dz && c.y && c.dy; }
+
+inline BnRoute bn_unit_route(const coclr_bn_fwd_call& c) {
+  return bn_fwd_route(c.N, c.C, (long)c.S, (long)c.y_nstride, (long)c.z_nstride);
+}
+inline BnRoute bn_unit_route(const coclr_bn_bwd_call& c, const BnBwdExtra& x = BnBwdExtra{}) {
+  return bn_bwd_route(c.N, c.C, (long)c.S, (long)c.dz_nstride, (long)c.y_nstride, (long)c.dy_nstride, x.z != nullptr,
+                      x.z_nstride, x.dres != nullptr, x.dres_nstride, c.part[0] != nullptr);
+}
+
+int bn_run_unit(const coclr_bn_fwd_call& c, hipStream_t stream) {
+  const BnRoute rt = bn_unit_route(c);
+  if (rt.one_wg)
+    return launch_form<bn_fwd_fused_kernel<false>, bn_fwd_fused_kernel<true>>(
+        rt.vec, dim3(c.C), stream, c.sum, c.sumsq, c.ntiles, c.count, c.gamma, c.beta, c.running_mean,
+        c.running_var, c.num_batches_tracked, c.momentum, c.eps, c.mean, c.invstd, c.scale, c.shift, c.y, c.z, c.N,
+        (int)c.S, c.y_nstride, c.z_nstride, c.relu);
+  // large layers: statistics in one launch, the streaming apply pass in another
+  if (const int rc = coclr_bn_finalize(c.sum, c.sumsq, c.C, c.ntiles, c.count, c.gamma, c.beta, c.running_mean,
+                                       c.running_var, c.num_batches_tracked, c.momentum, c.eps, c.mean, c.invstd,
+                                       c.scale, c.shift, stream))
+    return rc;
+  return launch_apply(rt, c.y, c.scale, c.shift, nullptr, c.z, c.N, c.C, (long)c.S, (long)c.y_nstride,
+                      (long)c.z_nstride, 0, c.relu, stream);
+}
+
+int bn_run_unit(const coclr_bn_bwd_call& c, hipStream_t stream, const BnBwdExtra& x = BnBwdExtra{}) {
+  const bool from_partials = c.part[0] != nullptr;
+  if (from_partials) {
+    // the sums the producing data gradient(s) already formed: fold them instead of the reduce pass
+    if (!c.sums_ws || c.part_ntiles[0] <= 0 || (c.part[1] && c.part_ntiles[1] <= 0)) return COCLR_EINVAL;
+    hipLaunchKernelGGL(bn_bwd_fold_kernel, dim3(c.C), dim3(256), 0, stream, c.part[0], c.part_ntiles[0],
+                       c.part[1], c.part[1] ? c.part_ntiles[1] : 0, c.C, c.sums_ws);
+    COCLR_LAUNCH_CHECK();
+  }
+  const BnRoute rt = bn_unit_route(c, x);
+  if (rt.one_wg)    // small layers: one workgroup per channel, one launch (the workspace is not used)
+    return launch_form<bn_bwd_fused_kernel<false>, bn_bwd_fused_kernel<true>>(
+        rt.vec, dim3(c.C), stream, c.dz, c.y, c.scale, c.shift, c.mean, c.invstd, c.training, c.dgamma, c.dbeta,
+        c.dy, c.N, (int)c.S, c.dz_nstride, c.y_nstride, c.dy_nstride, c.relu);
+  if (!from_partials)
+    if (const int rc = launch_bwd_reduce(c, x, rt, stream)) return rc;
+  return launch_bwd_apply(c, x, rt, from_partials ? 1 : rt.groups, stream);
+}
+
+BnFwdUnit bn_unit(const coclr_bn_fwd_call& c) {
+  BnFwdUnit u;
+  u.sum = c.sum; u.sumsq = c.sumsq; u.gamma = c.gamma; u.beta = c.beta;
+  u.running_mean = c.running_mean; u.running_var = c.running_var; u.nbt = c.num_batches_tracked;
+  u.mean = c.mean; u.invstd = c.invstd; u.scale = c.scale; u.shift = c.shift;
+  u.y = c.y; u.z = c.z; u.count = c.count;
+  u.y_nstride = (long)c.y_nstride; u.z_nstride = (long)c.z_nstride;
+  u.C = c.C; u.ntiles = c.ntiles; u.N = c.N; u.S = (int)c.S; u.relu = c.relu;
+  u.momentum = c.momentum; u.eps = c.eps;
+  return u;
+}
+
+BnBwdUnit bn_unit(const coclr_bn_bwd_call& c) {
+  BnBwdUnit u;
+  u.dz = c.dz; u.y = c.y; u.scale = c.scale; u.shift = c.shift; u.mean = c.mean; u.invstd = c.invstd;
+  u.dgamma = c.dgamma; u.dbeta = c.dbeta; u.dy = c.dy;
+  u.dz_nstride = (long)c.dz_nstride; u.y_nstride = (long)c.y_nstride; u.dy_nstride = (long)c.dy_nstride;
+  u.C = c.C; u.N = c.N; u.S = (int)c.S; u.relu = c.relu; u.training = c.training;
+  return u;
+}
+
 // How the multi launchers cut a call into launches: the run that starts at unit i is up to four consecutive units
-// that each take the one-workgroup route (bn_route), share a vector width and (backward) carry no partial sums;
+// that each take the one-workgroup route (which a unit with partial sums never does) and share a vector width;
 // COCLR_PAIR=0 keeps every unit alone.  Returns the run's length (0: unit i itself does not fuse; a run of 0 or 1
-// goes through the single-unit entry point), -1 for an invalid unit among those looked at.  coclr_bn_multi_plan
-// reports the same cut.
+// goes through bn_run_unit), -1 for an invalid unit among those looked at.  coclr_bn_multi_plan reports the same
+// cut.
 inline bool bn_multi_fuse() {
   const char* env = getenv("COCLR_PAIR");
   return !(env && env[0] == '0');
 }
 
-inline int bn_fwd_run(const coclr_bn_fwd_call* calls, int n, int i, bool* vec0) {
+template <typename Call>
+int bn_run(const Call* calls, int n, int i, bool* vec0) {
   const bool fuse = bn_multi_fuse();
   int len = 0;
   for (int j = i; j < n && len < 4; ++j) {
-    const coclr_bn_fwd_call& c = calls[j];
-    if (c.C <= 0 || c.ntiles <= 0 || c.N <= 0 || c.S <= 0 || !c.y || !c.z) return -1;
-    const bool vec = bn_vec((long)c.S, (long)c.y_nstride, (long)c.z_nstride);
-    if (!bn_route(c.N, c.C, (long)c.S, vec, true, false).one_wg || !fuse) break;
-    if (len == 0) *vec0 = vec;
-    else if (vec != *vec0) break;
+    if (!bn_unit_ok(calls[j])) return -1;
+    const BnRoute rt = bn_unit_route(calls[j]);
+    if (!rt.one_wg || !fuse) break;
+    if (len == 0) *vec0 = rt.vec;
+    else if ((bool)rt.vec != *vec0) break;
     ++len;
   }
   return len;
 }
 
-inline int bn_bwd_run(const coclr_bn_bwd_call* calls, int n, int i, bool* vec0) {
-  const bool fuse = bn_multi_fuse();
-  int len = 0;
-  for (int j = i; j < n && len < 4; ++j) {
-    const coclr_bn_bwd_call& c = calls[j];
-    if (c.N <= 0 || c.C <= 0 || c.S <= 0 || !c.dz || !c.y || !c.dy) return -1;
-    const bool vec = bn_vec((long)c.S, (long)c.dz_nstride, (long)c.y_nstride, (long)c.dy_nstride);
-    if (!bn_route(c.N, c.C, (long)c.S, vec, true, true).one_wg || !fuse || c.part[0]) break;
-    if (len == 0) *vec0 = vec;
-    else if (vec != *vec0) break;
-    ++len;
+// the body of the two multi entry points; Table: BnFwdTable / BnBwdTable, Scalar / Vec: its multi kernel
+template <typename Table, auto Scalar, auto Vec, typename Call>
+int bn_run_multi(const Call* calls, int n, hipStream_t stream) {
+  if (!calls || n < 1) return COCLR_EINVAL;
+  for (int i = 0; i < n;) {
+    bool vec0 = false;
+    const int len = bn_run(calls, n, i, &vec0);
+    if (len < 0) return COCLR_EINVAL;
+    if (len < 2) {
+      if (const int rc = bn_run_unit(calls[i], stream)) return rc;
+      ++i;
+      continue;
+    }
+    Table t;
+    t.n = len;
+    long blocks = 0;
+    for (int q = 0; q < len; ++q) {
+      t.u[q] = bn_unit(calls[i + q]);
+      blocks += calls[i + q].C;
+    }
+    if (const int rc = launch_form<Scalar, Vec>(vec0, dim3((unsigned)blocks), stream, t)) return rc;
+    i += len;
   }
-  return len;
+  return 0;
 }
 
 }  // namespace
@@ -805,75 +933,17 @@ extern "C" int coclr_bn_finalize_apply(const float* sum, const float* sumsq, int
                                        int64_t* num_batches_tracked, float momentum, float eps,
                                        float* mean, float* invstd, float* scale, float* shift,
                                        const float* y, float* z, int N, int64_t S, int64_t y_nstride,
-                                       int64_t z_nstride, int relu, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (C <= 0 || ntiles <= 0 || N <= 0 || S <= 0 || !y || !z) return COCLR_EINVAL;
-  const BnRoute rt = bn_route(N, C, (long)S, bn_vec((long)S, (long)y_nstride, (long)z_nstride), true, false);
-  if (!rt.one_wg) {
-    // large layers: statistics in one launch, the streaming apply pass in another
-    int rc = coclr_bn_finalize(sum, sumsq, C, ntiles, count, gamma, beta, running_mean, running_var,
-                               num_batches_tracked, momentum, eps, mean, invstd, scale, shift, stream_);
-    if (rc) return rc;
-    return coclr_bn_act_apply(y, scale, shift, nullptr, z, N, C, S, y_nstride, z_nstride, 0, relu,
-                              stream_);
-  }
-  if (rt.vec)
-    hipLaunchKernelGGL(bn_fwd_fused_kernel<true>, dim3(C), dim3(256), 0, stream, sum, sumsq, ntiles,
-                       count, gamma, beta, running_mean, running_var, num_batches_tracked, momentum,
-                       eps, mean, invstd, scale, shift, y, z, N, (int)S, (long)y_nstride,
-                       (long)z_nstride, relu);
-  else
-    hipLaunchKernelGGL(bn_fwd_fused_kernel<false>, dim3(C), dim3(256), 0, stream, sum, sumsq, ntiles,
-                       count, gamma, beta, running_mean, running_var, num_batches_tracked, momentum,
-                       eps, mean, invstd, scale, shift, y, z, N, (int)S, (long)y_nstride,
-                       (long)z_nstride, relu);
-  COCLR_LAUNCH_CHECK();
-  return 0;
+                                       int64_t z_nstride, int relu, void* stream) {
+  const coclr_bn_fwd_call c = {sum, sumsq, gamma, beta, running_mean, running_var, num_batches_tracked,
+                               mean, invstd, scale, shift, y, z, count, S, y_nstride, z_nstride,
+                               C, ntiles, N, relu, momentum, eps};
+  if (!bn_unit_ok(c)) return COCLR_EINVAL;
+  return bn_run_unit(c, (hipStream_t)stream);
 }
 
-extern "C" int coclr_bn_finalize_apply_multi(const coclr_bn_fwd_call* calls, int n, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (!calls || n < 1) return COCLR_EINVAL;
-  int i = 0;
-  while (i < n) {
-    // a run of up to four small units (one workgroup per channel) with the same vector width
-    bool vec0 = false;
-    const int len = bn_fwd_run(calls, n, i, &vec0);
-    if (len < 0) return COCLR_EINVAL;
-    BnFwdTable t;
-    t.n = 0;
-    long blocks = 0;
-    const int j = i + len;
-    for (int q = i; q < j && len >= 2; ++q) {
-      const coclr_bn_fwd_call& c = calls[q];
-      BnFwdUnit& u = t.u[t.n++];
-      u.sum = c.sum; u.sumsq = c.sumsq; u.gamma = c.gamma; u.beta = c.beta;
-      u.running_mean = c.running_mean; u.running_var = c.running_var; u.nbt = c.num_batches_tracked;
-      u.mean = c.mean; u.invstd = c.invstd; u.scale = c.scale; u.shift = c.shift;
-      u.y = c.y; u.z = c.z; u.count = c.count;
-      u.y_nstride = (long)c.y_nstride; u.z_nstride = (long)c.z_nstride;
-      u.C = c.C; u.ntiles = c.ntiles; u.N = c.N; u.S = (int)c.S; u.relu = c.relu;
-      u.momentum = c.momentum; u.eps = c.eps;
-      blocks += c.C;
-    }
-    if (t.n >= 2) {
-      if (vec0)
-        hipLaunchKernelGGL(bn_fwd_fused_multi_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, t);
-      else
-        hipLaunchKernelGGL(bn_fwd_fused_multi_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, t);
-      COCLR_LAUNCH_CHECK();
-      i = j;
-      continue;
-    }
-    const coclr_bn_fwd_call& c = calls[i];
-    int rc = coclr_bn_finalize_apply(c.sum, c.sumsq, c.C, c.ntiles, c.count, c.gamma, c.beta,
-                                     c.running_mean, c.running_var, c.num_batches_tracked, c.momentum,
-                                     c.eps, c.mean, c.invstd, c.scale, c.shift, c.y, c.z, c.N, c.S,
-                                     c.y_nstride, c.z_nstride, c.relu, stream_);
-    if (rc) return rc;
-    ++i;
-  }
-  return 0;
+extern "C" int coclr_bn_finalize_apply_multi(const coclr_bn_fwd_call* calls, int n, void* stream) {
+  return bn_run_multi<BnFwdTable, bn_fwd_fused_multi_kernel<false>, bn_fwd_fused_multi_kernel<true>>(
+      calls, n, (hipStream_t)stream);
 }
 
 extern "C" int coclr_bn_eval_affine(const float* gamma, const float* beta, const float* running_mean,
@@ -891,29 +961,10 @@ extern "C" int coclr_bn_act_apply(const float* y, const float* scale, const floa
                                   int64_t y_nstride, int64_t z_nstride, int64_t res_nstride,
                                   int relu, void* stream) {
   if (N <= 0 || C <= 0 || S <= 0) return COCLR_EINVAL;
-  const BnRoute rt = bn_route(N, C, (long)S, bn_vec((long)S, (long)y_nstride, (long)z_nstride,
-                                                     residual ? (long)res_nstride : 0), false, false);
-  const bool vec = rt.vec;
-  const dim3 grid(rt.gx, rt.gy);
-  // Non-temporal loads / stores in the streaming BatchNorm passes: they move tensors of up to 2 GB through a chip
-  // whose other streams run MFMA-bound kernels that live on what they keep re-reading from L2 / the 256 MB
-  // infinity cache (weights, stencil windows, split-K partials).  Measured inside the step, same box, alternating
-  // x4 (profiles/r06_bn_nontemporal_ab.txt): +1.3 % with every such pass non-temporal, +0.9 % with only the
-  // tensors above 200 MB.  COCLR_BN_NT_MB=<MB> sets the size from which a pass is non-temporal, -1 switches it off.
-  if (rt.nt)
-    hipLaunchKernelGGL((bn_act_apply_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, y, scale,
-                       shift, residual, z, N, C, (int)S, (long)y_nstride, (long)z_nstride,
-                       (long)res_nstride, relu);
-  else if (vec)
-    hipLaunchKernelGGL(bn_act_apply_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, y, scale,
-                       shift, residual, z, N, C, (int)S, (long)y_nstride, (long)z_nstride,
-                       (long)res_nstride, relu);
-  else
-    hipLaunchKernelGGL(bn_act_apply_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, y, scale,
-                       shift, residual, z, N, C, (int)S, (long)y_nstride, (long)z_nstride,
-                       (long)res_nstride, relu);
-  COCLR_LAUNCH_CHECK();
-  return 0;
+  const BnRoute rt = bn_apply_route(N, C, (long)S, (long)y_nstride, (long)z_nstride, residual != nullptr,
+                                    (long)res_nstride);
+  return launch_apply(rt, y, scale, shift, residual, z, N, C, (long)S, (long)y_nstride, (long)z_nstride,
+                      (long)res_nstride, relu, (hipStream_t)stream);
 }
 
 extern "C" int coclr_bn_backward_workspace(int N, int C, int64_t* doubles) {
@@ -928,56 +979,12 @@ extern "C" int coclr_bn_act_backward(const float* dz, const float* y, const floa
                                      float* dgamma, float* dbeta, int N, int C, int64_t S,
                                      int64_t dz_nstride, int64_t y_nstride, int64_t dy_nstride,
                                      int64_t z_nstride, int64_t dres_nstride, int relu,
-                                     int training, int dres_accumulate, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+                                     int training, int dres_accumulate, void* stream) {
   if (N <= 0 || C <= 0 || S <= 0) return COCLR_EINVAL;
-  const BnRoute rt = bn_route(N, C, (long)S,
-                              bn_vec((long)S, (long)dz_nstride, (long)y_nstride, (long)dy_nstride,
-                                     z ? (long)z_nstride : 0, dres ? (long)dres_nstride : 0),
-                              !z && !dres, true);
-  const bool vec = rt.vec;
-  if (rt.one_wg) {
-    // small layers: one workgroup per channel, one launch (the workspace is not used)
-    if (vec)
-      hipLaunchKernelGGL(bn_bwd_fused_kernel<true>, dim3(C), dim3(256), 0, stream, dz, y, scale, shift,
-                         mean, invstd, training, dgamma, dbeta, dy, N, (int)S, (long)dz_nstride,
-                         (long)y_nstride, (long)dy_nstride, relu);
-    else
-      hipLaunchKernelGGL(bn_bwd_fused_kernel<false>, dim3(C), dim3(256), 0, stream, dz, y, scale,
-                         shift, mean, invstd, training, dgamma, dbeta, dy, N, (int)S,
-                         (long)dz_nstride, (long)y_nstride, (long)dy_nstride, relu);
-    COCLR_LAUNCH_CHECK();
-    return 0;
-  }
-  relu = relu ? 1 : 0;
-  if (rt.nt) relu |= 2;                                  // bit 1: non-temporal passes (see coclr_bn_act_apply)
-  // pass 1: per (channel, sample group) partial sums of g and g*xhat
-  const int groups = rt.groups;
-  dim3 rgrid(C, groups);
-  if (vec)
-    hipLaunchKernelGGL(bn_act_bwd_reduce_kernel<true>, rgrid, dim3(256), 0, stream, dz, y, z, scale,
-                       shift, mean, invstd, sums_ws, N, C, (int)S, (long)dz_nstride,
-                       (long)y_nstride, (long)z_nstride, relu);
-  else
-    hipLaunchKernelGGL(bn_act_bwd_reduce_kernel<false>, rgrid, dim3(256), 0, stream, dz, y, z,
-                       scale, shift, mean, invstd, sums_ws, N, C, (int)S, (long)dz_nstride,
-                       (long)y_nstride, (long)z_nstride, relu);
-  COCLR_LAUNCH_CHECK();
-  // pass 2: fold the partials, coefficients, dy (+ dres), dgamma / dbeta
-  const double count = (double)N * (double)S;
-  const dim3 grid(rt.gx, rt.gy);
-  if (vec)
-    hipLaunchKernelGGL(bn_act_bwd_apply_kernel<true>, grid, dim3(256), 0, stream, dz, y, z, scale,
-                       shift, mean, invstd, sums_ws, groups, count, training, dgamma, dbeta, dy, dres,
-                       N, C, (int)S, (long)dz_nstride, (long)y_nstride, (long)dy_nstride,
-                       (long)z_nstride, (long)dres_nstride, relu, dres_accumulate);
-  else
-    hipLaunchKernelGGL(bn_act_bwd_apply_kernel<false>, grid, dim3(256), 0, stream, dz, y, z, scale,
-                       shift, mean, invstd, sums_ws, groups, count, training, dgamma, dbeta, dy, dres,
-                       N, C, (int)S, (long)dz_nstride, (long)y_nstride, (long)dy_nstride,
-                       (long)z_nstride, (long)dres_nstride, relu, dres_accumulate);
-  COCLR_LAUNCH_CHECK();
-  return 0;
+  const coclr_bn_bwd_call c = {dz, y, scale, shift, mean, invstd, sums_ws, dy, dgamma, dbeta,
+                               S, dz_nstride, y_nstride, dy_nstride, N, C, relu, training, {nullptr, nullptr}, {0, 0}};
+  const BnBwdExtra x = {z, dres, (long)z_nstride, (long)dres_nstride, dres_accumulate};
+  return bn_run_unit(c, (hipStream_t)stream, x);
 }
 
 extern "C" int coclr_bn_act_backward_coeffs(const float* dz, const float* y, const float* scale,
@@ -987,102 +994,19 @@ extern "C" int coclr_bn_act_backward_coeffs(const float* dz, const float* y, con
                                             int relu, int training, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (N <= 0 || C <= 0 || S <= 0 || !coef || !sums_ws) return COCLR_EINVAL;
-  const BnRoute rt = bn_route(N, C, (long)S, bn_vec((long)S, (long)dz_nstride, (long)y_nstride), false, true);
-  const bool vec = rt.vec;
-  relu = relu ? 1 : 0;
-  if (rt.nt) relu |= 2;
-  const int groups = rt.groups;
-  dim3 rgrid(C, groups);
-  const float* noz = nullptr;
-  if (vec)
-    hipLaunchKernelGGL(bn_act_bwd_reduce_kernel<true>, rgrid, dim3(256), 0, stream, dz, y, noz, scale,
-                       shift, mean, invstd, sums_ws, N, C, (int)S, (long)dz_nstride, (long)y_nstride, 0L,
-                       relu);
-  else
-    hipLaunchKernelGGL(bn_act_bwd_reduce_kernel<false>, rgrid, dim3(256), 0, stream, dz, y, noz, scale,
-                       shift, mean, invstd, sums_ws, N, C, (int)S, (long)dz_nstride, (long)y_nstride, 0L,
-                       relu);
-  COCLR_LAUNCH_CHECK();
+  const coclr_bn_bwd_call c = {dz, y, scale, shift, mean, invstd, sums_ws, nullptr, dgamma, dbeta,
+                               S, dz_nstride, y_nstride, 0, N, C, relu, training, {nullptr, nullptr}, {0, 0}};
+  const BnRoute rt = bn_coeffs_route(N, C, (long)S, (long)dz_nstride, (long)y_nstride);
+  if (const int rc = launch_bwd_reduce(c, BnBwdExtra{}, rt, stream)) return rc;
   hipLaunchKernelGGL(bn_bwd_coeffs_kernel, dim3(C), dim3(64), 0, stream, scale, shift, mean, invstd, sums_ws,
-                     groups, (double)N * (double)S, training, C, coef, dgamma, dbeta);
+                     rt.groups, (double)N * (double)S, training, C, coef, dgamma, dbeta);
   COCLR_LAUNCH_CHECK();
   return 0;
 }
 
-namespace {
-// BatchNorm(+ReLU) backward of a unit whose sums the producing data gradient already formed: fold + apply
-int bn_backward_from_partials(const coclr_bn_bwd_call& c, hipStream_t stream) {
-  if (!c.sums_ws || c.part_ntiles[0] <= 0 || (c.part[1] && c.part_ntiles[1] <= 0)) return COCLR_EINVAL;
-  hipLaunchKernelGGL(bn_bwd_fold_kernel, dim3(c.C), dim3(256), 0, stream, c.part[0], c.part_ntiles[0],
-                     c.part[1], c.part[1] ? c.part_ntiles[1] : 0, c.C, c.sums_ws);
-  COCLR_LAUNCH_CHECK();
-  const BnRoute rt = bn_route(c.N, c.C, (long)c.S,
-                              bn_vec((long)c.S, (long)c.dz_nstride, (long)c.y_nstride, (long)c.dy_nstride),
-                              false, false);
-  const bool vec = rt.vec;
-  const double count = (double)c.N * (double)c.S;
-  const dim3 grid(rt.gx, rt.gy);
-  const float* nof = nullptr;
-  float* nod = nullptr;
-  if (vec)
-    hipLaunchKernelGGL(bn_act_bwd_apply_kernel<true>, grid, dim3(256), 0, stream, c.dz, c.y, nof, c.scale,
-                       c.shift, c.mean, c.invstd, c.sums_ws, 1, count, c.training, c.dgamma, c.dbeta, c.dy, nod,
-                       c.N, c.C, (int)c.S, (long)c.dz_nstride, (long)c.y_nstride, (long)c.dy_nstride, 0L, 0L,
-                       c.relu, 0);
-  else
-    hipLaunchKernelGGL(bn_act_bwd_apply_kernel<false>, grid, dim3(256), 0, stream, c.dz, c.y, nof, c.scale,
-                       c.shift, c.mean, c.invstd, c.sums_ws, 1, count, c.training, c.dgamma, c.dbeta, c.dy, nod,
-                       c.N, c.C, (int)c.S, (long)c.dz_nstride, (long)c.y_nstride, (long)c.dy_nstride, 0L, 0L,
-                       c.relu, 0);
-  COCLR_LAUNCH_CHECK();
-  return 0;
-}
-}  // namespace
-
-extern "C" int coclr_bn_act_backward_multi(const coclr_bn_bwd_call* calls, int n, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (!calls || n < 1) return COCLR_EINVAL;
-  int i = 0;
-  while (i < n) {
-    bool vec0 = false;
-    const int len = bn_bwd_run(calls, n, i, &vec0);
-    if (len < 0) return COCLR_EINVAL;
-    BnBwdTable t;
-    t.n = 0;
-    long blocks = 0;
-    const int j = i + len;
-    for (int q = i; q < j && len >= 2; ++q) {
-      const coclr_bn_bwd_call& c = calls[q];
-      BnBwdUnit& u = t.u[t.n++];
-      u.dz = c.dz; u.y = c.y; u.scale = c.scale; u.shift = c.shift; u.mean = c.mean; u.invstd = c.invstd;
-      u.dgamma = c.dgamma; u.dbeta = c.dbeta; u.dy = c.dy;
-      u.dz_nstride = (long)c.dz_nstride; u.y_nstride = (long)c.y_nstride; u.dy_nstride = (long)c.dy_nstride;
-      u.C = c.C; u.N = c.N; u.S = (int)c.S; u.relu = c.relu; u.training = c.training;
-      blocks += c.C;
-    }
-    if (t.n >= 2) {
-      if (vec0)
-        hipLaunchKernelGGL(bn_bwd_fused_multi_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, t);
-      else
-        hipLaunchKernelGGL(bn_bwd_fused_multi_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, t);
-      COCLR_LAUNCH_CHECK();
-      i = j;
-      continue;
-    }
-    const coclr_bn_bwd_call& c = calls[i];
-    if (c.part[0]) {
-      int rc = bn_backward_from_partials(c, stream);
-      if (rc) return rc;
-      ++i;
-      continue;
-    }
-    int rc = coclr_bn_act_backward(c.dz, c.y, nullptr, c.scale, c.shift, c.mean, c.invstd, c.sums_ws, c.dy,
-                                   nullptr, c.dgamma, c.dbeta, c.N, c.C, c.S, c.dz_nstride, c.y_nstride,
-                                   c.dy_nstride, 0, 0, c.relu, c.training, 0, stream_);
-    if (rc) return rc;
-    ++i;
-  }
-  return 0;
+extern "C" int coclr_bn_act_backward_multi(const coclr_bn_bwd_call* calls, int n, void* stream) {
+  return bn_run_multi<BnBwdTable, bn_bwd_fused_multi_kernel<false>, bn_bwd_fused_multi_kernel<true>>(
+      calls, n, (hipStream_t)stream);
 }
 
 // The routes the entry points above take for one unit, nothing launched (usable without a device).  Forward:
@@ -1097,17 +1021,10 @@ extern "C" int coclr_bn_plan(int N, int C, int64_t S, int64_t y_nstride, int64_t
   if (N <= 0 || C <= 0 || S <= 0 || !out) return COCLR_EINVAL;
   if (has_partials && (has_z || has_dres)) return COCLR_EINVAL;
   for (int i = 0; i < 16; ++i) out[i] = 0;
-  const BnRoute f = bn_route(N, C, (long)S, bn_vec((long)S, (long)y_nstride, (long)z_nstride), true, false);
+  const BnRoute f = bn_fwd_route(N, C, (long)S, (long)y_nstride, (long)z_nstride);
   out[0] = f.one_wg; out[1] = f.vec; out[2] = f.nt; out[3] = f.gx; out[4] = f.gy;
-  BnRoute b;
-  if (has_partials)
-    b = bn_route(N, C, (long)S, bn_vec((long)S, (long)dz_nstride, (long)y_nstride, (long)dy_nstride), false, false);
-  else
-    b = bn_route(N, C, (long)S,
-                 bn_vec((long)S, (long)dz_nstride, (long)y_nstride, (long)dy_nstride, has_z ? (long)z_nstride : 0,
-                        has_dres ? (long)dres_nstride : 0),
-                 !has_z && !has_dres, true);
-  if (has_partials) b.nt = 0;      // the apply pass behind partial sums streams with temporal accesses
+  const BnRoute b = bn_bwd_route(N, C, (long)S, (long)dz_nstride, (long)y_nstride, (long)dy_nstride, has_z != 0,
+                                 (long)z_nstride, has_dres != 0, (long)dres_nstride, has_partials != 0);
   out[5] = b.one_wg; out[6] = b.vec; out[7] = b.nt; out[8] = b.groups; out[9] = b.gx; out[10] = b.gy;
   out[11] = has_partials ? 1 : 0;
   return 0;
@@ -1115,7 +1032,7 @@ extern "C" int coclr_bn_plan(int N, int C, int64_t S, int64_t y_nstride, int64_t
 
 // The launches coclr_bn_finalize_apply_multi (fwd given) or coclr_bn_act_backward_multi (bwd given) would make for
 // these n units, nothing launched: run_len[k] = units of launch k (>= 2: one fused multi launch; 1: the unit goes
-// through the single-unit entry point, or its from-partials form), terminated by 0; run_len holds n + 1 entries.
+// through bn_run_unit, from partials included), terminated by 0; run_len holds n + 1 entries.
 // Only the units' shapes, strides, part[0] and the non-nullness of their operands are read.
 extern "C" int coclr_bn_multi_plan(const coclr_bn_fwd_call* fwd, const coclr_bn_bwd_call* bwd, int n,
                                    int32_t* run_len) {
@@ -1123,7 +1040,7 @@ extern "C" int coclr_bn_multi_plan(const coclr_bn_fwd_call* fwd, const coclr_bn_
   int k = 0;
   for (int i = 0; i < n;) {
     bool vec0 = false;
-    int len = fwd ? bn_fwd_run(fwd, n, i, &vec0) : bn_bwd_run(bwd, n, i, &vec0);
+    int len = fwd ? bn_run(fwd, n, i, &vec0) : bn_run(bwd, n, i, &vec0);
     if (len < 0) return COCLR_EINVAL;
     if (len < 2) len = 1;
     run_len[k++] = len;

@@ -27,33 +27,8 @@ struct PoolGeom {
   int in_relu;
   int C0;                      // channels before T was folded into the plane count
   int tfold;
-  int nt;                      // stream the big operand with non-temporal loads / stores (see pool_nt_bytes)
+  int nt;                      // stream the big operand with non-temporal loads / stores (ld4 / st4, nt_bytes)
 };
-
-typedef float pool_f32x4 __attribute__((ext_vector_type(4)));
-
-// Non-temporal 16-byte access: the pooling passes over the stem's 1 GB tensors would otherwise evict what the
-// MFMA-bound kernels of the other streams keep re-reading from L2 / the infinity cache (csrc/bn.hip, same switch)
-__device__ __forceinline__ float4 pool_ld4(const float* p, int i, bool nt) {
-  if (nt) {
-    const pool_f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const pool_f32x4*>(p) + i);
-    return make_float4(t.x, t.y, t.z, t.w);
-  }
-  return reinterpret_cast<const float4*>(p)[i];
-}
-__device__ __forceinline__ void pool_st4(float* p, int i, const float4& w, bool nt) {
-  if (nt) {
-    pool_f32x4 t; t.x = w.x; t.y = w.y; t.z = w.z; t.w = w.w;
-    __builtin_nontemporal_store(t, reinterpret_cast<pool_f32x4*>(p) + i);
-  } else {
-    reinterpret_cast<float4*>(p)[i] = w;
-  }
-}
-inline long pool_nt_bytes() {
-  const char* e = getenv("COCLR_BN_NT_MB");
-  const long mb = e ? atol(e) : 0;
-  return mb < 0 ? -1 : (mb << 20);
-}
 
 __device__ __forceinline__ float pool_in(const PoolGeom& g, float v, int c) {
   if (g.in_scale) {
@@ -214,7 +189,7 @@ maxpool3d_tiled_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
         if (live[k]) {
           int i, n, c;
           pool_slot(slots, e, i, n, c);
-          r[k] = pool_ld4(x + (long)n * g.x_nstride + (long)c * Si, i, g.nt != 0);
+          r[k] = ld4(x + (long)n * g.x_nstride + (long)c * Si, i, g.nt != 0);
           if (g.in_scale) {
             const int ch = pool_quot(c, dfold);   // channel of the un-folded tensor (g.tfold == tfold)
             sc[k] = g.in_scale[ch];
@@ -243,7 +218,7 @@ maxpool3d_tiled_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
       const int ch = pool_quot(c, dfold);  // channel of the un-folded tensor (g.tfold == tfold)
       if (vec) {
         for (int i = threadIdx.x; i < S4; i += 256) {
-          float4 v = pool_ld4(xp, i, g.nt != 0);
+          float4 v = ld4(xp, i, g.nt != 0);
           v.x = pool_in(g, v.x, ch); v.y = pool_in(g, v.y, ch);
           v.z = pool_in(g, v.z, ch); v.w = pool_in(g, v.w, ch);
           reinterpret_cast<float4*>(tp)[i] = v;
@@ -768,7 +743,7 @@ bn_pool_bwd_apply_kernel(const float* __restrict__ pdy, const int* __restrict__ 
     if (vec) {      // PooledBnPlan::vec: Si % 4 == 0 and y_nstride, dy_nstride % 4 == 0
       for (int i = threadIdx.x; i < (Si >> 2); i += 256) {
         float4 gq = reinterpret_cast<const float4*>(tp)[i];
-        const float4 v = pool_ld4(yp, i, g.nt != 0);
+        const float4 v = ld4(yp, i, g.nt != 0);
         if (relu) {
           gq.x = fmaf(v.x, sc, sf) > 0.f ? gq.x : 0.f; gq.y = fmaf(v.y, sc, sf) > 0.f ? gq.y : 0.f;
           gq.z = fmaf(v.z, sc, sf) > 0.f ? gq.z : 0.f; gq.w = fmaf(v.w, sc, sf) > 0.f ? gq.w : 0.f;
@@ -776,7 +751,7 @@ bn_pool_bwd_apply_kernel(const float* __restrict__ pdy, const int* __restrict__ 
         float4 o;
         o.x = fmaf(A, gq.x, fmaf(B, v.x, D)); o.y = fmaf(A, gq.y, fmaf(B, v.y, D));
         o.z = fmaf(A, gq.z, fmaf(B, v.z, D)); o.w = fmaf(A, gq.w, fmaf(B, v.w, D));
-        pool_st4(dyp, i, o, g.nt != 0);
+        st4(dyp, i, o, g.nt != 0);
       }
     } else {
       for (int i = threadIdx.x; i < Si; i += 256) {
@@ -851,35 +826,14 @@ maxpool333_bwd_kernel(const float* __restrict__ dy, const int* __restrict__ idx,
 
 constexpr int kTileFloats = 16384;   // 64 KiB of LDS per workgroup
 
-// planes per workgroup so that the tile is <= kTileFloats and there are enough workgroups
-inline int pick_group(int planes, int Si) {
-  if (Si > kTileFloats) return 0;
-  // ~16 KiB tiles: 8 workgroups per CU so the load, scan and store phases of different
-  // workgroups overlap (64 KiB tiles left 2 per CU and ran at 1.2 TB/s)
-  int G = 4096 / Si;
+// Volumes per workgroup of an LDS-tiled kernel: what `budget` floats of LDS hold (at least one, at most `cap` when
+// given), halved while that leaves fewer than `min_wgs` workgroups.
+inline int volumes_per_wg(int planes, int Si, int budget, int min_wgs, int cap = 0) {
+  int G = budget / Si;
   if (G < 1) G = 1;
-  while (G > 1 && (planes + G - 1) / G < 2048) G >>= 1;
+  if (cap > 0 && G > cap) G = cap;
+  while (G > 1 && (planes + G - 1) / G < min_wgs) G >>= 1;
   return G;
-}
-
-template <int KT, int KH, int KW, int ST, int SH, int SW, int WPT>
-int launch_tiled_fwd(const PoolGeom& g, const float* x, float* y, int* idx, int G, int planes,
-                     int tfold, int vec, hipStream_t stream) {
-  const size_t lds = (size_t)G * g.Ti * g.Hi * g.Wi * sizeof(float);
-  const int blocks = (planes + G - 1) / G;
-  if (idx) {
-    auto k = maxpool3d_tiled_fwd_kernel<KT, KH, KW, ST, SH, SW, WPT, true>;
-    static std::atomic<uint64_t> done{0};
-    COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(k), kTileFloats * 4, done));
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds, stream, x, y, idx, g, G, planes, tfold, vec);
-  } else {
-    auto k = maxpool3d_tiled_fwd_kernel<KT, KH, KW, ST, SH, SW, WPT, false>;
-    static std::atomic<uint64_t> done{0};
-    COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(k), kTileFloats * 4, done));
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds, stream, x, y, idx, g, G, planes, tfold, vec);
-  }
-  COCLR_LAUNCH_CHECK();
-  return 0;
 }
 
 // Collapse T into the plane count when the stencil does not touch it.
@@ -930,38 +884,39 @@ inline PoolGeom to_geom(const coclr_pool_desc* d) {
   g.pt = d->pt; g.ph = d->ph; g.pw = d->pw;
   g.x_nstride = d->x_nstride; g.y_nstride = d->y_nstride;
   g.in_scale = g.in_shift = nullptr; g.in_relu = 0; g.C0 = d->C; g.tfold = 1;
-  {
-    static const long nt_bytes = pool_nt_bytes();
-    g.nt = (nt_bytes >= 0 && (long)d->N * d->C * d->Ti * d->Hi * d->Wi * 4 >= nt_bytes) ? 1 : 0;
-  }
+  static const long nt_from = nt_bytes();
+  g.nt = (nt_from >= 0 && (long)d->N * d->C * d->Ti * d->Hi * d->Wi * 4 >= nt_from) ? 1 : 0;
   return g;
 }
 
-}  // namespace
-
-static inline int ilog2_exact(int v) {
+inline int ilog2_exact(int v) {
   int l = 0;
   while ((1 << l) < v) ++l;
   return (1 << l) == v ? l : -1;
 }
-
-// ---------------------------------------------------------------------------
-// Dispatch plans.  Every launcher below switches on one of these structs and coclr_pool_plan reports the same
-// structs without launching, so the tests' view of "which kernel does this shape reach" is the launchers' own.
-// ---------------------------------------------------------------------------
-namespace {
-
-enum { kFwdGeneric = 0, kFwdSep333 = 1, kFwdTiled = 2 };
-enum { kBwdGeneric = 0, kBwdGather333 = 1, kBwdClasses = 2 };
 
 inline bool is_333_s1_p1(const PoolGeom& g) {
   return g.kt == 3 && g.kh == 3 && g.kw == 3 && g.st == 1 && g.sh == 1 && g.sw == 1 && g.pt == 1 && g.ph == 1 &&
          g.pw == 1;
 }
 
+// ---------------------------------------------------------------------------
+// Dispatch.  Each kernel family has ONE table; a row is one instantiation, built by a *_row<...>() template from a
+// single spelling of the template arguments: the numbers coclr_pool_plan reports about it and the function that
+// launches it.  A plan_* function picks the row and the launch numbers from the geometry; the entry points are
+// validate, plan, row->launch, and coclr_pool_plan reports the same plan structs and rows without launching, so the
+// tests' view of "which kernel does this shape reach" is the launchers' own.
+// ---------------------------------------------------------------------------
+enum { kFwdGeneric = 0, kFwdSep333 = 1, kFwdTiled = 2 };
+enum { kBwdGeneric = 0, kBwdGather333 = 1, kBwdClasses = 2 };
+
+// ---- forward ----------------------------------------------------------------------------------------------------
+struct PoolFwdPlan;
+typedef int (*PoolFwdFn)(const PoolFwdPlan&, const float* x, float* y, int32_t* idx, hipStream_t);
+
 struct PoolFwdPlan {
   int family;        // kFwd*
-  int tmpl;          // separable: TT (0: run-time frame count); tiled: row of the template table; generic: 0
+  int tmpl;          // separable: TT (0: run-time frame count); tiled: row of kTiledFwd; generic: 0
   int G;             // volumes per workgroup (PG of the separable kernel)
   int gx, gy;        // grid
   int tfold;
@@ -970,13 +925,56 @@ struct PoolFwdPlan {
   int lW, lHW;       // separable kernel only
   int planes;        // (folded) volumes
   PoolGeom g;        // the geometry the kernel gets (T folded into the planes for the tiled family)
+  const PoolFwdFn* launch;   // the row's launch functions {without, with indices}; nullptr: the generic kernel
 };
 
+template <auto Kern>
+int launch_tiled_fwd(const PoolFwdPlan& p, const float* x, float* y, int32_t* idx, hipStream_t st) {
+  return launch_dyn_lds<Kern, 256, kTileFloats * 4>(dim3(p.gx), (size_t)p.lds, st, x, y, idx, p.g, p.G, p.planes,
+                                                    p.tfold, p.vec);
+}
+
+template <auto Kern>
+int launch_sep333(const PoolFwdPlan& p, const float* x, float* y, int32_t* idx, hipStream_t st) {
+  hipLaunchKernelGGL(Kern, dim3(p.gx), dim3(256), (size_t)p.lds, st, x, y, idx, p.g, p.planes, p.lW, p.lHW, p.vec);
+  COCLR_LAUNCH_CHECK();
+  return 0;
+}
+
+struct TiledFwdRow { int kt, kh, kw, st, sh, sw, wpt; PoolFwdFn launch[2]; };
+template <int KT, int KH, int KW, int ST, int SH, int SW, int WPT>
+constexpr TiledFwdRow tiled_fwd_row() {
+  return {KT, KH, KW, ST, SH, SW, WPT,
+          {&launch_tiled_fwd<maxpool3d_tiled_fwd_kernel<KT, KH, KW, ST, SH, SW, WPT, false>>,
+           &launch_tiled_fwd<maxpool3d_tiled_fwd_kernel<KT, KH, KW, ST, SH, SW, WPT, true>>}};
+}
+// the row number is out[1] of coclr_pool_plan (ops.PoolGeom._FWD_TILED mirrors the rows in this order)
+constexpr TiledFwdRow kTiledFwd[] = {
+    tiled_fwd_row<1, 3, 3, 1, 2, 2, 2>(), tiled_fwd_row<3, 3, 3, 1, 1, 1, 4>(),
+    tiled_fwd_row<3, 3, 3, 2, 2, 2, 2>(), tiled_fwd_row<2, 2, 2, 2, 2, 2, 2>()};
+constexpr int kTiledFwdRows = sizeof(kTiledFwd) / sizeof(kTiledFwd[0]);
+constexpr bool tiled_fwd_is(const TiledFwdRow& r, int kt, int kh, int kw, int st, int sh, int sw, int wpt = 0) {
+  return r.kt == kt && r.kh == kh && r.kw == kw && r.st == st && r.sh == sh && r.sw == sw && (!wpt || r.wpt == wpt);
+}
+static_assert(kTiledFwdRows == 4 && tiled_fwd_is(kTiledFwd[0], 1, 3, 3, 1, 2, 2, 2) &&
+              tiled_fwd_is(kTiledFwd[1], 3, 3, 3, 1, 1, 1, 4) && tiled_fwd_is(kTiledFwd[2], 3, 3, 3, 2, 2, 2, 2) &&
+              tiled_fwd_is(kTiledFwd[3], 2, 2, 2, 2, 2, 2, 2), "row order is the out[1] contract of coclr_pool_plan");
+
+// separable 3x3x3: TT frames at compile time; the last row (TT = 0) takes the frame count at run time
+struct Sep333Row { int tt; PoolFwdFn launch[2]; };
+template <int TT>
+constexpr Sep333Row sep333_row() {
+  return {TT, {&launch_sep333<maxpool333_kernel<false, TT>>, &launch_sep333<maxpool333_kernel<true, TT>>}};
+}
+constexpr Sep333Row kSep333[] = {sep333_row<16>(), sep333_row<8>(), sep333_row<4>(), sep333_row<0>()};
+constexpr int kSep333Rows = sizeof(kSep333) / sizeof(kSep333[0]);
+static_assert(kSep333[kSep333Rows - 1].tt == 0, "the run-time frame count form is the fallback");
 inline PoolFwdPlan plan_pool_fwd(const PoolGeom& g, bool with_idx) {
   PoolFwdPlan p;
   p.family = kFwdGeneric; p.tmpl = 0; p.G = 1; p.tfold = 1; p.vec = 0; p.lds = 0; p.lW = p.lHW = 0;
   p.planes = g.N * g.C;
   p.g = g;
+  p.launch = nullptr;
   if (is_333_s1_p1(g)) {
     // inception pool branch: separable scan, thread = (volume, h, w)
     const int lW = ilog2_exact(g.Wi), lHW = ilog2_exact(g.Hi * g.Wi);
@@ -984,8 +982,10 @@ inline PoolFwdPlan plan_pool_fwd(const PoolGeom& g, bool with_idx) {
       const int PG = 256 >> lHW, S = g.Ti << lHW;
       const size_t lds = (size_t)PG * S * 4 * (with_idx ? 3 : 2);
       if (lds <= 64 * 1024) {
-        p.family = kFwdSep333;
-        p.tmpl = (g.Ti == 16 || g.Ti == 8 || g.Ti == 4) ? g.Ti : 0;
+        const Sep333Row* row = &kSep333[kSep333Rows - 1];
+        for (const Sep333Row& r : kSep333)
+          if (r.tt == g.Ti) { row = &r; break; }
+        p.family = kFwdSep333; p.tmpl = row->tt; p.launch = row->launch;
         p.G = PG; p.gx = cdiv(p.planes, PG); p.gy = 1;
         p.vec = (g.x_nstride & 3) == 0;
         p.lds = (int)lds; p.lW = lW; p.lHW = lHW;
@@ -998,18 +998,14 @@ inline PoolFwdPlan plan_pool_fwd(const PoolGeom& g, bool with_idx) {
     const PoolGeom f = fold_time(g);
     const int Si = f.Ti * f.Hi * f.Wi;
     const int planes = f.N * f.C;
-    const int G = pick_group(planes, Si);
-    if (G > 0) {
-      const int k[3] = {f.kt, f.kh, f.kw}, s[3] = {f.st, f.sh, f.sw};
-#define POOL_IS(a, b, c, e, ff, gg) (k[0] == a && k[1] == b && k[2] == c && s[0] == e && s[1] == ff && s[2] == gg)
-      int row = -1;
-      if (POOL_IS(1, 3, 3, 1, 2, 2)) row = 0;
-      else if (POOL_IS(3, 3, 3, 1, 1, 1)) row = 1;
-      else if (POOL_IS(3, 3, 3, 2, 2, 2)) row = 2;
-      else if (POOL_IS(2, 2, 2, 2, 2, 2)) row = 3;
-#undef POOL_IS
-      if (row >= 0) {
-        p.family = kFwdTiled; p.tmpl = row; p.G = G; p.gx = (planes + G - 1) / G; p.gy = 1;
+    if (Si <= kTileFloats) {
+      for (int row = 0; row < kTiledFwdRows; ++row) {
+        if (!tiled_fwd_is(kTiledFwd[row], f.kt, f.kh, f.kw, f.st, f.sh, f.sw)) continue;
+        // ~16 KiB tiles: 8 workgroups per CU so the load, scan and store phases of different
+        // workgroups overlap (64 KiB tiles left 2 per CU and ran at 1.2 TB/s)
+        const int G = volumes_per_wg(planes, Si, 4096, 2048);
+        p.family = kFwdTiled; p.tmpl = row; p.launch = kTiledFwd[row].launch;
+        p.G = G; p.gx = (planes + G - 1) / G; p.gy = 1;
         p.tfold = f.Ti == g.Ti ? 1 : g.Ti;
         p.vec = (Si & 3) == 0 && (f.x_nstride & 3) == 0;
         p.lds = (int)((size_t)G * Si * sizeof(float));
@@ -1021,6 +1017,165 @@ inline PoolFwdPlan plan_pool_fwd(const PoolGeom& g, bool with_idx) {
   }
   const dim3 grid = pool_grid(g.N * g.C, g.To * g.Ho * g.Wo);
   p.gx = (int)grid.x; p.gy = (int)grid.y;
+  return p;
+}
+
+// ---- backward ---------------------------------------------------------------------------------------------------
+// colour-class counts of a pool and the outputs a thread holds per class for G volumes per workgroup
+struct ClassShape { int pt, ph, pw, kq; };
+inline ClassShape class_shape(const PoolGeom& g, int G) {
+  ClassShape c;
+  c.pt = (g.kt + g.st - 1) / g.st; c.ph = (g.kh + g.sh - 1) / g.sh; c.pw = (g.kw + g.sw - 1) / g.sw;
+  const long m = (long)((g.To + c.pt - 1) / c.pt) * ((g.Ho + c.ph - 1) / c.ph) * ((g.Wo + c.pw - 1) / c.pw);
+  c.kq = (int)((G * m + 255) / 256);
+  static const bool off = getenv("COCLR_POOL_PRELOAD") && atoi(getenv("COCLR_POOL_PRELOAD")) == 0;
+  if (off) c.kq = 1 << 20;            // A/B switch: the generic one-round-trip-per-class form
+  return c;
+}
+
+// A colour-class template: PT, PH, PW, KQ and the function that launches that instantiation.  A pool takes the
+// first row of its table with its class counts and kq <= KQ, else the table's generic <0, 0, 0, 0> row.
+template <typename Fn>
+struct ClassRow { int pt, ph, pw, kq; Fn launch; };
+
+template <typename Fn, int NR>
+const ClassRow<Fn>* pick_class_template(const ClassShape& cs, const ClassRow<Fn> (&rows)[NR],
+                                        const ClassRow<Fn>* generic) {
+  for (const ClassRow<Fn>& r : rows)
+    if (cs.pt == r.pt && cs.ph == r.ph && cs.pw == r.pw && cs.kq <= r.kq) return &r;
+  return generic;
+}
+// first match wins: a later row with the same class counts must have the larger KQ (no duplicate, none unreachable)
+template <typename Fn, int NR>
+constexpr bool class_rows_ordered(const ClassRow<Fn> (&r)[NR]) {
+  for (int i = 0; i < NR; ++i)
+    for (int j = i + 1; j < NR; ++j)
+      if (r[i].pt == r[j].pt && r[i].ph == r[j].ph && r[i].pw == r[j].pw && r[i].kq >= r[j].kq) return false;
+  return true;
+}
+
+struct PoolBwdPlan;
+typedef int (*PoolBwdFn)(const PoolBwdPlan&, const float* dy, const int32_t* idx, float* dx, long dy_nstride,
+                         long dx_nstride, int accumulate, hipStream_t);
+
+struct PoolBwdPlan {
+  int family;        // kBwd*
+  const ClassRow<PoolBwdFn>* row;   // colour classes: the template row (kBwdGenericRow: generic form), else nullptr
+  int G, kq;         // volumes per workgroup; outputs per thread and class for that G (colour classes)
+  int gx, gy;
+  int tfold;
+  int vec;           // 333 gather: 16-byte staging of dy / indices; colour classes: 16-byte stores of dx
+  int lds;
+  int lW, lHW;       // 333 gather only
+  int planes, Si;
+  PoolGeom g;
+};
+
+template <int PT, int PH, int PW, int KQ>
+int launch_tiled_bwd(const PoolBwdPlan& p, const float* dy, const int32_t* idx, float* dx, long dy_nstride,
+                     long dx_nstride, int accumulate, hipStream_t st) {
+  return launch_dyn_lds<maxpool3d_tiled_bwd_kernel<PT, PH, PW, KQ>, 256, kTileFloats * 4>(
+      dim3(p.gx), (size_t)p.lds, st, dy, idx, dx, p.g, dy_nstride, dx_nstride, accumulate, p.G, p.planes, p.tfold,
+      p.vec);
+}
+template <int PT, int PH, int PW, int KQ>
+constexpr ClassRow<PoolBwdFn> bwd_row() { return {PT, PH, PW, KQ, &launch_tiled_bwd<PT, PH, PW, KQ>}; }
+
+constexpr ClassRow<PoolBwdFn> kBwdTemplates[] = {bwd_row<1, 2, 2, 1>(), bwd_row<3, 3, 3, 1>(), bwd_row<2, 2, 2, 1>(),
+                                                 bwd_row<1, 1, 1, 2>()};
+constexpr ClassRow<PoolBwdFn> kBwdGenericRow = bwd_row<0, 0, 0, 0>();
+inline PoolBwdPlan plan_pool_bwd(const PoolGeom& g0, long dy_nstride, long dx_nstride) {
+  PoolBwdPlan p;
+  p.family = kBwdGeneric; p.row = nullptr; p.G = 1; p.kq = 0; p.tfold = 1; p.vec = 0; p.lds = 0; p.lW = p.lHW = 0;
+  p.planes = g0.N * g0.C; p.Si = g0.Ti * g0.Hi * g0.Wi;
+  p.g = g0;
+  if (is_333_s1_p1(g0)) {
+    const int lW = ilog2_exact(g0.Wi), lHW = ilog2_exact(g0.Hi * g0.Wi);
+    const int S = p.Si;
+    // measured (B=32): 4x4x4 volumes 0.027 ms gather vs 0.055 colour classes; 8x8x8 0.084 vs 0.075;
+    // 16x16x16 0.327 vs 0.158 -- the 27-candidate scan is VALU-bound, it only pays on tiny volumes
+    if (lW >= 0 && lHW >= 0 && S <= 128) {
+      const int G = volumes_per_wg(p.planes, S, 2048, 2048);   // ~16 KiB of LDS (dy + indices): 8 workgroups per CU
+      p.family = kBwdGather333; p.G = G; p.gx = (p.planes + G - 1) / G; p.gy = 1;
+      p.vec = (S & 3) == 0 && (dy_nstride & 3) == 0;
+      p.lds = G * S * 8; p.lW = lW; p.lHW = lHW;
+      return p;
+    }
+  }
+  {
+    const PoolGeom g = fold_time(g0);
+    const int Si = g.Ti * g.Hi * g.Wi;
+    const int planes = g.N * g.C;
+    if (Si <= kTileFloats) {
+      // a colour class holds ~1/27 of a volume's outputs: keep enough volumes per workgroup for its
+      // 256 threads (1024 workgroups still fill the chip four deep)
+      const int G = volumes_per_wg(planes, Si, 4096, 1024);
+      const ClassShape cs = class_shape(g, G);
+      p.family = kBwdClasses; p.row = pick_class_template(cs, kBwdTemplates, &kBwdGenericRow);
+      p.G = G; p.kq = cs.kq; p.gx = (planes + G - 1) / G; p.gy = 1;
+      p.tfold = g.Ti == g0.Ti ? 1 : g0.Ti;
+      p.vec = (Si & 3) == 0 && (dx_nstride & 3) == 0;
+      p.lds = (int)((size_t)G * Si * sizeof(float));
+      p.planes = planes; p.Si = Si;
+      p.g = g;
+      return p;
+    }
+  }
+  const dim3 grid = pool_grid(g0.N * g0.C, g0.Ti * g0.Hi * g0.Wi);
+  p.gx = (int)grid.x; p.gy = (int)grid.y;
+  return p;
+}
+
+// ---- BatchNorm backward behind a pool ---------------------------------------------------------------------------
+struct PooledBnPlan;
+struct PooledBnOperands {
+  const float* pool_dy; const int32_t* pool_idx;
+  const float* y; const float* scale; const float* shift; const float* mean; const float* invstd;
+  double* sums;
+  float* dy; float* dgamma; float* dbeta;
+  long pool_dy_nstride, y_nstride, dy_nstride;
+  int relu, training;
+};
+typedef int (*PooledBnFn)(const PooledBnPlan&, const PooledBnOperands&, hipStream_t);
+
+struct PooledBnPlan {
+  int fits;
+  const ClassRow<PooledBnFn>* row;   // the template row (kPooledGenericRow: generic form); nullptr when !fits
+  int G, kq, blocks, tfold, vec, lds, planes, Si;
+  PoolGeom g;
+};
+
+template <int PT, int PH, int PW, int KQ>
+int launch_pooled_bn(const PooledBnPlan& p, const PooledBnOperands& a, hipStream_t st) {
+  const double count = (double)p.g.N * (p.Si * p.tfold);        // elements per channel of the unfolded geometry
+  return launch_dyn_lds<bn_pool_bwd_apply_kernel<PT, PH, PW, KQ>, 256, kTileFloats * 4>(
+      dim3(p.blocks), (size_t)p.lds, st, a.pool_dy, a.pool_idx, a.y, a.scale, a.shift, a.mean, a.invstd, a.sums,
+      p.g.N, count, a.training, a.dgamma, a.dbeta, a.dy, p.g, a.pool_dy_nstride, a.y_nstride, a.dy_nstride, a.relu,
+      p.G, p.planes, p.tfold, p.vec);
+}
+template <int PT, int PH, int PW, int KQ>
+constexpr ClassRow<PooledBnFn> pooled_row() { return {PT, PH, PW, KQ, &launch_pooled_bn<PT, PH, PW, KQ>}; }
+
+constexpr ClassRow<PooledBnFn> kPooledTemplates[] = {pooled_row<1, 2, 2, 1>(), pooled_row<2, 2, 2, 1>()};
+constexpr ClassRow<PooledBnFn> kPooledGenericRow = pooled_row<0, 0, 0, 0>();
+static_assert(class_rows_ordered(kBwdTemplates) && class_rows_ordered(kPooledTemplates), "duplicate / unreachable row");
+
+inline PooledBnPlan plan_pooled_bn(const PoolGeom& g0, long y_nstride, long dy_nstride) {
+  PooledBnPlan p;
+  const PoolGeom g = fold_time(g0);
+  p.g = g;
+  p.tfold = g.Ti == g0.Ti ? 1 : g0.Ti;
+  p.Si = g.Ti * g.Hi * g.Wi;
+  p.planes = g.N * g.C;
+  p.fits = p.Si <= kTileFloats;
+  p.row = nullptr; p.G = 0; p.kq = 0; p.blocks = 0; p.vec = 0; p.lds = 0;
+  if (!p.fits) return p;
+  const int G = volumes_per_wg(p.planes, p.Si, 4096, 1024, 8);   // at most 8: coef[8][4] of the apply kernel
+  const ClassShape cs = class_shape(g, G);
+  p.row = pick_class_template(cs, kPooledTemplates, &kPooledGenericRow);
+  p.G = G; p.kq = cs.kq; p.blocks = (p.planes + G - 1) / G;
+  p.vec = (p.Si & 3) == 0 && ((y_nstride | dy_nstride) & 3) == 0;
+  p.lds = (int)((size_t)G * p.Si * sizeof(float));
   return p;
 }
 
@@ -1036,163 +1191,11 @@ extern "C" int coclr_maxpool3d_fwd(const coclr_pool_desc* d, const float* x, flo
   g.in_scale = in_scale; g.in_shift = in_shift; g.in_relu = in_relu;
   const PoolFwdPlan p = plan_pool_fwd(g, indices != nullptr);
   hipStream_t st = (hipStream_t)stream;
-  if (p.family == kFwdSep333) {
-    const dim3 grid(p.gx);
-    const size_t lds = (size_t)p.lds;
-    const int planes = p.planes, lW = p.lW, lHW = p.lHW;
-#define POOL333(TT)                                                                                  \
-    if (indices) hipLaunchKernelGGL((maxpool333_kernel<true, TT>), grid, dim3(256), lds, st, x, y, \
-                                    indices, g, planes, lW, lHW, p.vec);                         \
-    else hipLaunchKernelGGL((maxpool333_kernel<false, TT>), grid, dim3(256), lds, st, x, y,       \
-                            indices, g, planes, lW, lHW, p.vec)
-    if (p.tmpl == 16) { POOL333(16); }
-    else if (p.tmpl == 8) { POOL333(8); }
-    else if (p.tmpl == 4) { POOL333(4); }
-    else { POOL333(0); }
-#undef POOL333
-    COCLR_LAUNCH_CHECK();
-    return 0;
-  }
-  if (p.family == kFwdTiled) {
-    switch (p.tmpl) {
-      case 0: return launch_tiled_fwd<1, 3, 3, 1, 2, 2, 2>(p.g, x, y, indices, p.G, p.planes, p.tfold, p.vec, st);
-      case 1: return launch_tiled_fwd<3, 3, 3, 1, 1, 1, 4>(p.g, x, y, indices, p.G, p.planes, p.tfold, p.vec, st);
-      case 2: return launch_tiled_fwd<3, 3, 3, 2, 2, 2, 2>(p.g, x, y, indices, p.G, p.planes, p.tfold, p.vec, st);
-      default: return launch_tiled_fwd<2, 2, 2, 2, 2, 2, 2>(p.g, x, y, indices, p.G, p.planes, p.tfold, p.vec, st);
-    }
-  }
+  if (p.launch) return p.launch[indices != nullptr](p, x, y, indices, st);
   hipLaunchKernelGGL(maxpool3d_fwd_kernel, dim3(p.gx, p.gy), dim3(256), 0, st, x, y, indices, g);
   COCLR_LAUNCH_CHECK();
   return 0;
 }
-
-// colour-class counts of a pool and the outputs a thread holds per class for G volumes per workgroup
-struct ClassShape { int pt, ph, pw, kq; };
-inline ClassShape class_shape(const PoolGeom& g, int G) {
-  ClassShape c;
-  c.pt = (g.kt + g.st - 1) / g.st; c.ph = (g.kh + g.sh - 1) / g.sh; c.pw = (g.kw + g.sw - 1) / g.sw;
-  const long m = (long)((g.To + c.pt - 1) / c.pt) * ((g.Ho + c.ph - 1) / c.ph) * ((g.Wo + c.pw - 1) / c.pw);
-  c.kq = (int)((G * m + 255) / 256);
-  static const bool off = getenv("COCLR_POOL_PRELOAD") && atoi(getenv("COCLR_POOL_PRELOAD")) == 0;
-  if (off) c.kq = 1 << 20;            // A/B switch: the generic one-round-trip-per-class form
-  return c;
-}
-
-template <int PT, int PH, int PW, int KQ>
-int launch_tiled_bwd(const float* dy, const int32_t* indices, float* dx, const PoolGeom& g,
-                     long dy_nstride, long dx_nstride, int accumulate, int G, int planes, int tfold,
-                     int Si, int vec, hipStream_t st) {
-  auto kern = maxpool3d_tiled_bwd_kernel<PT, PH, PW, KQ>;
-  static std::atomic<uint64_t> done{0};
-  COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), kTileFloats * 4, done));
-  hipLaunchKernelGGL(kern, dim3((planes + G - 1) / G), dim3(256), (size_t)G * Si * sizeof(float), st,
-                     dy, indices, dx, g, dy_nstride, dx_nstride, accumulate, G, planes, tfold, vec);
-  COCLR_LAUNCH_CHECK();
-  return 0;
-}
-
-namespace {
-
-// the colour-class templates: PT, PH, PW, KQ; a pool takes the first row with its class counts and kq <= KQ,
-// else the generic form (reported as 0, 0, 0, 0)
-struct ClassTemplate { int pt, ph, pw, kq; };
-constexpr ClassTemplate kBwdTemplates[4] = {{1, 2, 2, 1}, {3, 3, 3, 1}, {2, 2, 2, 1}, {1, 1, 1, 2}};
-constexpr ClassTemplate kPooledTemplates[2] = {{1, 2, 2, 1}, {2, 2, 2, 1}};
-
-inline int pick_class_template(const ClassShape& cs, const ClassTemplate* rows, int n) {
-  for (int i = 0; i < n; ++i)
-    if (cs.pt == rows[i].pt && cs.ph == rows[i].ph && cs.pw == rows[i].pw && cs.kq <= rows[i].kq) return i;
-  return -1;
-}
-
-struct PoolBwdPlan {
-  int family;        // kBwd*
-  int tmpl;          // colour classes: row of kBwdTemplates, -1: generic form
-  int G, kq;         // volumes per workgroup; outputs per thread and class for that G (colour classes)
-  int gx, gy;
-  int tfold;
-  int vec;           // 333 gather: 16-byte staging of dy / indices; colour classes: 16-byte stores of dx
-  int lds;
-  int lW, lHW;       // 333 gather only
-  int planes, Si;
-  PoolGeom g;
-};
-
-inline PoolBwdPlan plan_pool_bwd(const PoolGeom& g0, long dy_nstride, long dx_nstride) {
-  PoolBwdPlan p;
-  p.family = kBwdGeneric; p.tmpl = -1; p.G = 1; p.kq = 0; p.tfold = 1; p.vec = 0; p.lds = 0; p.lW = p.lHW = 0;
-  p.planes = g0.N * g0.C; p.Si = g0.Ti * g0.Hi * g0.Wi;
-  p.g = g0;
-  if (is_333_s1_p1(g0)) {
-    const int lW = ilog2_exact(g0.Wi), lHW = ilog2_exact(g0.Hi * g0.Wi);
-    const int S = g0.Ti * g0.Hi * g0.Wi;
-    // measured (B=32): 4x4x4 volumes 0.027 ms gather vs 0.055 colour classes; 8x8x8 0.084 vs 0.075;
-    // 16x16x16 0.327 vs 0.158 -- the 27-candidate scan is VALU-bound, it only pays on tiny volumes
-    if (lW >= 0 && lHW >= 0 && S <= 128) {
-      const int planes = g0.N * g0.C;
-      int G = 2048 / S;              // ~16 KiB of LDS (dy + indices): 8 workgroups per CU
-      if (G < 1) G = 1;
-      while (G > 1 && (planes + G - 1) / G < 2048) G >>= 1;
-      p.family = kBwdGather333; p.G = G; p.gx = (planes + G - 1) / G; p.gy = 1;
-      p.vec = (S & 3) == 0 && (dy_nstride & 3) == 0;
-      p.lds = G * S * 8; p.lW = lW; p.lHW = lHW;
-      return p;
-    }
-  }
-  {
-    const PoolGeom g = fold_time(g0);
-    const int Si = g.Ti * g.Hi * g.Wi;
-    const int planes = g.N * g.C;
-    if (pick_group(planes, Si) > 0) {
-      // a colour class holds ~1/27 of a volume's outputs: keep enough volumes per workgroup for its
-      // 256 threads (1024 workgroups still fill the chip four deep)
-      int G = 4096 / Si > 0 ? 4096 / Si : 1;
-      while (G > 1 && (planes + G - 1) / G < 1024) G >>= 1;
-      const ClassShape cs = class_shape(g, G);
-      p.family = kBwdClasses; p.tmpl = pick_class_template(cs, kBwdTemplates, 4);
-      p.G = G; p.kq = cs.kq; p.gx = (planes + G - 1) / G; p.gy = 1;
-      p.tfold = g.Ti == g0.Ti ? 1 : g0.Ti;
-      p.vec = (Si & 3) == 0 && (dx_nstride & 3) == 0;
-      p.lds = (int)((size_t)G * Si * sizeof(float));
-      p.planes = planes; p.Si = Si;
-      p.g = g;
-      return p;
-    }
-  }
-  const dim3 grid = pool_grid(g0.N * g0.C, g0.Ti * g0.Hi * g0.Wi);
-  p.gx = (int)grid.x; p.gy = (int)grid.y;
-  return p;
-}
-
-struct PooledBnPlan {
-  int fits;
-  int tmpl;          // row of kPooledTemplates, -1: generic form
-  int G, kq, blocks, tfold, vec, lds, planes, Si;
-  PoolGeom g;
-};
-
-inline PooledBnPlan plan_pooled_bn(const PoolGeom& g0, long y_nstride, long dy_nstride) {
-  PooledBnPlan p;
-  const PoolGeom g = fold_time(g0);
-  p.g = g;
-  p.tfold = g.Ti == g0.Ti ? 1 : g0.Ti;
-  p.Si = g.Ti * g.Hi * g.Wi;
-  p.planes = g.N * g.C;
-  p.fits = p.Si <= kTileFloats;
-  p.tmpl = -1; p.G = 0; p.kq = 0; p.blocks = 0; p.vec = 0; p.lds = 0;
-  if (!p.fits) return p;
-  int G = 4096 / p.Si > 0 ? 4096 / p.Si : 1;
-  if (G > 8) G = 8;                // coef[8][4] of the apply kernel
-  while (G > 1 && (p.planes + G - 1) / G < 1024) G >>= 1;
-  const ClassShape cs = class_shape(g, G);
-  p.tmpl = pick_class_template(cs, kPooledTemplates, 2);
-  p.G = G; p.kq = cs.kq; p.blocks = (p.planes + G - 1) / G;
-  p.vec = (p.Si & 3) == 0 && ((y_nstride | dy_nstride) & 3) == 0;
-  p.lds = (int)((size_t)G * p.Si * sizeof(float));
-  return p;
-}
-
-}  // namespace
 
 extern "C" int coclr_maxpool3d_bwd(const coclr_pool_desc* d, const float* dy, const int32_t* indices,
                                    float* dx, int64_t dy_nstride, int64_t dx_nstride,
@@ -1201,27 +1204,13 @@ extern "C" int coclr_maxpool3d_bwd(const coclr_pool_desc* d, const float* dy, co
   const PoolGeom g0 = to_geom(d);
   const PoolBwdPlan p = plan_pool_bwd(g0, (long)dy_nstride, (long)dx_nstride);
   hipStream_t st = (hipStream_t)stream;
-  if (p.family == kBwdGather333) {
+  if (p.row) return p.row->launch(p, dy, indices, dx, (long)dy_nstride, (long)dx_nstride, accumulate, st);
+  if (p.family == kBwdGather333)
     hipLaunchKernelGGL(maxpool333_bwd_kernel, dim3(p.gx), dim3(256), (size_t)p.lds, st, dy, indices, dx, g0,
                        (long)dy_nstride, (long)dx_nstride, accumulate, p.G, p.planes, p.lW, p.lHW, p.vec);
-    COCLR_LAUNCH_CHECK();
-    return 0;
-  }
-  if (p.family == kBwdClasses) {
-#define POOL_BWD(a, b, c, q)                                                                         \
-    return launch_tiled_bwd<a, b, c, q>(dy, indices, dx, p.g, (long)dy_nstride, (long)dx_nstride,    \
-                                        accumulate, p.G, p.planes, p.tfold, p.Si, p.vec, st)
-    switch (p.tmpl) {           // rows of kBwdTemplates
-      case 0: POOL_BWD(1, 2, 2, 1);
-      case 1: POOL_BWD(3, 3, 3, 1);
-      case 2: POOL_BWD(2, 2, 2, 1);
-      case 3: POOL_BWD(1, 1, 1, 2);
-      default: POOL_BWD(0, 0, 0, 0);
-    }
-#undef POOL_BWD
-  }
-  hipLaunchKernelGGL(maxpool3d_bwd_kernel, dim3(p.gx, p.gy), dim3(256), 0, st, dy, indices, dx, g0,
-                     (long)dy_nstride, (long)dx_nstride, accumulate);
+  else
+    hipLaunchKernelGGL(maxpool3d_bwd_kernel, dim3(p.gx, p.gy), dim3(256), 0, st, dy, indices, dx, g0,
+                       (long)dy_nstride, (long)dx_nstride, accumulate);
   COCLR_LAUNCH_CHECK();
   return 0;
 }
@@ -1243,31 +1232,15 @@ extern "C" int coclr_bn_act_backward_pooled(const coclr_pool_desc* d, const floa
   const PoolGeom g0 = to_geom(d);
   const PooledBnPlan p = plan_pooled_bn(g0, (long)y_nstride, (long)dy_nstride);
   if (!p.fits) return COCLR_EINVAL;                   // see coclr_bn_act_backward_pooled_fits
-  const PoolGeom& g = p.g;
-  const int tfold = p.tfold, Si = p.Si, planes = p.planes, G = p.G;
   hipStream_t st = (hipStream_t)stream;
   const int So0 = g0.To * g0.Ho * g0.Wo, Si0 = g0.Ti * g0.Hi * g0.Wi;
   hipLaunchKernelGGL(bn_pool_bwd_reduce_kernel, dim3(g0.C, g0.N), dim3(256), 0, st, pool_dy, pool_idx,
                      y, scale, shift, mean, invstd, sums, g0.C, So0, Si0, (long)pool_dy_nstride,
                      (long)y_nstride, relu);
   COCLR_LAUNCH_CHECK();
-  const double count = (double)g0.N * Si0;
-#define BN_POOL_BWD(a, b, c, q)                                                                      \
-  do {                                                                                               \
-    auto kern = bn_pool_bwd_apply_kernel<a, b, c, q>;                                                \
-    static std::atomic<uint64_t> done{0};                                                            \
-    COCLR_RETURN_IF(ensure_dyn_lds(reinterpret_cast<const void*>(kern), kTileFloats * 4, done));      \
-    hipLaunchKernelGGL(kern, dim3(p.blocks), dim3(256), (size_t)G * Si * sizeof(float),              \
-                       st, pool_dy, pool_idx, y, scale, shift, mean, invstd, sums, g0.N, count,      \
-                       training, dgamma, dbeta, dy, g, (long)pool_dy_nstride, (long)y_nstride,       \
-                       (long)dy_nstride, relu, G, planes, tfold, p.vec);                             \
-    COCLR_LAUNCH_CHECK();                                                                            \
-    return 0;                                                                                        \
-  } while (0)
-  if (p.tmpl == 0) BN_POOL_BWD(1, 2, 2, 1);           // rows of kPooledTemplates
-  if (p.tmpl == 1) BN_POOL_BWD(2, 2, 2, 1);
-  BN_POOL_BWD(0, 0, 0, 0);
-#undef BN_POOL_BWD
+  const PooledBnOperands a = {pool_dy, pool_idx, y, scale, shift, mean, invstd, sums, dy, dgamma, dbeta,
+                              (long)pool_dy_nstride, (long)y_nstride, (long)dy_nstride, relu, training};
+  return p.row->launch(p, a, st);
 }
 
 // What the three launchers above would do for this descriptor, nothing launched (usable without a device).
@@ -1285,13 +1258,12 @@ extern "C" int coclr_pool_plan(const coclr_pool_desc* d, int with_indices, int64
   out[0] = f.family; out[1] = f.tmpl; out[2] = f.G; out[3] = f.gx; out[4] = f.gy; out[5] = f.tfold;
   out[6] = f.vec; out[7] = f.lds;
   const PoolBwdPlan b = plan_pool_bwd(g, (long)dy_nstride, (long)dx_nstride);
-  const ClassTemplate none = {0, 0, 0, 0};
-  const ClassTemplate bt = b.tmpl >= 0 ? kBwdTemplates[b.tmpl] : none;
-  out[8] = b.family; out[9] = bt.pt; out[10] = bt.ph; out[11] = bt.pw; out[12] = bt.kq; out[13] = b.G;
-  out[14] = b.kq; out[15] = b.gx; out[16] = b.gy; out[17] = b.tfold; out[18] = b.vec; out[19] = b.lds;
+  out[8] = b.family;
+  if (b.row) { out[9] = b.row->pt; out[10] = b.row->ph; out[11] = b.row->pw; out[12] = b.row->kq; }
+  out[13] = b.G; out[14] = b.kq; out[15] = b.gx; out[16] = b.gy; out[17] = b.tfold; out[18] = b.vec; out[19] = b.lds;
   const PooledBnPlan q = plan_pooled_bn(g, (long)d->x_nstride, (long)dx_nstride);
-  const ClassTemplate qt = q.tmpl >= 0 ? kPooledTemplates[q.tmpl] : none;
-  out[20] = q.fits; out[21] = q.G; out[22] = qt.pt; out[23] = qt.ph; out[24] = qt.pw; out[25] = qt.kq;
+  out[20] = q.fits; out[21] = q.G;
+  if (q.row) { out[22] = q.row->pt; out[23] = q.row->ph; out[24] = q.row->pw; out[25] = q.row->kq; }
   out[26] = q.kq; out[27] = q.blocks; out[28] = q.tfold; out[29] = q.vec; out[30] = q.lds;
   out[31] = g.nt;
   return 0;
