@@ -96,6 +96,26 @@ __device__ __forceinline__ float row16_sum(float v) {
   return v;
 }
 
+// the statistics tail of the 2 x 2-wave kernels: the epilogue left four partial (sum, sum of squares) per output
+// row in LDS (red[slot][row][2]); their sum is this tile's slot of [2][Cout][ntiles]
+template <int BM>
+__device__ __forceinline__ void fold_tile_stats(const ConvArgs& a, const float* red, int tid, int cout0, int ntile) {
+  __syncthreads();
+  if (tid < BM) {
+    const int co = cout0 + tid;
+    if (co < a.Cout) {
+      float s = 0.f, ss = 0.f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        s += red[(k * BM + tid) * 2];
+        ss += red[(k * BM + tid) * 2 + 1];
+      }
+      a.stats[(long)co * a.ntiles + ntile] = s;
+      a.stats[((long)a.Cout + co) * a.ntiles + ntile] = ss;
+    }
+  }
+}
+
 // exact floor(e / d) for 0 <= e < 2^20 given inv = 1.0f / d
 __device__ __forceinline__ int fdiv(int e, float inv) { return (int)(((float)e + 0.5f) * inv); }
 
@@ -492,22 +512,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, int bid, cons
   else if (a.accumulate) emit(std::true_type{}, std::false_type{});
   else emit(std::false_type{}, std::false_type{});
 
-  if (want_stats) {
-    __syncthreads();
-    if (tid < BM) {
-      const int co = cout0 + tid;
-      if (co < a.Cout) {
-        float s = 0.f, ss = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          s += red[(k * BM + tid) * 2];
-          ss += red[(k * BM + tid) * 2 + 1];
-        }
-        a.stats[(long)co * a.ntiles + ntile] = s;
-        a.stats[((long)a.Cout + co) * a.ntiles + ntile] = ss;
-      }
-    }
-  }
+  if (want_stats) fold_tile_stats<BM>(a, red, tid, cout0, ntile);
 }
 
 template <int KT, int KH, int KW, int CC, int BM, int BN, int PCH, bool XV4 = false, bool XG = false>
@@ -530,7 +535,29 @@ conv_igemm_pair_kernel(const ConvArgs a0, const ConvArgs a1, const int nb0) {
 }
 
 // ------------------------------------------------------------------------------------
-// Temporal (3,1,1) stride-1 convolutions through Winograd F(2,3) along T.
+// The temporal Winograd family: one kernel body, conv_wino_tf_body, over four FORMS.  Seen from the
+// implicit-GEMM kernel above this is a (TAPS,1,1) stencil with temporal stride STEP over output "positions"
+// (groups of FO output frames): same box / window / LDS-DMA staging / weight tile; what differs is that the B
+// operand of virtual tap i is a combination of window rows (a few VALU ops), that a wave keeps TAPS accumulator
+// sets per 32x32 block, and that the epilogue emits FO frames per position.  A form gives
+//     TAPS           channel contractions (accumulator sets) = window frames read per lane
+//     FO             output frames per position
+//     STEP, ORG      window frames per position and the window origin: frame  position * STEP - ORG
+//     input()        d[TAPS] window frames -> D[TAPS] transformed operands
+//     output()       element i of the m[TAPS] contractions -> v[FO] output frames
+//     LATTICE        the destination is a lattice along T (a.yst, a.yot) and the frame count arrives in a.To_full;
+//                    without it the frame count arrives in a.yst and the frame pitch is 1
+//     PAIR           a two-problem kernel exists (coclr_conv3d_fwd_multi)
+//     POS_SUMS       the statistics take a position's frames added to each other first (s += u0 + u1), both old
+//                    values of an accumulate are loaded before either frame is stored; otherwise frame by frame
+//     BWD_SUMS       the epilogue that forms the backward sums of a BatchNorm unit exists (a.bwd_y, see
+//                    bwd_sums_variant)
+// The arithmetic of the transforms (fmaf nesting, parentheses) and the order in which the epilogue adds frames
+// into the statistics are part of the result: outputs and BatchNorm sums are held bit for bit.  output() reads the
+// accumulators in place for the same reason: staged through a scalar array the epilogue vectorises differently,
+// and which of its multiply-adds get fused changes with it.
+
+// Temporal (3,1,1) stride-1 convolutions through Winograd F(2,3) along T (coclr_conv_desc.algo = 1).
 //
 // A pair of output frames (2p, 2p+1) needs input frames d0..d3 = 2p-1 .. 2p+2 and FOUR channel
 // contractions instead of six:
@@ -540,401 +567,21 @@ conv_igemm_pair_kernel(const ConvArgs a0, const ConvArgs a1, const int nb0) {
 // by pack_weights_kernel as a 4-"tap" operand).  Everything stays fp32; measured against float64
 // the result is as accurate as the direct fp32 convolution (tools/winograd_probe.py: 5e-7).
 //
-// Seen from the implicit-GEMM kernel above this is a (4,1,1) stencil with temporal stride 2
-// over "pair positions": same box / window / LDS-DMA staging / weight tile; what differs is that
-// the B operand of virtual tap i is a difference or sum of two window rows (one VALU op), that a
-// wave keeps four accumulators per 32x32 block, and that the epilogue emits two frames.
-// 1.5x fewer MFMAs for the (3,1,1) layers (27 % of the S3D conv FLOPs), forward and dgrad.
-template <int CC, int BM, int BNP, int PCH, bool XV4>
-__device__ __forceinline__ void conv_wino_t_body(const ConvArgs& a, int bid, const int nblocks) {
-  constexpr int TAPS = 4;
-  constexpr int WM = 2, WN = 2;
-  constexpr int MF = BM / (WM * 32), NF = BNP / (WN * 32);
-  constexpr int RPP = 256 / BM;
-  constexpr int WPIECES = TAPS * CC / RPP;
-  static_assert(CC % RPP == 0 && CC % 4 == 0, "chunk shape");
-  constexpr int W_FLOATS = TAPS * CC * BM;
-
-  extern __shared__ __align__(16) float smem[];
-  const int planeS = a.planeS;
-  const int stage_floats = W_FLOATS + CC * planeS;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int half = lane >> 5, l31 = lane & 31;
-  const int wm = wave >> 1, wn = wave & 1;
-
-  if (a.xcd) {                        // XCD-aware tile ids (see conv_igemm_body)
-    const int per = nblocks >> 3;
-    if (bid < (per << 3)) bid = (bid & 7) * per + (bid >> 3);
+// A (4,1,1) stencil with temporal stride 2 over "pair positions", four accumulator sets per 32x32 block.
+// 1.5x fewer MFMAs for the (3,1,1) layers (27 % of the S3D conv FLOPs), forward and dgrad.  The oldest form:
+// the only one whose statistics add a position's two frames first and the only one with the backward-sums epilogue.
+struct WinoF23 {
+  static constexpr int TAPS = 4, FO = 2, STEP = 2, ORG = 1;
+  static constexpr bool LATTICE = false, PAIR = true, POS_SUMS = true, BWD_SUMS = true;
+  static __device__ __forceinline__ void input(const float (&d)[TAPS], float (&D)[TAPS]) {
+    const float d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3];
+    D[0] = d0 - d2; D[1] = d1 + d2; D[2] = d2 - d1; D[3] = d1 - d3;
   }
-  const int mt = bid % a.mtiles;
-  const int ntile = bid / a.mtiles;
-  int r = ntile;
-  const int bw_ = r % a.nbw; r /= a.nbw;
-  const int bh_ = r % a.nbh; r /= a.nbh;
-  const int bt_ = r % a.nbt; r /= a.nbt;
-  const int n0 = r << a.lTN;
-  const int ow0 = bw_ << a.lTW, oh0 = bh_ << a.lTH, ot0 = bt_ << a.lTT;   // ot0: PAIR index
-  const int cout0 = mt * BM;
-  const int vt0 = ot0 * 2 - 1, vh0 = oh0, vw0 = ow0;                      // window origin
-  const int plane = a.plane;
-
-  const float* xbase = a.x + (long)n0 * a.x_nstride;
-  const __amdgpu_buffer_rsrc_t rx =
-      __builtin_amdgcn_make_buffer_rsrc((void*)xbase, 0, BUF_RANGE, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rw =
-      __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, BUF_RANGE, 0x00020000);
-  float* ybase = a.y + (long)n0 * a.y_nstride;
-  const __amdgpu_buffer_rsrc_t ry =
-      __builtin_amdgcn_make_buffer_rsrc((void*)ybase, 0, BUF_RANGE, 0x00020000);
-
-  unsigned goff[PCH];
-  {
-    const int hw = a.WH * a.WW;
-#pragma unroll
-    for (int j = 0; j < PCH; ++j) {
-      const int e = j * 64 + lane;
-      unsigned off = OOB;
-      if (e < plane) {
-        const int wn_ = fdiv(e, a.inv_plane1);
-        int q = e - wn_ * a.plane1;
-        const int wt = fdiv(q, a.inv_hw); q -= wt * hw;
-        const int wh = fdiv(q, a.inv_ww);
-        const int ww = q - wh * a.WW;
-        const int n = n0 + wn_;
-        const int it = vt0 + wt, ih = vh0 + wh, iw = vw0 + ww;
-        if (n < a.N && it >= 0 && it < a.Ti && ih < a.Hi && iw < a.Wi)
-          off = (unsigned)(((long)wn_ * a.x_nstride + ((long)it * a.Hi + ih) * a.Wi + iw) * 4);
-      }
-      goff[j] = off;
-    }
+  static __device__ __forceinline__ void output(const f32x16 (&m)[TAPS], int i, float (&v)[FO]) {
+    const float m0 = m[0][i], m1 = m[1][i], m2 = m[2][i], m3 = m[3][i];
+    v[0] = (m0 + m1) + m2; v[1] = (m1 - m2) - m3;
   }
-  const unsigned wvoff = (unsigned)((((lane * 4) / BM) * a.CoutP + (lane * 4) % BM) * 4);
-
-  // XV4: the window of a temporal stencil has no halo along the flattened (H,W) axis, so with
-  // everything 16-byte aligned it can be staged by 16-byte DMA.  The LDS image [c][plane] is
-  // then filled in 1 KiB pieces that run across channel boundaries: piece j, lane L holds
-  // floats 256j + 4L .. +3.  Wave w owns pieces w, w+4, ...
-  constexpr int PV = (CC * PCH * 64 / 256 + 3) / 4;      // pieces per wave (upper bound)
-  unsigned xvoff[PV];
-  int xvc[PV];
-  if (XV4) {
-#pragma unroll
-    for (int jj = 0; jj < PV; ++jj) {
-      const int flat = (wave + 4 * jj) * 256 + lane * 4;
-      const int c = flat / plane, e = flat - c * plane;
-      unsigned off = OOB;
-      if (c < CC) {
-        const int wn_ = fdiv(e, a.inv_plane1);
-        const int q = e - wn_ * a.plane1;
-        const int wt = fdiv(q, a.inv_ww);              // WH == 1 here
-        const int ww = q - wt * a.WW;
-        const int n = n0 + wn_, it = vt0 + wt, iw = vw0 + ww;
-        if (n < a.N && it >= 0 && it < a.Ti && iw < a.Wi)
-          off = (unsigned)(((long)wn_ * a.x_nstride + (long)it * a.Wi + iw + (long)c * a.x_cstride) * 4);
-      }
-      xvoff[jj] = off;
-      xvc[jj] = c;
-    }
-  }
-
-  // pair position of this lane: window offset of its frame d0 (d1..d3 follow at +WH*WW each)
-  int lanebase[NF];
-  const int fstride = a.WH * a.WW;
-#pragma unroll
-  for (int nf = 0; nf < NF; ++nf) {
-    const int p = wn * (BNP / WN) + nf * 32 + l31;
-    const int tw = p & ((1 << a.lTW) - 1);
-    const int th = (p >> a.lTW) & ((1 << a.lTH) - 1);
-    const int tt = (p >> (a.lTW + a.lTH)) & ((1 << a.lTT) - 1);
-    const int tn = p >> (a.lTW + a.lTH + a.lTT);
-    lanebase[nf] = W_FLOATS + tn * a.plane1 + ((tt * 2) * a.WH + th) * a.WW + tw + half * planeS;
-  }
-  const int abase = half * BM + wm * (BM / WM) + l31;
-
-  f32x16 acc[MF][NF][4];
-#pragma unroll
-  for (int mf = 0; mf < MF; ++mf)
-#pragma unroll
-    for (int nf = 0; nf < NF; ++nf)
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[mf][nf][t][i] = 0.f;
-
-  auto stage = [&](int cin0, float* sbase) {
-    for (int p = wave; p < WPIECES; p += 4) {
-      const int row0 = p * RPP;
-      const int tap = row0 / CC, c0 = row0 % CC;
-      const unsigned soff = (unsigned)((((long)tap * a.CinP + cin0 + c0) * a.CoutP + cout0) * 4);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, LDS_PTR(sbase + p * 256), 16, wvoff, soff, 0, 0);
-    }
-    float* xs = sbase + W_FLOATS;
-    if (XV4) {
-      const unsigned soff = (unsigned)cin0 * (unsigned)a.x_cstride * 4u;
-#pragma unroll
-      for (int jj = 0; jj < PV; ++jj) {
-        const int j = wave + 4 * jj;
-        if (j * 256 < CC * plane && xvc[jj] < CC) {   // exec-masked: lanes past the image write nothing
-          const unsigned vo = cin0 + xvc[jj] < a.Cin ? xvoff[jj] : OOB;
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, LDS_PTR(xs + j * 256), 16, vo, soff, 0, 0);
-        }
-      }
-    } else
-#pragma unroll
-    for (int ci = 0; ci < CC / 4; ++ci) {
-      const int c = ci * 4 + wave;
-      const int cin = cin0 + c;
-      if (cin < a.Cin) {
-        const unsigned soff = (unsigned)cin * (unsigned)a.x_cstride * 4u;
-#pragma unroll
-        for (int j = 0; j < PCH; ++j)
-          if (j * 64 < plane)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, LDS_PTR(xs + c * planeS + j * 64), 4,
-                                                     goff[j], soff, 0, 0);
-      } else {
-#pragma unroll
-        for (int j = 0; j < PCH; ++j)
-          if (j * 64 < plane) xs[c * planeS + j * 64 + lane] = 0.f;
-      }
-    }
-  };
-
-  const int nchunks = a.nchunks;
-  stage(0, smem);
-  for (int ch = 0; ch < nchunks; ++ch) {
-    const float* cur = smem + (ch & 1) * stage_floats;
-    __builtin_amdgcn_s_waitcnt(0x0f70);
-    __syncthreads();
-    if (ch + 1 < nchunks) stage((ch + 1) * CC, smem + ((ch + 1) & 1) * stage_floats);
-
-    constexpr int QS = CC / 2;
-    // step q: channel pair (2q, 2q+1); operands of step q+1 are fetched under the MFMAs of q
-    auto fetch = [&](int q, float (&av)[MF][4], float (&dv)[NF][4]) {
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int mf = 0; mf < MF; ++mf) av[mf][t] = cur[abase + (t * CC + 2 * q) * BM + mf * 32];
-#pragma unroll
-      for (int nf = 0; nf < NF; ++nf)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) dv[nf][k] = cur[lanebase[nf] + k * fstride + 2 * q * planeS];
-    };
-    float av[2][MF][4], dv[2][NF][4];
-    fetch(0, av[0], dv[0]);
-#pragma unroll
-    for (int q = 0; q < QS; ++q) {
-      if (q + 1 < QS) fetch(q + 1, av[(q + 1) & 1], dv[(q + 1) & 1]);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int nf = 0; nf < NF; ++nf) {
-        const float d0 = dv[q & 1][nf][0], d1 = dv[q & 1][nf][1], d2 = dv[q & 1][nf][2],
-                    d3 = dv[q & 1][nf][3];
-        const float D[4] = {d0 - d2, d1 + d2, d2 - d1, d1 - d3};
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int mf = 0; mf < MF; ++mf)
-            acc[mf][nf][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q & 1][mf][t], D[t],
-                                                                  acc[mf][nf][t], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-
-  // ---- epilogue: y[2p] = m0+m1+m2, y[2p+1] = m1-m2-m3 ---------------------------------------
-  unsigned yvoff[NF];
-  bool pvalid[NF], p2valid[NF];
-  const unsigned half_rows = (unsigned)half * 4u * (unsigned)a.y_cstride * 4u;
-  const unsigned frame_bytes = (unsigned)(a.yHf * a.yWf) * 4u;
-  const int To_full = a.yst;     // launcher passes the un-paired frame count here
-#pragma unroll
-  for (int nf = 0; nf < NF; ++nf) {
-    const int p = wn * (BNP / WN) + nf * 32 + l31;
-    const int tw = p & ((1 << a.lTW) - 1);
-    const int th = (p >> a.lTW) & ((1 << a.lTH) - 1);
-    const int tt = (p >> (a.lTW + a.lTH)) & ((1 << a.lTT) - 1);
-    const int tn = p >> (a.lTW + a.lTH + a.lTT);
-    const int n = n0 + tn, tp = ot0 + tt, oh = oh0 + th, ow = ow0 + tw;
-    pvalid[nf] = n < a.N && 2 * tp < To_full && oh < a.Ho && ow < a.Wo;
-    p2valid[nf] = pvalid[nf] && 2 * tp + 1 < To_full;
-    const long e = (long)tn * a.y_nstride + ((long)(2 * tp) * a.yHf + oh) * a.yWf + ow;
-    yvoff[nf] = pvalid[nf] ? (unsigned)(e * 4) + half_rows : OOB;
-  }
-
-  const bool want_stats = a.stats != nullptr;
-  float* red = smem;
-  if (want_stats) __syncthreads();
-
-  auto emit = [&](auto acc_tag, auto fancy_tag) {       // FANCY: see conv_igemm_body
-    constexpr bool ACCUM = decltype(acc_tag)::value;
-    constexpr bool FANCY = decltype(fancy_tag)::value;
-#pragma unroll
-    for (int mf = 0; mf < MF; ++mf) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int rowu = wm * (BM / WM) + mf * 32 + (i & 3) + 8 * (i >> 2);
-        const int ml = rowu + 4 * half;
-        const int co = cout0 + ml;
-        const bool cok = co < a.Cout;
-        const unsigned soff = (unsigned)(cout0 + rowu) * (unsigned)a.y_cstride * 4u;
-        float s = 0.f, ss = 0.f;
-        float bia = 0.f, sc = 1.f, sf = 0.f;
-        if (FANCY) {
-          if (a.bias && cok) bia = a.bias[co];
-          if (a.ep_scale && cok) { sc = a.ep_scale[co]; sf = a.ep_shift[co]; }
-        }
-#pragma unroll
-        for (int nf = 0; nf < NF; ++nf) {
-          const float m0 = acc[mf][nf][0][i], m1 = acc[mf][nf][1][i], m2 = acc[mf][nf][2][i],
-                      m3 = acc[mf][nf][3][i];
-          float v0 = (m0 + m1) + m2, v1 = (m1 - m2) - m3;
-          const unsigned vo0 = cok ? yvoff[nf] : OOB;
-          const unsigned vo1 = (cok && p2valid[nf]) ? yvoff[nf] + frame_bytes : OOB;
-          if (ACCUM) {
-            v0 += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ry, vo0, soff, 0));
-            v1 += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ry, vo1, soff, 0));
-          }
-          const float u0 = pvalid[nf] ? v0 : 0.f, u1 = p2valid[nf] ? v1 : 0.f;
-          s += u0 + u1; ss += u0 * u0 + u1 * u1;
-          if (FANCY) {
-            v0 = (v0 + bia) * sc + sf;
-            v1 = (v1 + bia) * sc + sf;
-            if (a.relu) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }
-          }
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v0), ry, vo0, soff, 0);
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v1), ry, vo1, soff, 0);
-        }
-        if (want_stats) {
-          s = row16_sum(s);
-          ss = row16_sum(ss);
-          if ((lane & 15) == 0) {
-            const int slot = wn * 2 + (l31 >> 4);
-            red[(slot * BM + ml) * 2 + 0] = s;
-            red[(slot * BM + ml) * 2 + 1] = ss;
-          }
-        }
-      }
-    }
-  };
-  // see conv_igemm_body: the destination is the dz of a BatchNorm(+ReLU) unit, its backward sums are
-  // formed here from the two frames in registers
-  auto emit_bwd = [&]() {
-    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(a.bwd_y + (long)n0 * a.y_nstride), 0, BUF_RANGE, 0x00020000);
-#pragma unroll
-    for (int mf = 0; mf < MF; ++mf) {
-#pragma unroll
-      for (int i0 = 0; i0 < 16; i0 += 4) {
-        float yv[4][NF][2];
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii) {
-          const int i = i0 + ii;
-          const int rowu = wm * (BM / WM) + mf * 32 + (i & 3) + 8 * (i >> 2);
-          const bool cok = cout0 + rowu + 4 * half < a.Cout;
-          const unsigned soff = (unsigned)(cout0 + rowu) * (unsigned)a.y_cstride * 4u;
-#pragma unroll
-          for (int nf = 0; nf < NF; ++nf) {
-            const unsigned vo0 = cok ? yvoff[nf] : OOB;
-            const unsigned vo1 = (cok && p2valid[nf]) ? yvoff[nf] + frame_bytes : OOB;
-            yv[ii][nf][0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rb, vo0, soff, 0));
-            yv[ii][nf][1] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rb, vo1, soff, 0));
-          }
-        }
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii) {
-          const int i = i0 + ii;
-          const int rowu = wm * (BM / WM) + mf * 32 + (i & 3) + 8 * (i >> 2);
-          const int ml = rowu + 4 * half;
-          const int co = cout0 + ml;
-          const bool cok = co < a.Cout;
-          const unsigned soff = (unsigned)(cout0 + rowu) * (unsigned)a.y_cstride * 4u;
-          float bsc = 0.f, bsf = 0.f, mu = 0.f, is = 0.f;
-          if (cok) { bsc = a.bwd_scale[co]; bsf = a.bwd_shift[co]; mu = a.bwd_mean[co]; is = a.bwd_invstd[co]; }
-          float s = 0.f, ss = 0.f;
-#pragma unroll
-          for (int nf = 0; nf < NF; ++nf) {
-            const float m0 = acc[mf][nf][0][i], m1 = acc[mf][nf][1][i], m2 = acc[mf][nf][2][i],
-                        m3 = acc[mf][nf][3][i];
-            const float v0 = (m0 + m1) + m2, v1 = (m1 - m2) - m3;
-            const unsigned vo0 = cok ? yvoff[nf] : OOB;
-            const unsigned vo1 = (cok && p2valid[nf]) ? yvoff[nf] + frame_bytes : OOB;
-            const float u0 = yv[ii][nf][0], u1 = yv[ii][nf][1];
-            const bool on0 = pvalid[nf] && (!a.bwd_relu || fmaf(u0, bsc, bsf) > 0.f);
-            const bool on1 = p2valid[nf] && (!a.bwd_relu || fmaf(u1, bsc, bsf) > 0.f);
-            const float g0 = on0 ? v0 : 0.f, g1 = on1 ? v1 : 0.f;
-            s += g0 + g1;
-            ss += g0 * ((u0 - mu) * is) + g1 * ((u1 - mu) * is);
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v0), ry, vo0, soff, 0);
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v1), ry, vo1, soff, 0);
-          }
-          s = row16_sum(s);
-          ss = row16_sum(ss);
-          if ((lane & 15) == 0) {
-            const int slot = wn * 2 + (l31 >> 4);
-            red[(slot * BM + ml) * 2 + 0] = s;
-            red[(slot * BM + ml) * 2 + 1] = ss;
-          }
-        }
-      }
-    }
-  };
-  const bool fancy = a.bias || a.ep_scale || a.relu;
-  if (a.bwd_y) emit_bwd();
-  else if (fancy) { if (a.accumulate) emit(std::true_type{}, std::true_type{}); else emit(std::false_type{}, std::true_type{}); }
-  else if (a.accumulate) emit(std::true_type{}, std::false_type{});
-  else emit(std::false_type{}, std::false_type{});
-
-  if (want_stats) {
-    __syncthreads();
-    if (tid < BM) {
-      const int co = cout0 + tid;
-      if (co < a.Cout) {
-        float s = 0.f, ss = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          s += red[(k * BM + tid) * 2];
-          ss += red[(k * BM + tid) * 2 + 1];
-        }
-        a.stats[(long)co * a.ntiles + ntile] = s;
-        a.stats[((long)a.Cout + co) * a.ntiles + ntile] = ss;
-      }
-    }
-  }
-}
-
-template <int CC, int BM, int BNP, int PCH, bool XV4, int OCC = 1>
-__global__ void __launch_bounds__(256, OCC)
-conv_wino_t_kernel(const ConvArgs a) {
-  conv_wino_t_body<CC, BM, BNP, PCH, XV4>(a, (int)blockIdx.x, (int)gridDim.x);
-}
-
-// two problems in one launch, see conv_igemm_pair_kernel
-template <int CC, int BM, int BNP, int PCH, bool XV4, int OCC = 1>
-__global__ void __launch_bounds__(256, OCC)
-conv_wino_t_pair_kernel(const ConvArgs a0, const ConvArgs a1, const int nb0) {
-  if ((int)blockIdx.x < nb0) conv_wino_t_body<CC, BM, BNP, PCH, XV4>(a0, (int)blockIdx.x, nb0);
-  else conv_wino_t_body<CC, BM, BNP, PCH, XV4>(a1, (int)blockIdx.x - nb0, (int)gridDim.x - nb0);
-}
-
-// ------------------------------------------------------------------------------------
-// The temporal Winograd family: one kernel body, conv_wino_tf_body, over three FORMS.  Same structure as
-// conv_wino_t_body: a (TAPS,1,1) stencil with temporal stride STEP over output "positions" (groups of FO output
-// frames), TAPS accumulator sets per 32x32 block, the epilogue emits FO frames per position.  A form gives
-//     TAPS           channel contractions (accumulator sets) = window frames read per lane
-//     FO             output frames per position
-//     STEP, ORG      window frames per position and the window origin: frame  position * STEP - ORG
-//     input()        d[TAPS] window frames -> D[TAPS] transformed operands
-//     output()       element i of the m[TAPS] contractions -> v[FO] output frames
-//     LATTICE        the destination is a lattice along T (a.yst, a.yot) and the frame count arrives in a.To_full;
-//                    without it the frame count arrives in a.yst and the frame pitch is 1
-//     PAIR           a two-problem kernel exists (coclr_conv3d_fwd_multi)
-// The arithmetic of the transforms (fmaf nesting, parentheses) and the order in which the epilogue adds frames
-// into the statistics are part of the result: outputs and BatchNorm sums are held bit for bit.  output() reads the
-// accumulators in place for the same reason: staged through a scalar array the epilogue vectorises differently,
-// and which of its multiply-adds get fused changes with it.
+};
 
 // Temporal (3,1,1) stride-1 convolutions through Winograd F(4,3) along T (coclr_conv_desc.algo = 2).
 //
@@ -955,7 +602,7 @@ conv_wino_t_pair_kernel(const ConvArgs a0, const ConvArgs a1, const int nb0) {
 // 2x fewer MFMAs than the direct form, 1.33x fewer than F(2,3).
 struct WinoF43 {
   static constexpr int TAPS = 6, FO = 4, STEP = 4, ORG = 1;
-  static constexpr bool LATTICE = true, PAIR = true;
+  static constexpr bool LATTICE = true, PAIR = true, POS_SUMS = false, BWD_SUMS = false;
   static __device__ __forceinline__ void input(const float (&d)[TAPS], float (&D)[TAPS]) {
     const float d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3], d4 = d[4], d5 = d[5];
     const float t1 = fmaf(-4.f, d2, d4), t2 = fmaf(-4.f, d1, d3);
@@ -980,7 +627,7 @@ struct WinoF43 {
 // Writes through the destination lattice along T like WinoF43.
 struct WinoF24 {
   static constexpr int TAPS = 5, FO = 2, STEP = 2, ORG = 1;
-  static constexpr bool LATTICE = true, PAIR = false;
+  static constexpr bool LATTICE = true, PAIR = false, POS_SUMS = false, BWD_SUMS = false;
   static __device__ __forceinline__ void input(const float (&d)[TAPS], float (&D)[TAPS]) {
     const float o0 = d[0], o1 = d[1], o2 = d[2], o3 = d[3], o4 = d[4];
     const float oa = o3 - o2, o31 = o3 - o1;
@@ -1012,7 +659,7 @@ struct WinoF24 {
 // (144 registers: two workgroups per CU).  The only form with the optional affine(+ReLU) on load (INAFF).
 struct StemPoly7 {
   static constexpr int TAPS = 9, FO = 2, STEP = 4, ORG = 3;
-  static constexpr bool LATTICE = false, PAIR = false;
+  static constexpr bool LATTICE = false, PAIR = false, POS_SUMS = false, BWD_SUMS = false;
   static __device__ __forceinline__ void input(const float (&r_)[TAPS], float (&D)[TAPS]) {
     // odd taps (w1, w3, w5) on frames r1, r3, r5, r7: F(2,3); even taps (w0, w2, w4, w6) on r0, r2, r4, r6, r8: F(2,4)
     const float e0 = r_[1], e1 = r_[3], e2 = r_[5], e3 = r_[7];
@@ -1099,8 +746,11 @@ __device__ __forceinline__ void conv_wino_tf_body(const ConvArgs& a, int bid, co
   }
   const unsigned wvoff = (unsigned)((((lane * 4) / BM) * a.CoutP + (lane * 4) % BM) * 4);
 
-  // XV4: 16-byte DMA of the halo-free window, 1 KiB pieces across channel rows (see conv_wino_t_body)
-  constexpr int PV = (CC * PCH * 64 / 256 + 3) / 4;
+  // XV4: the window of a temporal stencil has no halo along the flattened (H,W) axis, so with
+  // everything 16-byte aligned it can be staged by 16-byte DMA.  The LDS image [c][plane] is
+  // then filled in 1 KiB pieces that run across channel boundaries: piece j, lane L holds
+  // floats 256j + 4L .. +3.  Wave w owns pieces w, w+4, ...
+  constexpr int PV = (CC * PCH * 64 / 256 + 3) / 4;      // pieces per wave (upper bound)
   unsigned xvoff[PV];
   int xvc[PV];
   if (XV4) {
@@ -1314,6 +964,25 @@ __device__ __forceinline__ void conv_wino_tf_body(const ConvArgs& a, int bid, co
         for (int nf = 0; nf < NF; ++nf) {
           float v[FO];
           Form::output(acc[mf][nf], i, v);
+          if constexpr (Form::POS_SUMS) {                // the position's two frames together
+            static_assert(FO == 2, "POS_SUMS is written for two frames per position");
+            const bool v0ok = nvalid[nf] > 0, v1ok = nvalid[nf] > 1;
+            const unsigned vo0 = cok ? yvoff[nf] : OOB;
+            const unsigned vo1 = (cok && v1ok) ? yvoff[nf] + frame_bytes : OOB;
+            if (ACCUM) {
+              v[0] += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ry, vo0, soff, 0));
+              v[1] += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ry, vo1, soff, 0));
+            }
+            const float u0 = v0ok ? v[0] : 0.f, u1 = v1ok ? v[1] : 0.f;
+            s += u0 + u1; ss += u0 * u0 + u1 * u1;
+            if (FANCY) {
+              v[0] = (v[0] + bia) * sc + sf;
+              v[1] = (v[1] + bia) * sc + sf;
+              if (a.relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); }
+            }
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[0]), ry, vo0, soff, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[1]), ry, vo1, soff, 0);
+          } else
 #pragma unroll
           for (int f = 0; f < FO; ++f) {                 // frame by frame: the order of the sums into s / ss
             const bool fv = f < nvalid[nf];
@@ -1340,27 +1009,78 @@ __device__ __forceinline__ void conv_wino_tf_body(const ConvArgs& a, int bid, co
       }
     }
   };
+  // BWD_SUMS, see conv_igemm_body: the destination is the dz of a BatchNorm(+ReLU) unit, its backward sums are
+  // formed here from the two frames in registers
+  auto emit_bwd = [&]() {
+    if constexpr (Form::BWD_SUMS) {
+      static_assert(FO == 2, "the backward-sums epilogue is written for two frames per position");
+      const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
+          (void*)(a.bwd_y + (long)n0 * a.y_nstride), 0, BUF_RANGE, 0x00020000);
+#pragma unroll
+      for (int mf = 0; mf < MF; ++mf) {
+#pragma unroll
+        for (int i0 = 0; i0 < 16; i0 += 4) {
+          float yv[4][NF][2];
+#pragma unroll
+          for (int ii = 0; ii < 4; ++ii) {
+            const int i = i0 + ii;
+            const int rowu = wm * (BM / WM) + mf * 32 + (i & 3) + 8 * (i >> 2);
+            const bool cok = cout0 + rowu + 4 * half < a.Cout;
+            const unsigned soff = (unsigned)(cout0 + rowu) * (unsigned)a.y_cstride * 4u;
+#pragma unroll
+            for (int nf = 0; nf < NF; ++nf) {
+              const unsigned vo0 = cok ? yvoff[nf] : OOB;
+              const unsigned vo1 = (cok && nvalid[nf] > 1) ? yvoff[nf] + frame_bytes : OOB;
+              yv[ii][nf][0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rb, vo0, soff, 0));
+              yv[ii][nf][1] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rb, vo1, soff, 0));
+            }
+          }
+#pragma unroll
+          for (int ii = 0; ii < 4; ++ii) {
+            const int i = i0 + ii;
+            const int rowu = wm * (BM / WM) + mf * 32 + (i & 3) + 8 * (i >> 2);
+            const int ml = rowu + 4 * half;
+            const int co = cout0 + ml;
+            const bool cok = co < a.Cout;
+            const unsigned soff = (unsigned)(cout0 + rowu) * (unsigned)a.y_cstride * 4u;
+            float bsc = 0.f, bsf = 0.f, mu = 0.f, is = 0.f;
+            if (cok) { bsc = a.bwd_scale[co]; bsf = a.bwd_shift[co]; mu = a.bwd_mean[co]; is = a.bwd_invstd[co]; }
+            float s = 0.f, ss = 0.f;
+#pragma unroll
+            for (int nf = 0; nf < NF; ++nf) {
+              float v[FO];
+              Form::output(acc[mf][nf], i, v);
+              const bool v0ok = nvalid[nf] > 0, v1ok = nvalid[nf] > 1;
+              const unsigned vo0 = cok ? yvoff[nf] : OOB;
+              const unsigned vo1 = (cok && v1ok) ? yvoff[nf] + frame_bytes : OOB;
+              const float u0 = yv[ii][nf][0], u1 = yv[ii][nf][1];
+              const bool on0 = v0ok && (!a.bwd_relu || fmaf(u0, bsc, bsf) > 0.f);
+              const bool on1 = v1ok && (!a.bwd_relu || fmaf(u1, bsc, bsf) > 0.f);
+              const float g0 = on0 ? v[0] : 0.f, g1 = on1 ? v[1] : 0.f;
+              s += g0 + g1;
+              ss += g0 * ((u0 - mu) * is) + g1 * ((u1 - mu) * is);
+              __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[0]), ry, vo0, soff, 0);
+              __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[1]), ry, vo1, soff, 0);
+            }
+            s = row16_sum(s);
+            ss = row16_sum(ss);
+            if ((lane & 15) == 0) {
+              const int slot = wn * 2 + (l31 >> 4);
+              red[(slot * BM + ml) * 2 + 0] = s;
+              red[(slot * BM + ml) * 2 + 1] = ss;
+            }
+          }
+        }
+      }
+    }
+  };
   const bool fancy = a.bias || a.ep_scale || a.relu;
-  if (fancy) { if (a.accumulate) emit(std::true_type{}, std::true_type{}); else emit(std::false_type{}, std::true_type{}); }
+  if (Form::BWD_SUMS && a.bwd_y) emit_bwd();
+  else if (fancy) { if (a.accumulate) emit(std::true_type{}, std::true_type{}); else emit(std::false_type{}, std::true_type{}); }
   else if (a.accumulate) emit(std::true_type{}, std::false_type{});
   else emit(std::false_type{}, std::false_type{});
 
-  if (want_stats) {
-    __syncthreads();
-    if (tid < BM) {
-      const int co = cout0 + tid;
-      if (co < a.Cout) {
-        float s = 0.f, ss = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          s += red[(k * BM + tid) * 2];
-          ss += red[(k * BM + tid) * 2 + 1];
-        }
-        a.stats[(long)co * a.ntiles + ntile] = s;
-        a.stats[((long)a.Cout + co) * a.ntiles + ntile] = ss;
-      }
-    }
-  }
+  if (want_stats) fold_tile_stats<BM>(a, red, tid, cout0, ntile);
 }
 
 template <typename Form, int CC, int BM, int BNQ, int PCH, bool XV4, int OCC = 1, bool INAFF = false>
@@ -2782,10 +2502,12 @@ conv_igemm_133_mixed_kernel(const ConvArgs a0, const ConvArgs a1, const int nb0)
 // A row is one kernel instantiation: the numbers coclr_conv3d_fwd_plan reports about it and the functions that
 // launch it.  Rows are only ever built by the *_row<...>() templates below, from the SAME template arguments for
 // both, so what is reported is what runs.
-enum { FF_IGEMM = 0, FF_WINO_T = 1, FF_WINO_TF = 2, FF_WINO_HW = 3, FF_WINO_HW8 = 4, FF_STEM = 5 };
+// (1 is the number coclr_conv3d_fwd_plan reports for F(2,3), which was a family of its own before it became a
+// form of FF_WINO_TF)
+enum { FF_IGEMM = 0, FF_WINO_TF = 2, FF_WINO_HW = 3, FF_WINO_HW8 = 4, FF_STEM = 5 };
 struct KernelRow {
   int family;      // FF_*
-  int form;        // FF_WINO_TF: matrices of the form (6: F(4,3), 5: F(2,4), 9: polyphase stem); 0 otherwise
+  int form;        // FF_WINO_TF: matrices of the form (4: F(2,3), 6: F(4,3), 5: F(2,4), 9: polyphase stem); 0 otherwise
   int KT, KH, KW, CC, BM, BN, PCH, OCC;   // template numbers (0: the kernel has none)
   bool XV4, XG, X16, INAFF;
   int threads;
@@ -2804,16 +2526,9 @@ constexpr KernelRow igemm_row() {
           &launch_single<conv_igemm_kernel<KT, KH, KW, CC, BM, BN, PCH, XV4, XG>>, pair};
 }
 
-// (the pair kernels of the 4-byte forms of F(2,3) and F(4,3) are built with their rows but never selected:
-// select_forward pairs these families only under 16-byte staging)
-template <int CC, int BM, int BNP, int PCH, bool XV4, int OCC = 1>
-constexpr KernelRow wino_t_row() {
-  return {FF_WINO_T, 0, 3, 1, 1, CC, BM, BNP, PCH, OCC, XV4, false, false, false, 256,
-          &launch_single<conv_wino_t_kernel<CC, BM, BNP, PCH, XV4, OCC>>,
-          &launch_pair<conv_wino_t_pair_kernel<CC, BM, BNP, PCH, XV4, OCC>>};
-}
-
 // the temporal Winograd family (conv_wino_tf_body) on a KT-tap stencil: Form::TAPS weight matrices per stage
+// (the pair kernels of the 4-byte forms of F(2,3) and F(4,3) are built with their rows but never selected:
+// select_forward pairs this family only under 16-byte staging)
 template <typename Form, int KT, int CC, int BM, int BNQ, int PCH, bool XV4, int OCC, bool INAFF = false>
 constexpr KernelRow wino_tf_row() {
   PairFn pair = nullptr;
@@ -2908,8 +2623,8 @@ constexpr FwdTableRow kFwdTable[] = {
     {V_POLY7, ALT_16B, wino_tf_row<StemPoly7, 7, 8, 64, 64, 6, true, 2>()},
     {V_POLY7, ALT_INAFF + ALT_4B, wino_tf_row<StemPoly7, 7, 8, 64, 64, 6, false, 2, true>()},
     {V_POLY7, ALT_INAFF + ALT_16B, wino_tf_row<StemPoly7, 7, 8, 64, 64, 6, true, 2, true>()},
-    {V_F23, ALT_4B, wino_t_row<16, 64, 64, 4, false>()},
-    {V_F23, ALT_16B, wino_t_row<8, 64, 64, 4, true, 4>()},
+    {V_F23, ALT_4B, wino_tf_row<WinoF23, 3, 16, 64, 64, 4, false, 1>()},
+    {V_F23, ALT_16B, wino_tf_row<WinoF23, 3, 8, 64, 64, 4, true, 4>()},
     {V_F43, ALT_4B, wino_tf_row<WinoF43, 3, 8, 64, 64, 6, false, 3>()},
     {V_F43, ALT_16B, wino_tf_row<WinoF43, 3, 8, 64, 64, 6, true, 3>()},
     {V_F24, ALT_4B, wino_tf_row<WinoF24, 4, 8, 64, 64, 4, false, 3>()},
@@ -3234,7 +2949,7 @@ struct FwdSel {
   long lds, grid;
 };
 
-// stages of the chunked kernels (direct, F(2,3), the temporal Winograd family): `taps` weight matrices and a
+// stages of the chunked kernels (direct, the temporal Winograd family): `taps` weight matrices and a
 // window per chunk, double buffered when there is more than one chunk, `extra` bytes behind them
 inline int sel_staged(FwdSel& s, const ConvPlan& p, int taps, size_t extra) {
   const KernelRow& k = s.k;
@@ -3373,10 +3088,8 @@ int select_forward(const coclr_conv_desc* d, const ConvPlan& p, int variant, con
       case FF_IGEMM:
         s.pairable = k->pair != nullptr;
         return sel_staged(s, p, k->KT * k->KH * k->KW, 0);
-      case FF_WINO_T:
-        s.pairable = k->XV4;
-        return sel_staged(s, p, 4, 0);
       case FF_WINO_TF:
+        // (F(2,3) is dense only: its planner refuses a lattice)
         s.pairable = k->pair != nullptr && k->XV4 && !s.lattice;
         // the affine table of INAFF sits behind the stages
         return sel_staged(s, p, k->form, k->INAFF ? (size_t)2 * CinP * sizeof(float) : 0);
@@ -3447,18 +3160,14 @@ void apply(const FwdSel& s, const coclr_conv_desc* d, const ConvPlan& p, ConvArg
     a.inv_ww = 1.0f / (float)(s.WW / 4);
   }
   switch (s.k.family) {
-    case FF_WINO_T:
-      // a.To = frame pairs; the kernel finds the frame count in yst and the plane pitch in yHf/yWf
-      a.yst = d->To; a.yHf = p.Ho; a.yWf = p.Wo;
-      a.y_cstride = d->To * p.Ho * p.Wo;
-      a.st = 1;
-      break;
     case FF_WINO_TF:
-      if (s.k.form == StemPoly7::TAPS) {
-        // a.To = output pairs; the kernel finds the frame count in yst and the plane pitch in yHf/yWf
+      if (s.k.form == WinoF23::TAPS || s.k.form == StemPoly7::TAPS) {
+        // the forms without a lattice: a.To = frame / output pairs; the kernel finds the frame count in yst and the
+        // plane pitch in yHf/yWf
         a.yst = d->To; a.yHf = p.Ho; a.yWf = p.Wo;
         a.y_cstride = d->To * p.Ho * p.Wo;
-        a.st = 1; a.pt = 3;
+        a.st = 1;
+        if (s.k.form == StemPoly7::TAPS) a.pt = 3;
         break;
       }
       // a.To = frame quads (F(4,3)) / pairs (F(2,4)); the kernel finds the frame count in To_full and, when the
@@ -3572,7 +3281,9 @@ extern "C" int coclr_conv3d_fwd_plan(const coclr_conv_desc* d, int flags, int32_
   rc = select_forward(d, p, variant, q, &s);
   if (rc) return rc;
   const KernelRow& k = s.k;
-  const int32_t v[40] = {variant, k.family, k.form, k.KT, k.KH, k.KW, k.CC, k.BM, k.BN, k.PCH,
+  // F(2,3) keeps the labels it was first reported under: family 1, form 0
+  const bool f23 = k.family == FF_WINO_TF && k.form == WinoF23::TAPS;
+  const int32_t v[40] = {variant, f23 ? 1 : k.family, f23 ? 0 : k.form, k.KT, k.KH, k.KW, k.CC, k.BM, k.BN, k.PCH,
                          k.OCC, k.XV4, k.XG, k.X16, k.INAFF, s.lattice, s.pairable, p.lTW, p.lTH, p.lTT,
                          p.lTN, p.WT, p.WH, s.WW, s.plane, p.ntiles, s.mtiles, s.nchunks, s.planeS, (int32_t)s.lds,
                          (int32_t)s.grid, k.threads, s.pairable && q.slot, p.nboxes, p.nbw, p.nbh, p.nbt, p.nbn,

@@ -178,7 +178,8 @@ int coclr_conv3d_bwd_sums_ok(const coclr_conv_desc* d, int* ok);
  *        16 the call sits in a pair slot of coclr_conv3d_fwd_multi, 32 backward sums (bwd_y) are asked for.
  * out:
  *   [0]  planner variant
- *   [1]  kernel family: 0 conv_igemm_kernel, 1 conv_wino_t_kernel (F(2,3)), 2 conv_wino_tf_kernel,
+ *   [1]  kernel family: 0 conv_igemm_kernel, 1 conv_wino_tf_kernel<WinoF23> (F(2,3); reported as a family of
+ *        its own, as when it had a kernel of its own), 2 conv_wino_tf_kernel in its other forms,
  *        3 conv_wino_hw_kernel, 4 conv_wino_hw8_kernel, 5 conv_stem_kernel
  *   [2]  family 2: matrices of the form (6: F(4,3), 5: F(2,4), 9: polyphase stem); 0 otherwise
  *   [3..10]  template numbers KT KH KW CC BM BN PCH OCC (0: the kernel has none)
